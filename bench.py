@@ -22,14 +22,21 @@ gather milliseconds.
 Precision: `value` is measured on the MIXED-precision device path (TAKE_PRECISION_MIXED): every path's first three
 rounds — camera ray and the next two bounces, where a flipped hit / miss decision costs the most radiance — run in the
 reference's arithmetic (Real = double, src/take.h:27) on the f64 scene, the surviving paths continue on f32 records and
-the f32 scene.  The line carries its own proof: at N = 1 the same workload is also timed on the pure f64 path
-(`reference_precision`: images at rounding level of the pinned oracle, tests/test_gpu_parity.py) and on the pure f32
-path (`production_f32`), and `parity` reports the per-pixel RMSE of the mixed image and of the f32 image against the
-f64 image of this very workload at matched seeds (north-star tolerance: 1e-3; f32 alone sits at ~1.8e-3 on the 1M
-soup, the mixed path at ~0.6e-3).  `--precision f64` / `f32` make one of the pure paths the headline.
+the f32 scene.  `--precision f64` / `f32` make one of the pure paths the headline.
 
-One JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel
-(closest-hit traversal, measured with HIP events inside the timed region) and `cpu_baseline` (rank 0, N = 1 only).
+A plain run does only what the headline needs: set-up, `--warmup` untimed steps, `--steps` timed steps, one JSON line on
+rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...).
+`--full` adds everything else the benchmark measures: per-kernel milliseconds (HIP events in the timed region),
+`roofline` for the dominant kernel (closest-hit traversal; needs a counting pass of its own), and at N = 1 the line's
+own proof — the same workload timed on the pure f64 path (`reference_precision`: images at rounding level of the pinned
+oracle, tests/test_gpu_parity.py) and on the pure f32 path (`production_f32`), `parity` = the per-pixel RMSE of the mixed
+image and of the f32 image against the f64 image of this very workload at matched seeds (north-star tolerance: 1e-3;
+f32 alone sits at ~1.8e-3 on the 1M soup, the mixed path at ~0.6e-3) — and `cpu_baseline` (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes, after the timed steps, the image the timed path returned in its last step (rank 0, the
+gathered image when N > 1) as DIR/image.npy in the path's own precision (float64 for mixed / f64, float32 for f32).  An
+image above 64 MB is written as a fixed seeded sample of its pixels instead (DIR/image_sample.npy, see dump_outputs).
+The scenes are procedural and seeded and the render seed is fixed: the same arguments give the same inputs every run.
 """
 import argparse
 import json
@@ -46,6 +53,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 STATE_BYTES_PER_RAY = 4 + 6 * 4 + 4 * 4  # queue word + origin/direction read + hit record written (f32)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: at most 64 MB in all
 
 
 def parse_args():
@@ -82,11 +90,19 @@ def parse_args():
                          "(default: meets the RMSE tolerance, see `parity`); f64 = the reference's Real throughout; f32 = the "
                          "production arithmetic throughout")
     ap.add_argument("--exact-bounces", type=int, default=0, help="mixed precision: rounds computed in f64 (0 = the library's default, 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times, `roofline` (own counting pass), "
+                         "the other precisions' legs with `parity`, `cpu_baseline`")
     ap.add_argument("--alt-steps", "--f64-steps", dest="alt_steps", type=int, default=2,
-                    help="timed steps of the same workload on each of the OTHER precisions' device paths, N = 1 only; 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", default="640x360x1", help="WxHxSPP of the CPU-baseline sample")
+                    help="with --full: timed steps of the same workload on each of the OTHER precisions' device paths, N = 1 "
+                         "only; 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--cpu-sample", default="640x360x1", help="with --full: WxHxSPP of the CPU-baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image of the last one to DIR/image.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     dw, dh, ds = (4096, 4096, 1024) if args.config == 3 else (1920, 1080, 256)
     args.width = dw if args.width is None else args.width
     args.height = dh if args.height is None else args.height
@@ -212,10 +228,24 @@ def roofline_of(args, precision, bytes_per_ray, acc, node_bytes):
             "rays_per_launch": rays_in / n_launch}
 
 
+def dump_outputs(directory, image):
+    """--dump-outputs: `image` (numpy, H x W x 3, the path's own float dtype) as DIR/image.npy; above DUMP_MAX_BYTES
+    (e.g. --config 3's 4096x4096 f64 image) a fixed sample of its pixels instead — DUMP_MAX_BYTES worth of pixels drawn
+    without replacement by default_rng(0) and kept in raster order — as DIR/image_sample.npy (pixels x 3)."""
+    os.makedirs(directory, exist_ok=True)
+    if image.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(directory, "image.npy"), image)
+        return
+    px = image.reshape(-1, image.shape[-1])
+    keep = np.sort(np.random.default_rng(0).choice(len(px), size=DUMP_MAX_BYTES // px[0].nbytes, replace=False))
+    np.save(os.path.join(directory, "image_sample.npy"), px[keep])
+
+
 def run_leg(args, sd, precision, steps, warmup, rank, world, backend, spp_total, is_main):
     """Build the scene at `precision`, warm up, time `steps` steps (render + gather when N > 1).  Returns a dict:
-    value, elapsed, per-kernel ms, the last image (rank 0), roofline inputs.  The timed region is bracketed by a
-    barrier + synchronize on both sides and the maximum over the ranks is taken."""
+    value, elapsed, the last image (rank 0: on the host for --dump-outputs, as float64 on the device for `parity`) and,
+    with --full, per-kernel ms and roofline inputs.  The timed region is bracketed by a barrier + synchronize on both
+    sides and the maximum over the ranks is taken."""
     import torch
     import torch.distributed as dist
 
@@ -240,14 +270,17 @@ def run_leg(args, sd, precision, steps, warmup, rank, world, backend, spp_total,
         scene.render_device(out.data_ptr(), spp, depth, seed=seed, strip_first=rank, strip_stride=world,
                             samples_per_batch=spb, stream=stream)
 
-    # algorithmic bytes per closest-hit ray: one counting pass (instrumented kernel, never timed), 1 spp
-    scene.set_instrumentation(timing=False, counting=True)
-    render(1, args.max_depth, 0, 0)
-    cc = scene.counters()
-    rays_counted = cc["rays_closest"] + cc["rays_shadow"]
-    bytes_per_ray = ((cc["node_visits"] * cc["node_bytes"] + cc["prim_tests"] * cc["prim_bytes"]) / max(rays_counted, 1)
-                     + (2 * STATE_BYTES_PER_RAY - 4 if precision == "f64" else STATE_BYTES_PER_RAY))
-    scene.set_instrumentation(timing=True, counting=False)
+    bytes_per_ray = node_bytes = None
+    if args.full:
+        # algorithmic bytes per closest-hit ray: one counting pass (instrumented kernel, never timed), 1 spp
+        scene.set_instrumentation(timing=False, counting=True)
+        render(1, args.max_depth, 0, 0)
+        cc = scene.counters()
+        rays_counted = cc["rays_closest"] + cc["rays_shadow"]
+        bytes_per_ray = ((cc["node_visits"] * cc["node_bytes"] + cc["prim_tests"] * cc["prim_bytes"]) / max(rays_counted, 1)
+                         + (2 * STATE_BYTES_PER_RAY - 4 if precision == "f64" else STATE_BYTES_PER_RAY))
+        node_bytes = cc["node_bytes"]
+        scene.set_instrumentation(timing=True, counting=False)  # (per-kernel HIP events in the timed steps)
     if warmup == 0 and not is_main:
         # (secondary leg: kernels loaded AND the batch workspace of the timed steps allocated — a first hipMalloc of
         # > 100 GB of path state costs seconds and is not the workload; depth 0 keeps it to two rounds)
@@ -291,15 +324,16 @@ def run_leg(args, sd, precision, steps, warmup, rank, world, backend, spp_total,
     report = multi_gpu_report(render_s / max(steps, 1) * 1e3, gather_s / max(steps, 1) * 1e3) if world > 1 else None
     if rank == 0:
         assert img is not None and torch.isfinite(img).all()
-    keep = rank == 0 and world == 1 and img is not None and (not is_main or args.alt_steps > 0)  # (for `parity`)
+    keep = args.full and rank == 0 and world == 1 and img is not None and (not is_main or args.alt_steps > 0)  # (`parity`)
     image64 = img.to(torch.float64).clone() if keep else None
+    image_host = img.cpu().numpy() if (is_main and rank == 0 and args.dump_outputs) else None
     scene.close()
     del out
     torch.cuda.empty_cache()
     samples = args.width * args.height * spp_total * steps
     return {"precision": precision, "value": samples / elapsed / 1e6, "elapsed": elapsed, "steps": steps, "acc": acc,
-            "bytes_per_ray": bytes_per_ray, "node_bytes": cc["node_bytes"], "stats": stats, "setup_s": t_setup,
-            "image64": image64, "multi_gpu": report, "samples": samples}
+            "bytes_per_ray": bytes_per_ray, "node_bytes": node_bytes, "stats": stats, "setup_s": t_setup,
+            "image64": image64, "image_host": image_host, "multi_gpu": report, "samples": samples}
 
 
 def main():
@@ -340,6 +374,8 @@ def main():
                                materials=args.materials, envmap=(2048, 1024) if args.envmap else None)
 
     main_leg = run_leg(args, sd, args.precision, args.steps, args.warmup, rank, world, backend, spp_total, True)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg.pop("image_host"))
     if rank == 0:
         acc, stats = main_leg["acc"], main_leg["stats"]
         mode = ("strong scaling: BASELINE configs[3], 4096x4096 x 1024 spp total, rows sharded over the ranks" if strong
@@ -371,13 +407,14 @@ def main():
                        "bvh": {"builder": args.builder, "nodes": stats["n_nodes"], "prims": stats["n_prims"], "depth": stats["depth"],
                                "scene_bytes": stats["device_bytes"]},
                        "setup_s": main_leg["setup_s"], "rays_per_sample": (acc["rays_closest"] + acc["rays_shadow"]) * world
-                       / max(main_leg["samples"], 1),
-                       "kernel_ms": {k: acc[k] for k in KERNEL_MS}},
-            "roofline": roofline_of(args, args.precision, main_leg["bytes_per_ray"], acc, main_leg["node_bytes"]),
+                       / max(main_leg["samples"], 1)},
         }
+        if args.full:
+            line["config"]["kernel_ms"] = {k: acc[k] for k in KERNEL_MS}
+            line["roofline"] = roofline_of(args, args.precision, main_leg["bytes_per_ray"], acc, main_leg["node_bytes"])
         if world > 1:
             line["multi_gpu"] = main_leg["multi_gpu"]
-        if world == 1 and args.alt_steps > 0:
+        if args.full and world == 1 and args.alt_steps > 0:
             # the same workload on the other arithmetics (own scene, own warm-up), and every leg's image against the f64 one
             images = {args.precision: main_leg["image64"]}
             for alt_prec in [p for p in ("f64", "f32", "mixed") if p != args.precision and not (p == "mixed" and args.precision != "mixed")]:
@@ -407,7 +444,7 @@ def main():
                 if args.precision != "f64":
                     par["headline_within_tolerance"] = bool(par.get(f"{args.precision}_vs_f64_rmse", 1.0) < 1e-3)
                 line["parity"] = par
-        if world == 1 and not args.no_cpu_baseline and not args.instanced:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.instanced:
             try:
                 line["cpu_baseline"] = cpu_baseline(args, sd)
             except Exception as e:  # the bench line must still come out

@@ -60,7 +60,7 @@ def test_reference_cli_with_gpu_render_matches_c_abi(name, tmp_path):
     assert ref_hdr["channels"] == our_hdr["channels"] and ref_hdr["compression"] == our_hdr["compression"]
 
 
-def test_reference_cli_without_gpu_fails_like_the_parser_does():
+def test_reference_cli_without_gpu_fails_like_the_parser_does(tmp_path):
     """no HIP device: the library has no CPU path; the error leaves as the reference's exception type"""
     if not os.path.exists(CLI):
         pytest.skip("oracle/_ref/take_gpu was not built")
@@ -69,7 +69,7 @@ def test_reference_cli_without_gpu_fails_like_the_parser_does():
         pytest.skip("a GPU is visible")
     except capi.TakeError:
         pass  # no HIP device: the case under test
-    r = run_cli(os.path.join(GOLD, "scenes", "cbox.xml"), "/tmp", 5, {})
+    r = run_cli(os.path.join(GOLD, "scenes", "cbox.xml"), str(tmp_path), 5, {})
     assert r.returncode != 0
     assert "fl_exception" in r.stderr and "no HIP device" in r.stderr
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # A/B of bench.py under different environments: tools/ab_env.sh <bench args> -- "NAME=ENV1=V1 ENV2=V2" "NAME2=" ...
 # (each spec: a label, '=', then space-separated VAR=value assignments; an empty list = the defaults)
-args=(); while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
+args=(--full); while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
 mkdir -p gpurun_out
 for spec in "$@"; do
   name="${spec%%=*}"; envs="${spec#*=}"

@@ -11,9 +11,9 @@ except Exception as e:
     print(name, "failed", e)
 PY
 }
-run c1 --tris 100000 --width 1024 --height 1024 --spp 64 --alt-steps 1 --no-cpu-baseline
+run c1 --full --tris 100000 --width 1024 --height 1024 --spp 64 --alt-steps 1 --no-cpu-baseline
 run c3 --config 3 --spp 64 --alt-steps 0 --no-cpu-baseline
-run mats --materials mixed --spp 64 --alt-steps 1 --no-cpu-baseline
+run mats --full --materials mixed --spp 64 --alt-steps 1 --no-cpu-baseline
 run soup10m --tris 10000000 --spp 64 --alt-steps 0 --no-cpu-baseline --builder auto
-run inst --instanced 1000x10000 --spp 64 --alt-steps 1 --no-cpu-baseline
+run inst --full --instanced 1000x10000 --spp 64 --alt-steps 1 --no-cpu-baseline
 run instflat --instanced 1000x10000 --flatten --builder auto --precision f32 --spp 64 --alt-steps 0 --no-cpu-baseline

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
-# The judged profile of round 3: rocprofv3 over the DEFAULT bench command (python3 bench.py: the mixed-precision
-# headline with its f64 and f32 legs) — one plain run, one --kernel-trace --stats pass over the same command — and, per
-# precision (mixed / f64 / f32, each as `--precision P --alt-steps 0 --no-cpu-baseline`: the timed steps are the same
+# The judged profile of round 3: rocprofv3 over the full bench command (python3 bench.py --full: the mixed-precision
+# headline with its f64 and f32 legs) — one run, one --kernel-trace --stats pass over the same command — and, per
+# precision (mixed / f64 / f32, each as `--full --precision P --alt-steps 0 --no-cpu-baseline`: the timed steps are the same
 # ones, the legs they skip are not profiled), FETCH_SIZE, WRITE_SIZE, TCC hit/miss, two SQ passes and GRBM in separate
 # PMC passes (counters are never combined with tracing domains other than --kernel-trace).
 set -u
@@ -14,12 +14,12 @@ cd /tmp
 # ~15 minutes of GPU time, so it can be split over several gpurun calls — gpurun_out/ is merged back between them)
 what="${*:-default mixed f64 f32 summary}"
 if [[ " $what " == *" default "* ]]; then
-echo "--- plain run"; python3 "$root/bench.py" > "$out/bench_plain.log" 2>&1; tail -n 1 "$out/bench_plain.log" | cut -c1-300
-echo "--- stats"; rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 "$root/bench.py" > "$out/stats.log" 2>&1; tail -n 1 "$out/stats.log" | cut -c1-120
+echo "--- full run"; python3 "$root/bench.py" --full > "$out/bench_full.log" 2>&1; tail -n 1 "$out/bench_full.log" | cut -c1-300
+echo "--- stats"; rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python3 "$root/bench.py" --full > "$out/stats.log" 2>&1; tail -n 1 "$out/stats.log" | cut -c1-120
 fi
 for prec in mixed f64 f32; do
   [[ " $what " == *" $prec "* ]] || continue
-  pass() { local name="$1"; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/${prec}_$name" -- python3 "$root/bench.py" --precision $prec --alt-steps 0 --no-cpu-baseline > "$out/${prec}_$name.log" 2>&1; echo "pass $prec $name rc=$?"; }
+  pass() { local name="$1"; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/${prec}_$name" -- python3 "$root/bench.py" --full --precision $prec --alt-steps 0 --no-cpu-baseline > "$out/${prec}_$name.log" 2>&1; echo "pass $prec $name rc=$?"; }
   pass fetch FETCH_SIZE
   pass write WRITE_SIZE
   pass tcc TCC_HIT_sum TCC_MISS_sum

@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # A/B runs of tuning builds: tools/variants.sh <bench args> -- name1 name2 ...   (libs in take_amd/variants/lib_<name>.so)
-args=(); while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
+args=(--full); while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
 mkdir -p gpurun_out
 for v in base "$@"; do
   if [ "$v" = base ]; then unset TAKE_HIP_LIB; else export TAKE_HIP_LIB="$PWD/take_amd/variants/lib_$v.so"; fi
