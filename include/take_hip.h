@@ -330,8 +330,8 @@ int take_hip_render_device(TakeScene *scene, const TakeRenderOpts *opts, void *d
  * ends a sequence), and writes the mean over ALL samples so far to d_rgb_out (device memory, same layout as
  * take_hip_render_device).  The samples continue the one-shot render's numbering — same random streams, same order of
  * the additions — so after calls with a, b, c.. samples the image equals take_hip_render(spp = a + b + c ..) BIT FOR
- * BIT.  seed, max_depth, integrator, ray_epsilon and the strip set must stay the same within a sequence
- * (TAKE_E_INVALID otherwise).  take_hip_accumulated_samples: samples per pixel in the accumulator. */
+ * BIT.  seed, max_depth, integrator, ray_epsilon, the strip set and — on mixed scenes — the effective exact_bounces
+ * must stay the same within a sequence (TAKE_E_INVALID otherwise).  take_hip_accumulated_samples: samples per pixel in the accumulator. */
 int take_hip_render_accumulate(TakeScene *scene, const TakeRenderOpts *opts, int32_t restart, void *d_rgb_out,
                                void *stream);
 int64_t take_hip_accumulated_samples(const TakeScene *scene);

@@ -43,6 +43,9 @@ def lib():
         L.oracle_pt_mt2.argtypes = [C.c_void_p, C.c_int, dp, C.c_int64, dp, C.c_int]
         L.oracle_render2.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, dp, C.c_int, C.c_int]
         L.oracle_render2.restype = C.c_double
+        L.oracle_render3.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, dp, C.c_int, C.c_int,
+                                     C.c_int]
+        L.oracle_render3.restype = C.c_double
         L.oracle_get_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.oracle_counter_words.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
         _LIB = L
@@ -74,6 +77,7 @@ def table(name, inp):
 
 
 RNG_MT_PER_TILE, RNG_COUNTER = 0, 1
+PRECISION_MIXED = 2  # TAKE_PRECISION_MIXED: the scene in both arithmetics, rendered by path_tracing_mixed
 
 
 class OracleScene:
@@ -115,10 +119,19 @@ class OracleScene:
         lib().oracle_pt_mt2(self.h, int(max_depth), _dp(inp), inp.shape[0], _dp(out), int(integrator))
         return out
 
-    def render(self, spp, max_depth, rng_mode=RNG_COUNTER, seed=0, threads=None, counters=False, integrator=0):
-        """-> (H,W,3) float64 image (row 0 = top); self.seconds = tile-loop time"""
+    def render(self, spp, max_depth, rng_mode=RNG_COUNTER, seed=0, threads=None, counters=False, integrator=0,
+               exact_bounces=0):
+        """-> (H,W,3) float64 image (row 0 = top); self.seconds = tile-loop time.  precision=2 (mixed): the first
+        `exact_bounces` rounds of every path in double, the rest in float (path_tracing_mixed; <= 0: the library's
+        default), counter stream and integrator 0 only"""
         threads = threads or os.cpu_count() or 1
         out = np.zeros((self.sd.height, self.sd.width, 3), np.float64)
+        if self.precision == PRECISION_MIXED:
+            self.seconds = lib().oracle_render3(self.h, int(spp), int(max_depth), int(rng_mode), int(seed), int(threads),
+                                                _dp(out), int(counters), int(integrator), int(exact_bounces))
+            if self.seconds < 0:
+                raise ValueError("mixed precision: counter stream, integrator 0 and no counters only")
+            return out
         self.seconds = lib().oracle_render2(self.h, int(spp), int(max_depth), int(rng_mode), int(seed), int(threads),
                                             _dp(out), int(counters), int(integrator))
         return out

@@ -244,12 +244,13 @@ void oracle_tab_bvh(const double *in, int64_t n, double *out) {
 void *oracle_scene_create(const TakeSceneDesc *desc, int precision, double ray_eps) {
     Handle *h = new Handle();
     h->precision = precision;
-    if (precision == TAKE_PRECISION_F64) {
+    if (precision == TAKE_PRECISION_F64 || precision == TAKE_PRECISION_MIXED) {
         scene_from_desc(*desc, h->d);
         h->d.ray_eps = ray_eps > 0 ? ray_eps : 1e-7;
         build_bvh(h->d);
         fill_light_power(h->d);
-    } else {
+    }
+    if (precision != TAKE_PRECISION_F64) {  // f32, and the float half of a mixed scene
         scene_from_desc(*desc, h->f);
         h->f.ray_eps = ray_eps > 0 ? (float)ray_eps : 1e-4f;
         build_bvh(h->f);
@@ -340,6 +341,20 @@ double oracle_render2(void *p, int spp, int max_depth, int rng_mode, uint64_t se
         render(h->f, spp, max_depth, RNG_COUNTER, seed, threads, tmp.data(), with_counters ? &h->counters : nullptr, integrator);
         for (size_t i = 0; i < n; i++) out[i] = tmp[i];
     }
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+// Mixed precision (path_tracing_mixed): a scene created with TAKE_PRECISION_MIXED holds both arithmetics.  Counter
+// stream and the reference's path_tracing only; exact_bounces <= 0: TAKE_DEFAULT_EXACT_BOUNCES.  Other handles: as
+// oracle_render2.  Returns seconds spent in the tile loop, or -1 for a request it cannot render.
+double oracle_render3(void *p, int spp, int max_depth, int rng_mode, uint64_t seed, int threads, double *out,
+                      int with_counters, int integrator, int exact_bounces) {
+    Handle *h = (Handle *)p;
+    if (h->precision != TAKE_PRECISION_MIXED)
+        return oracle_render2(p, spp, max_depth, rng_mode, seed, threads, out, with_counters, integrator);
+    if (rng_mode != RNG_COUNTER || integrator != 0 || with_counters) return -1.0;
+    h->counters = PathCounters{};
+    auto t0 = std::chrono::steady_clock::now();
+    render_mixed(h->d, h->f, spp, max_depth, exact_bounces, seed, threads, out);
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 // out[9]: closest rays, node visits, box tests, prim tests, shadow rays, node visits, box tests, prim tests, bounces

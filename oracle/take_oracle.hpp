@@ -13,6 +13,8 @@
 //                         just set Real = float" (src/take.h:20-28) variant: the f32 twin of the
 //                         production GPU path, with the ray offset epsilon as a parameter
 //                         (src/take.h:30-31 offers 1e-7 and 1e-4)
+//   path_tracing_mixed     the two above in sequence — double for the first rounds of a path, float for the rest,
+//                         handed over where the device's mixed-precision render loop hands over (an extension)
 //
 // Parity status: PINNED.  tests/test_oracle_golden.py checks this file against every table and
 // seeded render under tests/golden/, all produced by the compiled reference (oracle/Makefile `ref`,
@@ -1129,6 +1131,166 @@ V3<R> integrate(int integrator, const Scene<R> &sc, const Ray<R> &ray, Rng &rng,
     }
 }
 
+// ------------------------------------------------------------------ mixed precision (TAKE_PRECISION_MIXED; an extension)
+// path_tracing above, cut into the two halves of a loop iteration so that it can change arithmetic in the middle of
+// one, where the device's render loop (tk_integrate.h, tk_kernels.h) changes it.  Device round k = 0 handles the
+// camera ray's hit; round k >= 1 finishes loop iteration k-1 (trace its BSDF ray, C2 term, throughput update) and
+// starts iteration k (NEE + shadow ray, BSDF sample).  With E exact rounds (k < E on the f64 records and scene):
+//   iterations 0 .. E-2          entirely in double;
+//   iteration E-1                NEE, shadow ray and BSDF sample in double (round E-1) ...
+//                                ... its BSDF ray traced and finished in float (round E), as are
+//   iterations E .. max_depth    entirely in float, on the float scene and with its ray epsilon.
+// The conversion (tk_kernels.h k_convert_state, and k_shade's in-register form of it) moves the ray, throughput,
+// radiance so far, pending sample (FG, pdf), stream counter and specular flag to float; the f64 side keeps only what
+// iteration E-1's shadow ray adds.  A sample's value is a + (double)b (k_accumulate_mixed).
+template <class R> struct PathHalf {
+    Intersection<R> v;            // current vertex
+    Ray<R> r;                     // the ray that found v; after first_half: the sampled ray leaving v
+    V3<R> throughput{R(1), R(1), R(1)}, radiance{R(0), R(0), R(0)};
+    V3<R> FG{R(0), R(0), R(0)};   // pending BSDF sample (valid after first_half returned true)
+    R pdf = R(0);
+    bool is_specular = false;
+    V3<R> nee{R(0), R(0), R(0)};  // throughput * C1 of this iteration, to be added when `lit`
+    bool lit = false;             // the shadow ray of this iteration was traced and reached the light
+};
+// path_tracing.h:22-81 — NEE (kept in nee/lit, not added) and the BSDF sample; false: the loop `break`s
+template <class R> bool pt_first_half(const Scene<R> &sc, PathHalf<R> &s, CounterRng &rng) {
+    const Intersection<R> &v = s.v;
+    const R nlights = R(sc.lights.size());
+    const V3<R> dir_in = -s.r.dir;
+    const Material<R> &m = sc.materials[v.material_id];
+    const bool is_specular = (m.tag == TAKE_MAT_PLASTIC || m.tag == TAKE_MAT_MIRROR);
+    s.lit = false;
+    if (sc.lights.size() > 0 && !is_specular) {
+        const int light_id = static_cast<int>(std::floor(Draw<R, CounterRng>::real(rng) * nlights));
+        const Light<R> &light = sc.lights[light_id];
+        if (light.kind == 2) {
+            EnvSample<R> es = env_sample(sc, rng);
+            R light_pdf = es.pdf / nlights;
+            if (light_pdf <= 0) return false;
+            R bsdf_pdf = get_bsdf_pdf(m, dir_in, es.dir, v, sc);
+            if (bsdf_pdf > 0 && !std::isinf(light_pdf)) {
+                SampleRecord<R> rec{};
+                rec.dir_out = es.dir;
+                V3<R> FG = eval_bsdf(m, dir_in, rec, v, sc);
+                if (!scene_occluded(sc, Ray<R>{v.pos, es.dir, sc.ray_eps, K<R>::inf()})) {
+                    s.nee = s.throughput * (FG * es.radiance * light_pdf / (light_pdf * light_pdf + bsdf_pdf * bsdf_pdf));
+                    s.lit = true;
+                }
+            }
+        } else if (light.kind == 1) {
+            PointAndNormal<R> lp = sample_on_shape(sc, sc.shapes.at(light.shape_id), v.pos, rng);
+            R d = length(lp.position - v.pos);
+            V3<R> light_dir = normalize(lp.position - v.pos);
+            R light_pdf = get_light_pdf(sc, light_id, lp, v.pos) * (d * d) /
+                          (std::fmax(dot(-lp.normal, light_dir), R(0)) * nlights);
+            if (light_pdf <= 0) return false;
+            R bsdf_pdf = get_bsdf_pdf(m, dir_in, light_dir, v, sc);
+            if (bsdf_pdf > 0 && !std::isinf(light_pdf)) {
+                SampleRecord<R> rec{};
+                rec.dir_out = light_dir;
+                V3<R> FG = eval_bsdf(m, dir_in, rec, v, sc);
+                if (!scene_occluded(sc, Ray<R>{v.pos, light_dir, sc.ray_eps, (1 - sc.ray_eps) * d})) {
+                    s.nee = s.throughput * (FG * light.intensity * light_pdf / (light_pdf * light_pdf + bsdf_pdf * bsdf_pdf));
+                    s.lit = true;
+                }
+            }
+        }
+    }
+    auto rec_ = sample_bsdf(m, dir_in, v, sc, rng);
+    if (!rec_) return false;
+    s.FG = eval_bsdf(m, dir_in, *rec_, v, sc);
+    const V3<R> dir_out = normalize(rec_->dir_out);
+    s.pdf = rec_->pdf;
+    if (s.pdf <= R(0)) return false;
+    s.is_specular = is_specular;
+    s.r = Ray<R>{v.pos, dir_out, sc.ray_eps, K<R>::inf()};
+    return true;
+}
+// path_tracing.h:82-108 — trace the pending sample's ray, C2, throughput update; false: the path has ended
+template <class R> bool pt_second_half(const Scene<R> &sc, PathHalf<R> &s) {
+    const R nlights = R(sc.lights.size());
+    const V3<R> from = s.r.origin;
+    auto new_v = scene_intersect(sc, s.r);
+    if (!new_v) {
+        if (sc.env.light >= 0) {
+            R env_pdf;
+            V3<R> L = env_eval(sc, s.r.dir, env_pdf);
+            R lp = env_pdf / nlights;
+            s.radiance = s.radiance + s.throughput * (s.FG * L * (s.is_specular ? (1 / s.pdf) : (s.pdf / (lp * lp + s.pdf * s.pdf))));
+            return false;
+        }
+        s.throughput = s.throughput * (s.FG / s.pdf);
+        s.radiance = s.radiance + s.throughput * sc.background;
+        return false;
+    }
+    V3<R> C2{R(0), R(0), R(0)};
+    if (new_v->area_light_id != -1) {
+        R d = length(new_v->pos - from);
+        V3<R> light_dir = normalize(new_v->pos - from);
+        R light_pdf = get_light_pdf(sc, new_v->area_light_id, PointAndNormal<R>{new_v->pos, new_v->geo_normal}, from) *
+                      (d * d) / (std::fmax(dot(-new_v->geo_normal, light_dir), R(0)) * nlights);
+        if (light_pdf <= 0) return false;
+        const Light<R> &light = sc.lights[new_v->area_light_id];
+        if (light.kind == 1)
+            C2 = s.FG * light.intensity * (s.is_specular ? (1 / s.pdf) : (s.pdf / (light_pdf * light_pdf + s.pdf * s.pdf)));
+    }
+    s.radiance = s.radiance + s.throughput * C2;
+    s.throughput = s.throughput * (s.FG / s.pdf);
+    s.v = *new_v;
+    return true;
+}
+template <class R> V3<float> f32v(V3<R> a) { return {(float)a.x, (float)a.y, (float)a.z}; }
+// iterations i0 .. max_depth of the loop on the state `s` (whose own first half has run), all in R
+template <class R> V3<R> pt_iterations(const Scene<R> &sc, PathHalf<R> &s, CounterRng &rng, int i0, int max_depth) {
+    for (int i = i0; i <= max_depth; ++i) {
+        const bool pending = pt_first_half(sc, s, rng);
+        if (s.lit) s.radiance = s.radiance + s.nee;
+        if (!pending || !pt_second_half(sc, s)) break;
+    }
+    return s.radiance;
+}
+inline V3<double> path_tracing_mixed(const Scene<double> &sd, const Scene<float> &sf, const Ray<double> &ray,
+                                     CounterRng &rng, int max_depth, int exact_bounces) {
+    const int E = exact_bounces > 0 ? exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
+    PathHalf<double> s;
+    s.r = ray;
+    auto v_ = scene_intersect(sd, s.r);
+    if (!v_) {
+        if (sd.env.light >= 0) {
+            double unused;
+            return env_eval(sd, s.r.dir, unused);
+        }
+        return sd.background;
+    }
+    s.v = *v_;
+    if (s.v.area_light_id != -1) {
+        const Light<double> &light = sd.lights.at(s.v.area_light_id);
+        if (light.kind == 1) s.radiance = s.radiance + s.throughput * light.intensity;
+    }
+    for (int i = 0; i <= max_depth; ++i) {
+        const bool pending = pt_first_half(sd, s, rng);
+        if (i == E - 1) {  // device round E-1: the last exact shade round
+            if (!pending) return s.lit ? s.radiance + s.nee : s.radiance;  // not converted: the f64 record holds it all
+            // the conversion (k_convert_state): ray, throughput, radiance so far, pending sample, counter (rng), flags
+            PathHalf<float> f;
+            f.r = Ray<float>{f32v(s.r.origin), f32v(s.r.dir), sf.ray_eps, K<float>::inf()};
+            f.throughput = f32v(s.throughput);
+            f.radiance = f32v(s.radiance);
+            f.FG = f32v(s.FG);
+            f.pdf = (float)s.pdf;
+            f.is_specular = s.is_specular;
+            // f64 side: its radiance cleared, then what this round's shadow ray adds
+            const V3<double> a = s.lit ? V3<double>{0.0, 0.0, 0.0} + s.nee : V3<double>{0.0, 0.0, 0.0};
+            const V3<float> b = pt_second_half(sf, f) ? pt_iterations(sf, f, rng, E, max_depth) : f.radiance;
+            return {a.x + (double)b.x, a.y + (double)b.y, a.z + (double)b.z};  // k_accumulate_mixed
+        }
+        if (s.lit) s.radiance = s.radiance + s.nee;
+        if (!pending || !pt_second_half(sd, s)) break;
+    }
+    return s.radiance;
+}
+
 // ------------------------------------------------------------------ src/render.cpp:37-82
 template <class R> struct CameraBasis {
     V3<R> u, v, w, lookfrom;
@@ -1228,6 +1390,35 @@ void render(const Scene<R> &sc, int spp, int max_depth, int rng_mode, uint64_t s
             }
         }
     }
+}
+// The same tile loop for mixed precision: counter stream only, path_tracing_mixed per sample, double image.
+inline void render_mixed(const Scene<double> &sd, const Scene<float> &sf, int spp, int max_depth, int exact_bounces,
+                         uint64_t seed, int threads, double *out) {
+    const CameraBasis<double> cb = camera_basis<double>(sd.camera);
+    const int W = cb.width, H = cb.height;
+    std::atomic<int> next{0};
+    auto worker = [&]() {
+        for (int y; (y = next.fetch_add(1)) < H;) {
+            for (int x = 0; x < W; x++) {
+                V3<double> color{0.0, 0.0, 0.0};
+                for (int i = 0; i < spp; i++) {
+                    CounterRng cr(seed, (uint64_t)y * W + x, (uint64_t)i);
+                    double ry = Draw<double, CounterRng>::real(cr);
+                    double rx = Draw<double, CounterRng>::real(cr);
+                    Ray<double> r = camera_ray(cb, x, y, rx, ry, sd.ray_eps);
+                    color = color + path_tracing_mixed(sd, sf, r, cr, max_depth, exact_bounces);
+                }
+                V3<double> px = color / double(spp);
+                double *o = out + ((size_t)(H - y - 1) * W + x) * 3;
+                o[0] = px.x;
+                o[1] = px.y;
+                o[2] = px.z;
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 0; t < std::max(threads, 1); t++) pool.emplace_back(worker);
+    for (auto &t : pool) t.join();
 }
 
 }  // namespace oracle

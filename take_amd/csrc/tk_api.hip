@@ -962,6 +962,16 @@ void launch_round(TakeScene *ts, SceneT<RR> &sc, const RoundWs &ws, PathState<RR
         }
     }
     tm.end();
+    if constexpr (sizeof(RR) == 8) {
+        if (!TK_SHADE_RECORD && to_f32 != nullptr) {
+            // mixed precision, last exact round, builds without the register copy of the record: the paths that go on
+            // continue on f32 records from here — converted before this round's shadow rays, as k_shade does it
+            tm.begin(TK_OTHER);
+            hipLaunchKernelGGL(k_convert_state, dim3(ws.wide_grid), dim3(BLOCK), 0, stream, st, PathState<float>{to_f32, slots},
+                               ws.queue[next], n_next);
+            tm.end();
+        }
+    }
     if (dump >= 0 && dump < slots) dump_slot(st, dump, "after shade", k, stream);
     if (k <= rp.max_depth && rp.integrator == 0) {  // integrators 1..3 trace no shadow rays
         tm.begin(TK_SHADOW);
@@ -1113,17 +1123,11 @@ template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void 
             const int next = (k & 1) ^ 1;
             int32_t *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
             if constexpr (sizeof(R) == 8) {
-                if (mixed && k == exact_rounds && !TK_SHADE_RECORD) {
-                    // mixed precision: the paths still alive continue on f32 records (and the f32 scene) from here on
-                    // (with TK_SHADE_RECORD the last exact shade round has written them already: k_shade, to_f32)
-                    tm.begin(TK_OTHER);
-                    hipLaunchKernelGGL(k_convert_state, dim3(wide_grid), dim3(BLOCK), 0, stream, st, st32, ws.queue[k & 1],
-                                       q + ((k & 1) ? Q_N_EXT1 : Q_N_EXT0));
-                    tm.end();
-                }
+                // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
+                // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
                 if (mixed && k >= exact_rounds) launch_round<float>(ts, ts->f, ws, st32, rp32, k, n_bound, tm, counting, sort_materials, stream, -1, slots, true);
                 else launch_round<R>(ts, sc, ws, st, rp, k, n_bound, tm, counting, sort_materials, stream, dump, slots, false,
-                                     (mixed && TK_SHADE_RECORD && k == exact_rounds - 1) ? st32.r : nullptr);
+                                     (mixed && k == exact_rounds - 1) ? st32.r : nullptr);
             } else {
                 launch_round<R>(ts, sc, ws, st, rp, k, n_bound, tm, counting, sort_materials, stream, dump, slots);
             }
@@ -1672,10 +1676,15 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
     const bool f64 = is_f64(ts);
     const TakeRenderOpts &a = ts->acc_opts;
     const bool fresh = restart != 0 || ts->acc_samples == 0;
+    // (mixed scenes: the exact rounds the samples were rendered with, <= 0 meaning the default; f32 / f64 ignore the field)
+    auto exact = [ts](const TakeRenderOpts &o) {
+        return ts->precision != TAKE_PRECISION_MIXED ? 0 : o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
+    };
     if (!fresh && (a.seed != opts->seed || a.max_depth != opts->max_depth || a.integrator != opts->integrator ||
-                   a.strip_first != opts->strip_first || a.strip_stride != opts->strip_stride || a.ray_epsilon != opts->ray_epsilon))
+                   a.strip_first != opts->strip_first || a.strip_stride != opts->strip_stride || a.ray_epsilon != opts->ray_epsilon ||
+                   exact(a) != exact(*opts)))
         return fail(TAKE_E_INVALID, "take_hip_render_accumulate: options differ from the ones the accumulated samples were "
-                                    "rendered with (seed, max_depth, integrator, strips, ray_epsilon): pass restart = 1");
+                                    "rendered with (seed, max_depth, integrator, strips, ray_epsilon, exact_bounces): pass restart = 1");
     const int64_t first = fresh ? 0 : ts->acc_samples;
     if (first + (int64_t)opts->spp >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many accumulated samples");
     // (a workspace grown for a bigger batch keeps the accumulator: ensure_workspace only ever enlarges it, and the

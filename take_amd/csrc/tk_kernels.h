@@ -195,6 +195,7 @@ k_shade(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, const int32_t *_
                 for (int w = 0; w < 16; w++) fv.w[WORDS[w]] = (float)rv.w[WORDS[w]];
                 fv.I_(S_CTR, 0) = rv.I_(S_CTR, 0);
                 fv.I_(S_FLAGS, 0) = rv.I_(S_FLAGS, 0);
+                fv.I_(S_OCC, 0) = -1;  // (counting mode: no previous occluder — not primitive 0)
                 rv.w[S_LX] = 0.0, rv.w[S_LY] = 0.0, rv.w[S_LZ] = 0.0;
                 rv.I_(S_CONV, 0) = 1;
                 uint4 *out32 = (uint4 *)(to_f32 + (int64_t)slot * PATH_REC);
@@ -360,7 +361,9 @@ k_accumulate(PathState<R> st, R *accum, int32_t npix, int32_t spb) {
 // moves with the path (the f64 record's is cleared), so that a sample's value is the sum of the two records' radiance
 // whichever round its path ended in (k_accumulate_mixed; S_CONV in the f64 record says whether the f32 record counts).
 // The render loop does this inside the last exact shade round (k_shade, to_f32); this kernel is the stand-alone form
-// for builds without the register copy of the record (TK_SHADE_RECORD = 0).
+// for builds without the register copy of the record (TK_SHADE_RECORD = 0), launched at the same point: after that
+// round's shade, over its extend queue, before its shadow rays — so that in both forms the f64 record keeps exactly
+// what the last exact shadow ray adds.
 __global__ void __launch_bounds__(BLOCK)
 k_convert_state(PathState<double> a, PathState<float> b, const int32_t *__restrict__ queue, const int32_t *__restrict__ n_ptr) {
     const int32_t n = *n_ptr;
@@ -371,6 +374,7 @@ k_convert_state(PathState<double> a, PathState<float> b, const int32_t *__restri
         for (int w = 0; w < 16; w++) b.R_(WORDS[w], s) = (float)a.R_(WORDS[w], s);
         b.I_(S_CTR, s) = a.I_(S_CTR, s);
         b.I_(S_FLAGS, s) = a.I_(S_FLAGS, s);
+        b.I_(S_OCC, s) = -1;  // (counting mode: no previous occluder — the f32 record may hold anything)
         a.R_(S_LX, s) = 0.0, a.R_(S_LY, s) = 0.0, a.R_(S_LZ, s) = 0.0;
         a.I_(S_CONV, s) = 1;
     }

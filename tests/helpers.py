@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 
 from take_amd import cdefs as D
-from take_amd.scene import load_tkscene
+from take_amd.scene import SceneData, load_tkscene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
@@ -35,11 +35,11 @@ def hostsim():
 
 
 def render_opts(spp, max_depth, seed=0, ray_epsilon=0.0, strip_first=0, strip_stride=1, samples_per_batch=0,
-                integrator=0):
+                integrator=0, exact_bounces=0):
     o = D.TakeRenderOpts()
     o.spp, o.max_depth, o.seed, o.ray_epsilon = spp, max_depth, seed, ray_epsilon
     o.strip_first, o.strip_stride, o.samples_per_batch = strip_first, strip_stride, samples_per_batch
-    o.integrator = integrator
+    o.integrator, o.exact_bounces = integrator, exact_bounces
     return o
 
 
@@ -51,11 +51,13 @@ def n_local_rows(height, first, stride):
 
 
 def hostsim_render(sd, precision, spp, max_depth, seed=0, ray_epsilon=0.0, strip_first=0, strip_stride=1,
-                   samples_per_batch=0, integrator=0):
+                   samples_per_batch=0, integrator=0, exact_bounces=0):
+    """precision 0 f32, 1 f64, 2 mixed (the first `exact_bounces` rounds in double, the rest in float; double image)"""
     desc, keep = sd.to_desc()
-    o = render_opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+    o = render_opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator,
+                    exact_bounces)
     rows = n_local_rows(sd.height, strip_first, strip_stride)
-    out = np.zeros((rows, sd.width, 3), np.float64 if precision == 1 else np.float32)
+    out = np.zeros((rows, sd.width, 3), np.float32 if precision == 0 else np.float64)
     stats = (C.c_uint64 * 7)()
     rc = hostsim().hostsim_render(C.addressof(desc), precision, C.addressof(o), out.ctypes.data, stats)
     if rc != 0:
@@ -98,3 +100,22 @@ def rmse(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float(np.sqrt(np.mean((a - b) ** 2)))
+
+
+def mirror_box_scene(width=48, height=32, n_soup=12, seed=7):
+    """A scene whose paths, on the device, need no transcendental function: triangles only (a sphere hit takes acos /
+    atan2 for its uv), every surface a white Mirror (F0 = 1: the Schlick term's pow is multiplied by 0 — FG is exactly
+    1), so NEE never runs (specular) and the quad light is reached by reflected rays alone.  What is left is +, -, x, /
+    and sqrt: the GPU's image can equal the oracle's bit for bit.  The box is open at the front, so paths also end on
+    the constant background, whose value (like the light's) is not a float: a path ending in a float round
+    contributes float(value), one ending in a double round the value itself — which round a path ends in shows in
+    the image."""
+    from take_amd import scenes
+
+    sd = SceneData(width=width, height=height, lookfrom=(0.0, 0.0, 3.9), lookat=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0),
+                   vfov=scenes.vfov_from_xfov(39.0, width, height), background=(0.3, 0.2, 0.1), spp=2, max_depth=50)
+    mirror = sd.add_material(D.MAT_MIRROR, (1.0, 1.0, 1.0))
+    scenes.box_with_light(sd, mirror, mirror, mirror, light_half=0.35, radiance=(5.3, 4.1, 2.7))
+    pos, idx = scenes.soup_triangles(n_soup, seed, half=0.6, jitter=0.35)
+    sd.add_mesh(pos, idx, mirror)
+    return sd

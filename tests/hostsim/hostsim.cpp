@@ -44,91 +44,159 @@ template <class R> void dump_slot(const PathState<R> &st, int64_t slot, const ch
     std::fprintf(stderr, "\n");
 }
 
-template <class R> int render_t(const TakeSceneDesc &desc, const TakeRenderOpts &o, void *out_v, uint64_t *stats) {
+struct Stats {
+    uint64_t closest = 0, shadow = 0, nodes = 0, prims = 0, max_stack = 0;
+};
+// Mixed precision, last exact round: what k_shade does in registers for a path that goes on (k_convert_state is the
+// stand-alone form): ray, pending sample, throughput, radiance so far, stream counter and flags move to the f32
+// record of the slot; the f64 record's radiance is cleared (it receives what this round's shadow ray adds) and
+// S_CONV says that the f32 record counts.
+void convert_to_f32(const PathState<double> &a, const PathState<float> &b, int64_t s) {
+    constexpr int WORDS[] = {S_OX, S_OY, S_OZ, S_DX, S_DY, S_DZ, S_PDF, S_TX, S_TY, S_TZ, S_LX, S_LY, S_LZ, S_FX, S_FY, S_FZ};
+    for (int w : WORDS) b.R_(w, s) = (float)a.R_(w, s);
+    b.I_(S_CTR, s) = a.I_(S_CTR, s);
+    b.I_(S_FLAGS, s) = a.I_(S_FLAGS, s);
+    b.I_(S_OCC, s) = -1;
+    a.R_(S_LX, s) = 0.0, a.R_(S_LY, s) = 0.0, a.R_(S_LZ, s) = 0.0;
+    a.I_(S_CONV, s) = 1;
+}
+
+// One launch round k over the paths of `cur`: k_trace<closest>, k_shade (next / shadow requests), k_trace<shadow>.
+// to_f32 (R = double only): the round is the last exact one of a mixed render — its continuing paths are converted
+// after the shade and before the shadow rays, as the device does.
+template <class R>
+void run_round(const DeviceScene<R> &sc, const RenderParams<R> &rp, const PathState<R> &st, const std::vector<int32_t> &cur,
+               std::vector<int32_t> &next, std::vector<int32_t> &shadow, int k, Stats &n, int64_t dump, int64_t slots,
+               const PathState<float> *to_f32) {
+    next.clear();
+    shadow.clear();
+    for (int32_t slot : cur) {  // k_trace<closest>
+        RayT<R> ray = make_ray(st.R_(S_OX, slot), st.R_(S_OY, slot), st.R_(S_OZ, slot), st.R_(S_DX, slot),
+                               st.R_(S_DY, slot), st.R_(S_DZ, slot), rp.ray_eps, Const<R>::inf());
+        HitT<R> hit;
+        ArrayStack stack;
+        TravCount tc;
+        traverse<R, false, true>(sc, ray, stack, hit, tc);
+        n.nodes += tc.nodes, n.prims += tc.prims, n.closest++;
+        n.max_stack = std::max<uint64_t>(n.max_stack, stack.max_level);
+        st.I_(S_HIT, slot) = hit.prim;
+        st.I_(S_INST, slot) = hit.inst;
+        st.R_(S_HT, slot) = hit.t;
+        st.R_(S_HU, slot) = hit.u;
+        st.R_(S_HV, slot) = hit.v;
+    }
+    if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_closest", k);
+    for (int32_t slot : cur) {  // k_shade
+        uint32_t req = rp.integrator ? shade_path_alt(sc, rp, st, (int64_t)slot, k) : shade_path(sc, rp, st, (int64_t)slot, k);
+        if (req & REQ_EXTEND) next.push_back(slot);
+        if (req & REQ_SHADOW) shadow.push_back(slot);
+    }
+    if constexpr (sizeof(R) == 8) {
+        if (to_f32)
+            for (int32_t slot : next) convert_to_f32(st, *to_f32, slot);
+    }
+    if (dump >= 0 && dump < slots) dump_slot(st, dump, "after shade", k);
+    for (int32_t slot : shadow) {  // k_trace<shadow>
+        RayT<R> ray = make_ray(st.R_(S_OX, slot), st.R_(S_OY, slot), st.R_(S_OZ, slot), st.R_(S_SX, slot),
+                               st.R_(S_SY, slot), st.R_(S_SZ, slot), rp.ray_eps, st.R_(S_ST, slot));
+        HitT<R> hit;
+        ArrayStack stack;
+        TravCount tc;
+        traverse<R, true, true>(sc, ray, stack, hit, tc);
+        n.nodes += tc.nodes, n.prims += tc.prims, n.shadow++;
+        if (hit.prim < 0) {
+            st.R_(S_LX, slot) = st.R_(S_LX, slot) + st.R_(S_CX, slot);
+            st.R_(S_LY, slot) = st.R_(S_LY, slot) + st.R_(S_CY, slot);
+            st.R_(S_LZ, slot) = st.R_(S_LZ, slot) + st.R_(S_CZ, slot);
+        }
+    }
+    if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_shadow", k);
+}
+
+template <class R> RenderParams<R> render_params(const HostScene<R> &hs, const TakeRenderOpts &o, int n_rows) {
+    RenderParams<R> rp{};
+    const int W = hs.cam.width, H = hs.cam.height;
+    rp.width = W, rp.height = H, rp.n_local_rows = n_rows, rp.npix = (int32_t)((int64_t)n_rows * W);
+    rp.inv_npix = 1.0 / (double)rp.npix, rp.inv_width = 1.0 / (double)W;
+    rp.strip_first = o.strip_first, rp.strip_stride = o.strip_stride > 0 ? o.strip_stride : 1;
+    rp.spp = o.spp, rp.max_depth = o.max_depth, rp.seed = o.seed, rp.integrator = o.integrator;
+    rp.ray_eps = o.ray_epsilon > 0 ? R(o.ray_epsilon) : (sizeof(R) == 8 ? R(1e-7) : R(1e-4));
+    return rp;
+}
+
+// MIXED: R = double, and rounds k >= exact_bounces (<= 0: TAKE_DEFAULT_EXACT_BOUNCES) run on f32 records of the same
+// slots and the f32 scene (tk_api.hip render_impl); the samples are accumulated as k_accumulate_mixed does.
+template <class R, bool MIXED = false>
+int render_t(const TakeSceneDesc &desc, const TakeRenderOpts &o, void *out_v, uint64_t *stats) {
+    const int max_leaf = std::getenv("HOSTSIM_MAX_LEAF") ? std::atoi(std::getenv("HOSTSIM_MAX_LEAF")) : 0;
     HostScene<R> hs;
-    g_err = prepare_scene<R>(desc, std::getenv("HOSTSIM_MAX_LEAF") ? std::atoi(std::getenv("HOSTSIM_MAX_LEAF")) : 0, 1, hs);
+    g_err = prepare_scene<R>(desc, max_leaf, 1, hs);
     if (!g_err.empty()) return TAKE_E_INVALID;
+    HostScene<float> hs32;
+    if (MIXED) {
+        if (o.integrator != 0) {
+            g_err = "mixed precision renders the reference's path_tracing (integrator 0) only";
+            return TAKE_E_INVALID;
+        }
+        g_err = prepare_scene<float>(desc, max_leaf, 1, hs32);
+        if (!g_err.empty()) return TAKE_E_INVALID;
+    }
     DeviceScene<R> sc = hs.view();
+    DeviceScene<float> sc32 = MIXED ? hs32.view() : DeviceScene<float>{};
+    const int exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
     const int W = hs.cam.width, H = hs.cam.height;
     const int stride = o.strip_stride > 0 ? o.strip_stride : 1;
     const int n_strips = (H + TILE_ROWS - 1) / TILE_ROWS;
     int n_rows = 0;
     for (int s = o.strip_first; s < n_strips; s += stride) n_rows += std::min(H, (s + 1) * TILE_ROWS) - s * TILE_ROWS;
     const int64_t npix = (int64_t)n_rows * W;
-    RenderParams<R> rp{};
-    rp.width = W, rp.height = H, rp.n_local_rows = n_rows, rp.npix = (int32_t)npix;
-    rp.inv_npix = 1.0 / (double)npix, rp.inv_width = 1.0 / (double)W;
-    rp.strip_first = o.strip_first, rp.strip_stride = stride;
-    rp.spp = o.spp, rp.max_depth = o.max_depth, rp.seed = o.seed, rp.integrator = o.integrator;
-    rp.ray_eps = o.ray_epsilon > 0 ? R(o.ray_epsilon) : (sizeof(R) == 8 ? R(1e-7) : R(1e-4));
+    RenderParams<R> rp = render_params(hs, o, n_rows);
+    RenderParams<float> rp32{};
+    if (MIXED) {  // the f32 rounds' parameters: the same but for the ray epsilon (1e-4 unless given)
+        rp32 = render_params(hs32, o, n_rows);
+        rp32.ray_eps = o.ray_epsilon > 0 ? (float)o.ray_epsilon : 1e-4f;
+    }
     const int spb = o.samples_per_batch > 0 ? std::min(o.samples_per_batch, o.spp) : o.spp;
     const int64_t slots = (int64_t)spb * npix;
     std::vector<R> sr((size_t)PATH_REC * slots);
     PathState<R> st{sr.data(), slots};
+    std::vector<float> sr32(MIXED ? (size_t)PATH_REC * slots : 0);
+    PathState<float> st32{sr32.data(), slots};
     std::vector<R> accum(3 * npix, R(0));
     std::vector<int32_t> q[2], shadow;
-    uint64_t n_closest = 0, n_shadow = 0, n_nodes = 0, n_prims = 0, max_stack = 0;
+    Stats n;
     const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT");
     const int64_t dump = dump_env ? std::atoll(dump_env) : -1;
     for (int s0 = 0; s0 < o.spp; s0 += spb) {
         const int nb = std::min(spb, o.spp - s0);
-        const int64_t n = (int64_t)nb * npix;
-        rp.s0 = s0;
-        rp.spb = nb;
+        const int64_t nslot = (int64_t)nb * npix;
+        rp.s0 = rp32.s0 = s0;
+        rp.spb = rp32.spb = nb;
         q[0].clear();
-        for (int64_t s = 0; s < n; s++) {
+        for (int64_t s = 0; s < nslot; s++) {
             generate_path(sc, rp, st, s);
             q[0].push_back((int32_t)s);
         }
         for (int k = 0; k < o.max_depth + 2; k++) {
             const int cur = k & 1, next = cur ^ 1;
-            q[next].clear();
-            shadow.clear();
-            for (int32_t slot : q[cur]) {  // k_trace<closest>
-                RayT<R> ray = make_ray(st.R_(S_OX, slot), st.R_(S_OY, slot), st.R_(S_OZ, slot), st.R_(S_DX, slot),
-                                       st.R_(S_DY, slot), st.R_(S_DZ, slot), rp.ray_eps, Const<R>::inf());
-                HitT<R> hit;
-                ArrayStack stack;
-                TravCount tc;
-                traverse<R, false, true>(sc, ray, stack, hit, tc);
-                n_nodes += tc.nodes, n_prims += tc.prims, n_closest++;
-                max_stack = std::max<uint64_t>(max_stack, stack.max_level);
-                st.I_(S_HIT, slot) = hit.prim;
-                st.I_(S_INST, slot) = hit.inst;
-                st.R_(S_HT, slot) = hit.t;
-                st.R_(S_HU, slot) = hit.u;
-                st.R_(S_HV, slot) = hit.v;
-            }
-            if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_closest", k);
-            for (int32_t slot : q[cur]) {  // k_shade
-                uint32_t req = rp.integrator ? shade_path_alt(sc, rp, st, (int64_t)slot, k) : shade_path(sc, rp, st, (int64_t)slot, k);
-                if (req & REQ_EXTEND) q[next].push_back(slot);
-                if (req & REQ_SHADOW) shadow.push_back(slot);
-            }
-            if (dump >= 0 && dump < slots) dump_slot(st, dump, "after shade", k);
-            for (int32_t slot : shadow) {  // k_trace<shadow>
-                RayT<R> ray = make_ray(st.R_(S_OX, slot), st.R_(S_OY, slot), st.R_(S_OZ, slot), st.R_(S_SX, slot),
-                                       st.R_(S_SY, slot), st.R_(S_SZ, slot), rp.ray_eps, st.R_(S_ST, slot));
-                HitT<R> hit;
-                ArrayStack stack;
-                TravCount tc;
-                traverse<R, true, true>(sc, ray, stack, hit, tc);
-                n_nodes += tc.nodes, n_prims += tc.prims, n_shadow++;
-                if (hit.prim < 0) {
-                    st.R_(S_LX, slot) = st.R_(S_LX, slot) + st.R_(S_CX, slot);
-                    st.R_(S_LY, slot) = st.R_(S_LY, slot) + st.R_(S_CY, slot);
-                    st.R_(S_LZ, slot) = st.R_(S_LZ, slot) + st.R_(S_CZ, slot);
-                }
-            }
-            if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_shadow", k);
+            if (MIXED && k >= exact_rounds)
+                run_round<float>(sc32, rp32, st32, q[cur], q[next], shadow, k, n, dump, slots, nullptr);
+            else
+                run_round<R>(sc, rp, st, q[cur], q[next], shadow, k, n, dump, slots,
+                             MIXED && k == exact_rounds - 1 ? &st32 : nullptr);
             if (q[next].empty()) break;
         }
-        for (int64_t p = 0; p < npix; p++)  // k_accumulate
+        for (int64_t p = 0; p < npix; p++)  // k_accumulate / k_accumulate_mixed
             for (int s = 0; s < nb; s++) {
                 const int64_t slot = (int64_t)s * npix + p;
-                accum[3 * p] = accum[3 * p] + st.R_(S_LX, slot);
-                accum[3 * p + 1] = accum[3 * p + 1] + st.R_(S_LY, slot);
-                accum[3 * p + 2] = accum[3 * p + 2] + st.R_(S_LZ, slot);
+                for (int c = 0; c < 3; c++) {
+                    if (MIXED) {
+                        const bool conv = st.I_(S_CONV, slot) != 0;
+                        accum[3 * p + c] = accum[3 * p + c] + (st.R_(S_LX + c, slot) + (conv ? (double)st32.R_(S_LX + c, slot) : 0.0));
+                    } else {
+                        accum[3 * p + c] = accum[3 * p + c] + st.R_(S_LX + c, slot);
+                    }
+                }
             }
     }
     R *out = (R *)out_v;  // k_resolve
@@ -139,7 +207,7 @@ template <class R> int render_t(const TakeSceneDesc &desc, const TakeRenderOpts 
         for (int c = 0; c < 3; c++) out[oidx + c] = accum[3 * p + c] * inv;
     }
     if (stats) {
-        stats[0] = n_closest, stats[1] = n_shadow, stats[2] = n_nodes, stats[3] = n_prims, stats[4] = max_stack;
+        stats[0] = n.closest, stats[1] = n.shadow, stats[2] = n.nodes, stats[3] = n.prims, stats[4] = n.max_stack;
         stats[5] = (uint64_t)hs.stats.n_nodes, stats[6] = (uint64_t)hs.stats.depth;
     }
     return TAKE_OK;
@@ -198,8 +266,9 @@ static void check_qnodes_w(const HostScene<float> &hs, const std::vector<NodeW<f
 
 extern "C" {
 const char *hostsim_last_error(void) { return g_err.c_str(); }
-// out: rows*W*3 Real (float for f32, double for f64); stats: 7 words (may be null)
+// out: rows*W*3 Real (float for f32, double for f64 and mixed); stats: 7 words (may be null)
 int hostsim_render(const TakeSceneDesc *desc, int precision, const TakeRenderOpts *opts, void *out, uint64_t *stats) {
+    if (precision == TAKE_PRECISION_MIXED) return render_t<double, true>(*desc, *opts, out, stats);
     return precision == TAKE_PRECISION_F64 ? render_t<double>(*desc, *opts, out, stats)
                                            : render_t<float>(*desc, *opts, out, stats);
 }
