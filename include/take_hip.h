@@ -113,7 +113,7 @@ typedef struct TakeMesh {
     const double *uvs;       /* n_vertices * 2, or NULL (mesh.uvs.empty())     */
     int32_t material_id;
     int32_t flags;           /* 0, or TAKE_MESH_DEVICE_ARRAYS: the four arrays live in device memory (a mesh that
-                                take_hip_mesh_from_ply decoded there) */
+                                take_hip_mesh_from_ply / _serialized / _obj decoded there) */
 } TakeMesh;
 #define TAKE_MESH_DEVICE_ARRAYS 1
 
@@ -432,6 +432,21 @@ int take_hip_mesh_from_serialized(const void *file_bytes, size_t n_bytes, int32_
                                   const double *inv_to_world, int32_t material_id, TakeMesh *out);
 int take_hip_mesh_from_serialized_file(const char *path, int32_t shape_index, const double *to_world,
                                        const double *inv_to_world, int32_t material_id, TakeMesh *out);
+/* Wavefront OBJ -> device mesh arrays: the reference's parse_obj (src/parse/parse_obj.cpp:118-203), to_world applied as
+ * parse_obj's get_vertex_id applies it (xform_point; normals through xform_normal(inv_to_world)).  The whole file is
+ * decoded on the device; the arrays are bit-identical to the reference's TriangleMesh.  Scope: `v x y z [w]` (w
+ * divides), `vt s t` (stored as (s, 1 - t)), `vn x y z` (normalized), `f` with 3 or 4 corners `v`, `v/vt`, `v//vn`,
+ * `v/vt/vn` (a quad is (v0, v1, v2), (v0, v2, v3)); every other line is ignored.  Vertices are deduplicated on the raw
+ * index triple in order of first use; a negative index is relative to its pool at the face's line (vt: pool + vt - 1,
+ * as the reference resolves it).  uvs / normals are NULL when no vertex has a vt / vn.
+ * TAKE_E_INVALID: a face with more than 4 corners (the reference's n-gon error) or fewer than 3, a vertex index 0, an
+ * index outside its pool at its line.  TAKE_E_INVALID with a message that starts with "unsupported": a token the
+ * reference's std::stoi would throw on, a number missing or outside [+-]?(d+(.d*)?|.d+)([eE][+-]?d+)?, a number out of
+ * the range of a double, or only some vertices with a vt (vn) — the caller keeps its host parser for those. */
+int take_hip_mesh_from_obj(const void *file_bytes, size_t n_bytes, const double *to_world, const double *inv_to_world,
+                           int32_t material_id, TakeMesh *out);
+int take_hip_mesh_from_obj_file(const char *path, const double *to_world, const double *inv_to_world, int32_t material_id,
+                                TakeMesh *out);
 /* copy a device-array mesh to host arrays the caller sized from n_vertices / n_faces (NULL = skip that array) */
 int take_hip_mesh_download(const TakeMesh *mesh, double *positions, int32_t *indices, double *normals, double *uvs);
 int take_hip_mesh_release(TakeMesh *mesh);

@@ -19,6 +19,10 @@
 #include <fcntl.h>
 #include <memory>
 #include <zlib.h>
+#include <atomic>
+#include <cerrno>
+#include <clocale>
+#include <locale.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -28,6 +32,7 @@
 #include "tk_build_gpu.h"
 #include "tk_kernels.h"
 #include "tk_ply.h"
+#include "tk_obj.h"
 
 using namespace tk;
 
@@ -1557,6 +1562,240 @@ int take_hip_mesh_from_serialized_file(const char *path, int32_t shape_index, co
     MappedFile mf(path);
     if (!mf.p) return fail(TAKE_E_INVALID, mf.err);
     return take_hip_mesh_from_serialized(mf.p, mf.n, shape_index, to_world, inv_to_world, material_id, out);
+}
+
+// ---- Wavefront OBJ (src/parse/parse_obj.cpp:118-203): the whole file decoded on the device (tk_obj.h) -------------
+}  // extern "C"
+namespace {
+template <class T> struct ScopedBuf : DevBuf<T> {
+    ~ScopedBuf() { this->release(); }
+};
+
+// the three scan phases of tk_obj.h; `up` leaves the total in bsum[nb] (bsum: nb + 1 elements)
+inline int64_t scan_tiles(int64_t n) { return (n + obj::SCAN_TILE - 1) / obj::SCAN_TILE; }
+template <class T, class F> void scan_up(const F &f, int64_t n, T *bsum, hipStream_t st) {
+    const int64_t nb = scan_tiles(n);
+    if (nb > 0) hipLaunchKernelGGL((obj::k_scan_reduce<T, F>), dim3((unsigned)nb), dim3(obj::SCAN_BLK), 0, st, f, n, bsum);
+    hipLaunchKernelGGL((obj::k_scan_blocks<T>), dim3(1), dim3(obj::SCAN_BLK), 0, st, bsum, nb);
+}
+template <class T, class F> void scan_down(const F &f, int64_t n, const T *bsum, hipStream_t st) {
+    const int64_t nb = scan_tiles(n);
+    if (nb > 0) hipLaunchKernelGGL((obj::k_scan_down<T, F>), dim3((unsigned)nb), dim3(obj::SCAN_BLK), 0, st, f, n, bsum);
+}
+inline dim3 grid_for(int64_t n, int blk) { return dim3((unsigned)std::max<int64_t>((n + blk - 1) / blk, 1)); }
+
+// the numbers the device left to the host: strtod in the "C" locale, what `ss >> Real` computes.  -> the file offset
+// of the first one out of the range of a double (the reference's stream fails on those), or -1
+int64_t convert_fixups(const uint8_t *file, const std::vector<obj::Fix> &fx, std::vector<double> &val) {
+    val.resize(fx.size());
+    static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+    std::atomic<int64_t> bad{INT64_MAX};
+    auto work = [&](size_t lo, size_t hi) {
+        std::string tok;
+        for (size_t k = lo; k < hi; k++) {
+            tok.assign((const char *)file + fx[k].off, fx[k].len);
+            errno = 0;
+            val[k] = strtod_l(tok.c_str(), nullptr, c_locale);
+            if (errno == ERANGE) {
+                int64_t cur = bad.load();
+                while ((int64_t)fx[k].off < cur && !bad.compare_exchange_weak(cur, (int64_t)fx[k].off)) {
+                }
+            }
+        }
+    };
+    const size_t nt = fx.size() < 65536 ? 1 : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < nt; t++) pool.emplace_back(work, fx.size() * t / nt, fx.size() * (t + 1) / nt);
+    work(0, fx.size() / nt);
+    for (auto &t : pool) t.join();
+    return bad.load() == INT64_MAX ? -1 : bad.load();
+}
+
+std::string obj_message(uint32_t code, int64_t line) {
+    const std::string at = "OBJ line " + std::to_string(line + 1) + ": ";
+    switch (code) {
+    case obj::S_UNSUPPORTED:
+        return "unsupported " + at + "a token the reference's parser would not read (std::stoi throws, or a number is missing "
+               "or not in the grammar [+-]?(d+(.d*)?|.d+)([eE][+-]?d+)?): keep the host parser";
+    case obj::S_FEW: return at + "a face with fewer than 3 corners";
+    case obj::S_V0: return at + "a vertex index 0";
+    case obj::S_RANGE: return at + "an index outside its pool as it stands at that line";
+    default: return at + "The object file contains n-gon (n>4) that we do not support.";
+    }
+}
+
+int decode_obj(const uint8_t *file, size_t n_bytes, const double *to_world, const double *inv_to_world, int32_t material_id,
+               TakeMesh *out) {
+    if (n_bytes >= ((size_t)1 << 31) - 1) return fail(TAKE_E_INVALID, "unsupported OBJ file: 2 GiB or larger");
+    const int64_t n = (int64_t)n_bytes;
+    ply::Mat4 X, Xi;
+    static const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::memcpy(X.m, to_world ? to_world : I, sizeof(I));
+    std::memcpy(Xi.m, inv_to_world ? inv_to_world : I, sizeof(I));
+    ScopedBuf<uint8_t> body, type;
+    ScopedBuf<int32_t> nl, bsum_i, owner, minseq, slot, rank;
+    ScopedBuf<obj::Cnt> pre, bsum_c;
+    ScopedBuf<double> raw, fixval;
+    ScopedBuf<obj::Corner> corners;
+    ScopedBuf<obj::Face> faces;
+    ScopedBuf<obj::Fix> fix;
+    ScopedBuf<unsigned int> nfix, counts;
+    ScopedBuf<unsigned long long> status;
+    TakeMesh m{};
+    m.material_id = material_id, m.flags = TAKE_MESH_DEVICE_ARRAYS;
+    auto bail = [&](int rc) {
+        free_mesh_arrays(&m);
+        return rc;
+    };
+    auto nomem = [&]() { return bail(fail(TAKE_E_NOMEM, "out of device memory for an OBJ mesh of " + std::to_string(n) + " bytes")); };
+    auto dev = [&](hipError_t e) { return bail(fail(TAKE_E_DEVICE, std::string("OBJ decode: ") + hipGetErrorString(e))); };
+    constexpr int BLK = 256;
+    PinnedUploads pin;
+    const hipStream_t st = pin.stream;
+    hipError_t e = hipSuccess;
+    // 1. the file -> HBM; '\n' positions
+    if (body.alloc((size_t)std::max<int64_t>(n, 1)) != hipSuccess || bsum_i.alloc(scan_tiles(std::max(n, (int64_t)1)) + 1) != hipSuccess ||
+        status.alloc(1) != hipSuccess || nfix.alloc(1) != hipSuccess || counts.alloc(2) != hipSuccess)
+        return nomem();
+    e = pin.copy(body.p, file, (size_t)n);
+    if (e == hipSuccess) e = hipMemsetAsync(status.p, 0xFF, sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(nfix.p, 0, sizeof(unsigned int), st);
+    if (e == hipSuccess) e = hipMemsetAsync(counts.p, 0, 2 * sizeof(unsigned int), st);
+    if (e != hipSuccess) return dev(e);
+    obj::NewlineF nf_{body.p, nullptr};
+    scan_up<int32_t>(nf_, n, bsum_i.p, st);
+    int32_t nnl = 0;
+    e = hipMemcpyAsync(&nnl, bsum_i.p + scan_tiles(n), sizeof(nnl), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev(e);
+    const int64_t nlines = (int64_t)nnl + 1;
+    if (nl.alloc(std::max(nnl, 1)) != hipSuccess || type.alloc(nlines) != hipSuccess || pre.alloc(nlines) != hipSuccess ||
+        bsum_c.alloc(scan_tiles(nlines) + 1) != hipSuccess)
+        return nomem();
+    nf_.nl = nl.p;
+    scan_down<int32_t>(nf_, n, bsum_i.p, st);
+    // 2. line types; 3. their scan
+    hipLaunchKernelGGL(obj::k_obj_classify, grid_for(nlines, BLK), dim3(BLK), 0, st, body.p, n, nl.p, (int64_t)nnl, type.p);
+    const obj::LineF lf{type.p, pre.p};
+    scan_up<obj::Cnt>(lf, nlines, bsum_c.p, st);
+    scan_down<obj::Cnt>(lf, nlines, bsum_c.p, st);
+    obj::Cnt T{};
+    e = hipMemcpyAsync(&T, bsum_c.p + scan_tiles(nlines), sizeof(T), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev(e);
+    if (T.c >= (1 << 28)) return bail(fail(TAKE_E_INVALID, "unsupported OBJ file: more than 2^28 face corners"));
+    if (to_world && !inv_to_world && T.vn > 0)
+        return bail(fail(TAKE_E_INVALID, "the file has normals: pass inverse(to_world) along with to_world"));
+    // 4. numbers, corners, faces
+    const int64_t off_vt = 4 * (int64_t)T.v, off_vn = off_vt + 2 * (int64_t)T.vt, n_raw = off_vn + 3 * (int64_t)T.vn;
+    if (raw.alloc(std::max<int64_t>(n_raw, 1)) != hipSuccess || fix.alloc(std::max<int64_t>(n_raw, 1)) != hipSuccess ||
+        corners.alloc(std::max(T.c, 1)) != hipSuccess || faces.alloc(std::max(T.f, 1)) != hipSuccess)
+        return nomem();
+    hipLaunchKernelGGL(obj::k_obj_parse, grid_for(nlines, BLK), dim3(BLK), 0, st, body.p, n, nl.p, (int64_t)nnl, type.p, pre.p,
+                       raw.p, off_vt, off_vn, corners.p, faces.p, fix.p, nfix.p, status.p);
+    unsigned int n_fix = 0;
+    e = hipMemcpyAsync(&n_fix, nfix.p, sizeof(n_fix), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev(e);
+    int64_t host_bad = -1;  // file offset of a number out of the range of a double
+    if (n_fix > 0) {
+        std::vector<obj::Fix> fx(n_fix);
+        std::vector<double> val;
+        e = hipMemcpy(fx.data(), fix.p, n_fix * sizeof(obj::Fix), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return dev(e);
+        host_bad = convert_fixups(file, fx, val);
+        if (fixval.alloc(n_fix) != hipSuccess) return nomem();
+        e = hipMemcpy(fixval.p, val.data(), n_fix * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return dev(e);
+        hipLaunchKernelGGL(obj::k_obj_patch, grid_for(n_fix, BLK), dim3(BLK), 0, st, fix.p, fixval.p, (int64_t)n_fix, raw.p);
+    }
+    // 5. deduplication on the raw triple
+    uint32_t cap = 64;
+    while (cap < 2 * (uint32_t)T.c) cap <<= 1;
+    if (owner.alloc(cap) != hipSuccess || minseq.alloc(cap) != hipSuccess || slot.alloc(std::max(T.c, 1)) != hipSuccess ||
+        rank.alloc(std::max(T.c, 1)) != hipSuccess)
+        return nomem();
+    e = hipMemsetAsync(owner.p, 0xFF, cap * sizeof(int32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(minseq.p, 0x7F, cap * sizeof(int32_t), st);
+    if (e != hipSuccess) return dev(e);
+    if (T.c > 0) hipLaunchKernelGGL(obj::k_obj_insert, grid_for(T.c, BLK), dim3(BLK), 0, st, corners.p, (int64_t)T.c, owner.p, minseq.p, cap - 1, slot.p);
+    const obj::FirstF ff{slot.p, minseq.p, rank.p};
+    scan_up<int32_t>(ff, T.c, bsum_i.p, st);  // (bsum_i has room: corners < bytes)
+    scan_down<int32_t>(ff, T.c, bsum_i.p, st);
+    int32_t nvert = 0;
+    e = hipMemcpyAsync(&nvert, bsum_i.p + scan_tiles(T.c), sizeof(nvert), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return dev(e);
+    // 6. the vertices, the triangles
+    const int64_t ntri = (int64_t)T.c - 2 * (int64_t)T.f;
+    m.n_vertices = nvert, m.n_faces = ntri;
+    auto dmalloc = [&](auto *&p, size_t count) -> bool {
+        void *q = nullptr;
+        if (count == 0) return true;
+        if (inject_alloc_failure() || hipMalloc(&q, count * sizeof(*p)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        p = (std::remove_reference_t<decltype(p)>)q;
+        return true;
+    };
+    double *pos = nullptr, *nrm = nullptr, *uv = nullptr;
+    int32_t *idx = nullptr;
+    const bool ok = dmalloc(pos, 3 * (size_t)nvert) && dmalloc(idx, 3 * (size_t)ntri) && (T.vn == 0 || dmalloc(nrm, 3 * (size_t)nvert)) &&
+                    (T.vt == 0 || dmalloc(uv, 2 * (size_t)nvert));
+    m.positions = pos, m.indices = idx, m.normals = nrm, m.uvs = uv;
+    if (!ok) return nomem();
+    if (T.c > 0)
+        hipLaunchKernelGGL(obj::k_obj_emit, grid_for(T.c, BLK), dim3(BLK), 0, st, corners.p, (int64_t)T.c, faces.p, slot.p, minseq.p,
+                           rank.p, raw.p, off_vt, off_vn, X, Xi, pos, nrm, uv, status.p, counts.p);
+    if (T.f > 0) hipLaunchKernelGGL(obj::k_obj_indices, grid_for(T.f, BLK), dim3(BLK), 0, st, faces.p, (int64_t)T.f, slot.p, minseq.p, rank.p, idx);
+    e = hipGetLastError();
+    unsigned long long stw = 0;
+    unsigned int cnt[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(&stw, status.p, sizeof(stw), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, counts.p, sizeof(cnt), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = pin.finish();
+    if (e != hipSuccess) return dev(e);
+    // the earliest line with a problem decides, as in the reference's loop
+    int64_t bad_line = stw == ~0ull ? INT64_MAX : (int64_t)(stw >> 8);
+    uint32_t code = (uint32_t)(stw & 0xFF);
+    if (host_bad >= 0) {
+        const int64_t line = (int64_t)std::count(file, file + host_bad, (uint8_t)'\n');
+        if (line < bad_line || (line == bad_line && code >= obj::S_UNSUPPORTED))
+            return bail(fail(TAKE_E_INVALID, "unsupported OBJ line " + std::to_string(line + 1) +
+                                                 ": a number outside the range of a double (the reference's stream fails on it)"));
+    }
+    if (bad_line != INT64_MAX) return bail(fail(TAKE_E_INVALID, obj_message(code, bad_line)));
+    // TakeMesh holds one uv / normal per position: all vertices have one, or none has
+    if (uv && cnt[0] == 0) (void)hipFree(uv), m.uvs = nullptr;
+    if (nrm && cnt[1] == 0) (void)hipFree(nrm), m.normals = nullptr;
+    if (cnt[0] != 0 && cnt[0] != (unsigned)nvert)
+        return bail(fail(TAKE_E_INVALID, "unsupported OBJ mesh: only some vertices have a texture coordinate (the reference's uvs would "
+                                         "not match its positions)"));
+    if (cnt[1] != 0 && cnt[1] != (unsigned)nvert)
+        return bail(fail(TAKE_E_INVALID, "unsupported OBJ mesh: only some vertices have a normal (the reference's normals would not "
+                                         "match its positions)"));
+    *out = m;
+    return TAKE_OK;
+}
+}  // namespace
+extern "C" {
+
+int take_hip_mesh_from_obj(const void *file_bytes, size_t n_bytes, const double *to_world, const double *inv_to_world,
+                           int32_t material_id, TakeMesh *out) {
+    if (!file_bytes || !out) return fail(TAKE_E_INVALID, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    return decode_obj((const uint8_t *)file_bytes, n_bytes, to_world, inv_to_world, material_id, out);
+}
+
+int take_hip_mesh_from_obj_file(const char *path, const double *to_world, const double *inv_to_world, int32_t material_id, TakeMesh *out) {
+    if (!path || !out) return fail(TAKE_E_INVALID, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    MappedFile mf(path);
+    if (!mf.p) return fail(TAKE_E_INVALID, mf.err);
+    return take_hip_mesh_from_obj(mf.p, mf.n, to_world, inv_to_world, material_id, out);
 }
 
 int take_hip_mesh_download(const TakeMesh *m, double *positions, int32_t *indices, double *normals, double *uvs) {

@@ -259,10 +259,32 @@ struct Mat4 {
     double m[16];  // row-major: m[4 * i + j] = Matrix4x4(i, j)
 };
 
+// xform_point (src/transform.cpp:79-87): homogeneous multiply, then times 1 / w
+TK_HD void xform_point(const Mat4 &X, double x, double y, double z, double *out) {
+    const double *m = X.m;
+    const double tx = m[0] * x + m[1] * y + m[2] * z + m[3];
+    const double ty = m[4] * x + m[5] * y + m[6] * z + m[7];
+    const double tz = m[8] * x + m[9] * y + m[10] * z + m[11];
+    const double tw = m[12] * x + m[13] * y + m[14] * z + m[15];
+    const double inv_w = 1.0 / tw;
+    out[0] = tx * inv_w, out[1] = ty * inv_w, out[2] = tz * inv_w;
+}
+// normalize() (src/vector.h:250-257): zero vector when the length is not positive; Vector3 / Real multiplies by the
+// reciprocal (src/vector.h:194-197)
+TK_HD void normalize3(double x, double y, double z, double *out) {
+    const double l = sqrt(x * x + y * y + z * z);
+    const double inv_l = 1.0 / l;
+    if (l <= 0) out[0] = 0, out[1] = 0, out[2] = 0;
+    else out[0] = x * inv_l, out[1] = y * inv_l, out[2] = z * inv_l;
+}
+// xform_normal (src/transform.cpp:95-100) with the INVERSE matrix, transposed access, then normalize()
+TK_HD void xform_normal(const Mat4 &Xi, double x, double y, double z, double *out) {
+    const double *m = Xi.m;
+    normalize3(m[0] * x + m[4] * y + m[8] * z, m[1] * x + m[5] * y + m[9] * z, m[2] * x + m[6] * y + m[10] * z, out);
+}
+
 #if defined(__HIPCC__)
-// positions: xform_point (src/transform.cpp:79-87) — homogeneous multiply, then times 1 / w
-// normals:   xform_normal (src/transform.cpp:95-100) with the INVERSE matrix, transposed access, then normalize()
-//            (src/vector.h:250-257: zero vector when the length is not positive)
+// positions: xform_point; normals: xform_normal with the reference's inverse(to_world)
 __global__ void k_ply_vertices(const uint8_t *file, Layout L, Mat4 X, Mat4 Xi, double *pos, double *nrm, double *uv) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L.n_vertices) return;
@@ -270,26 +292,13 @@ __global__ void k_ply_vertices(const uint8_t *file, Layout L, Mat4 X, Mat4 Xi, d
     {
         const double x = load_real(row + L.pos_off[0], L.pos_type), y = load_real(row + L.pos_off[1], L.pos_type),
                      z = load_real(row + L.pos_off[2], L.pos_type);
-        const double *m = X.m;
-        const double tx = m[0] * x + m[1] * y + m[2] * z + m[3];
-        const double ty = m[4] * x + m[5] * y + m[6] * z + m[7];
-        const double tz = m[8] * x + m[9] * y + m[10] * z + m[11];
-        const double tw = m[12] * x + m[13] * y + m[14] * z + m[15];
-        const double inv_w = 1.0 / tw;
-        pos[3 * i + 0] = tx * inv_w, pos[3 * i + 1] = ty * inv_w, pos[3 * i + 2] = tz * inv_w;
+        xform_point(X, x, y, z, pos + 3 * i);
     }
     if (nrm) {
         const uint8_t *nrow = file + L.nrm_base + i * (int64_t)L.nrm_stride;
         const double x = load_real(nrow + L.nrm_off[0], L.nrm_type), y = load_real(nrow + L.nrm_off[1], L.nrm_type),
                      z = load_real(nrow + L.nrm_off[2], L.nrm_type);
-        const double *m = Xi.m;
-        const double nx = m[0] * x + m[4] * y + m[8] * z;
-        const double ny = m[1] * x + m[5] * y + m[9] * z;
-        const double nz = m[2] * x + m[6] * y + m[10] * z;
-        const double l = sqrt(nx * nx + ny * ny + nz * nz);
-        const double inv_l = 1.0 / l;  // (Vector3 / Real multiplies by the reciprocal: src/vector.h:194-197)
-        if (l <= 0) nrm[3 * i + 0] = 0, nrm[3 * i + 1] = 0, nrm[3 * i + 2] = 0;
-        else nrm[3 * i + 0] = nx * inv_l, nrm[3 * i + 1] = ny * inv_l, nrm[3 * i + 2] = nz * inv_l;
+        xform_normal(Xi, x, y, z, nrm + 3 * i);
     }
     if (uv) {
         const uint8_t *urow = file + L.uv_base + i * (int64_t)L.uv_stride;
