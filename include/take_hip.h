@@ -447,6 +447,17 @@ int take_hip_mesh_from_obj(const void *file_bytes, size_t n_bytes, const double 
                            int32_t material_id, TakeMesh *out);
 int take_hip_mesh_from_obj_file(const char *path, const double *to_world, const double *inv_to_world, int32_t material_id,
                                 TakeMesh *out);
+/* compute_normals (src/compute_normals.cpp:12-47): Nelson Max angle-weighted vertex normals, what parse_scene
+ * puts into a mesh loaded without normals unless the shape sets faceNormals. Device-array mesh
+ * (TAKE_MESH_DEVICE_ARRAYS) whose normals are NULL: on success mesh->normals is a library-owned device array
+ * (freed by take_hip_mesh_release). A mesh that already has normals, or host arrays: TAKE_E_INVALID.
+ * The sums run in the reference's order (a stable sort, no atomics): the result is deterministic, and differs from
+ * the reference's only where the device asin differs from the C library's in the last bit.  An index outside
+ * [0, n_vertices), or more than INT32_MAX corners: TAKE_E_INVALID. */
+int take_hip_mesh_compute_normals(TakeMesh *mesh);
+/* the same on host arrays (upload, the same kernels, download): normals_out = n_vertices * 3 doubles */
+int take_hip_compute_normals(const double *positions, int64_t n_vertices, const int32_t *indices, int64_t n_faces,
+                             double *normals_out);
 /* copy a device-array mesh to host arrays the caller sized from n_vertices / n_faces (NULL = skip that array) */
 int take_hip_mesh_download(const TakeMesh *mesh, double *positions, int32_t *indices, double *normals, double *uvs);
 int take_hip_mesh_release(TakeMesh *mesh);

@@ -25,7 +25,7 @@ EXPORTS = [
     "take_hip_group_size", "take_hip_group_get_counters", "take_hip_pack_exr_scanlines", "take_hip_render_exr_scanlines",
     "take_hip_ply_layout", "take_hip_mesh_from_ply", "take_hip_mesh_from_ply_file",
     "take_hip_mesh_from_serialized", "take_hip_mesh_from_serialized_file", "take_hip_mesh_download", "take_hip_mesh_release",
-    "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file",
+    "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
 ]
 
 
@@ -89,6 +89,8 @@ def lib():
         L.take_hip_mesh_from_obj_file.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(D.TakeMesh)]
         L.take_hip_mesh_download.argtypes = [C.POINTER(D.TakeMesh), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.take_hip_mesh_release.argtypes = [C.POINTER(D.TakeMesh)]
+        L.take_hip_mesh_compute_normals.argtypes = [C.POINTER(D.TakeMesh)]
+        L.take_hip_compute_normals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -111,6 +113,16 @@ def ply_layout(data):
     return {k: getattr(out, k) for k, _ in D.TakePlyLayout._fields_ if k != "reserved"}
 
 
+def compute_normals(positions, indices):
+    """the reference's compute_normals (src/compute_normals.cpp:12-47) on the device, for host arrays: (nv, 3) positions,
+    (nf, 3) vertex indices -> (nv, 3) angle-weighted unit vertex normals ((0, 0, 0) where the sum vanishes)"""
+    pos = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    out = np.zeros_like(pos)
+    _check(lib().take_hip_compute_normals(pos.ctypes.data, pos.shape[0], idx.ctypes.data, idx.shape[0], out.ctypes.data))
+    return out
+
+
 class DeviceMesh:
     """A triangle mesh decoded from a binary PLY file, a Mitsuba `.serialized` file or a Wavefront OBJ file ON the device
     (take_hip_mesh_from_ply / _from_serialized / _from_obj: replace the reference's parse_ply,
@@ -120,13 +132,18 @@ class DeviceMesh:
     None = told from the source: a path ending in `.obj` (any case) is OBJ, otherwise the first bytes decide (`ply` /
     anything else = serialized, whose sub-mesh `shape_index` picks); bytes holding an OBJ file need format="obj".
     to_world: 4x4 (the reference's Matrix4x4); inv_to_world: the caller's inverse of it (the reference passes its own
-    `inverse(to_world)`), default numpy's."""
+    `inverse(to_world)`), default numpy's.  `normals`: None = the file's normals, or none; "scene" = what parse_scene
+    does for a shape without faceNormals: the file's normals if it has any, else compute_normals' (computed on the
+    device, compute_normals())."""
 
     FORMATS = (None, "ply", "serialized", "obj")
+    NORMALS = (None, "scene")
 
-    def __init__(self, source, material_id=0, to_world=None, inv_to_world=None, shape_index=0, format=None):
+    def __init__(self, source, material_id=0, to_world=None, inv_to_world=None, shape_index=0, format=None, normals=None):
         if format not in self.FORMATS:
             raise ValueError(f"format must be one of {self.FORMATS}, not {format!r}")
+        if normals not in self.NORMALS:
+            raise ValueError(f"normals must be one of {self.NORMALS}, not {normals!r}")
         self.c = D.TakeMesh()
         xw = xi = None
         if to_world is not None:
@@ -158,9 +175,17 @@ class DeviceMesh:
             else:
                 _check(lib().take_hip_mesh_from_serialized_file(path, int(shape_index), a, b, int(material_id), C.byref(self.c)))
         self.material_id = int(material_id)
+        if normals == "scene" and not self.c.normals:
+            self.compute_normals()
 
     n_vertices = property(lambda self: int(self.c.n_vertices))
     n_faces = property(lambda self: int(self.c.n_faces))
+
+    def compute_normals(self):
+        """fill the mesh's missing normals in place: the reference's compute_normals on the device
+        (take_hip_mesh_compute_normals); a mesh that has normals already is refused"""
+        _check(lib().take_hip_mesh_compute_normals(C.byref(self.c)))
+        return self
 
     def download(self):
         """-> scene.Mesh with host copies of the arrays (tests; the render path never needs it)"""

@@ -33,6 +33,7 @@
 #include "tk_kernels.h"
 #include "tk_ply.h"
 #include "tk_obj.h"
+#include "tk_normals.h"
 
 using namespace tk;
 
@@ -1778,8 +1779,114 @@ int decode_obj(const uint8_t *file, size_t n_bytes, const double *to_world, cons
     *out = m;
     return TAKE_OK;
 }
+
+// ---- compute_normals (src/compute_normals.cpp:12-47) on device arrays (tk_normals.h) -------------------------------
+int normals_counts(int64_t nv, int64_t nf) {
+    if (nv < 0 || nf < 0) return fail(TAKE_E_INVALID, "compute_normals: negative vertex or face count");
+    if (nf > INT32_MAX / 3)
+        return fail(TAKE_E_INVALID, "compute_normals: " + std::to_string(nf) + " faces are more than INT32_MAX corners (the kernels "
+                                    "index corners with 32-bit integers)");
+    if (nv >= INT32_MAX) return fail(TAKE_E_INVALID, "compute_normals: more vertices than 32-bit indices can name");
+    return TAKE_OK;
+}
+
+// d_out: 3 * nv doubles, every one written.  Synchronous on `st`.
+int normals_on_device(const double *d_pos, int64_t nv, const int32_t *d_idx, int64_t nf, double *d_out, hipStream_t st) {
+    const int rc = normals_counts(nv, nf);
+    if (rc != TAKE_OK) return rc;
+    const int64_t nc = 3 * nf;
+    const int64_t heavy_cap = std::max<int64_t>(1, std::min<int64_t>(nv, nc / (nrm::HEAVY + 1)));
+    ScopedBuf<double> contrib;
+    ScopedBuf<uint32_t> keys, keys_s, status;
+    ScopedBuf<int32_t> vals, vals_s, begin, end, heavy;
+    ScopedBuf<char> temp;
+    if (contrib.alloc(3 * (size_t)nc) != hipSuccess || keys.alloc((size_t)nc) != hipSuccess || keys_s.alloc((size_t)nc) != hipSuccess ||
+        vals.alloc((size_t)nc) != hipSuccess || vals_s.alloc((size_t)nc) != hipSuccess || begin.alloc((size_t)nv) != hipSuccess ||
+        end.alloc((size_t)nv) != hipSuccess || heavy.alloc((size_t)heavy_cap) != hipSuccess || status.alloc(2) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for compute_normals on " + std::to_string(nf) + " faces");
+    // the sort keys: vertex indices and the "adds nothing" key nv
+    const int end_bit = std::max(1, 32 - __builtin_clz((uint32_t)std::max<int64_t>(nv, 1)));
+    size_t temp_bytes = 0;
+    if (nc > 0) {
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)nc, 0, end_bit, st));
+        if (temp.alloc(std::max<size_t>(temp_bytes, 1)) != hipSuccess)
+            return fail(TAKE_E_NOMEM, "out of device memory for compute_normals' sort");
+    }
+    const int B = nrm::BLK;
+    HIP_TRY(hipMemsetAsync(status.p, 0, status.bytes(), st));
+    if (nv > 0) {
+        HIP_TRY(hipMemsetAsync(begin.p, 0, begin.bytes(), st));
+        HIP_TRY(hipMemsetAsync(end.p, 0, end.bytes(), st));
+    }
+    if (nc > 0) {
+        hipLaunchKernelGGL(nrm::k_nrm_faces, grid_for(nf, B), dim3(B), 0, st, d_pos, d_idx, nf, nv, contrib.p, keys.p, vals.p, status.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)nc, 0, end_bit, st));
+        hipLaunchKernelGGL(nrm::k_nrm_bounds, grid_for(nc, B), dim3(B), 0, st, keys_s.p, nc, (uint32_t)nv, begin.p, end.p, heavy.p, status.p);
+    }
+    if (nv > 0) {
+        hipLaunchKernelGGL(nrm::k_nrm_vertices, grid_for(nv, B), dim3(B), 0, st, contrib.p, vals_s.p, begin.p, end.p, nv, d_out);
+        const int64_t heavy_waves = std::min<int64_t>(heavy_cap, 1024);
+        if (nc > nrm::HEAVY)
+            hipLaunchKernelGGL(nrm::k_nrm_heavy, grid_for(heavy_waves * 64, B), dim3(B), 0, st, contrib.p, vals_s.p, begin.p, end.p,
+                               heavy.p, status.p, d_out);
+    }
+    HIP_TRY(hipGetLastError());
+    uint32_t st_h[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(st_h, status.p, sizeof(st_h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (st_h[0] & 1) return fail(TAKE_E_INVALID, "compute_normals: a face indexes outside the vertex array [0, " + std::to_string(nv) + ")");
+    return TAKE_OK;
+}
 }  // namespace
 extern "C" {
+
+int take_hip_mesh_compute_normals(TakeMesh *mesh) {
+    if (!mesh) return fail(TAKE_E_INVALID, "null mesh");
+    if (!(mesh->flags & TAKE_MESH_DEVICE_ARRAYS))
+        return fail(TAKE_E_INVALID, "compute_normals: not a device-array mesh (host arrays: take_hip_compute_normals)");
+    if (mesh->normals) return fail(TAKE_E_INVALID, "compute_normals: the mesh has normals already");
+    int rc = normals_counts(mesh->n_vertices, mesh->n_faces);
+    if (rc != TAKE_OK) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    double *nrm = nullptr;
+    if (mesh->n_vertices > 0) {
+        if (inject_alloc_failure() || hipMalloc((void **)&nrm, 3 * sizeof(double) * (size_t)mesh->n_vertices) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TAKE_E_NOMEM, "out of device memory for the normals of a " + std::to_string(mesh->n_vertices) + "-vertex mesh");
+        }
+    }
+    rc = normals_on_device(mesh->positions, mesh->n_vertices, mesh->indices, mesh->n_faces, nrm, nullptr);
+    if (rc != TAKE_OK) {
+        if (nrm) (void)hipFree(nrm);
+        return rc;
+    }
+    mesh->normals = nrm;
+    return TAKE_OK;
+}
+
+int take_hip_compute_normals(const double *positions, int64_t n_vertices, const int32_t *indices, int64_t n_faces,
+                             double *normals_out) {
+    int rc = normals_counts(n_vertices, n_faces);
+    if (rc != TAKE_OK) return rc;
+    if ((n_vertices > 0 && (!positions || !normals_out)) || (n_faces > 0 && !indices)) return fail(TAKE_E_INVALID, "null argument");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    ScopedBuf<double> pos, out;
+    ScopedBuf<int32_t> idx;
+    if (pos.alloc(3 * (size_t)n_vertices) != hipSuccess || out.alloc(3 * (size_t)n_vertices) != hipSuccess ||
+        idx.alloc(3 * (size_t)n_faces) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for compute_normals on " + std::to_string(n_faces) + " faces");
+    PinnedUploads pin;
+    HIP_TRY(pin.copy(pos.p, positions, pos.bytes()));
+    HIP_TRY(pin.copy(idx.p, indices, idx.bytes()));
+    rc = normals_on_device(pos.p, n_vertices, idx.p, n_faces, out.p, pin.stream);
+    HIP_TRY(pin.finish());
+    if (rc != TAKE_OK) return rc;
+    if (out.n) HIP_TRY(hipMemcpy(normals_out, out.p, out.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
 
 int take_hip_mesh_from_obj(const void *file_bytes, size_t n_bytes, const double *to_world, const double *inv_to_world,
                            int32_t material_id, TakeMesh *out) {
