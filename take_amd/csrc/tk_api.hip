@@ -1,7 +1,8 @@
 // tk_api.hip — implementation of the C ABI of include/take_hip.h: scene upload, the wavefront render loop,
-// the trace hooks.  Host code here only orchestrates: every per-sample operation runs in the kernels of
+// the trace hooks, scene groups.  Host code here only orchestrates: every per-sample operation runs in the kernels of
 // tk_kernels.h.  There is no CPU rendering path in this library: without a HIP device every entry point
-// returns TAKE_E_NO_GPU.
+// returns TAKE_E_NO_GPU.  The mesh entry points (PLY, serialized, OBJ, compute_normals) are tk_mesh.hip; the
+// plumbing both units share is tk_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,127 +10,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include <fcntl.h>
-#include <memory>
-#include <zlib.h>
-#include <atomic>
-#include <cerrno>
-#include <clocale>
-#include <locale.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include "take_hip.h"
+#include "tk_host.h"
 #include "tk_host_scene.h"
 #include "tk_build_gpu.h"
 #include "tk_kernels.h"
-#include "tk_ply.h"
-#include "tk_obj.h"
-#include "tk_normals.h"
 
 using namespace tk;
+using namespace tk_host;
 
 namespace {
-
-thread_local std::string g_error;
-int fail(int code, const std::string &msg) {
-    g_error = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(TAKE_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));             \
-    } while (0)
-
-// Fault injection for the allocation-failure tests (tests/test_gpu_robustness.py): TAKE_HIP_FAIL_ALLOC=<k> makes the
-// k-th device allocation after the variable was (re)set fail with hipErrorOutOfMemory.  A real out-of-memory cannot
-// be provoked reliably from a test: the driver over-commits, a 300 GB request on a 288 GB device succeeded.
-// (allocations happen on several host threads at once — one per shard of a scene group — hence the lock)
-inline bool inject_alloc_failure() {
-    static std::mutex mu;
-    static std::string seen;
-    static long calls = 0;
-    const char *e = std::getenv("TAKE_HIP_FAIL_ALLOC");
-    std::lock_guard<std::mutex> lock(mu);
-    if (!e || !*e) {
-        seen.clear();
-        return false;
-    }
-    if (seen != e) seen = e, calls = 0;
-    return ++calls == std::atol(e);
-}
-
-// Host -> device copies of the caller's large arrays (mesh positions, shape arrays) for the device-side scene build
-// (SURVEY.md §8(f)2): the pages are pinned IN PLACE (hipHostRegister) so that the DMA engine reads the caller's memory
-// directly — no bounce through the runtime's staging buffers — and the copies of all arrays are in flight together;
-// the registrations are dropped once the stream has drained.  Arrays below 4 MiB, and memory that cannot be
-// registered, take the ordinary pageable path.  TAKE_HIP_PINNED_UPLOAD=0 turns the registration off (A/B runs).
-struct PinnedUploads {
-    hipStream_t stream = nullptr;
-    std::vector<void *> regs;
-    size_t pinned_bytes = 0, plain_bytes = 0;
-    bool enabled = !(std::getenv("TAKE_HIP_PINNED_UPLOAD") && std::atoi(std::getenv("TAKE_HIP_PINNED_UPLOAD")) == 0);
-    hipError_t copy(void *dst, const void *src, size_t bytes) {
-        if (bytes == 0) return hipSuccess;
-        if (enabled && bytes >= ((size_t)4 << 20)) {
-            if (hipHostRegister(const_cast<void *>(src), bytes, hipHostRegisterDefault) == hipSuccess) {
-                regs.push_back(const_cast<void *>(src));
-                pinned_bytes += bytes;
-            } else {
-                (void)hipGetLastError();  // (already registered, read-only mapping, ...): pageable copy
-                plain_bytes += bytes;
-            }
-        } else {
-            plain_bytes += bytes;
-        }
-        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
-    }
-    hipError_t finish() {
-        const hipError_t e = hipStreamSynchronize(stream);
-        for (void *p : regs) (void)hipHostUnregister(p);
-        regs.clear();
-        return e;
-    }
-    ~PinnedUploads() { (void)finish(); }
-};
-
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        release();  // p = nullptr, n = 0: the state a failed allocation leaves behind
-        if (count == 0) return hipSuccess;
-        const hipError_t e = inject_alloc_failure() ? hipErrorOutOfMemory : hipMalloc((void **)&p, count * sizeof(T));
-        if (e != hipSuccess) {
-            p = nullptr;
-            (void)hipGetLastError();  // the error is reported through the return value, not left sticky
-            return e;
-        }
-        n = count;
-        return hipSuccess;
-    }
-    hipError_t upload(const std::vector<T> &v) {
-        hipError_t e = alloc(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
 
 struct EventPool {
     std::vector<hipEvent_t> ev;
@@ -254,14 +150,6 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     DevBuf<int2> child;
     DevBuf<char> temp;
     DevBuf<double> acc;
-    struct Cleanup {
-        std::function<void()> f;
-        ~Cleanup() { f(); }
-    } cleanup{[&] {
-        pb.release(), lbox.release(), ibox.release(), keys.release(), vals.release(), keys_s.release(), vals_s.release();
-        lkey.release(), scene_ord.release(), parent_i.release(), parent_l.release(), flag.release();
-        frontier[0].release(), frontier[1].release(), lvl.release(), child.release(), temp.release(), acc.release();
-    }};
     HIP_TRY(pb.alloc(n));
     HIP_TRY(keys.alloc(n));
     HIP_TRY(vals.alloc(n));
@@ -343,8 +231,7 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     HIP_TRY(prims_sorted.alloc(n));
     hipLaunchKernelGGL((k_permute<PrimRec<float>>), grid(n), blk, 0, stream, sc.prims.p, vals_s.p, n, prims_sorted.p);
     HIP_TRY(hipStreamSynchronize(stream));
-    sc.prims.release();
-    sc.prims = prims_sorted;  // DevBuf is a plain handle: ownership moves
+    sc.prims = std::move(prims_sorted);  // (frees the shape-order records)
     HIP_TRY(hipGetLastError());
     return TAKE_OK;
 }
@@ -531,10 +418,6 @@ int make_prims_on_device(SceneT<float> &sc, const TakeSceneDesc &d, const double
     DevBuf<int32_t> d_kind, d_ref, d_face, d_al;
     DevBuf<MeshSrc> d_ms;
     DevBuf<SphereSrc> d_ss;
-    struct Cleanup {
-        std::function<void()> f;
-        ~Cleanup() { f(); }
-    } cleanup{[&] { d_pos.release(), d_kind.release(), d_ref.release(), d_face.release(), d_al.release(), d_ms.release(), d_ss.release(); }};
     HIP_TRY(d_pos.alloc(3 * (size_t)std::max<int64_t>(nv, 1)));
     PinnedUploads pin;
     for (int i = 0; i < d.n_meshes; i++) {
@@ -1270,24 +1153,15 @@ template <class R> int trace_host(TakeScene *ts, const void *rays, int64_t n, vo
     DevBuf<HitAoS<R>> d_hits;
     DevBuf<int32_t> d_occ;
     HIP_TRY(d_rays.alloc(n));
-    int rc = TAKE_OK;
-    do {
-        if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess) {
-            rc = fail(TAKE_E_DEVICE, "ray upload failed");
-            break;
-        }
-        if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) {
-            rc = fail(TAKE_E_NOMEM, "hit buffer allocation failed");
-            break;
-        }
-        rc = trace_impl<R>(ts, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
-        if (rc) break;
-        hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
-                           : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(TAKE_E_DEVICE, "hit download failed");
-    } while (0);
-    d_rays.release(), d_hits.release(), d_occ.release();
-    return rc;
+    if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "ray upload failed");
+    if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) return fail(TAKE_E_NOMEM, "hit buffer allocation failed");
+    const int rc = trace_impl<R>(ts, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
+    if (rc) return rc;
+    hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
+                       : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(TAKE_E_DEVICE, "hit download failed");
+    return TAKE_OK;
 }
 
 // A scene lives on the device that was current when it was created; every entry point that touches it makes that
@@ -1308,125 +1182,6 @@ struct DeviceGuard {
     DeviceGuard guard_((ts)->device);                                                                 \
     if (!guard_.ok) return fail(TAKE_E_DEVICE, "cannot make the scene's device current")
 
-int check_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(TAKE_E_NO_GPU, "no HIP device visible: libtake_hip has no CPU path");
-    return n;
-}
-
-}  // namespace
-
-// ---- PLY -> device mesh arrays (tk_ply.h) --------------------------------------------------------------------------
-namespace {
-void fill_layout(const ply::Layout &L, TakePlyLayout *o) {
-    std::memset(o, 0, sizeof(*o));
-    o->n_vertices = L.n_vertices, o->n_faces = L.n_faces;
-    o->vertex_offset = L.vertex_off, o->face_offset = L.face_off;
-    o->vertex_stride = L.vertex_stride, o->face_stride = L.face_stride;
-    o->has_normals = L.nrm_type != ply::T_NONE, o->has_uvs = L.uv_type != ply::T_NONE;
-    o->position_is_f64 = L.pos_type == ply::T_F64, o->index_bytes = ply::type_size(L.index_type);
-    o->header_bytes = L.header_bytes;
-}
-
-// a file, memory-mapped read-only (the body is read once: by the copy to the device, or by the inflater)
-struct MappedFile {
-    void *p = nullptr;
-    size_t n = 0;
-    std::string err;
-    explicit MappedFile(const char *path) {
-        const int fd = open(path, O_RDONLY);
-        if (fd < 0) {
-            err = std::string("cannot open ") + path;
-            return;
-        }
-        struct stat sb;
-        if (fstat(fd, &sb) != 0 || sb.st_size <= 0) {
-            close(fd);
-            err = std::string("cannot read ") + path;
-            return;
-        }
-        void *q = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-        close(fd);
-        if (q == MAP_FAILED) {
-            err = std::string("cannot map ") + path;
-            return;
-        }
-        (void)madvise(q, (size_t)sb.st_size, MADV_SEQUENTIAL);
-        p = q, n = (size_t)sb.st_size;
-    }
-    ~MappedFile() {
-        if (p) munmap(p, n);
-    }
-    MappedFile(const MappedFile &) = delete;
-    MappedFile &operator=(const MappedFile &) = delete;
-};
-
-void free_mesh_arrays(TakeMesh *m) {
-    if (m->positions) (void)hipFree(const_cast<double *>(m->positions));
-    if (m->indices) (void)hipFree(const_cast<int32_t *>(m->indices));
-    if (m->normals) (void)hipFree(const_cast<double *>(m->normals));
-    if (m->uvs) (void)hipFree(const_cast<double *>(m->uvs));
-    std::memset(m, 0, sizeof(*m));
-}
-
-// body (host) -> HBM, then the two decode kernels (tk_ply.h); D's offsets are relative to `host_body`
-int decode_mesh_body(const uint8_t *host_body, const ply::Layout &D, const double *to_world, const double *inv_to_world,
-                     int32_t material_id, const char *what, TakeMesh *out) {
-    ply::Mat4 X, Xi;
-    static const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::memcpy(X.m, to_world ? to_world : I, sizeof(I));
-    std::memcpy(Xi.m, inv_to_world ? inv_to_world : I, sizeof(I));
-    if (to_world && !inv_to_world && D.nrm_type != ply::T_NONE)
-        return fail(TAKE_E_INVALID, "the file has normals: pass inverse(to_world) along with to_world");
-    DevBuf<uint8_t> body;
-    DevBuf<int32_t> status;
-    TakeMesh m{};
-    m.n_vertices = D.n_vertices, m.n_faces = D.n_faces, m.material_id = material_id, m.flags = TAKE_MESH_DEVICE_ARRAYS;
-    auto bail = [&](int rc) {
-        body.release(), status.release();
-        free_mesh_arrays(&m);
-        return rc;
-    };
-    auto dmalloc = [&](auto *&p, size_t count) -> bool {
-        void *q = nullptr;
-        if (count == 0) return true;
-        if (inject_alloc_failure() || hipMalloc(&q, count * sizeof(*p)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        p = (std::remove_reference_t<decltype(p)>)q;
-        return true;
-    };
-    double *pos = nullptr, *nrm = nullptr, *uv = nullptr;
-    int32_t *idx = nullptr;
-    const bool ok = body.alloc((size_t)std::max<int64_t>(D.end_off, 1)) == hipSuccess && status.alloc(1) == hipSuccess &&
-                    dmalloc(pos, 3 * (size_t)D.n_vertices) && dmalloc(idx, 3 * (size_t)D.n_faces) &&
-                    (D.nrm_type == ply::T_NONE || dmalloc(nrm, 3 * (size_t)D.n_vertices)) &&
-                    (D.uv_type == ply::T_NONE || dmalloc(uv, 2 * (size_t)D.n_vertices));
-    m.positions = pos, m.indices = idx, m.normals = nrm, m.uvs = uv;
-    if (!ok) return bail(fail(TAKE_E_NOMEM, "out of device memory for a " + std::to_string(D.n_faces) + "-face " + what + " mesh"));
-    {
-        PinnedUploads pin;
-        hipError_t e = pin.copy(body.p, host_body, (size_t)D.end_off);
-        if (e == hipSuccess) e = hipMemsetAsync(status.p, 0, sizeof(int32_t), pin.stream);
-        constexpr int BLK = 256;
-        if (e == hipSuccess && D.n_vertices > 0)
-            hipLaunchKernelGGL(ply::k_ply_vertices, dim3((unsigned)((D.n_vertices + BLK - 1) / BLK)), dim3(BLK), 0, pin.stream, body.p, D, X, Xi, pos, nrm, uv);
-        if (e == hipSuccess && D.n_faces > 0)
-            hipLaunchKernelGGL(ply::k_ply_faces, dim3((unsigned)((D.n_faces + BLK - 1) / BLK)), dim3(BLK), 0, pin.stream, body.p, D, idx, status.p);
-        if (e == hipSuccess) e = hipGetLastError();
-        int32_t st = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&st, status.p, sizeof(st), hipMemcpyDeviceToHost, pin.stream);
-        if (e == hipSuccess) e = pin.finish();
-        if (e != hipSuccess) return bail(fail(TAKE_E_DEVICE, std::string(what) + " decode: " + hipGetErrorString(e)));
-        if (st & 1) return bail(fail(TAKE_E_INVALID, std::string("a face of the ") + what + " file is not a triangle (the reference reads three indices per face)"));
-        if (st & 2) return bail(fail(TAKE_E_INVALID, std::string("a face of the ") + what + " file indexes past its vertex array"));
-    }
-    body.release(), status.release();
-    *out = m;
-    return TAKE_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -1434,495 +1189,6 @@ extern "C" {
 const char *take_hip_last_error(void) { return g_error.c_str(); }
 int take_hip_abi_version(void) { return TAKE_HIP_ABI_VERSION; }
 int take_hip_device_count(void) { return check_device(); }
-
-int take_hip_ply_layout(const void *file_bytes, size_t n_bytes, TakePlyLayout *out) {
-    if (!file_bytes || !out) return fail(TAKE_E_INVALID, "null argument");
-    ply::Layout L;
-    const std::string err = ply::parse_header((const uint8_t *)file_bytes, n_bytes, L);
-    if (!err.empty()) return fail(TAKE_E_INVALID, err);
-    fill_layout(L, out);
-    return TAKE_OK;
-}
-
-int take_hip_mesh_from_ply(const void *file_bytes, size_t n_bytes, const double *to_world, const double *inv_to_world,
-                           int32_t material_id, TakeMesh *out) {
-    if (!file_bytes || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    ply::Layout L;
-    const std::string err = ply::parse_header((const uint8_t *)file_bytes, n_bytes, L);
-    if (!err.empty()) return fail(TAKE_E_INVALID, err);
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    // the body as it lies in the file: one copy, from the first to the last byte the two elements span
-    const int64_t lo = std::min(L.vertex_off, L.face_off);
-    ply::Layout D = L;  // offsets relative to the copied span
-    D.vertex_off -= lo, D.face_off -= lo, D.nrm_base -= lo, D.uv_base -= lo, D.end_off -= lo;
-    return decode_mesh_body((const uint8_t *)file_bytes + lo, D, to_world, inv_to_world, material_id, "PLY", out);
-}
-
-// ---- Mitsuba serialized meshes (src/parse/parse_serialized.cpp:174-256): inflate on the host, decode on the device --
-namespace {
-struct Inflater {
-    z_stream z{};
-    bool open = false;
-    const uint8_t *src;
-    size_t left;
-    Inflater(const uint8_t *p, size_t n) : src(p), left(n) {
-        open = inflateInit2(&z, 15) == Z_OK;  // (windowBits 15: parse_serialized.cpp:47)
-    }
-    ~Inflater() {
-        if (open) inflateEnd(&z);
-    }
-    // exactly `size` inflated bytes into dst, or what is wrong (the messages of ZStream::read, parse_serialized.cpp:60-104)
-    const char *read(void *dst, size_t size) {
-        uint8_t *out = (uint8_t *)dst;
-        while (size > 0) {
-            if (z.avail_in == 0) {
-                const size_t take = std::min<size_t>(left, (size_t)1 << 30);
-                if (take == 0) return "read less data than expected";
-                z.next_in = const_cast<uint8_t *>(src), z.avail_in = (uInt)take;
-                src += take, left -= take;
-            }
-            const size_t want = std::min<size_t>(size, (size_t)1 << 30);
-            z.next_out = out, z.avail_out = (uInt)want;
-            const int rv = inflate(&z, Z_NO_FLUSH);
-            if (rv == Z_STREAM_ERROR) return "inflate(): stream error";
-            if (rv == Z_NEED_DICT) return "inflate(): need dictionary";
-            if (rv == Z_DATA_ERROR) return "inflate(): data error";
-            if (rv == Z_MEM_ERROR) return "inflate(): memory error";
-            const size_t got = want - z.avail_out;
-            out += got, size -= got;
-            if (size > 0 && rv == Z_STREAM_END) return "inflate(): attempting to read past the end of the stream";
-            if (got == 0 && rv == Z_BUF_ERROR && left == 0 && z.avail_in == 0) return "read less data than expected";
-        }
-        return nullptr;
-    }
-};
-}  // namespace
-
-int take_hip_mesh_from_serialized(const void *file_bytes, size_t n_bytes, int32_t shape_index, const double *to_world,
-                                  const double *inv_to_world, int32_t material_id, TakeMesh *out) {
-    if (!file_bytes || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    const uint8_t *f = (const uint8_t *)file_bytes;
-    if (n_bytes < 4) return fail(TAKE_E_INVALID, "not a serialized mesh file: shorter than its header");
-    uint16_t version = 0;
-    std::memcpy(&version, f + 2, 2);  // (the magic number in front of it is ignored: parse_serialized.cpp:178)
-    if (version != 3 && version != 4) return fail(TAKE_E_INVALID, "serialized mesh: unknown format version " + std::to_string(version));
-    size_t at = 0;
-    if (shape_index > 0) {  // skip_to_idx (parse_serialized.cpp:117-133): the offset table at the end of the file
-        uint32_t count = 0;
-        std::memcpy(&count, f + n_bytes - 4, 4);
-        const size_t esz = version == 4 ? 8 : 4;
-        if ((uint64_t)shape_index >= count || n_bytes < 4 + esz * (size_t)count)
-            return fail(TAKE_E_INVALID, "serialized mesh: shape index " + std::to_string(shape_index) + " of " + std::to_string(count));
-        uint64_t off = 0;
-        std::memcpy(&off, f + n_bytes - 4 - esz * ((size_t)count - (size_t)shape_index), esz);
-        if (off + 4 > n_bytes) return fail(TAKE_E_INVALID, "serialized mesh: sub-mesh offset past the end of the file");
-        at = (size_t)off;
-    } else if (shape_index < 0) {
-        return fail(TAKE_E_INVALID, "serialized mesh: negative shape index");
-    }
-    Inflater z(f + at + 4, n_bytes - at - 4);
-    if (!z.open) return fail(TAKE_E_DEVICE, "could not initialize zlib");
-    uint32_t flags = 0;
-    uint64_t nv = 0, nf = 0;
-    const char *bad = z.read(&flags, 4);
-    if (!bad && version == 4) {  // the mesh's name, NUL-terminated
-        char c = 1;
-        while (!bad && c != 0) bad = z.read(&c, 1);
-    }
-    if (!bad) bad = z.read(&nv, 8);
-    if (!bad) bad = z.read(&nf, 8);
-    if (bad) return fail(TAKE_E_INVALID, std::string("serialized mesh: ") + bad);
-    if (nv >= ((uint64_t)1 << 31) || nf >= ((uint64_t)1 << 31) / 3) return fail(TAKE_E_INVALID, "serialized mesh too large for 32-bit vertex indices");
-    ply::Layout L;
-    ply::serialized_layout(flags, (int64_t)nv, (int64_t)nf, L);
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    // the blocks, inflated once into one host buffer; the kernels read them where the stream put them
-    std::unique_ptr<uint8_t[]> body(new (std::nothrow) uint8_t[(size_t)std::max<int64_t>(L.end_off, 1)]);
-    if (!body) return fail(TAKE_E_NOMEM, "out of host memory for the inflated mesh");
-    bad = z.read(body.get(), (size_t)L.end_off);
-    if (bad) return fail(TAKE_E_INVALID, std::string("serialized mesh: ") + bad);
-    return decode_mesh_body(body.get(), L, to_world, inv_to_world, material_id, "serialized", out);
-}
-
-int take_hip_mesh_from_ply_file(const char *path, const double *to_world, const double *inv_to_world, int32_t material_id, TakeMesh *out) {
-    if (!path || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    MappedFile mf(path);
-    if (!mf.p) return fail(TAKE_E_INVALID, mf.err);
-    return take_hip_mesh_from_ply(mf.p, mf.n, to_world, inv_to_world, material_id, out);
-}
-
-int take_hip_mesh_from_serialized_file(const char *path, int32_t shape_index, const double *to_world, const double *inv_to_world,
-                                       int32_t material_id, TakeMesh *out) {
-    if (!path || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    MappedFile mf(path);
-    if (!mf.p) return fail(TAKE_E_INVALID, mf.err);
-    return take_hip_mesh_from_serialized(mf.p, mf.n, shape_index, to_world, inv_to_world, material_id, out);
-}
-
-// ---- Wavefront OBJ (src/parse/parse_obj.cpp:118-203): the whole file decoded on the device (tk_obj.h) -------------
-}  // extern "C"
-namespace {
-template <class T> struct ScopedBuf : DevBuf<T> {
-    ~ScopedBuf() { this->release(); }
-};
-
-// the three scan phases of tk_obj.h; `up` leaves the total in bsum[nb] (bsum: nb + 1 elements)
-inline int64_t scan_tiles(int64_t n) { return (n + obj::SCAN_TILE - 1) / obj::SCAN_TILE; }
-template <class T, class F> void scan_up(const F &f, int64_t n, T *bsum, hipStream_t st) {
-    const int64_t nb = scan_tiles(n);
-    if (nb > 0) hipLaunchKernelGGL((obj::k_scan_reduce<T, F>), dim3((unsigned)nb), dim3(obj::SCAN_BLK), 0, st, f, n, bsum);
-    hipLaunchKernelGGL((obj::k_scan_blocks<T>), dim3(1), dim3(obj::SCAN_BLK), 0, st, bsum, nb);
-}
-template <class T, class F> void scan_down(const F &f, int64_t n, const T *bsum, hipStream_t st) {
-    const int64_t nb = scan_tiles(n);
-    if (nb > 0) hipLaunchKernelGGL((obj::k_scan_down<T, F>), dim3((unsigned)nb), dim3(obj::SCAN_BLK), 0, st, f, n, bsum);
-}
-inline dim3 grid_for(int64_t n, int blk) { return dim3((unsigned)std::max<int64_t>((n + blk - 1) / blk, 1)); }
-
-// the numbers the device left to the host: strtod in the "C" locale, what `ss >> Real` computes.  -> the file offset
-// of the first one out of the range of a double (the reference's stream fails on those), or -1
-int64_t convert_fixups(const uint8_t *file, const std::vector<obj::Fix> &fx, std::vector<double> &val) {
-    val.resize(fx.size());
-    static locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-    std::atomic<int64_t> bad{INT64_MAX};
-    auto work = [&](size_t lo, size_t hi) {
-        std::string tok;
-        for (size_t k = lo; k < hi; k++) {
-            tok.assign((const char *)file + fx[k].off, fx[k].len);
-            errno = 0;
-            val[k] = strtod_l(tok.c_str(), nullptr, c_locale);
-            if (errno == ERANGE) {
-                int64_t cur = bad.load();
-                while ((int64_t)fx[k].off < cur && !bad.compare_exchange_weak(cur, (int64_t)fx[k].off)) {
-                }
-            }
-        }
-    };
-    const size_t nt = fx.size() < 65536 ? 1 : std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < nt; t++) pool.emplace_back(work, fx.size() * t / nt, fx.size() * (t + 1) / nt);
-    work(0, fx.size() / nt);
-    for (auto &t : pool) t.join();
-    return bad.load() == INT64_MAX ? -1 : bad.load();
-}
-
-std::string obj_message(uint32_t code, int64_t line) {
-    const std::string at = "OBJ line " + std::to_string(line + 1) + ": ";
-    switch (code) {
-    case obj::S_UNSUPPORTED:
-        return "unsupported " + at + "a token the reference's parser would not read (std::stoi throws, or a number is missing "
-               "or not in the grammar [+-]?(d+(.d*)?|.d+)([eE][+-]?d+)?): keep the host parser";
-    case obj::S_FEW: return at + "a face with fewer than 3 corners";
-    case obj::S_V0: return at + "a vertex index 0";
-    case obj::S_RANGE: return at + "an index outside its pool as it stands at that line";
-    default: return at + "The object file contains n-gon (n>4) that we do not support.";
-    }
-}
-
-int decode_obj(const uint8_t *file, size_t n_bytes, const double *to_world, const double *inv_to_world, int32_t material_id,
-               TakeMesh *out) {
-    if (n_bytes >= ((size_t)1 << 31) - 1) return fail(TAKE_E_INVALID, "unsupported OBJ file: 2 GiB or larger");
-    const int64_t n = (int64_t)n_bytes;
-    ply::Mat4 X, Xi;
-    static const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    std::memcpy(X.m, to_world ? to_world : I, sizeof(I));
-    std::memcpy(Xi.m, inv_to_world ? inv_to_world : I, sizeof(I));
-    ScopedBuf<uint8_t> body, type;
-    ScopedBuf<int32_t> nl, bsum_i, owner, minseq, slot, rank;
-    ScopedBuf<obj::Cnt> pre, bsum_c;
-    ScopedBuf<double> raw, fixval;
-    ScopedBuf<obj::Corner> corners;
-    ScopedBuf<obj::Face> faces;
-    ScopedBuf<obj::Fix> fix;
-    ScopedBuf<unsigned int> nfix, counts;
-    ScopedBuf<unsigned long long> status;
-    TakeMesh m{};
-    m.material_id = material_id, m.flags = TAKE_MESH_DEVICE_ARRAYS;
-    auto bail = [&](int rc) {
-        free_mesh_arrays(&m);
-        return rc;
-    };
-    auto nomem = [&]() { return bail(fail(TAKE_E_NOMEM, "out of device memory for an OBJ mesh of " + std::to_string(n) + " bytes")); };
-    auto dev = [&](hipError_t e) { return bail(fail(TAKE_E_DEVICE, std::string("OBJ decode: ") + hipGetErrorString(e))); };
-    constexpr int BLK = 256;
-    PinnedUploads pin;
-    const hipStream_t st = pin.stream;
-    hipError_t e = hipSuccess;
-    // 1. the file -> HBM; '\n' positions
-    if (body.alloc((size_t)std::max<int64_t>(n, 1)) != hipSuccess || bsum_i.alloc(scan_tiles(std::max(n, (int64_t)1)) + 1) != hipSuccess ||
-        status.alloc(1) != hipSuccess || nfix.alloc(1) != hipSuccess || counts.alloc(2) != hipSuccess)
-        return nomem();
-    e = pin.copy(body.p, file, (size_t)n);
-    if (e == hipSuccess) e = hipMemsetAsync(status.p, 0xFF, sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(nfix.p, 0, sizeof(unsigned int), st);
-    if (e == hipSuccess) e = hipMemsetAsync(counts.p, 0, 2 * sizeof(unsigned int), st);
-    if (e != hipSuccess) return dev(e);
-    obj::NewlineF nf_{body.p, nullptr};
-    scan_up<int32_t>(nf_, n, bsum_i.p, st);
-    int32_t nnl = 0;
-    e = hipMemcpyAsync(&nnl, bsum_i.p + scan_tiles(n), sizeof(nnl), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev(e);
-    const int64_t nlines = (int64_t)nnl + 1;
-    if (nl.alloc(std::max(nnl, 1)) != hipSuccess || type.alloc(nlines) != hipSuccess || pre.alloc(nlines) != hipSuccess ||
-        bsum_c.alloc(scan_tiles(nlines) + 1) != hipSuccess)
-        return nomem();
-    nf_.nl = nl.p;
-    scan_down<int32_t>(nf_, n, bsum_i.p, st);
-    // 2. line types; 3. their scan
-    hipLaunchKernelGGL(obj::k_obj_classify, grid_for(nlines, BLK), dim3(BLK), 0, st, body.p, n, nl.p, (int64_t)nnl, type.p);
-    const obj::LineF lf{type.p, pre.p};
-    scan_up<obj::Cnt>(lf, nlines, bsum_c.p, st);
-    scan_down<obj::Cnt>(lf, nlines, bsum_c.p, st);
-    obj::Cnt T{};
-    e = hipMemcpyAsync(&T, bsum_c.p + scan_tiles(nlines), sizeof(T), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev(e);
-    if (T.c >= (1 << 28)) return bail(fail(TAKE_E_INVALID, "unsupported OBJ file: more than 2^28 face corners"));
-    if (to_world && !inv_to_world && T.vn > 0)
-        return bail(fail(TAKE_E_INVALID, "the file has normals: pass inverse(to_world) along with to_world"));
-    // 4. numbers, corners, faces
-    const int64_t off_vt = 4 * (int64_t)T.v, off_vn = off_vt + 2 * (int64_t)T.vt, n_raw = off_vn + 3 * (int64_t)T.vn;
-    if (raw.alloc(std::max<int64_t>(n_raw, 1)) != hipSuccess || fix.alloc(std::max<int64_t>(n_raw, 1)) != hipSuccess ||
-        corners.alloc(std::max(T.c, 1)) != hipSuccess || faces.alloc(std::max(T.f, 1)) != hipSuccess)
-        return nomem();
-    hipLaunchKernelGGL(obj::k_obj_parse, grid_for(nlines, BLK), dim3(BLK), 0, st, body.p, n, nl.p, (int64_t)nnl, type.p, pre.p,
-                       raw.p, off_vt, off_vn, corners.p, faces.p, fix.p, nfix.p, status.p);
-    unsigned int n_fix = 0;
-    e = hipMemcpyAsync(&n_fix, nfix.p, sizeof(n_fix), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev(e);
-    int64_t host_bad = -1;  // file offset of a number out of the range of a double
-    if (n_fix > 0) {
-        std::vector<obj::Fix> fx(n_fix);
-        std::vector<double> val;
-        e = hipMemcpy(fx.data(), fix.p, n_fix * sizeof(obj::Fix), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return dev(e);
-        host_bad = convert_fixups(file, fx, val);
-        if (fixval.alloc(n_fix) != hipSuccess) return nomem();
-        e = hipMemcpy(fixval.p, val.data(), n_fix * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return dev(e);
-        hipLaunchKernelGGL(obj::k_obj_patch, grid_for(n_fix, BLK), dim3(BLK), 0, st, fix.p, fixval.p, (int64_t)n_fix, raw.p);
-    }
-    // 5. deduplication on the raw triple
-    uint32_t cap = 64;
-    while (cap < 2 * (uint32_t)T.c) cap <<= 1;
-    if (owner.alloc(cap) != hipSuccess || minseq.alloc(cap) != hipSuccess || slot.alloc(std::max(T.c, 1)) != hipSuccess ||
-        rank.alloc(std::max(T.c, 1)) != hipSuccess)
-        return nomem();
-    e = hipMemsetAsync(owner.p, 0xFF, cap * sizeof(int32_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(minseq.p, 0x7F, cap * sizeof(int32_t), st);
-    if (e != hipSuccess) return dev(e);
-    if (T.c > 0) hipLaunchKernelGGL(obj::k_obj_insert, grid_for(T.c, BLK), dim3(BLK), 0, st, corners.p, (int64_t)T.c, owner.p, minseq.p, cap - 1, slot.p);
-    const obj::FirstF ff{slot.p, minseq.p, rank.p};
-    scan_up<int32_t>(ff, T.c, bsum_i.p, st);  // (bsum_i has room: corners < bytes)
-    scan_down<int32_t>(ff, T.c, bsum_i.p, st);
-    int32_t nvert = 0;
-    e = hipMemcpyAsync(&nvert, bsum_i.p + scan_tiles(T.c), sizeof(nvert), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return dev(e);
-    // 6. the vertices, the triangles
-    const int64_t ntri = (int64_t)T.c - 2 * (int64_t)T.f;
-    m.n_vertices = nvert, m.n_faces = ntri;
-    auto dmalloc = [&](auto *&p, size_t count) -> bool {
-        void *q = nullptr;
-        if (count == 0) return true;
-        if (inject_alloc_failure() || hipMalloc(&q, count * sizeof(*p)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        p = (std::remove_reference_t<decltype(p)>)q;
-        return true;
-    };
-    double *pos = nullptr, *nrm = nullptr, *uv = nullptr;
-    int32_t *idx = nullptr;
-    const bool ok = dmalloc(pos, 3 * (size_t)nvert) && dmalloc(idx, 3 * (size_t)ntri) && (T.vn == 0 || dmalloc(nrm, 3 * (size_t)nvert)) &&
-                    (T.vt == 0 || dmalloc(uv, 2 * (size_t)nvert));
-    m.positions = pos, m.indices = idx, m.normals = nrm, m.uvs = uv;
-    if (!ok) return nomem();
-    if (T.c > 0)
-        hipLaunchKernelGGL(obj::k_obj_emit, grid_for(T.c, BLK), dim3(BLK), 0, st, corners.p, (int64_t)T.c, faces.p, slot.p, minseq.p,
-                           rank.p, raw.p, off_vt, off_vn, X, Xi, pos, nrm, uv, status.p, counts.p);
-    if (T.f > 0) hipLaunchKernelGGL(obj::k_obj_indices, grid_for(T.f, BLK), dim3(BLK), 0, st, faces.p, (int64_t)T.f, slot.p, minseq.p, rank.p, idx);
-    e = hipGetLastError();
-    unsigned long long stw = 0;
-    unsigned int cnt[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(&stw, status.p, sizeof(stw), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, counts.p, sizeof(cnt), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = pin.finish();
-    if (e != hipSuccess) return dev(e);
-    // the earliest line with a problem decides, as in the reference's loop
-    int64_t bad_line = stw == ~0ull ? INT64_MAX : (int64_t)(stw >> 8);
-    uint32_t code = (uint32_t)(stw & 0xFF);
-    if (host_bad >= 0) {
-        const int64_t line = (int64_t)std::count(file, file + host_bad, (uint8_t)'\n');
-        if (line < bad_line || (line == bad_line && code >= obj::S_UNSUPPORTED))
-            return bail(fail(TAKE_E_INVALID, "unsupported OBJ line " + std::to_string(line + 1) +
-                                                 ": a number outside the range of a double (the reference's stream fails on it)"));
-    }
-    if (bad_line != INT64_MAX) return bail(fail(TAKE_E_INVALID, obj_message(code, bad_line)));
-    // TakeMesh holds one uv / normal per position: all vertices have one, or none has
-    if (uv && cnt[0] == 0) (void)hipFree(uv), m.uvs = nullptr;
-    if (nrm && cnt[1] == 0) (void)hipFree(nrm), m.normals = nullptr;
-    if (cnt[0] != 0 && cnt[0] != (unsigned)nvert)
-        return bail(fail(TAKE_E_INVALID, "unsupported OBJ mesh: only some vertices have a texture coordinate (the reference's uvs would "
-                                         "not match its positions)"));
-    if (cnt[1] != 0 && cnt[1] != (unsigned)nvert)
-        return bail(fail(TAKE_E_INVALID, "unsupported OBJ mesh: only some vertices have a normal (the reference's normals would not "
-                                         "match its positions)"));
-    *out = m;
-    return TAKE_OK;
-}
-
-// ---- compute_normals (src/compute_normals.cpp:12-47) on device arrays (tk_normals.h) -------------------------------
-int normals_counts(int64_t nv, int64_t nf) {
-    if (nv < 0 || nf < 0) return fail(TAKE_E_INVALID, "compute_normals: negative vertex or face count");
-    if (nf > INT32_MAX / 3)
-        return fail(TAKE_E_INVALID, "compute_normals: " + std::to_string(nf) + " faces are more than INT32_MAX corners (the kernels "
-                                    "index corners with 32-bit integers)");
-    if (nv >= INT32_MAX) return fail(TAKE_E_INVALID, "compute_normals: more vertices than 32-bit indices can name");
-    return TAKE_OK;
-}
-
-// d_out: 3 * nv doubles, every one written.  Synchronous on `st`.
-int normals_on_device(const double *d_pos, int64_t nv, const int32_t *d_idx, int64_t nf, double *d_out, hipStream_t st) {
-    const int rc = normals_counts(nv, nf);
-    if (rc != TAKE_OK) return rc;
-    const int64_t nc = 3 * nf;
-    const int64_t heavy_cap = std::max<int64_t>(1, std::min<int64_t>(nv, nc / (nrm::HEAVY + 1)));
-    ScopedBuf<double> contrib;
-    ScopedBuf<uint32_t> keys, keys_s, status;
-    ScopedBuf<int32_t> vals, vals_s, begin, end, heavy;
-    ScopedBuf<char> temp;
-    if (contrib.alloc(3 * (size_t)nc) != hipSuccess || keys.alloc((size_t)nc) != hipSuccess || keys_s.alloc((size_t)nc) != hipSuccess ||
-        vals.alloc((size_t)nc) != hipSuccess || vals_s.alloc((size_t)nc) != hipSuccess || begin.alloc((size_t)nv) != hipSuccess ||
-        end.alloc((size_t)nv) != hipSuccess || heavy.alloc((size_t)heavy_cap) != hipSuccess || status.alloc(2) != hipSuccess)
-        return fail(TAKE_E_NOMEM, "out of device memory for compute_normals on " + std::to_string(nf) + " faces");
-    // the sort keys: vertex indices and the "adds nothing" key nv
-    const int end_bit = std::max(1, 32 - __builtin_clz((uint32_t)std::max<int64_t>(nv, 1)));
-    size_t temp_bytes = 0;
-    if (nc > 0) {
-        HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)nc, 0, end_bit, st));
-        if (temp.alloc(std::max<size_t>(temp_bytes, 1)) != hipSuccess)
-            return fail(TAKE_E_NOMEM, "out of device memory for compute_normals' sort");
-    }
-    const int B = nrm::BLK;
-    HIP_TRY(hipMemsetAsync(status.p, 0, status.bytes(), st));
-    if (nv > 0) {
-        HIP_TRY(hipMemsetAsync(begin.p, 0, begin.bytes(), st));
-        HIP_TRY(hipMemsetAsync(end.p, 0, end.bytes(), st));
-    }
-    if (nc > 0) {
-        hipLaunchKernelGGL(nrm::k_nrm_faces, grid_for(nf, B), dim3(B), 0, st, d_pos, d_idx, nf, nv, contrib.p, keys.p, vals.p, status.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)nc, 0, end_bit, st));
-        hipLaunchKernelGGL(nrm::k_nrm_bounds, grid_for(nc, B), dim3(B), 0, st, keys_s.p, nc, (uint32_t)nv, begin.p, end.p, heavy.p, status.p);
-    }
-    if (nv > 0) {
-        hipLaunchKernelGGL(nrm::k_nrm_vertices, grid_for(nv, B), dim3(B), 0, st, contrib.p, vals_s.p, begin.p, end.p, nv, d_out);
-        const int64_t heavy_waves = std::min<int64_t>(heavy_cap, 1024);
-        if (nc > nrm::HEAVY)
-            hipLaunchKernelGGL(nrm::k_nrm_heavy, grid_for(heavy_waves * 64, B), dim3(B), 0, st, contrib.p, vals_s.p, begin.p, end.p,
-                               heavy.p, status.p, d_out);
-    }
-    HIP_TRY(hipGetLastError());
-    uint32_t st_h[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(st_h, status.p, sizeof(st_h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (st_h[0] & 1) return fail(TAKE_E_INVALID, "compute_normals: a face indexes outside the vertex array [0, " + std::to_string(nv) + ")");
-    return TAKE_OK;
-}
-}  // namespace
-extern "C" {
-
-int take_hip_mesh_compute_normals(TakeMesh *mesh) {
-    if (!mesh) return fail(TAKE_E_INVALID, "null mesh");
-    if (!(mesh->flags & TAKE_MESH_DEVICE_ARRAYS))
-        return fail(TAKE_E_INVALID, "compute_normals: not a device-array mesh (host arrays: take_hip_compute_normals)");
-    if (mesh->normals) return fail(TAKE_E_INVALID, "compute_normals: the mesh has normals already");
-    int rc = normals_counts(mesh->n_vertices, mesh->n_faces);
-    if (rc != TAKE_OK) return rc;
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    double *nrm = nullptr;
-    if (mesh->n_vertices > 0) {
-        if (inject_alloc_failure() || hipMalloc((void **)&nrm, 3 * sizeof(double) * (size_t)mesh->n_vertices) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TAKE_E_NOMEM, "out of device memory for the normals of a " + std::to_string(mesh->n_vertices) + "-vertex mesh");
-        }
-    }
-    rc = normals_on_device(mesh->positions, mesh->n_vertices, mesh->indices, mesh->n_faces, nrm, nullptr);
-    if (rc != TAKE_OK) {
-        if (nrm) (void)hipFree(nrm);
-        return rc;
-    }
-    mesh->normals = nrm;
-    return TAKE_OK;
-}
-
-int take_hip_compute_normals(const double *positions, int64_t n_vertices, const int32_t *indices, int64_t n_faces,
-                             double *normals_out) {
-    int rc = normals_counts(n_vertices, n_faces);
-    if (rc != TAKE_OK) return rc;
-    if ((n_vertices > 0 && (!positions || !normals_out)) || (n_faces > 0 && !indices)) return fail(TAKE_E_INVALID, "null argument");
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    ScopedBuf<double> pos, out;
-    ScopedBuf<int32_t> idx;
-    if (pos.alloc(3 * (size_t)n_vertices) != hipSuccess || out.alloc(3 * (size_t)n_vertices) != hipSuccess ||
-        idx.alloc(3 * (size_t)n_faces) != hipSuccess)
-        return fail(TAKE_E_NOMEM, "out of device memory for compute_normals on " + std::to_string(n_faces) + " faces");
-    PinnedUploads pin;
-    HIP_TRY(pin.copy(pos.p, positions, pos.bytes()));
-    HIP_TRY(pin.copy(idx.p, indices, idx.bytes()));
-    rc = normals_on_device(pos.p, n_vertices, idx.p, n_faces, out.p, pin.stream);
-    HIP_TRY(pin.finish());
-    if (rc != TAKE_OK) return rc;
-    if (out.n) HIP_TRY(hipMemcpy(normals_out, out.p, out.bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
-}
-
-int take_hip_mesh_from_obj(const void *file_bytes, size_t n_bytes, const double *to_world, const double *inv_to_world,
-                           int32_t material_id, TakeMesh *out) {
-    if (!file_bytes || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    return decode_obj((const uint8_t *)file_bytes, n_bytes, to_world, inv_to_world, material_id, out);
-}
-
-int take_hip_mesh_from_obj_file(const char *path, const double *to_world, const double *inv_to_world, int32_t material_id, TakeMesh *out) {
-    if (!path || !out) return fail(TAKE_E_INVALID, "null argument");
-    std::memset(out, 0, sizeof(*out));
-    MappedFile mf(path);
-    if (!mf.p) return fail(TAKE_E_INVALID, mf.err);
-    return take_hip_mesh_from_obj(mf.p, mf.n, to_world, inv_to_world, material_id, out);
-}
-
-int take_hip_mesh_download(const TakeMesh *m, double *positions, int32_t *indices, double *normals, double *uvs) {
-    if (!m) return fail(TAKE_E_INVALID, "null mesh");
-    if (!(m->flags & TAKE_MESH_DEVICE_ARRAYS)) return fail(TAKE_E_INVALID, "not a device-array mesh");
-    auto down = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-        return (dst && src && bytes) ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
-    };
-    HIP_TRY(down(positions, m->positions, sizeof(double) * 3 * (size_t)m->n_vertices));
-    HIP_TRY(down(indices, m->indices, sizeof(int32_t) * 3 * (size_t)m->n_faces));
-    HIP_TRY(down(normals, m->normals, sizeof(double) * 3 * (size_t)m->n_vertices));
-    HIP_TRY(down(uvs, m->uvs, sizeof(double) * 2 * (size_t)m->n_vertices));
-    return TAKE_OK;
-}
-
-int take_hip_mesh_release(TakeMesh *m) {
-    if (!m) return TAKE_OK;
-    if (m->flags & TAKE_MESH_DEVICE_ARRAYS) free_mesh_arrays(m);
-    return TAKE_OK;
-}
 
 int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, TakeScene **out) {
     if (!desc || !out) return fail(TAKE_E_INVALID, "null argument");
@@ -2106,7 +1372,6 @@ int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uin
     rc = take_hip_pack_exr_scanlines(d_img, ts->precision, W, H, halves.p, nullptr);
     if (!rc && hipMemcpy(out_host, halves.p, halves.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(TAKE_E_DEVICE, "scanline download failed");
-    halves.release();
     return rc;
 }
 
@@ -2151,39 +1416,28 @@ int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int6
             for (int a = 0; a < 3; a++) td[3 * (y * 5 + x) + a] = c[a], tf[3 * (y * 5 + x) + a] = (float)c[a];
         }
     std::vector<ImageInfo> img{ImageInfo{5, 4, 0}};
-    int rc = TAKE_OK;
-    do {
-        if (d_in.alloc((size_t)n * in_cols) != hipSuccess || d_rnd.alloc((size_t)n * TAB_RND) != hipSuccess ||
-            d_out.alloc((size_t)n * out_cols) != hipSuccess || d_img.upload(img) != hipSuccess ||
-            d_texf.upload(tf) != hipSuccess || d_texd.upload(td) != hipSuccess) {
-            rc = fail(TAKE_E_NOMEM, "debug table allocation failed");
-            break;
-        }
-        if (hipMemcpy(d_in.p, in, d_in.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_rnd.p, rnd, d_rnd.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(d_out.p, 0, d_out.bytes()) != hipSuccess) {
-            rc = fail(TAKE_E_DEVICE, "debug table upload failed");
-            break;
-        }
-        const dim3 g((unsigned)((n + BLOCK - 1) / BLOCK)), b(BLOCK);
-        if (precision == TAKE_PRECISION_F64) {
-            DeviceScene<double> sc{};
-            sc.images = d_img.p, sc.texels = d_texd.p;
-            hipLaunchKernelGGL((k_debug_table<double>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
-        } else {
-            DeviceScene<float> sc{};
-            sc.images = d_img.p, sc.texels = d_texf.p;
-            hipLaunchKernelGGL((k_debug_table<float>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
-        }
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
-            rc = fail(TAKE_E_DEVICE, "debug table kernel failed");
-            break;
-        }
-        if (hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(TAKE_E_DEVICE, "debug table download failed");
-    } while (0);
-    d_in.release(), d_rnd.release(), d_out.release(), d_img.release(), d_texf.release(), d_texd.release();
-    return rc;
+    if (d_in.alloc((size_t)n * in_cols) != hipSuccess || d_rnd.alloc((size_t)n * TAB_RND) != hipSuccess ||
+        d_out.alloc((size_t)n * out_cols) != hipSuccess || d_img.upload(img) != hipSuccess ||
+        d_texf.upload(tf) != hipSuccess || d_texd.upload(td) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "debug table allocation failed");
+    if (hipMemcpy(d_in.p, in, d_in.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_rnd.p, rnd, d_rnd.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_out.p, 0, d_out.bytes()) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "debug table upload failed");
+    const dim3 g((unsigned)((n + BLOCK - 1) / BLOCK)), b(BLOCK);
+    if (precision == TAKE_PRECISION_F64) {
+        DeviceScene<double> sc{};
+        sc.images = d_img.p, sc.texels = d_texd.p;
+        hipLaunchKernelGGL((k_debug_table<double>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
+    } else {
+        DeviceScene<float> sc{};
+        sc.images = d_img.p, sc.texels = d_texf.p;
+        hipLaunchKernelGGL((k_debug_table<float>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(TAKE_E_DEVICE, "debug table kernel failed");
+    if (hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "debug table download failed");
+    return TAKE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ scene groups

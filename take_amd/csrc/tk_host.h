@@ -1,0 +1,136 @@
+// tk_host.h — host plumbing shared by the library's two units, tk_api.hip (scenes, rendering, trace hooks) and
+// tk_mesh.hip (mesh ingest): the error string, fault injection, pinned uploads, the owning device buffer.
+// Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
+// take_hip_last_error returns) and ONE TAKE_HIP_FAIL_ALLOC counter.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "take_hip.h"
+
+namespace tk_host {
+
+inline thread_local std::string g_error;
+inline int fail(int code, const std::string &msg) {
+    g_error = msg;
+    return code;
+}
+#define HIP_TRY(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return fail(TAKE_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));             \
+    } while (0)
+
+// Fault injection for the allocation-failure tests (tests/test_gpu_robustness.py): TAKE_HIP_FAIL_ALLOC=<k> makes the
+// k-th device allocation after the variable was (re)set fail with hipErrorOutOfMemory.  A real out-of-memory cannot
+// be provoked reliably from a test: the driver over-commits, a 300 GB request on a 288 GB device succeeded.
+// (allocations happen on several host threads at once — one per shard of a scene group — hence the lock)
+inline bool inject_alloc_failure() {
+    static std::mutex mu;
+    static std::string seen;
+    static long calls = 0;
+    const char *e = std::getenv("TAKE_HIP_FAIL_ALLOC");
+    std::lock_guard<std::mutex> lock(mu);
+    if (!e || !*e) {
+        seen.clear();
+        return false;
+    }
+    if (seen != e) seen = e, calls = 0;
+    return ++calls == std::atol(e);
+}
+
+// Host -> device copies of the caller's large arrays (mesh positions, shape arrays) for the device-side scene build
+// (SURVEY.md §8(f)2): the pages are pinned IN PLACE (hipHostRegister) so that the DMA engine reads the caller's memory
+// directly — no bounce through the runtime's staging buffers — and the copies of all arrays are in flight together;
+// the registrations are dropped once the stream has drained.  Arrays below 4 MiB, and memory that cannot be
+// registered, take the ordinary pageable path.  TAKE_HIP_PINNED_UPLOAD=0 turns the registration off (A/B runs).
+struct PinnedUploads {
+    hipStream_t stream = nullptr;
+    std::vector<void *> regs;
+    size_t pinned_bytes = 0, plain_bytes = 0;
+    bool enabled = !(std::getenv("TAKE_HIP_PINNED_UPLOAD") && std::atoi(std::getenv("TAKE_HIP_PINNED_UPLOAD")) == 0);
+    hipError_t copy(void *dst, const void *src, size_t bytes) {
+        if (bytes == 0) return hipSuccess;
+        if (enabled && bytes >= ((size_t)4 << 20)) {
+            if (hipHostRegister(const_cast<void *>(src), bytes, hipHostRegisterDefault) == hipSuccess) {
+                regs.push_back(const_cast<void *>(src));
+                pinned_bytes += bytes;
+            } else {
+                (void)hipGetLastError();  // (already registered, read-only mapping, ...): pageable copy
+                plain_bytes += bytes;
+            }
+        } else {
+            plain_bytes += bytes;
+        }
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream);
+    }
+    hipError_t finish() {
+        const hipError_t e = hipStreamSynchronize(stream);
+        for (void *p : regs) (void)hipHostUnregister(p);
+        regs.clear();
+        return e;
+    }
+    ~PinnedUploads() { (void)finish(); }
+};
+
+// A device array that owns its allocation: freed when it goes out of scope or is moved over, handed on with detach().
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, n = o.n;
+            o.p = nullptr, o.n = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count) {
+        release();  // p = nullptr, n = 0: the state a failed allocation leaves behind
+        if (count == 0) return hipSuccess;
+        const hipError_t e = inject_alloc_failure() ? hipErrorOutOfMemory : hipMalloc((void **)&p, count * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();  // the error is reported through the return value, not left sticky
+            return e;
+        }
+        n = count;
+        return hipSuccess;
+    }
+    hipError_t upload(const std::vector<T> &v) {
+        hipError_t e = alloc(v.size());
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    // the allocation, no longer owned (it goes into a caller's TakeMesh)
+    T *detach() {
+        T *q = p;
+        p = nullptr, n = 0;
+        return q;
+    }
+    size_t bytes() const { return n * sizeof(T); }
+};
+
+inline int check_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(TAKE_E_NO_GPU, "no HIP device visible: libtake_hip has no CPU path");
+    return n;
+}
+
+}  // namespace tk_host
