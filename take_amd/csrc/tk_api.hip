@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -30,6 +31,12 @@ namespace {
 struct EventPool {
     std::vector<hipEvent_t> ev;
     size_t used = 0;
+    EventPool() = default;
+    EventPool(const EventPool &) = delete;
+    EventPool &operator=(const EventPool &) = delete;
+    ~EventPool() {
+        for (auto e : ev) (void)hipEventDestroy(e);
+    }
     hipEvent_t get() {
         if (used == ev.size()) {
             hipEvent_t e = nullptr;
@@ -39,10 +46,27 @@ struct EventPool {
         return ev[used++];
     }
     void reset() { used = 0; }
-    void destroy() {
-        for (auto e : ev) (void)hipEventDestroy(e);
-        ev.clear();
-        used = 0;
+};
+
+// Queue lengths read back WITHOUT stalling the launch loop (render_impl): a ring of pinned words + events, made by the
+// first render.
+struct PollRing {
+    static constexpr int SIZE = 64;
+    int32_t *word = nullptr;  // SIZE pinned words
+    hipEvent_t ev[SIZE] = {};
+    PollRing() = default;
+    PollRing(const PollRing &) = delete;
+    PollRing &operator=(const PollRing &) = delete;
+    ~PollRing() {
+        if (word) (void)hipHostFree(word);
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {  // (a no-op once it has succeeded; after a failure the next call makes what is missing)
+        hipError_t r = word ? hipSuccess : hipHostMalloc((void **)&word, sizeof(int32_t) * SIZE, hipHostMallocDefault);
+        for (int i = 0; i < SIZE && r == hipSuccess; i++)
+            if (!ev[i]) r = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        return r;
     }
 };
 
@@ -54,7 +78,6 @@ template <class R> struct SceneT {
     DevBuf<QNode4> qnodes;
     DevBuf<QNode8> qnodes8;
     DevBuf<PrimRec<R>> prims;
-    DevBuf<ShapeInfo> shapes;
     DevBuf<MeshInfo> meshes;
     DevBuf<int32_t> face_idx;
     DevBuf<R> normals, uvs, texels;
@@ -82,17 +105,28 @@ template <class R> struct SceneT {
     bool built_on_device = false;
     int64_t spill_stride = 0;  // ray groups in the persistent trace grid
 
-    size_t scene_bytes() const {
-        return nodes.bytes() + qnodes.bytes() + qnodes8.bytes() + prims.bytes() + shapes.bytes() + meshes.bytes() + face_idx.bytes() + normals.bytes() +
-               uvs.bytes() + texels.bytes() + materials.bytes() + images.bytes() + lights.bytes() + inst_trace.bytes() + inst_shade.bytes();
+    // The scene arrays: f(x.nodes...), f(x.qnodes...), ... for the scenes x, in the order replicate_t allocates them.
+    template <class F, class... S> static void for_each_array(F &&f, S &...x) {
+        f(x.nodes...), f(x.qnodes...), f(x.qnodes8...), f(x.prims...), f(x.meshes...), f(x.face_idx...), f(x.normals...);
+        f(x.uvs...), f(x.texels...), f(x.materials...), f(x.images...), f(x.lights...), f(x.light_pmf...), f(x.light_cdf...);
+        f(x.inst_trace...), f(x.inst_shade...), f(x.env_marginal...), f(x.env_conditional...), f(x.env_guide_m...), f(x.env_guide_c...);
     }
-    void release() {
-        nodes.release(), qnodes.release(), qnodes8.release(), prims.release(), shapes.release(), meshes.release(), face_idx.release();
-        normals.release(), uvs.release(), texels.release(), materials.release(), images.release(), lights.release();
-        env_marginal.release(), env_conditional.release(), env_guide_m.release(), env_guide_c.release();
-        light_pmf.release(), light_cdf.release(), inst_trace.release(), inst_shade.release();
-        state_r.release(), queue[0].release(), queue[1].release(), shadow_queue.release();
-        sorted_queue.release(), sort_keys.release(), sort_hist.release(), sort_base.release(), accum.release(), out.release(), qwords.release(), counters.release(), spill.release();
+    // dev's pointers into this scene's arrays: null where an array is empty, and for the node formats not in use (only
+    // the format the kernels traverse is allocated)
+    void bind() {
+        dev.nodes = nodes.p, dev.qnodes = qnodes.p, dev.qnodes8 = qnodes8.p, dev.prims = prims.p;
+        dev.shapes = nullptr;  // (ShapeInfo stays on the host: every kernel reads the shading side of a primitive from its own record)
+        dev.meshes = meshes.p, dev.face_idx = face_idx.p, dev.normals = normals.p, dev.uvs = uvs.p, dev.texels = texels.p;
+        dev.materials = materials.p, dev.images = images.p, dev.lights = lights.p, dev.light_pmf = light_pmf.p, dev.light_cdf = light_cdf.p;
+        dev.inst_trace = inst_trace.p, dev.inst_shade = inst_shade.p;
+        dev.env.marginal = env_marginal.p, dev.env.conditional = env_conditional.p, dev.env.guide_m = env_guide_m.p, dev.env.guide_c = env_guide_c.p;
+    }
+    // device bytes of the scene (take_hip_scene_stats): the light-picking and environment-map tables have never been
+    // counted in this figure
+    size_t scene_bytes() const {
+        size_t n = 0;
+        for_each_array([&n](const auto &b) { n += b.bytes(); }, *this);
+        return n - light_pmf.bytes() - light_cdf.bytes() - env_marginal.bytes() - env_conditional.bytes() - env_guide_m.bytes() - env_guide_c.bytes();
     }
 };
 
@@ -112,20 +146,17 @@ struct TakeScene {
     TakeCounters counters{};
     EventPool events;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> timed;
-    // queue lengths read back WITHOUT stalling the launch loop: a ring of pinned words + events (render_impl)
-    static constexpr int POLL_RING = 64;
-    int32_t *poll_host = nullptr;  // POLL_RING pinned words
-    hipEvent_t poll_ev[POLL_RING] = {};
+    PollRing poll;
+    // records, images and trace hooks of a mixed-precision scene are the f64 ones (its f32 side finishes the paths)
+    bool f64() const { return precision != TAKE_PRECISION_F32; }
+    int width() const { return f64() ? d.host.cam.width : f.host.cam.width; }
+    int height() const { return f64() ? d.host.cam.height : f.host.cam.height; }
 };
 
 namespace {
 
-// records, images and trace hooks of a mixed-precision scene are the f64 ones (its f32 side finishes the paths)
-inline bool is_f64(const TakeScene *s) { return s->precision != TAKE_PRECISION_F32; }
-
-template <class R> SceneT<R> &pick(TakeScene *s);
-template <> SceneT<float> &pick<float>(TakeScene *s) { return s->f; }
-template <> SceneT<double> &pick<double>(TakeScene *s) { return s->d; }
+// f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
+template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
 
 // BVH build on the device (tk_build_gpu.h).  In: sc.prims uploaded in SHAPE order.  Out: the records in
 // leaf order, sc.nodes or sc.qnodes, host-side stats and grid.  Returns TAKE_OK, an error, or 1 = "use the host
@@ -391,7 +422,6 @@ struct StagedMeshes {
         return TAKE_OK;
     }
 };
-thread_local StagedMeshes *t_staged = nullptr;  // set by scene_create while upload_scene runs on a staged description
 
 // Primitive records on the device from the caller's arrays (tk_build_gpu.h::k_make_prims): the mesh positions go up as
 // they are (double, one copy per mesh, no host staging), the face indices are the validated concatenation the shading
@@ -449,7 +479,6 @@ int make_prims_on_device(SceneT<float> &sc, const TakeSceneDesc &d, const double
         std::fprintf(stderr, "[take_hip] scene_create: uploads pinned in place %.1f MB, pageable %.1f MB\n", pin.pinned_bytes / 1e6, pin.plain_bytes / 1e6);
     return TAKE_OK;
 }
-template <class R> int make_prims_on_device(SceneT<R> &, const TakeSceneDesc &, const double *const *) { return 1; }
 
 // phase timer of scene_create (TAKE_HIP_VERBOSE=1 prints the phases to stderr)
 struct PhaseClock {
@@ -463,11 +492,13 @@ struct PhaseClock {
     }
 };
 
-template <class R> int upload_scene(TakeScene *ts, const TakeSceneDesc &desc, const TakeBuildOpts &opts) {
-    SceneT<R> &sc = pick<R>(ts);
+// One precision's side of a new scene: records, tree and shading tables prepared on the host and uploaded, or with
+// device_builder (f32 only) the records and the tree made on the device — and, when the device tree would be too deep,
+// on the host after all.  staged: the description's device-array meshes (StagedMeshes::stage).
+template <class R>
+int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const TakeBuildOpts &opts, int threads, bool device_builder,
+                 StagedMeshes &staged) {
     PhaseClock clock;
-    int threads = opts.bvh_threads > 0 ? opts.bvh_threads : (int)std::thread::hardware_concurrency();
-    if (threads <= 0) threads = 1;
     int max_leaf = opts.max_leaf_size;
     if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));  // tuning knob
     // lanes per ray: one (TQ_GROUP).  Round 1 measured quad 143.6 / pair 121.5 / one ray per lane 128.8 ms of closest-hit
@@ -476,61 +507,47 @@ template <class R> int upload_scene(TakeScene *ts, const TakeSceneDesc &desc, co
     sc.group = TQ_GROUP;
     const char *fmt_env = std::getenv("TAKE_HIP_NODES");
     const std::string fmt = fmt_env ? fmt_env : "";
-    // device build: f32 scenes with enough primitives to make a tree; otherwise (and as its fall-back) the host SAH build
-    // builder: AUTO = host SAH (best trees) up to 4M shapes, device LBVH beyond (f32): at 10M triangles the host build
-    // is 6 s of setup against 0.2 s, for 2-6 % of traversal speed
-    const bool want_device = opts.builder == TAKE_BUILDER_DEVICE_LBVH ||
-                             (opts.builder == TAKE_BUILDER_AUTO && desc.n_shapes >= TAKE_AUTO_DEVICE_BUILD_SHAPES);
-    bool on_device = want_device && sizeof(R) == 4 && desc.n_shapes >= 8 && desc.n_instances == 0;
+    bool on_device = device_builder && sizeof(R) == 4;  // (the f64 side of a mixed-precision scene: the host builder)
     std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_TABLES : PREP_ALL, opts.burley_lobes != 0);
     if (!err.empty()) return fail(TAKE_E_INVALID, err);
     clock.lap(on_device ? "host validation + tables" : "host records + SAH build");
     HostScene<R> &h = sc.host;
-    bool use_q = false;
-    if (on_device) {
-        int rc = TAKE_OK;
-        if constexpr (sizeof(R) == 4) {
-            rc = make_prims_on_device(sc, desc, t_staged && t_staged->any ? t_staged->d_positions.data() : nullptr);
+    if constexpr (sizeof(R) == 4) {
+        if (on_device) {
+            int rc = make_prims_on_device(sc, desc, staged.any ? staged.d_positions.data() : nullptr);
             clock.lap("mesh arrays -> HBM, records");
             if (!rc) rc = build_bvh_device(sc, max_leaf, sc.group <= 2 && fmt != "wide", fmt == "q16");
-        } else {
-            rc = 1;
-        }
-        if (rc == 1) {  // not buildable on the device (tree too deep): do it on the host after all
-            on_device = false;
-            if (t_staged && t_staged->any) {
-                const int rs = t_staged->ensure_positions();
+            if (rc == 1) {  // not buildable on the device (tree too deep): do it on the host after all
+                on_device = false;
+                const int rs = staged.ensure_positions();
                 if (rs) return rs;
+                err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_ALL, opts.burley_lobes != 0);
+                if (!err.empty()) return fail(TAKE_E_INVALID, err);
+            } else if (rc != TAKE_OK) {
+                return rc;
             }
-            err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_ALL, opts.burley_lobes != 0);
-            if (!err.empty()) return fail(TAKE_E_INVALID, err);
-        } else if (rc != TAKE_OK) {
-            return rc;
-        } else {
-            use_q = sc.qnodes.p != nullptr;
         }
     }
     if (!on_device) {
         HIP_TRY(sc.prims.upload(h.prims));
         clock.lap("primitive records -> HBM");
-    }
-    if (!on_device) {
-        use_q = sc.group <= 2 && (!h.qnodes.empty() || !h.qnodes8.empty());  // compressed nodes (not in the quad kernel)
+        const bool use_q = sc.group <= 2 && (!h.qnodes.empty() || !h.qnodes8.empty());  // compressed nodes (not in the quad kernel)
         if (!h.qnodes8.empty()) HIP_TRY(sc.qnodes8.upload(h.qnodes8));
         else if (use_q) HIP_TRY(sc.qnodes.upload(h.qnodes));
         else HIP_TRY(sc.nodes.upload(h.nodes));
     }
     sc.built_on_device = on_device;
     clock.lap(on_device ? "device LBVH build" : "nodes -> HBM");
+    // (only the node format the kernels traverse is allocated)
+    const bool w8 = sc.qnodes8.p != nullptr, use_q = sc.qnodes.p != nullptr;
     // the trace kernels address nodes and primitive records with 32-bit byte offsets (full-rate integer math)
     {
-        const uint64_t node_bytes = (uint64_t)h.stats.n_nodes * (sc.qnodes8.p ? sizeof(QNode8) : (use_q ? sizeof(QNode4) : sizeof(Node4<R>)));
+        const uint64_t node_bytes = (uint64_t)h.stats.n_nodes * (w8 ? sizeof(QNode8) : (use_q ? sizeof(QNode4) : sizeof(Node4<R>)));
         const uint64_t prim_bytes = (uint64_t)sc.prims.n * sizeof(PrimRec<R>);
         if (node_bytes >= (1ull << 32) || prim_bytes >= (1ull << 32))
             return fail(TAKE_E_INVALID, "scene too large for the 32-bit record offsets of the trace kernels (" +
                                             std::to_string(sc.prims.n) + " primitives, " + std::to_string(h.stats.n_nodes) + " nodes)");
     }
-    // (ShapeInfo stays on the host: every kernel reads the shading side of a primitive from its own record)
     HIP_TRY(sc.meshes.upload(h.meshes));
     if (!on_device) HIP_TRY(sc.face_idx.upload(h.face_idx));  // (device build: already there, k_make_prims read it)
     HIP_TRY(sc.normals.upload(h.normals));
@@ -547,37 +564,14 @@ template <class R> int upload_scene(TakeScene *ts, const TakeSceneDesc &desc, co
     HIP_TRY(sc.env_conditional.upload(h.env_conditional));
     HIP_TRY(sc.env_guide_m.upload(h.env_guide_m));
     HIP_TRY(sc.env_guide_c.upload(h.env_guide_c));
-    DeviceScene<R> &d = sc.dev;
-    d = h.view();
-    d.n_nodes = (int32_t)h.stats.n_nodes;
-    d.nodes = sc.nodes.p;
-    d.qnodes = use_q ? sc.qnodes.p : nullptr;
-    d.qnodes8 = sc.qnodes8.p;
-    d.prims = sc.prims.p;
-    d.shapes = nullptr;
-    d.meshes = sc.meshes.p;
-    d.face_idx = sc.face_idx.p;
-    d.normals = sc.normals.p;
-    d.uvs = sc.uvs.p;
-    d.texels = sc.texels.p;
-    d.materials = sc.materials.p;
-    d.images = sc.images.p;
-    d.lights = sc.lights.p;
-    d.inst_trace = sc.inst_trace.p;
-    d.inst_shade = sc.inst_shade.p;
-    d.light_pmf = sc.light_pmf.p;
-    d.light_cdf = sc.light_cdf.p;
-    d.env.marginal = sc.env_marginal.p;
-    d.env.conditional = sc.env_conditional.p;
-    d.env.guide_m = sc.env_guide_m.p;
-    d.env.guide_c = sc.env_guide_c.p;
+    sc.dev = h.view();  // (the counts, camera and small tables; the pointers are the device arrays')
+    sc.bind();
     HIP_TRY(sc.qwords.alloc(Q_NUM_WORDS + 2 * N_SORT_KEYS));
     HIP_TRY(hipMemset(sc.qwords.p, 0, sc.qwords.bytes()));
     HIP_TRY(sc.counters.alloc(C_NUM_WORDS));
     HIP_TRY(hipMemset(sc.counters.p, 0, sc.counters.bytes()));
     // persistent trace grid: resident blocks of the heaviest trace kernel x CUs
     int per_cu = 0;
-    const bool w8 = sc.qnodes8.p != nullptr;
     const int groups_per_block = GroupGeom<TQ_GROUP>::GROUPS;
     const int spill_levels = w8 ? GroupGeom<TQ_GROUP == 1 ? 1 : TQ_GROUP, TQ_GROUP == 1 ? 8 : 4>::SPILL : GroupGeom<TQ_GROUP>::SPILL;
     if constexpr (TQ_GROUP == 1) {
@@ -594,7 +588,7 @@ template <class R> int upload_scene(TakeScene *ts, const TakeSceneDesc &desc, co
     }
     per_cu = std::max(1, std::min(per_cu, 8));
     if (const char *e = std::getenv("TAKE_HIP_TRACE_BLOCKS")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));  // experiment: leave room for a concurrent kernel
-    sc.trace_grid = ts->num_cus * per_cu;
+    sc.trace_grid = num_cus * per_cu;
     sc.spill_stride = (int64_t)sc.trace_grid * groups_per_block;
     HIP_TRY(sc.spill.alloc((size_t)sc.spill_stride * spill_levels));
     clock.lap("shading tables -> HBM, grid");
@@ -871,12 +865,19 @@ void launch_round(TakeScene *ts, SceneT<RR> &sc, const RoundWs &ws, PathState<RR
     }
 }
 
+// the counters of a new call: zeros, and the bytes the traversal of `sc` reads per node and per primitive test
+template <class R> TakeCounters fresh_counters(const SceneT<R> &sc) {
+    TakeCounters c{};
+    c.node_bytes = sc.dev.qnodes8 ? sizeof(QNode8) : (sc.dev.qnodes ? sizeof(QNode4) : sizeof(Node4<R>));
+    c.prim_bytes = PRIM_TEST_BYTES * (int)(sizeof(R) / 4);
+    return c;
+}
+
 // first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
 // random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
 // to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
-template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
+template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
                                    int64_t first_sample = 0, bool keep_accum = false) {
-    SceneT<R> &sc = pick<R>(ts);
     if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
     const int W = sc.host.cam.width, H = sc.host.cam.height;
     if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
@@ -889,9 +890,7 @@ template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void 
     if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
     const int n_rows = rows_of(H, first, stride, nullptr);
     const int64_t npix = (int64_t)n_rows * W;
-    ts->counters = TakeCounters{};
-    ts->counters.node_bytes = sc.dev.qnodes8 ? sizeof(QNode8) : (sc.dev.qnodes ? sizeof(QNode4) : sizeof(Node4<R>));
-    ts->counters.prim_bytes = PRIM_TEST_BYTES * (int)(sizeof(R) / 4);
+    ts->counters = fresh_counters(sc);
     if (ts->precision == TAKE_PRECISION_MIXED) ts->counters.prim_bytes = PRIM_TEST_BYTES;  // (most rounds read the f32 records)
     if (npix == 0) return TAKE_OK;
     if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
@@ -989,10 +988,7 @@ template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void 
     HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
     hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
     HIP_TRY(hipEventRecord(ev_begin, stream));
-    if (!ts->poll_host) {
-        HIP_TRY(hipHostMalloc((void **)&ts->poll_host, sizeof(int32_t) * TakeScene::POLL_RING, hipHostMallocDefault));
-        for (int i = 0; i < TakeScene::POLL_RING; i++) HIP_TRY(hipEventCreateWithFlags(&ts->poll_ev[i], hipEventDisableTiming));
-    }
+    HIP_TRY(ts->poll.create());
     int64_t poll_issued = 0, poll_done = 0;
 
     for (int s0 = 0; s0 < o.spp; s0 += spb) {
@@ -1024,25 +1020,25 @@ template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void 
             // never waits for the GPU): any value that has arrived bounds the grids of all later rounds (queues only
             // shrink), and a zero ends the launching.  (Round 1 blocked on a stream sync every 4 rounds: with the
             // ~370 launches of a small render that was a third of its 12 ms.)
-            if (k + 1 < rounds && poll_issued - poll_done < TakeScene::POLL_RING) {
-                const int slot = poll_issued % TakeScene::POLL_RING;
-                HIP_TRY(hipMemcpyAsync(ts->poll_host + slot, n_next, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipEventRecord(ts->poll_ev[slot], stream));
+            if (k + 1 < rounds && poll_issued - poll_done < PollRing::SIZE) {
+                const int slot = poll_issued % PollRing::SIZE;
+                HIP_TRY(hipMemcpyAsync(ts->poll.word + slot, n_next, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipEventRecord(ts->poll.ev[slot], stream));
                 poll_issued++;
             }
             bool finished = false;
             while (poll_done < poll_issued) {
-                const int slot = poll_done % TakeScene::POLL_RING;
-                hipError_t q = hipEventQuery(ts->poll_ev[slot]);
+                const int slot = poll_done % PollRing::SIZE;
+                hipError_t q = hipEventQuery(ts->poll.ev[slot]);
                 if (q == hipErrorNotReady) {
                     (void)hipGetLastError();  // "not ready" is an answer, not an error: keep it out of the sticky state
                     // stay at most 8 rounds ahead of the GPU: enough queued work that it never idles, close enough
                     // that a batch whose paths have all ended stops being launched
                     if (poll_issued - poll_done < 8) break;
-                    q = hipEventSynchronize(ts->poll_ev[slot]);
+                    q = hipEventSynchronize(ts->poll.ev[slot]);
                 }
                 HIP_TRY(q);
-                const int32_t alive = ts->poll_host[slot];
+                const int32_t alive = ts->poll.word[slot];
                 poll_done++;
                 n_bound = std::min<int64_t>(n_bound, alive);
                 if (alive == 0) finished = true;
@@ -1105,9 +1101,8 @@ template <class R> int render_impl(TakeScene *ts, const TakeRenderOpts &o, void 
 }
 
 template <class R>
-int trace_impl(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any, bool count,
+int trace_impl(TakeScene *ts, SceneT<R> &sc, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any, bool count,
                hipStream_t stream) {
-    SceneT<R> &sc = pick<R>(ts);
     if (n < 0 || n >= ((int64_t)1 << 31) - (1 << 26)) return fail(TAKE_E_INVALID, "ray count out of range");
     StackSpill spill{sc.spill.p, sc.spill_stride};
     int32_t *q = sc.qwords.p;
@@ -1125,9 +1120,7 @@ int trace_impl(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, int32
     HIP_TRY(hipStreamSynchronize(stream));
     unsigned long long c[C_NUM_WORDS];
     HIP_TRY(hipMemcpy(c, sc.counters.p, sizeof c, hipMemcpyDeviceToHost));
-    ts->counters = TakeCounters{};
-    ts->counters.node_bytes = sc.dev.qnodes8 ? sizeof(QNode8) : (sc.dev.qnodes ? sizeof(QNode4) : sizeof(Node4<R>));
-    ts->counters.prim_bytes = PRIM_TEST_BYTES * (int)(sizeof(R) / 4);
+    ts->counters = fresh_counters(sc);
     (any ? ts->counters.rays_shadow : ts->counters.rays_closest) = (uint64_t)n;
     ts->counters.node_visits = c[C_NODE_VISITS];
     ts->counters.prim_tests = c[C_PRIM_TESTS];
@@ -1142,7 +1135,7 @@ int trace_impl(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, int32
     return TAKE_OK;
 }
 
-template <class R> int trace_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
+template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     if (n == 0) return TAKE_OK;
     // entry distances are ordered through their bit patterns (non-negative floats): a ray must start at tmin >= 0
     for (int64_t i = 0; i < n; i++) {
@@ -1156,12 +1149,20 @@ template <class R> int trace_host(TakeScene *ts, const void *rays, int64_t n, vo
     if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess)
         return fail(TAKE_E_DEVICE, "ray upload failed");
     if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) return fail(TAKE_E_NOMEM, "hit buffer allocation failed");
-    const int rc = trace_impl<R>(ts, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
+    const int rc = trace_impl(ts, sc, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
     if (rc) return rc;
     hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
                        : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(TAKE_E_DEVICE, "hit download failed");
     return TAKE_OK;
+}
+
+// a render of npix pixels into the scene's own output buffer, sc.out (-> img)
+template <class R> int render_to_out(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, const void *&img) {
+    int rc = ensure_workspace(sc, 0, npix);
+    if (!rc) rc = render_impl(ts, sc, o, sc.out.p, nullptr);
+    img = sc.out.p;
+    return rc;
 }
 
 // A scene lives on the device that was current when it was created; every entry point that touches it makes that
@@ -1201,15 +1202,15 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         return fail(TAKE_E_INVALID, "unknown precision");
     if (o.builder < TAKE_BUILDER_AUTO || o.builder > TAKE_BUILDER_HOST_SAH) return fail(TAKE_E_INVALID, "unknown builder");
     if (o.instances != TAKE_INSTANCES_TWO_LEVEL && o.instances != TAKE_INSTANCES_FLATTEN) return fail(TAKE_E_INVALID, "unknown instance mode");
-    TakeScene *ts = new (std::nothrow) TakeScene();
+    // (a scene that fails is freed on return, with its device current: nothing here changes the current device)
+    std::unique_ptr<TakeScene> ts(new (std::nothrow) TakeScene());
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
     ts->precision = o.precision;
     hipDeviceProp_t prop;
-    if (hipGetDevice(&ts->device) != hipSuccess || hipGetDeviceProperties(&prop, ts->device) != hipSuccess) {
-        delete ts;
+    if (hipGetDevice(&ts->device) != hipSuccess || hipGetDeviceProperties(&prop, ts->device) != hipSuccess)
         return fail(TAKE_E_DEVICE, "cannot query the HIP device");
-    }
     ts->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    const int threads = std::max(1, o.bvh_threads > 0 ? o.bvh_threads : (int)std::thread::hardware_concurrency());
     int rc;
     try {
         // device-array meshes (take_hip_mesh_from_ply): the host side of the build — index validation, the face / normal /
@@ -1219,49 +1220,32 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         FlattenedInstances flat;
         TakeSceneDesc local = *desc;
         if (o.instances == TAKE_INSTANCES_FLATTEN) {
-            int threads = o.bvh_threads > 0 ? o.bvh_threads : (int)std::thread::hardware_concurrency();
-            const int rf = flat.expand(local, std::max(1, threads));
-            if (rf) {
-                delete ts;
-                return rf;
-            }
+            const int rf = flat.expand(local, threads);
+            if (rf) return rf;
         }
-        desc = &local;  // (from here on: the description as it will be built)
-        const bool device_build = o.precision == TAKE_PRECISION_F32 && desc->n_shapes >= 8 && desc->n_instances == 0 &&
-                                  (o.builder == TAKE_BUILDER_DEVICE_LBVH || (o.builder == TAKE_BUILDER_AUTO && desc->n_shapes >= TAKE_AUTO_DEVICE_BUILD_SHAPES));
-        rc = staged.stage(local, !device_build);
-        struct Reset {
-            ~Reset() { t_staged = nullptr; }
-        } reset;
-        t_staged = &staged;
-        if (!rc) rc = o.precision != TAKE_PRECISION_F32 ? upload_scene<double>(ts, local, o) : upload_scene<float>(ts, local, o);
-        if (!rc && o.precision == TAKE_PRECISION_MIXED) rc = upload_scene<float>(ts, local, o);  // the same scene in f32 beside it
+        // builder of the f32 tree: AUTO = host SAH (best trees) up to 4M shapes, device LBVH beyond: at 10M triangles the
+        // host build is 6 s of setup against 0.2 s, for 2-6 % of traversal speed.  The device builder
+        // needs enough primitives to make a tree and no instances; f64 trees are built on the host.
+        const bool device_builder = local.n_shapes >= 8 && local.n_instances == 0 &&
+                                    (o.builder == TAKE_BUILDER_DEVICE_LBVH || (o.builder == TAKE_BUILDER_AUTO && local.n_shapes >= TAKE_AUTO_DEVICE_BUILD_SHAPES));
+        // every position comes to the host unless the device builder makes the only tree
+        rc = staged.stage(local, !(device_builder && o.precision == TAKE_PRECISION_F32));
+        // the f64 side of F64 and MIXED scenes, the f32 side of F32 and MIXED ones
+        if (!rc && o.precision != TAKE_PRECISION_F32) rc = upload_scene(ts->d, ts->num_cus, local, o, threads, device_builder, staged);
+        if (!rc && o.precision != TAKE_PRECISION_F64) rc = upload_scene(ts->f, ts->num_cus, local, o, threads, device_builder, staged);
     } catch (const std::bad_alloc &) {
         rc = fail(TAKE_E_NOMEM, "out of host memory while preparing the scene");
     } catch (const std::exception &e) {
         rc = fail(TAKE_E_INVALID, e.what());
     }
-    if (rc) {
-        ts->f.release();
-        ts->d.release();
-        delete ts;
-        return rc;
-    }
-    *out = ts;
+    if (rc) return rc;
+    *out = ts.release();
     return TAKE_OK;
 }
 
 int take_hip_scene_destroy(TakeScene *ts) {
     if (!ts) return TAKE_OK;
     DeviceGuard guard_(ts->device);
-    ts->f.release();
-    ts->d.release();
-    ts->events.destroy();
-    if (ts->poll_host) {
-        (void)hipHostFree(ts->poll_host);
-        for (auto e : ts->poll_ev)
-            if (e) (void)hipEventDestroy(e);
-    }
     delete ts;
     return TAKE_OK;
 }
@@ -1270,22 +1254,19 @@ int take_hip_render_rows(const TakeScene *ts, int32_t strip_first, int32_t strip
     if (!ts) return fail(TAKE_E_INVALID, "null scene");
     if (strip_stride <= 0 || strip_first < 0 || strip_first >= strip_stride)
         return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int H = is_f64(ts) ? ts->d.host.cam.height : ts->f.host.cam.height;
-    return rows_of(H, strip_first, strip_stride, rows_out);
+    return rows_of(ts->height(), strip_first, strip_stride, rows_out);
 }
 
 int take_hip_render_device(TakeScene *ts, const TakeRenderOpts *opts, void *d_rgb_out, void *stream) {
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    if (is_f64(ts)) return render_impl<double>(ts, *opts, d_rgb_out, (hipStream_t)stream);
-    return render_impl<float>(ts, *opts, d_rgb_out, (hipStream_t)stream);
+    return on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, *opts, d_rgb_out, (hipStream_t)stream); });
 }
 
 // Progressive rendering (the per-pixel accumulate of src/render.cpp:68-78 kept resident between calls).
 int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_t restart, void *d_rgb_out, void *stream) {
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    const bool f64 = is_f64(ts);
     const TakeRenderOpts &a = ts->acc_opts;
     const bool fresh = restart != 0 || ts->acc_samples == 0;
     // (mixed scenes: the exact rounds the samples were rendered with, <= 0 meaning the default; f32 / f64 ignore the field)
@@ -1301,8 +1282,7 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
     if (first + (int64_t)opts->spp >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many accumulated samples");
     // (a workspace grown for a bigger batch keeps the accumulator: ensure_workspace only ever enlarges it, and the
     // strip set — hence the pixel count — is fixed for the sequence)
-    const int rc = f64 ? render_impl<double>(ts, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh)
-                       : render_impl<float>(ts, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh);
+    const int rc = on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh); });
     if (rc) {
         ts->acc_samples = 0;  // the accumulator may hold a partial batch: the sequence has to restart
         return rc;
@@ -1316,27 +1296,20 @@ int64_t take_hip_accumulated_samples(const TakeScene *ts) { return ts ? ts->acc_
 int take_hip_render(TakeScene *ts, const TakeRenderOpts *opts, void *rgb_out_host) {
     if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    const bool f64 = is_f64(ts);
-    const int W = f64 ? ts->d.host.cam.width : ts->f.host.cam.width;
+    const int W = ts->width();
     const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
     if (opts->strip_first < 0 || opts->strip_first >= stride)
         return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
     const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
     if (rows < 0) return rows;
-    const size_t bytes = (size_t)rows * W * 3 * (f64 ? 8 : 4);
+    const size_t bytes = (size_t)rows * W * 3 * (ts->f64() ? 8 : 4);
     if (bytes == 0) return TAKE_OK;
     // render into the scene's own output buffer, then copy out
-    int rc;
-    if (f64) {
-        rc = ensure_workspace(ts->d, 0, (int64_t)rows * W);
-        if (!rc) rc = render_impl<double>(ts, *opts, ts->d.out.p, nullptr);
-        if (!rc) HIP_TRY(hipMemcpy(rgb_out_host, ts->d.out.p, bytes, hipMemcpyDeviceToHost));
-    } else {
-        rc = ensure_workspace(ts->f, 0, (int64_t)rows * W);
-        if (!rc) rc = render_impl<float>(ts, *opts, ts->f.out.p, nullptr);
-        if (!rc) HIP_TRY(hipMemcpy(rgb_out_host, ts->f.out.p, bytes, hipMemcpyDeviceToHost));
-    }
-    return rc;
+    const void *img = nullptr;
+    const int rc = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, *opts, (int64_t)rows * W, img); });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rgb_out_host, img, bytes, hipMemcpyDeviceToHost));
+    return TAKE_OK;
 }
 
 int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t width, int32_t height, uint16_t *d_out, void *stream) {
@@ -1358,14 +1331,11 @@ int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t wi
 int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uint16_t *out_host) {
     if (!ts || !opts || !out_host) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    const bool f64 = is_f64(ts);
-    const int W = f64 ? ts->d.host.cam.width : ts->f.host.cam.width, H = f64 ? ts->d.host.cam.height : ts->f.host.cam.height;
+    const int W = ts->width(), H = ts->height();
     TakeRenderOpts o = *opts;
     o.strip_first = 0, o.strip_stride = 1;
-    int rc = f64 ? ensure_workspace(ts->d, 0, (int64_t)W * H) : ensure_workspace(ts->f, 0, (int64_t)W * H);
-    if (rc) return rc;
-    void *d_img = f64 ? (void *)ts->d.out.p : (void *)ts->f.out.p;
-    rc = f64 ? render_impl<double>(ts, o, d_img, nullptr) : render_impl<float>(ts, o, d_img, nullptr);
+    const void *d_img = nullptr;
+    int rc = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, o, (int64_t)W * H, d_img); });
     if (rc) return rc;
     DevBuf<uint16_t> halves;
     if (halves.alloc((size_t)W * H * 3) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the scanline buffer");
@@ -1378,23 +1348,19 @@ int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uin
 int take_hip_trace_closest(TakeScene *ts, const void *rays, int64_t n, void *hits) {
     if (!ts || (n > 0 && (!rays || !hits))) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    return is_f64(ts) ? trace_host<double>(ts, rays, n, hits, nullptr, false)
-                                               : trace_host<float>(ts, rays, n, hits, nullptr, false);
+    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, hits, nullptr, false); });
 }
 int take_hip_trace_any(TakeScene *ts, const void *rays, int64_t n, int32_t *occluded) {
     if (!ts || (n > 0 && (!rays || !occluded))) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    return is_f64(ts) ? trace_host<double>(ts, rays, n, nullptr, occluded, true)
-                                               : trace_host<float>(ts, rays, n, nullptr, occluded, true);
+    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, nullptr, occluded, true); });
 }
 int take_hip_trace_closest_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, int32_t count_mode,
                                   void *stream) {
     if (!ts || (n > 0 && (!d_rays || !d_hits))) return fail(TAKE_E_INVALID, "null argument");
     if (n == 0) return TAKE_OK;
     TAKE_ON_DEVICE(ts);
-    return is_f64(ts)
-               ? trace_impl<double>(ts, d_rays, n, d_hits, nullptr, false, count_mode != 0, (hipStream_t)stream)
-               : trace_impl<float>(ts, d_rays, n, d_hits, nullptr, false, count_mode != 0, (hipStream_t)stream);
+    return on_primary(ts, [&](auto &sc) { return trace_impl(ts, sc, d_rays, n, d_hits, nullptr, false, count_mode != 0, (hipStream_t)stream); });
 }
 
 int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int64_t n, int32_t in_cols,
@@ -1454,28 +1420,11 @@ template <class T> int peer_copy(DevBuf<T> &dst, int dst_dev, const DevBuf<T> &s
 }
 template <class R> int replicate_t(const SceneT<R> &a, int a_dev, int a_cus, SceneT<R> &b, int b_dev, int b_cus) {
     int rc = TAKE_OK;
-#define TK_COPY(member) if (!rc) rc = peer_copy(b.member, b_dev, a.member, a_dev)
-    TK_COPY(nodes); TK_COPY(qnodes); TK_COPY(qnodes8); TK_COPY(prims); TK_COPY(meshes); TK_COPY(face_idx); TK_COPY(normals); TK_COPY(uvs);
-    TK_COPY(texels); TK_COPY(materials); TK_COPY(images); TK_COPY(lights); TK_COPY(light_pmf); TK_COPY(light_cdf);
-    TK_COPY(inst_trace); TK_COPY(inst_shade); TK_COPY(env_marginal); TK_COPY(env_conditional); TK_COPY(env_guide_m);
-    TK_COPY(env_guide_c);
-#undef TK_COPY
+    SceneT<R>::for_each_array([&](auto &dst, const auto &src) { if (!rc) rc = peer_copy(dst, b_dev, src, a_dev); }, b, a);
     if (rc) return rc;
-    // small host tables (the large vectors were dropped after the upload)
-    b.host.cam = a.host.cam;
-    b.host.env = a.host.env;
-    b.host.stats = a.host.stats;
-    b.host.n_material_tags = a.host.n_material_tags, b.host.tag_mask = a.host.tag_mask, b.host.single_tag = a.host.single_tag;
-    b.host.q_inflation = a.host.q_inflation, b.host.root_child = a.host.root_child, b.host.node_width = a.host.node_width;
-    b.host.n_blas = a.host.n_blas, b.host.blas_nodes = a.host.blas_nodes, b.host.blas_prims = a.host.blas_prims;
-    for (int k = 0; k < 3; k++) b.host.grid_lo[k] = a.host.grid_lo[k], b.host.grid_step[k] = a.host.grid_step[k], b.host.background[k] = a.host.background[k];
-    DeviceScene<R> &d = b.dev;
-    d = a.dev;  // the plain values; then the pointers of this device
-    d.nodes = b.nodes.p, d.qnodes = a.dev.qnodes ? b.qnodes.p : nullptr, d.qnodes8 = b.qnodes8.p, d.prims = b.prims.p, d.shapes = nullptr;
-    d.meshes = b.meshes.p, d.face_idx = b.face_idx.p, d.normals = b.normals.p, d.uvs = b.uvs.p, d.texels = b.texels.p;
-    d.materials = b.materials.p, d.images = b.images.p, d.lights = b.lights.p, d.light_pmf = b.light_pmf.p, d.light_cdf = b.light_cdf.p;
-    d.inst_trace = b.inst_trace.p, d.inst_shade = b.inst_shade.p;
-    d.env.marginal = b.env_marginal.p, d.env.conditional = b.env_conditional.p, d.env.guide_m = b.env_guide_m.p, d.env.guide_c = b.env_guide_c.p;
+    b.host = a.host;  // (the camera, counts and small tables: upload_scene dropped the large vectors)
+    b.dev = a.dev;    // the plain values; then the pointers of this device
+    b.bind();
     // the persistent trace grid of THIS device: blocks per CU are a property of the kernels (the same code object on
     // every device), the CU count is the replica device's own
     const int per_cu = std::max(1, a.trace_grid / std::max(1, a_cus));
@@ -1492,37 +1441,41 @@ template <class R> int replicate_t(const SceneT<R> &a, int a_dev, int a_cus, Sce
 // -> a new scene handle on `device` (made current for the call), equal to `src`
 int replicate_scene(const TakeScene *src, int device, TakeScene **out) {
     *out = nullptr;
-    TakeScene *ts = new (std::nothrow) TakeScene();
+    DeviceGuard guard(device);  // (declared before the replica: a failed one is freed with its device current)
+    std::unique_ptr<TakeScene> ts(new (std::nothrow) TakeScene());
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
     ts->precision = src->precision, ts->device = device, ts->num_cus = src->num_cus, ts->instrumentation = 0;
-    DeviceGuard guard(device);
-    int rc = guard.ok ? TAKE_OK : fail(TAKE_E_DEVICE, "cannot make the replica's device current");
-    if (!rc) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ts->num_cus = cus;
-        (void)hipGetLastError();
-    }
-    if (!rc) rc = is_f64(src) ? replicate_t(src->d, src->device, src->num_cus, ts->d, device, ts->num_cus)
-                              : replicate_t(src->f, src->device, src->num_cus, ts->f, device, ts->num_cus);
-    if (!rc && src->precision == TAKE_PRECISION_MIXED) rc = replicate_t(src->f, src->device, src->num_cus, ts->f, device, ts->num_cus);
-    if (rc) {
-        ts->f.release(), ts->d.release();
-        delete ts;
-        return rc;
-    }
-    *out = ts;
+    if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the replica's device current");
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ts->num_cus = cus;
+    (void)hipGetLastError();
+    // the sides take_hip_scene_create made, in its order
+    int rc = TAKE_OK;
+    if (src->precision != TAKE_PRECISION_F32) rc = replicate_t(src->d, src->device, src->num_cus, ts->d, device, ts->num_cus);
+    if (!rc && src->precision != TAKE_PRECISION_F64) rc = replicate_t(src->f, src->device, src->num_cus, ts->f, device, ts->num_cus);
+    if (rc) return rc;
+    *out = ts.release();
     return TAKE_OK;
 }
 }  // namespace
 
 struct TakeSceneGroup {
-    std::vector<TakeScene *> scenes;  // one per shard, each on its device
-    std::vector<void *> staging;      // on the first device: shard k's compact rows (k > 0), copied peer to peer
-    std::vector<int32_t *> d_rows;    // on the first device: image row of each compact row of shard k
+    std::vector<TakeScene *> scenes;        // one per shard, each on its device
+    std::vector<DevBuf<char>> staging;      // on the first device: shard k's compact rows (k > 0), copied peer to peer
+    std::vector<DevBuf<int32_t>> d_rows;    // on the first device: image row of each compact row of shard k
     std::vector<int> n_rows;
-    void *d_full = nullptr;           // on the first device: the assembled image (take_hip_group_render)
+    DevBuf<char> d_full;                    // on the first device: the assembled image (take_hip_group_render)
     int width = 0, height = 0;
     bool f64 = false;
+    ~TakeSceneGroup() {
+        // the group's buffers are freed here, in the guard's scope: freed as members, they would go after the guard
+        // (they exist only once the first shard does)
+        if (!scenes.empty()) {
+            DeviceGuard guard(scenes[0]->device);
+            staging.clear(), d_rows.clear(), d_full = DevBuf<char>();
+        }
+        for (TakeScene *ts : scenes) take_hip_scene_destroy(ts);
+    }
 };
 
 namespace {
@@ -1535,20 +1488,6 @@ __global__ void __launch_bounds__(BLOCK) k_place_rows(const R *__restrict__ src,
         const int r = (int)(i / row_words), c = (int)(i % row_words);
         dst[(int64_t)rows[r] * row_words + c] = src[i];
     }
-}
-
-void group_release(TakeSceneGroup *g) {
-    if (!g) return;
-    if (!g->scenes.empty() && g->scenes[0]) {
-        DeviceGuard guard(g->scenes[0]->device);
-        for (void *p : g->staging)
-            if (p) (void)hipFree(p);
-        for (int32_t *p : g->d_rows)
-            if (p) (void)hipFree(p);
-        if (g->d_full) (void)hipFree(g->d_full);
-    }
-    for (TakeScene *ts : g->scenes) take_hip_scene_destroy(ts);
-    delete g;
 }
 
 int group_render(TakeSceneGroup *g, const TakeRenderOpts &opts, void *d_out) {
@@ -1570,12 +1509,10 @@ int group_render(TakeSceneGroup *g, const TakeRenderOpts &opts, void *d_out) {
                 rc[k] = TAKE_E_DEVICE, err[k] = "cannot make the shard's device current";
                 return;
             }
-            int r = g->f64 ? ensure_workspace(ts->d, 0, (int64_t)g->n_rows[k] * g->width)
-                           : ensure_workspace(ts->f, 0, (int64_t)g->n_rows[k] * g->width);
-            if (!r) r = g->f64 ? render_impl<double>(ts, o, ts->d.out.p, nullptr) : render_impl<float>(ts, o, ts->f.out.p, nullptr);
+            const void *rows = nullptr;
+            int r = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, o, (int64_t)g->n_rows[k] * g->width, rows); });
             if (!r && k > 0) {  // the one exchange: this shard's rows to the first device
-                const hipError_t e = hipMemcpyPeer(g->staging[k], g->scenes[0]->device, g->f64 ? (void *)ts->d.out.p : (void *)ts->f.out.p,
-                                                   ts->device, (size_t)g->n_rows[k] * row_words * esz);
+                const hipError_t e = hipMemcpyPeer(g->staging[k].p, g->scenes[0]->device, rows, ts->device, (size_t)g->n_rows[k] * row_words * esz);
                 if (e != hipSuccess) r = TAKE_E_DEVICE, g_error = std::string("hipMemcpyPeer: ") + hipGetErrorString(e);
             }
             rc[k] = r;
@@ -1587,14 +1524,16 @@ int group_render(TakeSceneGroup *g, const TakeRenderOpts &opts, void *d_out) {
     // assemble on the first device
     DeviceGuard guard(g->scenes[0]->device);
     if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the first device current");
-    for (int k = 0; k < n; k++) {
-        if (g->n_rows[k] == 0) continue;
-        const void *src = k == 0 ? (g->f64 ? (void *)g->scenes[0]->d.out.p : (void *)g->scenes[0]->f.out.p) : g->staging[k];
-        const int64_t total = (int64_t)g->n_rows[k] * row_words;
-        const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 4096));
-        if (g->f64) hipLaunchKernelGGL((k_place_rows<double>), grid, dim3(BLOCK), 0, nullptr, (const double *)src, g->d_rows[k], g->n_rows[k], row_words, (double *)d_out);
-        else hipLaunchKernelGGL((k_place_rows<float>), grid, dim3(BLOCK), 0, nullptr, (const float *)src, g->d_rows[k], g->n_rows[k], row_words, (float *)d_out);
-    }
+    on_primary(g->scenes[0], [&](auto &sc0) {
+        using R = std::remove_pointer_t<decltype(sc0.out.p)>;
+        for (int k = 0; k < n; k++) {
+            if (g->n_rows[k] == 0) continue;
+            const R *src = k == 0 ? sc0.out.p : (const R *)g->staging[k].p;
+            const int64_t total = (int64_t)g->n_rows[k] * row_words;
+            const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 4096));
+            hipLaunchKernelGGL((k_place_rows<R>), grid, dim3(BLOCK), 0, nullptr, src, g->d_rows[k].p, g->n_rows[k], row_words, (R *)d_out);
+        }
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return TAKE_OK;
@@ -1614,7 +1553,7 @@ int take_hip_group_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         const int dev = devices ? devices[k] : k;
         if (dev < 0 || dev >= nd) return fail(TAKE_E_INVALID, "device " + std::to_string(dev) + " of shard " + std::to_string(k) + " is not visible (" + std::to_string(nd) + " devices)");
     }
-    TakeSceneGroup *g = new (std::nothrow) TakeSceneGroup();
+    std::unique_ptr<TakeSceneGroup> g(new (std::nothrow) TakeSceneGroup());
     if (!g) return fail(TAKE_E_NOMEM, "out of host memory");
     int prev = 0;
     (void)hipGetDevice(&prev);
@@ -1637,20 +1576,17 @@ int take_hip_group_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
             x->mem_share = share;
         }
         TakeScene *t0 = g->scenes[0];
-        g->f64 = is_f64(t0);
-        g->width = g->f64 ? t0->d.host.cam.width : t0->f.host.cam.width;
-        g->height = g->f64 ? t0->d.host.cam.height : t0->f.host.cam.height;
+        g->f64 = t0->f64(), g->width = t0->width(), g->height = t0->height();
         const size_t esz = g->f64 ? 8 : 4;
-        g->staging.assign(n_gpus, nullptr), g->d_rows.assign(n_gpus, nullptr), g->n_rows.assign(n_gpus, 0);
+        g->staging.resize(n_gpus), g->d_rows.resize(n_gpus), g->n_rows.assign(n_gpus, 0);
         if (hipSetDevice(t0->device) != hipSuccess) rc = fail(TAKE_E_DEVICE, "hipSetDevice failed");
         for (int k = 0; k < n_gpus && !rc; k++) {
             std::vector<int32_t> rows((size_t)g->height);
             const int nr = rows_of(g->height, k, n_gpus, rows.data());
+            rows.resize(nr);
             g->n_rows[k] = nr;
             if (nr == 0) continue;
-            if (hipMalloc((void **)&g->d_rows[k], (size_t)nr * sizeof(int32_t)) != hipSuccess ||
-                hipMemcpy(g->d_rows[k], rows.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                (k > 0 && hipMalloc(&g->staging[k], (size_t)nr * g->width * 3 * esz) != hipSuccess))
+            if (g->d_rows[k].upload(rows) != hipSuccess || (k > 0 && g->staging[k].alloc((size_t)nr * g->width * 3 * esz) != hipSuccess))
                 rc = fail(TAKE_E_NOMEM, "out of device memory for the strip staging buffers");
             if (!rc && k > 0 && g->scenes[k]->device != t0->device) {
                 // direct peer access if the fabric offers it (hipMemcpyPeer works either way)
@@ -1662,17 +1598,13 @@ int take_hip_group_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         }
     }
     (void)hipSetDevice(prev);
-    if (rc) {
-        const std::string msg = g_error;
-        group_release(g);
-        return fail(rc, msg);
-    }
-    *out = g;
+    if (rc) return rc;
+    *out = g.release();
     return TAKE_OK;
 }
 
 int take_hip_group_destroy(TakeSceneGroup *g) {
-    group_release(g);
+    delete g;
     return TAKE_OK;
 }
 int take_hip_group_size(const TakeSceneGroup *g) { return g ? (int)g->scenes.size() : fail(TAKE_E_INVALID, "null group"); }
@@ -1687,13 +1619,10 @@ int take_hip_group_render(TakeSceneGroup *g, const TakeRenderOpts *opts, void *r
     const size_t bytes = (size_t)g->width * g->height * 3 * (g->f64 ? 8 : 4);
     DeviceGuard guard(g->scenes[0]->device);
     if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the first device current");
-    if (!g->d_full && hipMalloc(&g->d_full, bytes) != hipSuccess) {
-        g->d_full = nullptr;
-        return fail(TAKE_E_NOMEM, "out of device memory for the assembled image");
-    }
-    const int rc = group_render(g, *opts, g->d_full);
+    if (!g->d_full.p && g->d_full.alloc(bytes) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the assembled image");
+    const int rc = group_render(g, *opts, g->d_full.p);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(rgb_out_host, g->d_full, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rgb_out_host, g->d_full.p, bytes, hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
 
@@ -1716,12 +1645,12 @@ int take_hip_set_instrumentation(TakeScene *ts, int32_t flags) {
 int take_hip_scene_stats(const TakeScene *ts, int64_t *n_nodes, int64_t *n_prims, int32_t *depth,
                          int64_t *device_bytes) {
     if (!ts) return fail(TAKE_E_INVALID, "null scene");
-    const bool f64 = is_f64(ts);
-    const WideBvhStats &s = f64 ? ts->d.host.stats : ts->f.host.stats;
+    const WideBvhStats s = on_primary(ts, [](const auto &sc) { return sc.host.stats; });
     if (n_nodes) *n_nodes = s.n_nodes;
     if (n_prims) *n_prims = s.n_prims;
     if (depth) *depth = s.depth;
-    if (device_bytes) *device_bytes = (int64_t)((f64 ? ts->d.scene_bytes() : 0) + (ts->precision != TAKE_PRECISION_F64 ? ts->f.scene_bytes() : 0));
+    // (a side the scene's precision does not make is empty: 0 bytes)
+    if (device_bytes) *device_bytes = (int64_t)(ts->d.scene_bytes() + ts->f.scene_bytes());
     return TAKE_OK;
 }
 
