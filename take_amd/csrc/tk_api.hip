@@ -301,26 +301,20 @@ struct FlattenedInstances {
             for (int64_t i = lo; i < hi; i++) {
                 const TakeInstance &in = d.instances[i];
                 const TakeMesh &m = d.meshes[in.mesh_id];
-                const double *x = in.xform;
-                const double a00 = x[0], a01 = x[1], a02 = x[2], a10 = x[4], a11 = x[5], a12 = x[6], a20 = x[8], a21 = x[9], a22 = x[10];
+                const Affine3 x{in.xform};
                 std::vector<double> &pos = arrays[2 * (size_t)i], &nrm = arrays[2 * (size_t)i + 1];
                 pos.resize(3 * (size_t)m.n_vertices);
                 for (int64_t v = 0; v < m.n_vertices; v++) {
                     const double px = m.positions[3 * v], py = m.positions[3 * v + 1], pz = m.positions[3 * v + 2];
-                    pos[3 * v + 0] = a00 * px + a01 * py + a02 * pz + x[3];
-                    pos[3 * v + 1] = a10 * px + a11 * py + a12 * pz + x[7];
-                    pos[3 * v + 2] = a20 * px + a21 * py + a22 * pz + x[11];
+                    for (int a = 0; a < 3; a++) pos[3 * v + a] = x.image(a, px, py, pz);
                 }
                 if (m.normals) {
-                    const double det = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
-                    if (!(std::fabs(det) > 1e-300)) {
+                    double inv[9];
+                    if (!x.inverse_linear(inv)) {
                         std::lock_guard<std::mutex> lock(mu);
                         err = "instance " + std::to_string(i) + ": singular transform";
                         return;
                     }
-                    const double inv[9] = {(a11 * a22 - a12 * a21) / det, (a02 * a21 - a01 * a22) / det, (a01 * a12 - a02 * a11) / det,
-                                           (a12 * a20 - a10 * a22) / det, (a00 * a22 - a02 * a20) / det, (a02 * a10 - a00 * a12) / det,
-                                           (a10 * a21 - a11 * a20) / det, (a01 * a20 - a00 * a21) / det, (a00 * a11 - a01 * a10) / det};
                     nrm.resize(3 * (size_t)m.n_vertices);
                     for (int64_t v = 0; v < m.n_vertices; v++) {
                         const double nx = m.normals[3 * v], ny = m.normals[3 * v + 1], nz = m.normals[3 * v + 2];
@@ -508,7 +502,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     const char *fmt_env = std::getenv("TAKE_HIP_NODES");
     const std::string fmt = fmt_env ? fmt_env : "";
     bool on_device = device_builder && sizeof(R) == 4;  // (the f64 side of a mixed-precision scene: the host builder)
-    std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_TABLES : PREP_ALL, opts.burley_lobes != 0);
+    std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_DEVICE_BUILD : PREP_HOST_BUILD, opts.burley_lobes != 0);
     if (!err.empty()) return fail(TAKE_E_INVALID, err);
     clock.lap(on_device ? "host validation + tables" : "host records + SAH build");
     HostScene<R> &h = sc.host;
@@ -521,7 +515,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
                 on_device = false;
                 const int rs = staged.ensure_positions();
                 if (rs) return rs;
-                err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_ALL, opts.burley_lobes != 0);
+                err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_HOST_BUILD, opts.burley_lobes != 0);
                 if (!err.empty()) return fail(TAKE_E_INVALID, err);
             } else if (rc != TAKE_OK) {
                 return rc;
