@@ -26,6 +26,7 @@ EXPORTS = [
     "take_hip_ply_layout", "take_hip_mesh_from_ply", "take_hip_mesh_from_ply_file",
     "take_hip_mesh_from_serialized", "take_hip_mesh_from_serialized_file", "take_hip_mesh_download", "take_hip_mesh_release",
     "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
+    "take_hip_scene_build_info",
 ]
 
 
@@ -71,6 +72,7 @@ def lib():
         L.take_hip_set_instrumentation.argtypes = [C.c_void_p, C.c_int32]
         L.take_hip_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
         L.take_hip_group_create.argtypes = [C.POINTER(D.TakeSceneDesc), C.POINTER(D.TakeBuildOpts), C.c_int32,
@@ -340,6 +342,13 @@ class Scene:
         nn, npr, dep, by = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
         _check(lib().take_hip_scene_stats(self.h, C.byref(nn), C.byref(npr), C.byref(dep), C.byref(by)))
         return {"n_nodes": nn.value, "n_prims": npr.value, "depth": dep.value, "device_bytes": by.value}
+
+    def build_info(self):
+        """who built the trees: {"f32": builder, "f64": builder}, each TAKE_BUILDER_DEVICE_LBVH, TAKE_BUILDER_HOST_SAH
+        (asked for, or the fall-back of a device build) or -1 for a side a scene of this precision does not have"""
+        f, d = C.c_int32(), C.c_int32()
+        _check(lib().take_hip_scene_build_info(self.h, C.byref(f), C.byref(d)))
+        return {"f32": f.value, "f64": d.value}
 
 
 class SceneGroup:

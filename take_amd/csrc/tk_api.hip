@@ -158,12 +158,41 @@ namespace {
 // f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
 template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
 
+// device memory in use (the whole device's, as hipMemGetInfo sees it), for the TAKE_HIP_VERBOSE lines; 0 if the runtime
+// cannot say
+double device_mb_in_use() {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
+    return (double)(total_b - free_b) / 1e6;
+}
+// The high-water mark of a device build (TAKE_HIP_VERBOSE only): sampled where a phase holds the most — after the last
+// allocation of the sort, the hierarchy, the collapse, the compression and the permute — each phase freeing what the
+// next ones do not read.
+struct BuildMemory {
+    bool on = std::getenv("TAKE_HIP_VERBOSE") != nullptr;
+    const char *side;
+    double peak = 0;
+    const char *peak_at = "";
+    explicit BuildMemory(const char *side_) : side(side_) {}
+    void sample(const char *phase) {
+        if (!on) return;
+        const double mb = device_mb_in_use();
+        std::fprintf(stderr, "[take_hip] scene_create: %s device build, %-12s %8.1f MB of device memory in use\n", side, phase, mb);
+        if (mb > peak) peak = mb, peak_at = phase;
+    }
+    void report() const {
+        if (on) std::fprintf(stderr, "[take_hip] scene_create: %s device build, peak %.1f MB of device memory in use (%s)\n", side, peak, peak_at);
+    }
+};
+
 // BVH build on the device (tk_build_gpu.h).  In: sc.prims uploaded in SHAPE order.  Out: the records in
 // leaf order, sc.nodes or sc.qnodes, host-side stats and grid.  Returns TAKE_OK, an error, or 1 = "use the host
 // builder" (tree deeper than the traversal stack allows: long runs of equal Morton codes).
-int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool compressed_forced) {
+// The tree is made of float nodes whatever R is (tk_build_gpu.h: only records and primitive boxes know the
+// precision); a double scene that is refused compression gets them widened, n_nodes of them.
+template <class R> int build_bvh_device(SceneT<R> &sc, int max_leaf, bool compressed_ok, bool compressed_forced) {
     using namespace lbvh;
-    HostScene<float> &h = sc.host;
+    HostScene<R> &h = sc.host;
     const int n = (int)sc.prims.n;
     // default 1 primitive per leaf: two Morton neighbours need not be close, and a leaf box around both costs more
     // primitive tests than the extra node (1M soup, 16 spp: 1 / 2 / 4 per leaf = 55.2 / 38.3 / 30.0 Msamples/s)
@@ -173,7 +202,9 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     auto grid = [](int64_t items) { return dim3((unsigned)((items + BLK - 1) / BLK)); };
+    BuildMemory mem(sizeof(R) == 4 ? "f32" : "f64");
 
+    // (a release waits for the kernels launched before it: hipFree synchronises the device)
     DevBuf<Box> pb, lbox, ibox;
     DevBuf<uint64_t> keys, keys_s, lkey;
     DevBuf<uint32_t> vals, vals_s;
@@ -181,6 +212,8 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     DevBuf<int2> child;
     DevBuf<char> temp;
     DevBuf<double> acc;
+    DevBuf<Node4<float>> fnodes;
+    // boxes, Morton codes, sort
     HIP_TRY(pb.alloc(n));
     HIP_TRY(keys.alloc(n));
     HIP_TRY(vals.alloc(n));
@@ -189,46 +222,51 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     HIP_TRY(scene_ord.alloc(6));
     const int ord_init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
     HIP_TRY(hipMemcpy(scene_ord.p, ord_init, sizeof(ord_init), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_prim_boxes, grid(n), blk, 0, stream, sc.prims.p, n, pb.p, scene_ord.p);
+    hipLaunchKernelGGL(k_prim_boxes<R>, grid(n), blk, 0, stream, sc.prims.p, n, pb.p, scene_ord.p);
     hipLaunchKernelGGL(k_morton, grid(n), blk, 0, stream, pb.p, n, scene_ord.p, keys.p, vals.p);
     size_t temp_bytes = 0;
     HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)n, 0, 63, stream));
     HIP_TRY(temp.alloc(temp_bytes));
+    mem.sample("sort");
     HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, keys.p, keys_s.p, vals.p, vals_s.p, (size_t)n, 0, 63, stream));
+    keys.release(), vals.release(), temp.release();
 
+    // leaves, hierarchy, refit
     HIP_TRY(lbox.alloc(n_leaves));
     HIP_TRY(lkey.alloc(n_leaves));
+    hipLaunchKernelGGL(k_leaves, grid(n_leaves), blk, 0, stream, pb.p, keys_s.p, vals_s.p, n, leaf_size, n_leaves, lbox.p, lkey.p);
+    pb.release(), keys_s.release();
     HIP_TRY(ibox.alloc(n_leaves));
     HIP_TRY(child.alloc(n_leaves));
     HIP_TRY(parent_i.alloc(n_leaves));
     HIP_TRY(parent_l.alloc(n_leaves));
     HIP_TRY(flag.alloc(n_leaves));
+    mem.sample("hierarchy");
     HIP_TRY(hipMemsetAsync(flag.p, 0, flag.bytes(), stream));
-    hipLaunchKernelGGL(k_leaves, grid(n_leaves), blk, 0, stream, pb.p, keys_s.p, vals_s.p, n, leaf_size, n_leaves, lbox.p, lkey.p);
     hipLaunchKernelGGL(k_hierarchy, grid(n_leaves - 1), blk, 0, stream, lkey.p, n_leaves, child.p, parent_i.p, parent_l.p);
     hipLaunchKernelGGL(k_refit, grid(n_leaves), blk, 0, stream, n_leaves, child.p, parent_i.p, parent_l.p, lbox.p, ibox.p, flag.p);
+    lkey.release(), parent_i.release(), parent_l.release(), flag.release();
 
-    // collapse to 4-wide nodes, breadth-first, one launch per level
-    HIP_TRY(sc.nodes.alloc(n_leaves));
+    // collapse to 4-wide nodes, breadth-first, one launch per level (at most one node per leaf; the count is known after)
+    HIP_TRY(fnodes.alloc(n_leaves));
     HIP_TRY(frontier[0].alloc(n_leaves));
     HIP_TRY(frontier[1].alloc(n_leaves));
     HIP_TRY(lvl.alloc(MAX_LEVELS + 2));
+    mem.sample("collapse");
     HIP_TRY(hipMemsetAsync(lvl.p, 0, lvl.bytes(), stream));
     hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, lvl.p, 1, 1);           // one node on level 0 ...
     hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, frontier[0].p, 1, 0);   // ... made from BVH2 node 0
     const int cgrid = std::max(1, std::min((n_leaves + BLK - 1) / BLK, 2048));
     for (int level = 0; level < MAX_LEVELS; level++)
         hipLaunchKernelGGL(k_collapse, dim3(cgrid), blk, 0, stream, level, frontier[level & 1].p, frontier[(level + 1) & 1].p,
-                           lvl.p, child.p, ibox.p, lbox.p, leaf_size, n, sc.nodes.p);
+                           lvl.p, child.p, ibox.p, lbox.p, leaf_size, n, fnodes.p);
     int lvl_h[MAX_LEVELS + 2];
     int ord_h[6];
     HIP_TRY(hipMemcpyAsync(lvl_h, lvl.p, sizeof(lvl_h), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(ord_h, scene_ord.p, sizeof(ord_h), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    if (lvl_h[MAX_LEVELS] != 0) {
-        sc.nodes.release();
-        return 1;  // deeper than the traversal stack allows
-    }
+    if (lvl_h[MAX_LEVELS] != 0) return 1;  // deeper than the traversal stack allows
+    lbox.release(), ibox.release(), child.release(), frontier[0].release(), frontier[1].release();
     int64_t n_nodes = 0;
     int depth = 0;
     for (int k = 0; k < MAX_LEVELS; k++)
@@ -236,7 +274,7 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
     h.stats = WideBvhStats{};
     h.stats.n_nodes = n_nodes, h.stats.n_prims = n, h.stats.depth = depth;
     h.root_child = 0;
-    sc.nodes.n = (size_t)n_nodes;  // the tail of the allocation is unused
+    fnodes.n = (size_t)n_nodes;  // the tail of the allocation is unused
 
     // compressed nodes on the scene grid (same fall-back rule as the host path)
     h.q_inflation = 1.0;
@@ -247,23 +285,36 @@ int build_bvh_device(SceneT<float> &sc, int max_leaf, bool compressed_ok, bool c
         const QGrid g = make_qgrid(lo, hi);
         HIP_TRY(sc.qnodes.alloc((size_t)n_nodes));
         HIP_TRY(acc.alloc(2));
+        mem.sample("compression");
         HIP_TRY(hipMemsetAsync(acc.p, 0, acc.bytes(), stream));
-        hipLaunchKernelGGL(k_quantise, grid(n_nodes), blk, 0, stream, sc.nodes.p, (int)n_nodes, g, sc.qnodes.p, acc.p);
+        hipLaunchKernelGGL(k_quantise, grid(n_nodes), blk, 0, stream, fnodes.p, (int)n_nodes, g, sc.qnodes.p, acc.p);
         double acc_h[2] = {0, 0};
         HIP_TRY(hipMemcpy(acc_h, acc.p, sizeof(acc_h), hipMemcpyDeviceToHost));
         h.q_inflation = acc_h[1] > 0 ? acc_h[0] / acc_h[1] : 1.0;
         use_q = compressed_forced || h.q_inflation <= 1.10;
         for (int a = 0; a < 3; a++) h.grid_lo[a] = g.lo[a], h.grid_step[a] = g.step[a];
-        if (use_q) sc.nodes.release();
-        else sc.qnodes.release();
+        if (!use_q) sc.qnodes.release();
     }
-    // records into leaf order
-    DevBuf<PrimRec<float>> prims_sorted;
+    if (!use_q) {  // full-width nodes: the float ones as they are, or widened to double (exact: still conservative)
+        if constexpr (sizeof(R) == 4) {
+            sc.nodes = std::move(fnodes);
+        } else {
+            HIP_TRY(sc.nodes.alloc((size_t)n_nodes));
+            mem.sample("wide nodes");
+            hipLaunchKernelGGL(k_widen_nodes, grid(n_nodes), blk, 0, stream, fnodes.p, (int)n_nodes, sc.nodes.p);
+        }
+    }
+    fnodes.release();
+    // records into leaf order (a stable sort: coincident primitives stay in shape order): shape-order and leaf-order
+    // records coexist, next to the permutation and the finished nodes only
+    DevBuf<PrimRec<R>> prims_sorted;
     HIP_TRY(prims_sorted.alloc(n));
-    hipLaunchKernelGGL((k_permute<PrimRec<float>>), grid(n), blk, 0, stream, sc.prims.p, vals_s.p, n, prims_sorted.p);
+    mem.sample("permute");
+    hipLaunchKernelGGL((k_permute<PrimRec<R>>), grid(n), blk, 0, stream, sc.prims.p, vals_s.p, n, prims_sorted.p);
     HIP_TRY(hipStreamSynchronize(stream));
     sc.prims = std::move(prims_sorted);  // (frees the shape-order records)
     HIP_TRY(hipGetLastError());
+    mem.report();
     return TAKE_OK;
 }
 // TAKE_INSTANCES_FLATTEN: the description with every placement expanded to a world-space mesh of its own — the geometry
@@ -417,60 +468,86 @@ struct StagedMeshes {
     }
 };
 
-// Primitive records on the device from the caller's arrays (tk_build_gpu.h::k_make_prims): the mesh positions go up as
-// they are (double, one copy per mesh, no host staging), the face indices are the validated concatenation the shading
-// side keeps anyway (sc.face_idx, uploaded here), the four shape arrays go up as they are.
+// What k_make_prims reads of the caller's arrays, in device memory: the mesh positions as they are (double, one copy
+// per mesh, no host staging) and the four shape arrays.  Uploaded once per scene: both sides of a mixed-precision
+// scene make their records from these.
 // device_positions: per mesh, positions that are in device memory already (a mesh take_hip_mesh_from_ply decoded; the
 // description then holds host copies of what the host side validates and tabulates, not of these), or null
-int make_prims_on_device(SceneT<float> &sc, const TakeSceneDesc &d, const double *const *device_positions) {
+struct DeviceBuildInputs {
+    DevBuf<double> pos;
+    DevBuf<int32_t> kind, ref, face, area_light;
+    std::vector<int64_t> pos_off;         // per mesh: its first vertex in pos
+    const int32_t *face_idx = nullptr;    // the validated face indices on the device: the array of the side that uploaded them
+    bool ready = false;
+    int upload(const TakeSceneDesc &d, const double *const *device_positions) {
+        if (ready) return TAKE_OK;
+        const size_t n = (size_t)d.n_shapes;
+        pos_off.resize((size_t)d.n_meshes);
+        int64_t nv = 0;
+        for (int i = 0; i < d.n_meshes; i++) pos_off[i] = nv, nv += d.meshes[i].n_vertices;
+        HIP_TRY(pos.alloc(3 * (size_t)std::max<int64_t>(nv, 1)));
+        PinnedUploads pin;
+        for (int i = 0; i < d.n_meshes; i++) {
+            if (d.meshes[i].n_vertices <= 0) continue;
+            const size_t bytes = sizeof(double) * 3 * (size_t)d.meshes[i].n_vertices;
+            // a mesh decoded on the device (take_hip_mesh_from_ply): its positions never were on the host
+            if (device_positions && device_positions[i])
+                HIP_TRY(hipMemcpyAsync(pos.p + 3 * pos_off[i], device_positions[i], bytes, hipMemcpyDeviceToDevice, pin.stream));
+            else
+                HIP_TRY(pin.copy(pos.p + 3 * pos_off[i], d.meshes[i].positions, bytes));
+        }
+        auto up = [&](DevBuf<int32_t> &b, const int32_t *src) -> hipError_t {
+            hipError_t e = b.alloc(n);
+            return e != hipSuccess ? e : pin.copy(b.p, src, sizeof(int32_t) * n);
+        };
+        HIP_TRY(up(kind, d.shape_kind));
+        HIP_TRY(up(ref, d.shape_ref));
+        HIP_TRY(up(face, d.shape_face));
+        HIP_TRY(up(area_light, d.shape_area_light));
+        HIP_TRY(pin.finish());
+        if (std::getenv("TAKE_HIP_VERBOSE"))
+            std::fprintf(stderr, "[take_hip] scene_create: uploads pinned in place %.1f MB, pageable %.1f MB\n", pin.pinned_bytes / 1e6, pin.plain_bytes / 1e6);
+        ready = true;
+        return TAKE_OK;
+    }
+    void release() { pos.release(), kind.release(), ref.release(), face.release(), area_light.release(); }
+};
+
+// Primitive records of one side on the device (tk_build_gpu.h::k_make_prims<R>) from the shared inputs; the face indices
+// are the validated concatenation the shading side keeps anyway (sc.face_idx: uploaded by the first side, copied on
+// the device by the second).
+template <class R> int make_prims_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions) {
     using namespace lbvh;
     const int n = (int)d.n_shapes;
-    HostScene<float> &h = sc.host;
+    HostScene<R> &h = sc.host;
+    const int ru = in.upload(d, device_positions);
+    if (ru) return ru;
     std::vector<MeshSrc> ms(d.n_meshes);
-    int64_t nv = 0;
     for (int i = 0; i < d.n_meshes; i++) {
         const MeshInfo &mi = h.meshes[i];
-        ms[i] = MeshSrc{nv, mi.fbase, mi.material, h.materials[mi.material].tag, (mi.nbase >= 0 || mi.uvbase >= 0) ? 1 : 0};
-        nv += d.meshes[i].n_vertices;
+        ms[i] = MeshSrc{in.pos_off[i], mi.fbase, mi.material, h.materials[mi.material].tag, (mi.nbase >= 0 || mi.uvbase >= 0) ? 1 : 0};
     }
     std::vector<SphereSrc> ss(d.n_spheres);
     for (int i = 0; i < d.n_spheres; i++) {
         const TakeSphere &s = d.spheres[i];
         ss[i] = SphereSrc{{s.center[0], s.center[1], s.center[2]}, s.radius, s.material_id, h.materials[s.material_id].tag};
     }
-    DevBuf<double> d_pos;
-    DevBuf<int32_t> d_kind, d_ref, d_face, d_al;
     DevBuf<MeshSrc> d_ms;
     DevBuf<SphereSrc> d_ss;
-    HIP_TRY(d_pos.alloc(3 * (size_t)std::max<int64_t>(nv, 1)));
-    PinnedUploads pin;
-    for (int i = 0; i < d.n_meshes; i++) {
-        if (d.meshes[i].n_vertices <= 0) continue;
-        const size_t bytes = sizeof(double) * 3 * (size_t)d.meshes[i].n_vertices;
-        // a mesh decoded on the device (take_hip_mesh_from_ply): its positions never were on the host
-        if (device_positions && device_positions[i])
-            HIP_TRY(hipMemcpyAsync(d_pos.p + 3 * ms[i].pos_off, device_positions[i], bytes, hipMemcpyDeviceToDevice, pin.stream));
-        else
-            HIP_TRY(pin.copy(d_pos.p + 3 * ms[i].pos_off, d.meshes[i].positions, bytes));
+    if (in.face_idx) {
+        HIP_TRY(sc.face_idx.alloc(h.face_idx.size()));
+        if (sc.face_idx.n) HIP_TRY(hipMemcpy(sc.face_idx.p, in.face_idx, sc.face_idx.bytes(), hipMemcpyDeviceToDevice));
+    } else {
+        HIP_TRY(sc.face_idx.upload(h.face_idx));
+        in.face_idx = sc.face_idx.p;
     }
-    HIP_TRY(sc.face_idx.upload(h.face_idx));
-    auto up = [&](DevBuf<int32_t> &b, const int32_t *src) -> hipError_t {
-        hipError_t e = b.alloc((size_t)n);
-        return e != hipSuccess ? e : pin.copy(b.p, src, sizeof(int32_t) * (size_t)n);
-    };
-    HIP_TRY(up(d_kind, d.shape_kind));
-    HIP_TRY(up(d_ref, d.shape_ref));
-    HIP_TRY(up(d_face, d.shape_face));
-    HIP_TRY(up(d_al, d.shape_area_light));
     HIP_TRY(d_ms.upload(ms));
     HIP_TRY(d_ss.upload(ss));
     HIP_TRY(sc.prims.alloc((size_t)n));
-    hipLaunchKernelGGL(k_make_prims, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, nullptr, d_kind.p, d_ref.p, d_face.p, d_al.p,
-                       d_ms.p, d_pos.p, sc.face_idx.p, d_ss.p, n, sc.prims.p);
+    hipLaunchKernelGGL(k_make_prims<R>, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, nullptr, in.kind.p, in.ref.p, in.face.p,
+                       in.area_light.p, d_ms.p, in.pos.p, sc.face_idx.p, d_ss.p, n, sc.prims.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(pin.finish());  // (the kernel is behind the copies on the same stream)
-    if (std::getenv("TAKE_HIP_VERBOSE"))
-        std::fprintf(stderr, "[take_hip] scene_create: uploads pinned in place %.1f MB, pageable %.1f MB\n", pin.pinned_bytes / 1e6, pin.plain_bytes / 1e6);
+    HIP_TRY(hipStreamSynchronize(nullptr));  // (a failed kernel is reported here, not by a later call)
     return TAKE_OK;
 }
 
@@ -478,21 +555,24 @@ int make_prims_on_device(SceneT<float> &sc, const TakeSceneDesc &d, const double
 struct PhaseClock {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     bool on = std::getenv("TAKE_HIP_VERBOSE") != nullptr;
+    const char *side;  // "f32" / "f64": the side of the scene the phases belong to
+    explicit PhaseClock(const char *side_) : side(side_) {}
     void lap(const char *what) {
         if (!on) return;
         const auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[take_hip] scene_create: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        std::fprintf(stderr, "[take_hip] scene_create: %s %-28s %8.1f ms\n", side, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
         t0 = t1;
     }
 };
 
 // One precision's side of a new scene: records, tree and shading tables prepared on the host and uploaded, or with
-// device_builder (f32 only) the records and the tree made on the device — and, when the device tree would be too deep,
-// on the host after all.  staged: the description's device-array meshes (StagedMeshes::stage).
+// device_builder the records and the tree made on the device — and, when the device tree would be too deep, on the
+// host after all.  staged: the description's device-array meshes (StagedMeshes::stage).  inputs: what the device
+// builder reads of the caller's arrays, shared by the sides of the scene; last_side: nothing needs them after this one.
 template <class R>
 int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const TakeBuildOpts &opts, int threads, bool device_builder,
-                 StagedMeshes &staged) {
-    PhaseClock clock;
+                 StagedMeshes &staged, DeviceBuildInputs &inputs, bool last_side) {
+    PhaseClock clock(sizeof(R) == 4 ? "f32" : "f64");
     int max_leaf = opts.max_leaf_size;
     if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));  // tuning knob
     // lanes per ray: one (TQ_GROUP).  Round 1 measured quad 143.6 / pair 121.5 / one ray per lane 128.8 ms of closest-hit
@@ -501,25 +581,25 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     sc.group = TQ_GROUP;
     const char *fmt_env = std::getenv("TAKE_HIP_NODES");
     const std::string fmt = fmt_env ? fmt_env : "";
-    bool on_device = device_builder && sizeof(R) == 4;  // (the f64 side of a mixed-precision scene: the host builder)
+    bool on_device = device_builder;
     std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_DEVICE_BUILD : PREP_HOST_BUILD, opts.burley_lobes != 0);
     if (!err.empty()) return fail(TAKE_E_INVALID, err);
     clock.lap(on_device ? "host validation + tables" : "host records + SAH build");
     HostScene<R> &h = sc.host;
-    if constexpr (sizeof(R) == 4) {
-        if (on_device) {
-            int rc = make_prims_on_device(sc, desc, staged.any ? staged.d_positions.data() : nullptr);
-            clock.lap("mesh arrays -> HBM, records");
-            if (!rc) rc = build_bvh_device(sc, max_leaf, sc.group <= 2 && fmt != "wide", fmt == "q16");
-            if (rc == 1) {  // not buildable on the device (tree too deep): do it on the host after all
-                on_device = false;
-                const int rs = staged.ensure_positions();
-                if (rs) return rs;
-                err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_HOST_BUILD, opts.burley_lobes != 0);
-                if (!err.empty()) return fail(TAKE_E_INVALID, err);
-            } else if (rc != TAKE_OK) {
-                return rc;
-            }
+    if (on_device) {
+        int rc = make_prims_on_device(sc, desc, inputs, staged.any ? staged.d_positions.data() : nullptr);
+        if (last_side) inputs.release();  // (positions and shape arrays: not part of the build's peak)
+        clock.lap("mesh arrays -> HBM, records");
+        if (!rc) rc = build_bvh_device(sc, max_leaf, sc.group <= 2 && fmt != "wide", fmt == "q16");
+        if (rc == 1) {  // not buildable on the device (tree too deep): do it on the host after all
+            on_device = false;
+            sc.prims.release();
+            const int rs = staged.ensure_positions();
+            if (rs) return rs;
+            err = prepare_scene<R>(desc, max_leaf, threads, sc.host, PREP_HOST_BUILD, opts.burley_lobes != 0);
+            if (!err.empty()) return fail(TAKE_E_INVALID, err);
+        } else if (rc != TAKE_OK) {
+            return rc;
         }
     }
     if (!on_device) {
@@ -543,7 +623,8 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
                                             std::to_string(sc.prims.n) + " primitives, " + std::to_string(h.stats.n_nodes) + " nodes)");
     }
     HIP_TRY(sc.meshes.upload(h.meshes));
-    if (!on_device) HIP_TRY(sc.face_idx.upload(h.face_idx));  // (device build: already there, k_make_prims read it)
+    // (device build: already there, k_make_prims read it — also after a fall-back to the host builder)
+    if (!sc.face_idx.p) HIP_TRY(sc.face_idx.upload(h.face_idx));
     HIP_TRY(sc.normals.upload(h.normals));
     HIP_TRY(sc.uvs.upload(h.uvs));
     HIP_TRY(sc.texels.upload(h.texels));
@@ -1217,16 +1298,19 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
             const int rf = flat.expand(local, threads);
             if (rf) return rf;
         }
-        // builder of the f32 tree: AUTO = host SAH (best trees) up to 4M shapes, device LBVH beyond: at 10M triangles the
-        // host build is 6 s of setup against 0.2 s, for 2-6 % of traversal speed.  The device builder
-        // needs enough primitives to make a tree and no instances; f64 trees are built on the host.
+        // builder of every side's tree: AUTO = host SAH (best trees) up to 4M shapes, device LBVH beyond: at 10M triangles
+        // the host build is 6 s of setup per side against 0.2 s, for 2-6 % of traversal speed.  The device
+        // builder needs enough primitives to make a tree and no instances.
         const bool device_builder = local.n_shapes >= 8 && local.n_instances == 0 &&
                                     (o.builder == TAKE_BUILDER_DEVICE_LBVH || (o.builder == TAKE_BUILDER_AUTO && local.n_shapes >= TAKE_AUTO_DEVICE_BUILD_SHAPES));
-        // every position comes to the host unless the device builder makes the only tree
-        rc = staged.stage(local, !(device_builder && o.precision == TAKE_PRECISION_F32));
-        // the f64 side of F64 and MIXED scenes, the f32 side of F32 and MIXED ones
-        if (!rc && o.precision != TAKE_PRECISION_F32) rc = upload_scene(ts->d, ts->num_cus, local, o, threads, device_builder, staged);
-        if (!rc && o.precision != TAKE_PRECISION_F64) rc = upload_scene(ts->f, ts->num_cus, local, o, threads, device_builder, staged);
+        // every position comes to the host unless the device builder makes the trees
+        rc = staged.stage(local, !device_builder);
+        // the f64 side of F64 and MIXED scenes, the f32 side of F32 and MIXED ones; a mixed scene's two sides are two
+        // independent trees (each from its own records' boxes) over one upload of the caller's arrays
+        DeviceBuildInputs inputs;
+        if (!rc && o.precision != TAKE_PRECISION_F32)
+            rc = upload_scene(ts->d, ts->num_cus, local, o, threads, device_builder, staged, inputs, o.precision == TAKE_PRECISION_F64);
+        if (!rc && o.precision != TAKE_PRECISION_F64) rc = upload_scene(ts->f, ts->num_cus, local, o, threads, device_builder, staged, inputs, true);
     } catch (const std::bad_alloc &) {
         rc = fail(TAKE_E_NOMEM, "out of host memory while preparing the scene");
     } catch (const std::exception &e) {
@@ -1645,6 +1729,14 @@ int take_hip_scene_stats(const TakeScene *ts, int64_t *n_nodes, int64_t *n_prims
     if (depth) *depth = s.depth;
     // (a side the scene's precision does not make is empty: 0 bytes)
     if (device_bytes) *device_bytes = (int64_t)(ts->d.scene_bytes() + ts->f.scene_bytes());
+    return TAKE_OK;
+}
+int take_hip_scene_build_info(const TakeScene *ts, int32_t *f32_builder, int32_t *f64_builder) {
+    if (!ts) return fail(TAKE_E_INVALID, "null scene");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    if (f32_builder) *f32_builder = ts->precision == TAKE_PRECISION_F64 ? -1 : (ts->f.built_on_device ? TAKE_BUILDER_DEVICE_LBVH : TAKE_BUILDER_HOST_SAH);
+    if (f64_builder) *f64_builder = ts->precision == TAKE_PRECISION_F32 ? -1 : (ts->d.built_on_device ? TAKE_BUILDER_DEVICE_LBVH : TAKE_BUILDER_HOST_SAH);
     return TAKE_OK;
 }
 

@@ -1,8 +1,9 @@
-// tk_build_gpu.h — BVH construction on the device (f32 scenes): the GPU counterpart of `construct_bvh`
-// (src/bvh.cpp:8-45) for scenes where the host SAH build is the wait (10M triangles: ~6 s on 16 cores).
+// tk_build_gpu.h — BVH construction on the device (f32 and f64 sides of a scene): the GPU counterpart of
+// `construct_bvh` (src/bvh.cpp:8-45) for scenes where the host SAH build is the wait (10M triangles: ~6 s on 16 cores).
 //
-//   k_prim_boxes     primitive AABBs (of the geometry the intersection tests see: v0, v0+e1, v0+e2 — one ulp wider)
-//                    + scene bounds (wave reduce, ordered-int atomics)
+//   k_make_prims     primitive records, float or double, from the caller's mesh arrays
+//   k_prim_boxes     primitive AABBs (of the geometry the intersection tests see: v0, v0+e1, v0+e2 — one ulp wider;
+//                    double records: rounded outwards to float first) + scene bounds (wave reduce, ordered-int atomics)
 //   k_morton         63-bit Morton code of the box centre (21 bits per axis: 30 bits leave whole clusters of a 10M-
 //                    triangle scene in one cell); rocPRIM radix sort of (code, primitive) pairs
 //   k_leaves         leaves = runs of `leaf_size` consecutive primitives in Morton order
@@ -11,11 +12,17 @@
 //   k_collapse       BVH2 -> 4-wide nodes, one launch per tree level, breadth-first numbering (same layout and the
 //                    same "open the child with the largest area" rule as the host collapse, tk_bvh.h)
 //   k_quantise       64-byte compressed nodes on the 15-bit scene grid (same rounding rules as quantise_nodes)
+//   k_widen_nodes    double scenes without compression: the float nodes as Node4<double>
 //   k_permute        primitive and shading records into leaf order
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
 // tests): the parity tests require bit-identical hit tables and images for both builders.
+//
+// Double scenes.  Only the records and the primitive boxes know the precision: every box of the pipeline is a float
+// box (a conservative box test may be done in any precision), and a float box around double geometry is
+// what k_prim_boxes<double> makes.  Everything after it is the f32 pipeline, float nodes included; the full-width
+// fall-back of a double scene (Node4<double>) is those nodes widened to double by k_widen_nodes, which is exact.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +32,7 @@
 #include <limits>
 
 #include "tk_bvh.h"
+#include "tk_round.h"
 #include "tk_scene.h"
 
 namespace tk {
@@ -37,16 +45,6 @@ struct Box {
     float lo[3], hi[3];
 };
 
-__device__ __forceinline__ float f_below(float x) {  // the float just below x (x finite)
-    uint32_t u = __float_as_uint(x);
-    u = x > 0.0f ? u - 1u : (x < 0.0f ? u + 1u : 0x80000001u);
-    return __uint_as_float(u);
-}
-__device__ __forceinline__ float f_above(float x) {
-    uint32_t u = __float_as_uint(x);
-    u = x > 0.0f ? u + 1u : (x < 0.0f ? u - 1u : 0x00000001u);
-    return __uint_as_float(u);
-}
 // floats as integers with the same order (for atomicMin / atomicMax)
 __host__ __device__ __forceinline__ int f2ord(float f) {
     int i;
@@ -71,8 +69,9 @@ __device__ __forceinline__ float half_area(const Box &b) {
 }
 
 // ---- primitive records straight from the caller's mesh arrays (parser -> device buffers).
-// The same arithmetic as the host loop of tk_host_scene.h (positions rounded to float, e_k = v_k - v0 in float, no
-// contraction), so the records — and with them every hit — are bit-identical to the host-built ones.
+// The same arithmetic as the host loop of tk_host_scene.h (triangle_record<R>, shape_record<R>: positions taken as R,
+// e_k = v_k - v0 in R, no contraction), so the records — and with them every hit — are bit-identical to the host-built
+// ones in float and in double.
 struct MeshSrc {
     int64_t pos_off;   // first vertex of this mesh in the concatenated double positions (units: vertices)
     int32_t fbase;     // first face in face_idx (units: faces)
@@ -84,28 +83,29 @@ struct SphereSrc {
     double c[3], r;
     int32_t material, tag;
 };
+template <class R>
 __global__ void __launch_bounds__(BLK)
 k_make_prims(const int32_t *__restrict__ kind, const int32_t *__restrict__ ref, const int32_t *__restrict__ face,
              const int32_t *__restrict__ area_light, const MeshSrc *__restrict__ meshes, const double *__restrict__ positions,
-             const int32_t *__restrict__ face_idx, const SphereSrc *__restrict__ spheres, int n, PrimRec<float> *out) {
+             const int32_t *__restrict__ face_idx, const SphereSrc *__restrict__ spheres, int n, PrimRec<R> *out) {
     const int i = blockIdx.x * BLK + threadIdx.x;
     if (i >= n) return;
-    PrimRec<float> p{};
+    PrimRec<R> p{};
     p.shape_id = i;
     p.area_light = area_light[i];
     p.nidx = -1;
     if (kind[i] == 0) {
         const SphereSrc s = spheres[ref[i]];
-        p.a[0] = (float)s.c[0], p.a[1] = (float)s.c[1], p.a[2] = (float)s.c[2], p.a[3] = (float)s.r;
+        p.a[0] = (R)s.c[0], p.a[1] = (R)s.c[1], p.a[2] = (R)s.c[2], p.a[3] = (R)s.r;
         p.meta = PRIM_SPHERE | (s.tag << 8);
         p.material = s.material;
         p.mesh = -(1 + ref[i]);
     } else {
         const MeshSrc m = meshes[ref[i]];
         const int32_t *idx = face_idx + 3 * ((int64_t)m.fbase + face[i]);
-        float v[3][3];
+        R v[3][3];
         for (int k = 0; k < 3; k++)
-            for (int a = 0; a < 3; a++) v[k][a] = (float)positions[3 * (m.pos_off + idx[k]) + a];
+            for (int a = 0; a < 3; a++) v[k][a] = (R)positions[3 * (m.pos_off + idx[k]) + a];
         for (int a = 0; a < 3; a++) p.a[a] = v[0][a], p.a[3 + a] = v[1][a] - v[0][a], p.a[6 + a] = v[2][a] - v[0][a];
         p.meta = PRIM_TRIANGLE | (m.tag << 8);
         p.material = m.material;
@@ -115,24 +115,39 @@ k_make_prims(const int32_t *__restrict__ kind, const int32_t *__restrict__ ref, 
     out[i] = p;
 }
 
-// scene_ord[0..2] = min of lo (ordered ints), [3..5] = max of hi; initialised to INT_MAX / INT_MIN by the caller
-__global__ void __launch_bounds__(BLK) k_prim_boxes(const PrimRec<float> *__restrict__ prims, int n, Box *pb, int *scene_ord) {
+// One coordinate interval [lo, hi] of a record's geometry -> a float interval that contains it.
+// float records: the sums v0 + e_k and c -+ r round by at most half an ulp, so one float further out contains them.
+// double records: the geometry the intersection tests see is the REAL triangle v0 + u e1 + v e2 (real sphere |x - c|
+// = r) of the stored doubles; its extreme coordinates are the real numbers v0, v0 + e1, v0 + e2 (c -+ r), of which
+// the double sums computed here are within half a DOUBLE ulp.  d2f_down / d2f_up (tk_round.h) give floats lo' <= the
+// computed minimum and hi' >= the computed maximum, whatever the magnitude — far from the origin a rounding to nearest
+// would land inside the triangle by up to half a float ulp, which is the case this exists for — and the one float
+// further out that the f32 path also takes is 2^29 double ulps: more than the half ulp the real sums can lie beyond
+// the computed ones.  (The caller's v1, v2 need not be looked at: e_k = fl(v_k - v0) makes v0 + e_k differ from v_k by
+// a rounding, but only v0 + e_k is geometry to any test.)
+__device__ __forceinline__ void widen(float lo, float hi, float &blo, float &bhi) { blo = f_below(lo), bhi = f_above(hi); }
+__device__ __forceinline__ void widen(double lo, double hi, float &blo, float &bhi) { blo = f_below(d2f_down(lo)), bhi = f_above(d2f_up(hi)); }
+
+// scene_ord[0..2] = min of lo (ordered ints), [3..5] = max of hi; initialised to INT_MAX / INT_MIN by the caller.
+// With outward-rounded boxes the float scene bounds contain the double scene, so the grid make_qgrid lays over them
+// and QRay's 2^-20-extent slack (tk_traverse.h) are what the host path gives an f64 scene: the same argument holds.
+template <class R>
+__global__ void __launch_bounds__(BLK) k_prim_boxes(const PrimRec<R> *__restrict__ prims, int n, Box *pb, int *scene_ord) {
     const int i = blockIdx.x * BLK + threadIdx.x;
     Box b;
 #pragma unroll
     for (int k = 0; k < 3; k++) b.lo[k] = __builtin_huge_valf(), b.hi[k] = -__builtin_huge_valf();
     if (i < n) {
-        const PrimRec<float> p = prims[i];
+        const PrimRec<R> p = prims[i];
         if ((p.meta & 0xff) == PRIM_TRIANGLE) {
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                const float v0 = p.a[k], v1 = p.a[k] + p.a[3 + k], v2 = p.a[k] + p.a[6 + k];
-                b.lo[k] = f_below(fminf(v0, fminf(v1, v2)));  // the sums round by at most half an ulp
-                b.hi[k] = f_above(fmaxf(v0, fmaxf(v1, v2)));
+                const R v0 = p.a[k], v1 = p.a[k] + p.a[3 + k], v2 = p.a[k] + p.a[6 + k];
+                widen(tk_fmin(v0, tk_fmin(v1, v2)), tk_fmax(v0, tk_fmax(v1, v2)), b.lo[k], b.hi[k]);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < 3; k++) b.lo[k] = f_below(p.a[k] - p.a[3]), b.hi[k] = f_above(p.a[k] + p.a[3]);
+            for (int k = 0; k < 3; k++) widen(p.a[k] - p.a[3], p.a[k] + p.a[3], b.lo[k], b.hi[k]);
         }
         pb[i] = b;
     }
@@ -342,6 +357,20 @@ __global__ void __launch_bounds__(BLK) k_quantise(const Node4<float> *__restrict
         atomicAdd(&acc[0], ratio);
         atomicAdd(&acc[1], slots);
     }
+}
+
+// Full-width nodes of a double scene (compression refused): the float planes as doubles — the same numbers, so the
+// boxes contain what they contained; an empty slot's infinities stay infinities.
+__global__ void __launch_bounds__(BLK) k_widen_nodes(const Node4<float> *__restrict__ in, int n, Node4<double> *out) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    const Node4<float> a = in[i];
+    Node4<double> b;
+    for (int c = 0; c < 4; c++) {
+        for (int k = 0; k < 3; k++) b.c[c].bmin[k] = (double)a.c[c].bmin[k], b.c[c].bmax[k] = (double)a.c[c].bmax[k];
+        b.c[c].child = a.c[c].child, b.c[c].pad = 0;
+    }
+    out[i] = b;
 }
 
 template <class T>
