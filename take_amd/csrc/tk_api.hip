@@ -1,8 +1,8 @@
-// tk_api.hip — implementation of the C ABI of include/take_hip.h: scene upload, the wavefront render loop,
-// the trace hooks, scene groups.  Host code here only orchestrates: every per-sample operation runs in the kernels of
-// tk_kernels.h.  There is no CPU rendering path in this library: without a HIP device every entry point
-// returns TAKE_E_NO_GPU.  The mesh entry points (PLY, serialized, OBJ, compute_normals) are tk_mesh.hip; the
-// plumbing both units share is tk_host.h.
+// tk_api.hip — implementation of the C ABI of include/take_hip.h: scene creation (host preparation, upload, the
+// device build), scene groups, and the C entry points.  Tracing and rendering — everything that launches a kernel of
+// tk_kernels.h — is tk_render.hip, reached through the functions of tk_scene_handle.h.  There is no CPU rendering
+// path in this library: without a HIP device every entry point returns TAKE_E_NO_GPU.  The mesh entry points (PLY,
+// serialized, OBJ, compute_normals) are tk_mesh.hip; the plumbing all units share is tk_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,145 +18,13 @@
 #include <vector>
 
 #include "take_hip.h"
-#include "tk_host.h"
-#include "tk_host_scene.h"
+#include "tk_scene_handle.h"
 #include "tk_build_gpu.h"
-#include "tk_kernels.h"
 
 using namespace tk;
 using namespace tk_host;
 
 namespace {
-
-struct EventPool {
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;
-    EventPool() = default;
-    EventPool(const EventPool &) = delete;
-    EventPool &operator=(const EventPool &) = delete;
-    ~EventPool() {
-        for (auto e : ev) (void)hipEventDestroy(e);
-    }
-    hipEvent_t get() {
-        if (used == ev.size()) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;  // callers treat a null event as a failed timing call
-            ev.push_back(e);
-        }
-        return ev[used++];
-    }
-    void reset() { used = 0; }
-};
-
-// Queue lengths read back WITHOUT stalling the launch loop (render_impl): a ring of pinned words + events, made by the
-// first render.
-struct PollRing {
-    static constexpr int SIZE = 64;
-    int32_t *word = nullptr;  // SIZE pinned words
-    hipEvent_t ev[SIZE] = {};
-    PollRing() = default;
-    PollRing(const PollRing &) = delete;
-    PollRing &operator=(const PollRing &) = delete;
-    ~PollRing() {
-        if (word) (void)hipHostFree(word);
-        for (auto e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    hipError_t create() {  // (a no-op once it has succeeded; after a failure the next call makes what is missing)
-        hipError_t r = word ? hipSuccess : hipHostMalloc((void **)&word, sizeof(int32_t) * SIZE, hipHostMallocDefault);
-        for (int i = 0; i < SIZE && r == hipSuccess; i++)
-            if (!ev[i]) r = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        return r;
-    }
-};
-
-enum TimedKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_OTHER, TK_CLOSEST_TAIL /* mixed precision: closest hits of the f32 rounds */, TK_NUM };
-
-template <class R> struct SceneT {
-    HostScene<R> host;  // kept: cheap relative to HBM copies, used for stats
-    DevBuf<Node4<R>> nodes;
-    DevBuf<QNode4> qnodes;
-    DevBuf<QNode8> qnodes8;
-    DevBuf<PrimRec<R>> prims;
-    DevBuf<MeshInfo> meshes;
-    DevBuf<int32_t> face_idx;
-    DevBuf<R> normals, uvs, texels;
-    DevBuf<MaterialRec<R>> materials;
-    DevBuf<ImageInfo> images;
-    DevBuf<LightRec<R>> lights;
-    DevBuf<R> light_pmf, light_cdf;
-    DevBuf<InstTrace<R>> inst_trace;
-    DevBuf<InstShade<R>> inst_shade;
-    DevBuf<R> env_marginal, env_conditional;
-    DevBuf<int32_t> env_guide_m, env_guide_c;
-    DeviceScene<R> dev{};
-    // render workspace (grown on demand)
-    DevBuf<R> state_r;
-    DevBuf<int32_t> queue[2], shadow_queue, sorted_queue;
-    DevBuf<uint8_t> sort_keys;            // one key byte per queue entry (material sort)
-    DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
-    DevBuf<R> accum, out;
-    DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
-    DevBuf<unsigned long long> counters;
-    DevBuf<unsigned long long> spill;
-    int64_t capacity = 0;  // path slots allocated
-    int trace_grid = 0;
-    int group = TQ_GROUP;      // lanes per ray of the trace kernel (one instantiated size)
-    bool built_on_device = false;
-    int64_t spill_stride = 0;  // ray groups in the persistent trace grid
-
-    // The scene arrays: f(x.nodes...), f(x.qnodes...), ... for the scenes x, in the order replicate_t allocates them.
-    template <class F, class... S> static void for_each_array(F &&f, S &...x) {
-        f(x.nodes...), f(x.qnodes...), f(x.qnodes8...), f(x.prims...), f(x.meshes...), f(x.face_idx...), f(x.normals...);
-        f(x.uvs...), f(x.texels...), f(x.materials...), f(x.images...), f(x.lights...), f(x.light_pmf...), f(x.light_cdf...);
-        f(x.inst_trace...), f(x.inst_shade...), f(x.env_marginal...), f(x.env_conditional...), f(x.env_guide_m...), f(x.env_guide_c...);
-    }
-    // dev's pointers into this scene's arrays: null where an array is empty, and for the node formats not in use (only
-    // the format the kernels traverse is allocated)
-    void bind() {
-        dev.nodes = nodes.p, dev.qnodes = qnodes.p, dev.qnodes8 = qnodes8.p, dev.prims = prims.p;
-        dev.shapes = nullptr;  // (ShapeInfo stays on the host: every kernel reads the shading side of a primitive from its own record)
-        dev.meshes = meshes.p, dev.face_idx = face_idx.p, dev.normals = normals.p, dev.uvs = uvs.p, dev.texels = texels.p;
-        dev.materials = materials.p, dev.images = images.p, dev.lights = lights.p, dev.light_pmf = light_pmf.p, dev.light_cdf = light_cdf.p;
-        dev.inst_trace = inst_trace.p, dev.inst_shade = inst_shade.p;
-        dev.env.marginal = env_marginal.p, dev.env.conditional = env_conditional.p, dev.env.guide_m = env_guide_m.p, dev.env.guide_c = env_guide_c.p;
-    }
-    // device bytes of the scene (take_hip_scene_stats): the light-picking and environment-map tables have never been
-    // counted in this figure
-    size_t scene_bytes() const {
-        size_t n = 0;
-        for_each_array([&n](const auto &b) { n += b.bytes(); }, *this);
-        return n - light_pmf.bytes() - light_cdf.bytes() - env_marginal.bytes() - env_conditional.bytes() - env_guide_m.bytes() - env_guide_c.bytes();
-    }
-};
-
-}  // namespace
-
-struct TakeScene {
-    int precision = TAKE_PRECISION_F32;
-    int device = 0;
-    int num_cus = 256;
-    // progressive rendering (take_hip_render_accumulate): samples per pixel summed in `accum` so far, under which options
-    int64_t acc_samples = 0;
-    TakeRenderOpts acc_opts{};
-    int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
-    int instrumentation = 0;
-    SceneT<float> f;
-    SceneT<double> d;
-    TakeCounters counters{};
-    EventPool events;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> timed;
-    PollRing poll;
-    // records, images and trace hooks of a mixed-precision scene are the f64 ones (its f32 side finishes the paths)
-    bool f64() const { return precision != TAKE_PRECISION_F32; }
-    int width() const { return f64() ? d.host.cam.width : f.host.cam.width; }
-    int height() const { return f64() ? d.host.cam.height : f.host.cam.height; }
-};
-
-namespace {
-
-// f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
-template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
 
 // device memory in use (the whole device's, as hipMemGetInfo sees it), for the TAKE_HIP_VERBOSE lines; 0 if the runtime
 // cannot say
@@ -575,10 +443,6 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     PhaseClock clock(sizeof(R) == 4 ? "f32" : "f64");
     int max_leaf = opts.max_leaf_size;
     if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));  // tuning knob
-    // lanes per ray: one (TQ_GROUP).  Round 1 measured quad 143.6 / pair 121.5 / one ray per lane 128.8 ms of closest-hit
-    // time per 8.3 M samples on full-width nodes; on the 64-byte nodes one ray per lane is 9 % (f32) and 22 % (f64)
-    // ahead of the pair kernel.  The other group sizes stay behind -DTQ_GROUP for comparison builds.
-    sc.group = TQ_GROUP;
     const char *fmt_env = std::getenv("TAKE_HIP_NODES");
     const std::string fmt = fmt_env ? fmt_env : "";
     bool on_device = device_builder;
@@ -590,7 +454,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
         int rc = make_prims_on_device(sc, desc, inputs, staged.any ? staged.d_positions.data() : nullptr);
         if (last_side) inputs.release();  // (positions and shape arrays: not part of the build's peak)
         clock.lap("mesh arrays -> HBM, records");
-        if (!rc) rc = build_bvh_device(sc, max_leaf, sc.group <= 2 && fmt != "wide", fmt == "q16");
+        if (!rc) rc = build_bvh_device(sc, max_leaf, compressed_nodes_supported() && fmt != "wide", fmt == "q16");
         if (rc == 1) {  // not buildable on the device (tree too deep): do it on the host after all
             on_device = false;
             sc.prims.release();
@@ -605,7 +469,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     if (!on_device) {
         HIP_TRY(sc.prims.upload(h.prims));
         clock.lap("primitive records -> HBM");
-        const bool use_q = sc.group <= 2 && (!h.qnodes.empty() || !h.qnodes8.empty());  // compressed nodes (not in the quad kernel)
+        const bool use_q = compressed_nodes_supported() && (!h.qnodes.empty() || !h.qnodes8.empty());
         if (!h.qnodes8.empty()) HIP_TRY(sc.qnodes8.upload(h.qnodes8));
         else if (use_q) HIP_TRY(sc.qnodes.upload(h.qnodes));
         else HIP_TRY(sc.nodes.upload(h.nodes));
@@ -613,12 +477,12 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     sc.built_on_device = on_device;
     clock.lap(on_device ? "device LBVH build" : "nodes -> HBM");
     // (only the node format the kernels traverse is allocated)
-    const bool w8 = sc.qnodes8.p != nullptr, use_q = sc.qnodes.p != nullptr;
+    sc.trace = TraceKind{sc.qnodes8.p ? NodeFormat::Q8 : (sc.qnodes.p ? NodeFormat::Q4 : NodeFormat::WIDE), !h.inst_trace.empty()};
     // the trace kernels address nodes and primitive records with 32-bit byte offsets (full-rate integer math)
     {
-        const uint64_t node_bytes = (uint64_t)h.stats.n_nodes * (w8 ? sizeof(QNode8) : (use_q ? sizeof(QNode4) : sizeof(Node4<R>)));
+        const uint64_t tree_bytes = (uint64_t)h.stats.n_nodes * node_bytes<R>(sc.trace.nodes);
         const uint64_t prim_bytes = (uint64_t)sc.prims.n * sizeof(PrimRec<R>);
-        if (node_bytes >= (1ull << 32) || prim_bytes >= (1ull << 32))
+        if (tree_bytes >= (1ull << 32) || prim_bytes >= (1ull << 32))
             return fail(TAKE_E_INVALID, "scene too large for the 32-bit record offsets of the trace kernels (" +
                                             std::to_string(sc.prims.n) + " primitives, " + std::to_string(h.stats.n_nodes) + " nodes)");
     }
@@ -641,31 +505,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     HIP_TRY(sc.env_guide_c.upload(h.env_guide_c));
     sc.dev = h.view();  // (the counts, camera and small tables; the pointers are the device arrays')
     sc.bind();
-    HIP_TRY(sc.qwords.alloc(Q_NUM_WORDS + 2 * N_SORT_KEYS));
-    HIP_TRY(hipMemset(sc.qwords.p, 0, sc.qwords.bytes()));
-    HIP_TRY(sc.counters.alloc(C_NUM_WORDS));
-    HIP_TRY(hipMemset(sc.counters.p, 0, sc.counters.bytes()));
-    // persistent trace grid: resident blocks of the heaviest trace kernel x CUs
-    int per_cu = 0;
-    const int groups_per_block = GroupGeom<TQ_GROUP>::GROUPS;
-    const int spill_levels = w8 ? GroupGeom<TQ_GROUP == 1 ? 1 : TQ_GROUP, TQ_GROUP == 1 ? 8 : 4>::SPILL : GroupGeom<TQ_GROUP>::SPILL;
-    if constexpr (TQ_GROUP == 1) {
-        if (w8 && sc.inst_trace.n) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, 1, false, false, PathIo<R>, true, true, 8>, TQ_BLOCK, 0));
-        else if (w8) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, 1, false, false, PathIo<R>, true, false, 8>, TQ_BLOCK, 0));
-    }
-    if (!w8) {
-        if (use_q) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, TQ_GROUP, false, false, PathIo<R>, true>, TQ_BLOCK, 0));
-        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, TQ_GROUP, false, false, PathIo<R>>, TQ_BLOCK, 0));
-        if (sc.inst_trace.n) {  // two-level scenes run the INST instances: size the persistent grid for them
-            if (use_q) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, TQ_GROUP, false, false, PathIo<R>, true, true>, TQ_BLOCK, 0));
-            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace_group<R, TQ_GROUP, false, false, PathIo<R>, false, true>, TQ_BLOCK, 0));
-        }
-    }
-    per_cu = std::max(1, std::min(per_cu, 8));
-    if (const char *e = std::getenv("TAKE_HIP_TRACE_BLOCKS")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));  // experiment: leave room for a concurrent kernel
-    sc.trace_grid = num_cus * per_cu;
-    sc.spill_stride = (int64_t)sc.trace_grid * groups_per_block;
-    HIP_TRY(sc.spill.alloc((size_t)sc.spill_stride * spill_levels));
+    HIP_TRY(alloc_trace_state(sc, num_cus));  // queue words, counters, the persistent trace grid
     clock.lap("shading tables -> HBM, grid");
     // everything the kernels read is in HBM now; the host keeps the small tables (camera, material tags, tree
     // statistics) and drops the copies of the large arrays (1.1 GB at 10M triangles)
@@ -673,590 +513,6 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     h.inst_trace = {}, h.inst_shade = {};
     return TAKE_OK;
 }
-
-// Path-state / queue / framebuffer workspace of a scene, grown on demand.  A failed allocation leaves the scene
-// WITHOUT a workspace (capacity 0, every buffer released) and returns TAKE_E_NOMEM: the next render allocates afresh
-// instead of trusting a stale capacity over null pointers.
-template <class R> void release_workspace(SceneT<R> &sc) {
-    sc.state_r.release(), sc.queue[0].release(), sc.queue[1].release(), sc.shadow_queue.release();
-    sc.sorted_queue.release(), sc.sort_keys.release();
-    sc.capacity = 0;
-}
-template <class R> int ensure_workspace(SceneT<R> &sc, int64_t slots, int64_t npix) {
-    if (slots > sc.capacity) {
-        release_workspace(sc);
-        const bool ok = sc.state_r.alloc((size_t)PATH_REC * slots) == hipSuccess && sc.queue[0].alloc(slots) == hipSuccess &&
-                        sc.queue[1].alloc(slots) == hipSuccess && sc.shadow_queue.alloc(slots) == hipSuccess &&
-                        sc.sorted_queue.alloc(slots) == hipSuccess && sc.sort_keys.alloc(slots) == hipSuccess;
-        if (!ok) {
-            release_workspace(sc);
-            return fail(TAKE_E_NOMEM, "out of device memory for " + std::to_string(slots) + " path slots (" +
-                                          std::to_string((size_t)slots * (PATH_REC * sizeof(R) + 17) >> 20) + " MiB)");
-        }
-        sc.capacity = slots;
-    }
-    if ((int64_t)sc.accum.n < 3 * npix) {
-        if (sc.accum.alloc(3 * npix) != hipSuccess || sc.out.alloc(3 * npix) != hipSuccess) {
-            sc.accum.release(), sc.out.release();
-            return fail(TAKE_E_NOMEM, "out of device memory for the framebuffer");
-        }
-    }
-    return TAKE_OK;
-}
-
-__global__ void k_prep(int32_t *q, int next) {
-    const int t = threadIdx.x;
-    if (t == 0) {
-        q[Q_HEAD_CLOSEST] = 0;
-        q[Q_HEAD_SHADOW] = 0;
-        q[Q_N_SHADOW] = 0;
-        q[next ? Q_N_EXT1 : Q_N_EXT0] = 0;
-    }
-    if (t < 2 * N_SORT_KEYS) q[Q_NUM_WORDS + t] = 0;
-}
-__global__ void k_set_word(int32_t *q, int word, int32_t value) { q[word] = value; }
-
-int rows_of(int height, int first, int stride, int32_t *rows_out) {
-    const int n_strips = (height + TILE_ROWS - 1) / TILE_ROWS;
-    int n = 0;
-    std::vector<int> ys;
-    for (int s = first; s < n_strips; s += stride)
-        for (int y = s * TILE_ROWS; y < std::min(height, (s + 1) * TILE_ROWS); y++) ys.push_back(y);
-    n = (int)ys.size();
-    if (rows_out)
-        for (int j = 0; j < n; j++) rows_out[j] = height - 1 - ys[n - 1 - j];  // increasing image row
-    return n;
-}
-
-struct Timer {
-    TakeScene *ts;
-    hipStream_t stream;
-    bool on;
-    hipError_t err = hipSuccess;  // first failure of an event call; render_impl reports it instead of bogus times
-    void begin(int which) {
-        if (!on) return;
-        hipEvent_t a = ts->events.get(), b = ts->events.get();
-        const hipError_t e = (a && b) ? hipEventRecord(a, stream) : hipErrorOutOfMemory;
-        if (e != hipSuccess && err == hipSuccess) err = e;
-        ts->timed.push_back({which, {a, b}});
-    }
-    void end() {
-        if (!on) return;
-        const hipEvent_t b = ts->timed.back().second.second;
-        const hipError_t e = b ? hipEventRecord(b, stream) : hipErrorOutOfMemory;
-        if (e != hipSuccess && err == hipSuccess) err = e;
-    }
-};
-
-// launch the trace kernel instance for (lanes per ray, any-hit, counting)
-template <class R, class Io>
-void launch_trace(int group, bool any, bool count, dim3 grid, hipStream_t stream, const DeviceScene<R> &dev, const Io &io,
-                  const int32_t *n_ptr, int32_t n_direct, int32_t *head, unsigned long long *counters, int counter_word,
-                  StackSpill spill) {
-#define TK_LAUNCH(A, C, Q, I, W)                                                                                              \
-    hipLaunchKernelGGL((k_trace_group<R, TQ_GROUP, A, C, Io, Q, I, W>), grid, dim3(TQ_BLOCK), 0, stream, dev, io, n_ptr, n_direct, head, \
-                       counters, counter_word, spill)
-#define TK_LAUNCH_AC(Q, I, W)                          \
-    do {                                            \
-        if (any && count) TK_LAUNCH(true, true, Q, I, W);       \
-        else if (any) TK_LAUNCH(true, false, Q, I, W);          \
-        else if (count) TK_LAUNCH(false, true, Q, I, W);        \
-        else TK_LAUNCH(false, false, Q, I, W);                  \
-    } while (0)
-    (void)group;  // one instantiated group size (TQ_GROUP)
-    const bool q = dev.qnodes != nullptr, two_level = dev.inst_trace != nullptr;
-    if constexpr (TQ_GROUP == 1) {
-        if (dev.qnodes8 != nullptr) {  // the 8-wide tree
-            if (two_level) TK_LAUNCH_AC(true, true, 8);
-            else TK_LAUNCH_AC(true, false, 8);
-            return;
-        }
-    }
-    if (q && two_level) TK_LAUNCH_AC(true, true, 4);
-    else if (q) TK_LAUNCH_AC(true, false, 4);
-    else if (two_level) TK_LAUNCH_AC(false, true, 4);
-    else TK_LAUNCH_AC(false, false, 4);
-#undef TK_LAUNCH_AC
-#undef TK_LAUNCH
-}
-
-template <class R> struct ShadeArgs {
-    DeviceScene<R> dev;
-    RenderParams<R> rp;
-    PathState<R> st;
-    const int32_t *queue;
-    const int32_t *n_cur;
-    const int32_t *tag_count;
-    int32_t *next_queue, *n_next, *shadow_queue, *n_shadow;
-    int k;
-    unsigned long long *counters;
-    int grid;
-    hipStream_t stream;
-    float *to_f32;  // mixed precision, last exact round: the f32 records the continuing paths are converted into (else null)
-};
-template <class R, int TAG> void launch_shade_tag(const ShadeArgs<R> &a) {
-    if (a.rp.integrator != 0)
-        hipLaunchKernelGGL((k_shade<R, TAG, true>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
-                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
-    else
-        hipLaunchKernelGGL((k_shade<R, TAG, false>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
-                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
-}
-template <class R> void launch_shade(int tag, const ShadeArgs<R> &a) {
-    switch (tag) {
-        case 0: launch_shade_tag<R, 0>(a); break;
-        case 1: launch_shade_tag<R, 1>(a); break;
-        case 2: launch_shade_tag<R, 2>(a); break;
-        case 3: launch_shade_tag<R, 3>(a); break;
-        case 4: launch_shade_tag<R, 4>(a); break;
-        case 5: launch_shade_tag<R, 5>(a); break;
-        case 6: launch_shade_tag<R, 6>(a); break;
-        case 7: launch_shade_tag<R, 7>(a); break;
-        case 8: launch_shade_tag<R, 8>(a); break;
-        case 9: launch_shade_tag<R, 9>(a); break;
-        case 10: launch_shade_tag<R, 10>(a); break;
-        case 11: launch_shade_tag<R, 11>(a); break;
-        case 12: launch_shade_tag<R, 12>(a); break;
-        case 13: launch_shade_tag<R, 13>(a); break;
-        case 14: launch_shade_tag<R, 14>(a); break;
-        case 15: launch_shade_tag<R, 15>(a); break;
-        case 16: launch_shade_tag<R, 16>(a); break;
-        default: launch_shade_tag<R, TAG_MISS>(a); break;
-    }
-}
-
-// Debug aid (TAKE_HIP_DUMP_SLOT=<slot>): print one path's state after every kernel of a round.
-template <class R> void dump_slot(const PathState<R> &st, int64_t slot, const char *tag, int k, hipStream_t stream) {
-    (void)hipStreamSynchronize(stream);
-    std::fprintf(stderr, "[slot %lld] k=%d %s R:", (long long)slot, k, tag);
-    R rec[PATH_REC];
-    (void)hipMemcpy(rec, st.r + slot * PATH_REC, sizeof rec, hipMemcpyDeviceToHost);
-    for (int c = 0; c < PATH_REC; c++)
-        if (c != S_HIT && c != S_CTR && c != S_FLAGS) std::fprintf(stderr, " %.17g", (double)rec[c]);
-    std::fprintf(stderr, " I:");
-    for (int c : {(int)S_HIT, (int)S_CTR, (int)S_FLAGS}) std::fprintf(stderr, " %d", *reinterpret_cast<int32_t *>(&rec[c]));
-    std::fprintf(stderr, "\n");
-}
-
-// The shared buffers of a render's rounds: queues, queue words, sort scratch, counters.  They belong to the scene whose
-// precision owns the workspace (mixed-precision renders: the f64 scene's; the f32 rounds use them too — slot numbers
-// and queue words do not depend on the precision of the records they point to).
-struct RoundWs {
-    int32_t *q;  // queue words + tag counts
-    int32_t *queue[2], *shadow_queue, *sorted_queue;
-    uint8_t *sort_keys;
-    int32_t *sort_hist, *sort_base;
-    unsigned long long *counters;
-    int wide_grid;
-};
-// One round k of a batch on the records of precision RR: closest hits of the extend queue, material sort, shade,
-// shadow rays.  (Everything is enqueued; nothing waits.)
-// Round 0 of the default integrator on the default node format: no generate pass (CameraIo).  The counting instances,
-// the other integrators (their shade rounds read the initial flag word) and the other node formats keep k_generate.
-// TAKE_HIP_CAMERA_FUSED=0 turns it off (A/B runs).
-template <class RR> bool camera_fused(const SceneT<RR> &sc, const RenderParams<RR> &rp, bool counting) {
-    static const bool enabled = !(std::getenv("TAKE_HIP_CAMERA_FUSED") && std::atoi(std::getenv("TAKE_HIP_CAMERA_FUSED")) == 0);
-    return enabled && TQ_GROUP == 1 && !counting && rp.integrator == 0 && sc.dev.qnodes != nullptr && sc.dev.qnodes8 == nullptr;
-}
-
-template <class RR>
-void launch_round(TakeScene *ts, SceneT<RR> &sc, const RoundWs &ws, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound,
-                  Timer &tm, bool counting, bool sort_materials, hipStream_t stream, int64_t dump, int64_t slots, bool tail = false,
-                  float *to_f32 = nullptr) {
-    int32_t *q = ws.q;
-    int32_t *tag_count = q + Q_NUM_WORDS;
-    const int cur = k & 1, next = cur ^ 1;
-    int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0), *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
-    StackSpill spill{sc.spill.p, sc.spill_stride};
-    const PathIo<RR> io_ext{sc.dev.prims, st, ws.queue[cur], rp.ray_eps}, io_shadow{sc.dev.prims, st, ws.shadow_queue, rp.ray_eps};
-    // persistent trace grid, cut down when the queue (bounded by n_bound) cannot fill it: one block per 128 rays
-    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));
-    hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, stream, q, next);
-    tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
-    if (k == 0 && camera_fused<RR>(sc, rp, counting)) {
-        // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
-        CameraIo<RR> io_cam;
-        static_cast<PathIo<RR> &>(io_cam) = io_ext;
-        io_cam.cam = sc.dev.cam, io_cam.rp = rp;
-        if (sc.dev.inst_trace)
-            hipLaunchKernelGGL((k_trace_group<RR, TQ_GROUP, false, false, CameraIo<RR>, true, true, 4>), tgrid, dim3(TQ_BLOCK), 0, stream, sc.dev,
-                               io_cam, n_cur, 0, q + Q_HEAD_CLOSEST, ws.counters, (int)C_RAYS_CLOSEST, spill);
-        else
-            hipLaunchKernelGGL((k_trace_group<RR, TQ_GROUP, false, false, CameraIo<RR>, true, false, 4>), tgrid, dim3(TQ_BLOCK), 0, stream, sc.dev,
-                               io_cam, n_cur, 0, q + Q_HEAD_CLOSEST, ws.counters, (int)C_RAYS_CLOSEST, spill);
-    } else {
-        launch_trace<RR>(sc.group, false, counting, tgrid, stream, sc.dev, io_ext, n_cur, 0, q + Q_HEAD_CLOSEST, ws.counters,
-                         tail ? (int)C_RAYS_CLOSEST_TAIL : (int)C_RAYS_CLOSEST, spill);
-    }
-    tm.end();
-    if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_closest", k, stream);
-    const int32_t *shade_in = ws.queue[cur];
-    if (sort_materials) {
-        tm.begin(TK_OTHER);
-        // every wave of the sort gets >= 512 entries of the (bounded) queue: the one-block scan walks
-        // 13 x waves counters, which must not dominate small rounds (it was 40 % of a 256x256 render)
-        const int sort_grid = (int)std::max<int64_t>(1, std::min<int64_t>(ws.wide_grid, (n_bound + 2047) / 2048));
-        hipLaunchKernelGGL((k_sort_count<RR>), dim3(sort_grid), dim3(BLOCK), 0, stream, sc.dev.prims, sc.dev.inst_shade, st,
-                           ws.queue[cur], n_cur, ws.sort_keys, ws.sort_hist);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_SCAN_THREADS), 0, stream, ws.sort_hist, ws.sort_base, tag_count,
-                           sort_grid * (BLOCK / WAVE));
-        hipLaunchKernelGGL(k_sort_scatter, dim3(sort_grid), dim3(BLOCK), 0, stream, ws.queue[cur], n_cur, ws.sort_keys, ws.sort_base,
-                           ws.sorted_queue);
-        tm.end();
-        shade_in = ws.sorted_queue;
-    }
-    tm.begin(TK_SHADE);
-    {
-        const int shade_grid = (int)((n_bound + BLOCK - 1) / BLOCK);
-        ShadeArgs<RR> sa{sc.dev, rp, st, shade_in, n_cur, sort_materials ? tag_count : nullptr, ws.queue[next],
-                         n_next, ws.shadow_queue, q + Q_N_SHADOW, k, ws.counters, shade_grid, stream, to_f32};
-        if (sort_materials) {
-            // one specialised launch per material tag present in the scene + the miss segment
-            for (int t = 0; t < TAKE_MAT_COUNT; t++)
-                if (sc.host.tag_mask & (1u << t)) launch_shade<RR>(t, sa);
-            launch_shade<RR>(TAG_MISS, sa);
-        } else {
-            launch_shade<RR>(sc.host.single_tag, sa);
-        }
-    }
-    tm.end();
-    if constexpr (sizeof(RR) == 8) {
-        if (!TK_SHADE_RECORD && to_f32 != nullptr) {
-            // mixed precision, last exact round, builds without the register copy of the record: the paths that go on
-            // continue on f32 records from here — converted before this round's shadow rays, as k_shade does it
-            tm.begin(TK_OTHER);
-            hipLaunchKernelGGL(k_convert_state, dim3(ws.wide_grid), dim3(BLOCK), 0, stream, st, PathState<float>{to_f32, slots},
-                               ws.queue[next], n_next);
-            tm.end();
-        }
-    }
-    if (dump >= 0 && dump < slots) dump_slot(st, dump, "after shade", k, stream);
-    if (k <= rp.max_depth && rp.integrator == 0) {  // integrators 1..3 trace no shadow rays
-        tm.begin(TK_SHADOW);
-        launch_trace<RR>(sc.group, true, counting, tgrid, stream, sc.dev, io_shadow, q + Q_N_SHADOW, 0, q + Q_HEAD_SHADOW, ws.counters,
-                         (int)C_RAYS_SHADOW, spill);
-        tm.end();
-        if (dump >= 0 && dump < slots) dump_slot(st, dump, "after trace_shadow", k, stream);
-    }
-}
-
-// the counters of a new call: zeros, and the bytes the traversal of `sc` reads per node and per primitive test
-template <class R> TakeCounters fresh_counters(const SceneT<R> &sc) {
-    TakeCounters c{};
-    c.node_bytes = sc.dev.qnodes8 ? sizeof(QNode8) : (sc.dev.qnodes ? sizeof(QNode4) : sizeof(Node4<R>));
-    c.prim_bytes = PRIM_TEST_BYTES * (int)(sizeof(R) / 4);
-    return c;
-}
-
-// first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
-// random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
-// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
-template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
-                                   int64_t first_sample = 0, bool keep_accum = false) {
-    if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
-    const int W = sc.host.cam.width, H = sc.host.cam.height;
-    if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
-    if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
-    if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
-    if (o.integrator != 0 && sc.host.env.light >= 0)
-        return fail(TAKE_E_INVALID, "integrators 1..3 are the reference's own: they do not know the environment-map extension");
-    const int stride = o.strip_stride > 0 ? o.strip_stride : 1;
-    const int first = o.strip_first;
-    if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int n_rows = rows_of(H, first, stride, nullptr);
-    const int64_t npix = (int64_t)n_rows * W;
-    ts->counters = fresh_counters(sc);
-    if (ts->precision == TAKE_PRECISION_MIXED) ts->counters.prim_bytes = PRIM_TEST_BYTES;  // (most rounds read the f32 records)
-    if (npix == 0) return TAKE_OK;
-    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
-
-    // paths in flight per batch: up to 512 Mi (69 GB of f32 path state + 9 GB of queues) — bigger batches keep the
-    // persistent trace grid full for more of each bounce (measured on the 1M-triangle scene, spp per batch 8 / 16 / 32 /
-    // 64 / 128 / 256 = 53.2 / 57.7 / 60.3 / 61.9 | 64.5 / 64.9 / 65.5 Msamples/s), and a 288 GB device has the room;
-    // capped at four fifths of what is free now (round 3: it was half — a mixed-precision render, 418 B per path, then
-    // needed two batches for 256 spp at 1920x1080 and lost ~1 % to the second set of thin late rounds)
-    int64_t target = (int64_t)512 << 20;
-    {
-        size_t free_b = 0, total_b = 0;
-        // (mixed precision: every slot has an f32 record beside its f64 one)
-        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (ts->precision == TAKE_PRECISION_MIXED ? sizeof(float) : 0)) +
-                                 4 * (int64_t)sizeof(int32_t);
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const int64_t have = (int64_t)sc.capacity * per_path;  // already allocated by an earlier render
-            // (shards of a scene group that share a device size their batches concurrently: each takes its share)
-            target = std::min<int64_t>(target, std::max<int64_t>((int64_t)1 << 20, ((int64_t)free_b / std::max(1, ts->mem_share) + have) / 5 * 4 / per_path));
-        }
-    }
-    int spb = o.samples_per_batch > 0 ? o.samples_per_batch : (int)std::max<int64_t>(1, target / npix);
-    spb = std::min(spb, o.spp);
-    while ((int64_t)spb * npix >= ((int64_t)1 << 31) - (1 << 26)) spb--;
-    // The free-memory figure above is a snapshot: another process on the device (or another host thread) may take the
-    // memory before the allocation lands.  A batch size the caller did not pin is then halved until it fits — the
-    // image does not depend on it (a sample's random stream is a function of seed, pixel and sample index only).
-    const bool mixed_records = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
-    int64_t slots = 0;
-    int rc = TAKE_OK;
-    for (;;) {
-        slots = (int64_t)spb * npix;
-        rc = ensure_workspace(sc, slots, npix);
-        if (rc == TAKE_OK && mixed_records && (int64_t)ts->f.state_r.n < (int64_t)PATH_REC * slots &&
-            ts->f.state_r.alloc((size_t)PATH_REC * slots) != hipSuccess) {
-            ts->f.state_r.release();
-            release_workspace(sc);
-            rc = fail(TAKE_E_NOMEM, "out of device memory for the f32 path records of a mixed-precision render (" + std::to_string(slots) + " path slots)");
-        }
-        if (rc != TAKE_E_NOMEM || spb == 1 || o.samples_per_batch > 0) break;
-        (void)hipGetLastError();
-        spb = (spb + 1) / 2;
-    }
-    if (rc) return rc;
-
-    PathState<R> st{sc.state_r.p, sc.capacity};
-    RenderParams<R> rp{};
-    rp.width = W, rp.height = H, rp.n_local_rows = n_rows, rp.npix = (int32_t)npix;
-    rp.inv_npix = 1.0 / (double)npix, rp.inv_width = 1.0 / (double)W;
-    rp.strip_first = first, rp.strip_stride = stride;
-    rp.spp = o.spp, rp.max_depth = o.max_depth, rp.seed = o.seed, rp.integrator = o.integrator;
-    rp.ray_eps = o.ray_epsilon > 0 ? R(o.ray_epsilon) : (sizeof(R) == 8 ? R(1e-7) : R(1e-4));
-
-    const bool timing = (ts->instrumentation & 1) != 0;
-    const bool counting = (ts->instrumentation & 2) != 0;
-    const bool sort_materials = sc.host.n_material_tags > 1;
-    const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT");
-    const int64_t dump = dump_env ? std::atoll(dump_env) : -1;
-    ts->events.reset();
-    ts->timed.clear();
-    Timer tm{ts, stream, timing};
-    int32_t *q = sc.qwords.p;
-    const int wide_grid = (int)std::min<int64_t>((slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-    const int pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-
-    if (sort_materials) {
-        const size_t need = (size_t)N_SORT_KEYS * wide_grid * (BLOCK / WAVE);
-        if (sc.sort_hist.n != need) {
-            HIP_TRY(sc.sort_hist.alloc(need));
-            HIP_TRY(sc.sort_base.alloc(need));
-        }
-    }
-    const RoundWs ws{q, {sc.queue[0].p, sc.queue[1].p}, sc.shadow_queue.p, sc.sorted_queue.p, sc.sort_keys.p, sc.sort_hist.p, sc.sort_base.p,
-                     sc.counters.p, wide_grid};
-    // mixed precision (TAKE_PRECISION_MIXED): rounds k < exact_rounds on the f64 records and scene, the rest on f32
-    // records of the same slots and the f32 scene
-    bool mixed = false;
-    int exact_rounds = 0;
-    PathState<float> st32{nullptr, 0};
-    RenderParams<float> rp32{};
-    if constexpr (sizeof(R) == 8) {
-        mixed = ts->precision == TAKE_PRECISION_MIXED;
-        if (mixed) {
-            exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
-            if (o.integrator != 0) return fail(TAKE_E_INVALID, "mixed precision renders the reference's path_tracing (integrator 0) only");
-            st32 = PathState<float>{ts->f.state_r.p, slots};
-            rp32.width = rp.width, rp32.height = rp.height, rp32.n_local_rows = rp.n_local_rows, rp32.npix = rp.npix;
-            rp32.inv_npix = rp.inv_npix, rp32.inv_width = rp.inv_width;
-            rp32.strip_first = rp.strip_first, rp32.strip_stride = rp.strip_stride, rp32.spp = rp.spp, rp32.max_depth = rp.max_depth;
-            rp32.integrator = rp.integrator, rp32.seed = rp.seed;
-            rp32.ray_eps = o.ray_epsilon > 0 ? (float)o.ray_epsilon : 1e-4f;
-        }
-    }
-    if (!keep_accum) HIP_TRY(hipMemsetAsync(sc.accum.p, 0, sizeof(R) * 3 * npix, stream));
-    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
-    hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
-    HIP_TRY(hipEventRecord(ev_begin, stream));
-    HIP_TRY(ts->poll.create());
-    int64_t poll_issued = 0, poll_done = 0;
-
-    for (int s0 = 0; s0 < o.spp; s0 += spb) {
-        const int nb = std::min(spb, o.spp - s0);
-        const int64_t n = (int64_t)nb * npix;
-        rp.s0 = (int32_t)first_sample + s0;
-        rp.spb = nb;
-        rp32.s0 = rp.s0, rp32.spb = nb;
-        tm.begin(TK_OTHER);
-        if (camera_fused<R>(sc, rp, counting)) hipLaunchKernelGGL(k_iota, dim3(wide_grid), dim3(BLOCK), 0, stream, sc.queue[0].p, n);
-        else hipLaunchKernelGGL((k_generate<R>), dim3(wide_grid), dim3(BLOCK), 0, stream, sc.dev, rp, st, sc.queue[0].p, n);
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, q, (int)Q_N_EXT0, (int32_t)n);
-        tm.end();
-        const int rounds = o.max_depth + 2;
-        int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
-        for (int k = 0; k < rounds; k++) {
-            const int next = (k & 1) ^ 1;
-            int32_t *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
-            if constexpr (sizeof(R) == 8) {
-                // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
-                // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
-                if (mixed && k >= exact_rounds) launch_round<float>(ts, ts->f, ws, st32, rp32, k, n_bound, tm, counting, sort_materials, stream, -1, slots, true);
-                else launch_round<R>(ts, sc, ws, st, rp, k, n_bound, tm, counting, sort_materials, stream, dump, slots, false,
-                                     (mixed && k == exact_rounds - 1) ? st32.r : nullptr);
-            } else {
-                launch_round<R>(ts, sc, ws, st, rp, k, n_bound, tm, counting, sort_materials, stream, dump, slots);
-            }
-            // Queue length of the next round, read back asynchronously (pinned word + event, polled — the launch loop
-            // never waits for the GPU): any value that has arrived bounds the grids of all later rounds (queues only
-            // shrink), and a zero ends the launching.  (Round 1 blocked on a stream sync every 4 rounds: with the
-            // ~370 launches of a small render that was a third of its 12 ms.)
-            if (k + 1 < rounds && poll_issued - poll_done < PollRing::SIZE) {
-                const int slot = poll_issued % PollRing::SIZE;
-                HIP_TRY(hipMemcpyAsync(ts->poll.word + slot, n_next, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipEventRecord(ts->poll.ev[slot], stream));
-                poll_issued++;
-            }
-            bool finished = false;
-            while (poll_done < poll_issued) {
-                const int slot = poll_done % PollRing::SIZE;
-                hipError_t q = hipEventQuery(ts->poll.ev[slot]);
-                if (q == hipErrorNotReady) {
-                    (void)hipGetLastError();  // "not ready" is an answer, not an error: keep it out of the sticky state
-                    // stay at most 8 rounds ahead of the GPU: enough queued work that it never idles, close enough
-                    // that a batch whose paths have all ended stops being launched
-                    if (poll_issued - poll_done < 8) break;
-                    q = hipEventSynchronize(ts->poll.ev[slot]);
-                }
-                HIP_TRY(q);
-                const int32_t alive = ts->poll.word[slot];
-                poll_done++;
-                n_bound = std::min<int64_t>(n_bound, alive);
-                if (alive == 0) finished = true;
-            }
-            if (finished) break;
-        }
-        // (outstanding read-backs of this batch complete with the stream; the ring indices just move on)
-        poll_done = poll_issued;
-        tm.begin(TK_OTHER);
-        if constexpr (sizeof(R) == 8) {
-            if (mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(pix_grid), dim3(BLOCK), 0, stream, st, st32, sc.accum.p, (int32_t)npix, nb);
-            else hipLaunchKernelGGL((k_accumulate<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, st, sc.accum.p, (int32_t)npix, nb);
-        } else {
-            hipLaunchKernelGGL((k_accumulate<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, st, sc.accum.p, (int32_t)npix, nb);
-        }
-        tm.end();
-    }
-    tm.begin(TK_OTHER);
-    hipLaunchKernelGGL((k_resolve<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.accum.p, (R *)d_out, W, n_rows,
-                       (int32_t)first_sample + o.spp);
-    tm.end();
-    HIP_TRY(hipEventRecord(ev_end, stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(tm.err));
-
-    unsigned long long c[C_NUM_WORDS];
-    HIP_TRY(hipMemcpy(c, sc.counters.p, sizeof c, hipMemcpyDeviceToHost));
-    TakeCounters &tc = ts->counters;
-    tc.samples = (uint64_t)npix * (uint64_t)o.spp;
-    tc.rays_closest = c[C_RAYS_CLOSEST] + c[C_RAYS_CLOSEST_TAIL];
-    tc.rays_closest_f32 = c[C_RAYS_CLOSEST_TAIL];
-    tc.rays_shadow = c[C_RAYS_SHADOW];
-    tc.node_visits = c[C_NODE_VISITS];
-    tc.prim_tests = c[C_PRIM_TESTS];
-    tc.bounces = c[C_BOUNCES];
-    tc.leaf_visits = c[C_LEAF_VISITS];
-    tc.wave_node_steps = c[C_WAVE_NODE_STEPS];
-    tc.wave_leaf_steps = c[C_WAVE_LEAF_STEPS];
-    if (std::getenv("TAKE_HIP_VERBOSE"))
-        std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
-                     c[C_WAIT_SLOTS], c[C_IDLE_SLOTS], c[C_NODE_VISITS], c[C_OCC_CACHE_HITS], c[C_RAYS_SHADOW]);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    tc.ms_total = ms;
-    double acc[TK_NUM] = {0, 0, 0, 0, 0};
-    for (auto &t : ts->timed) {
-        float m = 0;
-        if (hipEventElapsedTime(&m, t.second.first, t.second.second) == hipSuccess) acc[t.first] += m;
-        if (t.first == TK_CLOSEST || t.first == TK_CLOSEST_TAIL) tc.launches_trace_closest++;
-        if (t.first == TK_CLOSEST_TAIL) tc.launches_trace_closest_f32++;
-        if (t.first == TK_SHADOW) tc.launches_trace_shadow++;
-    }
-    tc.ms_trace_closest = acc[TK_CLOSEST] + acc[TK_CLOSEST_TAIL];
-    tc.ms_trace_closest_f32 = acc[TK_CLOSEST_TAIL];
-    tc.ms_trace_shadow = acc[TK_SHADOW];
-    tc.ms_shade = acc[TK_SHADE];
-    tc.ms_other = acc[TK_OTHER];
-    return TAKE_OK;
-}
-
-template <class R>
-int trace_impl(TakeScene *ts, SceneT<R> &sc, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any, bool count,
-               hipStream_t stream) {
-    if (n < 0 || n >= ((int64_t)1 << 31) - (1 << 26)) return fail(TAKE_E_INVALID, "ray count out of range");
-    StackSpill spill{sc.spill.p, sc.spill_stride};
-    int32_t *q = sc.qwords.p;
-    HIP_TRY(hipMemsetAsync(q + Q_HEAD_CLOSEST, 0, sizeof(int32_t), stream));
-    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
-    hipEvent_t a = nullptr, b = nullptr;
-    ts->events.reset();
-    a = ts->events.get(), b = ts->events.get();
-    HIP_TRY(hipEventRecord(a, stream));
-    const HookIo<R> io{sc.dev.prims, (const RayAoS<R> *)d_rays, (HitAoS<R> *)d_hits, d_occ, sc.dev.inst_shade};
-    launch_trace<R>(sc.group, any, count, dim3(sc.trace_grid), stream, sc.dev, io, nullptr, (int32_t)n, q + Q_HEAD_CLOSEST,
-                    sc.counters.p, -1, spill);
-    HIP_TRY(hipEventRecord(b, stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    unsigned long long c[C_NUM_WORDS];
-    HIP_TRY(hipMemcpy(c, sc.counters.p, sizeof c, hipMemcpyDeviceToHost));
-    ts->counters = fresh_counters(sc);
-    (any ? ts->counters.rays_shadow : ts->counters.rays_closest) = (uint64_t)n;
-    ts->counters.node_visits = c[C_NODE_VISITS];
-    ts->counters.prim_tests = c[C_PRIM_TESTS];
-    ts->counters.leaf_visits = c[C_LEAF_VISITS];
-    ts->counters.wave_node_steps = c[C_WAVE_NODE_STEPS];
-    ts->counters.wave_leaf_steps = c[C_WAVE_LEAF_STEPS];
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, a, b));
-    (any ? ts->counters.ms_trace_shadow : ts->counters.ms_trace_closest) = ms;
-    (any ? ts->counters.launches_trace_shadow : ts->counters.launches_trace_closest) = 1;
-    ts->counters.ms_total = ms;
-    return TAKE_OK;
-}
-
-template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
-    if (n == 0) return TAKE_OK;
-    // entry distances are ordered through their bit patterns (non-negative floats): a ray must start at tmin >= 0
-    for (int64_t i = 0; i < n; i++) {
-        const RayAoS<R> &q = ((const RayAoS<R> *)rays)[i];
-        if (!(q.tmin >= R(0))) return fail(TAKE_E_INVALID, "ray " + std::to_string(i) + ": tmin must be >= 0");
-    }
-    DevBuf<RayAoS<R>> d_rays;
-    DevBuf<HitAoS<R>> d_hits;
-    DevBuf<int32_t> d_occ;
-    HIP_TRY(d_rays.alloc(n));
-    if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TAKE_E_DEVICE, "ray upload failed");
-    if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) return fail(TAKE_E_NOMEM, "hit buffer allocation failed");
-    const int rc = trace_impl(ts, sc, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
-    if (rc) return rc;
-    hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
-                       : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(TAKE_E_DEVICE, "hit download failed");
-    return TAKE_OK;
-}
-
-// a render of npix pixels into the scene's own output buffer, sc.out (-> img)
-template <class R> int render_to_out(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, const void *&img) {
-    int rc = ensure_workspace(sc, 0, npix);
-    if (!rc) rc = render_impl(ts, sc, o, sc.out.p, nullptr);
-    img = sc.out.p;
-    return rc;
-}
-
-// A scene lives on the device that was current when it was created; every entry point that touches it makes that
-// device current for the duration of the call and restores the caller's afterwards.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-#define TAKE_ON_DEVICE(ts)                                                                            \
-    DeviceGuard guard_((ts)->device);                                                                 \
-    if (!guard_.ok) return fail(TAKE_E_DEVICE, "cannot make the scene's device current")
 
 }  // namespace
 
@@ -1338,7 +594,7 @@ int take_hip_render_rows(const TakeScene *ts, int32_t strip_first, int32_t strip
 int take_hip_render_device(TakeScene *ts, const TakeRenderOpts *opts, void *d_rgb_out, void *stream) {
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    return on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, *opts, d_rgb_out, (hipStream_t)stream); });
+    return render_scene(ts, *opts, d_rgb_out, (hipStream_t)stream);
 }
 
 // Progressive rendering (the per-pixel accumulate of src/render.cpp:68-78 kept resident between calls).
@@ -1360,7 +616,7 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
     if (first + (int64_t)opts->spp >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many accumulated samples");
     // (a workspace grown for a bigger batch keeps the accumulator: ensure_workspace only ever enlarges it, and the
     // strip set — hence the pixel count — is fixed for the sequence)
-    const int rc = on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh); });
+    const int rc = render_scene(ts, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh);
     if (rc) {
         ts->acc_samples = 0;  // the accumulator may hold a partial batch: the sequence has to restart
         return rc;
@@ -1384,25 +640,9 @@ int take_hip_render(TakeScene *ts, const TakeRenderOpts *opts, void *rgb_out_hos
     if (bytes == 0) return TAKE_OK;
     // render into the scene's own output buffer, then copy out
     const void *img = nullptr;
-    const int rc = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, *opts, (int64_t)rows * W, img); });
+    const int rc = render_scene_to_out(ts, *opts, (int64_t)rows * W, img);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(rgb_out_host, img, bytes, hipMemcpyDeviceToHost));
-    return TAKE_OK;
-}
-
-int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t width, int32_t height, uint16_t *d_out, void *stream) {
-    if (!d_rgb || !d_out || width <= 0 || height <= 0) return fail(TAKE_E_INVALID, "bad argument");
-    if (precision != TAKE_PRECISION_F32 && precision != TAKE_PRECISION_F64) return fail(TAKE_E_INVALID, "unknown precision");
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    const int64_t total = (int64_t)width * height * 3;
-    const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 8192));
-    if (precision == TAKE_PRECISION_F64)
-        hipLaunchKernelGGL((k_pack_exr<double>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const double *)d_rgb, width, height, d_out);
-    else
-        hipLaunchKernelGGL((k_pack_exr<float>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const float *)d_rgb, width, height, d_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return TAKE_OK;
 }
 
@@ -1413,7 +653,7 @@ int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uin
     TakeRenderOpts o = *opts;
     o.strip_first = 0, o.strip_stride = 1;
     const void *d_img = nullptr;
-    int rc = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, o, (int64_t)W * H, d_img); });
+    int rc = render_scene_to_out(ts, o, (int64_t)W * H, d_img);
     if (rc) return rc;
     DevBuf<uint16_t> halves;
     if (halves.alloc((size_t)W * H * 3) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the scanline buffer");
@@ -1426,63 +666,21 @@ int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uin
 int take_hip_trace_closest(TakeScene *ts, const void *rays, int64_t n, void *hits) {
     if (!ts || (n > 0 && (!rays || !hits))) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, hits, nullptr, false); });
+    return trace_rays_host(ts, rays, n, hits, nullptr, false);
 }
 int take_hip_trace_any(TakeScene *ts, const void *rays, int64_t n, int32_t *occluded) {
     if (!ts || (n > 0 && (!rays || !occluded))) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, nullptr, occluded, true); });
+    return trace_rays_host(ts, rays, n, nullptr, occluded, true);
 }
 int take_hip_trace_closest_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, int32_t count_mode,
                                   void *stream) {
     if (!ts || (n > 0 && (!d_rays || !d_hits))) return fail(TAKE_E_INVALID, "null argument");
     if (n == 0) return TAKE_OK;
     TAKE_ON_DEVICE(ts);
-    return on_primary(ts, [&](auto &sc) { return trace_impl(ts, sc, d_rays, n, d_hits, nullptr, false, count_mode != 0, (hipStream_t)stream); });
+    return trace_rays_device(ts, d_rays, n, d_hits, count_mode != 0, (hipStream_t)stream);
 }
 
-int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int64_t n, int32_t in_cols,
-                         const double *rnd, double *out, int32_t out_cols) {
-    if (!in || !out || !rnd || n < 0) return fail(TAKE_E_INVALID, "null argument");
-    int nd = check_device();
-    if (nd < 0) return nd;
-    if (n == 0) return TAKE_OK;
-    DevBuf<double> d_in, d_rnd, d_out;
-    DevBuf<ImageInfo> d_img;
-    DevBuf<float> d_texf;
-    DevBuf<double> d_texd;
-    // the fixed 5x4 image the reference harness used for the material / texture tables (oracle/ref_harness.cpp)
-    std::vector<float> tf(60);
-    std::vector<double> td(60);
-    for (int y = 0; y < 4; y++)
-        for (int x = 0; x < 5; x++) {
-            const double c[3] = {0.1 + 0.15 * x + 0.01 * y, 0.9 - 0.2 * y + 0.02 * x, 0.3 + 0.05 * ((x * 3 + y * 7) % 5)};
-            for (int a = 0; a < 3; a++) td[3 * (y * 5 + x) + a] = c[a], tf[3 * (y * 5 + x) + a] = (float)c[a];
-        }
-    std::vector<ImageInfo> img{ImageInfo{5, 4, 0}};
-    if (d_in.alloc((size_t)n * in_cols) != hipSuccess || d_rnd.alloc((size_t)n * TAB_RND) != hipSuccess ||
-        d_out.alloc((size_t)n * out_cols) != hipSuccess || d_img.upload(img) != hipSuccess ||
-        d_texf.upload(tf) != hipSuccess || d_texd.upload(td) != hipSuccess)
-        return fail(TAKE_E_NOMEM, "debug table allocation failed");
-    if (hipMemcpy(d_in.p, in, d_in.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_rnd.p, rnd, d_rnd.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_out.p, 0, d_out.bytes()) != hipSuccess)
-        return fail(TAKE_E_DEVICE, "debug table upload failed");
-    const dim3 g((unsigned)((n + BLOCK - 1) / BLOCK)), b(BLOCK);
-    if (precision == TAKE_PRECISION_F64) {
-        DeviceScene<double> sc{};
-        sc.images = d_img.p, sc.texels = d_texd.p;
-        hipLaunchKernelGGL((k_debug_table<double>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
-    } else {
-        DeviceScene<float> sc{};
-        sc.images = d_img.p, sc.texels = d_texf.p;
-        hipLaunchKernelGGL((k_debug_table<float>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
-    }
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(TAKE_E_DEVICE, "debug table kernel failed");
-    if (hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(TAKE_E_DEVICE, "debug table download failed");
-    return TAKE_OK;
-}
 
 // ------------------------------------------------------------------------------------------------ scene groups
 }  // extern "C"
@@ -1496,7 +694,7 @@ template <class T> int peer_copy(DevBuf<T> &dst, int dst_dev, const DevBuf<T> &s
         return fail(TAKE_E_DEVICE, "hipMemcpyPeer of a scene array failed");
     return TAKE_OK;
 }
-template <class R> int replicate_t(const SceneT<R> &a, int a_dev, int a_cus, SceneT<R> &b, int b_dev, int b_cus) {
+template <class R> int replicate_t(const SceneT<R> &a, int a_dev, SceneT<R> &b, int b_dev, int b_cus) {
     int rc = TAKE_OK;
     SceneT<R>::for_each_array([&](auto &dst, const auto &src) { if (!rc) rc = peer_copy(dst, b_dev, src, a_dev); }, b, a);
     if (rc) return rc;
@@ -1505,15 +703,10 @@ template <class R> int replicate_t(const SceneT<R> &a, int a_dev, int a_cus, Sce
     b.bind();
     // the persistent trace grid of THIS device: blocks per CU are a property of the kernels (the same code object on
     // every device), the CU count is the replica device's own
-    const int per_cu = std::max(1, a.trace_grid / std::max(1, a_cus));
-    const int64_t groups_per_block = a.trace_grid > 0 ? a.spill_stride / a.trace_grid : 0;
-    const int64_t spill_levels = a.spill_stride > 0 ? (int64_t)a.spill.n / a.spill_stride : 0;
-    b.group = a.group, b.built_on_device = a.built_on_device, b.trace_grid = per_cu * b_cus, b.spill_stride = (int64_t)b.trace_grid * groups_per_block;
-    if (b.qwords.alloc(a.qwords.n) != hipSuccess || b.counters.alloc(a.counters.n) != hipSuccess ||
-        b.spill.alloc((size_t)(b.spill_stride * spill_levels)) != hipSuccess)
-        return fail(TAKE_E_NOMEM, "out of device memory for a scene replica");
-    HIP_TRY(hipMemset(b.qwords.p, 0, b.qwords.bytes()));
-    HIP_TRY(hipMemset(b.counters.p, 0, b.counters.bytes()));
+    b.built_on_device = a.built_on_device, b.trace = a.trace, b.blocks_per_cu = a.blocks_per_cu;
+    const hipError_t e = alloc_trace_state(b, b_cus);
+    if (e == hipErrorOutOfMemory) return fail(TAKE_E_NOMEM, "out of device memory for a scene replica");
+    HIP_TRY(e);
     return TAKE_OK;
 }
 // -> a new scene handle on `device` (made current for the call), equal to `src`
@@ -1529,8 +722,8 @@ int replicate_scene(const TakeScene *src, int device, TakeScene **out) {
     (void)hipGetLastError();
     // the sides take_hip_scene_create made, in its order
     int rc = TAKE_OK;
-    if (src->precision != TAKE_PRECISION_F32) rc = replicate_t(src->d, src->device, src->num_cus, ts->d, device, ts->num_cus);
-    if (!rc && src->precision != TAKE_PRECISION_F64) rc = replicate_t(src->f, src->device, src->num_cus, ts->f, device, ts->num_cus);
+    if (src->precision != TAKE_PRECISION_F32) rc = replicate_t(src->d, src->device, ts->d, device, ts->num_cus);
+    if (!rc && src->precision != TAKE_PRECISION_F64) rc = replicate_t(src->f, src->device, ts->f, device, ts->num_cus);
     if (rc) return rc;
     *out = ts.release();
     return TAKE_OK;
@@ -1557,6 +750,7 @@ struct TakeSceneGroup {
 };
 
 namespace {
+constexpr int BLOCK = 256;  // threads per block of k_place_rows
 // compact rows of one shard -> their rows of the full image
 template <class R>
 __global__ void __launch_bounds__(BLOCK) k_place_rows(const R *__restrict__ src, const int32_t *__restrict__ rows, int n_rows,
@@ -1588,7 +782,7 @@ int group_render(TakeSceneGroup *g, const TakeRenderOpts &opts, void *d_out) {
                 return;
             }
             const void *rows = nullptr;
-            int r = on_primary(ts, [&](auto &sc) { return render_to_out(ts, sc, o, (int64_t)g->n_rows[k] * g->width, rows); });
+            int r = render_scene_to_out(ts, o, (int64_t)g->n_rows[k] * g->width, rows);
             if (!r && k > 0) {  // the one exchange: this shard's rows to the first device
                 const hipError_t e = hipMemcpyPeer(g->staging[k].p, g->scenes[0]->device, rows, ts->device, (size_t)g->n_rows[k] * row_words * esz);
                 if (e != hipSuccess) r = TAKE_E_DEVICE, g_error = std::string("hipMemcpyPeer: ") + hipGetErrorString(e);

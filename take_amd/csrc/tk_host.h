@@ -1,5 +1,6 @@
-// tk_host.h — host plumbing shared by the library's two units, tk_api.hip (scenes, rendering, trace hooks) and
-// tk_mesh.hip (mesh ingest): the error string, fault injection, pinned uploads, the owning device buffer.
+// tk_host.h — host plumbing shared by the library's units, tk_api.hip (scenes, groups, the C entry points),
+// tk_render.hip (rendering, trace hooks) and tk_mesh.hip (mesh ingest): the error string, fault injection, pinned
+// uploads, the owning device buffer.  (The scene handle the first two share is tk_scene_handle.h.)
 // Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
 // take_hip_last_error returns) and ONE TAKE_HIP_FAIL_ALLOC counter.
 #pragma once

@@ -1,0 +1,719 @@
+// tk_render.hip — the host side of tracing and rendering: the render workspace, the kernel launchers, the wavefront
+// render loop, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h; what tk_api.hip (scene
+// creation, groups, the C entry points) calls here is declared in tk_scene_handle.h.  Host code only orchestrates:
+// every per-sample operation runs in the kernels.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "take_hip.h"
+#include "tk_scene_handle.h"
+#include "tk_kernels.h"
+
+using namespace tk;
+using namespace tk_host;
+
+namespace {
+
+enum TimedKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_OTHER, TK_CLOSEST_TAIL /* mixed precision: closest hits of the f32 rounds */, TK_NUM };
+
+// The trace kernel instance for (scene's traversal, any-hit, counting, Io): fn(kernel, its block geometry).  The one
+// place that names an instance; the occupancy query, the launches and the spill size all come through here, so they
+// cannot disagree.  Instantiated: every node format (the 8-wide one with one ray per lane only) for PathIo and HookIo;
+// CameraIo for closest hits on compressed 4-wide nodes, not counting, only.  A combination outside that runs nothing: false.
+template <class R, bool ANY_HIT, bool COUNT, class Io, class Fn> bool with_trace_kernel(TraceKind kind, Fn &&fn) {
+    constexpr bool camera = std::is_same<Io, CameraIo<R>>::value;
+    auto pick = [&](auto qn, auto width) {
+        constexpr bool QN = decltype(qn)::value;
+        constexpr int W = decltype(width)::value;
+        if (kind.two_level) fn(k_trace_group<R, TQ_GROUP, ANY_HIT, COUNT, Io, QN, true, W>, GroupGeom<TQ_GROUP, W>{});
+        else fn(k_trace_group<R, TQ_GROUP, ANY_HIT, COUNT, Io, QN, false, W>, GroupGeom<TQ_GROUP, W>{});
+        return true;
+    };
+    if constexpr (!camera || (!ANY_HIT && !COUNT))
+        if (kind.nodes == NodeFormat::Q4) return pick(std::true_type{}, std::integral_constant<int, 4>{});
+    if constexpr (!camera) {
+        if (kind.nodes == NodeFormat::WIDE) return pick(std::false_type{}, std::integral_constant<int, 4>{});
+        if constexpr (TQ_GROUP == 1)
+            if (kind.nodes == NodeFormat::Q8) return pick(std::true_type{}, std::integral_constant<int, 8>{});
+    }
+    return false;
+}
+
+// Path-state / queue / framebuffer workspace of a scene, grown on demand.  A failed allocation leaves the scene
+// WITHOUT a workspace (capacity 0, every buffer released) and returns TAKE_E_NOMEM: the next render allocates afresh
+// instead of trusting a stale capacity over null pointers.
+template <class R> void release_workspace(SceneT<R> &sc) {
+    sc.state_r.release(), sc.queue[0].release(), sc.queue[1].release(), sc.shadow_queue.release();
+    sc.sorted_queue.release(), sc.sort_keys.release();
+    sc.capacity = 0;
+}
+template <class R> int ensure_workspace(SceneT<R> &sc, int64_t slots, int64_t npix) {
+    if (slots > sc.capacity) {
+        release_workspace(sc);
+        const bool ok = sc.state_r.alloc((size_t)PATH_REC * slots) == hipSuccess && sc.queue[0].alloc(slots) == hipSuccess &&
+                        sc.queue[1].alloc(slots) == hipSuccess && sc.shadow_queue.alloc(slots) == hipSuccess &&
+                        sc.sorted_queue.alloc(slots) == hipSuccess && sc.sort_keys.alloc(slots) == hipSuccess;
+        if (!ok) {
+            release_workspace(sc);
+            return fail(TAKE_E_NOMEM, "out of device memory for " + std::to_string(slots) + " path slots (" +
+                                          std::to_string((size_t)slots * (PATH_REC * sizeof(R) + 17) >> 20) + " MiB)");
+        }
+        sc.capacity = slots;
+    }
+    if ((int64_t)sc.accum.n < 3 * npix) {
+        if (sc.accum.alloc(3 * npix) != hipSuccess || sc.out.alloc(3 * npix) != hipSuccess) {
+            sc.accum.release(), sc.out.release();
+            return fail(TAKE_E_NOMEM, "out of device memory for the framebuffer");
+        }
+    }
+    return TAKE_OK;
+}
+
+__global__ void k_prep(int32_t *q, int next) {
+    const int t = threadIdx.x;
+    if (t == 0) {
+        q[Q_HEAD_CLOSEST] = 0;
+        q[Q_HEAD_SHADOW] = 0;
+        q[Q_N_SHADOW] = 0;
+        q[next ? Q_N_EXT1 : Q_N_EXT0] = 0;
+    }
+    if (t < 2 * N_SORT_KEYS) q[Q_NUM_WORDS + t] = 0;
+}
+__global__ void k_set_word(int32_t *q, int word, int32_t value) { q[word] = value; }
+
+struct Timer {
+    TakeScene *ts;
+    hipStream_t stream;
+    bool on;
+    hipError_t err = hipSuccess;  // first failure of an event call; render_impl reports it instead of bogus times
+    void begin(int which) {
+        if (!on) return;
+        hipEvent_t a = ts->events.get(), b = ts->events.get();
+        const hipError_t e = (a && b) ? hipEventRecord(a, stream) : hipErrorOutOfMemory;
+        if (e != hipSuccess && err == hipSuccess) err = e;
+        ts->timed.push_back({which, {a, b}});
+    }
+    void end() {
+        if (!on) return;
+        const hipEvent_t b = ts->timed.back().second.second;
+        const hipError_t e = b ? hipEventRecord(b, stream) : hipErrorOutOfMemory;
+        if (e != hipSuccess && err == hipSuccess) err = e;
+    }
+};
+
+// launch the trace kernel instance of a scene for (any-hit, counting)
+template <class R, class Io>
+hipError_t launch_trace(TraceKind kind, bool any, bool count, dim3 grid, hipStream_t stream, const DeviceScene<R> &dev, const Io &io,
+                        const int32_t *n_ptr, int32_t n_direct, int32_t *head, unsigned long long *counters, int counter_word,
+                        StackSpill spill) {
+    auto launch = [&](auto kernel, auto) {
+        hipLaunchKernelGGL(kernel, grid, dim3(TQ_BLOCK), 0, stream, dev, io, n_ptr, n_direct, head, counters, counter_word, spill);
+    };
+    const bool found = any ? (count ? with_trace_kernel<R, true, true, Io>(kind, launch) : with_trace_kernel<R, true, false, Io>(kind, launch))
+                           : (count ? with_trace_kernel<R, false, true, Io>(kind, launch) : with_trace_kernel<R, false, false, Io>(kind, launch));
+    return found ? hipSuccess : hipErrorInvalidDeviceFunction;
+}
+
+template <class R> struct ShadeArgs {
+    DeviceScene<R> dev;
+    RenderParams<R> rp;
+    PathState<R> st;
+    const int32_t *queue;
+    const int32_t *n_cur;
+    const int32_t *tag_count;
+    int32_t *next_queue, *n_next, *shadow_queue, *n_shadow;
+    int k;
+    unsigned long long *counters;
+    int grid;
+    hipStream_t stream;
+    float *to_f32;  // mixed precision, last exact round: the f32 records the continuing paths are converted into (else null)
+};
+template <class R, int TAG> void launch_shade_tag(const ShadeArgs<R> &a) {
+    if (a.rp.integrator != 0)
+        hipLaunchKernelGGL((k_shade<R, TAG, true>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
+                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
+    else
+        hipLaunchKernelGGL((k_shade<R, TAG, false>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
+                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
+}
+template <class R> void launch_shade(int tag, const ShadeArgs<R> &a) {
+    switch (tag) {
+        case 0: launch_shade_tag<R, 0>(a); break;
+        case 1: launch_shade_tag<R, 1>(a); break;
+        case 2: launch_shade_tag<R, 2>(a); break;
+        case 3: launch_shade_tag<R, 3>(a); break;
+        case 4: launch_shade_tag<R, 4>(a); break;
+        case 5: launch_shade_tag<R, 5>(a); break;
+        case 6: launch_shade_tag<R, 6>(a); break;
+        case 7: launch_shade_tag<R, 7>(a); break;
+        case 8: launch_shade_tag<R, 8>(a); break;
+        case 9: launch_shade_tag<R, 9>(a); break;
+        case 10: launch_shade_tag<R, 10>(a); break;
+        case 11: launch_shade_tag<R, 11>(a); break;
+        case 12: launch_shade_tag<R, 12>(a); break;
+        case 13: launch_shade_tag<R, 13>(a); break;
+        case 14: launch_shade_tag<R, 14>(a); break;
+        case 15: launch_shade_tag<R, 15>(a); break;
+        case 16: launch_shade_tag<R, 16>(a); break;
+        default: launch_shade_tag<R, TAG_MISS>(a); break;
+    }
+}
+
+// Debug aid (TAKE_HIP_DUMP_SLOT=<slot>): print one path's state after every kernel of a round.
+template <class R> void dump_slot(const PathState<R> &st, int64_t slot, const char *tag, int k, hipStream_t stream) {
+    (void)hipStreamSynchronize(stream);
+    std::fprintf(stderr, "[slot %lld] k=%d %s R:", (long long)slot, k, tag);
+    R rec[PATH_REC];
+    (void)hipMemcpy(rec, st.r + slot * PATH_REC, sizeof rec, hipMemcpyDeviceToHost);
+    for (int c = 0; c < PATH_REC; c++)
+        if (c != S_HIT && c != S_CTR && c != S_FLAGS) std::fprintf(stderr, " %.17g", (double)rec[c]);
+    std::fprintf(stderr, " I:");
+    for (int c : {(int)S_HIT, (int)S_CTR, (int)S_FLAGS}) std::fprintf(stderr, " %d", *reinterpret_cast<int32_t *>(&rec[c]));
+    std::fprintf(stderr, "\n");
+}
+
+// What the rounds of one render share: the queues, queue words, sort scratch and counters — they belong to the scene
+// whose precision owns the workspace (mixed-precision renders: the f64 scene's; the f32 rounds use them too — slot
+// numbers and queue words do not depend on the precision of the records they point to) — and the render's options.
+struct RoundCtx {
+    int32_t *q;  // queue words + tag counts
+    int32_t *queue[2], *shadow_queue, *sorted_queue;
+    uint8_t *sort_keys;
+    int32_t *sort_hist, *sort_base;
+    unsigned long long *counters;
+    int wide_grid;
+    Timer *tm;
+    bool counting, sort_materials;
+    hipStream_t stream;
+    int64_t dump;  // TAKE_HIP_DUMP_SLOT (or -1)
+    int64_t slots;
+};
+// Round 0 of the default integrator on the default node format: no generate pass (CameraIo).  The counting instances,
+// the other integrators (their shade rounds read the initial flag word) and the other node formats keep k_generate.
+// TAKE_HIP_CAMERA_FUSED=0 turns it off (A/B runs).
+bool camera_fused(TraceKind kind, int integrator, bool counting) {
+    static const bool enabled = !(std::getenv("TAKE_HIP_CAMERA_FUSED") && std::atoi(std::getenv("TAKE_HIP_CAMERA_FUSED")) == 0);
+    return enabled && TQ_GROUP == 1 && !counting && integrator == 0 && kind.nodes == NodeFormat::Q4;
+}
+
+// One round k of a batch on the records of precision RR: closest hits of the extend queue, material sort, shade,
+// shadow rays.  (Everything is enqueued; nothing waits.)  tail: an f32 round of a mixed-precision render; to_f32: see
+// ShadeArgs.  (Long because it is the round, kernel by kernel in stream order.)
+template <class RR>
+hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound,
+                        bool tail, float *to_f32) {
+    Timer &tm = *c.tm;
+    int32_t *q = c.q;
+    int32_t *tag_count = q + Q_NUM_WORDS;
+    const int cur = k & 1, next = cur ^ 1;
+    int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0), *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
+    const bool dump = !tail && c.dump >= 0 && c.dump < c.slots;  // (the slot's f64 record)
+    StackSpill spill{sc.spill.p, sc.spill_stride};
+    const PathIo<RR> io_ext{sc.dev.prims, st, c.queue[cur], rp.ray_eps}, io_shadow{sc.dev.prims, st, c.shadow_queue, rp.ray_eps};
+    // persistent trace grid, cut down when the queue (bounded by n_bound) cannot fill it: one block per 128 rays
+    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));
+    hipError_t e;
+    hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
+    tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
+    if (k == 0 && camera_fused(sc.trace, rp.integrator, c.counting)) {
+        // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
+        CameraIo<RR> io_cam;
+        static_cast<PathIo<RR> &>(io_cam) = io_ext;
+        io_cam.cam = sc.dev.cam, io_cam.rp = rp;
+        e = launch_trace<RR>(sc.trace, false, false, tgrid, c.stream, sc.dev, io_cam, n_cur, 0, q + Q_HEAD_CLOSEST, c.counters, (int)C_RAYS_CLOSEST, spill);
+    } else {
+        e = launch_trace<RR>(sc.trace, false, c.counting, tgrid, c.stream, sc.dev, io_ext, n_cur, 0, q + Q_HEAD_CLOSEST, c.counters,
+                             tail ? (int)C_RAYS_CLOSEST_TAIL : (int)C_RAYS_CLOSEST, spill);
+    }
+    if (e != hipSuccess) return e;
+    tm.end();
+    if (dump) dump_slot(st, c.dump, "after trace_closest", k, c.stream);
+    const int32_t *shade_in = c.queue[cur];
+    if (c.sort_materials) {
+        tm.begin(TK_OTHER);
+        // every wave of the sort gets >= 512 entries of the (bounded) queue: the one-block scan walks
+        // 13 x waves counters, which must not dominate small rounds (it was 40 % of a 256x256 render)
+        const int sort_grid = (int)std::max<int64_t>(1, std::min<int64_t>(c.wide_grid, (n_bound + 2047) / 2048));
+        hipLaunchKernelGGL((k_sort_count<RR>), dim3(sort_grid), dim3(BLOCK), 0, c.stream, sc.dev.prims, sc.dev.inst_shade, st,
+                           c.queue[cur], n_cur, c.sort_keys, c.sort_hist);
+        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_SCAN_THREADS), 0, c.stream, c.sort_hist, c.sort_base, tag_count,
+                           sort_grid * (BLOCK / WAVE));
+        hipLaunchKernelGGL(k_sort_scatter, dim3(sort_grid), dim3(BLOCK), 0, c.stream, c.queue[cur], n_cur, c.sort_keys, c.sort_base,
+                           c.sorted_queue);
+        tm.end();
+        shade_in = c.sorted_queue;
+    }
+    tm.begin(TK_SHADE);
+    {
+        const int shade_grid = (int)((n_bound + BLOCK - 1) / BLOCK);
+        ShadeArgs<RR> sa{sc.dev, rp, st, shade_in, n_cur, c.sort_materials ? tag_count : nullptr, c.queue[next],
+                         n_next, c.shadow_queue, q + Q_N_SHADOW, k, c.counters, shade_grid, c.stream, to_f32};
+        if (c.sort_materials) {
+            // one specialised launch per material tag present in the scene + the miss segment
+            for (int t = 0; t < TAKE_MAT_COUNT; t++)
+                if (sc.host.tag_mask & (1u << t)) launch_shade<RR>(t, sa);
+            launch_shade<RR>(TAG_MISS, sa);
+        } else {
+            launch_shade<RR>(sc.host.single_tag, sa);
+        }
+    }
+    tm.end();
+    if constexpr (sizeof(RR) == 8) {
+        if (!TK_SHADE_RECORD && to_f32 != nullptr) {
+            // mixed precision, last exact round, builds without the register copy of the record: the paths that go on
+            // continue on f32 records from here — converted before this round's shadow rays, as k_shade does it
+            tm.begin(TK_OTHER);
+            hipLaunchKernelGGL(k_convert_state, dim3(c.wide_grid), dim3(BLOCK), 0, c.stream, st, PathState<float>{to_f32, c.slots},
+                               c.queue[next], n_next);
+            tm.end();
+        }
+    }
+    if (dump) dump_slot(st, c.dump, "after shade", k, c.stream);
+    if (k <= rp.max_depth && rp.integrator == 0) {  // integrators 1..3 trace no shadow rays
+        tm.begin(TK_SHADOW);
+        e = launch_trace<RR>(sc.trace, true, c.counting, tgrid, c.stream, sc.dev, io_shadow, q + Q_N_SHADOW, 0, q + Q_HEAD_SHADOW, c.counters,
+                             (int)C_RAYS_SHADOW, spill);
+        if (e != hipSuccess) return e;
+        tm.end();
+        if (dump) dump_slot(st, c.dump, "after trace_shadow", k, c.stream);
+    }
+    return hipSuccess;
+}
+
+// the counters of a new call: zeros, and the bytes the traversal of `sc` reads per node and per primitive test
+template <class R> TakeCounters fresh_counters(const SceneT<R> &sc) {
+    TakeCounters c{};
+    c.node_bytes = (int)node_bytes<R>(sc.trace.nodes);
+    c.prim_bytes = PRIM_TEST_BYTES * (int)(sizeof(R) / 4);
+    return c;
+}
+// the device counters of the call that has just finished -> tc (and raw, for the caller's own lines)
+template <class R> int read_counters(const SceneT<R> &sc, TakeCounters &tc, unsigned long long (&raw)[C_NUM_WORDS]) {
+    HIP_TRY(hipMemcpy(raw, sc.counters.p, sizeof raw, hipMemcpyDeviceToHost));
+    tc.rays_closest = raw[C_RAYS_CLOSEST] + raw[C_RAYS_CLOSEST_TAIL];
+    tc.rays_closest_f32 = raw[C_RAYS_CLOSEST_TAIL];
+    tc.rays_shadow = raw[C_RAYS_SHADOW];
+    tc.node_visits = raw[C_NODE_VISITS];
+    tc.prim_tests = raw[C_PRIM_TESTS];
+    tc.bounces = raw[C_BOUNCES];
+    tc.leaf_visits = raw[C_LEAF_VISITS];
+    tc.wave_node_steps = raw[C_WAVE_NODE_STEPS];
+    tc.wave_leaf_steps = raw[C_WAVE_LEAF_STEPS];
+    return TAKE_OK;
+}
+
+// Samples per batch of a render of npix pixels (-> spb, slots = spb * npix) with the workspace for them allocated.
+template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, int &spb, int64_t &slots) {
+    // paths in flight per batch: up to 512 Mi (69 GB of f32 path state + 9 GB of queues) — bigger batches keep the
+    // persistent trace grid full for more of each bounce (measured on the 1M-triangle scene, spp per batch 8 / 16 / 32 /
+    // 64 / 128 / 256 = 53.2 / 57.7 / 60.3 / 61.9 | 64.5 / 64.9 / 65.5 Msamples/s), and a 288 GB device has the room;
+    // capped at four fifths of what is free now (round 3: it was half — a mixed-precision render, 418 B per path, then
+    // needed two batches for 256 spp at 1920x1080 and lost ~1 % to the second set of thin late rounds)
+    int64_t target = (int64_t)512 << 20;
+    {
+        size_t free_b = 0, total_b = 0;
+        // (mixed precision: every slot has an f32 record beside its f64 one)
+        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (ts->precision == TAKE_PRECISION_MIXED ? sizeof(float) : 0)) +
+                                 4 * (int64_t)sizeof(int32_t);
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const int64_t have = (int64_t)sc.capacity * per_path;  // already allocated by an earlier render
+            // (shards of a scene group that share a device size their batches concurrently: each takes its share)
+            target = std::min<int64_t>(target, std::max<int64_t>((int64_t)1 << 20, ((int64_t)free_b / std::max(1, ts->mem_share) + have) / 5 * 4 / per_path));
+        }
+    }
+    spb = o.samples_per_batch > 0 ? o.samples_per_batch : (int)std::max<int64_t>(1, target / npix);
+    spb = std::min(spb, o.spp);
+    while ((int64_t)spb * npix >= ((int64_t)1 << 31) - (1 << 26)) spb--;
+    // The free-memory figure above is a snapshot: another process on the device (or another host thread) may take the
+    // memory before the allocation lands.  A batch size the caller did not pin is then halved until it fits — the
+    // image does not depend on it (a sample's random stream is a function of seed, pixel and sample index only).
+    const bool mixed_records = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
+    for (;;) {
+        slots = (int64_t)spb * npix;
+        int rc = ensure_workspace(sc, slots, npix);
+        if (rc == TAKE_OK && mixed_records && (int64_t)ts->f.state_r.n < (int64_t)PATH_REC * slots &&
+            ts->f.state_r.alloc((size_t)PATH_REC * slots) != hipSuccess) {
+            ts->f.state_r.release();
+            release_workspace(sc);
+            rc = fail(TAKE_E_NOMEM, "out of device memory for the f32 path records of a mixed-precision render (" + std::to_string(slots) + " path slots)");
+        }
+        if (rc != TAKE_E_NOMEM || spb == 1 || o.samples_per_batch > 0) return rc;
+        (void)hipGetLastError();
+        spb = (spb + 1) / 2;
+    }
+}
+
+// The kernels' view of a render's options, for records of precision R (a mixed-precision render makes both from here;
+// s0 and spb are the batch's)
+template <class R> RenderParams<R> make_params(const TakeRenderOpts &o, int W, int H, int n_rows, int first, int stride) {
+    const int64_t npix = (int64_t)n_rows * W;
+    RenderParams<R> rp{};
+    rp.width = W, rp.height = H, rp.n_local_rows = n_rows, rp.npix = (int32_t)npix;
+    rp.inv_npix = 1.0 / (double)npix, rp.inv_width = 1.0 / (double)W;
+    rp.strip_first = first, rp.strip_stride = stride;
+    rp.spp = o.spp, rp.max_depth = o.max_depth, rp.seed = o.seed, rp.integrator = o.integrator;
+    rp.ray_eps = o.ray_epsilon > 0 ? R(o.ray_epsilon) : (sizeof(R) == 8 ? R(1e-7) : R(1e-4));
+    return rp;
+}
+
+// Queue lengths read back asynchronously (PollRing: pinned word + event, polled — the launch loop never waits for the
+// GPU): any value that has arrived bounds the grids of all later rounds (queues only shrink), and a zero ends the
+// launching.  (Round 1 blocked on a stream sync every 4 rounds: with the ~370 launches of a small render that was a
+// third of its 12 ms.)
+struct QueuePoll {
+    PollRing &ring;
+    hipStream_t stream;
+    int64_t issued = 0, done = 0;
+    int post(const int32_t *d_length) {  // (skipped while the ring is full)
+        if (issued - done >= PollRing::SIZE) return TAKE_OK;
+        const int slot = issued % PollRing::SIZE;
+        HIP_TRY(hipMemcpyAsync(ring.word + slot, d_length, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(ring.ev[slot], stream));
+        issued++;
+        return TAKE_OK;
+    }
+    // the lengths that have arrived: n_bound lowered to them, finished once one was zero
+    int drain(int64_t &n_bound, bool &finished) {
+        while (done < issued) {
+            const int slot = done % PollRing::SIZE;
+            hipError_t q = hipEventQuery(ring.ev[slot]);
+            if (q == hipErrorNotReady) {
+                (void)hipGetLastError();  // "not ready" is an answer, not an error: keep it out of the sticky state
+                // stay at most 8 rounds ahead of the GPU: enough queued work that it never idles, close enough
+                // that a batch whose paths have all ended stops being launched
+                if (issued - done < 8) break;
+                q = hipEventSynchronize(ring.ev[slot]);
+            }
+            HIP_TRY(q);
+            const int32_t alive = ring.word[slot];
+            done++;
+            n_bound = std::min<int64_t>(n_bound, alive);
+            if (alive == 0) finished = true;
+        }
+        return TAKE_OK;
+    }
+    // (outstanding read-backs of a batch complete with the stream; the ring indices just move on)
+    void end_batch() { done = issued; }
+};
+
+// the event pairs of an instrumented render -> milliseconds and launch counts per kernel class
+void sum_timings(const TakeScene *ts, TakeCounters &tc) {
+    double acc[TK_NUM] = {0, 0, 0, 0, 0};
+    for (auto &t : ts->timed) {
+        float m = 0;
+        if (hipEventElapsedTime(&m, t.second.first, t.second.second) == hipSuccess) acc[t.first] += m;
+        if (t.first == TK_CLOSEST || t.first == TK_CLOSEST_TAIL) tc.launches_trace_closest++;
+        if (t.first == TK_CLOSEST_TAIL) tc.launches_trace_closest_f32++;
+        if (t.first == TK_SHADOW) tc.launches_trace_shadow++;
+    }
+    tc.ms_trace_closest = acc[TK_CLOSEST] + acc[TK_CLOSEST_TAIL];
+    tc.ms_trace_closest_f32 = acc[TK_CLOSEST_TAIL];
+    tc.ms_trace_shadow = acc[TK_SHADOW];
+    tc.ms_shade = acc[TK_SHADE];
+    tc.ms_other = acc[TK_OTHER];
+}
+
+// first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
+// random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
+// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
+// (Long because it is the frame in stream order: checks, set-up, the batch / round loop, resolve, read-back.)
+template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
+                                   int64_t first_sample, bool keep_accum) {
+    if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
+    const int W = sc.host.cam.width, H = sc.host.cam.height;
+    if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
+    if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
+    if (o.integrator != 0 && sc.host.env.light >= 0)
+        return fail(TAKE_E_INVALID, "integrators 1..3 are the reference's own: they do not know the environment-map extension");
+    const int stride = o.strip_stride > 0 ? o.strip_stride : 1;
+    const int first = o.strip_first;
+    if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    const int n_rows = rows_of(H, first, stride, nullptr);
+    const int64_t npix = (int64_t)n_rows * W;
+    ts->counters = fresh_counters(sc);
+    if (ts->precision == TAKE_PRECISION_MIXED) ts->counters.prim_bytes = PRIM_TEST_BYTES;  // (most rounds read the f32 records)
+    if (npix == 0) return TAKE_OK;
+    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
+    int spb = 0;
+    int64_t slots = 0;
+    int rc = size_batches(ts, sc, o, npix, spb, slots);
+    if (rc) return rc;
+
+    PathState<R> st{sc.state_r.p, sc.capacity};
+    RenderParams<R> rp = make_params<R>(o, W, H, n_rows, first, stride);
+    const bool counting = (ts->instrumentation & 2) != 0;
+    const bool sort_materials = sc.host.n_material_tags > 1;
+    const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT");
+    ts->events.reset();
+    ts->timed.clear();
+    Timer tm{ts, stream, (ts->instrumentation & 1) != 0};
+    int32_t *q = sc.qwords.p;
+    const int wide_grid = (int)std::min<int64_t>((slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    const int pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    if (sort_materials) {
+        const size_t need = (size_t)N_SORT_KEYS * wide_grid * (BLOCK / WAVE);
+        if (sc.sort_hist.n != need) {
+            HIP_TRY(sc.sort_hist.alloc(need));
+            HIP_TRY(sc.sort_base.alloc(need));
+        }
+    }
+    const RoundCtx ctx{q, {sc.queue[0].p, sc.queue[1].p}, sc.shadow_queue.p, sc.sorted_queue.p, sc.sort_keys.p, sc.sort_hist.p, sc.sort_base.p,
+                       sc.counters.p, wide_grid, &tm, counting, sort_materials, stream, dump_env ? std::atoll(dump_env) : -1, slots};
+    // mixed precision (TAKE_PRECISION_MIXED): rounds k < exact_rounds on the f64 records and scene, the rest on f32
+    // records of the same slots and the f32 scene
+    const bool mixed = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
+    int exact_rounds = 0;
+    PathState<float> st32{nullptr, 0};
+    RenderParams<float> rp32{};
+    if (mixed) {
+        exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
+        if (o.integrator != 0) return fail(TAKE_E_INVALID, "mixed precision renders the reference's path_tracing (integrator 0) only");
+        st32 = PathState<float>{ts->f.state_r.p, slots};
+        rp32 = make_params<float>(o, W, H, n_rows, first, stride);
+    }
+    if (!keep_accum) HIP_TRY(hipMemsetAsync(sc.accum.p, 0, sizeof(R) * 3 * npix, stream));
+    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
+    hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
+    HIP_TRY(hipEventRecord(ev_begin, stream));
+    HIP_TRY(ts->poll.create());
+    QueuePoll poll{ts->poll, stream};
+
+    for (int s0 = 0; s0 < o.spp; s0 += spb) {
+        const int nb = std::min(spb, o.spp - s0);
+        const int64_t n = (int64_t)nb * npix;
+        rp.s0 = (int32_t)first_sample + s0;
+        rp.spb = nb;
+        rp32.s0 = rp.s0, rp32.spb = nb;
+        tm.begin(TK_OTHER);
+        if (camera_fused(sc.trace, rp.integrator, counting)) hipLaunchKernelGGL(k_iota, dim3(wide_grid), dim3(BLOCK), 0, stream, sc.queue[0].p, n);
+        else hipLaunchKernelGGL((k_generate<R>), dim3(wide_grid), dim3(BLOCK), 0, stream, sc.dev, rp, st, sc.queue[0].p, n);
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, q, (int)Q_N_EXT0, (int32_t)n);
+        tm.end();
+        const int rounds = o.max_depth + 2;
+        int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
+        bool finished = false;
+        for (int k = 0; k < rounds && !finished; k++) {
+            // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
+            // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
+            if (mixed && k >= exact_rounds) HIP_TRY(launch_round<float>(ctx, ts->f, st32, rp32, k, n_bound, true, nullptr));
+            else HIP_TRY(launch_round<R>(ctx, sc, st, rp, k, n_bound, false, (mixed && k == exact_rounds - 1) ? st32.r : nullptr));
+            if (k + 1 < rounds) rc = poll.post(q + (k & 1 ? Q_N_EXT0 : Q_N_EXT1));  // the length of the next round's queue
+            if (!rc) rc = poll.drain(n_bound, finished);
+            if (rc) return rc;
+        }
+        poll.end_batch();
+        tm.begin(TK_OTHER);
+        if constexpr (sizeof(R) == 8)
+            if (mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(pix_grid), dim3(BLOCK), 0, stream, st, st32, sc.accum.p, (int32_t)npix, nb);
+        if (!mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, st, sc.accum.p, (int32_t)npix, nb);
+        tm.end();
+    }
+    tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((k_resolve<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.accum.p, (R *)d_out, W, n_rows,
+                       (int32_t)first_sample + o.spp);
+    tm.end();
+    HIP_TRY(hipEventRecord(ev_end, stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(tm.err));
+
+    unsigned long long c[C_NUM_WORDS];
+    TakeCounters &tc = ts->counters;
+    rc = read_counters(sc, tc, c);
+    if (rc) return rc;
+    tc.samples = (uint64_t)npix * (uint64_t)o.spp;
+    if (std::getenv("TAKE_HIP_VERBOSE"))
+        std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
+                     c[C_WAIT_SLOTS], c[C_IDLE_SLOTS], c[C_NODE_VISITS], c[C_OCC_CACHE_HITS], c[C_RAYS_SHADOW]);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    tc.ms_total = ms;
+    sum_timings(ts, tc);
+    return TAKE_OK;
+}
+
+template <class R>
+int trace_impl(TakeScene *ts, SceneT<R> &sc, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any, bool count,
+               hipStream_t stream) {
+    if (n < 0 || n >= ((int64_t)1 << 31) - (1 << 26)) return fail(TAKE_E_INVALID, "ray count out of range");
+    StackSpill spill{sc.spill.p, sc.spill_stride};
+    int32_t *q = sc.qwords.p;
+    HIP_TRY(hipMemsetAsync(q + Q_HEAD_CLOSEST, 0, sizeof(int32_t), stream));
+    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
+    ts->events.reset();
+    hipEvent_t a = ts->events.get(), b = ts->events.get();
+    HIP_TRY(hipEventRecord(a, stream));
+    const HookIo<R> io{sc.dev.prims, (const RayAoS<R> *)d_rays, (HitAoS<R> *)d_hits, d_occ, sc.dev.inst_shade};
+    HIP_TRY(launch_trace<R>(sc.trace, any, count, dim3(sc.trace_grid), stream, sc.dev, io, nullptr, (int32_t)n, q + Q_HEAD_CLOSEST,
+                            sc.counters.p, -1, spill));
+    HIP_TRY(hipEventRecord(b, stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned long long c[C_NUM_WORDS];
+    ts->counters = fresh_counters(sc);
+    const int rc = read_counters(sc, ts->counters, c);  // (the hooks count no rays on the device: n of the one kind)
+    if (rc) return rc;
+    (any ? ts->counters.rays_shadow : ts->counters.rays_closest) = (uint64_t)n;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, a, b));
+    (any ? ts->counters.ms_trace_shadow : ts->counters.ms_trace_closest) = ms;
+    (any ? ts->counters.launches_trace_shadow : ts->counters.launches_trace_closest) = 1;
+    ts->counters.ms_total = ms;
+    return TAKE_OK;
+}
+
+template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
+    if (n == 0) return TAKE_OK;
+    // entry distances are ordered through their bit patterns (non-negative floats): a ray must start at tmin >= 0
+    for (int64_t i = 0; i < n; i++) {
+        const RayAoS<R> &q = ((const RayAoS<R> *)rays)[i];
+        if (!(q.tmin >= R(0))) return fail(TAKE_E_INVALID, "ray " + std::to_string(i) + ": tmin must be >= 0");
+    }
+    DevBuf<RayAoS<R>> d_rays;
+    DevBuf<HitAoS<R>> d_hits;
+    DevBuf<int32_t> d_occ;
+    HIP_TRY(d_rays.alloc(n));
+    if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "ray upload failed");
+    if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) return fail(TAKE_E_NOMEM, "hit buffer allocation failed");
+    const int rc = trace_impl(ts, sc, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
+    if (rc) return rc;
+    hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
+                       : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(TAKE_E_DEVICE, "hit download failed");
+    return TAKE_OK;
+}
+
+}  // namespace
+
+namespace tk_host {
+
+bool compressed_nodes_supported() { return TQ_GROUP <= 2; }
+
+// The grid is resident blocks of the instance the render's closest-hit rounds run x CUs.  Blocks per CU: the
+// occupancy of that instance, asked once per scene — a replica arrives with its source's figure.
+template <class R> hipError_t alloc_trace_state(SceneT<R> &sc, int num_cus) {
+    hipError_t e = sc.qwords.alloc(Q_NUM_WORDS + 2 * N_SORT_KEYS);
+    if (e == hipSuccess) e = sc.counters.alloc(C_NUM_WORDS);
+    int rays_per_block = 0;
+    const bool found = with_trace_kernel<R, false, false, PathIo<R>>(sc.trace, [&](auto kernel, auto geom) {
+        rays_per_block = geom.GROUPS, sc.spill_levels = geom.SPILL;
+        if (e != hipSuccess || sc.blocks_per_cu > 0) return;
+        int per_cu = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TQ_BLOCK, 0);
+        per_cu = std::max(1, std::min(per_cu, 8));
+        if (const char *env = std::getenv("TAKE_HIP_TRACE_BLOCKS")) per_cu = std::max(1, std::min(per_cu, std::atoi(env)));  // experiment: leave room for a concurrent kernel
+        sc.blocks_per_cu = per_cu;
+    });
+    if (e != hipSuccess) return e;
+    if (!found) return hipErrorInvalidDeviceFunction;
+    sc.trace_grid = num_cus * sc.blocks_per_cu;
+    sc.spill_stride = (int64_t)sc.trace_grid * rays_per_block;
+    if ((e = sc.spill.alloc((size_t)sc.spill_stride * sc.spill_levels)) != hipSuccess) return e;
+    if ((e = hipMemset(sc.qwords.p, 0, sc.qwords.bytes())) != hipSuccess) return e;
+    return hipMemset(sc.counters.p, 0, sc.counters.bytes());
+}
+template hipError_t alloc_trace_state<float>(SceneT<float> &, int);
+template hipError_t alloc_trace_state<double>(SceneT<double> &, int);
+
+int rows_of(int height, int first, int stride, int32_t *rows_out) {
+    const int n_strips = (height + TILE_ROWS - 1) / TILE_ROWS;
+    int n = 0;
+    std::vector<int> ys;
+    for (int s = first; s < n_strips; s += stride)
+        for (int y = s * TILE_ROWS; y < std::min(height, (s + 1) * TILE_ROWS); y++) ys.push_back(y);
+    n = (int)ys.size();
+    if (rows_out)
+        for (int j = 0; j < n; j++) rows_out[j] = height - 1 - ys[n - 1 - j];  // increasing image row
+    return n;
+}
+
+int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample, bool keep_accum) {
+    return on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, o, d_out, stream, first_sample, keep_accum); });
+}
+int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img) {
+    return on_primary(ts, [&](auto &sc) {
+        int rc = ensure_workspace(sc, 0, npix);
+        if (!rc) rc = render_impl(ts, sc, o, sc.out.p, nullptr, 0, false);
+        img = sc.out.p;
+        return rc;
+    });
+}
+int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
+    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, hits, occ, any); });
+}
+int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream) {
+    return on_primary(ts, [&](auto &sc) { return trace_impl(ts, sc, d_rays, n, d_hits, nullptr, false, count, stream); });
+}
+
+}  // namespace tk_host
+
+extern "C" {
+
+int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t width, int32_t height, uint16_t *d_out, void *stream) {
+    if (!d_rgb || !d_out || width <= 0 || height <= 0) return fail(TAKE_E_INVALID, "bad argument");
+    if (precision != TAKE_PRECISION_F32 && precision != TAKE_PRECISION_F64) return fail(TAKE_E_INVALID, "unknown precision");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const int64_t total = (int64_t)width * height * 3;
+    const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 8192));
+    if (precision == TAKE_PRECISION_F64)
+        hipLaunchKernelGGL((k_pack_exr<double>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const double *)d_rgb, width, height, d_out);
+    else
+        hipLaunchKernelGGL((k_pack_exr<float>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const float *)d_rgb, width, height, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return TAKE_OK;
+}
+
+int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int64_t n, int32_t in_cols,
+                         const double *rnd, double *out, int32_t out_cols) {
+    if (!in || !out || !rnd || n < 0) return fail(TAKE_E_INVALID, "null argument");
+    int nd = check_device();
+    if (nd < 0) return nd;
+    if (n == 0) return TAKE_OK;
+    DevBuf<double> d_in, d_rnd, d_out;
+    DevBuf<ImageInfo> d_img;
+    DevBuf<float> d_texf;
+    DevBuf<double> d_texd;
+    // the fixed 5x4 image the reference harness used for the material / texture tables (oracle/ref_harness.cpp)
+    std::vector<float> tf(60);
+    std::vector<double> td(60);
+    for (int y = 0; y < 4; y++)
+        for (int x = 0; x < 5; x++) {
+            const double c[3] = {0.1 + 0.15 * x + 0.01 * y, 0.9 - 0.2 * y + 0.02 * x, 0.3 + 0.05 * ((x * 3 + y * 7) % 5)};
+            for (int a = 0; a < 3; a++) td[3 * (y * 5 + x) + a] = c[a], tf[3 * (y * 5 + x) + a] = (float)c[a];
+        }
+    std::vector<ImageInfo> img{ImageInfo{5, 4, 0}};
+    if (d_in.alloc((size_t)n * in_cols) != hipSuccess || d_rnd.alloc((size_t)n * TAB_RND) != hipSuccess ||
+        d_out.alloc((size_t)n * out_cols) != hipSuccess || d_img.upload(img) != hipSuccess ||
+        d_texf.upload(tf) != hipSuccess || d_texd.upload(td) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "debug table allocation failed");
+    if (hipMemcpy(d_in.p, in, d_in.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_rnd.p, rnd, d_rnd.bytes(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_out.p, 0, d_out.bytes()) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "debug table upload failed");
+    const dim3 g((unsigned)((n + BLOCK - 1) / BLOCK)), b(BLOCK);
+    if (precision == TAKE_PRECISION_F64) {
+        DeviceScene<double> sc{};
+        sc.images = d_img.p, sc.texels = d_texd.p;
+        hipLaunchKernelGGL((k_debug_table<double>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
+    } else {
+        DeviceScene<float> sc{};
+        sc.images = d_img.p, sc.texels = d_texf.p;
+        hipLaunchKernelGGL((k_debug_table<float>), g, b, 0, nullptr, sc, kind, d_in.p, d_rnd.p, n, d_out.p);
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(TAKE_E_DEVICE, "debug table kernel failed");
+    if (hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TAKE_E_DEVICE, "debug table download failed");
+    return TAKE_OK;
+}
+
+}  // extern "C"

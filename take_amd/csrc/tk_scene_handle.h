@@ -1,0 +1,190 @@
+// tk_scene_handle.h — the scene handle (TakeScene: one SceneT per precision side) and the few functions that
+// tk_api.hip (scene creation, device build, groups, the C entry points) and tk_render.hip (tracing and rendering: the
+// only unit that compiles the kernels of tk_kernels.h) call across.  Includes no kernel source.
+#pragma once
+#include <vector>
+
+#include "tk_host.h"
+#include "tk_host_scene.h"
+
+namespace tk_host {
+using namespace tk;
+
+struct EventPool {
+    std::vector<hipEvent_t> ev;
+    size_t used = 0;
+    EventPool() = default;
+    EventPool(const EventPool &) = delete;
+    EventPool &operator=(const EventPool &) = delete;
+    ~EventPool() {
+        for (auto e : ev) (void)hipEventDestroy(e);
+    }
+    hipEvent_t get() {
+        if (used == ev.size()) {
+            hipEvent_t e = nullptr;
+            if (hipEventCreate(&e) != hipSuccess) return nullptr;  // callers treat a null event as a failed timing call
+            ev.push_back(e);
+        }
+        return ev[used++];
+    }
+    void reset() { used = 0; }
+};
+
+// Queue lengths read back WITHOUT stalling the launch loop (render_impl): a ring of pinned words + events, made by the
+// first render.
+struct PollRing {
+    static constexpr int SIZE = 64;
+    int32_t *word = nullptr;  // SIZE pinned words
+    hipEvent_t ev[SIZE] = {};
+    PollRing() = default;
+    PollRing(const PollRing &) = delete;
+    PollRing &operator=(const PollRing &) = delete;
+    ~PollRing() {
+        if (word) (void)hipHostFree(word);
+        for (auto e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {  // (a no-op once it has succeeded; after a failure the next call makes what is missing)
+        hipError_t r = word ? hipSuccess : hipHostMalloc((void **)&word, sizeof(int32_t) * SIZE, hipHostMallocDefault);
+        for (int i = 0; i < SIZE && r == hipSuccess; i++)
+            if (!ev[i]) r = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        return r;
+    }
+};
+
+// What the traversal of a scene is: set once from what upload_scene uploaded, copied by replicas.  The trace kernel
+// instance, its node size and its block geometry all follow from it (tk_render.hip: with_trace_kernel).
+enum class NodeFormat { WIDE /* Node4<R> */, Q4 /* QNode4, compressed */, Q8 /* QNode8, compressed 8-wide */ };
+struct TraceKind {
+    NodeFormat nodes = NodeFormat::WIDE;
+    bool two_level = false;  // instances (InstTrace): the INST kernels
+};
+template <class R> constexpr size_t node_bytes(NodeFormat f) {
+    return f == NodeFormat::Q8 ? sizeof(QNode8) : (f == NodeFormat::Q4 ? sizeof(QNode4) : sizeof(Node4<R>));
+}
+
+template <class R> struct SceneT {
+    HostScene<R> host;  // kept: cheap relative to HBM copies, used for stats
+    DevBuf<Node4<R>> nodes;
+    DevBuf<QNode4> qnodes;
+    DevBuf<QNode8> qnodes8;
+    DevBuf<PrimRec<R>> prims;
+    DevBuf<MeshInfo> meshes;
+    DevBuf<int32_t> face_idx;
+    DevBuf<R> normals, uvs, texels;
+    DevBuf<MaterialRec<R>> materials;
+    DevBuf<ImageInfo> images;
+    DevBuf<LightRec<R>> lights;
+    DevBuf<R> light_pmf, light_cdf;
+    DevBuf<InstTrace<R>> inst_trace;
+    DevBuf<InstShade<R>> inst_shade;
+    DevBuf<R> env_marginal, env_conditional;
+    DevBuf<int32_t> env_guide_m, env_guide_c;
+    DeviceScene<R> dev{};
+    // render workspace (grown on demand)
+    DevBuf<R> state_r;
+    DevBuf<int32_t> queue[2], shadow_queue, sorted_queue;
+    DevBuf<uint8_t> sort_keys;            // one key byte per queue entry (material sort)
+    DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
+    DevBuf<R> accum, out;
+    DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
+    DevBuf<unsigned long long> counters;
+    DevBuf<unsigned long long> spill;
+    int64_t capacity = 0;  // path slots allocated
+    bool built_on_device = false;
+    TraceKind trace;           // which trace kernel instance traverses this scene
+    // the persistent trace grid (alloc_trace_state): blocks per CU and spill levels are properties of the instance
+    // (a replica takes them from its source), the grid is that times the CUs of the scene's own device
+    int blocks_per_cu = 0, spill_levels = 0;
+    int trace_grid = 0;
+    int64_t spill_stride = 0;  // ray groups in the persistent trace grid
+
+    // The scene arrays: f(x.nodes...), f(x.qnodes...), ... for the scenes x, in the order replicate_t allocates them.
+    template <class F, class... S> static void for_each_array(F &&f, S &...x) {
+        f(x.nodes...), f(x.qnodes...), f(x.qnodes8...), f(x.prims...), f(x.meshes...), f(x.face_idx...), f(x.normals...);
+        f(x.uvs...), f(x.texels...), f(x.materials...), f(x.images...), f(x.lights...), f(x.light_pmf...), f(x.light_cdf...);
+        f(x.inst_trace...), f(x.inst_shade...), f(x.env_marginal...), f(x.env_conditional...), f(x.env_guide_m...), f(x.env_guide_c...);
+    }
+    // dev's pointers into this scene's arrays: null where an array is empty, and for the node formats not in use (only
+    // the format the kernels traverse is allocated)
+    void bind() {
+        dev.nodes = nodes.p, dev.qnodes = qnodes.p, dev.qnodes8 = qnodes8.p, dev.prims = prims.p;
+        dev.shapes = nullptr;  // (ShapeInfo stays on the host: every kernel reads the shading side of a primitive from its own record)
+        dev.meshes = meshes.p, dev.face_idx = face_idx.p, dev.normals = normals.p, dev.uvs = uvs.p, dev.texels = texels.p;
+        dev.materials = materials.p, dev.images = images.p, dev.lights = lights.p, dev.light_pmf = light_pmf.p, dev.light_cdf = light_cdf.p;
+        dev.inst_trace = inst_trace.p, dev.inst_shade = inst_shade.p;
+        dev.env.marginal = env_marginal.p, dev.env.conditional = env_conditional.p, dev.env.guide_m = env_guide_m.p, dev.env.guide_c = env_guide_c.p;
+    }
+    // device bytes of the scene (take_hip_scene_stats): the light-picking and environment-map tables have never been
+    // counted in this figure
+    size_t scene_bytes() const {
+        size_t n = 0;
+        for_each_array([&n](const auto &b) { n += b.bytes(); }, *this);
+        return n - light_pmf.bytes() - light_cdf.bytes() - env_marginal.bytes() - env_conditional.bytes() - env_guide_m.bytes() - env_guide_c.bytes();
+    }
+};
+
+}  // namespace tk_host
+
+struct TakeScene {
+    int precision = TAKE_PRECISION_F32;
+    int device = 0;
+    int num_cus = 256;
+    // progressive rendering (take_hip_render_accumulate): samples per pixel summed in `accum` so far, under which options
+    int64_t acc_samples = 0;
+    TakeRenderOpts acc_opts{};
+    int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
+    int instrumentation = 0;
+    tk_host::SceneT<float> f;
+    tk_host::SceneT<double> d;
+    TakeCounters counters{};
+    tk_host::EventPool events;
+    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> timed;
+    tk_host::PollRing poll;
+    // records, images and trace hooks of a mixed-precision scene are the f64 ones (its f32 side finishes the paths)
+    bool f64() const { return precision != TAKE_PRECISION_F32; }
+    int width() const { return f64() ? d.host.cam.width : f.host.cam.width; }
+    int height() const { return f64() ? d.host.cam.height : f.host.cam.height; }
+};
+
+namespace tk_host {
+
+// f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
+template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
+
+// A scene lives on the device that was current when it was created; every entry point that touches it makes that
+// device current for the duration of the call and restores the caller's afterwards.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+#define TAKE_ON_DEVICE(ts)                                                                            \
+    DeviceGuard guard_((ts)->device);                                                                 \
+    if (!guard_.ok) return fail(TAKE_E_DEVICE, "cannot make the scene's device current")
+
+// ---- defined in tk_render.hip
+// Lanes per ray of the trace kernels: one (TQ_GROUP).  Round 1 measured quad 143.6 / pair 121.5 / one ray per lane
+// 128.8 ms of closest-hit time per 8.3 M samples on full-width nodes; on the 64-byte nodes one ray per lane is 9 %
+// (f32) and 22 % (f64) ahead of the pair kernel.  The other group sizes stay behind -DTQ_GROUP for
+// comparison builds; the quad kernel does not traverse compressed nodes.
+bool compressed_nodes_supported();
+// Zeroed queue words and counters of a scene side, its persistent trace grid on a device of num_cus CUs, the spill.
+template <class R> hipError_t alloc_trace_state(SceneT<R> &sc, int num_cus);
+// image rows of the strips first, first + stride, ... (increasing; rows_out may be null) -> their number
+int rows_of(int height, int first, int stride, int32_t *rows_out);
+// first_sample / keep_accum: progressive rendering (render_impl)
+int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample = 0, bool keep_accum = false);
+// a render of npix pixels into the scene's own output buffer (-> img)
+int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img);
+int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
+int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
+
+}  // namespace tk_host
