@@ -200,13 +200,16 @@ typedef struct TakeBuildOpts {
     int32_t precision;     /* TAKE_PRECISION_F32 (production) or _F64 (parity mode) */
     int32_t bvh_threads;   /* host threads for the BVH build; <=0: hardware_concurrency */
     int32_t max_leaf_size; /* primitives per leaf, 1..4; <=0: default (1) */
-    int32_t builder;       /* TAKE_BUILDER_AUTO (0): host SAH below TAKE_AUTO_DEVICE_BUILD_SHAPES shapes, device
-                              LBVH from there on (scenes without instances; the threshold is the same for every
-                              precision, and every side of a scene — both trees of a mixed one — gets that builder);
+    int32_t builder;       /* TAKE_BUILDER_AUTO (0): host SAH below TAKE_AUTO_DEVICE_BUILD_SHAPES primitives, device
+                              LBVH from there on (the threshold is the same for every precision, and every side of a
+                              scene — both trees of a mixed one — gets that builder; a two-level scene counts its
+                              shapes + the faces of its distinct prototypes + its placements);
                               TAKE_BUILDER_DEVICE_LBVH: primitive records, Morton-order tree and its compression are
                               made on the GPU straight from the caller's mesh arrays (10M triangles: 0.2 s);
                               TAKE_BUILDER_HOST_SAH: binned SAH on the host (10M triangles: 6 s; traversal 2-6 %
-                              faster).  Results do not depend on the builder (conservative box tests).          */
+                              faster).  Results do not depend on the builder (conservative box tests).  Two-level
+                              scenes (TakeInstance) are built by either: the device makes every prototype's tree,
+                              the placements' boxes and the top-level tree.                     */
     int32_t burley_lobes;  /* 0: materials as given (tags 7..11 behave as the reference's stubs do);
                               1: tags 7..11 are taken as 12..16 — the scene's Disney materials get real lobes */
     int32_t instances;     /* what scene_create does with TakeSceneDesc.instances:
@@ -467,8 +470,9 @@ int take_hip_mesh_release(TakeMesh *mesh);
 int take_hip_scene_stats(const TakeScene *scene, int64_t *n_nodes, int64_t *n_prims,
                          int32_t *depth, int64_t *device_bytes);
 /* Who built the scene's trees, per side: TAKE_BUILDER_DEVICE_LBVH, TAKE_BUILDER_HOST_SAH (asked for, chosen by AUTO,
- * or the fall-back of a device build: fewer than 8 shapes, instances, a Morton-order tree deeper than the traversal
- * stack), or -1 for a side the scene does not have (f32_builder of an F64 scene, f64_builder of an F32 one; a MIXED
+ * or the fall-back of a device build: fewer than 8 primitives, a Morton-order tree deeper than the traversal stack —
+ * both levels of a two-level scene counted —, a prototype of a single leaf, or a two-level scene under TAKE_HIP_BRAID > 1
+ * or TAKE_HIP_NODES=q8), or -1 for a side the scene does not have (f32_builder of an F64 scene, f64_builder of an F32 one; a MIXED
  * scene has both).  Either pointer may be NULL. */
 int take_hip_scene_build_info(const TakeScene *scene, int32_t *f32_builder, int32_t *f64_builder);
 

@@ -2,6 +2,7 @@
 // `construct_bvh` (src/bvh.cpp:8-45) for scenes where the host SAH build is the wait (10M triangles: ~6 s on 16 cores).
 //
 //   k_make_prims     primitive records, float or double, from the caller's mesh arrays
+//   k_make_proto_prims  the same for a prototype mesh of a two-level scene: object space, shape_id = face
 //   k_prim_boxes     primitive AABBs (of the geometry the intersection tests see: v0, v0+e1, v0+e2 — one ulp wider;
 //                    double records: rounded outwards to float first) + scene bounds (wave reduce, ordered-int atomics)
 //   k_morton         63-bit Morton code of the box centre (21 bits per axis: 30 bits leave whole clusters of a 10M-
@@ -14,6 +15,12 @@
 //   k_quantise       64-byte compressed nodes on the 15-bit scene grid (same rounding rules as quantise_nodes)
 //   k_widen_nodes    double scenes without compression: the float nodes as Node4<double>
 //   k_permute        primitive and shading records into leaf order
+// Two-level scenes (TakeInstance) add
+//   k_placement_boxes   tight world box of every placement: its prototype's vertices under the transform, in double
+//   k_placement_pad     the padded float box of a placement, behind the shapes' boxes of the top-level build
+//   k_flag_shapes / k_top_leaves / k_permute_top   the top-level tree's leaves: a placement becomes an instance word,
+//                    the shapes' records are compacted into leaf order
+//   k_rebase         a prototype tree's child words (local node indices, local leaf ranges) -> the scene's arrays
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
@@ -83,6 +90,20 @@ struct SphereSrc {
     double c[3], r;
     int32_t material, tag;
 };
+// triangle `face` of mesh `mesh_id` (m) into p: geometry, the mesh's material, its attribute index
+template <class R>
+__device__ __forceinline__ void triangle_into(PrimRec<R> &p, const MeshSrc &m, int32_t mesh_id, int32_t face, const double *__restrict__ positions,
+                                              const int32_t *__restrict__ face_idx) {
+    const int32_t *idx = face_idx + 3 * ((int64_t)m.fbase + face);
+    R v[3][3];
+    for (int k = 0; k < 3; k++)
+        for (int a = 0; a < 3; a++) v[k][a] = (R)positions[3 * (m.pos_off + idx[k]) + a];
+    for (int a = 0; a < 3; a++) p.a[a] = v[0][a], p.a[3 + a] = v[1][a] - v[0][a], p.a[6 + a] = v[2][a] - v[0][a];
+    p.meta = PRIM_TRIANGLE | (m.tag << 8);
+    p.material = m.material;
+    p.mesh = mesh_id;
+    if (m.has_attr) p.nidx = m.fbase + face, p.meta |= META_HAS_ATTR;
+}
 template <class R>
 __global__ void __launch_bounds__(BLK)
 k_make_prims(const int32_t *__restrict__ kind, const int32_t *__restrict__ ref, const int32_t *__restrict__ face,
@@ -101,18 +122,24 @@ k_make_prims(const int32_t *__restrict__ kind, const int32_t *__restrict__ ref, 
         p.material = s.material;
         p.mesh = -(1 + ref[i]);
     } else {
-        const MeshSrc m = meshes[ref[i]];
-        const int32_t *idx = face_idx + 3 * ((int64_t)m.fbase + face[i]);
-        R v[3][3];
-        for (int k = 0; k < 3; k++)
-            for (int a = 0; a < 3; a++) v[k][a] = (R)positions[3 * (m.pos_off + idx[k]) + a];
-        for (int a = 0; a < 3; a++) p.a[a] = v[0][a], p.a[3 + a] = v[1][a] - v[0][a], p.a[6 + a] = v[2][a] - v[0][a];
-        p.meta = PRIM_TRIANGLE | (m.tag << 8);
-        p.material = m.material;
-        p.mesh = ref[i];
-        if (m.has_attr) p.nidx = m.fbase + face[i], p.meta |= META_HAS_ATTR;
+        triangle_into(p, meshes[ref[i]], ref[i], face[i], positions, face_idx);
     }
     out[i] = p;
+}
+// The records of a prototype mesh (two-level scenes), in object space and in face order: what Prototype::build
+// (tk_host_scene.h) makes with triangle_record — the shape id is the face (InstShade::shape_base is added at a hit),
+// no area light.
+template <class R>
+__global__ void __launch_bounds__(BLK)
+k_make_proto_prims(MeshSrc m, int32_t mesh_id, const double *__restrict__ positions, const int32_t *__restrict__ face_idx, int n_faces, PrimRec<R> *out) {
+    const int f = blockIdx.x * BLK + threadIdx.x;
+    if (f >= n_faces) return;
+    PrimRec<R> p{};
+    p.shape_id = f;
+    p.area_light = -1;
+    p.nidx = -1;
+    triangle_into(p, m, mesh_id, f, positions, face_idx);
+    out[f] = p;
 }
 
 // One coordinate interval [lo, hi] of a record's geometry -> a float interval that contains it.
@@ -381,6 +408,131 @@ __global__ void __launch_bounds__(BLK) k_permute(const T *__restrict__ in, const
 __global__ void k_fill_int(int *p, int n, int v) {
     const int i = blockIdx.x * BLK + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+
+// ---- two-level scenes: placement boxes, the top-level tree's leaves, assembly
+// doubles as 64-bit integers with the same order (atomicMin / atomicMax on long long)
+__host__ __device__ __forceinline__ long long d2ord(double d) {
+    long long i;
+    __builtin_memcpy(&i, &d, 8);
+    return i >= 0 ? i : i ^ 0x7fffffffffffffffll;
+}
+__host__ __device__ __forceinline__ double ord2d(long long i) {
+    i = i >= 0 ? i : i ^ 0x7fffffffffffffffll;
+    double d;
+    __builtin_memcpy(&d, &i, 8);
+    return d;
+}
+constexpr int PLACEMENT_CHUNK = 16 * BLK;  // vertices one block of k_placement_boxes transforms
+
+// tight[6 i .. 6 i + 5] = ordered (min x y z, max x y z) of placement i's box, initialised to LLONG_MAX / LLONG_MIN by
+// the caller.  One launch per prototype: block b transforms chunk b % chunks of the prototype's vertices (pos: its
+// first vertex, n_vertices of them) under the transform of placement ids[b / chunks].  The image of a vertex is
+// Affine3::image's expression (tk_host_scene.h), operand order included, and the build does not contract: min and max
+// are exact and commute, so the box is the one placement_box computes on the host, to the sign of a zero.
+__global__ void __launch_bounds__(BLK) k_placement_boxes(const double *__restrict__ pos, int64_t n_vertices, int chunks, const int32_t *__restrict__ ids,
+                                                          const double *__restrict__ xforms, long long *tight) {
+    __shared__ double part[BLK / 64][6];
+    const int32_t pl = ids[blockIdx.x / (unsigned)chunks];
+    const double *M = xforms + 12 * (int64_t)pl;
+    double m[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) m[k] = M[k];
+    double lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) lo[a] = __builtin_huge_val(), hi[a] = -__builtin_huge_val();
+    const int64_t v0 = (int64_t)(blockIdx.x % (unsigned)chunks) * PLACEMENT_CHUNK, v1 = min(n_vertices, v0 + PLACEMENT_CHUNK);
+    for (int64_t v = v0 + threadIdx.x; v < v1; v += BLK) {
+        const double px = pos[3 * v], py = pos[3 * v + 1], pz = pos[3 * v + 2];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const double w = m[4 * a] * px + m[4 * a + 1] * py + m[4 * a + 2] * pz + m[4 * a + 3];
+            lo[a] = fmin(lo[a], w), hi[a] = fmax(hi[a], w);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        for (int off = 32; off > 0; off >>= 1) lo[a] = fmin(lo[a], __shfl_xor(lo[a], off)), hi[a] = fmax(hi[a], __shfl_xor(hi[a], off));
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][a] = lo[a], part[threadIdx.x >> 6][3 + a] = hi[a];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        double l = part[0][a], h = part[0][3 + a];
+        for (int w = 1; w < BLK / 64; w++) l = fmin(l, part[w][a]), h = fmax(h, part[w][3 + a]);
+        if (l <= h) {
+            atomicMin(&tight[6 * (int64_t)pl + a], d2ord(l));
+            atomicMax(&tight[6 * (int64_t)pl + 3 + a], d2ord(h));
+        }
+    }
+}
+
+// The top-level box of placement i from its tight box: padded as make_placement pads (mag * 4e-6 for float scenes,
+// mag * 1e-13 for double ones, in double), then rounded outwards to float; written behind the n_shapes shapes' boxes,
+// and into the scene bounds as k_prim_boxes does.
+template <class R>
+__global__ void __launch_bounds__(BLK) k_placement_pad(const long long *__restrict__ tight, int n_instances, int n_shapes, Box *pb, int *scene_ord) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    Box b;
+#pragma unroll
+    for (int k = 0; k < 3; k++) b.lo[k] = __builtin_huge_valf(), b.hi[k] = -__builtin_huge_valf();
+    if (i < n_instances) {
+        double lo[3], hi[3], mag = 0;
+        for (int a = 0; a < 3; a++) {
+            lo[a] = ord2d(tight[6 * (int64_t)i + a]), hi[a] = ord2d(tight[6 * (int64_t)i + 3 + a]);
+            mag = fmax(mag, fmax(fabs(lo[a]), fabs(hi[a])));
+        }
+        const double pad = mag * (sizeof(R) == 4 ? 4e-6 : 1e-13);
+        for (int a = 0; a < 3; a++) b.lo[a] = d2f_down(lo[a] - pad), b.hi[a] = d2f_up(hi[a] + pad);
+        pb[n_shapes + i] = b;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float lo = b.lo[k], hi = b.hi[k];
+        for (int off = 32; off > 0; off >>= 1) lo = fminf(lo, __shfl_xor(lo, off)), hi = fmaxf(hi, __shfl_xor(hi, off));
+        if ((threadIdx.x & 63) == 0 && lo <= hi) {
+            atomicMin(&scene_ord[k], f2ord(lo));
+            atomicMax(&scene_ord[3 + k], f2ord(hi));
+        }
+    }
+}
+
+// Top-level tree over n_shapes shapes and the placements behind them, one entry per leaf.  order[l] = the entry at
+// position l of the Morton order; is_shape[l] = 1 if it is a shape.  Its exclusive prefix sum `rank` is where the
+// shape's record goes: the records of the top-level tree are its shapes only, in leaf order.
+__global__ void __launch_bounds__(BLK) k_flag_shapes(const uint32_t *__restrict__ order, int n, int n_shapes, int *is_shape) {
+    const int l = blockIdx.x * BLK + threadIdx.x;
+    if (l < n) is_shape[l] = order[l] < (uint32_t)n_shapes;
+}
+// leaf words of the collapse (position l in the Morton order, one entry) -> an instance word for a placement (what
+// collapse_to_wide writes when it is given the build boxes, tk_bvh.h), the compacted record range for a shape
+__global__ void __launch_bounds__(BLK) k_top_leaves(Node4<float> *nodes, int n, const uint32_t *__restrict__ order, const int *__restrict__ rank, int n_shapes) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    for (int c = 0; c < 4; c++) {
+        const int32_t w = nodes[i].c[c].child;
+        if (w >= 0 || w == CHILD_EMPTY) continue;
+        const int l = leaf_first(w);
+        const uint32_t e = order[l];
+        nodes[i].c[c].child = e >= (uint32_t)n_shapes ? make_instance_word((int32_t)(e - (uint32_t)n_shapes)) : make_leaf(rank[l], 1);
+    }
+}
+template <class T>
+__global__ void __launch_bounds__(BLK) k_permute_top(const T *__restrict__ in, const uint32_t *__restrict__ order, const int *__restrict__ rank, int n, int n_shapes, T *out) {
+    const int l = blockIdx.x * BLK + threadIdx.x;
+    if (l < n && order[l] < (uint32_t)n_shapes) out[rank[l]] = in[order[l]];
+}
+// rebase_child (tk_host_scene.h) over the n nodes of a prototype's tree, in the format the scene traverses
+template <class NodeT>
+__global__ void __launch_bounds__(BLK) k_rebase(NodeT *nodes, int n, int32_t node_base, int32_t prim_base) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    for (int c = 0; c < 4; c++) {
+        const int32_t w = nodes[i].c[c].child;
+        if (w == CHILD_EMPTY) continue;
+        nodes[i].c[c].child = w >= 0 ? w + node_base : make_leaf(leaf_first(w) + prim_base, leaf_count(w));
+    }
 }
 
 }  // namespace lbvh

@@ -22,6 +22,12 @@
 
 namespace tk {
 
+// which meshes the device builder makes prototype trees of (plan_placements)
+struct PlacementPlan {
+    std::vector<int32_t> proto_mesh;  // per prototype: its mesh
+    std::vector<int32_t> inst_proto;  // per placement: its prototype
+};
+
 template <class R> struct HostScene {
     std::vector<Node4<R>> nodes;
     std::vector<QNode4> qnodes;  // compressed copy of nodes (empty = not in use)
@@ -43,6 +49,7 @@ template <class R> struct HostScene {
     std::vector<InstTrace<R>> inst_trace;  // two-level scenes (TakeInstance): one record per placement
     std::vector<InstShade<R>> inst_shade;
     int64_t n_blas = 0, blas_nodes = 0, blas_prims = 0;  // stats: prototype trees and their total size
+    PlacementPlan placements;  // PREP_DEVICE_BUILD of a two-level scene: what the device builder is to build
     EnvMap<R> env{-1, 0, 0, 1, 1, 0, 0, {R(0), R(0), R(0)}, nullptr, nullptr, nullptr, nullptr};  // pointers: view() / the uploader
     std::vector<R> env_marginal, env_conditional;
     std::vector<int32_t> env_guide_m, env_guide_c;
@@ -323,24 +330,23 @@ inline Bounds placement_box(const TakeSceneDesc &d, const TakeMesh &m, const Bou
     return w;
 }
 
-// Placement i of a two-level scene, prototype b: one InstTrace / InstShade and one top-level box per ENTRY of the
-// prototype ("virtual instances", placement-major: the tie rule on the instance id keeps ordering placements as the
-// caller numbered them).  shape_next: the first shape id of this placement's faces, advanced.
-template <class R, int W>
-std::string make_placement(const TakeSceneDesc &d, int64_t i, const Prototype<R, W> &b, HostScene<R> &hs, int64_t &shape_next, std::vector<BuildPrim> &bp) {
+// The trace and shade records of placement i: the inverse transform (in double) for the ray, the forward linear part,
+// the resolved material.  shape_next: the first shape id of this placement's faces, advanced.  root_child and the grid
+// are the builder's to fill in.
+template <class R>
+std::string placement_records(const TakeSceneDesc &d, int64_t i, const HostScene<R> &hs, int64_t &shape_next, InstTrace<R> &it, InstShade<R> &is) {
     const TakeInstance &in = d.instances[i];
     const TakeMesh &m = d.meshes[in.mesh_id];
-    // transforms: forward linear part for shading, inverse (in double) for the ray
     const double *M = in.xform;
     const Affine3 x{M};
     double inv[9];
     if (!x.inverse_linear(inv)) return "instance " + std::to_string(i) + ": singular transform";
-    InstTrace<R> it{};
+    it = InstTrace<R>{};
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) it.inv[4 * r + c] = R(inv[3 * r + c]);
         it.inv[4 * r + 3] = R(-(inv[3 * r] * M[3] + inv[3 * r + 1] * M[7] + inv[3 * r + 2] * M[11]));
     }
-    InstShade<R> is{};
+    is = InstShade<R>{};
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) is.fwd[3 * r + c] = R(M[4 * r + c]);
     is.material = in.material_id >= 0 ? in.material_id : m.material_id;
@@ -348,6 +354,29 @@ std::string make_placement(const TakeSceneDesc &d, int64_t i, const Prototype<R,
     is.shape_base = (int32_t)shape_next;
     shape_next += m.n_faces;
     if (shape_next >= (int64_t)1 << 31) return "too many instanced faces for 32-bit shape ids";
+    return "";
+}
+// what is checked about placement i of a description before anything reads it: "" or the error
+inline std::string validate_instance(const TakeSceneDesc &d, int64_t i) {
+    const TakeInstance &in = d.instances[i];
+    if (in.mesh_id < 0 || in.mesh_id >= d.n_meshes) return "instance " + std::to_string(i) + ": bad mesh id";
+    if (in.material_id < -1 || in.material_id >= d.n_materials) return "instance " + std::to_string(i) + ": bad material id";
+    if (d.meshes[in.mesh_id].n_faces <= 0) return "instance " + std::to_string(i) + ": empty prototype mesh";
+    return "";
+}
+
+// Placement i of a two-level scene, prototype b: one InstTrace / InstShade and one top-level box per ENTRY of the
+// prototype ("virtual instances", placement-major: the tie rule on the instance id keeps ordering placements as the
+// caller numbered them).  shape_next: the first shape id of this placement's faces, advanced.
+template <class R, int W>
+std::string make_placement(const TakeSceneDesc &d, int64_t i, const Prototype<R, W> &b, HostScene<R> &hs, int64_t &shape_next, std::vector<BuildPrim> &bp) {
+    const TakeInstance &in = d.instances[i];
+    const TakeMesh &m = d.meshes[in.mesh_id];
+    const Affine3 x{in.xform};
+    InstTrace<R> it;
+    InstShade<R> is;
+    const std::string perr = placement_records(d, i, hs, shape_next, it, is);
+    if (!perr.empty()) return perr;
     // the placement's world box, padded for the rounding of the transformed ray (the specification is the flattened
     // geometry to fp rounding, see take_hip.h)
     const Bounds pb = placement_box(d, m, b.box, x);
@@ -438,6 +467,28 @@ void quantise_trees(const std::vector<NodeW<R, W>> &nodes, size_t top_nodes, con
     if (hs.q_inflation > 1.10 && fmt != "q16") qnodes.clear();
 }
 
+// The host's share of a two-level scene the DEVICE builds (tk_api.hip): the placements validated, their InstTrace /
+// InstShade records (small tables; root_child and grid are filled in after the build), and which meshes are prototypes
+// — each distinct one once, in the order the placements first name them, as build_host_trees numbers them
+// (PlacementPlan, above HostScene).
+template <class R> std::string plan_placements(const TakeSceneDesc &d, HostScene<R> &hs, PlacementPlan &plan) {
+    plan = PlacementPlan{};
+    std::vector<int> proto_of_mesh(d.n_meshes, -1);
+    int64_t shape_next = d.n_shapes;
+    hs.inst_trace.assign((size_t)d.n_instances, InstTrace<R>{}), hs.inst_shade.assign((size_t)d.n_instances, InstShade<R>{});
+    plan.inst_proto.resize((size_t)d.n_instances);
+    for (int64_t i = 0; i < d.n_instances; i++) {
+        std::string err = validate_instance(d, i);
+        if (!err.empty()) return err;
+        const int32_t mesh = d.instances[i].mesh_id;
+        if (proto_of_mesh[mesh] < 0) proto_of_mesh[mesh] = (int)plan.proto_mesh.size(), plan.proto_mesh.push_back(mesh);
+        plan.inst_proto[i] = proto_of_mesh[mesh];
+        if (!(err = placement_records(d, i, hs, shape_next, hs.inst_trace[i], hs.inst_shade[i])).empty()) return err;
+        hs.inst_trace[i].root_child = CHILD_EMPTY;
+    }
+    return "";
+}
+
 struct TreeOpts { int leaf_size, threads; std::string fmt; };  // fmt: TAKE_HIP_NODES
 
 // The host-side trees of a scene, W-wide: the top-level tree over `bp` (the shapes' boxes; one box per placement entry
@@ -456,9 +507,8 @@ std::string build_host_trees(const TakeSceneDesc &d, HostScene<R> &hs, std::vect
     hs.inst_trace.clear(), hs.inst_shade.clear();
     for (int64_t i = 0; i < d.n_instances; i++) {
         const TakeInstance &in = d.instances[i];
-        if (in.mesh_id < 0 || in.mesh_id >= d.n_meshes) return "instance " + std::to_string(i) + ": bad mesh id";
-        if (in.material_id < -1 || in.material_id >= d.n_materials) return "instance " + std::to_string(i) + ": bad material id";
-        if (d.meshes[in.mesh_id].n_faces <= 0) return "instance " + std::to_string(i) + ": empty prototype mesh";
+        const std::string verr = validate_instance(d, i);
+        if (!verr.empty()) return verr;
         if (proto_of_mesh[in.mesh_id] < 0) {
             proto_of_mesh[in.mesh_id] = (int)protos.size();
             protos.emplace_back();
@@ -824,7 +874,6 @@ std::string prepare_scene(const TakeSceneDesc &d, int max_leaf, int threads, Hos
     if (d.n_shapes >= (int64_t)1 << 28) return "too many shapes for the 4-wide leaf encoding (2^28)";
     if (d.n_instances < 0 || (d.n_instances > 0 && !d.instances)) return "instance array missing";
     if (d.n_instances >= (int64_t)1 << 28) return "too many instances";
-    if (d.n_instances > 0 && !host_build) return "instanced scenes are built by the host builder";
     std::string err;
     make_camera<R>(d.camera, hs.cam);
     for (int a = 0; a < 3; a++) hs.background[a] = R(d.background[a]);
@@ -852,7 +901,7 @@ std::string prepare_scene(const TakeSceneDesc &d, int max_leaf, int threads, Hos
 
     if (!host_build) {  // no tree, no records
         hs.nodes.clear(), hs.qnodes.clear(), hs.qnodes8.clear(), hs.nodes8.clear(), hs.prims.clear();
-        hs.inst_trace.clear(), hs.inst_shade.clear();
+        if (!(err = plan_placements(d, hs, hs.placements)).empty()) return err;
         hs.node_width = 4, hs.root_child = CHILD_EMPTY;
         hs.n_blas = hs.blas_nodes = hs.blas_prims = 0;
         hs.stats = WideBvhStats{};
