@@ -1,12 +1,12 @@
-// tk_api.hip — implementation of the C ABI of include/take_hip.h: scene creation (host preparation, upload, the
-// device build), scene groups, and the C entry points.  Tracing and rendering — everything that launches a kernel of
-// tk_kernels.h — is tk_render.hip, reached through the functions of tk_scene_handle.h.  There is no CPU rendering
-// path in this library: without a HIP device every entry point returns TAKE_E_NO_GPU.  The mesh entry points (PLY,
-// serialized, OBJ, compute_normals) are tk_mesh.hip; the plumbing all units share is tk_host.h.
+// tk_api.hip — implementation of the C ABI of include/take_hip.h: scene creation (host preparation, the choice of
+// builder, upload), scene groups, and the C entry points.  Tracing and rendering — everything that launches a kernel of
+// tk_kernels.h — is tk_render.hip; the device LBVH build — every kernel of tk_build_gpu.h — is tk_build.hip; both are
+// reached through the functions of tk_scene_handle.h.  The one kernel launched here is the groups' row scatter.  There
+// is no CPU rendering path in this library: without a HIP device every entry point returns TAKE_E_NO_GPU.  The mesh
+// entry points (PLY, serialized, OBJ, compute_normals) are tk_mesh.hip; the plumbing all units share is tk_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,214 +19,12 @@
 
 #include "take_hip.h"
 #include "tk_scene_handle.h"
-#include "tk_build_gpu.h"
 
 using namespace tk;
 using namespace tk_host;
 
 namespace {
 
-// device memory in use (the whole device's, as hipMemGetInfo sees it), for the TAKE_HIP_VERBOSE lines; 0 if the runtime
-// cannot say
-double device_mb_in_use() {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
-    return (double)(total_b - free_b) / 1e6;
-}
-// The high-water mark of a device build (TAKE_HIP_VERBOSE only): sampled where a phase holds the most — after the last
-// allocation of the sort, the hierarchy, the collapse, the compression and the permute — each phase freeing what the
-// next ones do not read.
-struct BuildMemory {
-    bool on = std::getenv("TAKE_HIP_VERBOSE") != nullptr;
-    const char *side;
-    double peak = 0;
-    const char *peak_at = "";
-    explicit BuildMemory(const char *side_) : side(side_) {}
-    void sample(const char *phase) {
-        if (!on) return;
-        const double mb = device_mb_in_use();
-        std::fprintf(stderr, "[take_hip] scene_create: %s device build, %-12s %8.1f MB of device memory in use\n", side, phase, mb);
-        if (mb > peak) peak = mb, peak_at = phase;
-    }
-    void report() const {
-        if (on) std::fprintf(stderr, "[take_hip] scene_create: %s device build, peak %.1f MB of device memory in use (%s)\n", side, peak, peak_at);
-    }
-};
-
-// One LBVH on the device (tk_build_gpu.h): Morton codes -> rocPRIM sort -> k_leaves -> k_hierarchy -> k_refit ->
-// k_collapse.  The scene's only tree, the top-level tree of a two-level scene, or a prototype's.
-struct DeviceTree {
-    DevBuf<Node4<float>> nodes;  // breadth-first; child words local to the tree: node indices from 0, a leaf = a range of `order`
-    DevBuf<uint32_t> order;      // Morton order -> entry of the span (a stable sort: coincident entries keep their order)
-    int64_t n_nodes = 0;
-    int depth = 0;
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // bounds of the span's boxes: the tree's quantisation grid is laid over them
-};
-const int ORD_INIT[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};  // empty bounds (k_prim_boxes)
-dim3 blocks_for(int64_t items) { return dim3((unsigned)((items + lbvh::BLK - 1) / lbvh::BLK)); }
-
-// In: the n boxes of a span (pb: freed here, once the leaves exist) and their bounds (scene_ord: ordered ints, as
-// k_prim_boxes leaves them).  Out: t.  Returns TAKE_OK, an error, or 1 = "use the host builder": fewer than two leaves,
-// or a tree deeper than the traversal stack allows (long runs of equal Morton codes).
-// The tree is made of float nodes whatever the scene's precision is (tk_build_gpu.h: only records and primitive boxes
-// know it).
-int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n, int leaf_size, BuildMemory &mem, DeviceTree &t) {
-    using namespace lbvh;
-    const int n_leaves = (n + leaf_size - 1) / leaf_size;
-    if (n_leaves < 2) return 1;
-    hipStream_t stream = nullptr;
-    const dim3 blk(BLK);
-    // (a release waits for the kernels launched before it: hipFree synchronises the device)
-    DevBuf<Box> lbox, ibox;
-    DevBuf<uint64_t> keys, keys_s, lkey;
-    DevBuf<uint32_t> vals;
-    DevBuf<int> parent_i, parent_l, flag, frontier[2], lvl;
-    DevBuf<int2> child;
-    DevBuf<char> temp;
-    // Morton codes, sort
-    HIP_TRY(keys.alloc(n));
-    HIP_TRY(vals.alloc(n));
-    HIP_TRY(keys_s.alloc(n));
-    HIP_TRY(t.order.alloc(n));
-    hipLaunchKernelGGL(k_morton, blocks_for(n), blk, 0, stream, pb.p, n, scene_ord.p, keys.p, vals.p);
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys.p, keys_s.p, vals.p, t.order.p, (size_t)n, 0, 63, stream));
-    HIP_TRY(temp.alloc(temp_bytes));
-    mem.sample("sort");
-    HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_bytes, keys.p, keys_s.p, vals.p, t.order.p, (size_t)n, 0, 63, stream));
-    keys.release(), vals.release(), temp.release();
-
-    // leaves, hierarchy, refit
-    HIP_TRY(lbox.alloc(n_leaves));
-    HIP_TRY(lkey.alloc(n_leaves));
-    hipLaunchKernelGGL(k_leaves, blocks_for(n_leaves), blk, 0, stream, pb.p, keys_s.p, t.order.p, n, leaf_size, n_leaves, lbox.p, lkey.p);
-    pb.release(), keys_s.release();
-    HIP_TRY(ibox.alloc(n_leaves));
-    HIP_TRY(child.alloc(n_leaves));
-    HIP_TRY(parent_i.alloc(n_leaves));
-    HIP_TRY(parent_l.alloc(n_leaves));
-    HIP_TRY(flag.alloc(n_leaves));
-    mem.sample("hierarchy");
-    HIP_TRY(hipMemsetAsync(flag.p, 0, flag.bytes(), stream));
-    hipLaunchKernelGGL(k_hierarchy, blocks_for(n_leaves - 1), blk, 0, stream, lkey.p, n_leaves, child.p, parent_i.p, parent_l.p);
-    hipLaunchKernelGGL(k_refit, blocks_for(n_leaves), blk, 0, stream, n_leaves, child.p, parent_i.p, parent_l.p, lbox.p, ibox.p, flag.p);
-    lkey.release(), parent_i.release(), parent_l.release(), flag.release();
-
-    // collapse to 4-wide nodes, breadth-first, one launch per level (at most one node per leaf; the count is known after)
-    HIP_TRY(t.nodes.alloc(n_leaves));
-    HIP_TRY(frontier[0].alloc(n_leaves));
-    HIP_TRY(frontier[1].alloc(n_leaves));
-    HIP_TRY(lvl.alloc(MAX_LEVELS + 2));
-    mem.sample("collapse");
-    HIP_TRY(hipMemsetAsync(lvl.p, 0, lvl.bytes(), stream));
-    hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, lvl.p, 1, 1);           // one node on level 0 ...
-    hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, frontier[0].p, 1, 0);   // ... made from BVH2 node 0
-    const int cgrid = std::max(1, std::min((n_leaves + BLK - 1) / BLK, 2048));
-    for (int level = 0; level < MAX_LEVELS; level++)
-        hipLaunchKernelGGL(k_collapse, dim3(cgrid), blk, 0, stream, level, frontier[level & 1].p, frontier[(level + 1) & 1].p,
-                           lvl.p, child.p, ibox.p, lbox.p, leaf_size, n, t.nodes.p);
-    int lvl_h[MAX_LEVELS + 2];
-    int ord_h[6];
-    HIP_TRY(hipMemcpyAsync(lvl_h, lvl.p, sizeof(lvl_h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(ord_h, scene_ord.p, sizeof(ord_h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (lvl_h[MAX_LEVELS] != 0) return 1;  // deeper than the traversal stack allows
-    t.n_nodes = 0, t.depth = 0;
-    for (int k = 0; k < MAX_LEVELS; k++)
-        if (lvl_h[k] > 0) t.n_nodes += lvl_h[k], t.depth = k + 1;
-    t.nodes.n = (size_t)t.n_nodes;  // the tail of the allocation is unused
-    for (int a = 0; a < 3; a++) t.lo[a] = ord2f(ord_h[a]), t.hi[a] = ord2f(ord_h[3 + a]);
-    return TAKE_OK;
-}
-
-// Compressed nodes of one tree on its own 15-bit grid (g: laid over the tree's bounds), into `out`; -> the mean
-// surface-area inflation of its child boxes (quantise_nodes' figure, tk_bvh.h).  acc: two doubles of scratch.
-int quantise_tree_device(const DeviceTree &t, QNode4 *out, DevBuf<double> &acc, QGrid &g, double &inflation) {
-    using namespace lbvh;
-    g = make_qgrid(t.lo, t.hi);
-    HIP_TRY(hipMemsetAsync(acc.p, 0, acc.bytes(), nullptr));
-    hipLaunchKernelGGL(k_quantise, blocks_for(t.n_nodes), dim3(BLK), 0, nullptr, t.nodes.p, (int)t.n_nodes, g, out, acc.p);
-    double acc_h[2] = {0, 0};
-    HIP_TRY(hipMemcpy(acc_h, acc.p, sizeof(acc_h), hipMemcpyDeviceToHost));
-    inflation = acc_h[1] > 0 ? acc_h[0] / acc_h[1] : 1.0;
-    return TAKE_OK;
-}
-// full-width nodes of one tree into `out`: the float ones as they are, or widened to double (exact: still conservative)
-int wide_nodes_device(const DeviceTree &t, Node4<float> *out) {
-    HIP_TRY(hipMemcpy(out, t.nodes.p, (size_t)t.n_nodes * sizeof(Node4<float>), hipMemcpyDeviceToDevice));
-    return TAKE_OK;
-}
-int wide_nodes_device(const DeviceTree &t, Node4<double> *out) {
-    hipLaunchKernelGGL(lbvh::k_widen_nodes, blocks_for(t.n_nodes), dim3(lbvh::BLK), 0, nullptr, t.nodes.p, (int)t.n_nodes, out);
-    return TAKE_OK;
-}
-// the builder's default: 1 primitive per leaf — two Morton neighbours need not be close, and a leaf box around both costs
-// more primitive tests than the extra node (1M soup, 16 spp: 1 / 2 / 4 per leaf = 55.2 / 38.3 / 30.0 Msamples/s)
-int device_leaf_size(int max_leaf) { return std::max(1, std::min(max_leaf > 0 ? max_leaf : 1, (int)MAX_LEAF)); }
-
-// BVH build on the device of a scene without placements.  In: sc.prims uploaded in SHAPE order.  Out: the records in
-// leaf order, sc.nodes or sc.qnodes, host-side stats and grid.  Returns TAKE_OK, an error, or 1 = "use the host
-// builder" (build_tree_device).  A double scene that is refused compression gets its float nodes widened.
-template <class R> int build_bvh_device(SceneT<R> &sc, int max_leaf, bool compressed_ok, bool compressed_forced) {
-    using namespace lbvh;
-    HostScene<R> &h = sc.host;
-    const int n = (int)sc.prims.n;
-    const int leaf_size = device_leaf_size(max_leaf);
-    if ((n + leaf_size - 1) / leaf_size < 2) return 1;
-    hipStream_t stream = nullptr;
-    const dim3 blk(BLK);
-    BuildMemory mem(sizeof(R) == 4 ? "f32" : "f64");
-    DevBuf<Box> pb;
-    DevBuf<int> scene_ord;
-    DevBuf<double> acc;
-    DeviceTree t;
-    HIP_TRY(pb.alloc(n));
-    HIP_TRY(scene_ord.alloc(6));
-    HIP_TRY(hipMemcpy(scene_ord.p, ORD_INIT, sizeof(ORD_INIT), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_prim_boxes<R>, blocks_for(n), blk, 0, stream, sc.prims.p, n, pb.p, scene_ord.p);
-    const int rt = build_tree_device(pb, scene_ord, n, leaf_size, mem, t);
-    if (rt) return rt;
-    h.stats = WideBvhStats{};
-    h.stats.n_nodes = t.n_nodes, h.stats.n_prims = n, h.stats.depth = t.depth;
-    h.root_child = 0;
-
-    // compressed nodes on the scene grid (same fall-back rule as the host path)
-    h.q_inflation = 1.0;
-    bool use_q = false;
-    if (compressed_ok) {
-        QGrid g;
-        HIP_TRY(sc.qnodes.alloc((size_t)t.n_nodes));
-        HIP_TRY(acc.alloc(2));
-        mem.sample("compression");
-        const int rq = quantise_tree_device(t, sc.qnodes.p, acc, g, h.q_inflation);
-        if (rq) return rq;
-        use_q = compressed_forced || h.q_inflation <= 1.10;
-        for (int a = 0; a < 3; a++) h.grid_lo[a] = g.lo[a], h.grid_step[a] = g.step[a];
-        if (!use_q) sc.qnodes.release();
-    }
-    if (!use_q) {  // full-width nodes
-        if constexpr (sizeof(R) == 4) {
-            sc.nodes = std::move(t.nodes);
-        } else {
-            HIP_TRY(sc.nodes.alloc((size_t)t.n_nodes));
-            mem.sample("wide nodes");
-            const int rw = wide_nodes_device(t, sc.nodes.p);
-            if (rw) return rw;
-        }
-    }
-    t.nodes.release();
-    // records into leaf order (a stable sort: coincident primitives stay in shape order): shape-order and leaf-order
-    // records coexist, next to the permutation and the finished nodes only
-    DevBuf<PrimRec<R>> prims_sorted;
-    HIP_TRY(prims_sorted.alloc(n));
-    mem.sample("permute");
-    hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(n), blk, 0, stream, sc.prims.p, t.order.p, n, prims_sorted.p);
-    HIP_TRY(hipStreamSynchronize(stream));
-    sc.prims = std::move(prims_sorted);  // (frees the shape-order records)
-    HIP_TRY(hipGetLastError());
-    mem.report();
-    return TAKE_OK;
-}
 // TAKE_INSTANCES_FLATTEN: the description with every placement expanded to a world-space mesh of its own — the geometry
 // an instanced render is specified to equal (TakeInstance, include/take_hip.h).  Placement i becomes mesh n_meshes + i:
 // positions M[:, :3] p + M[:, 3] and normals n^T L^-1 (not re-normalised: interpolation commutes with the linear map
@@ -378,295 +176,6 @@ struct StagedMeshes {
     }
 };
 
-// What k_make_prims — and, in a two-level scene, k_make_proto_prims and k_placement_boxes — read of the caller's
-// arrays, in device memory: the mesh positions as they are (double, one copy per mesh, no host staging) and the four
-// shape arrays.  Uploaded once per scene: both sides of a mixed-precision scene make their records from these.
-// device_positions: per mesh, positions that are in device memory already (a mesh take_hip_mesh_from_ply decoded; the
-// description then holds host copies of what the host side validates and tabulates, not of these), or null
-struct DeviceBuildInputs {
-    DevBuf<double> pos;
-    DevBuf<int32_t> kind, ref, face, area_light;
-    std::vector<int64_t> pos_off;         // per mesh: its first vertex in pos
-    const int32_t *face_idx = nullptr;    // the validated face indices on the device: the array of the side that uploaded them
-    bool ready = false;
-    int upload(const TakeSceneDesc &d, const double *const *device_positions) {
-        if (ready) return TAKE_OK;
-        const size_t n = (size_t)d.n_shapes;
-        pos_off.resize((size_t)d.n_meshes);
-        int64_t nv = 0;
-        for (int i = 0; i < d.n_meshes; i++) pos_off[i] = nv, nv += d.meshes[i].n_vertices;
-        HIP_TRY(pos.alloc(3 * (size_t)std::max<int64_t>(nv, 1)));
-        PinnedUploads pin;
-        for (int i = 0; i < d.n_meshes; i++) {
-            if (d.meshes[i].n_vertices <= 0) continue;
-            const size_t bytes = sizeof(double) * 3 * (size_t)d.meshes[i].n_vertices;
-            // a mesh decoded on the device (take_hip_mesh_from_ply): its positions never were on the host
-            if (device_positions && device_positions[i])
-                HIP_TRY(hipMemcpyAsync(pos.p + 3 * pos_off[i], device_positions[i], bytes, hipMemcpyDeviceToDevice, pin.stream));
-            else
-                HIP_TRY(pin.copy(pos.p + 3 * pos_off[i], d.meshes[i].positions, bytes));
-        }
-        auto up = [&](DevBuf<int32_t> &b, const int32_t *src) -> hipError_t {
-            hipError_t e = b.alloc(n);
-            return e != hipSuccess ? e : pin.copy(b.p, src, sizeof(int32_t) * n);
-        };
-        HIP_TRY(up(kind, d.shape_kind));
-        HIP_TRY(up(ref, d.shape_ref));
-        HIP_TRY(up(face, d.shape_face));
-        HIP_TRY(up(area_light, d.shape_area_light));
-        HIP_TRY(pin.finish());
-        if (std::getenv("TAKE_HIP_VERBOSE"))
-            std::fprintf(stderr, "[take_hip] scene_create: uploads pinned in place %.1f MB, pageable %.1f MB\n", pin.pinned_bytes / 1e6, pin.plain_bytes / 1e6);
-        ready = true;
-        return TAKE_OK;
-    }
-    void release() { pos.release(), kind.release(), ref.release(), face.release(), area_light.release(); }
-};
-
-// Primitive records of one side on the device (tk_build_gpu.h::k_make_prims<R>) from the shared inputs; the face indices
-// are the validated concatenation the shading side keeps anyway (sc.face_idx: uploaded by the first side, copied on
-// the device by the second).
-template <class R> lbvh::MeshSrc mesh_src(const HostScene<R> &h, const DeviceBuildInputs &in, int mesh) {
-    const MeshInfo &mi = h.meshes[mesh];
-    return lbvh::MeshSrc{in.pos_off[mesh], mi.fbase, mi.material, h.materials[mi.material].tag, (mi.nbase >= 0 || mi.uvbase >= 0) ? 1 : 0};
-}
-template <class R> int make_prims_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions) {
-    using namespace lbvh;
-    const int n = (int)d.n_shapes;
-    HostScene<R> &h = sc.host;
-    const int ru = in.upload(d, device_positions);
-    if (ru) return ru;
-    std::vector<MeshSrc> ms(d.n_meshes);
-    for (int i = 0; i < d.n_meshes; i++) ms[i] = mesh_src(h, in, i);
-    std::vector<SphereSrc> ss(d.n_spheres);
-    for (int i = 0; i < d.n_spheres; i++) {
-        const TakeSphere &s = d.spheres[i];
-        ss[i] = SphereSrc{{s.center[0], s.center[1], s.center[2]}, s.radius, s.material_id, h.materials[s.material_id].tag};
-    }
-    DevBuf<MeshSrc> d_ms;
-    DevBuf<SphereSrc> d_ss;
-    if (in.face_idx) {
-        HIP_TRY(sc.face_idx.alloc(h.face_idx.size()));
-        if (sc.face_idx.n) HIP_TRY(hipMemcpy(sc.face_idx.p, in.face_idx, sc.face_idx.bytes(), hipMemcpyDeviceToDevice));
-    } else {
-        HIP_TRY(sc.face_idx.upload(h.face_idx));
-        in.face_idx = sc.face_idx.p;
-    }
-    HIP_TRY(d_ms.upload(ms));
-    HIP_TRY(d_ss.upload(ss));
-    HIP_TRY(sc.prims.alloc((size_t)n));
-    if (n > 0)  // (a two-level scene may consist of placements only)
-        hipLaunchKernelGGL(k_make_prims<R>, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, nullptr, in.kind.p, in.ref.p, in.face.p,
-                           in.area_light.p, d_ms.p, in.pos.p, sc.face_idx.p, d_ss.p, n, sc.prims.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));  // (a failed kernel is reported here, not by a later call)
-    return TAKE_OK;
-}
-
-// BVH build on the device of a two-level scene (TakeInstance placements, TAKE_INSTANCES_TWO_LEVEL): the scene
-// build_host_trees makes, with LBVH trees.  In: sc.prims = the shapes' records in shape order (possibly none),
-// sc.face_idx, sc.host as prepare_scene(PREP_DEVICE_BUILD) leaves it (the placements' records and the PlacementPlan),
-// `in` still holding the positions.  Out: sc.prims = the top-level tree's records in leaf order, then each prototype's;
-// sc.qnodes or sc.nodes = the top-level tree's nodes, then each prototype's, child words global; the placements'
-// root_child and grid; stats.  Returns TAKE_OK, an error, or 1 = "use the host builder" — for the whole scene: a tree
-// of fewer than two leaves (a one-face prototype) or too deep a stack over both levels.
-//   1. per distinct prototype, one pass: k_make_proto_prims -> k_prim_boxes -> build_tree_device; its records go
-//      straight to their place behind the shapes' records, its float nodes wait (cut to size) for step 4;
-//   2. k_placement_boxes / k_placement_pad: the placements' boxes behind the shapes' boxes (host formula beyond 4e8
-//      vertex transforms, placement_box);
-//   3. the top-level tree over both, ONE entry per leaf whatever max_leaf is (a placement is a leaf of its own, and
-//      the compacted record ranges of k_top_leaves are single records); k_top_leaves, k_permute_top;
-//   4. every tree quantised on its own grid into the scene's node array — the worst inflation over all trees decides
-//      for the whole scene between compressed and full-width nodes, as quantise_trees does — and k_rebase.
-template <class R>
-int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBuildInputs &in, int max_leaf, bool compressed_ok, bool compressed_forced) {
-    using namespace lbvh;
-    HostScene<R> &h = sc.host;
-    const PlacementPlan &plan = h.placements;
-    const int n_shapes = (int)d.n_shapes, n_inst = (int)d.n_instances, n_top = n_shapes + n_inst;
-    const int n_protos = (int)plan.proto_mesh.size();
-    const int leaf_size = device_leaf_size(max_leaf);
-    hipStream_t stream = nullptr;
-    const dim3 blk(BLK);
-    BuildMemory mem(sizeof(R) == 4 ? "f32" : "f64");
-    if (n_top < 2) return 1;
-    std::vector<int64_t> prim_base(n_protos + 1), node_base(n_protos + 1);
-    prim_base[0] = n_shapes;
-    for (int k = 0; k < n_protos; k++) {
-        const int64_t nf = d.meshes[plan.proto_mesh[k]].n_faces;
-        if ((nf + leaf_size - 1) / leaf_size < 2) return 1;
-        prim_base[k + 1] = prim_base[k] + nf;
-    }
-    if (prim_base[n_protos] >= ((int64_t)1 << 28)) return fail(TAKE_E_INVALID, "too many primitive records for the 4-wide leaf encoding (2^28)");
-    DevBuf<PrimRec<R>> prims;  // the scene's records
-    HIP_TRY(prims.alloc((size_t)prim_base[n_protos]));
-    DevBuf<int> scene_ord;
-    HIP_TRY(scene_ord.alloc(6));
-
-    // 1. the prototypes' trees
-    std::vector<DeviceTree> protos(n_protos);
-    int proto_depth = 0;
-    for (int k = 0; k < n_protos; k++) {
-        const int mesh = plan.proto_mesh[k], nf = (int)d.meshes[mesh].n_faces;
-        DevBuf<PrimRec<R>> recs;
-        DevBuf<Box> pb;
-        HIP_TRY(recs.alloc(nf));
-        HIP_TRY(pb.alloc(nf));
-        HIP_TRY(hipMemcpyAsync(scene_ord.p, ORD_INIT, sizeof(ORD_INIT), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_make_proto_prims<R>, blocks_for(nf), blk, 0, stream, mesh_src(h, in, mesh), mesh, in.pos.p, sc.face_idx.p, nf, recs.p);
-        hipLaunchKernelGGL(k_prim_boxes<R>, blocks_for(nf), blk, 0, stream, recs.p, nf, pb.p, scene_ord.p);
-        DeviceTree &t = protos[k];
-        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t);
-        if (rt) return rt;
-        hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), blk, 0, stream, recs.p, t.order.p, nf, prims.p + prim_base[k]);
-        DevBuf<Node4<float>> cut;  // (the collapse allocates a node per leaf and uses about a third)
-        HIP_TRY(cut.alloc((size_t)t.n_nodes));
-        HIP_TRY(hipMemcpy(cut.p, t.nodes.p, cut.bytes(), hipMemcpyDeviceToDevice));
-        t.nodes = std::move(cut);
-        t.order.release();
-        proto_depth = std::max(proto_depth, t.depth);
-    }
-    mem.sample("prototypes");
-
-    // 2. the placements' boxes, behind the shapes'
-    DevBuf<Box> pb;
-    HIP_TRY(pb.alloc(n_top));
-    HIP_TRY(hipMemcpy(scene_ord.p, ORD_INIT, sizeof(ORD_INIT), hipMemcpyHostToDevice));
-    if (n_shapes > 0) hipLaunchKernelGGL(k_prim_boxes<R>, blocks_for(n_shapes), blk, 0, stream, sc.prims.p, n_shapes, pb.p, scene_ord.p);
-    {
-        std::vector<long long> tight_h(6 * (size_t)n_inst);
-        std::vector<double> xf(12 * (size_t)n_inst);
-        std::vector<std::vector<int32_t>> of_proto(n_protos);
-        for (int i = 0; i < n_inst; i++) {
-            for (int a = 0; a < 3; a++) tight_h[6 * (size_t)i + a] = INT64_MAX, tight_h[6 * (size_t)i + 3 + a] = INT64_MIN;
-            std::memcpy(&xf[12 * (size_t)i], d.instances[i].xform, 12 * sizeof(double));
-            of_proto[plan.inst_proto[i]].push_back(i);
-        }
-        // beyond 4e8 vertex transforms (placement_box's rule): the object box's corners under the transform, cut by the
-        // image of its bounding sphere — the object box being the tree's float bounds, which contain the host's box
-        std::vector<char> tight_on_device(n_protos);
-        for (int k = 0; k < n_protos; k++) {
-            const TakeMesh &m = d.meshes[plan.proto_mesh[k]];
-            tight_on_device[k] = (double)m.n_vertices * (double)d.n_instances <= 4e8;
-            if (tight_on_device[k]) continue;
-            Bounds ob;
-            ob.grow(protos[k].lo, protos[k].hi);
-            for (int32_t i : of_proto[k]) {
-                const Bounds w = placement_box(d, m, ob, Affine3{d.instances[i].xform});
-                for (int a = 0; a < 3; a++) tight_h[6 * (size_t)i + a] = d2ord(w.lo[a]), tight_h[6 * (size_t)i + 3 + a] = d2ord(w.hi[a]);
-            }
-        }
-        DevBuf<long long> tight;
-        DevBuf<double> xforms;
-        DevBuf<int32_t> ids;
-        HIP_TRY(tight.upload(tight_h));
-        HIP_TRY(xforms.upload(xf));
-        for (int k = 0; k < n_protos; k++) {
-            if (!tight_on_device[k]) continue;
-            const int mesh = plan.proto_mesh[k];
-            const int64_t nv = d.meshes[mesh].n_vertices;
-            const int chunks = (int)((nv + PLACEMENT_CHUNK - 1) / PLACEMENT_CHUNK);
-            HIP_TRY(ids.upload(of_proto[k]));  // (frees the previous prototype's list: waits for its kernel)
-            hipLaunchKernelGGL(k_placement_boxes, dim3((unsigned)((int64_t)chunks * (int64_t)of_proto[k].size())), blk, 0, stream,
-                               in.pos.p + 3 * in.pos_off[mesh], nv, chunks, ids.p, xforms.p, tight.p);
-        }
-        hipLaunchKernelGGL(k_placement_pad<R>, blocks_for(n_inst), blk, 0, stream, tight.p, n_inst, n_shapes, pb.p, scene_ord.p);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-    }
-
-    // 3. the top-level tree
-    DeviceTree top;
-    const int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top);
-    if (rt) return rt;
-    const int depth = top.depth + proto_depth;
-    if (3 * depth + 2 > MAX_STACK_ENTRIES) return 1;  // the traversal stack holds both levels and one return marker
-    {
-        DevBuf<int> is_shape, rank;
-        DevBuf<char> temp;
-        HIP_TRY(is_shape.alloc(n_top));
-        HIP_TRY(rank.alloc(n_top));
-        hipLaunchKernelGGL(k_flag_shapes, blocks_for(n_top), blk, 0, stream, top.order.p, n_top, n_shapes, is_shape.p);
-        size_t temp_bytes = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        HIP_TRY(temp.alloc(temp_bytes));
-        HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        hipLaunchKernelGGL(k_top_leaves, blocks_for(top.n_nodes), blk, 0, stream, top.nodes.p, (int)top.n_nodes, top.order.p, rank.p, n_shapes);
-        hipLaunchKernelGGL((k_permute_top<PrimRec<R>>), blocks_for(n_top), blk, 0, stream, sc.prims.p, top.order.p, rank.p, n_top, n_shapes, prims.p);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-    }
-    top.order.release();
-    sc.prims = std::move(prims);  // (frees the shape-order records)
-
-    // 4. assembly: the top-level tree's nodes, then each prototype's
-    node_base[0] = top.n_nodes;
-    for (int k = 0; k < n_protos; k++) node_base[k + 1] = node_base[k] + protos[k].n_nodes;
-    const int64_t n_nodes = node_base[n_protos];
-    if (n_nodes >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many nodes");
-    h.stats = WideBvhStats{};
-    h.stats.n_nodes = n_nodes, h.stats.n_prims = n_shapes, h.stats.depth = depth;
-    h.root_child = 0;
-    h.n_blas = n_protos, h.blas_nodes = n_nodes - top.n_nodes, h.blas_prims = prim_base[n_protos] - n_shapes;
-    h.q_inflation = 1.0;
-    bool use_q = false;
-    std::vector<QGrid> grids(n_protos);
-    if (compressed_ok) {
-        DevBuf<double> acc;
-        HIP_TRY(sc.qnodes.alloc((size_t)n_nodes));
-        HIP_TRY(acc.alloc(2));
-        mem.sample("compression");
-        QGrid g;
-        int rq = quantise_tree_device(top, sc.qnodes.p, acc, g, h.q_inflation);
-        for (int a = 0; a < 3; a++) h.grid_lo[a] = g.lo[a], h.grid_step[a] = g.step[a];
-        for (int k = 0; k < n_protos && !rq; k++) {
-            double infl = 1.0;
-            rq = quantise_tree_device(protos[k], sc.qnodes.p + node_base[k], acc, grids[k], infl);
-            h.q_inflation = std::max(h.q_inflation, infl);
-        }
-        if (rq) return rq;
-        use_q = compressed_forced || h.q_inflation <= 1.10;
-        if (!use_q) sc.qnodes.release();
-    }
-    if (!use_q) {
-        HIP_TRY(sc.nodes.alloc((size_t)n_nodes));
-        mem.sample("wide nodes");
-        int rw = wide_nodes_device(top, sc.nodes.p);
-        for (int k = 0; k < n_protos && !rw; k++) rw = wide_nodes_device(protos[k], sc.nodes.p + node_base[k]);
-        if (rw) return rw;
-    }
-    for (int k = 0; k < n_protos; k++) {
-        const int nk = (int)protos[k].n_nodes;
-        if (use_q) hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(nk), blk, 0, stream, sc.qnodes.p + node_base[k], nk, (int32_t)node_base[k], (int32_t)prim_base[k]);
-        else hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(nk), blk, 0, stream, sc.nodes.p + node_base[k], nk, (int32_t)node_base[k], (int32_t)prim_base[k]);
-    }
-    // (a prototype's root is node 0 of its tree: it has at least two leaves)
-    for (int i = 0; i < n_inst; i++) {
-        const int k = plan.inst_proto[i];
-        InstTrace<R> &it = h.inst_trace[i];
-        it.root_child = (int32_t)node_base[k];
-        if (compressed_ok)
-            for (int a = 0; a < 3; a++) it.grid_lo[a] = grids[k].lo[a], it.grid_step[a] = grids[k].step[a];
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipGetLastError());
-    mem.report();
-    return TAKE_OK;
-}
-
-// phase timer of scene_create (TAKE_HIP_VERBOSE=1 prints the phases to stderr)
-struct PhaseClock {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    bool on = std::getenv("TAKE_HIP_VERBOSE") != nullptr;
-    const char *side;  // "f32" / "f64": the side of the scene the phases belong to
-    explicit PhaseClock(const char *side_) : side(side_) {}
-    void lap(const char *what) {
-        if (!on) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[take_hip] scene_create: %s %-28s %8.1f ms\n", side, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
 
 // One precision's side of a new scene: records, tree and shading tables prepared on the host and uploaded, or with
 // device_builder the records and the tree made on the device — and, when the device tree would be too deep, on the
@@ -678,23 +187,16 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     PhaseClock clock(sizeof(R) == 4 ? "f32" : "f64");
     int max_leaf = opts.max_leaf_size;
     if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));  // tuning knob
-    const char *fmt_env = std::getenv("TAKE_HIP_NODES");
-    const std::string fmt = fmt_env ? fmt_env : "";
+    const std::string fmt = tree_knobs().nodes;
     bool on_device = device_builder;
     std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_DEVICE_BUILD : PREP_HOST_BUILD, opts.burley_lobes != 0);
     if (!err.empty()) return fail(TAKE_E_INVALID, err);
     clock.lap(on_device ? "host validation + tables" : "host records + SAH build");
     HostScene<R> &h = sc.host;
     if (on_device) {
-        const bool two_level = desc.n_instances > 0;
         const bool compressed_ok = compressed_nodes_supported() && fmt != "wide";
-        int rc = make_prims_on_device(sc, desc, inputs, staged.any ? staged.d_positions.data() : nullptr);
-        // (positions and shape arrays: not part of the build's peak — but a two-level build reads the prototypes' positions)
-        if (last_side && !two_level) inputs.release();
-        clock.lap("mesh arrays -> HBM, records");
-        if (!rc) rc = two_level ? build_two_level_device(sc, desc, inputs, max_leaf, compressed_ok, fmt == "q16")
-                                : build_bvh_device(sc, max_leaf, compressed_ok, fmt == "q16");
-        if (last_side) inputs.release();
+        const int rc = build_side_on_device(sc, desc, inputs, staged.any ? staged.d_positions.data() : nullptr, max_leaf, compressed_ok,
+                                            fmt == "q16", last_side, clock);
         if (rc == 1) {  // not buildable on the device (a tree too deep or of one leaf): do it on the host after all
             on_device = false;
             sc.prims.release(), sc.qnodes.release(), sc.nodes.release();
@@ -811,8 +313,8 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
                 n_build += std::max<int64_t>(local.meshes[mi].n_faces, 0);
             }
             n_build += local.n_instances;
-            const char *braid = std::getenv("TAKE_HIP_BRAID"), *nodes = std::getenv("TAKE_HIP_NODES");
-            device_can = !(braid && std::atoi(braid) > 1) && !(nodes && std::string(nodes) == "q8");
+            const TreeKnobs knobs = tree_knobs();
+            device_can = knobs.braid == 1 && knobs.nodes != "q8";
         }
         const bool device_builder = n_build >= 8 && device_can &&
                                     (o.builder == TAKE_BUILDER_DEVICE_LBVH || (o.builder == TAKE_BUILDER_AUTO && n_build >= TAKE_AUTO_DEVICE_BUILD_SHAPES));

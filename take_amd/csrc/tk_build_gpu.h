@@ -1,5 +1,6 @@
 // tk_build_gpu.h — BVH construction on the device (f32 and f64 sides of a scene): the GPU counterpart of
 // `construct_bvh` (src/bvh.cpp:8-45) for scenes where the host SAH build is the wait (10M triangles: ~6 s on 16 cores).
+// The kernels; the host driver that launches them is tk_build.hip, the only unit that includes this header.
 //
 //   k_make_prims     primitive records, float or double, from the caller's mesh arrays
 //   k_make_proto_prims  the same for a prototype mesh of a two-level scene: object space, shape_id = face

@@ -359,6 +359,8 @@ inline QGrid make_qgrid(const double lo_in[3], const double hi_in[3]) {
     }
     return g;
 }
+// "large": compressed nodes are refused beyond 10 % (the host's quantise_trees and the device build's assemble_nodes)
+constexpr double Q_MAX_INFLATION = 1.10;
 template <class R, int W>
 inline double quantise_nodes(const std::vector<NodeW<R, W>> &in, std::vector<QNodeW<W>> &out, float grid_lo[3],
                              float grid_step[3]) {

@@ -1,6 +1,6 @@
 // tk_host_scene.h — host-side preparation of a scene: validates a TakeSceneDesc, converts it to the
 // R-typed arrays of tk_scene.h, builds the wide BVH.  The result is a set of plain host vectors; the C-ABI
-// layer (tk_api.hip) uploads them to HBM.  Counterpart of the part of the reference's render() between
+// layer (tk_api.hip: upload_scene) uploads them to HBM.  Counterpart of the part of the reference's render() between
 // parse_scene and the tile loop (src/render.cpp:37-50) plus build_bvh (src/scene.cpp:4-23).
 // prepare_scene runs the steps: counts and camera, mesh_tables, material_table, image_table, validate_shape /
 // shape_record per shape, light_records (env_light), light_power_tables, build_trees, records into leaf order;
@@ -60,7 +60,7 @@ template <class R> struct HostScene {
     uint32_t tag_mask = 0;    // bit t set: some material has tag t
     int single_tag = 0;       // the tag when n_material_tags == 1
 
-    // pointers into the vectors above (a host "device scene" for tests/hostsim; tk_api.hip builds the real one)
+    // pointers into the vectors above (a host "device scene" for tests/hostsim; tk_api.hip's upload_scene builds the real one)
     DeviceScene<R> view() const {
         DeviceScene<R> d{};
         d.nodes = nodes.data();
@@ -175,7 +175,7 @@ template <class F> inline std::string for_chunks(int64_t n, int threads, F fn) {
 }
 
 // A placement transform (TakeInstance::xform: 3x4, row-major, object -> world), in double.  The expressions are the ones
-// the flattening of tk_api.hip and SceneData.flattened() use, operand order included: the "instanced equals flattened"
+// the flattening of tk_api.hip (FlattenedInstances) and SceneData.flattened() use, operand order included: the "instanced equals flattened"
 // tests compare bits.
 struct Affine3 {
     const double *m;
@@ -464,10 +464,10 @@ void quantise_trees(const std::vector<NodeW<R, W>> &nodes, size_t top_nodes, con
     for (size_t i = 0; i < inst_proto.size(); i++)
         for (int a = 0; a < 3; a++)
             hs.inst_trace[i].grid_lo[a] = grids[inst_proto[i]][a], hs.inst_trace[i].grid_step[a] = grids[inst_proto[i]][3 + a];
-    if (hs.q_inflation > 1.10 && fmt != "q16") qnodes.clear();
+    if (hs.q_inflation > Q_MAX_INFLATION && fmt != "q16") qnodes.clear();
 }
 
-// The host's share of a two-level scene the DEVICE builds (tk_api.hip): the placements validated, their InstTrace /
+// The host's share of a two-level scene the DEVICE builds (tk_build.hip: build_two_level_device): the placements validated, their InstTrace /
 // InstShade records (small tables; root_child and grid are filled in after the build), and which meshes are prototypes
 // — each distinct one once, in the order the placements first name them, as build_host_trees numbers them
 // (PlacementPlan, above HostScene).
@@ -489,7 +489,16 @@ template <class R> std::string plan_placements(const TakeSceneDesc &d, HostScene
     return "";
 }
 
-struct TreeOpts { int leaf_size, threads; std::string fmt; };  // fmt: TAKE_HIP_NODES
+// The tree tuning knobs of the environment (experiments and tests; read when a scene is built), for everyone who
+// asks: TAKE_HIP_NODES, the node format request — "" (compressed 4-wide unless the grid is too coarse), wide, q16
+// (compressed whatever the grid), q8 (the 8-wide tree) — and TAKE_HIP_BRAID, the top-level entries per placement, 1..64.
+struct TreeKnobs { std::string nodes; int braid; };
+inline TreeKnobs tree_knobs() {
+    const char *nodes = std::getenv("TAKE_HIP_NODES"), *braid = std::getenv("TAKE_HIP_BRAID");
+    return TreeKnobs{nodes ? nodes : "", std::max(1, std::min(braid ? std::atoi(braid) : 1, 64))};
+}
+
+struct TreeOpts { int leaf_size, threads; std::string fmt; int braid; };  // fmt, braid: tree_knobs
 
 // The host-side trees of a scene, W-wide: the top-level tree over `bp` (the shapes' boxes; one box per placement entry
 // of a two-level scene is appended here), the prototype trees behind it, their compressed form.  Out: `nodes` (full
@@ -498,8 +507,6 @@ struct TreeOpts { int leaf_size, threads; std::string fmt; };  // fmt: TAKE_HIP_
 template <class R, int W>
 std::string build_host_trees(const TakeSceneDesc &d, HostScene<R> &hs, std::vector<BuildPrim> &bp, const TreeOpts &o,
                              std::vector<int32_t> &order, std::vector<NodeW<R, W>> &nodes, std::vector<QNodeW<W>> &qnodes) {
-    const char *braid_env = std::getenv("TAKE_HIP_BRAID");
-    const int braid = std::max(1, std::min(braid_env ? std::atoi(braid_env) : 1, 64));
     std::vector<Prototype<R, W>> protos;
     std::vector<int> proto_of_mesh(d.n_meshes, -1);
     std::vector<int> inst_proto;  // per virtual instance: its prototype
@@ -512,7 +519,7 @@ std::string build_host_trees(const TakeSceneDesc &d, HostScene<R> &hs, std::vect
         if (proto_of_mesh[in.mesh_id] < 0) {
             proto_of_mesh[in.mesh_id] = (int)protos.size();
             protos.emplace_back();
-            protos.back().build(d, hs, in.mesh_id, o.leaf_size, o.threads, braid);
+            protos.back().build(d, hs, in.mesh_id, o.leaf_size, o.threads, o.braid);
         }
         const int k = proto_of_mesh[in.mesh_id];
         const std::string err = make_placement(d, i, protos[k], hs, shape_next, bp);
@@ -541,8 +548,8 @@ std::string build_trees(const TakeSceneDesc &d, int max_leaf, int threads, HostS
     // interior nodes cost (1M soup: 48.5 node + 10.8 primitive tests per ray vs 42.6 + 42.6 with 4 per leaf)
     // one primitive per leaf: with one ray per lane a leaf's primitives are tested one after the other, so a second
     // one doubles the leaf step of the whole wave (measured 1 / 2 / 3 / 4 per leaf: 75.6 / 71.0 / 61.0 / 50.8 Msamples/s)
-    const char *fmt_env = std::getenv("TAKE_HIP_NODES");
-    const TreeOpts o{max_leaf > 0 ? max_leaf : 1, threads, fmt_env ? fmt_env : ""};
+    const TreeKnobs knobs = tree_knobs();
+    const TreeOpts o{max_leaf > 0 ? max_leaf : 1, threads, knobs.nodes, knobs.braid};
     hs.node_width = 4;
     if (o.fmt == "q8") {
         const std::string err = build_host_trees<R, 8>(d, hs, bp, o, order, hs.nodes8, hs.qnodes8);

@@ -1,6 +1,6 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace, the kernel launchers, the wavefront
-// render loop, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h; what tk_api.hip (scene
-// creation, groups, the C entry points) calls here is declared in tk_scene_handle.h.  Host code only orchestrates:
+// render loop, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h (as tk_build.hip is for
+// tk_build_gpu.h); what tk_api.hip (scene creation, groups, the C entry points) calls here is declared in tk_scene_handle.h.  Host code only orchestrates:
 // every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
 

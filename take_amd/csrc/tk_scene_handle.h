@@ -1,7 +1,10 @@
 // tk_scene_handle.h — the scene handle (TakeScene: one SceneT per precision side) and the few functions that
-// tk_api.hip (scene creation, device build, groups, the C entry points) and tk_render.hip (tracing and rendering: the
-// only unit that compiles the kernels of tk_kernels.h) call across.  Includes no kernel source.
+// tk_api.hip (scene creation, groups, the C entry points) calls across: of tk_render.hip (tracing and rendering: the only
+// unit that compiles the kernels of tk_kernels.h) and of tk_build.hip (the device LBVH build: the only unit that
+// compiles the kernels of tk_build_gpu.h).  Includes no kernel source.
 #pragma once
+#include <chrono>
+#include <cstdio>
 #include <vector>
 
 #include "tk_host.h"
@@ -170,6 +173,20 @@ struct DeviceGuard {
     DeviceGuard guard_((ts)->device);                                                                 \
     if (!guard_.ok) return fail(TAKE_E_DEVICE, "cannot make the scene's device current")
 
+// phase timer of scene_create (TAKE_HIP_VERBOSE=1 prints the phases to stderr)
+struct PhaseClock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    bool on = std::getenv("TAKE_HIP_VERBOSE") != nullptr;
+    const char *side;  // "f32" / "f64": the side of the scene the phases belong to
+    explicit PhaseClock(const char *side_) : side(side_) {}
+    void lap(const char *what) {
+        if (!on) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[take_hip] scene_create: %s %-28s %8.1f ms\n", side, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    }
+};
+
 // ---- defined in tk_render.hip
 // Lanes per ray of the trace kernels: one (TQ_GROUP).  Round 1 measured quad 143.6 / pair 121.5 / one ray per lane
 // 128.8 ms of closest-hit time per 8.3 M samples on full-width nodes; on the 64-byte nodes one ray per lane is 9 %
@@ -186,5 +203,31 @@ int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
+
+// ---- defined in tk_build.hip
+// What k_make_prims — and, in a two-level scene, k_make_proto_prims and k_placement_boxes — read of the caller's
+// arrays, in device memory: the mesh positions as they are (double, one copy per mesh, no host staging) and the four
+// shape arrays.  Uploaded once per scene: both sides of a mixed-precision scene make their records from these.
+// device_positions: per mesh, positions that are in device memory already (a mesh take_hip_mesh_from_ply decoded; the
+// description then holds host copies of what the host side validates and tabulates, not of these), or null
+struct DeviceBuildInputs {
+    DevBuf<double> pos;
+    DevBuf<int32_t> kind, ref, face, area_light;
+    std::vector<int64_t> pos_off;         // per mesh: its first vertex in pos
+    const int32_t *face_idx = nullptr;    // the validated face indices on the device: the array of the side that uploaded them
+    bool ready = false;
+    int upload(const TakeSceneDesc &d, const double *const *device_positions);  // (a no-op for the second side)
+    void release() { pos.release(), kind.release(), ref.release(), face.release(), area_light.release(); }
+};
+// Records and trees of one side of a new scene, made on the device (the LBVH builder, tk_build_gpu.h).  In: sc.host as
+// prepare_scene(PREP_DEVICE_BUILD) leaves it; `in`: shared by the sides of the scene, uploaded by the first and released
+// here by the last (last_side) — after the records of a scene without placements, so that it stays out of the build's
+// peak; after the build of a two-level one, which reads the prototypes' positions.  Out: sc.prims in leaf order,
+// sc.qnodes or sc.nodes, sc.face_idx, the stats, grid and placements' roots in sc.host.  compressed_ok / _forced: 64-byte
+// nodes unless the grid is too coarse (Q_MAX_INFLATION) / even then.  Returns TAKE_OK, an error, or 1 = "use the host
+// builder": a tree of fewer than two leaves, or too deep for the traversal stack.  Laps "mesh arrays -> HBM, records".
+template <class R>
+int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions, int max_leaf,
+                         bool compressed_ok, bool compressed_forced, bool last_side, PhaseClock &clock);
 
 }  // namespace tk_host

@@ -125,7 +125,7 @@ template <class R> RenderParams<R> render_params(const HostScene<R> &hs, const T
 }
 
 // MIXED: R = double, and rounds k >= exact_bounces (<= 0: TAKE_DEFAULT_EXACT_BOUNCES) run on f32 records of the same
-// slots and the f32 scene (tk_api.hip render_impl); the samples are accumulated as k_accumulate_mixed does.
+// slots and the f32 scene (tk_render.hip: render_impl); the samples are accumulated as k_accumulate_mixed does.
 template <class R, bool MIXED = false>
 int render_t(const TakeSceneDesc &desc, const TakeRenderOpts &o, void *out_v, uint64_t *stats) {
     const int max_leaf = std::getenv("HOSTSIM_MAX_LEAF") ? std::atoi(std::getenv("HOSTSIM_MAX_LEAF")) : 0;

@@ -1,5 +1,5 @@
 """Two-level (instanced) scenes built on the device (TAKE_BUILDER_DEVICE_LBVH: k_make_proto_prims, k_placement_boxes,
-k_placement_pad, the top-level tree with instance words, k_rebase — take_amd/csrc/tk_build_gpu.h, tk_api.hip) against
+k_placement_pad, the top-level tree with instance words, k_rebase — take_amd/csrc/tk_build_gpu.h, tk_build.hip) against
 the host SAH build of the same scene and against the flattened geometry.  The trees differ and the RESULTS must not:
 box tests are conservative and ties are broken on values, so every DEV-against-HOST comparison is np.array_equal; the
 comparisons with the flattened scene use the bars of tests/test_instancing.py."""
@@ -436,7 +436,7 @@ def seven_primitive_scene(one_face=False):
 @pytest.mark.parametrize("precision", [F32, F64, MIXED])
 def test_tiny_scenes_and_one_face_prototypes_are_built_by_the_host(precision):
     """fewer than 8 primitives in all: the documented minimum.  A prototype of one face makes a tree of one leaf: the
-    whole scene takes the host route (tk_api.hip: build_two_level_device)"""
+    whole scene takes the host route (tk_build.hip: build_two_level_device)"""
     for sd in (seven_primitive_scene(), seven_primitive_scene(one_face=True)):
         a, b = pair(sd, precision, HOST)
         try:
