@@ -318,6 +318,34 @@ int take_hip_device_count(void);
 int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, TakeScene **out);
 int take_hip_scene_destroy(TakeScene *scene);
 
+/* ---- a resident scene changes (new symbols of ABI version 5; no struct changed).  All three calls: a failed call
+ * leaves the scene exactly as it was (same hits, same image); a successful one ends a progressive sequence
+ * (take_hip_accumulated_samples = 0) and the next take_hip_render_accumulate must be called with restart != 0
+ * (TAKE_E_INVALID otherwise); F32, F64 and MIXED scenes — a mixed scene changes on both sides or on neither.  Scene
+ * groups (take_hip_group_*) are out of scope: a group's replicas cannot be changed, create a new group.
+ *
+ * New object -> world transforms for ALL placements of a two-level scene, in the order of TakeSceneDesc.instances
+ * (n must equal the scene's n_instances; 12 doubles each, as TakeInstance::xform).  Prototypes, materials and
+ * shape ids stay as they are.  Afterwards the scene traces and renders exactly as a scene newly created from
+ * the same description with these transforms would: hits and images bit for bit.  Only the top level is made again,
+ * on the device, from what the scene keeps there: the placements' records and boxes (the prototypes' records under the
+ * new transforms), an LBVH over the shapes and the placements, the node array with the prototypes' trees copied
+ * behind the new top-level tree.  No mesh, texture or light table is read or uploaded; the prototypes' trees are not
+ * touched; the scene keeps its node format.  Who built the scene does not matter (a host-SAH scene has an LBVH top
+ * level from its first update on).
+ * TAKE_E_INVALID: a NULL argument, a wrong n, a scene without placements (none given, or expanded by
+ * TAKE_INSTANCES_FLATTEN), a singular (|det| <= 1e-300) or non-finite transform — the message names the first such
+ * placement.  TAKE_E_INVALID with a message that starts with "unsupported": a scene built under TAKE_HIP_BRAID > 1 or
+ * TAKE_HIP_NODES=q8, or a new top-level tree of fewer than two leaves or too deep for the traversal stack. */
+int take_hip_scene_set_instance_transforms(TakeScene *scene, const double *xforms, int64_t n);
+/* the same with the transforms in device memory (e.g. a torch tensor): waits for `stream` (hipStream_t, NULL = default
+ * stream), whose work may still be writing them, builds on the default stream as scene_create does, returns after it
+ * has completed */
+int take_hip_scene_set_instance_transforms_device(TakeScene *scene, const double *d_xforms, int64_t n, void *stream);
+/* New camera; width and height must equal the scene's (the render buffers are sized from them), TAKE_E_INVALID
+ * otherwise.  Any scene, with or without placements. */
+int take_hip_scene_set_camera(TakeScene *scene, const TakeCamera *camera);
+
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order
  * (n_rows(strip_first, strip_stride) * width * 3 Real), already flipped as

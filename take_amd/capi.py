@@ -27,6 +27,7 @@ EXPORTS = [
     "take_hip_mesh_from_serialized", "take_hip_mesh_from_serialized_file", "take_hip_mesh_download", "take_hip_mesh_release",
     "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
     "take_hip_scene_build_info",
+    "take_hip_scene_set_instance_transforms", "take_hip_scene_set_instance_transforms_device", "take_hip_scene_set_camera",
 ]
 
 
@@ -73,6 +74,8 @@ def lib():
         L.take_hip_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        for name, argtypes in D.SCENE_UPDATE_PROTOTYPES.items():
+            getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
         L.take_hip_group_create.argtypes = [C.POINTER(D.TakeSceneDesc), C.POINTER(D.TakeBuildOpts), C.c_int32,
@@ -307,6 +310,33 @@ class Scene:
         o = self._opts(more_spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
         _check(lib().take_hip_render_accumulate(self.h, C.byref(o), 1 if restart else 0, C.c_void_p(d_ptr), C.c_void_p(stream or 0)))
         return int(lib().take_hip_accumulated_samples(self.h))
+
+    def set_instance_transforms(self, xforms, stream=None):
+        """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the
+        description's instances; only the top level is rebuilt, on the device (take_hip_scene_set_instance_transforms).
+        A numpy array (or anything numpy converts) goes through the host entry point; a torch device tensor or an
+        integer device pointer — then `n` is the scene's placement count — through the device one."""
+        if isinstance(xforms, int):
+            n, ptr = len(self.sd.instance_mesh), xforms
+        elif hasattr(xforms, "data_ptr") and getattr(xforms, "is_cuda", False):
+            if str(xforms.dtype) != "torch.float64" or not xforms.is_contiguous() or xforms.numel() % 12:
+                raise ValueError("transforms on the device must be a contiguous float64 tensor of shape (n, 3, 4)")
+            n, ptr = xforms.numel() // 12, xforms.data_ptr()
+        else:
+            if hasattr(xforms, "data_ptr"):  # a torch tensor in host memory
+                xforms = xforms.numpy()
+            x = np.ascontiguousarray(xforms, np.float64)
+            if x.size % 12:
+                raise ValueError("transforms must have shape (n, 3, 4)")
+            _check(lib().take_hip_scene_set_instance_transforms(self.h, x.ctypes.data, x.size // 12))
+            return
+        _check(lib().take_hip_scene_set_instance_transforms_device(self.h, C.c_void_p(ptr), n, C.c_void_p(stream or 0)))
+
+    def set_camera(self, lookfrom, lookat, up, vfov, width=None, height=None):
+        """a new camera for the resident scene (take_hip_scene_set_camera); width and height stay the scene's"""
+        cam = D.TakeCamera(self.sd.width if width is None else int(width), self.sd.height if height is None else int(height),
+                           D.c_double3(*map(float, lookfrom)), D.c_double3(*map(float, lookat)), D.c_double3(*map(float, up)), float(vfov))
+        _check(lib().take_hip_scene_set_camera(self.h, C.byref(cam)))
 
     def trace_closest(self, rays_abi):
         """rays_abi: (n,8) array in TakeRayF/D layout (org3 tmin dir3 tmax) -> structured hits"""

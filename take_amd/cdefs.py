@@ -87,6 +87,14 @@ TAKE_BUILDER_DEVICE_LBVH = 1
 TAKE_BUILDER_HOST_SAH = 2
 
 
+# prototypes of the entry points that change a resident scene (include/take_hip.h): name -> argument types
+SCENE_UPDATE_PROTOTYPES = {
+    "take_hip_scene_set_instance_transforms": [C.c_void_p, C.c_void_p, C.c_int64],
+    "take_hip_scene_set_instance_transforms_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "take_hip_scene_set_camera": [C.c_void_p, C.POINTER(TakeCamera)],
+}
+
+
 class TakeRenderOpts(C.Structure):
     _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64), ("ray_epsilon", C.c_double),
                 ("strip_first", C.c_int32), ("strip_stride", C.c_int32), ("samples_per_batch", C.c_int32),

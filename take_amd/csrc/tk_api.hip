@@ -332,6 +332,7 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         rc = fail(TAKE_E_INVALID, e.what());
     }
     if (rc) return rc;
+    ts->n_placements = o.instances == TAKE_INSTANCES_TWO_LEVEL ? desc->n_instances : 0;
     *out = ts.release();
     return TAKE_OK;
 }
@@ -360,6 +361,8 @@ int take_hip_render_device(TakeScene *ts, const TakeRenderOpts *opts, void *d_rg
 int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_t restart, void *d_rgb_out, void *stream) {
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
+    if (ts->acc_restart_needed && restart == 0)
+        return fail(TAKE_E_INVALID, "take_hip_render_accumulate: the scene's placements or camera changed since the last call: pass restart = 1");
     const TakeRenderOpts &a = ts->acc_opts;
     const bool fresh = restart != 0 || ts->acc_samples == 0;
     // (mixed scenes: the exact rounds the samples were rendered with, <= 0 meaning the default; f32 / f64 ignore the field)
@@ -382,6 +385,7 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
     }
     ts->acc_samples = first + opts->spp;
     ts->acc_opts = *opts;
+    ts->acc_restart_needed = false;
     return TAKE_OK;
 }
 int64_t take_hip_accumulated_samples(const TakeScene *ts) { return ts ? ts->acc_samples : 0; }
@@ -441,6 +445,77 @@ int take_hip_trace_closest_device(TakeScene *ts, const void *d_rays, int64_t n, 
 }
 
 
+// ------------------------------------------------------------------------------------------------ a resident scene changes
+}  // extern "C"
+
+namespace {
+// what take_hip_scene_set_instance_transforms accepts, checked before anything is read or made
+int check_repose(const TakeScene *ts, int64_t n) {
+    if (ts->n_placements <= 0) return fail(TAKE_E_INVALID, "the scene has no placements (none were given, or TAKE_INSTANCES_FLATTEN expanded them)");
+    if (n != ts->n_placements) return fail(TAKE_E_INVALID, "n = " + std::to_string(n) + ", but the scene has " + std::to_string(ts->n_placements) + " placements");
+    const bool plain = on_primary(ts, [&](const auto &sc) {
+        return sc.trace.two_level && sc.trace.nodes != NodeFormat::Q8 && (int64_t)sc.inst_trace.n == n && (int64_t)sc.host.placements.inst_proto.size() == n;
+    });
+    if (!plain) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_BRAID > 1 or TAKE_HIP_NODES=q8");
+    return TAKE_OK;
+}
+// New transforms (device memory, complete) for all placements of ts (check_repose passed): every side staged, then
+// every side committed — a mixed scene gets both or neither.
+int set_instance_transforms(TakeScene *ts, const double *d_xforms, int64_t n) {
+    try {
+        ReposeStage<double> sd;
+        ReposeStage<float> sf;
+        int rc = TAKE_OK;
+        if (ts->precision != TAKE_PRECISION_F32) rc = repose_two_level_device(ts->d, d_xforms, n, sd);
+        if (!rc && ts->precision != TAKE_PRECISION_F64) rc = repose_two_level_device(ts->f, d_xforms, n, sf);
+        if (rc) return rc;
+        if (ts->precision != TAKE_PRECISION_F32) rc = sd.commit(ts->d);
+        if (!rc && ts->precision != TAKE_PRECISION_F64) rc = sf.commit(ts->f);
+        ts->acc_samples = 0, ts->acc_restart_needed = true;
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(TAKE_E_NOMEM, "out of host memory while re-posing the placements");
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int take_hip_scene_set_instance_transforms_device(TakeScene *ts, const double *d_xforms, int64_t n, void *stream) {
+    if (!ts || !d_xforms) return fail(TAKE_E_INVALID, "null argument");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    // (the build runs on the default stream, as scene_create's does: first whatever `stream` still has to write into d_xforms)
+    const int rc = check_repose(ts, n);
+    if (rc) return rc;
+    if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return set_instance_transforms(ts, d_xforms, n);
+}
+int take_hip_scene_set_instance_transforms(TakeScene *ts, const double *xforms, int64_t n) {
+    if (!ts || !xforms) return fail(TAKE_E_INVALID, "null argument");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    const int rc = check_repose(ts, n);
+    if (rc) return rc;
+    DevBuf<double> d_xforms;
+    if (d_xforms.alloc(12 * (size_t)n) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the transforms");
+    HIP_TRY(hipMemcpy(d_xforms.p, xforms, d_xforms.bytes(), hipMemcpyHostToDevice));
+    return set_instance_transforms(ts, d_xforms.p, n);
+}
+int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
+    if (!ts || !camera) return fail(TAKE_E_INVALID, "null argument");
+    if (camera->width != ts->width() || camera->height != ts->height())
+        return fail(TAKE_E_INVALID, "the new camera is " + std::to_string(camera->width) + " x " + std::to_string(camera->height) + ", the scene " +
+                                        std::to_string(ts->width()) + " x " + std::to_string(ts->height()) + ": the render buffers are sized at creation");
+    if (ts->precision != TAKE_PRECISION_F32) make_camera<double>(*camera, ts->d.host.cam), ts->d.dev.cam = ts->d.host.cam;
+    if (ts->precision != TAKE_PRECISION_F64) make_camera<float>(*camera, ts->f.host.cam), ts->f.dev.cam = ts->f.host.cam;
+    ts->acc_samples = 0, ts->acc_restart_needed = true;
+    return TAKE_OK;
+}
+
+
 // ------------------------------------------------------------------------------------------------ scene groups
 }  // extern "C"
 
@@ -475,6 +550,7 @@ int replicate_scene(const TakeScene *src, int device, TakeScene **out) {
     std::unique_ptr<TakeScene> ts(new (std::nothrow) TakeScene());
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
     ts->precision = src->precision, ts->device = device, ts->num_cus = src->num_cus, ts->instrumentation = 0;
+    ts->n_placements = src->n_placements;
     if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the replica's device current");
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ts->num_cus = cus;

@@ -1,6 +1,7 @@
 // tk_build.hip — the host driver of the device LBVH builder: the records and trees of one side of a new scene made on
 // the device from the caller's arrays (build_side_on_device, declared in tk_scene_handle.h; tk_api.hip's upload_scene
-// calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
+// calls it), and the top-level half of it entered again for a resident scene whose placements get new transforms
+// (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -474,6 +475,9 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     if (n_nodes >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many nodes");
     init_stats(h, n_nodes, n_shapes, depth);
     h.n_blas = n_protos, h.blas_nodes = n_nodes - top.n_nodes, h.blas_prims = prim_base[n_protos] - n_shapes;
+    h.blas_depth = proto_depth;
+    h.blas_prim_first.assign(prim_base.begin(), prim_base.begin() + n_protos), h.blas_prim_count.resize(n_protos);
+    for (int k = 0; k < n_protos; k++) h.blas_prim_count[k] = prim_base[k + 1] - prim_base[k];
     bool use_q;
     std::vector<QGrid> grids;  // [1 + k]: prototype k's
     const int ra = assemble_nodes(sc, trees, node_at, compressed_ok, compressed_forced, mem, use_q, grids);
@@ -517,5 +521,148 @@ int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInput
 }
 template int build_side_on_device<float>(SceneT<float> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
 template int build_side_on_device<double>(SceneT<double> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
+
+template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n64, ReposeStage<R> &out) {
+    using namespace lbvh;
+    const HostScene<R> &h = sc.host;
+    const int n_inst = (int)n64, n_protos = (int)h.blas_prim_first.size();
+    const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims), n_top = n_shapes + n_inst;
+    const bool use_q = sc.trace.nodes == NodeFormat::Q4;
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    BuildMemory mem(sizeof(R) == 4 ? "f32 (placements re-posed)" : "f64 (placements re-posed)");
+
+    // 1. the placements' records; a transform that cannot be inverted is reported before anything else is made
+    {
+        DevBuf<int> bad;
+        const int none = INT32_MAX;
+        int bad_h = none;
+        HIP_TRY(out.inst_trace.alloc(n_inst));
+        HIP_TRY(out.inst_shade.alloc(n_inst));
+        HIP_TRY(bad.alloc(1));
+        HIP_TRY(hipMemcpyAsync(bad.p, &none, sizeof(int), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), blk, 0, stream, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p,
+                           out.inst_trace.p, out.inst_shade.p, bad.p);
+        HIP_TRY(hipMemcpy(&bad_h, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        if (bad_h != none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad_h) + ": singular or non-finite transform");
+    }
+
+    // 2. tight world boxes from the prototypes' resident records, 3. the shapes' boxes from theirs: the head of the
+    // record array, in the leaf order of the tree that is being replaced
+    DevBuf<Box> pb;
+    DevBuf<int> scene_ord;
+    HIP_TRY(pb.alloc(n_top));
+    HIP_TRY(scene_ord.alloc(6));
+    HIP_TRY(reset_bounds(scene_ord));
+    span_boxes(sc.prims.p, n_shapes, pb.p, scene_ord);
+    {
+        std::vector<int2> span_h((size_t)n_inst);
+        std::vector<int64_t> block0_h((size_t)n_inst + 1, 0);
+        std::vector<long long> tight_h(6 * (size_t)n_inst);
+        for (int i = 0; i < n_inst; i++) {
+            const int k = h.placements.inst_proto[i];
+            if (k < 0 || k >= n_protos) return fail(TAKE_E_INVALID, "the scene does not know the prototype of placement " + std::to_string(i));
+            span_h[i] = make_int2((int)h.blas_prim_first[k], (int)h.blas_prim_count[k]);
+            block0_h[i + 1] = block0_h[i] + (h.blas_prim_count[k] + REPOSE_CHUNK - 1) / REPOSE_CHUNK;
+            for (int a = 0; a < 3; a++) tight_h[6 * (size_t)i + a] = INT64_MAX, tight_h[6 * (size_t)i + 3 + a] = INT64_MIN;
+        }
+        if (block0_h[n_inst] >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "unsupported: too many prototype records times placements for one launch");
+        DevBuf<int2> span;
+        DevBuf<int64_t> block0;
+        DevBuf<long long> tight, maxabs;
+        HIP_TRY(span.upload(span_h));
+        HIP_TRY(block0.upload(block0_h));
+        HIP_TRY(tight.upload(tight_h));
+        HIP_TRY(maxabs.alloc(n_inst));
+        HIP_TRY(hipMemsetAsync(maxabs.p, 0, maxabs.bytes(), stream));
+        hipLaunchKernelGGL(k_placement_boxes_resident<R>, dim3((unsigned)block0_h[n_inst]), blk, 0, stream, sc.prims.p, span.p, block0.p, n_inst, d_xforms,
+                           tight.p, maxabs.p);
+        hipLaunchKernelGGL(k_widen_tight<R>, blocks_for(n_inst), blk, 0, stream, tight.p, maxabs.p, d_xforms, n_inst);
+        hipLaunchKernelGGL(k_placement_pad<R>, blocks_for(n_inst), blk, 0, stream, tight.p, n_inst, n_shapes, pb.p, scene_ord.p);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+    }
+
+    // 4. the top-level tree, one entry per leaf, and its records.  The shapes come out of the OLD leaf order, not the
+    // shape order a fresh build sorts: results do not depend on it.  Box tests are conservative, and a tie between
+    // coincident primitives is decided by values — inside the top level by the position of the record, where every
+    // group of coincident records holds its shape ids in ascending order (order_coincident; a stable sort of the shape
+    // order) and keeps them so here: equal geometry is equal boxes is equal Morton codes, and the sort is stable.
+    DeviceTree top;
+    const int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top);
+    if (rt == 1) return fail(TAKE_E_INVALID, n_top < 2 ? "unsupported: a top-level tree of fewer than two leaves"
+                                                       : "unsupported: the new top-level tree is too deep for the traversal stack");
+    if (rt) return rt;
+    out.depth = top.depth + h.blas_depth;
+    if (3 * out.depth + 2 > MAX_STACK_ENTRIES) return fail(TAKE_E_INVALID, "unsupported: the new top-level tree is too deep for the traversal stack");
+    {
+        DevBuf<int> is_shape, rank;
+        DevBuf<char> temp;
+        HIP_TRY(is_shape.alloc(n_top));
+        HIP_TRY(rank.alloc(n_top));
+        HIP_TRY(out.head.alloc(n_shapes));
+        hipLaunchKernelGGL(k_flag_shapes, blocks_for(n_top), blk, 0, stream, top.order.p, n_top, n_shapes, is_shape.p);
+        size_t temp_bytes = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
+        HIP_TRY(temp.alloc(temp_bytes));
+        HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
+        hipLaunchKernelGGL(k_top_leaves, blocks_for(top.n_nodes), blk, 0, stream, top.nodes.p, (int)top.n_nodes, top.order.p, rank.p, n_shapes);
+        if (n_shapes > 0)
+            hipLaunchKernelGGL((k_permute_top<PrimRec<R>>), blocks_for(n_top), blk, 0, stream, sc.prims.p, top.order.p, rank.p, n_top, n_shapes, out.head.p);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+    }
+    top.order.release();
+
+    // 5. assembly in the scene's node format: the new top-level tree on its own grid, the prototypes' nodes copied behind
+    // it — moved by the difference of the two top-level trees' sizes, and their child words and the placements' roots with them
+    const int64_t old_top = h.stats.n_nodes - h.blas_nodes, delta = top.n_nodes - old_top;
+    out.n_nodes = top.n_nodes + h.blas_nodes;
+    if (out.n_nodes >= ((int64_t)1 << 31) || (uint64_t)out.n_nodes * node_bytes<R>(sc.trace.nodes) >= (1ull << 32))
+        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
+    const int nb = (int)h.blas_nodes;
+    if (use_q) {
+        DevBuf<double> acc;
+        QGrid g;
+        double inflation = 1.0;
+        HIP_TRY(out.qnodes.alloc((size_t)out.n_nodes));
+        HIP_TRY(acc.alloc(2));
+        const int rq = quantise_tree_device(top, out.qnodes.p, acc, g, inflation);
+        if (rq) return rq;
+        for (int a = 0; a < 3; a++) out.grid_lo[a] = g.lo[a], out.grid_step[a] = g.step[a];
+        if (nb > 0) HIP_TRY(hipMemcpyAsync(out.qnodes.p + top.n_nodes, sc.qnodes.p + old_top, (size_t)nb * sizeof(QNode4), hipMemcpyDeviceToDevice, stream));
+        if (nb > 0 && delta) hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(nb), blk, 0, stream, out.qnodes.p + top.n_nodes, nb, (int32_t)delta, 0);
+    } else {
+        for (int a = 0; a < 3; a++) out.grid_lo[a] = h.grid_lo[a], out.grid_step[a] = h.grid_step[a];  // (not read by the traversal)
+        HIP_TRY(out.nodes.alloc((size_t)out.n_nodes));
+        const int rw = wide_nodes_device(top, out.nodes.p);
+        if (rw) return rw;
+        if (nb > 0) HIP_TRY(hipMemcpyAsync(out.nodes.p + top.n_nodes, sc.nodes.p + old_top, (size_t)nb * sizeof(Node4<R>), hipMemcpyDeviceToDevice, stream));
+        if (nb > 0 && delta) hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(nb), blk, 0, stream, out.nodes.p + top.n_nodes, nb, (int32_t)delta, 0);
+    }
+    if (delta) hipLaunchKernelGGL(k_shift_roots<R>, blocks_for(n_inst), blk, 0, stream, out.inst_trace.p, n_inst, (int32_t)delta);
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    mem.report();
+    return TAKE_OK;
+}
+template <class R> int ReposeStage<R>::commit(SceneT<R> &sc) {
+    HostScene<R> &h = sc.host;
+    if (head.n) HIP_TRY(hipMemcpy(sc.prims.p, head.p, head.bytes(), hipMemcpyDeviceToDevice));
+    if (qnodes.p) sc.qnodes = std::move(qnodes);
+    else sc.nodes = std::move(nodes);
+    sc.inst_trace = std::move(inst_trace), sc.inst_shade = std::move(inst_shade);
+    h.stats.n_nodes = n_nodes, h.stats.depth = depth;
+    h.root_child = 0;  // (the new tree has at least two leaves: its root is node 0)
+    for (int a = 0; a < 3; a++) h.grid_lo[a] = sc.dev.grid_lo[a] = grid_lo[a], h.grid_step[a] = sc.dev.grid_step[a] = grid_step[a];
+    sc.dev.root_child = 0, sc.dev.n_nodes = (int32_t)n_nodes;
+    sc.bind();
+    return TAKE_OK;
+}
+template struct ReposeStage<float>;
+template struct ReposeStage<double>;
+template int repose_two_level_device<float>(const SceneT<float> &, const double *, int64_t, ReposeStage<float> &);
+template int repose_two_level_device<double>(const SceneT<double> &, const double *, int64_t, ReposeStage<double> &);
 
 }  // namespace tk_host

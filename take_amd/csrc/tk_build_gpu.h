@@ -22,6 +22,10 @@
 //   k_flag_shapes / k_top_leaves / k_permute_top   the top-level tree's leaves: a placement becomes an instance word,
 //                    the shapes' records are compacted into leaf order
 //   k_rebase         a prototype tree's child words (local node indices, local leaf ranges) -> the scene's arrays
+// Re-posing the placements of a resident two-level scene (take_hip_scene_set_instance_transforms) adds
+//   k_placement_records          the placements' InstTrace / InstShade records under new transforms
+//   k_placement_boxes_resident   their tight world boxes from the prototypes' records in the scene, k_widen_tight
+//   k_shift_roots                the placements' roots after the top-level tree changed its size
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
@@ -534,6 +538,146 @@ __global__ void __launch_bounds__(BLK) k_rebase(NodeT *nodes, int n, int32_t nod
         if (w == CHILD_EMPTY) continue;
         nodes[i].c[c].child = w >= 0 ? w + node_base : make_leaf(leaf_first(w) + prim_base, leaf_count(w));
     }
+}
+
+// ---- re-posing the placements of a RESIDENT two-level scene (tk_build.hip: repose_two_level_device): new transforms,
+// everything else read from what the scene keeps in device memory — no mesh positions, nothing of the caller's.
+
+// The InstTrace / InstShade records of placement i under its new transform (xforms: 12 doubles per placement, as
+// TakeInstance::xform): the expressions of Affine3::inverse_linear and placement_records (tk_host_scene.h), operand
+// order included, and the build does not contract — the records are the bits a fresh scene_create computes on the
+// host.  What a transform does not change comes from the old records: the prototype's root and grid, the material, its
+// tag, the first shape id.  A transform inverse_linear refuses (|det| <= 1e-300, or a NaN that reaches the determinant),
+// or with an entry that is not finite, writes nothing and leaves the smallest such index in *bad (INT_MAX before).
+template <class R>
+__global__ void __launch_bounds__(BLK) k_placement_records(const double *__restrict__ xforms, int n, const InstTrace<R> *__restrict__ old_trace,
+                                                            const InstShade<R> *__restrict__ old_shade, InstTrace<R> *new_trace, InstShade<R> *new_shade, int *bad) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    double M[12];
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 12; k++) M[k] = xforms[12 * (int64_t)i + k], finite = finite && __builtin_isfinite(M[k]);
+    const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+    const double det = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
+    if (!finite || !(fabs(det) > 1e-300)) {
+        atomicMin(bad, i);
+        return;
+    }
+    double inv[9];
+    inv[0] = (a11 * a22 - a12 * a21) / det, inv[1] = (a02 * a21 - a01 * a22) / det, inv[2] = (a01 * a12 - a02 * a11) / det;
+    inv[3] = (a12 * a20 - a10 * a22) / det, inv[4] = (a00 * a22 - a02 * a20) / det, inv[5] = (a02 * a10 - a00 * a12) / det;
+    inv[6] = (a10 * a21 - a11 * a20) / det, inv[7] = (a01 * a20 - a00 * a21) / det, inv[8] = (a00 * a11 - a01 * a10) / det;
+    InstTrace<R> it = old_trace[i];
+    InstShade<R> is = old_shade[i];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) it.inv[4 * r + c] = (R)inv[3 * r + c], is.fwd[3 * r + c] = (R)M[4 * r + c];
+        it.inv[4 * r + 3] = (R)(-(inv[3 * r] * M[3] + inv[3 * r + 1] * M[7] + inv[3 * r + 2] * M[11]));
+    }
+    new_trace[i] = it;
+    new_shade[i] = is;
+}
+
+// Tight world boxes of the placements from the RESIDENT records of their prototypes.  span[i] = (first record, number
+// of records) of placement i's prototype in `prims`; block0[i] = the first block of placement i, which gets one block
+// per REPOSE_CHUNK records (block0[n] = the grid), found by bisection.  The vertices of a record are what k_prim_boxes
+// reads, a[0..2], a[0..2] + a[3..5], a[0..2] + a[6..8], here summed and transformed in double (Affine3::image's
+// expression, as k_placement_boxes); per-wave partials in LDS, then ordered 64-bit atomics into tight[6 i ..], and the
+// prototype's largest |coordinate| (the order of non-negative doubles is the order of their bits) into maxabs[i].
+// A streaming kernel: every record is read once per placement of its prototype, 36 (72) of its bytes.
+constexpr int REPOSE_CHUNK = 16 * BLK;
+template <class R>
+__global__ void __launch_bounds__(BLK) k_placement_boxes_resident(const PrimRec<R> *__restrict__ prims, const int2 *__restrict__ span,
+                                                                   const int64_t *__restrict__ block0, int n, const double *__restrict__ xforms,
+                                                                   long long *tight, long long *maxabs) {
+    __shared__ double part[BLK / 64][7];
+    int lo_i = 0, hi_i = n;  // block0[lo_i] <= blockIdx.x < block0[hi_i]
+    while (hi_i - lo_i > 1) {
+        const int mid = (lo_i + hi_i) >> 1;
+        if (block0[mid] <= (int64_t)blockIdx.x) lo_i = mid;
+        else hi_i = mid;
+    }
+    const int pl = lo_i;
+    const int2 sp = span[pl];
+    double m[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) m[k] = xforms[12 * (int64_t)pl + k];
+    double lo[3], hi[3], big = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) lo[a] = __builtin_huge_val(), hi[a] = -__builtin_huge_val();
+    const int r0 = (int)((int64_t)blockIdx.x - block0[pl]) * REPOSE_CHUNK, r1 = min(sp.y, r0 + REPOSE_CHUNK);
+    for (int r = r0 + (int)threadIdx.x; r < r1; r += BLK) {
+        const PrimRec<R> &p = prims[(int64_t)sp.x + r];
+        double g[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) g[k] = (double)p.a[k];
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+            const double px = v ? g[0] + g[3 * v] : g[0], py = v ? g[1] + g[3 * v + 1] : g[1], pz = v ? g[2] + g[3 * v + 2] : g[2];
+            big = fmax(big, fmax(fabs(px), fmax(fabs(py), fabs(pz))));
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                const double w = m[4 * a] * px + m[4 * a + 1] * py + m[4 * a + 2] * pz + m[4 * a + 3];
+                lo[a] = fmin(lo[a], w), hi[a] = fmax(hi[a], w);
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        for (int off = 32; off > 0; off >>= 1) lo[a] = fmin(lo[a], __shfl_xor(lo[a], off)), hi[a] = fmax(hi[a], __shfl_xor(hi[a], off));
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][a] = lo[a], part[threadIdx.x >> 6][3 + a] = hi[a];
+    }
+    for (int off = 32; off > 0; off >>= 1) big = fmax(big, __shfl_xor(big, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][6] = big;
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        double l = part[0][a], h = part[0][3 + a];
+        for (int w = 1; w < BLK / 64; w++) l = fmin(l, part[w][a]), h = fmax(h, part[w][3 + a]);
+        if (l <= h) {
+            atomicMin(&tight[6 * (int64_t)pl + a], d2ord(l));
+            atomicMax(&tight[6 * (int64_t)pl + 3 + a], d2ord(h));
+        }
+    } else if (threadIdx.x == 3) {
+        double b = part[0][6];
+        for (int w = 1; w < BLK / 64; w++) b = fmax(b, part[w][6]);
+        atomicMax(&maxabs[pl], d2ord(b));
+    }
+}
+
+// The tight boxes of k_placement_boxes_resident, widened until they contain the boxes a fresh scene_create computes
+// from the caller's double positions (k_placement_boxes) — k_placement_pad then pads them as it pads those, from a
+// magnitude that is no smaller.  The bound.  Let u be the unit roundoff of R (2^-24, 2^-53), p0 p1 p2 the caller's
+// vertices of a face and m the prototype's largest |coordinate| over the vertices read here (maxabs).  The record
+// holds v0 = fl(p0) and e1 = fl(fl(p1) - v0) (triangle_into), so per coordinate
+//     |v0 - p0| <= u |p0|,    |(v0 + e1) - p1| <= |fl(p1) - p1| + |e1 - (fl(p1) - v0)| <= u |p1| + u |fl(p1) - v0|,
+// with |fl(p1) - v0| <= 2 max(|p|) (1 + u) and max(|p|) <= m (1 + 4u): at most 3.1 u m; the double sum v0 + e1 read
+// above adds at most 2^-53 |v0 + e1| (nothing for float records whose exponents differ by less than 29).  delta =
+// 8 u m = m * 2^-21 (float) / m * 2^-50 (double) is twice that, which also pays for the roundings of the image of a
+// vertex and of the subtraction below (a few 2^-53 of the box's magnitude).  A vertex moved by at most delta per
+// coordinate moves coordinate a of its image by at most (|L[a][0]| + |L[a][1]| + |L[a][2]|) delta, L the transform's
+// linear part: the box grows by that on both sides.
+template <class R>
+__global__ void __launch_bounds__(BLK) k_widen_tight(long long *tight, const long long *__restrict__ maxabs, const double *__restrict__ xforms, int n) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    const double delta = ord2d(maxabs[i]) * (sizeof(R) == 4 ? 0x1p-21 : 0x1p-50);
+    const double *M = xforms + 12 * (int64_t)i;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double w = (fabs(M[4 * a]) + fabs(M[4 * a + 1]) + fabs(M[4 * a + 2])) * delta;
+        tight[6 * (int64_t)i + a] = d2ord(ord2d(tight[6 * (int64_t)i + a]) - w);
+        tight[6 * (int64_t)i + 3 + a] = d2ord(ord2d(tight[6 * (int64_t)i + 3 + a]) + w);
+    }
+}
+// The top-level tree changed its node count: the prototypes' nodes moved by `delta` nodes (k_rebase shifts their child
+// words), and so did the roots the placements enter at.  (A leaf word — a one-leaf prototype of a host-built scene —
+// names records, which stay where they are.)
+template <class R> __global__ void __launch_bounds__(BLK) k_shift_roots(InstTrace<R> *trace, int n, int32_t delta) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i < n && trace[i].root_child >= 0) trace[i].root_child += delta;
 }
 
 }  // namespace lbvh

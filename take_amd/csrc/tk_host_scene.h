@@ -49,7 +49,11 @@ template <class R> struct HostScene {
     std::vector<InstTrace<R>> inst_trace;  // two-level scenes (TakeInstance): one record per placement
     std::vector<InstShade<R>> inst_shade;
     int64_t n_blas = 0, blas_nodes = 0, blas_prims = 0;  // stats: prototype trees and their total size
-    PlacementPlan placements;  // PREP_DEVICE_BUILD of a two-level scene: what the device builder is to build
+    // what re-posing the placements of the resident scene needs to know of its prototypes (tk_build.hip:
+    // repose_two_level_device): per prototype its records in the scene's array, and the depth of the deepest tree
+    std::vector<int64_t> blas_prim_first, blas_prim_count;
+    int blas_depth = 0;
+    PlacementPlan placements;  // PREP_DEVICE_BUILD of a two-level scene: what the device builder is to build; inst_proto is kept by both builders
     EnvMap<R> env{-1, 0, 0, 1, 1, 0, 0, {R(0), R(0), R(0)}, nullptr, nullptr, nullptr, nullptr};  // pointers: view() / the uploader
     std::vector<R> env_marginal, env_conditional;
     std::vector<int32_t> env_guide_m, env_guide_c;
@@ -429,6 +433,10 @@ std::string append_prototypes(std::vector<Prototype<R, W>> &protos, const std::v
         hs.inst_trace[i].root_child = rebase_child(hs.inst_trace[i].root_child, b.node_base, b.prim_base);
     }
     hs.n_blas = (int64_t)protos.size(), hs.blas_nodes = (int64_t)(nb - top_nodes), hs.blas_prims = (int64_t)(pb - top_prims);
+    hs.blas_depth = max_depth;
+    hs.blas_prim_first.clear(), hs.blas_prim_count.clear();
+    for (const Prototype<R, W> &b : protos) hs.blas_prim_first.push_back((int64_t)b.prim_base), hs.blas_prim_count.push_back((int64_t)b.prims.size());
+    hs.placements.inst_proto.assign(inst_proto.begin(), inst_proto.end());  // (per top-level entry: per placement unless braided)
     hs.stats.n_nodes = (int64_t)nodes.size();
     hs.stats.depth += max_depth;  // the traversal stack holds both levels (+ one return marker)
     // primitive records: the top-level tree's in leaf order (prepare_scene fills them in), then each prototype's

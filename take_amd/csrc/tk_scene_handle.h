@@ -136,6 +136,8 @@ struct TakeScene {
     // progressive rendering (take_hip_render_accumulate): samples per pixel summed in `accum` so far, under which options
     int64_t acc_samples = 0;
     TakeRenderOpts acc_opts{};
+    bool acc_restart_needed = false;  // the scene changed (new transforms, a new camera): the next accumulate call has to restart
+    int64_t n_placements = 0;         // TakeSceneDesc.n_instances of a two-level scene (0: none, or flattened at creation)
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
     int instrumentation = 0;
     tk_host::SceneT<float> f;
@@ -229,5 +231,28 @@ struct DeviceBuildInputs {
 template <class R>
 int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions, int max_leaf,
                          bool compressed_ok, bool compressed_forced, bool last_side, PhaseClock &clock);
+
+// The placements of a resident two-level scene under new transforms (take_hip_scene_set_instance_transforms): the
+// top-level half of the device build entered a second time, reading only what the scene keeps — the old placement
+// records, the prototypes' records (tight boxes: k_placement_boxes_resident), the shapes' records now in leaf order.
+// d_xforms: 12 doubles per placement in device memory, complete; n = the scene's placements.  Everything is built into
+// `out` and sc stays as it is — a failure, or the failure of the other side of a mixed scene, changes nothing; commit()
+// then puts it into the scene (no allocation, nothing that fails short of a lost device).  The prototypes' trees are
+// copied, never rebuilt; the scene keeps its node format; who built it does not matter (the new top-level tree is an
+// LBVH).  Returns TAKE_OK or an error with its message: TAKE_E_INVALID naming the first singular or non-finite
+// transform, or starting with "unsupported" when the new top-level tree has fewer than two leaves or is too deep for
+// the traversal stack.
+template <class R> struct ReposeStage {
+    DevBuf<Node4<R>> nodes;      // the format the scene traverses: the new top-level tree's nodes, then the prototypes'
+    DevBuf<QNode4> qnodes;
+    DevBuf<PrimRec<R>> head;     // the shapes' records in the new leaf order (the head of sc.prims)
+    DevBuf<InstTrace<R>> inst_trace;
+    DevBuf<InstShade<R>> inst_shade;
+    float grid_lo[3] = {0, 0, 0}, grid_step[3] = {1, 1, 1};  // the new top-level tree's grid (compressed nodes)
+    int64_t n_nodes = 0;
+    int depth = 0;
+    int commit(SceneT<R> &sc);
+};
+template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n, ReposeStage<R> &out);
 
 }  // namespace tk_host
