@@ -379,6 +379,43 @@ int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t wi
  * (height * 3 * width uint16): the float framebuffer never leaves the device. */
 int take_hip_render_exr_scanlines(TakeScene *scene, const TakeRenderOpts *opts, uint16_t *out_host);
 
+/* ---- first-hit feature buffers: the auxiliary images a denoiser or compositor asks a path tracer for — albedo,
+ * shading normal, depth, coverage and the ids of the camera ray's hit — made on the device from the resident scene
+ * (one closest-hit launch + one streaming kernel per batch: no sort, no shade round, no shadow rays).
+ * Samples: the camera rays are exactly the ones take_hip_render traces for the same seed, spp, strip set and
+ * ray_epsilon (pixel key, sample index, the two jitter draws — y before x —, tmin).  samples_per_batch is honoured;
+ * max_depth, integrator and exact_bounces are ignored.
+ * Per sample that hits: albedo = the reflectance texture of the hit's material at the hit's uv (the placement's material
+ * where it overrides the prototype's; an emitter is a surface like any other; the Disney / Burley tags use their
+ * reflectance); normal = the shading normal in world space (through the transposed inverse on placements), facing
+ * as the reference's Intersection leaves it; depth = the hit's t; alpha = 1.  A sample that misses adds 0 to all
+ * four, with or without an environment map.
+ * Per pixel: the sum over the samples IN SAMPLE ORDER divided by spp — alpha-premultiplied; the normal is not
+ * re-normalised.  shape_id / material_id: those of SAMPLE 0's hit, -1 / -1 where it misses; shape ids as the trace
+ * hooks number them (placements: n_shapes + faces of the preceding placements + face).
+ * Layout: this rank's rows, compacted, row 0 = the top of the image (as take_hip_render_device); the albedo and
+ * normal planes can go straight into take_hip_pack_exr_scanlines.  f32 scenes write float, f64 and MIXED scenes
+ * double (a MIXED scene uses its f64 side: the planes are the F64 scene's bit for bit).
+ * The planes are bit-identical for any samples_per_batch and any strip sharding.
+ * The call has per-pixel sums of its own: a progressive sequence (take_hip_render_accumulate,
+ * take_hip_accumulated_samples) goes on after it as if it had not happened.  take_hip_get_counters afterwards:
+ * samples, rays_closest and the timing fields as after a render; ms_shade is the time of the feature kernel.
+ * TAKE_E_INVALID: a NULL scene, opts or buffers ("null argument", before a device is looked for), spp <= 0, a bad
+ * strip pair, all six pointers NULL; a failed call leaves the scene as it was.  Not for scene groups. */
+typedef struct TakeFeatureBuffers { /* every pointer may be NULL = not wanted */
+    void *albedo;         /* n_rows * width * 3 Real */
+    void *normal;         /* n_rows * width * 3 Real */
+    void *depth;          /* n_rows * width Real     */
+    void *alpha;          /* n_rows * width Real     */
+    int32_t *shape_id;    /* n_rows * width          */
+    int32_t *material_id; /* n_rows * width          */
+} TakeFeatureBuffers;
+/* d_out: pointers to device memory; enqueued on `stream`, returns after it has completed */
+int take_hip_render_features_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeFeatureBuffers *d_out,
+                                    void *stream);
+/* host_out: pointers to host memory */
+int take_hip_render_features(TakeScene *scene, const TakeRenderOpts *opts, const TakeFeatureBuffers *host_out);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

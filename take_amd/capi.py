@@ -28,6 +28,7 @@ EXPORTS = [
     "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
     "take_hip_scene_build_info",
     "take_hip_scene_set_instance_transforms", "take_hip_scene_set_instance_transforms_device", "take_hip_scene_set_camera",
+    "take_hip_render_features", "take_hip_render_features_device",
 ]
 
 
@@ -74,7 +75,7 @@ def lib():
         L.take_hip_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        for name, argtypes in D.SCENE_UPDATE_PROTOTYPES.items():
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -310,6 +311,34 @@ class Scene:
         o = self._opts(more_spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
         _check(lib().take_hip_render_accumulate(self.h, C.byref(o), 1 if restart else 0, C.c_void_p(d_ptr), C.c_void_p(stream or 0)))
         return int(lib().take_hip_accumulated_samples(self.h))
+
+    def render_features(self, spp, seed=0, ray_epsilon=0.0, strip_first=0, strip_stride=1, samples_per_batch=0,
+                        want=tuple(D.FEATURE_PLANES)):
+        """first-hit feature buffers (take_hip_render_features) -> {name: host array} for the names in `want`: albedo and
+        normal (rows, W, 3), depth and alpha (rows, W) in the scene's Real, shape_id and material_id (rows, W) int32; the
+        rows of this strip set, top row first; sums over the samples / spp (alpha-premultiplied), ids of sample 0"""
+        o = self._opts(spp, 0, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch)
+        n = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
+        out, bufs = {}, D.TakeFeatureBuffers()
+        for name in want:
+            per_pixel, real = D.FEATURE_PLANES[name]
+            out[name] = np.zeros((n, self.sd.width) + ((3,) if per_pixel == 3 else ()), self.dtype if real else np.int32)
+            setattr(bufs, name, out[name].ctypes.data)
+        _check(lib().take_hip_render_features(self.h, C.byref(o), C.byref(bufs)))
+        return out
+
+    def render_features_device(self, ptrs, spp, seed=0, ray_epsilon=0.0, strip_first=0, strip_stride=1, samples_per_batch=0,
+                               stream=None):
+        """the same into device memory (take_hip_render_features_device); ptrs: {name: torch device tensor or integer
+        device pointer} for the planes wanted — contiguous, of the scene's Real (int32 for the ids), sized for the rows
+        of the strip set; blocks until done"""
+        o = self._opts(spp, 0, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch)
+        bufs = D.TakeFeatureBuffers()
+        for name, p in ptrs.items():
+            if name not in D.FEATURE_PLANES:
+                raise ValueError(f"unknown feature plane {name!r}: one of {tuple(D.FEATURE_PLANES)}")
+            setattr(bufs, name, p.data_ptr() if hasattr(p, "data_ptr") else int(p))
+        _check(lib().take_hip_render_features_device(self.h, C.byref(o), C.byref(bufs), C.c_void_p(stream or 0)))
 
     def set_instance_transforms(self, xforms, stream=None):
         """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the

@@ -101,6 +101,22 @@ class TakeRenderOpts(C.Structure):
                 ("integrator", C.c_int32), ("exact_bounces", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TakeFeatureBuffers(C.Structure):
+    """take_hip_render_features*: one pointer per plane (host or device memory), None = not wanted"""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+                ("shape_id", C.c_void_p), ("material_id", C.c_void_p)]
+
+
+# the planes in the struct's order: name -> (values per pixel, True = the scene's Real / False = int32)
+FEATURE_PLANES = {"albedo": (3, True), "normal": (3, True), "depth": (1, True), "alpha": (1, True),
+                  "shape_id": (1, False), "material_id": (1, False)}
+
+FEATURE_PROTOTYPES = {
+    "take_hip_render_features_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeFeatureBuffers), C.c_void_p],
+    "take_hip_render_features": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeFeatureBuffers)],
+}
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

@@ -426,6 +426,39 @@ int take_hip_render_exr_scanlines(TakeScene *ts, const TakeRenderOpts *opts, uin
     return rc;
 }
 
+// First-hit feature buffers (albedo, shading normal, depth, coverage, ids): tk_render.hip, features_impl.
+int take_hip_render_features_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeFeatureBuffers *d_out, void *stream) {
+    if (!ts || !opts || !d_out) return fail(TAKE_E_INVALID, "null argument");
+    TAKE_ON_DEVICE(ts);
+    return render_features_scene(ts, *opts, *d_out, (hipStream_t)stream);
+}
+int take_hip_render_features(TakeScene *ts, const TakeRenderOpts *opts, const TakeFeatureBuffers *host_out) {
+    if (!ts || !opts || !host_out) return fail(TAKE_E_INVALID, "null argument");
+    TAKE_ON_DEVICE(ts);
+    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
+    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
+    if (rows < 0) return rows;
+    const size_t npix = (size_t)rows * ts->width(), real = ts->f64() ? 8 : 4;
+    // the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
+    const std::pair<void *, size_t> planes[6] = {{host_out->albedo, 3 * real}, {host_out->normal, 3 * real}, {host_out->depth, real},
+                                                 {host_out->alpha, real},      {host_out->shape_id, 4},      {host_out->material_id, 4}};
+    DevBuf<char> d_plane[6];
+    void *d_ptr[6] = {};
+    for (int k = 0; k < 6; k++) {
+        if (!planes[k].first || npix == 0) continue;
+        if (d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the feature buffers");
+        d_ptr[k] = d_plane[k].p;
+    }
+    const TakeFeatureBuffers d_out{d_ptr[0], d_ptr[1], d_ptr[2], d_ptr[3], (int32_t *)d_ptr[4], (int32_t *)d_ptr[5]};
+    TakeFeatureBuffers asked = npix == 0 ? *host_out : d_out;  // (an empty strip set: the checks run on what was asked for)
+    const int rc = render_features_scene(ts, *opts, asked, nullptr);
+    if (rc) return rc;
+    for (int k = 0; k < 6; k++)
+        if (d_ptr[k]) HIP_TRY(hipMemcpy(planes[k].first, d_ptr[k], d_plane[k].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
 int take_hip_trace_closest(TakeScene *ts, const void *rays, int64_t n, void *hits) {
     if (!ts || (n > 0 && (!rays || !hits))) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);

@@ -1,5 +1,5 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace, the kernel launchers, the wavefront
-// render loop, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h (as tk_build.hip is for
+// render loop, the feature pass, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h and tk_features.h (as tk_build.hip is for
 // tk_build_gpu.h); what tk_api.hip (scene creation, groups, the C entry points) calls here is declared in tk_scene_handle.h.  Host code only orchestrates:
 // every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "take_hip.h"
 #include "tk_scene_handle.h"
 #include "tk_kernels.h"
+#include "tk_features.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -202,20 +203,16 @@ bool camera_fused(TraceKind kind, int integrator, bool counting) {
     return enabled && TQ_GROUP == 1 && !counting && integrator == 0 && kind.nodes == NodeFormat::Q4;
 }
 
-// One round k of a batch on the records of precision RR: closest hits of the extend queue, material sort, shade,
-// shadow rays.  (Everything is enqueued; nothing waits.)  tail: an f32 round of a mixed-precision render; to_f32: see
-// ShadeArgs.  (Long because it is the round, kernel by kernel in stream order.)
+// The closest hits of round k of a batch for the extend queue (k = 0: the camera rays, made by the launch that traces
+// them where camera_fused says so).  tail: an f32 round of a mixed-precision render.
 template <class RR>
-hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound,
-                        bool tail, float *to_f32) {
+hipError_t launch_closest(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound, bool tail) {
     Timer &tm = *c.tm;
     int32_t *q = c.q;
-    int32_t *tag_count = q + Q_NUM_WORDS;
     const int cur = k & 1, next = cur ^ 1;
-    int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0), *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
-    const bool dump = !tail && c.dump >= 0 && c.dump < c.slots;  // (the slot's f64 record)
+    int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0);
     StackSpill spill{sc.spill.p, sc.spill_stride};
-    const PathIo<RR> io_ext{sc.dev.prims, st, c.queue[cur], rp.ray_eps}, io_shadow{sc.dev.prims, st, c.shadow_queue, rp.ray_eps};
+    const PathIo<RR> io_ext{sc.dev.prims, st, c.queue[cur], rp.ray_eps};
     // persistent trace grid, cut down when the queue (bounded by n_bound) cannot fill it: one block per 128 rays
     const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));
     hipError_t e;
@@ -233,6 +230,26 @@ hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, con
     }
     if (e != hipSuccess) return e;
     tm.end();
+    return hipSuccess;
+}
+
+// One round k of a batch on the records of precision RR: closest hits of the extend queue, material sort, shade,
+// shadow rays.  (Everything is enqueued; nothing waits.)  tail: an f32 round of a mixed-precision render; to_f32: see
+// ShadeArgs.  (Long because it is the round, kernel by kernel in stream order.)
+template <class RR>
+hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound,
+                        bool tail, float *to_f32) {
+    Timer &tm = *c.tm;
+    int32_t *q = c.q;
+    int32_t *tag_count = q + Q_NUM_WORDS;
+    const int cur = k & 1, next = cur ^ 1;
+    int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0), *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
+    const bool dump = !tail && c.dump >= 0 && c.dump < c.slots;  // (the slot's f64 record)
+    StackSpill spill{sc.spill.p, sc.spill_stride};
+    const PathIo<RR> io_shadow{sc.dev.prims, st, c.shadow_queue, rp.ray_eps};
+    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));  // (as launch_closest)
+    hipError_t e = launch_closest(c, sc, st, rp, k, n_bound, tail);
+    if (e != hipSuccess) return e;
     if (dump) dump_slot(st, c.dump, "after trace_closest", k, c.stream);
     const int32_t *shade_in = c.queue[cur];
     if (c.sort_materials) {
@@ -309,7 +326,9 @@ template <class R> int read_counters(const SceneT<R> &sc, TakeCounters &tc, unsi
 }
 
 // Samples per batch of a render of npix pixels (-> spb, slots = spb * npix) with the workspace for them allocated.
-template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, int &spb, int64_t &slots) {
+// render = false (the feature pass): path records and queues only — the framebuffer, which holds a progressive
+// sequence's sums, and the f32 records of a mixed scene stay as they are.
+template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, int &spb, int64_t &slots, bool render = true) {
     // paths in flight per batch: up to 512 Mi (69 GB of f32 path state + 9 GB of queues) — bigger batches keep the
     // persistent trace grid full for more of each bounce (measured on the 1M-triangle scene, spp per batch 8 / 16 / 32 /
     // 64 / 128 / 256 = 53.2 / 57.7 / 60.3 / 61.9 | 64.5 / 64.9 / 65.5 Msamples/s), and a 288 GB device has the room;
@@ -319,7 +338,7 @@ template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRend
     {
         size_t free_b = 0, total_b = 0;
         // (mixed precision: every slot has an f32 record beside its f64 one)
-        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (ts->precision == TAKE_PRECISION_MIXED ? sizeof(float) : 0)) +
+        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (render && ts->precision == TAKE_PRECISION_MIXED ? sizeof(float) : 0)) +
                                  4 * (int64_t)sizeof(int32_t);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const int64_t have = (int64_t)sc.capacity * per_path;  // already allocated by an earlier render
@@ -333,10 +352,10 @@ template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRend
     // The free-memory figure above is a snapshot: another process on the device (or another host thread) may take the
     // memory before the allocation lands.  A batch size the caller did not pin is then halved until it fits — the
     // image does not depend on it (a sample's random stream is a function of seed, pixel and sample index only).
-    const bool mixed_records = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
+    const bool mixed_records = render && sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
     for (;;) {
         slots = (int64_t)spb * npix;
-        int rc = ensure_workspace(sc, slots, npix);
+        int rc = ensure_workspace(sc, slots, render ? npix : 0);
         if (rc == TAKE_OK && mixed_records && (int64_t)ts->f.state_r.n < (int64_t)PATH_REC * slots &&
             ts->f.state_r.alloc((size_t)PATH_REC * slots) != hipSuccess) {
             ts->f.state_r.release();
@@ -419,6 +438,17 @@ void sum_timings(const TakeScene *ts, TakeCounters &tc) {
     tc.ms_other = acc[TK_OTHER];
 }
 
+// The extend queue of a new batch of n paths: the identity where the closest-hit launch of round 0 makes the camera
+// rays itself (camera_fused), else with the paths' initial records (k_generate).
+template <class R>
+void start_batch(SceneT<R> &sc, PathState<R> st, const RenderParams<R> &rp, int64_t n, int wide_grid, bool counting, Timer &tm, hipStream_t stream) {
+    tm.begin(TK_OTHER);
+    if (camera_fused(sc.trace, rp.integrator, counting)) hipLaunchKernelGGL(k_iota, dim3(wide_grid), dim3(BLOCK), 0, stream, sc.queue[0].p, n);
+    else hipLaunchKernelGGL((k_generate<R>), dim3(wide_grid), dim3(BLOCK), 0, stream, sc.dev, rp, st, sc.queue[0].p, n);
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, sc.qwords.p, (int)Q_N_EXT0, (int32_t)n);
+    tm.end();
+}
+
 // first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
 // random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
 // to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
@@ -491,11 +521,7 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRende
         rp.s0 = (int32_t)first_sample + s0;
         rp.spb = nb;
         rp32.s0 = rp.s0, rp32.spb = nb;
-        tm.begin(TK_OTHER);
-        if (camera_fused(sc.trace, rp.integrator, counting)) hipLaunchKernelGGL(k_iota, dim3(wide_grid), dim3(BLOCK), 0, stream, sc.queue[0].p, n);
-        else hipLaunchKernelGGL((k_generate<R>), dim3(wide_grid), dim3(BLOCK), 0, stream, sc.dev, rp, st, sc.queue[0].p, n);
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, q, (int)Q_N_EXT0, (int32_t)n);
-        tm.end();
+        start_batch(sc, st, rp, n, wide_grid, counting, tm, stream);
         const int rounds = o.max_depth + 2;
         int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
         bool finished = false;
@@ -532,6 +558,79 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRende
     if (std::getenv("TAKE_HIP_VERBOSE"))
         std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
                      c[C_WAIT_SLOTS], c[C_IDLE_SLOTS], c[C_NODE_VISITS], c[C_OCC_CACHE_HITS], c[C_RAYS_SHADOW]);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    tc.ms_total = ms;
+    sum_timings(ts, tc);
+    return TAKE_OK;
+}
+
+// The first-hit feature buffers of a scene (take_hip_render_features*; contract: include/take_hip.h): per batch the
+// camera + closest-hit launch of a render's round 0, then k_features over the batch's records; sums of its own
+// (sc.features), so a progressive sequence — its accumulator and sample count — goes on afterwards.  The timer files
+// k_features under the shade class: after the call ms_shade is its time.
+template <class R> int features_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &opts, const TakeFeatureBuffers &b, hipStream_t stream) {
+    const int W = sc.host.cam.width, H = sc.host.cam.height;
+    if (opts.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    const int stride = opts.strip_stride > 0 ? opts.strip_stride : 1;
+    const int first = opts.strip_first;
+    if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    const FeatureOut<R> out{(R *)b.albedo, (R *)b.normal, (R *)b.depth, (R *)b.alpha, b.shape_id, b.material_id};
+    const uint32_t want = out.want();
+    if (want == 0) return fail(TAKE_E_INVALID, "no feature buffer was asked for: every pointer of TakeFeatureBuffers is NULL");
+    TakeRenderOpts o = opts;
+    o.max_depth = 0, o.integrator = 0, o.exact_bounces = 0;  // (ignored by this pass: the camera rays do not depend on them)
+    const int n_rows = rows_of(H, first, stride, nullptr);
+    const int64_t npix = (int64_t)n_rows * W;
+    ts->counters = fresh_counters(sc);
+    if (npix == 0) return TAKE_OK;
+    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
+    int spb = 0;
+    int64_t slots = 0;
+    int rc = size_batches(ts, sc, o, npix, spb, slots, false);
+    if (rc) return rc;
+    if ((int64_t)sc.features.n < FEATURE_WORDS * npix && sc.features.alloc((size_t)FEATURE_WORDS * npix) != hipSuccess) {
+        sc.features.release();
+        return fail(TAKE_E_NOMEM, "out of device memory for the feature accumulators");
+    }
+
+    PathState<R> st{sc.state_r.p, sc.capacity};
+    RenderParams<R> rp = make_params<R>(o, W, H, n_rows, first, stride);
+    const bool counting = (ts->instrumentation & 2) != 0;
+    ts->events.reset();
+    ts->timed.clear();
+    Timer tm{ts, stream, (ts->instrumentation & 1) != 0};
+    const int wide_grid = (int)std::min<int64_t>((slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    const int pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    const RoundCtx ctx{sc.qwords.p, {sc.queue[0].p, sc.queue[1].p}, sc.shadow_queue.p, sc.sorted_queue.p, sc.sort_keys.p, nullptr, nullptr,
+                       sc.counters.p, wide_grid, &tm, counting, false, stream, -1, slots};
+    HIP_TRY(hipMemsetAsync(sc.features.p, 0, sizeof(R) * FEATURE_WORDS * npix, stream));
+    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
+    hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
+    HIP_TRY(hipEventRecord(ev_begin, stream));
+    for (int s0 = 0; s0 < o.spp; s0 += spb) {
+        const int nb = std::min(spb, o.spp - s0);
+        const int64_t n = (int64_t)nb * npix;
+        rp.s0 = s0, rp.spb = nb;
+        start_batch(sc, st, rp, n, wide_grid, counting, tm, stream);
+        HIP_TRY(launch_closest<R>(ctx, sc, st, rp, 0, n, false));
+        tm.begin(TK_SHADE);
+        hipLaunchKernelGGL((k_features<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.dev, st, sc.features.p, out, W, n_rows, nb, s0 == 0 ? 1 : 0, want);
+        tm.end();
+    }
+    tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((k_features_resolve<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.features.p, out, W, n_rows, o.spp);
+    tm.end();
+    HIP_TRY(hipEventRecord(ev_end, stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(tm.err));
+
+    unsigned long long c[C_NUM_WORDS];
+    TakeCounters &tc = ts->counters;
+    rc = read_counters(sc, tc, c);
+    if (rc) return rc;
+    tc.samples = (uint64_t)npix * (uint64_t)o.spp;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
     tc.ms_total = ms;
@@ -645,6 +744,9 @@ int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, co
         img = sc.out.p;
         return rc;
     });
+}
+int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream) {
+    return on_primary(ts, [&](auto &sc) { return features_impl(ts, sc, o, d_out, stream); });
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, hits, occ, any); });

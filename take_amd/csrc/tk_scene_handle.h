@@ -90,6 +90,7 @@ template <class R> struct SceneT {
     DevBuf<uint8_t> sort_keys;            // one key byte per queue entry (material sort)
     DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
     DevBuf<R> accum, out;
+    DevBuf<R> features;  // per-pixel sums of the feature pass (take_hip_render_features*): FEATURE_WORDS planes, its own — not accum
     DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
     DevBuf<unsigned long long> counters;
     DevBuf<unsigned long long> spill;
@@ -203,6 +204,8 @@ int rows_of(int height, int first, int stride, int32_t *rows_out);
 int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample = 0, bool keep_accum = false);
 // a render of npix pixels into the scene's own output buffer (-> img)
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img);
+// the first-hit feature buffers (include/take_hip.h: take_hip_render_features_device) into device memory
+int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
 
