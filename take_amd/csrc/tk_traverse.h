@@ -8,7 +8,10 @@
 //     determinant cull, inclusive [tmin, tmax], u/v/u+v bounds) so that t,u,v of a hit are bit-identical
 //     to the f32/f64 restatement in oracle/;
 //   * the box test is conservative (both planes widened by a few ulp), so a different tree shape cannot
-//     lose a hit the reference's tree finds; closest hit is then tree-independent up to exact ties;
+//     lose a hit the reference's tree finds; closest hit is then tree-independent up to exact ties — as long as a
+//     primitive test's t lies within those few ulp of the primitive's own box: f64 to 1e6 scene extents between ray
+//     origin and scene, f32 to about 100 (beyond, the cancellation in sphere_test / tri_test is larger than the margins:
+//     include/take_hip.h);
 //   * shadow rays stop at the first hit (scene_occluded only uses the boolean, src/scene.cpp:49-53).
 #pragma once
 
@@ -110,8 +113,18 @@ TK_HD bool box_test(const NodeChild<R> &c, Vec3<R> o, R idx, R idy, R idz, R tmi
     R t0x = (c.bmin[0] - o.x) * idx, t1x = (c.bmax[0] - o.x) * idx;
     R t0y = (c.bmin[1] - o.y) * idy, t1y = (c.bmax[1] - o.y) * idy;
     R t0z = (c.bmin[2] - o.z) * idz, t1z = (c.bmax[2] - o.z) * idz;
+    // A far plane at distance exactly 0 means the origin lies ON that plane.  For a ray that runs inside the plane (a
+    // direction component of +-0: safe_inv's 1e30 times a difference of 0 is 0, where the slab holds the whole ray) the
+    // axis must not limit the interval — an axis-parallel ray along the edge of an axis-aligned wall lost its hit here.
+    // A ray that really leaves the box at t = 0 pays a wasted visit.  (The compressed path needs no such rule: make_qgrid,
+    // tk_bvh.h, widens every child box by delta = 2^-20 grid extents before snapping it outwards, so an origin ON the
+    // geometry's own plane is strictly inside the compressed slab and the fma gives a far distance of ~delta x 1e30.)
+    auto far_plane = [](R a, R b) -> R {
+        const R f = tk_fmax(a, b);
+        return f == R(0) ? Const<R>::inf() : f;
+    };
     tn = tk_fmax(tk_fmax(tk_fmin(t0x, t1x), tk_fmin(t0y, t1y)), tk_fmax(tk_fmin(t0z, t1z), tmin));
-    R tf = tk_fmin(tk_fmin(tk_fmax(t0x, t1x), tk_fmax(t0y, t1y)), tk_fmin(tk_fmax(t0z, t1z), tbest));
+    R tf = tk_fmin(tk_fmin(far_plane(t0x, t1x), far_plane(t0y, t1y)), tk_fmin(far_plane(t0z, t1z), tbest));
     return (tn * Const<R>::BOX_SHRINK <= tf * Const<R>::BOX_GROW) && (c.child != CHILD_EMPTY);
 }
 

@@ -29,6 +29,8 @@ def hostsim():
         L.hostsim_last_error.restype = C.c_char_p
         L.hostsim_render.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.hostsim_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.hostsim_trace_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_uint64)]
         L.hostsim_check_qnodes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         _HOSTSIM = L
     return _HOSTSIM
@@ -81,6 +83,42 @@ def hostsim_trace(sd, precision, rays8, any_hit=False):
     if rc != 0:
         raise RuntimeError(hostsim().hostsim_last_error().decode())
     return hits
+
+
+def hostsim_trace_stats(sd, precision, rays8, any_hit=False, lds_levels=15, drop_from=-1, hits=False):
+    """Statistics of hostsim_trace on these rays: "max_stack" — the deepest traversal stack (entries, counted as the trace
+    kernel's single stack holds them: a prototype's entries above the top level's and the return marker); "n_nodes",
+    "depth" of the tree; "nodes", "prims", "leaves" — interior nodes visited, primitives tested, leaves visited, summed
+    over the rays; "rays_deep" — rays whose own stack went beyond `lds_levels` entries; "marker_level" — the highest
+    stack level a return marker was put at + 1 (0: no placement entered).
+    drop_from >= 0 is a deliberate fault: every entry at that level or above is lost when it is popped, as a broken spill
+    area would lose it.  hits=True: also the hit table, as a second value."""
+    desc, keep = sd.to_desc()
+    a = rays_to_abi(rays8, precision)
+    out = (C.c_uint64 * 8)()
+    table = np.zeros((a.shape[0], 4), a.dtype) if hits else None
+    rc = hostsim().hostsim_trace_stats(C.addressof(desc), precision, a.ctypes.data, a.shape[0], int(any_hit), lds_levels,
+                                       drop_from, table.ctypes.data if hits else None, out)
+    if rc != 0:
+        raise RuntimeError(hostsim().hostsim_last_error().decode())
+    st = dict(zip(["max_stack", "n_nodes", "depth", "nodes", "prims", "leaves", "rays_deep", "marker_level"], [int(x) for x in out]))
+    return (st, table) if hits else st
+
+
+def random_linear(rng, n, shear=0.4, scale=(0.4, 2.5)):
+    """n linear maps: rotation x non-uniform scale x shear"""
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q.T
+    rot = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
+                    np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
+                    np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], 1)
+    out = []
+    for k in range(n):
+        sh = np.eye(3)
+        sh[0, 1], sh[0, 2], sh[1, 2] = rng.uniform(-shear, shear, 3)
+        out.append(rot[k] @ np.diag(rng.uniform(*scale, 3)) @ sh)
+    return out
 
 
 def random_rays(n, seed, camera_fraction=0.25, bounded_fraction=0.3, tmin=1e-4):

@@ -237,6 +237,73 @@ template <class R> int trace_t(const TakeSceneDesc &desc, const void *rays_v, in
     }
     return TAKE_OK;
 }
+// The stack of hostsim_trace_stats: an ArrayStack that knows how deep the trace kernel's ONE stack is at the same point.
+// traverse() nests a second stack for the prototype of a two-level scene; the kernel (tk_trace_quad.h) goes on above the
+// entries of the top level and one return marker.  A nested stack therefore starts at the live entries of the one it
+// was created under + 1 (the marker sits at level base - 1); g_deepest is the highest entry count reached since it was
+// cleared, g_marker the highest level a return marker was put at (-1: none).
+// g_drop >= 0 is a deliberate fault for the tests' non-vacuity guards: every entry the kernel would keep at level
+// >= g_drop comes back as an empty child, i.e. is lost — what a spill area that loses its entries would do.
+struct DepthStack : ArrayStack {
+    static inline thread_local DepthStack *g_top = nullptr;
+    static inline thread_local int g_deepest = 0, g_marker = -1, g_drop = -1;
+    DepthStack *parent;
+    int base, live = 0;
+    DepthStack() : parent(g_top), base(g_top ? g_top->base + g_top->live + 1 : 0) {
+        g_top = this;
+        if (parent && base - 1 > g_marker) g_marker = base - 1;
+        if (base > g_deepest) g_deepest = base;
+    }
+    ~DepthStack() { g_top = parent; }
+    DepthStack(const DepthStack &) = delete;
+    void push(int level, int32_t c, float k) {
+        ArrayStack::push(level, c, k);
+        live = level + 1;
+        if (base + live > g_deepest) g_deepest = base + live;
+    }
+    void pop(int level, int32_t &c, float &k) {
+        ArrayStack::pop(level, c, k);
+        if (g_drop >= 0 && base + level >= g_drop) c = CHILD_EMPTY;
+        live = level;
+    }
+};
+// out[0] = deepest stack over the rays (entries, as the kernel counts them), out[1] = nodes, out[2] = depth of the tree,
+// out[3..5] = interior nodes visited, primitives tested, leaves visited over all rays (TravCount), out[6] = rays whose
+// own stack went beyond `lds_levels` entries, out[7] = highest level of a return marker + 1 (0: no placement entered).
+// hits (may be null): n x 4 Real as hostsim_trace writes them.  drop_from < 0: no fault (see DepthStack).
+template <class R>
+int trace_stats_t(const TakeSceneDesc &desc, const void *rays_v, int64_t n, int any, int lds_levels, int drop_from, void *hits_v, uint64_t *out) {
+    HostScene<R> hs;
+    g_err = prepare_scene<R>(desc, std::getenv("HOSTSIM_MAX_LEAF") ? std::atoi(std::getenv("HOSTSIM_MAX_LEAF")) : 0, 1, hs);
+    if (!g_err.empty()) return TAKE_E_INVALID;
+    DeviceScene<R> sc = hs.view();
+    const R *rays = (const R *)rays_v;  // org3 tmin dir3 tmax
+    R *hits = (R *)hits_v;
+    int deepest = 0;
+    uint64_t n_deep = 0;
+    DepthStack::g_marker = -1, DepthStack::g_drop = drop_from;
+    TravCount tc;
+    for (int64_t i = 0; i < n; i++) {
+        const R *q = rays + 8 * i;
+        RayT<R> ray = make_ray(q[0], q[1], q[2], q[4], q[5], q[6], q[3], q[7]);
+        HitT<R> hit;
+        DepthStack::g_deepest = 0;
+        {
+            DepthStack stack;
+            if (any)
+                traverse<R, true, true>(sc, ray, stack, hit, tc);
+            else
+                traverse<R, false, true>(sc, ray, stack, hit, tc);
+        }
+        deepest = std::max(deepest, DepthStack::g_deepest);
+        n_deep += DepthStack::g_deepest > lds_levels;
+        if (hits) hits[4 * i] = R(hit.shape), hits[4 * i + 1] = hit.prim >= 0 ? hit.t : R(0), hits[4 * i + 2] = hit.u, hits[4 * i + 3] = hit.v;
+    }
+    DepthStack::g_drop = -1;
+    out[0] = (uint64_t)deepest, out[1] = (uint64_t)hs.stats.n_nodes, out[2] = (uint64_t)hs.stats.depth;
+    out[3] = tc.nodes, out[4] = tc.prims, out[5] = tc.leaves, out[6] = n_deep, out[7] = (uint64_t)(DepthStack::g_marker + 1);
+    return TAKE_OK;
+}
 // Compressed nodes of the f32 scene against the full-width ones they were made from, in exact (double) arithmetic.
 // out[0] = child slots checked, out[1] = slots whose decoded box does NOT contain the true box widened by the
 // builder's slack (must be 0), out[2] = child words that differ (must be 0), out[3] = 1e6 * surface-area inflation,
@@ -324,5 +391,12 @@ int hostsim_check_qnodes(const TakeSceneDesc *desc, int64_t *out) {
 int hostsim_trace(const TakeSceneDesc *desc, int precision, const void *rays, int64_t n, void *hits, int any) {
     return precision == TAKE_PRECISION_F64 ? trace_t<double>(*desc, rays, n, hits, any)
                                            : trace_t<float>(*desc, rays, n, hits, any);
+}
+// the same rays with the statistics of their traversal: out = 8 words (trace_stats_t); hits may be null; drop_from >= 0
+// loses every stack entry at that level or above (the tests' stand-in for a broken spill area), < 0 changes nothing
+int hostsim_trace_stats(const TakeSceneDesc *desc, int precision, const void *rays, int64_t n, int any, int lds_levels, int drop_from,
+                        void *hits, uint64_t *out) {
+    return precision == TAKE_PRECISION_F64 ? trace_stats_t<double>(*desc, rays, n, any, lds_levels, drop_from, hits, out)
+                                           : trace_stats_t<float>(*desc, rays, n, any, lds_levels, drop_from, hits, out);
 }
 }

@@ -10,7 +10,7 @@ import time
 import numpy as np
 import pytest
 
-from helpers import random_rays, rays_to_abi, rmse
+from helpers import random_linear, random_rays, rays_to_abi, rmse
 from take_amd import capi, scenes
 from take_amd import cdefs as D
 from take_amd.scene import SceneData
@@ -114,22 +114,6 @@ def sheared_grid():
     lp, li, ln, lu = scenes._quad((0, 1.5, 0), (0.4, 0, 0), (0, 0, 0.4), (0, -1, 0))
     sd.add_mesh(lp, li, grey, normals=ln, uvs=lu, emission=(12.0, 12.0, 12.0))
     return sd
-
-
-def random_linear(rng, n, shear=0.4):
-    """n linear maps: rotation x non-uniform scale x shear"""
-    q = rng.normal(size=(n, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    w, x, y, z = q.T
-    rot = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
-                    np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
-                    np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], 1)
-    out = []
-    for k in range(n):
-        sh = np.eye(3)
-        sh[0, 1], sh[0, 2], sh[1, 2] = rng.uniform(-shear, shear, 3)
-        out.append(rot[k] @ np.diag(rng.uniform(0.4, 2.5, 3)) @ sh)
-    return out
 
 
 def everything_scene(offset=(0.0, 0.0, 0.0), res=64):
