@@ -475,6 +475,14 @@ int take_hip_set_instrumentation(TakeScene *scene, int32_t flags);
 int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int64_t n, int32_t in_cols,
                          const double *rnd, double *out, int32_t out_cols);
 
+/* Test hook: the environment-map functions of the shade kernel on the rows of `in`, against the tables and guide
+ * tables resident in `scene` (what its renders read).  side: TAKE_PRECISION_F32 / _F64 — which resident side (a MIXED
+ * scene has both).  kind 0: in = (u1, u2) per row, the two uniform draws of one light sample -> out = 8 columns:
+ * dir[3], radiance[3], pdf (solid angle), y * width + x of the texel the CDF searches found.  kind 1: in = dir[3] per
+ * row -> out = 5 columns: radiance[3], pdf, y * width + x of the texel the direction falls into.  f32 sides round the
+ * inputs to float.  TAKE_E_INVALID: a side the scene does not have, a scene without a map, NULL arguments. */
+int take_hip_debug_env(TakeScene *scene, int32_t side, int32_t kind, const double *in, int64_t n, double *out);
+
 /* ---- PLY -> device mesh arrays ------------------------------------------------------------
  * Replaces src/parse/parse_ply.cpp:9-123 (`TriangleMesh parse_ply(filename, to_world)`) for binary_little_endian
  * files: the host reads only the text header, the binary body goes to HBM as it lies in the file and kernels do what

@@ -367,7 +367,7 @@ template <class R> inline V3<R> env_eval(const Scene<R> &sc, const V3<R> &d, R &
     const R u = std::atan2(d.z, d.x) * K<R>::INVTWOPI + R(0.5);
     const int x = std::clamp((int)std::floor(u * R(w)), 0, w - 1);
     const int y = std::clamp((int)std::floor(theta * K<R>::INVPI * R(h)), 0, h - 1);
-    pdf = env_density(sc, x, y, std::sqrt(std::fmax(R(0), R(1) - cy * cy)));
+    pdf = env_density(sc, x, y, std::sqrt(std::fmax(R(0), (R(1) - cy) * (R(1) + cy))));
     return env_radiance(sc, x, y);
 }
 template <class R> inline int cdf_interval(const R *cdf, int n, R xi) {  // largest i < n with cdf[i] <= xi
@@ -388,10 +388,11 @@ template <class R, class Rng> inline EnvSample<R> env_sample(const Scene<R> &sc,
     const int x = cdf_interval(row, w, u2);
     const R m0 = sc.env.marginal[y], m1 = sc.env.marginal[y + 1], c0 = row[x], c1 = row[x + 1];
     const R dv = m1 > m0 ? (u1 - m0) / (m1 - m0) : R(0.5), du = c1 > c0 ? (u2 - c0) / (c1 - c0) : R(0.5);
-    const R theta = (R(y) + dv) / R(h) * K<R>::PI;
+    const bool south = 2 * y >= h;  // the polar angle is measured from the nearer pole
+    const R theta = (south ? R(h - 1 - y) + (R(1) - dv) : R(y) + dv) / R(h) * K<R>::PI;
     const R phi = ((R(x) + du) / R(w) - R(0.5)) * K<R>::TWOPI;
-    const R st = std::sin(theta);
-    return {V3<R>{st * std::cos(phi), std::cos(theta), st * std::sin(phi)}, env_radiance(sc, x, y), env_density(sc, x, y, st)};
+    const R st = std::sin(theta), ct = std::cos(theta);
+    return {V3<R>{st * std::cos(phi), south ? -ct : ct, st * std::sin(phi)}, env_radiance(sc, x, y), env_density(sc, x, y, st)};
 }
 
 // ------------------------------------------------------------------ src/bbox.h:18-55

@@ -20,7 +20,7 @@ EXPORTS = [
     "take_hip_scene_destroy", "take_hip_render", "take_hip_render_device", "take_hip_render_rows",
     "take_hip_render_accumulate", "take_hip_accumulated_samples",
     "take_hip_trace_closest", "take_hip_trace_any", "take_hip_trace_closest_device", "take_hip_get_counters",
-    "take_hip_set_instrumentation", "take_hip_scene_stats", "take_hip_debug_table",
+    "take_hip_set_instrumentation", "take_hip_scene_stats", "take_hip_debug_table", "take_hip_debug_env",
     "take_hip_group_create", "take_hip_group_destroy", "take_hip_group_render", "take_hip_group_render_device",
     "take_hip_group_size", "take_hip_group_get_counters", "take_hip_pack_exr_scanlines", "take_hip_render_exr_scanlines",
     "take_hip_ply_layout", "take_hip_mesh_from_ply", "take_hip_mesh_from_ply_file",
@@ -75,6 +75,7 @@ def lib():
         L.take_hip_scene_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -401,6 +402,17 @@ class Scene:
         nn, npr, dep, by = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
         _check(lib().take_hip_scene_stats(self.h, C.byref(nn), C.byref(npr), C.byref(dep), C.byref(by)))
         return {"n_nodes": nn.value, "n_prims": npr.value, "depth": dep.value, "device_bytes": by.value}
+
+    def debug_env(self, kind, inp, side=None):
+        """the shade kernel's environment-map functions on this scene's resident tables (take_hip_debug_env, a test hook).
+        kind 0: (n, 2) draws (u1, u2) -> (n, 8) dir[3], radiance[3], pdf, texel y * width + x; kind 1: (n, 3) directions
+        -> (n, 5) radiance[3], pdf, texel.  side: TAKE_PRECISION_F32 / _F64 (default: the scene's own, F64 for MIXED)"""
+        if side is None:
+            side = D.TAKE_PRECISION_F32 if self.precision == D.TAKE_PRECISION_F32 else D.TAKE_PRECISION_F64
+        inp = np.ascontiguousarray(inp, np.float64).reshape(-1, 3 if kind else 2)
+        out = np.zeros((inp.shape[0], 5 if kind else 8), np.float64)
+        _check(lib().take_hip_debug_env(self.h, int(side), int(kind), inp.ctypes.data, inp.shape[0], out.ctypes.data))
+        return out
 
     def build_info(self):
         """who built the trees: {"f32": builder, "f64": builder}, each TAKE_BUILDER_DEVICE_LBVH, TAKE_BUILDER_HOST_SAH

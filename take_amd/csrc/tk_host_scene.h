@@ -721,7 +721,7 @@ template <class R> inline void shape_record(const TakeSceneDesc &d, int64_t i, c
 // Sampling tables of an environment map (EnvMap, tk_scene.h), in double: per texel f = luminance * sin(theta of the
 // row centre) with luminance = 0.2126 r + 0.7152 g + 0.0722 b (negatives count as 0); cond[y][x] = sum of the row's
 // f left of x / row sum (x / width for an all-black row), marg[y] = sum of the row sums above y / total.  Both
-// start at 0 and end at exactly 1.  (The CPU checker under tests restates this recipe independently.)
+// start at 0 and end at exactly 1.  (tests/env_ref.py restates this recipe independently, in numpy.)
 inline bool env_tables(const double *rgb, int w, int h, std::vector<double> &marg, std::vector<double> &cond) {
     const double PI_D = 3.14159265358979323846;
     marg.assign((size_t)h + 1, 0.0);

@@ -549,4 +549,14 @@ k_debug_table(DeviceScene<R> sc, int kind, const double *__restrict__ in, const 
         out[4 * r + 3] = (double)random_real<R>(rng);
     }
 }
+
+// ---- take_hip_debug_env: the environment-map functions of tk_shade.h on a resident scene's own tables and guides.
+// kind 0: in = (u1, u2) per row, the two draws env_sample takes -> dir[3], radiance[3], pdf, y * width + x of the texel
+// its searches found; kind 1: in = dir[3] per row -> env_eval's radiance[3], pdf, y * width + x of env_lookup's texel
+// (debug_env_row, tk_shade.h: one lane per row).
+template <class R>
+__global__ void __launch_bounds__(BLOCK) k_debug_env(DeviceScene<R> sc, int kind, const double *__restrict__ in, int64_t n, double *out) {
+    const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (r < n) debug_env_row(sc, kind, in, r, out);
+}
 }  // namespace tk

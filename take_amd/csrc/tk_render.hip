@@ -690,6 +690,21 @@ template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays
     return TAKE_OK;
 }
 
+// take_hip_debug_env on one side of a scene (n <= 2^31 rows, checked by the caller: the grid size fits an unsigned)
+template <class R> int debug_env_side(SceneT<R> &sc, int kind, const double *in, int64_t n, double *out) {
+    if (sc.host.env.light < 0) return fail(TAKE_E_INVALID, "the scene has no environment map");
+    if (n == 0) return TAKE_OK;
+    DevBuf<double> d_in, d_out;
+    if (d_in.alloc((size_t)n * ENV_IN_COLS[kind]) != hipSuccess || d_out.alloc((size_t)n * ENV_OUT_COLS[kind]) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "debug env allocation failed");
+    HIP_TRY(hipMemcpy(d_in.p, in, d_in.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out.p, 0, d_out.bytes()));
+    hipLaunchKernelGGL((k_debug_env<R>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, nullptr, sc.dev, kind, d_in.p, n, d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
 }  // namespace
 
 namespace tk_host {
@@ -816,6 +831,18 @@ int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int6
     if (hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(TAKE_E_DEVICE, "debug table download failed");
     return TAKE_OK;
+}
+
+int take_hip_debug_env(TakeScene *ts, int32_t side, int32_t kind, const double *in, int64_t n, double *out) {
+    if (!ts || !in || !out || n < 0) return fail(TAKE_E_INVALID, "null argument");
+    if (n > ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "more than 2^31 rows");
+    if (kind != ENV_SAMPLE && kind != ENV_EVAL) return fail(TAKE_E_INVALID, "unknown kind");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    if (!(side == TAKE_PRECISION_F32 ? ts->precision != TAKE_PRECISION_F64 : side == TAKE_PRECISION_F64 && ts->precision != TAKE_PRECISION_F32))
+        return fail(TAKE_E_INVALID, "the scene has no such side");
+    TAKE_ON_DEVICE(ts);
+    return side == TAKE_PRECISION_F64 ? debug_env_side(ts->d, kind, in, n, out) : debug_env_side(ts->f, kind, in, n, out);
 }
 
 }  // extern "C"

@@ -138,7 +138,7 @@ template <class R> TK_HD void env_lookup(const DeviceScene<R> &sc, Vec3<R> d, in
     y = (int)tk_floor(theta * Const<R>::INVPI * R(sc.env.height));
     x = x < 0 ? 0 : (x >= sc.env.width ? sc.env.width - 1 : x);
     y = y < 0 ? 0 : (y >= sc.env.height ? sc.env.height - 1 : y);
-    sin_theta = tk_sqrt(tk_fmax(R(0), R(1) - cy * cy));
+    sin_theta = tk_sqrt(tk_fmax(R(0), (R(1) - cy) * (R(1) + cy)));  // (1 - cy * cy cancels near the poles; 1 - cy is exact there)
 }
 // radiance arriving from direction d, and the density with which env_sample would have produced d
 template <class R> TK_HD Vec3<R> env_eval(const DeviceScene<R> &sc, Vec3<R> d, R &pdf) {
@@ -171,22 +171,54 @@ template <class R> TK_HD int cdf_find_guided(const R *cdf, int n, const int32_t 
     }
     return lo;
 }
-template <class R, class G> TK_HD EnvSample<R> env_sample(const DeviceScene<R> &sc, G &rng) {
+// (x, y): the texel the two searches found — what take_hip_debug_env reports
+template <class R, class G> TK_HD EnvSample<R> env_sample(const DeviceScene<R> &sc, G &rng, int &x, int &y) {
     const R u1 = random_real<R>(rng);
     const R u2 = random_real<R>(rng);
-    const int y = cdf_find_guided(sc.env.marginal, sc.env.height, sc.env.guide_m, sc.env.n_guide_m, u1);
+    y = cdf_find_guided(sc.env.marginal, sc.env.height, sc.env.guide_m, sc.env.n_guide_m, u1);
     const R *row = sc.env.conditional + (int64_t)y * (sc.env.width + 1);
-    const int x = cdf_find_guided(row, sc.env.width, sc.env.guide_c + (int64_t)y * (sc.env.n_guide_c + 1), sc.env.n_guide_c, u2);
+    x = cdf_find_guided(row, sc.env.width, sc.env.guide_c + (int64_t)y * (sc.env.n_guide_c + 1), sc.env.n_guide_c, u2);
     const R m0 = sc.env.marginal[y], m1 = sc.env.marginal[y + 1], c0 = row[x], c1 = row[x + 1];
     const R dv = m1 > m0 ? (u1 - m0) / (m1 - m0) : R(0.5), du = c1 > c0 ? (u2 - c0) / (c1 - c0) : R(0.5);
-    const R theta = (R(y) + dv) / R(sc.env.height) * Const<R>::PI;
+    // the polar angle from the nearer pole: sin(theta) of a theta rounded next to pi has lost its leading digits
+    const bool south = 2 * y >= sc.env.height;
+    const R theta = (south ? R(sc.env.height - 1 - y) + (R(1) - dv) : R(y) + dv) / R(sc.env.height) * Const<R>::PI;
     const R phi = ((R(x) + du) / R(sc.env.width) - R(0.5)) * Const<R>::TWOPI;
-    const R st = tk_sin(theta);
+    const R st = tk_sin(theta), ct = tk_cos(theta);
     EnvSample<R> s;
-    s.dir = Vec3<R>{st * tk_cos(phi), tk_cos(theta), st * tk_sin(phi)};
+    s.dir = Vec3<R>{st * tk_cos(phi), south ? -ct : ct, st * tk_sin(phi)};
     s.radiance = env_texel(sc, x, y);
     s.pdf = env_texel_pdf(sc, x, y, st);
     return s;
+}
+template <class R, class G> TK_HD EnvSample<R> env_sample(const DeviceScene<R> &sc, G &rng) {
+    int x, y;
+    return env_sample(sc, rng, x, y);
+}
+// one row of the test hook take_hip_debug_env (tk_kernels.h: k_debug_env; tests/hostsim runs the same on the host)
+enum DebugEnv { ENV_SAMPLE = 0, ENV_EVAL = 1 };
+constexpr int ENV_IN_COLS[2] = {2, 3}, ENV_OUT_COLS[2] = {8, 5};
+template <class R> TK_HD void debug_env_row(const DeviceScene<R> &sc, int kind, const double *in, int64_t r, double *out) {
+    auto put = [](double *o, Vec3<R> v) { o[0] = (double)v.x, o[1] = (double)v.y, o[2] = (double)v.z; };
+    int x, y;
+    if (kind == ENV_SAMPLE) {
+        TableRng rng{in + 2 * r, 0};
+        double *o = out + 8 * r;
+        const EnvSample<R> s = env_sample(sc, rng, x, y);
+        put(o, s.dir);
+        put(o + 3, s.radiance);
+        o[6] = (double)s.pdf;
+        o[7] = (double)((int64_t)y * sc.env.width + x);
+    } else {
+        const double *p = in + 3 * r;
+        double *o = out + 5 * r;
+        const Vec3<R> d{R(p[0]), R(p[1]), R(p[2])};
+        R pdf, st;
+        put(o, env_eval(sc, d, pdf));
+        env_lookup(sc, d, x, y, st);
+        o[3] = (double)pdf;
+        o[4] = (double)((int64_t)y * sc.env.width + x);
+    }
 }
 
 // ---- materials

@@ -32,6 +32,7 @@ def hostsim():
         L.hostsim_trace_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_uint64)]
         L.hostsim_check_qnodes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.hostsim_env.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         _HOSTSIM = L
     return _HOSTSIM
 
@@ -103,6 +104,19 @@ def hostsim_trace_stats(sd, precision, rays8, any_hit=False, lds_levels=15, drop
         raise RuntimeError(hostsim().hostsim_last_error().decode())
     st = dict(zip(["max_stack", "n_nodes", "depth", "nodes", "prims", "leaves", "rays_deep", "marker_level"], [int(x) for x in out]))
     return (st, table) if hits else st
+
+
+def hostsim_env(sd, precision, kind, inp):
+    """the device's environment-map functions on the host, rows as take_hip_debug_env's (capi.Scene.debug_env):
+    kind 0 (n, 2) draws -> (n, 8) dir[3], radiance[3], pdf, texel; kind 1 (n, 3) directions -> (n, 5) radiance[3], pdf,
+    texel.  precision 0 f32, 1 f64"""
+    desc, keep = sd.to_desc()
+    inp = np.ascontiguousarray(inp, np.float64).reshape(-1, 3 if kind else 2)
+    out = np.zeros((inp.shape[0], 5 if kind else 8), np.float64)
+    rc = hostsim().hostsim_env(C.addressof(desc), precision, kind, inp.ctypes.data, inp.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(hostsim().hostsim_last_error().decode())
+    return out
 
 
 def random_linear(rng, n, shear=0.4, scale=(0.4, 2.5)):

@@ -329,6 +329,16 @@ static void check_qnodes_w(const HostScene<float> &hs, const std::vector<NodeW<f
             if (!ok) out[1]++;
         }
 }
+// take_hip_debug_env's rows (tk_shade.h: debug_env_row) on the scene as prepare_scene leaves it
+template <class R> int env_t(const TakeSceneDesc &desc, int kind, const double *in, int64_t n, double *out) {
+    HostScene<R> hs;
+    g_err = prepare_scene<R>(desc, 0, 1, hs);
+    if (g_err.empty() && hs.env.light < 0) g_err = "the scene has no environment map";
+    if (!g_err.empty()) return TAKE_E_INVALID;
+    const DeviceScene<R> sc = hs.view();
+    for (int64_t r = 0; r < n; r++) debug_env_row(sc, kind, in, r, out);
+    return TAKE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -398,5 +408,10 @@ int hostsim_trace_stats(const TakeSceneDesc *desc, int precision, const void *ra
                         void *hits, uint64_t *out) {
     return precision == TAKE_PRECISION_F64 ? trace_stats_t<double>(*desc, rays, n, any, lds_levels, drop_from, hits, out)
                                            : trace_stats_t<float>(*desc, rays, n, any, lds_levels, drop_from, hits, out);
+}
+// the environment-map functions on rows of draws (kind 0) or directions (kind 1): columns as take_hip_debug_env's
+int hostsim_env(const TakeSceneDesc *desc, int precision, int kind, const double *in, int64_t n, double *out) {
+    if (!desc || !in || !out || (kind != 0 && kind != 1)) return TAKE_E_INVALID;
+    return precision == TAKE_PRECISION_F64 ? env_t<double>(*desc, kind, in, n, out) : env_t<float>(*desc, kind, in, n, out);
 }
 }

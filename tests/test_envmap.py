@@ -22,15 +22,24 @@ def env_soup(n=300, res=32, env=(64, 32)):
     return scenes.soup_scene(n, res, res, spp=4, envmap=env)
 
 
-def plane_under_sky(c, rho, use_env):
-    """a big diffuse quad seen from above under a uniform sky; background = c when the map is not used"""
-    sd = SceneData(width=24, height=24, lookfrom=(0.0, 2.0, 0.0), lookat=(0.0, 0.0, 0.0), up=(0.0, 0.0, -1.0), vfov=30.0,
+def plane_under_sky(c, rho, use_env, img=None, scale=(1.0, 1.0, 1.0), normal=(0.0, 1.0, 0.0), res=24):
+    """a big diffuse quad through the origin with the given normal, seen along -normal from two units away, under a
+    uniform sky of radiance c or under the map `img`; background = c when the map is not used.  Every point the camera
+    sees has the whole hemisphere about `normal` open, so each pixel's expectation is rho / pi * irradiance(normal)"""
+    n = np.asarray(normal, np.float64)
+    n = n / np.linalg.norm(n)
+    e = np.array([0.0, 0.0, 1.0]) if abs(n[0]) > 0.9 else np.array([1.0, 0.0, 0.0])
+    t1 = e - (e @ n) * n
+    t1 = t1 / np.linalg.norm(t1)
+    t2 = np.cross(n, t1)  # t1 x t2 = n: the quad faces the camera
+    sd = SceneData(width=res, height=res, lookfrom=tuple(float(a) for a in 2.0 * n), lookat=(0.0, 0.0, 0.0),
+                   up=tuple(float(a) for a in t2), vfov=30.0,
                    background=(0.0, 0.0, 0.0) if use_env else (c, c, c), spp=64, max_depth=3)
     m = sd.add_material(D.MAT_DIFFUSE, (rho, rho, rho))
-    pos, idx, nrm, uv = scenes._quad((0, 0, 0), (50, 0, 0), (0, 0, -50), (0, 1, 0))
+    pos, idx, nrm, uv = scenes._quad((0, 0, 0), 50.0 * t1, 50.0 * t2, n)
     sd.add_mesh(pos, idx, m, normals=nrm, uvs=uv)
     if use_env:
-        sd.add_envmap(np.full((16, 32, 3), c))
+        sd.add_envmap(np.full((16, 32, 3), c) if img is None else np.array(img), scale=scale)
     return sd
 
 
