@@ -483,6 +483,31 @@ int take_hip_debug_table(int32_t kind, int32_t precision, const double *in, int6
  * inputs to float.  TAKE_E_INVALID: a side the scene does not have, a scene without a map, NULL arguments. */
 int take_hip_debug_env(TakeScene *scene, int32_t side, int32_t kind, const double *in, int64_t n, double *out);
 
+/* Test hook (new symbols of ABI version 5; no struct changed): the acceleration structure of one resident side of a
+ * scene, copied from device memory as the trace kernels read it — whoever built it, and after every
+ * take_hip_scene_set_instance_transforms.  side: TAKE_PRECISION_F32 / _F64 (a MIXED scene has both).
+ * take_hip_debug_tree_info says what there is; take_hip_debug_tree copies n_nodes * node_bytes bytes of nodes,
+ * n_prims * prim_bytes bytes of primitive records (leaf order; in a two-level scene the shapes' first, then each
+ * prototype's) and n_instances * inst_bytes bytes of placement records into host buffers the caller sized from the
+ * info (inst_trace may be NULL for a scene without placements).  The layouts are those of take_amd/csrc/tk_scene.h:
+ * node_format 0 = full-width 4-wide nodes of the side's Real (four slots of bmin[3], bmax[3], child word, pad),
+ * 1 = 64-byte compressed 4-wide nodes, 2 = 128-byte compressed 8-wide nodes (slots of q[3] = lo | hi << 16, child word);
+ * the records are PrimRec<Real> and InstTrace<Real>.  grid_lo / grid_step: the grid of the top-level tree's compressed
+ * nodes (a prototype's own grid is in its placements' records).
+ * TAKE_E_INVALID: NULL arguments ("null argument", before a device is looked for), a side the scene does not have. */
+typedef struct TakeDebugTreeInfo {
+    int32_t node_format; /* 0 full width, 1 compressed 4-wide, 2 compressed 8-wide */
+    int32_t node_width;  /* slots per node: 4 or 8 */
+    int32_t two_level;   /* 1: the scene has placements (instance words, prototype trees behind the top-level tree) */
+    int32_t root_child;  /* child word of the root */
+    int32_t real_bytes;  /* 4 or 8: the side's Real */
+    int32_t node_bytes, prim_bytes, inst_bytes; /* element sizes */
+    int64_t n_nodes, n_prims, n_instances;
+    float grid_lo[3], grid_step[3];
+} TakeDebugTreeInfo;
+int take_hip_debug_tree_info(const TakeScene *scene, int32_t side, TakeDebugTreeInfo *info);
+int take_hip_debug_tree(const TakeScene *scene, int32_t side, void *nodes, void *prims, void *inst_trace);
+
 /* ---- PLY -> device mesh arrays ------------------------------------------------------------
  * Replaces src/parse/parse_ply.cpp:9-123 (`TriangleMesh parse_ply(filename, to_world)`) for binary_little_endian
  * files: the host reads only the text header, the binary body goes to HBM as it lies in the file and kernels do what

@@ -29,6 +29,7 @@ EXPORTS = [
     "take_hip_scene_build_info",
     "take_hip_scene_set_instance_transforms", "take_hip_scene_set_instance_transforms_device", "take_hip_scene_set_camera",
     "take_hip_render_features", "take_hip_render_features_device",
+    "take_hip_debug_tree_info", "take_hip_debug_tree",
 ]
 
 
@@ -76,7 +77,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -413,6 +414,21 @@ class Scene:
         out = np.zeros((inp.shape[0], 5 if kind else 8), np.float64)
         _check(lib().take_hip_debug_env(self.h, int(side), int(kind), inp.ctypes.data, inp.shape[0], out.ctypes.data))
         return out
+
+    def debug_tree(self, side=None):
+        """the resident tree of one side, read back from device memory as the trace kernels read it (take_hip_debug_tree,
+        a test hook): a dict of the info's values (node_format, node_width, two_level, root_child, real_bytes, n_nodes,
+        n_prims, n_instances, grid_lo, grid_step) and the numpy structured arrays "nodes", "prims", "inst_trace"
+        (cdefs.debug_tree_dtypes).  side: TAKE_PRECISION_F32 / _F64 (default: the scene's own, F64 for MIXED)"""
+        if side is None:
+            side = D.TAKE_PRECISION_F32 if self.precision == D.TAKE_PRECISION_F32 else D.TAKE_PRECISION_F64
+        info = D.TakeDebugTreeInfo()
+        _check(lib().take_hip_debug_tree_info(self.h, int(side), C.byref(info)))
+        node_t, prim_t, inst_t = D.debug_tree_dtypes(info)
+        # (one spare element: a buffer is never NULL, an empty array is still an argument)
+        nodes, prims, inst = np.zeros(info.n_nodes + 1, node_t), np.zeros(info.n_prims + 1, prim_t), np.zeros(info.n_instances + 1, inst_t)
+        _check(lib().take_hip_debug_tree(self.h, int(side), nodes.ctypes.data, prims.ctypes.data, inst.ctypes.data))
+        return D.debug_tree_result(info, nodes[:-1], prims[:-1], inst[:-1])
 
     def build_info(self):
         """who built the trees: {"f32": builder, "f64": builder}, each TAKE_BUILDER_DEVICE_LBVH, TAKE_BUILDER_HOST_SAH

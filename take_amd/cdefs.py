@@ -150,3 +150,48 @@ class TakeCounters(C.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TakeDebugTreeInfo(C.Structure):
+    _fields_ = [("node_format", C.c_int32), ("node_width", C.c_int32), ("two_level", C.c_int32), ("root_child", C.c_int32),
+                ("real_bytes", C.c_int32), ("node_bytes", C.c_int32), ("prim_bytes", C.c_int32), ("inst_bytes", C.c_int32),
+                ("n_nodes", C.c_int64), ("n_prims", C.c_int64), ("n_instances", C.c_int64),
+                ("grid_lo", c_float3), ("grid_step", c_float3)]
+
+
+# the test hook that reads a resident tree back (include/take_hip.h: take_hip_debug_tree)
+DEBUG_TREE_PROTOTYPES = {
+    "take_hip_debug_tree_info": [C.c_void_p, C.c_int32, C.POINTER(TakeDebugTreeInfo)],
+    "take_hip_debug_tree": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+NODE_FORMAT_WIDE, NODE_FORMAT_Q4, NODE_FORMAT_Q8 = 0, 1, 2
+
+
+def debug_tree_dtypes(info):
+    """numpy dtypes of the arrays take_hip_debug_tree fills, from its info (the layouts of take_amd/csrc/tk_scene.h:
+    NodeW<Real, 4> / QNodeW<W>, PrimRec<Real>, InstTrace<Real>) -> (node, prim, inst)"""
+    import numpy as np
+
+    real = "<f4" if info.real_bytes == 4 else "<f8"
+    rb, w = info.real_bytes, info.node_width
+    if info.node_format == NODE_FORMAT_WIDE:
+        slot = np.dtype({"names": ["bmin", "bmax", "child", "pad"], "formats": [(real, 3), (real, 3), "<i4", "<i4"],
+                         "offsets": [0, 3 * rb, 6 * rb, 6 * rb + 4], "itemsize": 32 if rb == 4 else 64})
+    else:
+        slot = np.dtype([("q", "<u4", 3), ("child", "<i4")])
+    node = np.dtype([("c", slot, w)])
+    prim = np.dtype({"names": ["a", "shape_id", "meta", "material", "area_light", "nidx", "mesh"],
+                     "formats": [(real, 9)] + ["<i4"] * 6, "offsets": [0] + [9 * rb + 4 * k for k in range(6)],
+                     "itemsize": 64 if rb == 4 else 96})
+    inst = np.dtype({"names": ["inv", "grid_lo", "grid_step", "root_child"], "formats": [(real, 12), ("<f4", 3), ("<f4", 3), "<i4"],
+                     "offsets": [0, 12 * rb, 12 * rb + 12, 12 * rb + 24], "itemsize": 80 if rb == 4 else 128})
+    assert (node.itemsize, prim.itemsize, inst.itemsize) == (info.node_bytes, info.prim_bytes, info.inst_bytes), "layout of the tree hook changed"
+    return node, prim, inst
+
+
+def debug_tree_result(info, nodes, prims, inst):
+    """what Scene.debug_tree and the tests' host twin return: the info as plain values and the three structured arrays"""
+    return {"node_format": int(info.node_format), "node_width": int(info.node_width), "two_level": bool(info.two_level),
+            "root_child": int(info.root_child), "real_bytes": int(info.real_bytes), "n_nodes": int(info.n_nodes),
+            "n_prims": int(info.n_prims), "n_instances": int(info.n_instances), "grid_lo": [float(x) for x in info.grid_lo],
+            "grid_step": [float(x) for x in info.grid_step], "nodes": nodes, "prims": prims, "inst_trace": inst}

@@ -803,3 +803,55 @@ int take_hip_scene_build_info(const TakeScene *ts, int32_t *f32_builder, int32_t
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ test hook: the resident tree
+namespace {
+// what one side keeps in device memory of its tree: counts and sizes of the arrays the trace kernels read (sc.dev and
+// the device buffers; nothing of sc.host)
+template <class R> TakeDebugTreeInfo debug_tree_info(const SceneT<R> &sc) {
+    TakeDebugTreeInfo o{};
+    o.node_format = sc.trace.nodes == NodeFormat::Q8 ? 2 : (sc.trace.nodes == NodeFormat::Q4 ? 1 : 0);
+    o.node_width = sc.trace.nodes == NodeFormat::Q8 ? 8 : 4;
+    o.two_level = sc.trace.two_level ? 1 : 0;
+    o.root_child = sc.dev.root_child;
+    o.real_bytes = (int32_t)sizeof(R);
+    o.node_bytes = (int32_t)node_bytes<R>(sc.trace.nodes), o.prim_bytes = (int32_t)sizeof(PrimRec<R>), o.inst_bytes = (int32_t)sizeof(InstTrace<R>);
+    o.n_nodes = sc.dev.n_nodes, o.n_prims = (int64_t)sc.prims.n, o.n_instances = (int64_t)sc.inst_trace.n;
+    for (int a = 0; a < 3; a++) o.grid_lo[a] = sc.dev.grid_lo[a], o.grid_step[a] = sc.dev.grid_step[a];
+    return o;
+}
+template <class R> int debug_tree_copy(const SceneT<R> &sc, void *nodes, void *prims, void *inst_trace) {
+    const TakeDebugTreeInfo o = debug_tree_info(sc);
+    const void *d_nodes = sc.dev.qnodes8 ? (const void *)sc.dev.qnodes8 : (sc.dev.qnodes ? (const void *)sc.dev.qnodes : (const void *)sc.dev.nodes);
+    if ((o.n_nodes > 0 && !nodes) || (o.n_prims > 0 && !prims) || (o.n_instances > 0 && !inst_trace)) return fail(TAKE_E_INVALID, "null argument");
+    if (o.n_nodes > 0) HIP_TRY(hipMemcpy(nodes, d_nodes, (size_t)o.n_nodes * o.node_bytes, hipMemcpyDeviceToHost));
+    if (o.n_prims > 0) HIP_TRY(hipMemcpy(prims, sc.dev.prims, (size_t)o.n_prims * o.prim_bytes, hipMemcpyDeviceToHost));
+    if (o.n_instances > 0) HIP_TRY(hipMemcpy(inst_trace, sc.dev.inst_trace, (size_t)o.n_instances * o.inst_bytes, hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+bool has_side(const TakeScene *ts, int32_t side) {
+    return side == TAKE_PRECISION_F32 ? ts->precision != TAKE_PRECISION_F64 : side == TAKE_PRECISION_F64 && ts->precision != TAKE_PRECISION_F32;
+}
+}  // namespace
+
+extern "C" {
+
+int take_hip_debug_tree_info(const TakeScene *ts, int32_t side, TakeDebugTreeInfo *info) {
+    if (!ts || !info) return fail(TAKE_E_INVALID, "null argument");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    if (!has_side(ts, side)) return fail(TAKE_E_INVALID, "the scene has no such side");
+    *info = side == TAKE_PRECISION_F64 ? debug_tree_info(ts->d) : debug_tree_info(ts->f);
+    return TAKE_OK;
+}
+int take_hip_debug_tree(const TakeScene *ts, int32_t side, void *nodes, void *prims, void *inst_trace) {
+    if (!ts || !nodes || !prims) return fail(TAKE_E_INVALID, "null argument");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    if (!has_side(ts, side)) return fail(TAKE_E_INVALID, "the scene has no such side");
+    TAKE_ON_DEVICE(ts);
+    HIP_TRY(hipDeviceSynchronize());
+    return side == TAKE_PRECISION_F64 ? debug_tree_copy(ts->d, nodes, prims, inst_trace) : debug_tree_copy(ts->f, nodes, prims, inst_trace);
+}
+
+}  // extern "C"

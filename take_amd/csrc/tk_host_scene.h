@@ -210,8 +210,19 @@ struct Affine3 {
     }
 };
 
+// a + b rounded downwards / upwards to a double: the residual of the rounded sum (TwoSum, exact without contraction —
+// the build sets -ffp-contract=off) says on which side of it the real sum lies
+inline double sum_down(double a, double b) {
+    const double s = a + b, bb = s - a, err = (a - (s - bb)) + (b - bb);
+    return err < 0 ? std::nextafter(s, -std::numeric_limits<double>::infinity()) : s;
+}
+inline double sum_up(double a, double b) {
+    const double s = a + b, bb = s - a, err = (a - (s - bb)) + (b - bb);
+    return err > 0 ? std::nextafter(s, std::numeric_limits<double>::infinity()) : s;
+}
+
 // The record of face f of mesh `mesh` (the vertices rounded to R, e_k = v_k - v_0 in R; the mesh's material; its
-// attribute index) and its build box (from the R-typed vertices, in double).  Shape id and area light are the caller's.
+// attribute index) and its build box (of the record's geometry, in double).  Shape id and area light are the caller's.
 // (tk_build_gpu.h::k_make_prims is the device twin of this arithmetic.)
 template <class R> inline void triangle_record(const TakeSceneDesc &d, const HostScene<R> &hs, int32_t mesh, int64_t f, PrimRec<R> &p, BuildPrim &box) {
     const TakeMesh &m = d.meshes[mesh];
@@ -223,10 +234,13 @@ template <class R> inline void triangle_record(const TakeSceneDesc &d, const Hos
     p.a[0] = v[0].x, p.a[1] = v[0].y, p.a[2] = v[0].z;
     p.a[3] = e1.x, p.a[4] = e1.y, p.a[5] = e1.z;
     p.a[6] = e2.x, p.a[7] = e2.y, p.a[8] = e2.z;
+    // the box of the geometry the intersection tests see — the real numbers v0, v0 + e1, v0 + e2 of the record, as
+    // k_prim_boxes takes them (tk_build_gpu.h) —, not of the rounded vertices: e_k = fl(v_k - v0) puts v0 + e_k up to
+    // half an ulp of e_k beyond v_k, which a full-width box made from v_k would leave outside
     for (int a = 0; a < 3; a++) {
-        const double x0 = (double)(&v[0].x)[a], x1 = (double)(&v[1].x)[a], x2 = (double)(&v[2].x)[a];
-        box.bmin[a] = std::min(x0, std::min(x1, x2));
-        box.bmax[a] = std::max(x0, std::max(x1, x2));
+        const double x0 = (double)p.a[a], e1 = (double)p.a[3 + a], e2 = (double)p.a[6 + a];
+        box.bmin[a] = std::min(x0, std::min(sum_down(x0, e1), sum_down(x0, e2)));
+        box.bmax[a] = std::max(x0, std::max(sum_up(x0, e1), sum_up(x0, e2)));
     }
     const MeshInfo &mi = hs.meshes[mesh];
     p.meta = PRIM_TRIANGLE | (hs.materials[m.material_id].tag << 8);
@@ -705,9 +719,9 @@ template <class R> inline void shape_record(const TakeSceneDesc &d, int64_t i, c
         for (int a = 0; a < 3; a++) {  // bounds of src/scene.cpp:8-10, from the R-typed values
             box.bmin[a] = (double)(p.a[a] - p.a[3]);
             box.bmax[a] = (double)(p.a[a] + p.a[3]);
-            // an R-rounded centre-radius can round inwards by an ulp: widen in double
-            box.bmin[a] = std::min(box.bmin[a], (double)p.a[a] - (double)p.a[3]);
-            box.bmax[a] = std::max(box.bmax[a], (double)p.a[a] + (double)p.a[3]);
+            // an R-rounded centre -+ radius can round inwards: the real c -+ r, rounded outwards in double
+            box.bmin[a] = std::min(box.bmin[a], sum_down((double)p.a[a], -(double)p.a[3]));
+            box.bmax[a] = std::max(box.bmax[a], sum_up((double)p.a[a], (double)p.a[3]));
         }
         p.meta = PRIM_SPHERE | (hs.materials[s.material_id].tag << 8);
         p.material = s.material_id, p.nidx = -1, p.mesh = -(1 + si);

@@ -33,6 +33,8 @@ def hostsim():
                                           C.POINTER(C.c_uint64)]
         L.hostsim_check_qnodes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.hostsim_env.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.hostsim_tree_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(D.TakeDebugTreeInfo), C.POINTER(C.c_int32)]
+        L.hostsim_tree_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _HOSTSIM = L
     return _HOSTSIM
 
@@ -119,6 +121,21 @@ def hostsim_env(sd, precision, kind, inp):
     return out
 
 
+def hostsim_debug_tree(sd, precision, max_leaf_size=0):
+    """the tree the HOST builder makes for `sd` (prepare_scene<R>, TAKE_HIP_NODES as the environment has it), in the
+    layout of capi.Scene.debug_tree, plus "depth" (take_hip_scene_stats' figure).  precision 0 f32, 1 f64"""
+    desc, keep = sd.to_desc()
+    info, depth = D.TakeDebugTreeInfo(), C.c_int32()
+    if hostsim().hostsim_tree_prepare(C.addressof(desc), precision, max_leaf_size, C.byref(info), C.byref(depth)) != 0:
+        raise RuntimeError(hostsim().hostsim_last_error().decode())
+    node_t, prim_t, inst_t = D.debug_tree_dtypes(info)
+    nodes, prims, inst = np.zeros(info.n_nodes + 1, node_t), np.zeros(info.n_prims + 1, prim_t), np.zeros(info.n_instances + 1, inst_t)
+    hostsim().hostsim_tree_copy(precision, nodes.ctypes.data, prims.ctypes.data, inst.ctypes.data)
+    tree = D.debug_tree_result(info, nodes[:-1], prims[:-1], inst[:-1])
+    tree["depth"] = depth.value
+    return tree
+
+
 def random_linear(rng, n, shear=0.4, scale=(0.4, 2.5)):
     """n linear maps: rotation x non-uniform scale x shear"""
     q = rng.normal(size=(n, 4))
@@ -133,6 +150,20 @@ def random_linear(rng, n, shear=0.4, scale=(0.4, 2.5)):
         sh[0, 1], sh[0, 2], sh[1, 2] = rng.uniform(-shear, shear, 3)
         out.append(rot[k] @ np.diag(rng.uniform(*scale, 3)) @ sh)
     return out
+
+
+def sheared_placements():
+    """rotated, sheared, non-uniformly scaled placements of three prototypes and nothing else"""
+    from take_amd import scenes
+
+    sd = SceneData(width=32, height=32, lookfrom=(0.0, 0.0, 4.0), lookat=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), vfov=40.0,
+                   background=(0.3, 0.3, 0.3), spp=1, max_depth=2)
+    m = sd.add_material(D.MAT_DIFFUSE, (0.6, 0.6, 0.6))
+    rng = np.random.default_rng(12)
+    protos = [sd.add_prototype(*scenes.soup_triangles(300, 5 + k, 0.15, 0.05), m) for k in range(3)]
+    for k, lin in enumerate(random_linear(rng, 90, shear=0.8)):
+        sd.add_instance(protos[k % 3], np.concatenate([lin, rng.uniform(-0.8, 0.8, (3, 1))], axis=1))
+    return sd
 
 
 def random_rays(n, seed, camera_fraction=0.25, bounded_fraction=0.3, tmin=1e-4):

@@ -329,6 +329,43 @@ static void check_qnodes_w(const HostScene<float> &hs, const std::vector<NodeW<f
             if (!ok) out[1]++;
         }
 }
+// take_hip_debug_tree's view (include/take_hip.h) of a scene the HOST prepared: the tree of prepare_scene<R>, in the node
+// format upload_scene would send to the device, kept until the next call so that the caller can size its buffers
+// from the info first.  The 8-wide tree exists compressed only.
+template <class R> struct PreparedTree {
+    HostScene<R> hs;
+    TakeDebugTreeInfo info{};
+    const void *nodes = nullptr;
+    int prepare(const TakeSceneDesc &desc, int max_leaf, int32_t *depth) {
+        hs = HostScene<R>{};
+        g_err = prepare_scene<R>(desc, max_leaf, 2, hs);
+        if (!g_err.empty()) return TAKE_E_INVALID;
+        info = TakeDebugTreeInfo{};
+        info.node_format = !hs.qnodes8.empty() ? 2 : (!hs.qnodes.empty() ? 1 : 0);
+        info.node_width = hs.node_width;
+        info.two_level = hs.inst_trace.empty() ? 0 : 1;
+        info.root_child = hs.root_child;
+        info.real_bytes = (int32_t)sizeof(R);
+        info.node_bytes = (int32_t)(info.node_format == 2 ? sizeof(QNode8) : (info.node_format == 1 ? sizeof(QNode4) : sizeof(Node4<R>)));
+        info.prim_bytes = (int32_t)sizeof(PrimRec<R>), info.inst_bytes = (int32_t)sizeof(InstTrace<R>);
+        info.n_nodes = hs.stats.n_nodes, info.n_prims = (int64_t)hs.prims.size(), info.n_instances = (int64_t)hs.inst_trace.size();
+        for (int a = 0; a < 3; a++) info.grid_lo[a] = hs.grid_lo[a], info.grid_step[a] = hs.grid_step[a];
+        nodes = info.node_format == 2 ? (const void *)hs.qnodes8.data() : (info.node_format == 1 ? (const void *)hs.qnodes.data() : (const void *)hs.nodes.data());
+        if (info.node_format == 0 && hs.node_width != 4) {
+            g_err = "the 8-wide tree has no full-width form to traverse";
+            return TAKE_E_INVALID;
+        }
+        *depth = hs.stats.depth;
+        return TAKE_OK;
+    }
+    void copy(void *nodes_out, void *prims_out, void *inst_out) const {
+        if (info.n_nodes) std::memcpy(nodes_out, nodes, (size_t)info.n_nodes * info.node_bytes);
+        if (info.n_prims) std::memcpy(prims_out, hs.prims.data(), (size_t)info.n_prims * info.prim_bytes);
+        if (info.n_instances) std::memcpy(inst_out, hs.inst_trace.data(), (size_t)info.n_instances * info.inst_bytes);
+    }
+};
+PreparedTree<float> g_tree_f;
+PreparedTree<double> g_tree_d;
 // take_hip_debug_env's rows (tk_shade.h: debug_env_row) on the scene as prepare_scene leaves it
 template <class R> int env_t(const TakeSceneDesc &desc, int kind, const double *in, int64_t n, double *out) {
     HostScene<R> hs;
@@ -408,6 +445,21 @@ int hostsim_trace_stats(const TakeSceneDesc *desc, int precision, const void *ra
                         void *hits, uint64_t *out) {
     return precision == TAKE_PRECISION_F64 ? trace_stats_t<double>(*desc, rays, n, any, lds_levels, drop_from, hits, out)
                                            : trace_stats_t<float>(*desc, rays, n, any, lds_levels, drop_from, hits, out);
+}
+// The tree prepare_scene<R> builds for `desc` (TAKE_HIP_NODES as the environment has it), as take_hip_debug_tree shows a
+// resident one: hostsim_tree_prepare fills the info and the depth (take_hip_scene_stats' figure) and keeps the scene,
+// hostsim_tree_copy copies the kept scene's arrays into buffers sized from that info.
+int hostsim_tree_prepare(const TakeSceneDesc *desc, int precision, int max_leaf, TakeDebugTreeInfo *info, int32_t *depth) {
+    if (!desc || !info || !depth) return TAKE_E_INVALID;
+    const int rc = precision == TAKE_PRECISION_F64 ? g_tree_d.prepare(*desc, max_leaf, depth) : g_tree_f.prepare(*desc, max_leaf, depth);
+    if (rc == TAKE_OK) *info = precision == TAKE_PRECISION_F64 ? g_tree_d.info : g_tree_f.info;
+    return rc;
+}
+int hostsim_tree_copy(int precision, void *nodes, void *prims, void *inst_trace) {
+    if (!nodes || !prims || !inst_trace) return TAKE_E_INVALID;
+    if (precision == TAKE_PRECISION_F64) g_tree_d.copy(nodes, prims, inst_trace);
+    else g_tree_f.copy(nodes, prims, inst_trace);
+    return TAKE_OK;
 }
 // the environment-map functions on rows of draws (kind 0) or directions (kind 1): columns as take_hip_debug_env's
 int hostsim_env(const TakeSceneDesc *desc, int precision, int kind, const double *in, int64_t n, double *out) {

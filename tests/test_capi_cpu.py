@@ -47,6 +47,7 @@ def test_struct_layout_matches_header():
         "TakeSceneDesc": D.TakeSceneDesc, "TakeBuildOpts": D.TakeBuildOpts, "TakeRenderOpts": D.TakeRenderOpts,
         "TakeRayF": D.TakeRayF, "TakeRayD": D.TakeRayD, "TakeHitF": D.TakeHitF, "TakeHitD": D.TakeHitD,
         "TakeCounters": D.TakeCounters, "TakeInstance": D.TakeInstance, "TakePlyLayout": D.TakePlyLayout,
+        "TakeDebugTreeInfo": D.TakeDebugTreeInfo,
     }
     prog = ['#include <stdio.h>', '#include <stddef.h>', '#include "take_hip.h"', "int main(void){"]
     for n, cls in fields.items():
@@ -103,6 +104,25 @@ def test_group_and_egress_entry_points_without_gpu(lib):
     buf = (C.c_uint16 * 16)()
     rc = lib.take_hip_pack_exr_scanlines(C.cast(buf, C.c_void_p), 0, 2, 2, C.cast(buf, C.c_void_p), None)
     assert rc == -3
+    # the tree read-back hook: with every argument present the missing device is what it reports (the handle is never
+    # read before a device is found: any non-NULL pointer will do here)
+    handle, out, info = (C.c_char * 4096)(), (C.c_char * 64)(), D.TakeDebugTreeInfo()
+    assert lib.take_hip_debug_tree_info(C.cast(handle, C.c_void_p), D.TAKE_PRECISION_F32, C.byref(info)) == -3
+    assert lib.take_hip_debug_tree(C.cast(handle, C.c_void_p), D.TAKE_PRECISION_F64, out, out, out) == -3
+    assert b"no CPU path" in lib.take_hip_last_error()
+
+
+def test_tree_hook_refuses_null_arguments_before_it_looks_for_a_device(lib):
+    """take_hip_debug_tree_info / take_hip_debug_tree: "null argument" is TAKE_E_INVALID with or without a GPU"""
+    handle, out, info = (C.c_char * 4096)(), (C.c_char * 64)(), D.TakeDebugTreeInfo()
+    h = C.cast(handle, C.c_void_p)
+    for rc in (lib.take_hip_debug_tree_info(None, D.TAKE_PRECISION_F32, C.byref(info)),
+               lib.take_hip_debug_tree_info(h, D.TAKE_PRECISION_F32, None),
+               lib.take_hip_debug_tree(None, D.TAKE_PRECISION_F32, out, out, out),
+               lib.take_hip_debug_tree(h, D.TAKE_PRECISION_F32, None, out, out),
+               lib.take_hip_debug_tree(h, D.TAKE_PRECISION_F32, out, None, out)):
+        assert rc == D.TAKE_E_INVALID
+        assert b"null argument" in lib.take_hip_last_error()
 
 
 def test_product_never_imports_the_oracle():

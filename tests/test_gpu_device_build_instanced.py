@@ -10,7 +10,7 @@ import time
 import numpy as np
 import pytest
 
-from helpers import random_linear, random_rays, rays_to_abi, rmse
+from helpers import random_linear, random_rays, rays_to_abi, rmse, sheared_placements
 from take_amd import capi, scenes
 from take_amd import cdefs as D
 from take_amd.scene import SceneData
@@ -254,18 +254,6 @@ def test_device_built_instanced_equals_flattened(precision):
 
 
 # ------------------------------------------------------------------ 4. placement boxes, through hits
-def sheared_placements():
-    """rotated, sheared, non-uniformly scaled placements of three prototypes and nothing else"""
-    sd = SceneData(width=32, height=32, lookfrom=(0.0, 0.0, 4.0), lookat=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), vfov=40.0,
-                   background=(0.3, 0.3, 0.3), spp=1, max_depth=2)
-    m = sd.add_material(D.MAT_DIFFUSE, (0.6, 0.6, 0.6))
-    rng = np.random.default_rng(12)
-    protos = [sd.add_prototype(*scenes.soup_triangles(300, 5 + k, 0.15, 0.05), m) for k in range(3)]
-    for k, lin in enumerate(random_linear(rng, 90, shear=0.8)):
-        sd.add_instance(protos[k % 3], np.concatenate([lin, rng.uniform(-0.8, 0.8, (3, 1))], axis=1))
-    return sd
-
-
 @pytest.mark.parametrize("precision", [F32, F64])
 def test_sheared_placements_same_hits_as_the_host_build(precision):
     """both instances of k_placement_pad (mag * 4e-6 for float scenes, mag * 1e-13 for double ones) on boxes that are
