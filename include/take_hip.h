@@ -332,7 +332,7 @@ int take_hip_device_count(void);
 int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, TakeScene **out);
 int take_hip_scene_destroy(TakeScene *scene);
 
-/* ---- a resident scene changes (new symbols of ABI version 5; no struct changed).  All three calls: a failed call
+/* ---- a resident scene changes (new symbols of ABI version 5; no struct changed).  All of these calls: a failed call
  * leaves the scene exactly as it was (same hits, same image); a successful one ends a progressive sequence
  * (take_hip_accumulated_samples = 0) and the next take_hip_render_accumulate must be called with restart != 0
  * (TAKE_E_INVALID otherwise); F32, F64 and MIXED scenes — a mixed scene changes on both sides or on neither.  Scene
@@ -359,6 +359,33 @@ int take_hip_scene_set_instance_transforms_device(TakeScene *scene, const double
 /* New camera; width and height must equal the scene's (the render buffers are sized from them), TAKE_E_INVALID
  * otherwise.  Any scene, with or without placements. */
 int take_hip_scene_set_camera(TakeScene *scene, const TakeCamera *camera);
+/* New vertex positions — and, optionally, vertex normals — for meshes of a scene WITHOUT placements: the vertices
+ * move, the topology stays.  Vertex and face counts are the scene's own (the handle remembers the counts of the
+ * description it was created from); uvs, indices, materials, spheres and every mesh not named stay as they are.
+ * Afterwards the scene is, byte for byte, the scene that take_hip_scene_create with TAKE_BUILDER_DEVICE_LBVH and the
+ * same max_leaf_size makes from the description with the new arrays: records, nodes, grid, light records and power
+ * tables, hits and images.  Nothing of the description is read or uploaded again: the primitive records of the named
+ * meshes get new geometry from the scene's resident face indices, the tree is rebuilt on the device by the LBVH
+ * pipeline (no refit: no quality to decay) — compressed or full-width nodes are chosen afresh by the inflation rule —,
+ * new normals are converted in place, and area lights on faces of the named meshes get new records and power tables.
+ * take_hip_scene_build_info reports TAKE_BUILDER_DEVICE_LBVH for every side afterwards, whoever built the scene;
+ * take_hip_scene_stats reports the new tree.
+ * TAKE_E_INVALID — arguments that need no scene are looked at before the device is, the others right after it: a NULL
+ * scene or `updates`, n_updates <= 0, a mesh index out of range or named twice, positions == NULL, unknown flag bits,
+ * normals for a mesh without vertex normals; a new position that is not finite (the message names mesh and vertex).
+ * The finiteness check is the update's own — take_hip_scene_create has none — and covers what the records are made of:
+ * the coordinates of every vertex a face refers to, as the scene's arithmetic takes them (1e300 is not finite for an
+ * f32 or mixed scene).  A vertex no face refers to, and the normals, are taken as they are, as scene_create takes them.
+ * TAKE_E_INVALID with a message that starts with "unsupported": a two-level scene (n_instances > 0; its prototypes are
+ * a follow-up), a scene flattened from instances, a TAKE_HIP_NODES=q8 scene, a new tree of fewer than two leaves or too
+ * deep for the traversal stack. */
+typedef struct TakeMeshUpdate {
+    int32_t mesh;             /* index into the TakeSceneDesc.meshes the scene was created from */
+    int32_t flags;            /* 0, or TAKE_MESH_DEVICE_ARRAYS: the two pointers are device memory */
+    const double *positions;  /* n_vertices x 3 of that mesh, complete; required */
+    const double *normals;    /* n_vertices x 3, or NULL = keep; only for a mesh that has vertex normals */
+} TakeMeshUpdate;
+int take_hip_scene_set_mesh_vertices(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
 
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order

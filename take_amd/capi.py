@@ -28,6 +28,7 @@ EXPORTS = [
     "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
     "take_hip_scene_build_info",
     "take_hip_scene_set_instance_transforms", "take_hip_scene_set_instance_transforms_device", "take_hip_scene_set_camera",
+    "take_hip_scene_set_mesh_vertices",
     "take_hip_render_features", "take_hip_render_features_device",
     "take_hip_debug_tree_info", "take_hip_debug_tree",
 ]
@@ -368,6 +369,40 @@ class Scene:
         cam = D.TakeCamera(self.sd.width if width is None else int(width), self.sd.height if height is None else int(height),
                            D.c_double3(*map(float, lookfrom)), D.c_double3(*map(float, lookat)), D.c_double3(*map(float, up)), float(vfov))
         _check(lib().take_hip_scene_set_camera(self.h, C.byref(cam)))
+
+    def set_mesh_vertices(self, updates):
+        """new vertices for meshes of a scene without placements (take_hip_scene_set_mesh_vertices): `updates` is
+        {mesh_id: positions} or {mesh_id: (positions, normals)} (a tuple), every array (n_vertices, 3) float64 and complete, normals
+        None = keep.  numpy arrays (or anything numpy converts) are read from host memory; torch device tensors —
+        contiguous float64, all arrays of one mesh on the device — through their device pointers.  The tree is rebuilt
+        on the device; afterwards the scene equals one newly created from the description with these arrays."""
+        recs = (D.TakeMeshUpdate * max(len(updates), 1))()
+        keep = []
+
+        def on_device(a):
+            return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+        def pointer(a, device):
+            if a is None:
+                return None
+            if device:
+                if not on_device(a) or str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                    raise ValueError("arrays on the device must be contiguous float64 tensors, and all arrays of a mesh on the device")
+                keep.append(a)
+                return a.data_ptr()
+            if hasattr(a, "data_ptr"):  # a torch tensor in host memory
+                a = a.numpy()
+            a = np.ascontiguousarray(a, np.float64)
+            keep.append(a)
+            return a.ctypes.data
+
+        for k, (mesh, arrays) in enumerate(updates.items()):
+            pos, nrm = arrays if isinstance(arrays, tuple) and len(arrays) == 2 else (arrays, None)
+            device = on_device(pos)
+            recs[k].mesh, recs[k].flags = int(mesh), D.TAKE_MESH_DEVICE_ARRAYS if device else 0
+            recs[k].positions, recs[k].normals = pointer(pos, device), pointer(nrm, device)
+        _check(lib().take_hip_scene_set_mesh_vertices(self.h, recs, len(updates)))
+        del keep
 
     def trace_closest(self, rays_abi):
         """rays_abi: (n,8) array in TakeRayF/D layout (org3 tmin dir3 tmax) -> structured hits"""

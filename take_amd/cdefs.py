@@ -88,10 +88,16 @@ TAKE_BUILDER_HOST_SAH = 2
 
 
 # prototypes of the entry points that change a resident scene (include/take_hip.h): name -> argument types
+class TakeMeshUpdate(C.Structure):
+    """take_hip_scene_set_mesh_vertices: new arrays of one mesh (host memory, or device memory under TAKE_MESH_DEVICE_ARRAYS)"""
+    _fields_ = [("mesh", C.c_int32), ("flags", C.c_int32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
+
+
 SCENE_UPDATE_PROTOTYPES = {
     "take_hip_scene_set_instance_transforms": [C.c_void_p, C.c_void_p, C.c_int64],
     "take_hip_scene_set_instance_transforms_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "take_hip_scene_set_camera": [C.c_void_p, C.POINTER(TakeCamera)],
+    "take_hip_scene_set_mesh_vertices": [C.c_void_p, C.POINTER(TakeMeshUpdate), C.c_int32],
 }
 
 

@@ -177,6 +177,13 @@ struct StagedMeshes {
 };
 
 
+// the leaf size request of a build: the caller's, else the environment's (a tuning knob), else 0 = the builder's default
+int requested_max_leaf(const TakeBuildOpts &opts) {
+    int max_leaf = opts.max_leaf_size;
+    if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));
+    return max_leaf;
+}
+
 // One precision's side of a new scene: records, tree and shading tables prepared on the host and uploaded, or with
 // device_builder the records and the tree made on the device — and, when the device tree would be too deep, on the
 // host after all.  staged: the description's device-array meshes (StagedMeshes::stage).  inputs: what the device
@@ -185,8 +192,7 @@ template <class R>
 int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const TakeBuildOpts &opts, int threads, bool device_builder,
                  StagedMeshes &staged, DeviceBuildInputs &inputs, bool last_side) {
     PhaseClock clock(sizeof(R) == 4 ? "f32" : "f64");
-    int max_leaf = opts.max_leaf_size;
-    if (max_leaf <= 0 && std::getenv("TAKE_HIP_MAX_LEAF")) max_leaf = std::atoi(std::getenv("TAKE_HIP_MAX_LEAF"));  // tuning knob
+    const int max_leaf = requested_max_leaf(opts);
     const std::string fmt = tree_knobs().nodes;
     bool on_device = device_builder;
     std::string err = prepare_scene<R>(desc, max_leaf, threads, sc.host, on_device ? PREP_DEVICE_BUILD : PREP_HOST_BUILD, opts.burley_lobes != 0);
@@ -326,6 +332,21 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         if (!rc && o.precision != TAKE_PRECISION_F32)
             rc = upload_scene(ts->d, ts->num_cus, local, o, threads, device_builder, staged, inputs, o.precision == TAKE_PRECISION_F64);
         if (!rc && o.precision != TAKE_PRECISION_F64) rc = upload_scene(ts->f, ts->num_cus, local, o, threads, device_builder, staged, inputs, true);
+        // what take_hip_scene_set_mesh_vertices will need: the meshes' vertex counts, and for a scene without placements
+        // the shape_face array in device memory — the device builder's upload, or one made here
+        if (!rc) {
+            ts->mesh_vertices.resize((size_t)desc->n_meshes);
+            for (int i = 0; i < desc->n_meshes; i++) ts->mesh_vertices[i] = desc->meshes[i].n_vertices;
+            ts->max_leaf = requested_max_leaf(o), ts->flattened = flat.meshes.size() > 0, ts->node_knob = tree_knobs().nodes;
+            if (local.n_instances == 0 && !ts->flattened && local.n_shapes > 0) {
+                if (inputs.face.p) {
+                    ts->shape_face = std::move(inputs.face);
+                } else if (ts->shape_face.alloc((size_t)local.n_shapes) != hipSuccess ||
+                           hipMemcpy(ts->shape_face.p, local.shape_face, ts->shape_face.bytes(), hipMemcpyHostToDevice) != hipSuccess) {
+                    rc = fail(TAKE_E_NOMEM, "out of device memory for the shape_face array");
+                }
+            }
+        }
     } catch (const std::bad_alloc &) {
         rc = fail(TAKE_E_NOMEM, "out of host memory while preparing the scene");
     } catch (const std::exception &e) {
@@ -362,7 +383,7 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
     if (ts->acc_restart_needed && restart == 0)
-        return fail(TAKE_E_INVALID, "take_hip_render_accumulate: the scene's placements or camera changed since the last call: pass restart = 1");
+        return fail(TAKE_E_INVALID, "take_hip_render_accumulate: the scene's placements, vertices or camera changed since the last call: pass restart = 1");
     const TakeRenderOpts &a = ts->acc_opts;
     const bool fresh = restart != 0 || ts->acc_samples == 0;
     // (mixed scenes: the exact rounds the samples were rendered with, <= 0 meaning the default; f32 / f64 ignore the field)
@@ -536,6 +557,63 @@ int take_hip_scene_set_instance_transforms(TakeScene *ts, const double *xforms, 
     if (d_xforms.alloc(12 * (size_t)n) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the transforms");
     HIP_TRY(hipMemcpy(d_xforms.p, xforms, d_xforms.bytes(), hipMemcpyHostToDevice));
     return set_instance_transforms(ts, d_xforms.p, n);
+}
+// New vertices for meshes of a resident scene (include/take_hip.h): the arguments that need no scene, the device, the
+// arguments against the scene, what the path does not support; then every side staged and every side committed.
+int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) {
+    if (!ts || !updates) return fail(TAKE_E_INVALID, "null argument");
+    if (n_updates <= 0) return fail(TAKE_E_INVALID, "n_updates must be positive");
+    try {
+        std::vector<int32_t> ids((size_t)n_updates);
+        for (int32_t i = 0; i < n_updates; i++) {
+            const TakeMeshUpdate &u = updates[i];
+            const std::string who = "update " + std::to_string(i) + ": ";
+            if (u.mesh < 0) return fail(TAKE_E_INVALID, who + "mesh index out of range");
+            if (u.flags & ~TAKE_MESH_DEVICE_ARRAYS) return fail(TAKE_E_INVALID, who + "unknown flag bits");
+            if (!u.positions) return fail(TAKE_E_INVALID, who + "positions is null");
+            ids[i] = u.mesh;
+        }
+        std::sort(ids.begin(), ids.end());
+        for (int32_t i = 1; i < n_updates; i++)
+            if (ids[i] == ids[i - 1]) return fail(TAKE_E_INVALID, "mesh " + std::to_string(ids[i]) + " appears more than once");
+        const int nd = check_device();
+        if (nd < 0) return nd;
+        for (int32_t i = 0; i < n_updates; i++) {
+            const TakeMeshUpdate &u = updates[i];
+            const std::string who = "update " + std::to_string(i) + ": ";
+            if ((size_t)u.mesh >= ts->mesh_vertices.size()) return fail(TAKE_E_INVALID, who + "mesh index out of range");
+            const bool has_normals = on_primary(ts, [&](const auto &sc) { return (size_t)u.mesh < sc.host.meshes.size() && sc.host.meshes[u.mesh].nbase >= 0; });
+            if (u.normals && !has_normals) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
+        }
+        if (ts->n_placements > 0) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (the prototypes' trees are not rebuilt)");
+        if (ts->flattened) return fail(TAKE_E_INVALID, "unsupported: the scene was flattened from instances");
+        const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc) { return sc.trace.nodes == NodeFormat::Q8; });
+        if (q8) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_NODES=q8");
+        if (on_primary(ts, [&](const auto &sc) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
+        if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
+        if (on_primary(ts, [&](const auto &sc) { return sc.prims.n != ts->shape_face.n; }))
+            return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+        TAKE_ON_DEVICE(ts);
+        MeshUpdateInputs in;
+        int rc = in.upload(ts->mesh_vertices, updates, n_updates);
+        if (rc) return rc;
+        const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
+        MeshUpdateStage<double> sd;
+        MeshUpdateStage<float> sf;
+        if (ts->precision != TAKE_PRECISION_F32)
+            rc = update_mesh_vertices_device(ts->d, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, sd);
+        if (!rc && ts->precision != TAKE_PRECISION_F64)
+            rc = update_mesh_vertices_device(ts->f, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, sf);
+        if (rc) return rc;
+        if (ts->precision != TAKE_PRECISION_F32) sd.commit(ts->d);
+        if (ts->precision != TAKE_PRECISION_F64) sf.commit(ts->f);
+        ts->acc_samples = 0, ts->acc_restart_needed = true;
+        return TAKE_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(TAKE_E_NOMEM, "out of host memory while updating the meshes");
+    } catch (const std::exception &e) {
+        return fail(TAKE_E_INVALID, std::string("updating the meshes failed: ") + e.what());
+    }
 }
 int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
     if (!ts || !camera) return fail(TAKE_E_INVALID, "null argument");

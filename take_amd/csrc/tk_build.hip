@@ -1,7 +1,9 @@
 // tk_build.hip — the host driver of the device LBVH builder: the records and trees of one side of a new scene made on
 // the device from the caller's arrays (build_side_on_device, declared in tk_scene_handle.h; tk_api.hip's upload_scene
 // calls it), and the top-level half of it entered again for a resident scene whose placements get new transforms
-// (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
+// (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it), and creation's tail entered
+// again for a resident scene whose meshes get new vertices (update_mesh_vertices_device;
+// take_hip_scene_set_mesh_vertices calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,7 +86,7 @@ struct BuildMemory {
 };
 
 // One LBVH on the device (tk_build_gpu.h): Morton codes -> rocPRIM sort -> k_leaves -> k_hierarchy -> k_refit ->
-// k_collapse.  The scene's only tree, the top-level tree of a two-level scene, or a prototype's.
+// k_collapse_count / scan / k_collapse per level.  The scene's only tree, the top-level tree of a two-level scene, or a prototype's.
 struct DeviceTree {
     DevBuf<Node4<float>> nodes;  // breadth-first; child words local to the tree: node indices from 0, a leaf = a range of `order`
     DevBuf<uint32_t> order;      // Morton order -> entry of the span (a stable sort: coincident entries keep their order)
@@ -118,7 +120,7 @@ int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n
     DevBuf<Box> lbox, ibox;
     DevBuf<uint64_t> keys, keys_s, lkey;
     DevBuf<uint32_t> vals;
-    DevBuf<int> parent_i, parent_l, flag, frontier[2], lvl;
+    DevBuf<int> parent_i, parent_l, flag, frontier[2];
     DevBuf<int2> child;
     DevBuf<char> temp;
     // Morton codes, sort
@@ -150,28 +152,39 @@ int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n
     hipLaunchKernelGGL(k_refit, blocks_for(n_leaves), blk, 0, stream, n_leaves, child.p, parent_i.p, parent_l.p, lbox.p, ibox.p, flag.p);
     lkey.release(), parent_i.release(), parent_l.release(), flag.release();
 
-    // collapse to 4-wide nodes, breadth-first, one launch per level (at most one node per leaf; the count is known after)
+    // collapse to 4-wide nodes, breadth-first, level by level (at most one node per leaf; the count is known after).
+    // The host reads each level's size (4 bytes) before it launches the next: the grids and the scans are sized to the
+    // level, and the loop ends with the tree instead of running every level the stack allows.
+    DevBuf<int> cnt, off, n_next;
     HIP_TRY(t.nodes.alloc(n_leaves));
     HIP_TRY(frontier[0].alloc(n_leaves));
     HIP_TRY(frontier[1].alloc(n_leaves));
-    HIP_TRY(lvl.alloc(MAX_LEVELS + 2));
+    HIP_TRY(cnt.alloc(n_leaves));
+    HIP_TRY(off.alloc(n_leaves));
+    HIP_TRY(n_next.alloc(1));
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, cnt.p, off.p, 0, (size_t)n_leaves, rocprim::plus<int>(), stream));
+    HIP_TRY(temp.alloc(std::max<size_t>(scan_bytes, 1)));
     mem.sample("collapse");
-    HIP_TRY(hipMemsetAsync(lvl.p, 0, lvl.bytes(), stream));
-    hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, lvl.p, 1, 1);           // one node on level 0 ...
-    hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, frontier[0].p, 1, 0);   // ... made from BVH2 node 0
-    const int cgrid = std::max(1, std::min((n_leaves + BLK - 1) / BLK, 2048));
-    for (int level = 0; level < MAX_LEVELS; level++)
-        hipLaunchKernelGGL(k_collapse, dim3(cgrid), blk, 0, stream, level, frontier[level & 1].p, frontier[(level + 1) & 1].p,
-                           lvl.p, child.p, ibox.p, lbox.p, leaf_size, n, t.nodes.p);
-    int lvl_h[MAX_LEVELS + 2];
-    int ord_h[6];
-    HIP_TRY(hipMemcpyAsync(lvl_h, lvl.p, sizeof(lvl_h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(ord_h, scene_ord.p, sizeof(ord_h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (lvl_h[MAX_LEVELS] != 0) return 1;  // deeper than the traversal stack allows
+    hipLaunchKernelGGL(k_fill_int, dim3(1), blk, 0, stream, frontier[0].p, 1, 0);  // level 0: one node, made from BVH2 node 0
     t.n_nodes = 0, t.depth = 0;
-    for (int k = 0; k < MAX_LEVELS; k++)
-        if (lvl_h[k] > 0) t.n_nodes += lvl_h[k], t.depth = k + 1;
+    int n_in = 1;
+    for (int level = 0; n_in > 0; level++) {
+        if (level == MAX_LEVELS) return 1;  // deeper than the traversal stack allows
+        size_t need = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, need, cnt.p, off.p, 0, (size_t)n_in, rocprim::plus<int>(), stream));
+        if (need > temp.bytes()) HIP_TRY(temp.alloc(need));
+        hipLaunchKernelGGL(k_collapse_count, blocks_for(n_in), blk, 0, stream, frontier[level & 1].p, n_in, child.p, ibox.p, cnt.p);
+        HIP_TRY(rocprim::exclusive_scan(temp.p, need, cnt.p, off.p, 0, (size_t)n_in, rocprim::plus<int>(), stream));
+        hipLaunchKernelGGL(k_collapse, blocks_for(n_in), blk, 0, stream, frontier[level & 1].p, n_in, (int)t.n_nodes, off.p, frontier[(level + 1) & 1].p,
+                           n_next.p, child.p, ibox.p, lbox.p, leaf_size, n, t.nodes.p);
+        t.n_nodes += n_in, t.depth = level + 1;
+        HIP_TRY(hipMemcpy(&n_in, n_next.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (n_in < 0 || t.n_nodes + n_in > n_leaves) return fail(TAKE_E_DEVICE, "the device collapse lost count of its nodes");
+    }
+    HIP_TRY(hipGetLastError());
+    int ord_h[6];
+    HIP_TRY(hipMemcpy(ord_h, scene_ord.p, sizeof(ord_h), hipMemcpyDeviceToHost));
     t.nodes.n = (size_t)t.n_nodes;  // the tail of the allocation is unused
     for (int a = 0; a < 3; a++) t.lo[a] = ord2f(ord_h[a]), t.hi[a] = ord2f(ord_h[3 + a]);
     return TAKE_OK;
@@ -664,5 +677,132 @@ template struct ReposeStage<float>;
 template struct ReposeStage<double>;
 template int repose_two_level_device<float>(const SceneT<float> &, const double *, int64_t, ReposeStage<float> &);
 template int repose_two_level_device<double>(const SceneT<double> &, const double *, int64_t, ReposeStage<double> &);
+
+// ---- take_hip_scene_set_mesh_vertices
+int MeshUpdateInputs::upload(const std::vector<int64_t> &mesh_vertices, const TakeMeshUpdate *updates, int32_t n_updates) {
+    pos.assign(mesh_vertices.size(), nullptr), nrm.assign(mesh_vertices.size(), nullptr);
+    PinnedUploads pin;
+    for (int32_t i = 0; i < n_updates; i++) {
+        const TakeMeshUpdate &u = updates[i];
+        const size_t words = 3 * (size_t)std::max<int64_t>(mesh_vertices[u.mesh], 1);  // (an empty mesh: one word nobody reads)
+        const double *src[2] = {u.positions, u.normals};
+        const double **dst[2] = {&pos[u.mesh], &nrm[u.mesh]};
+        for (int k = 0; k < 2; k++) {
+            if (!src[k]) continue;
+            if (u.flags & TAKE_MESH_DEVICE_ARRAYS) {
+                *dst[k] = src[k];
+                continue;
+            }
+            owned.emplace_back();
+            HIP_TRY(owned.back().alloc(words));
+            HIP_TRY(pin.copy(owned.back().p, src[k], sizeof(double) * 3 * (size_t)mesh_vertices[u.mesh]));
+            *dst[k] = owned.back().p;
+        }
+    }
+    HIP_TRY(pin.finish());
+    HIP_TRY(d_pos.upload(pos));
+    HIP_TRY(d_nrm.upload(nrm));
+    return TAKE_OK;
+}
+
+template <class R>
+int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
+                                int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out) {
+    using namespace lbvh;
+    const int n = (int)sc.prims.n, n_lights = (int)sc.lights.n;
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    SceneT<R> &b = out.built;
+
+    // 1. the records, back in shape order; a coordinate that is not finite is reported before anything else is made
+    {
+        DevBuf<unsigned long long> bad;
+        const unsigned long long none = ~0ull;
+        unsigned long long bad_h = none;
+        HIP_TRY(b.prims.alloc((size_t)n));
+        HIP_TRY(bad.alloc(1));
+        HIP_TRY(hipMemcpyAsync(bad.p, &none, sizeof(none), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n), blk, 0, stream, sc.prims.p, n, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p, b.prims.p, bad.p);
+        HIP_TRY(hipMemcpy(&bad_h, bad.p, sizeof(bad_h), hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        if (bad_h != none)
+            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad_h >> 32) + ": vertex " + std::to_string(bad_h & 0xffffffffull) + ": a new position is not finite");
+    }
+
+    // 2. new vertex normals as the scene keeps them: a copy of the scene's whole array with the named meshes' parts
+    // rewritten, so that commit() only moves
+    for (size_t m = 0; m < in.nrm.size(); m++) {
+        if (!in.nrm[m] || mesh_vertices[m] <= 0) continue;
+        if (!out.new_normals) {
+            HIP_TRY(b.normals.alloc(sc.normals.n));
+            HIP_TRY(hipMemcpyAsync(b.normals.p, sc.normals.p, sc.normals.bytes(), hipMemcpyDeviceToDevice, stream));
+            out.new_normals = true;
+        }
+        const int64_t words = 3 * mesh_vertices[m];
+        hipLaunchKernelGGL(k_convert_normals<R>, blocks_for(words), blk, 0, stream, in.nrm[m], words, b.normals.p + 3 * (size_t)sc.host.meshes[m].nbase);
+    }
+
+    // 3. the light records of emissive faces, and the power tables from them: light_power_tables is a sequential sum
+    // in R in light order — the records come back and the host sums, as it does for a new scene
+    if (n_lights > 0) {
+        HIP_TRY(b.lights.alloc((size_t)n_lights));
+        HIP_TRY(hipMemcpyAsync(b.lights.p, sc.lights.p, sc.lights.bytes(), hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(k_update_lights<R>, blocks_for(n_lights), blk, 0, stream, b.lights.p, n_lights, b.prims.p, n, in.d_pos.p, in.d_nrm.p, sc.meshes.p,
+                           d_shape_face, sc.face_idx.p);
+        b.host.lights.resize((size_t)n_lights);
+        HIP_TRY(hipMemcpy(b.host.lights.data(), b.lights.p, b.lights.bytes(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        light_power_tables(b.host);
+        HIP_TRY(b.light_pmf.upload(b.host.light_pmf));
+        HIP_TRY(b.light_cdf.upload(b.host.light_cdf));
+        out.new_lights = true;
+    }
+
+    // 4. creation's tail: boxes, tree, nodes in the format the inflation rule chooses, records into leaf order
+    const int rb = build_bvh_device(b, max_leaf, compressed_ok, compressed_forced);
+    if (rb == 1) {
+        const int leaf_size = device_leaf_size(max_leaf);
+        return fail(TAKE_E_INVALID, (n + leaf_size - 1) / leaf_size < 2 ? "unsupported: a tree of fewer than two leaves"
+                                                                        : "unsupported: the new tree is too deep for the traversal stack");
+    }
+    if (rb) return rb;
+    b.trace = TraceKind{b.qnodes.p ? NodeFormat::Q4 : NodeFormat::WIDE, false};
+    if ((uint64_t)b.host.stats.n_nodes * node_bytes<R>(b.trace.nodes) >= (1ull << 32))
+        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
+    if (b.trace.nodes != sc.trace.nodes) {  // another trace kernel instance: its own grid and spill area
+        const hipError_t e = alloc_trace_state(b, num_cus);
+        if (e == hipErrorOutOfMemory) return fail(TAKE_E_NOMEM, "out of device memory for the trace state");
+        HIP_TRY(e);
+        out.new_trace_state = true;
+    }
+    return TAKE_OK;
+}
+template <class R> void MeshUpdateStage<R>::commit(SceneT<R> &sc) {
+    SceneT<R> &b = built;
+    HostScene<R> &h = sc.host;
+    if (new_normals) sc.normals = std::move(b.normals);
+    sc.prims = std::move(b.prims);
+    sc.qnodes = std::move(b.qnodes), sc.nodes = std::move(b.nodes);  // (the one the new format does not use is empty: the scene's is freed)
+    if (new_lights) {
+        sc.lights = std::move(b.lights), sc.light_pmf = std::move(b.light_pmf), sc.light_cdf = std::move(b.light_cdf);
+        h.lights = std::move(b.host.lights), h.light_pmf = std::move(b.host.light_pmf), h.light_cdf = std::move(b.host.light_cdf);
+    }
+    h.stats = b.host.stats, h.root_child = b.host.root_child, h.q_inflation = b.host.q_inflation, h.node_width = 4;
+    for (int a = 0; a < 3; a++) h.grid_lo[a] = sc.dev.grid_lo[a] = b.host.grid_lo[a], h.grid_step[a] = sc.dev.grid_step[a] = b.host.grid_step[a];
+    sc.dev.root_child = h.root_child, sc.dev.n_nodes = (int32_t)h.stats.n_nodes;
+    sc.trace = b.trace;
+    sc.built_on_device = true;  // whoever built the tree that is gone
+    if (new_trace_state) {
+        sc.qwords = std::move(b.qwords), sc.counters = std::move(b.counters), sc.spill = std::move(b.spill);
+        sc.blocks_per_cu = b.blocks_per_cu, sc.spill_levels = b.spill_levels, sc.trace_grid = b.trace_grid, sc.spill_stride = b.spill_stride;
+    }
+    sc.bind();
+}
+template struct MeshUpdateStage<float>;
+template struct MeshUpdateStage<double>;
+template int update_mesh_vertices_device<float>(const SceneT<float> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, int, bool, bool,
+                                                int, MeshUpdateStage<float> &);
+template int update_mesh_vertices_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, int, bool, bool,
+                                                 int, MeshUpdateStage<double> &);
 
 }  // namespace tk_host

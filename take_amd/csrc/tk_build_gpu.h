@@ -11,8 +11,9 @@
 //   k_leaves         leaves = runs of `leaf_size` consecutive primitives in Morton order
 //   k_hierarchy      Karras 2012: every internal node finds its key range and split in parallel
 //   k_refit          bottom-up boxes, second arrival at a node computes it (agent-scope fences around the flag)
-//   k_collapse       BVH2 -> 4-wide nodes, one launch per tree level, breadth-first numbering (same layout and the
-//                    same "open the child with the largest area" rule as the host collapse, tk_bvh.h)
+//   k_collapse       BVH2 -> 4-wide nodes, level by level (k_collapse_count, a scan, k_collapse), breadth-first
+//                    numbering in the order of the parents (same layout and the same "open the child with the largest
+//                    area" rule as the host collapse, tk_bvh.h); no atomic counter: the nodes are reproducible
 //   k_quantise       64-byte compressed nodes on the 15-bit scene grid (same rounding rules as quantise_nodes)
 //   k_widen_nodes    double scenes without compression: the float nodes as Node4<double>
 //   k_permute        primitive and shading records into leaf order
@@ -26,6 +27,9 @@
 //   k_placement_records          the placements' InstTrace / InstShade records under new transforms
 //   k_placement_boxes_resident   their tight world boxes from the prototypes' records in the scene, k_widen_tight
 //   k_shift_roots                the placements' roots after the top-level tree changed its size
+// Moving the vertices of meshes of a resident scene (take_hip_scene_set_mesh_vertices) adds
+//   k_update_prims     the resident records back into shape order, updated meshes' triangles with new geometry words
+//   k_convert_normals / k_update_lights   new vertex normals as R; the records of area lights on updated faces
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
@@ -95,15 +99,20 @@ struct SphereSrc {
     double c[3], r;
     int32_t material, tag;
 };
+// The geometry words of a triangle record (a[9]: v0, e1, e2) from the mesh's double positions (its vertex 0 first) and
+// the face's three vertex ids.  The one place this arithmetic lives on the device: a new scene's records
+// (triangle_into) and the records of a resident scene whose vertices moved (k_update_prims) are made by it.
+template <class R> __device__ __forceinline__ void triangle_geometry(R *a9, const double *__restrict__ mesh_positions, const int32_t *__restrict__ idx) {
+    R v[3][3];
+    for (int k = 0; k < 3; k++)
+        for (int a = 0; a < 3; a++) v[k][a] = (R)mesh_positions[3 * (int64_t)idx[k] + a];
+    for (int a = 0; a < 3; a++) a9[a] = v[0][a], a9[3 + a] = v[1][a] - v[0][a], a9[6 + a] = v[2][a] - v[0][a];
+}
 // triangle `face` of mesh `mesh_id` (m) into p: geometry, the mesh's material, its attribute index
 template <class R>
 __device__ __forceinline__ void triangle_into(PrimRec<R> &p, const MeshSrc &m, int32_t mesh_id, int32_t face, const double *__restrict__ positions,
                                               const int32_t *__restrict__ face_idx) {
-    const int32_t *idx = face_idx + 3 * ((int64_t)m.fbase + face);
-    R v[3][3];
-    for (int k = 0; k < 3; k++)
-        for (int a = 0; a < 3; a++) v[k][a] = (R)positions[3 * (m.pos_off + idx[k]) + a];
-    for (int a = 0; a < 3; a++) p.a[a] = v[0][a], p.a[3 + a] = v[1][a] - v[0][a], p.a[6 + a] = v[2][a] - v[0][a];
+    triangle_geometry(p.a, positions + 3 * m.pos_off, face_idx + 3 * ((int64_t)m.fbase + face));
     p.meta = PRIM_TRIANGLE | (m.tag << 8);
     p.material = m.material;
     p.mesh = mesh_id;
@@ -281,82 +290,84 @@ __global__ void __launch_bounds__(BLK) k_refit(int n_leaves, const int2 *__restr
     }
 }
 
-// One tree level of the collapse.  lvl[k] = number of wide nodes on level k (lvl[0] = 1 set by the caller);
-// node index = (nodes on earlier levels) + position in the level's frontier; frontier entries are BVH2 node ids.
-__global__ void __launch_bounds__(BLK) k_collapse(int level, const int *__restrict__ frontier_in, int *frontier_out, int *lvl, const int2 *__restrict__ child,
-                                                   const Box *__restrict__ ibox, const Box *__restrict__ lbox, int leaf_size, int n_prims, Node4<float> *nodes) {
-    int off_k = 0;
-    for (int j = 0; j < level; j++) off_k += lvl[j];
-    const int n_in = lvl[level], off_k1 = off_k + n_in;
-    const int lane = threadIdx.x & 63;
-    const int n_round = (n_in + 63) / 64 * 64;
-    for (int idx = blockIdx.x * BLK + threadIdx.x; idx < n_round; idx += gridDim.x * BLK) {
-        const bool valid = idx < n_in;
-        int kids[4] = {0, 0, 0, 0}, nk = 0, n_int = 0;
-        if (valid) {
-            const int2 c = child[frontier_in[idx]];
-            kids[0] = c.x, kids[1] = c.y, nk = 2;
-            while (nk < 4) {  // open the interior child with the largest surface area
-                int best = -1;
-                float best_area = -1.0f;
-                for (int i = 0; i < nk; i++)
-                    if (kids[i] >= 0) {
-                        const float a = half_area(ibox[kids[i]]);
-                        if (a > best_area) best_area = a, best = i;
-                    }
-                if (best < 0) break;
-                const int2 g = child[kids[best]];
-                kids[best] = g.x;
-                kids[nk++] = g.y;
+// The up to four children a wide node gets from BVH2 node `node`: its two children, then the interior child with the
+// largest surface area opened until there are four (or none is interior).  -> their number.
+__device__ __forceinline__ int wide_children(int node, const int2 *__restrict__ child, const Box *__restrict__ ibox, int kids[4]) {
+    const int2 c = child[node];
+    int nk = 2;
+    kids[0] = c.x, kids[1] = c.y, kids[2] = 0, kids[3] = 0;
+    while (nk < 4) {  // open the interior child with the largest surface area
+        int best = -1;
+        float best_area = -1.0f;
+        for (int i = 0; i < nk; i++)
+            if (kids[i] >= 0) {
+                const float a = half_area(ibox[kids[i]]);
+                if (a > best_area) best_area = a, best = i;
             }
-            for (int i = 0; i < nk; i++) n_int += kids[i] >= 0;
-            // slot order = visiting order of the (unranked) shadow-ray traversal: largest box first (tk_bvh.h)
-            float ar[4];
-            for (int i = 0; i < nk; i++) ar[i] = half_area(kids[i] >= 0 ? ibox[kids[i]] : lbox[~kids[i]]);
-            for (int i = 1; i < nk; i++)
-                for (int j = i; j > 0 && ar[j] > ar[j - 1]; j--) {
-                    const float ta = ar[j];
-                    ar[j] = ar[j - 1], ar[j - 1] = ta;
-                    const int tk = kids[j];
-                    kids[j] = kids[j - 1], kids[j - 1] = tk;
-                }
+        if (best < 0) break;
+        const int2 g = child[kids[best]];
+        kids[best] = g.x;
+        kids[nk++] = g.y;
+    }
+    return nk;
+}
+// One tree level of the collapse, in two launches around an exclusive scan.  The level's n_in wide nodes are made from
+// the BVH2 nodes frontier_in[0 .. n_in); node index = first (the nodes on earlier levels) + position in the frontier.
+// k_collapse_count: cnt[idx] = the interior children of node idx.  Their exclusive scan `off` numbers the next level's
+// nodes in the order of their parents — no atomic counter, so the node array is a function of the records alone: two
+// builds of the same input leave the same bytes (a scene whose vertices moved is compared with a fresh build byte for
+// byte, tests/test_gpu_mesh_update.py).  k_collapse writes the nodes, the next frontier and its size.
+__global__ void __launch_bounds__(BLK) k_collapse_count(const int *__restrict__ frontier_in, int n_in, const int2 *__restrict__ child,
+                                                         const Box *__restrict__ ibox, int *cnt) {
+    const int idx = blockIdx.x * BLK + threadIdx.x;
+    if (idx >= n_in) return;
+    int kids[4], n_int = 0;
+    const int nk = wide_children(frontier_in[idx], child, ibox, kids);
+    for (int i = 0; i < nk; i++) n_int += kids[i] >= 0;
+    cnt[idx] = n_int;
+}
+__global__ void __launch_bounds__(BLK) k_collapse(const int *__restrict__ frontier_in, int n_in, int first, const int *__restrict__ off, int *frontier_out,
+                                                   int *n_out, const int2 *__restrict__ child, const Box *__restrict__ ibox, const Box *__restrict__ lbox,
+                                                   int leaf_size, int n_prims, Node4<float> *nodes) {
+    const int idx = blockIdx.x * BLK + threadIdx.x;
+    if (idx >= n_in) return;
+    int kids[4];
+    const int nk = wide_children(frontier_in[idx], child, ibox, kids);
+    // slot order = visiting order of the (unranked) shadow-ray traversal: largest box first (tk_bvh.h)
+    float ar[4];
+    for (int i = 0; i < nk; i++) ar[i] = half_area(kids[i] >= 0 ? ibox[kids[i]] : lbox[~kids[i]]);
+    for (int i = 1; i < nk; i++)
+        for (int j = i; j > 0 && ar[j] > ar[j - 1]; j--) {
+            const float ta = ar[j];
+            ar[j] = ar[j - 1], ar[j - 1] = ta;
+            const int tk = kids[j];
+            kids[j] = kids[j - 1], kids[j - 1] = tk;
         }
-        // wave-aggregated allocation of the interior children on the next level
-        int incl = n_int;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
-        const int total = __shfl(incl, 63);
-        int base = 0;
-        if (lane == 0 && total) base = atomicAdd(&lvl[level + 1], total);
-        base = __shfl(base, 0);
-        if (valid) {
-            int next = base + incl - n_int;
-            Node4<float> nd;
-            for (int i = 0; i < 4; i++) {
-                NodeChild<float> &o = nd.c[i];
-                o.pad = 0;
-                if (i < nk) {
-                    const int k = kids[i];
-                    const Box b = k >= 0 ? ibox[k] : lbox[~k];
-                    for (int a = 0; a < 3; a++) o.bmin[a] = b.lo[a], o.bmax[a] = b.hi[a];
-                    if (k >= 0) {
-                        frontier_out[next] = k;
-                        o.child = off_k1 + next;
-                        next++;
-                    } else {
-                        const int first = (~k) * leaf_size;
-                        o.child = make_leaf(first, min(leaf_size, n_prims - first));
-                    }
-                } else {
-                    for (int a = 0; a < 3; a++) o.bmin[a] = __builtin_huge_valf(), o.bmax[a] = -__builtin_huge_valf();
-                    o.child = CHILD_EMPTY;
-                }
+    const int next_first = first + n_in;  // the next level's first node
+    int next = off[idx];
+    Node4<float> nd;
+    for (int i = 0; i < 4; i++) {
+        NodeChild<float> &o = nd.c[i];
+        o.pad = 0;
+        if (i < nk) {
+            const int k = kids[i];
+            const Box b = k >= 0 ? ibox[k] : lbox[~k];
+            for (int a = 0; a < 3; a++) o.bmin[a] = b.lo[a], o.bmax[a] = b.hi[a];
+            if (k >= 0) {
+                frontier_out[next] = k;
+                o.child = next_first + next;
+                next++;
+            } else {
+                const int first_prim = (~k) * leaf_size;
+                o.child = make_leaf(first_prim, min(leaf_size, n_prims - first_prim));
             }
-            nodes[off_k + idx] = nd;
+        } else {
+            for (int a = 0; a < 3; a++) o.bmin[a] = __builtin_huge_valf(), o.bmax[a] = -__builtin_huge_valf();
+            o.child = CHILD_EMPTY;
         }
     }
+    nodes[first + idx] = nd;
+    if (idx == n_in - 1) *n_out = next;  // the size of the next level
 }
 
 // acc[0] += sum of min(decoded area / true area, 100) over child boxes, acc[1] += number of child boxes
@@ -678,6 +689,69 @@ __global__ void __launch_bounds__(BLK) k_widen_tight(long long *tight, const lon
 template <class R> __global__ void __launch_bounds__(BLK) k_shift_roots(InstTrace<R> *trace, int n, int32_t delta) {
     const int i = blockIdx.x * BLK + threadIdx.x;
     if (i < n && trace[i].root_child >= 0) trace[i].root_child += delta;
+}
+
+
+// ---- moving the vertices of meshes of a RESIDENT scene without placements (tk_build.hip: update_mesh_vertices_device):
+// new positions (and vertex normals) of some meshes, everything else read from what the scene keeps in device memory.
+// new_pos[m] / new_nrm[m]: mesh m's new double arrays in device memory (its vertex 0 first), null = this mesh keeps its
+// own; shape_face: the description's shape_face, resident since creation (4 bytes per shape).
+
+// One lane per resident record, in the leaf order of the tree that is being replaced; the record goes to stage[its
+// shape id] — the shape order k_make_prims leaves for a fresh build (without placements the shape ids of the n records
+// are a permutation of 0 .. n-1).  A triangle of an updated mesh gets new geometry words (triangle_geometry, from the
+// resident face_idx at MeshInfo::fbase + face); every other word, and every other record, is copied.  A new coordinate
+// that is not finite as R writes nothing new into the record and leaves the smallest mesh << 32 | vertex in *bad (all
+// ones before).
+template <class R>
+__global__ void __launch_bounds__(BLK)
+k_update_prims(const PrimRec<R> *__restrict__ recs, int n, const double *const *__restrict__ new_pos, const MeshInfo *__restrict__ meshes,
+               const int32_t *__restrict__ shape_face, const int32_t *__restrict__ face_idx, PrimRec<R> *stage, unsigned long long *bad) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    PrimRec<R> p = recs[i];
+    if ((uint32_t)p.shape_id >= (uint32_t)n) return;  // (never: the host checked that the scene has one record per shape)
+    const double *pos = (p.meta & 0xff) == PRIM_TRIANGLE ? new_pos[p.mesh] : nullptr;
+    if (pos) {
+        const int32_t *idx = face_idx + 3 * ((int64_t)meshes[p.mesh].fbase + shape_face[p.shape_id]);
+        bool finite = true;
+        for (int k = 0; k < 3; k++)
+            for (int a = 0; a < 3; a++)
+                if (!__builtin_isfinite((R)pos[3 * (int64_t)idx[k] + a])) {
+                    finite = false;
+                    atomicMin(bad, ((unsigned long long)(uint32_t)p.mesh << 32) | (uint32_t)idx[k]);
+                }
+        if (finite) triangle_geometry(p.a, pos, idx);
+    }
+    stage[p.shape_id] = p;
+}
+// new vertex normals of one mesh as the scene keeps them: R(normal), what mesh_tables (tk_host_scene.h) stores
+template <class R> __global__ void __launch_bounds__(BLK) k_convert_normals(const double *__restrict__ in, int64_t n, R *out) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i < n) out[i] = (R)in[i];
+}
+// One lane per light record: an area light (kind 1) on a face of an updated mesh gets v[9] from the new positions and,
+// when the mesh got new normals, n[9] from them — light_records' expressions, R(position) and R(normal) of the face's
+// three vertices.  stage: the records in shape order (k_update_prims), which know the mesh of a shape.
+template <class R>
+__global__ void __launch_bounds__(BLK)
+k_update_lights(LightRec<R> *lights, int n_lights, const PrimRec<R> *__restrict__ stage, int n_shapes, const double *const *__restrict__ new_pos,
+                const double *const *__restrict__ new_nrm, const MeshInfo *__restrict__ meshes, const int32_t *__restrict__ shape_face,
+                const int32_t *__restrict__ face_idx) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n_lights) return;
+    LightRec<R> &l = lights[i];
+    const int32_t shape = l.shape_id;
+    if (l.kind != 1 || l.is_sphere || (uint32_t)shape >= (uint32_t)n_shapes) return;
+    const int32_t mesh = stage[shape].mesh;
+    const double *pos = new_pos[mesh], *nrm = new_nrm[mesh];
+    if (!pos) return;
+    const int32_t *idx = face_idx + 3 * ((int64_t)meshes[mesh].fbase + shape_face[shape]);
+    for (int k = 0; k < 3; k++)
+        for (int a = 0; a < 3; a++) {
+            l.v[3 * k + a] = (R)pos[3 * (int64_t)idx[k] + a];
+            if (nrm) l.n[3 * k + a] = (R)nrm[3 * (int64_t)idx[k] + a];
+        }
 }
 
 }  // namespace lbvh

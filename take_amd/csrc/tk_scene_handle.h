@@ -5,6 +5,8 @@
 #pragma once
 #include <chrono>
 #include <cstdio>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "tk_host.h"
@@ -139,6 +141,13 @@ struct TakeScene {
     TakeRenderOpts acc_opts{};
     bool acc_restart_needed = false;  // the scene changed (new transforms, a new camera): the next accumulate call has to restart
     int64_t n_placements = 0;         // TakeSceneDesc.n_instances of a two-level scene (0: none, or flattened at creation)
+    // what take_hip_scene_set_mesh_vertices needs to know of the description the scene was created from (a replica of
+    // a scene group knows none of it: groups take no updates)
+    std::vector<int64_t> mesh_vertices;   // per mesh: its vertex count
+    tk_host::DevBuf<int32_t> shape_face;  // TakeSceneDesc.shape_face in device memory (scenes without placements), shared by both sides
+    int max_leaf = 0;                     // the leaf size request the trees were built with (TakeBuildOpts / TAKE_HIP_MAX_LEAF)
+    bool flattened = false;               // TAKE_INSTANCES_FLATTEN expanded placements: the meshes are no longer the caller's
+    std::string node_knob;                // TAKE_HIP_NODES when the scene was built
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
     int instrumentation = 0;
     tk_host::SceneT<float> f;
@@ -222,7 +231,8 @@ struct DeviceBuildInputs {
     const int32_t *face_idx = nullptr;    // the validated face indices on the device: the array of the side that uploaded them
     bool ready = false;
     int upload(const TakeSceneDesc &d, const double *const *device_positions);  // (a no-op for the second side)
-    void release() { pos.release(), kind.release(), ref.release(), face.release(), area_light.release(); }
+    // (`face` stays: a scene without placements keeps it resident for take_hip_scene_set_mesh_vertices, 4 bytes per shape)
+    void release() { pos.release(), kind.release(), ref.release(), area_light.release(); }
 };
 // Records and trees of one side of a new scene, made on the device (the LBVH builder, tk_build_gpu.h).  In: sc.host as
 // prepare_scene(PREP_DEVICE_BUILD) leaves it; `in`: shared by the sides of the scene, uploaded by the first and released
@@ -257,5 +267,35 @@ template <class R> struct ReposeStage {
     int commit(SceneT<R> &sc);
 };
 template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n, ReposeStage<R> &out);
+
+// New vertex positions (and vertex normals) for some meshes of a resident scene WITHOUT placements
+// (take_hip_scene_set_mesh_vertices): the records are rewritten from what the scene keeps — its records, face_idx,
+// MeshInfo, shape_face — and the tree is built again by creation's own tail (build_bvh_device), so the result is the
+// bytes a fresh device build of the description with the new arrays leaves.
+// MeshUpdateInputs: the new arrays in device memory, shared by the sides of the scene — host arrays uploaded (pinned in
+// place, one buffer per updated array), device arrays borrowed — and per mesh of the scene a pointer or null.
+struct MeshUpdateInputs {
+    std::vector<DevBuf<double>> owned;
+    std::vector<const double *> pos, nrm;  // per mesh: new positions / normals in device memory, null = keeps its own
+    DevBuf<const double *> d_pos, d_nrm;   // the same tables in device memory
+    int upload(const std::vector<int64_t> &mesh_vertices, const TakeMeshUpdate *updates, int32_t n_updates);
+};
+// Everything is built into `out` and sc stays as it is — a failure, or the failure of the other side of a mixed scene,
+// changes nothing; commit() then moves it into the scene.
+// Returns TAKE_OK or an error with its message: TAKE_E_INVALID naming mesh and vertex of the first coordinate that is
+// not finite, or starting with "unsupported" when the new tree has fewer than two leaves or is too deep for the
+// traversal stack.  compressed_ok / _forced: as build_side_on_device.
+template <class R> struct MeshUpdateStage {
+    // a side of its own that creation's tail builds into: prims (leaf order), qnodes or nodes, lights and their tables,
+    // host.stats / root_child / grid / q_inflation / lights / light_pmf / light_cdf, trace — and, when the node format
+    // changed, the trace state of the new kernel instance (alloc_trace_state)
+    SceneT<R> built;
+    // built.normals: with new normals, the scene's whole array copied and the named meshes' parts rewritten
+    bool new_lights = false, new_normals = false, new_trace_state = false;
+    void commit(SceneT<R> &sc);  // moves only: it cannot fail, so a mixed scene gets both sides or neither
+};
+template <class R>
+int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
+                                int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out);
 
 }  // namespace tk_host
