@@ -1,5 +1,5 @@
 // tk_build.hip — the host driver of the device LBVH builder: the records and trees of one side of a new scene made on
-// the device from the caller's arrays (build_side_on_device, declared in tk_scene_handle.h; tk_api.hip's upload_scene
+// the device from the caller's arrays (build_side_on_device, declared in tk_scene_handle.h; tk_create.hip's upload_scene
 // calls it), and the top-level half of it entered again for a resident scene whose placements get new transforms
 // (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it), and creation's tail entered
 // again for a resident scene whose meshes get new vertices (update_mesh_vertices_device;
@@ -105,15 +105,36 @@ template <class R> void span_boxes(const PrimRec<R> *recs, int n, lbvh::Box *pb,
     if (n > 0) hipLaunchKernelGGL(lbvh::k_prim_boxes<R>, blocks_for(n), dim3(lbvh::BLK), 0, nullptr, recs, n, pb, ord.p);
 }
 
+// The first offender a checking kernel met (atomicMin into cell: one word, allocated and set to `none`, which no offender is, by arm())
+template <class T> struct FirstOffender {
+    T none, first = none;
+    DevBuf<T> cell;
+    hipError_t arm() { return cell.upload({none}); }
+    hipError_t read() { return hipMemcpy(&first, cell.p, sizeof(T), hipMemcpyDeviceToHost); }  // (waits for the kernel)
+};
+// A side takes a new tree, its arrays moved into sc already: what the host keeps of it (sc.host), what the kernels read (sc.dev)
+template <class R> void install_tree(SceneT<R> &sc, int64_t n_nodes, int depth, int32_t root_child, const float *grid_lo, const float *grid_step) {
+    sc.host.stats.n_nodes = n_nodes, sc.host.stats.depth = depth, sc.dev.n_nodes = (int32_t)n_nodes;
+    sc.host.root_child = sc.dev.root_child = root_child;
+    for (int a = 0; a < 3; a++) sc.host.grid_lo[a] = sc.dev.grid_lo[a] = grid_lo[a], sc.host.grid_step[a] = sc.dev.grid_step[a] = grid_step[a];
+    sc.bind();
+}
+// Next to a device build's TAKE_OK (`why`: callers start it at Built): the tree was built — or why it is the host builder's to make
+enum class BuildVerdict { Built, TooFewLeaves, TooDeep };
+// what an entry with no host builder to turn to returns for a build that ended in rc, or in why; what: "tree", "top-level tree"
+int unsupported(int rc, BuildVerdict why, const std::string &what) {
+    return rc ? rc : fail(TAKE_E_INVALID, why == BuildVerdict::TooFewLeaves ? "unsupported: a " + what + " of fewer than two leaves"
+                                                                           : "unsupported: the new " + what + " is too deep for the traversal stack");
+}
+
 // In: the n boxes of a span (pb: freed here, once the leaves exist) and their bounds (scene_ord: ordered ints, as
-// k_prim_boxes leaves them).  Out: t.  Returns TAKE_OK, an error, or 1 = "use the host builder": fewer than two leaves,
-// or a tree deeper than the traversal stack allows (long runs of equal Morton codes).
+// k_prim_boxes leaves them).  Out: t.  TooDeep: long runs of equal Morton codes.
 // The tree is made of float nodes whatever the scene's precision is (tk_build_gpu.h: only records and primitive boxes
 // know it).
-int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n, int leaf_size, BuildMemory &mem, DeviceTree &t) {
+int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n, int leaf_size, BuildMemory &mem, DeviceTree &t, BuildVerdict &why) {
     using namespace lbvh;
     const int n_leaves = (n + leaf_size - 1) / leaf_size;
-    if (n_leaves < 2) return 1;
+    if (n_leaves < 2) return why = BuildVerdict::TooFewLeaves, TAKE_OK;
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     // (a release waits for the kernels launched before it: hipFree synchronises the device)
@@ -170,7 +191,7 @@ int build_tree_device(DevBuf<lbvh::Box> &pb, const DevBuf<int> &scene_ord, int n
     t.n_nodes = 0, t.depth = 0;
     int n_in = 1;
     for (int level = 0; n_in > 0; level++) {
-        if (level == MAX_LEVELS) return 1;  // deeper than the traversal stack allows
+        if (level == MAX_LEVELS) return why = BuildVerdict::TooDeep, TAKE_OK;
         size_t need = 0;
         HIP_TRY(rocprim::exclusive_scan(nullptr, need, cnt.p, off.p, 0, (size_t)n_in, rocprim::plus<int>(), stream));
         if (need > temp.bytes()) HIP_TRY(temp.alloc(need));
@@ -266,13 +287,12 @@ template <class R> void init_stats(HostScene<R> &h, int64_t n_nodes, int64_t n_p
 }
 
 // BVH build on the device of a scene without placements.  In: sc.prims uploaded in SHAPE order.  Out: the records in
-// leaf order, sc.nodes or sc.qnodes, host-side stats and grid.  Returns TAKE_OK, an error, or 1 = "use the host
-// builder" (build_tree_device).  A double scene that is refused compression gets its float nodes widened.
-template <class R> int build_bvh_device(SceneT<R> &sc, int max_leaf, bool compressed_ok, bool compressed_forced) {
+// leaf order, sc.nodes or sc.qnodes, host-side stats and grid.  A double scene refused compression gets its float nodes widened.
+template <class R> int build_bvh_device(SceneT<R> &sc, int max_leaf, bool compressed_ok, bool compressed_forced, BuildVerdict &why) {
     using namespace lbvh;
     const int n = (int)sc.prims.n;
     const int leaf_size = device_leaf_size(max_leaf);
-    if ((n + leaf_size - 1) / leaf_size < 2) return 1;
+    if ((n + leaf_size - 1) / leaf_size < 2) return why = BuildVerdict::TooFewLeaves, TAKE_OK;
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     BuildMemory mem(sizeof(R) == 4 ? "f32" : "f64");
@@ -283,8 +303,8 @@ template <class R> int build_bvh_device(SceneT<R> &sc, int max_leaf, bool compre
     HIP_TRY(scene_ord.alloc(6));
     HIP_TRY(reset_bounds(scene_ord));
     span_boxes(sc.prims.p, n, pb.p, scene_ord);
-    const int rt = build_tree_device(pb, scene_ord, n, leaf_size, mem, t);
-    if (rt) return rt;
+    const int rt = build_tree_device(pb, scene_ord, n, leaf_size, mem, t, why);
+    if (rt || why != BuildVerdict::Built) return rt;
     init_stats(sc.host, t.n_nodes, n, t.depth);
     bool compressed;
     std::vector<QGrid> grids;
@@ -344,23 +364,53 @@ template <class R> int make_prims_on_device(SceneT<R> &sc, const TakeSceneDesc &
     return TAKE_OK;
 }
 
+// per placement the empty bounds (six ordered long longs) that k_placement_boxes* grow and k_placement_pad reads
+std::vector<long long> empty_tight(int n_inst) {
+    std::vector<long long> tight(6 * (size_t)n_inst);
+    for (size_t i = 0; i < tight.size(); i++) tight[i] = i % 6 < 3 ? INT64_MAX : INT64_MIN;
+    return tight;
+}
+// Step 3's finish of a built top-level tree: the shapes' records `src` into leaf order at the head of dst (empty: the head alone, allocated
+// here).  TooDeep: the traversal stack holds both levels (proto_depth: the prototypes') and one return marker.
+template <class R> int finish_top_level(DeviceTree &top, int proto_depth, int n_shapes, int n_top, const PrimRec<R> *src, DevBuf<PrimRec<R>> &dst, BuildVerdict &why) {
+    using namespace lbvh;
+    if (3 * (top.depth + proto_depth) + 2 > MAX_STACK_ENTRIES) return why = BuildVerdict::TooDeep, TAKE_OK;
+    DevBuf<int> is_shape, rank;
+    DevBuf<char> temp;
+    HIP_TRY(is_shape.alloc(n_top));
+    HIP_TRY(rank.alloc(n_top));
+    if (!dst.p) HIP_TRY(dst.alloc(n_shapes));
+    hipLaunchKernelGGL(k_flag_shapes, blocks_for(n_top), dim3(BLK), 0, nullptr, top.order.p, n_top, n_shapes, is_shape.p);
+    size_t temp_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), nullptr));
+    HIP_TRY(temp.alloc(temp_bytes));
+    HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), nullptr));
+    hipLaunchKernelGGL(k_top_leaves, blocks_for(top.n_nodes), dim3(BLK), 0, nullptr, top.nodes.p, (int)top.n_nodes, top.order.p, rank.p, n_shapes);
+    if (n_shapes > 0)  // (a scene of placements only: nothing to write, and dst may be empty)
+        hipLaunchKernelGGL((k_permute_top<PrimRec<R>>), blocks_for(n_top), dim3(BLK), 0, nullptr, src, top.order.p, rank.p, n_top, n_shapes, dst.p);
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipGetLastError());
+    top.order.release();
+    return TAKE_OK;
+}
+
 // BVH build on the device of a two-level scene (TakeInstance placements, TAKE_INSTANCES_TWO_LEVEL): the scene
 // build_host_trees makes, with LBVH trees.  In: sc.prims = the shapes' records in shape order (possibly none),
 // sc.face_idx, sc.host as prepare_scene(PREP_DEVICE_BUILD) leaves it (the placements' records and the PlacementPlan),
 // `in` still holding the positions.  Out: sc.prims = the top-level tree's records in leaf order, then each prototype's;
 // sc.qnodes or sc.nodes = the top-level tree's nodes, then each prototype's, child words global; the placements'
-// root_child and grid; stats.  Returns TAKE_OK, an error, or 1 = "use the host builder" — for the whole scene: a tree
-// of fewer than two leaves (a one-face prototype) or too deep a stack over both levels.
+// root_child and grid; stats.  Any verdict but Built is for the whole scene: a tree of fewer than two leaves (a
+// one-face prototype) or too deep a stack over both levels.
 //   1. per distinct prototype, one pass: k_make_proto_prims -> k_prim_boxes -> build_tree_device; its records go
 //      straight to their place behind the shapes' records, its float nodes wait (cut to size) for step 4;
 //   2. k_placement_boxes / k_placement_pad: the placements' boxes behind the shapes' boxes (host formula beyond 4e8
 //      vertex transforms, placement_box);
 //   3. the top-level tree over both, ONE entry per leaf whatever max_leaf is (a placement is a leaf of its own, and
-//      the compacted record ranges of k_top_leaves are single records); k_top_leaves, k_permute_top;
+//      the compacted record ranges of k_top_leaves are single records); finish_top_level;
 //   4. every tree quantised on its own grid into the scene's node array — the worst inflation over all trees decides
 //      for the whole scene between compressed and full-width nodes, as quantise_trees does — and k_rebase.
 template <class R>
-int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBuildInputs &in, int max_leaf, bool compressed_ok, bool compressed_forced) {
+int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBuildInputs &in, int max_leaf, bool compressed_ok, bool compressed_forced, BuildVerdict &why) {
     using namespace lbvh;
     HostScene<R> &h = sc.host;
     const PlacementPlan &plan = h.placements;
@@ -370,12 +420,12 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     BuildMemory mem(sizeof(R) == 4 ? "f32" : "f64");
-    if (n_top < 2) return 1;
+    if (n_top < 2) return why = BuildVerdict::TooFewLeaves, TAKE_OK;
     std::vector<int64_t> prim_base(n_protos + 1), node_at(n_protos + 2, 0);  // node_at: the top-level tree's nodes (0), each prototype's, the end
     prim_base[0] = n_shapes;
     for (int k = 0; k < n_protos; k++) {
         const int64_t nf = d.meshes[plan.proto_mesh[k]].n_faces;
-        if ((nf + leaf_size - 1) / leaf_size < 2) return 1;
+        if ((nf + leaf_size - 1) / leaf_size < 2) return why = BuildVerdict::TooFewLeaves, TAKE_OK;
         prim_base[k + 1] = prim_base[k] + nf;
     }
     if (prim_base[n_protos] >= ((int64_t)1 << 28)) return fail(TAKE_E_INVALID, "too many primitive records for the 4-wide leaf encoding (2^28)");
@@ -397,8 +447,8 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
         hipLaunchKernelGGL(k_make_proto_prims<R>, blocks_for(nf), blk, 0, stream, mesh_src(h, in, mesh), mesh, in.pos.p, sc.face_idx.p, nf, recs.p);
         span_boxes(recs.p, nf, pb.p, scene_ord);
         DeviceTree &t = protos[k];
-        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t);
-        if (rt) return rt;
+        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t, why);
+        if (rt || why != BuildVerdict::Built) return rt;
         hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), blk, 0, stream, recs.p, t.order.p, nf, prims.p + prim_base[k]);
         DevBuf<Node4<float>> cut;  // (the collapse allocates a node per leaf and uses about a third)
         HIP_TRY(cut.alloc((size_t)t.n_nodes));
@@ -415,11 +465,10 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     HIP_TRY(reset_bounds(scene_ord));
     span_boxes(sc.prims.p, n_shapes, pb.p, scene_ord);
     {
-        std::vector<long long> tight_h(6 * (size_t)n_inst);
+        std::vector<long long> tight_h = empty_tight(n_inst);
         std::vector<double> xf(12 * (size_t)n_inst);
         std::vector<std::vector<int32_t>> of_proto(n_protos);
         for (int i = 0; i < n_inst; i++) {
-            for (int a = 0; a < 3; a++) tight_h[6 * (size_t)i + a] = INT64_MAX, tight_h[6 * (size_t)i + 3 + a] = INT64_MIN;
             std::memcpy(&xf[12 * (size_t)i], d.instances[i].xform, 12 * sizeof(double));
             of_proto[plan.inst_proto[i]].push_back(i);
         }
@@ -458,26 +507,9 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
 
     // 3. the top-level tree
     DeviceTree top;
-    const int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top);
-    if (rt) return rt;
-    const int depth = top.depth + proto_depth;
-    if (3 * depth + 2 > MAX_STACK_ENTRIES) return 1;  // the traversal stack holds both levels and one return marker
-    {
-        DevBuf<int> is_shape, rank;
-        DevBuf<char> temp;
-        HIP_TRY(is_shape.alloc(n_top));
-        HIP_TRY(rank.alloc(n_top));
-        hipLaunchKernelGGL(k_flag_shapes, blocks_for(n_top), blk, 0, stream, top.order.p, n_top, n_shapes, is_shape.p);
-        size_t temp_bytes = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        HIP_TRY(temp.alloc(temp_bytes));
-        HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        hipLaunchKernelGGL(k_top_leaves, blocks_for(top.n_nodes), blk, 0, stream, top.nodes.p, (int)top.n_nodes, top.order.p, rank.p, n_shapes);
-        hipLaunchKernelGGL((k_permute_top<PrimRec<R>>), blocks_for(n_top), blk, 0, stream, sc.prims.p, top.order.p, rank.p, n_top, n_shapes, prims.p);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-    }
-    top.order.release();
+    int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top, why);
+    if (!rt && why == BuildVerdict::Built) rt = finish_top_level(top, proto_depth, n_shapes, n_top, sc.prims.p, prims, why);
+    if (rt || why != BuildVerdict::Built) return rt;
     sc.prims = std::move(prims);  // (frees the shape-order records)
 
     // 4. assembly: the top-level tree's nodes, then each prototype's
@@ -486,7 +518,7 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     for (int k = 0; k <= n_protos; k++) node_at[k + 1] = node_at[k] + trees[k]->n_nodes;
     const int64_t n_nodes = node_at[n_protos + 1];
     if (n_nodes >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many nodes");
-    init_stats(h, n_nodes, n_shapes, depth);
+    init_stats(h, n_nodes, n_shapes, top.depth + proto_depth);
     h.n_blas = n_protos, h.blas_nodes = n_nodes - top.n_nodes, h.blas_prims = prim_base[n_protos] - n_shapes;
     h.blas_depth = proto_depth;
     h.blas_prim_first.assign(prim_base.begin(), prim_base.begin() + n_protos), h.blas_prim_count.resize(n_protos);
@@ -523,14 +555,15 @@ template <class R>
 int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions, int max_leaf,
                          bool compressed_ok, bool compressed_forced, bool last_side, PhaseClock &clock) {
     const bool two_level = d.n_instances > 0;
+    BuildVerdict why = BuildVerdict::Built;
     int rc = make_prims_on_device(sc, d, in, device_positions);
     // (positions and shape arrays: not part of the build's peak — but a two-level build reads the prototypes' positions)
     if (last_side && !two_level) in.release();
     clock.lap("mesh arrays -> HBM, records");
-    if (!rc) rc = two_level ? build_two_level_device(sc, d, in, max_leaf, compressed_ok, compressed_forced)
-                            : build_bvh_device(sc, max_leaf, compressed_ok, compressed_forced);
+    if (!rc) rc = two_level ? build_two_level_device(sc, d, in, max_leaf, compressed_ok, compressed_forced, why)
+                            : build_bvh_device(sc, max_leaf, compressed_ok, compressed_forced, why);
     if (last_side) in.release();
-    return rc;
+    return rc || why == BuildVerdict::Built ? rc : 1;  // (the one bare 1: "use the host builder", whatever the verdict)
 }
 template int build_side_on_device<float>(SceneT<float> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
 template int build_side_on_device<double>(SceneT<double> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
@@ -547,18 +580,15 @@ template <class R> int repose_two_level_device(const SceneT<R> &sc, const double
 
     // 1. the placements' records; a transform that cannot be inverted is reported before anything else is made
     {
-        DevBuf<int> bad;
-        const int none = INT32_MAX;
-        int bad_h = none;
+        FirstOffender<int> bad{INT32_MAX};
         HIP_TRY(out.inst_trace.alloc(n_inst));
         HIP_TRY(out.inst_shade.alloc(n_inst));
-        HIP_TRY(bad.alloc(1));
-        HIP_TRY(hipMemcpyAsync(bad.p, &none, sizeof(int), hipMemcpyHostToDevice, stream));
+        HIP_TRY(bad.arm());
         hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), blk, 0, stream, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p,
-                           out.inst_trace.p, out.inst_shade.p, bad.p);
-        HIP_TRY(hipMemcpy(&bad_h, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+                           out.inst_trace.p, out.inst_shade.p, bad.cell.p);
+        HIP_TRY(bad.read());
         HIP_TRY(hipGetLastError());
-        if (bad_h != none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad_h) + ": singular or non-finite transform");
+        if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
     }
 
     // 2. tight world boxes from the prototypes' resident records, 3. the shapes' boxes from theirs: the head of the
@@ -572,13 +602,12 @@ template <class R> int repose_two_level_device(const SceneT<R> &sc, const double
     {
         std::vector<int2> span_h((size_t)n_inst);
         std::vector<int64_t> block0_h((size_t)n_inst + 1, 0);
-        std::vector<long long> tight_h(6 * (size_t)n_inst);
+        const std::vector<long long> tight_h = empty_tight(n_inst);
         for (int i = 0; i < n_inst; i++) {
             const int k = h.placements.inst_proto[i];
             if (k < 0 || k >= n_protos) return fail(TAKE_E_INVALID, "the scene does not know the prototype of placement " + std::to_string(i));
             span_h[i] = make_int2((int)h.blas_prim_first[k], (int)h.blas_prim_count[k]);
             block0_h[i + 1] = block0_h[i] + (h.blas_prim_count[k] + REPOSE_CHUNK - 1) / REPOSE_CHUNK;
-            for (int a = 0; a < 3; a++) tight_h[6 * (size_t)i + a] = INT64_MAX, tight_h[6 * (size_t)i + 3 + a] = INT64_MIN;
         }
         if (block0_h[n_inst] >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "unsupported: too many prototype records times placements for one launch");
         DevBuf<int2> span;
@@ -603,30 +632,11 @@ template <class R> int repose_two_level_device(const SceneT<R> &sc, const double
     // group of coincident records holds its shape ids in ascending order (order_coincident; a stable sort of the shape
     // order) and keeps them so here: equal geometry is equal boxes is equal Morton codes, and the sort is stable.
     DeviceTree top;
-    const int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top);
-    if (rt == 1) return fail(TAKE_E_INVALID, n_top < 2 ? "unsupported: a top-level tree of fewer than two leaves"
-                                                       : "unsupported: the new top-level tree is too deep for the traversal stack");
-    if (rt) return rt;
+    BuildVerdict why = BuildVerdict::Built;
+    int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top, why);
+    if (!rt && why == BuildVerdict::Built) rt = finish_top_level(top, h.blas_depth, n_shapes, n_top, sc.prims.p, out.head, why);
+    if (rt || why != BuildVerdict::Built) return unsupported(rt, why, "top-level tree");
     out.depth = top.depth + h.blas_depth;
-    if (3 * out.depth + 2 > MAX_STACK_ENTRIES) return fail(TAKE_E_INVALID, "unsupported: the new top-level tree is too deep for the traversal stack");
-    {
-        DevBuf<int> is_shape, rank;
-        DevBuf<char> temp;
-        HIP_TRY(is_shape.alloc(n_top));
-        HIP_TRY(rank.alloc(n_top));
-        HIP_TRY(out.head.alloc(n_shapes));
-        hipLaunchKernelGGL(k_flag_shapes, blocks_for(n_top), blk, 0, stream, top.order.p, n_top, n_shapes, is_shape.p);
-        size_t temp_bytes = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        HIP_TRY(temp.alloc(temp_bytes));
-        HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, is_shape.p, rank.p, 0, (size_t)n_top, rocprim::plus<int>(), stream));
-        hipLaunchKernelGGL(k_top_leaves, blocks_for(top.n_nodes), blk, 0, stream, top.nodes.p, (int)top.n_nodes, top.order.p, rank.p, n_shapes);
-        if (n_shapes > 0)
-            hipLaunchKernelGGL((k_permute_top<PrimRec<R>>), blocks_for(n_top), blk, 0, stream, sc.prims.p, top.order.p, rank.p, n_top, n_shapes, out.head.p);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-    }
-    top.order.release();
 
     // 5. assembly in the scene's node format: the new top-level tree on its own grid, the prototypes' nodes copied behind
     // it — moved by the difference of the two top-level trees' sizes, and their child words and the placements' roots with them
@@ -661,16 +671,11 @@ template <class R> int repose_two_level_device(const SceneT<R> &sc, const double
     return TAKE_OK;
 }
 template <class R> int ReposeStage<R>::commit(SceneT<R> &sc) {
-    HostScene<R> &h = sc.host;
     if (head.n) HIP_TRY(hipMemcpy(sc.prims.p, head.p, head.bytes(), hipMemcpyDeviceToDevice));
     if (qnodes.p) sc.qnodes = std::move(qnodes);
     else sc.nodes = std::move(nodes);
     sc.inst_trace = std::move(inst_trace), sc.inst_shade = std::move(inst_shade);
-    h.stats.n_nodes = n_nodes, h.stats.depth = depth;
-    h.root_child = 0;  // (the new tree has at least two leaves: its root is node 0)
-    for (int a = 0; a < 3; a++) h.grid_lo[a] = sc.dev.grid_lo[a] = grid_lo[a], h.grid_step[a] = sc.dev.grid_step[a] = grid_step[a];
-    sc.dev.root_child = 0, sc.dev.n_nodes = (int32_t)n_nodes;
-    sc.bind();
+    install_tree(sc, n_nodes, depth, 0, grid_lo, grid_step);  // (the new tree has at least two leaves: its root is node 0)
     return TAKE_OK;
 }
 template struct ReposeStage<float>;
@@ -716,17 +721,14 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
 
     // 1. the records, back in shape order; a coordinate that is not finite is reported before anything else is made
     {
-        DevBuf<unsigned long long> bad;
-        const unsigned long long none = ~0ull;
-        unsigned long long bad_h = none;
+        FirstOffender<unsigned long long> bad{~0ull};
         HIP_TRY(b.prims.alloc((size_t)n));
-        HIP_TRY(bad.alloc(1));
-        HIP_TRY(hipMemcpyAsync(bad.p, &none, sizeof(none), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n), blk, 0, stream, sc.prims.p, n, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p, b.prims.p, bad.p);
-        HIP_TRY(hipMemcpy(&bad_h, bad.p, sizeof(bad_h), hipMemcpyDeviceToHost));
+        HIP_TRY(bad.arm());
+        hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n), blk, 0, stream, sc.prims.p, n, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p, b.prims.p, bad.cell.p);
+        HIP_TRY(bad.read());
         HIP_TRY(hipGetLastError());
-        if (bad_h != none)
-            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad_h >> 32) + ": vertex " + std::to_string(bad_h & 0xffffffffull) + ": a new position is not finite");
+        if (bad.first != bad.none)
+            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
     }
 
     // 2. new vertex normals as the scene keeps them: a copy of the scene's whole array with the named meshes' parts
@@ -759,13 +761,9 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
     }
 
     // 4. creation's tail: boxes, tree, nodes in the format the inflation rule chooses, records into leaf order
-    const int rb = build_bvh_device(b, max_leaf, compressed_ok, compressed_forced);
-    if (rb == 1) {
-        const int leaf_size = device_leaf_size(max_leaf);
-        return fail(TAKE_E_INVALID, (n + leaf_size - 1) / leaf_size < 2 ? "unsupported: a tree of fewer than two leaves"
-                                                                        : "unsupported: the new tree is too deep for the traversal stack");
-    }
-    if (rb) return rb;
+    BuildVerdict why = BuildVerdict::Built;
+    const int rb = build_bvh_device(b, max_leaf, compressed_ok, compressed_forced, why);
+    if (rb || why != BuildVerdict::Built) return unsupported(rb, why, "tree");
     b.trace = TraceKind{b.qnodes.p ? NodeFormat::Q4 : NodeFormat::WIDE, false};
     if ((uint64_t)b.host.stats.n_nodes * node_bytes<R>(b.trace.nodes) >= (1ull << 32))
         return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
@@ -777,26 +775,23 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
     }
     return TAKE_OK;
 }
-template <class R> void MeshUpdateStage<R>::commit(SceneT<R> &sc) {
-    SceneT<R> &b = built;
-    HostScene<R> &h = sc.host;
-    if (new_normals) sc.normals = std::move(b.normals);
-    sc.prims = std::move(b.prims);
-    sc.qnodes = std::move(b.qnodes), sc.nodes = std::move(b.nodes);  // (the one the new format does not use is empty: the scene's is freed)
+template <class R> int MeshUpdateStage<R>::commit(SceneT<R> &sc) {
+    if (new_normals) sc.normals = std::move(built.normals);
+    sc.prims = std::move(built.prims);
+    sc.qnodes = std::move(built.qnodes), sc.nodes = std::move(built.nodes);  // (the one the new format does not use is empty: the scene's is freed)
     if (new_lights) {
-        sc.lights = std::move(b.lights), sc.light_pmf = std::move(b.light_pmf), sc.light_cdf = std::move(b.light_cdf);
-        h.lights = std::move(b.host.lights), h.light_pmf = std::move(b.host.light_pmf), h.light_cdf = std::move(b.host.light_cdf);
+        sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
+        sc.host.lights = std::move(built.host.lights), sc.host.light_pmf = std::move(built.host.light_pmf), sc.host.light_cdf = std::move(built.host.light_cdf);
     }
-    h.stats = b.host.stats, h.root_child = b.host.root_child, h.q_inflation = b.host.q_inflation, h.node_width = 4;
-    for (int a = 0; a < 3; a++) h.grid_lo[a] = sc.dev.grid_lo[a] = b.host.grid_lo[a], h.grid_step[a] = sc.dev.grid_step[a] = b.host.grid_step[a];
-    sc.dev.root_child = h.root_child, sc.dev.n_nodes = (int32_t)h.stats.n_nodes;
-    sc.trace = b.trace;
+    sc.host.stats = built.host.stats, sc.host.q_inflation = built.host.q_inflation, sc.host.node_width = 4;  // (stats: n_prims and sah too)
+    install_tree(sc, built.host.stats.n_nodes, built.host.stats.depth, built.host.root_child, built.host.grid_lo, built.host.grid_step);
+    sc.trace = built.trace;
     sc.built_on_device = true;  // whoever built the tree that is gone
     if (new_trace_state) {
-        sc.qwords = std::move(b.qwords), sc.counters = std::move(b.counters), sc.spill = std::move(b.spill);
-        sc.blocks_per_cu = b.blocks_per_cu, sc.spill_levels = b.spill_levels, sc.trace_grid = b.trace_grid, sc.spill_stride = b.spill_stride;
+        sc.qwords = std::move(built.qwords), sc.counters = std::move(built.counters), sc.spill = std::move(built.spill);
+        sc.blocks_per_cu = built.blocks_per_cu, sc.spill_levels = built.spill_levels, sc.trace_grid = built.trace_grid, sc.spill_stride = built.spill_stride;
     }
-    sc.bind();
+    return TAKE_OK;
 }
 template struct MeshUpdateStage<float>;
 template struct MeshUpdateStage<double>;

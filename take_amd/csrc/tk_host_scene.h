@@ -1,6 +1,6 @@
 // tk_host_scene.h — host-side preparation of a scene: validates a TakeSceneDesc, converts it to the
 // R-typed arrays of tk_scene.h, builds the wide BVH.  The result is a set of plain host vectors; the C-ABI
-// layer (tk_api.hip: upload_scene) uploads them to HBM.  Counterpart of the part of the reference's render() between
+// layer (tk_create.hip: upload_scene) uploads them to HBM.  Counterpart of the part of the reference's render() between
 // parse_scene and the tile loop (src/render.cpp:37-50) plus build_bvh (src/scene.cpp:4-23).
 // prepare_scene runs the steps: counts and camera, mesh_tables, material_table, image_table, validate_shape /
 // shape_record per shape, light_records (env_light), light_power_tables, build_trees, records into leaf order;
@@ -64,7 +64,7 @@ template <class R> struct HostScene {
     uint32_t tag_mask = 0;    // bit t set: some material has tag t
     int single_tag = 0;       // the tag when n_material_tags == 1
 
-    // pointers into the vectors above (a host "device scene" for tests/hostsim; tk_api.hip's upload_scene builds the real one)
+    // pointers into the vectors above (a host "device scene" for tests/hostsim; tk_create.hip's upload_scene builds the real one)
     DeviceScene<R> view() const {
         DeviceScene<R> d{};
         d.nodes = nodes.data();
@@ -179,7 +179,7 @@ template <class F> inline std::string for_chunks(int64_t n, int threads, F fn) {
 }
 
 // A placement transform (TakeInstance::xform: 3x4, row-major, object -> world), in double.  The expressions are the ones
-// the flattening of tk_api.hip (FlattenedInstances) and SceneData.flattened() use, operand order included: the "instanced equals flattened"
+// the flattening of tk_create.hip (FlattenedInstances) and SceneData.flattened() use, operand order included: the "instanced equals flattened"
 // tests compare bits.
 struct Affine3 {
     const double *m;

@@ -1,6 +1,6 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace, the kernel launchers, the wavefront
 // render loop, the feature pass, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h and tk_features.h (as tk_build.hip is for
-// tk_build_gpu.h); what tk_api.hip (scene creation, groups, the C entry points) calls here is declared in tk_scene_handle.h.  Host code only orchestrates:
+// tk_build_gpu.h); what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared in tk_scene_handle.h.  Host code only orchestrates:
 // every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
 
@@ -839,10 +839,9 @@ int take_hip_debug_env(TakeScene *ts, int32_t side, int32_t kind, const double *
     if (kind != ENV_SAMPLE && kind != ENV_EVAL) return fail(TAKE_E_INVALID, "unknown kind");
     const int nd = check_device();
     if (nd < 0) return nd;
-    if (!(side == TAKE_PRECISION_F32 ? ts->precision != TAKE_PRECISION_F64 : side == TAKE_PRECISION_F64 && ts->precision != TAKE_PRECISION_F32))
-        return fail(TAKE_E_INVALID, "the scene has no such side");
+    if (!has_side(ts, side)) return fail(TAKE_E_INVALID, "the scene has no such side");
     TAKE_ON_DEVICE(ts);
-    return side == TAKE_PRECISION_F64 ? debug_env_side(ts->d, kind, in, n, out) : debug_env_side(ts->f, kind, in, n, out);
+    return on_side(ts, side, [&](auto &sc) { return debug_env_side(sc, kind, in, n, out); });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// tk_scene_handle.h — the scene handle (TakeScene: one SceneT per precision side) and the few functions that
-// tk_api.hip (scene creation, groups, the C entry points) calls across: of tk_render.hip (tracing and rendering: the only
-// unit that compiles the kernels of tk_kernels.h) and of tk_build.hip (the device LBVH build: the only unit that
-// compiles the kernels of tk_build_gpu.h).  Includes no kernel source.
+// tk_scene_handle.h — the scene handle (TakeScene: one SceneT per precision side), the walks over its sides
+// (on_primary, for_each_side, on_side, stage_then_commit) and what tk_create.hip (scene creation), tk_group.hip (groups)
+// and tk_api.hip (the other entry points) call of tk_render.hip (the only unit that compiles the kernels of tk_kernels.h)
+// and of tk_build.hip (the device LBVH build: the only one that compiles tk_build_gpu.h's).  Includes no kernel source.
 #pragma once
 #include <chrono>
 #include <cstdio>
@@ -166,6 +166,23 @@ namespace tk_host {
 
 // f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
 template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
+// The sides a scene has: the f64 one (side = TAKE_PRECISION_F64) of F64 and MIXED scenes, the f32 one of F32 and MIXED ones.
+// on_side: f(the named side).  for_each_side: f(every side), f64 first as creation makes them, and of `more` the same
+// side with it; f returns a TAKE_* code, and the first that is not TAKE_OK ends the walk and is returned.
+inline bool has_side(const TakeScene *ts, int32_t side) { return side == TAKE_PRECISION_F64 ? ts->f64() : side == TAKE_PRECISION_F32 && ts->precision != TAKE_PRECISION_F64; }
+template <class TS, class F> decltype(auto) on_side(TS *ts, int32_t side, F &&f) { return side == TAKE_PRECISION_F64 ? f(ts->d) : f(ts->f); }
+template <class TS, class F, class... S> int for_each_side(TS *ts, F &&f, S *...more) {
+    const int rc = has_side(ts, TAKE_PRECISION_F64) ? f(ts->d, more->d...) : TAKE_OK;
+    return rc || !has_side(ts, TAKE_PRECISION_F32) ? rc : f(ts->f, more->f...);
+}
+// A change of a resident scene (Stage = ReposeStage, MeshUpdateStage): stage_side(sc, its stage) builds every side aside and leaves
+// sc as it is; only when all succeeded commit() puts them in — a mixed scene gets both sides or neither — and a progressive sequence restarts.
+template <template <class> class Stage, class F> int stage_then_commit(TakeScene *ts, F &&stage_side) {
+    struct { Stage<double> d; Stage<float> f; } stages;  // (sides named as the scene's: for_each_side pairs them)
+    if (const int rc = for_each_side(ts, stage_side, &stages)) return rc;
+    ts->acc_samples = 0, ts->acc_restart_needed = true;
+    return for_each_side(ts, [](auto &sc, auto &stage) { return stage.commit(sc); }, &stages);
+}
 
 // A scene lives on the device that was current when it was created; every entry point that touches it makes that
 // device current for the duration of the call and restores the caller's afterwards.
@@ -248,13 +265,12 @@ int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInput
 // The placements of a resident two-level scene under new transforms (take_hip_scene_set_instance_transforms): the
 // top-level half of the device build entered a second time, reading only what the scene keeps — the old placement
 // records, the prototypes' records (tight boxes: k_placement_boxes_resident), the shapes' records now in leaf order.
-// d_xforms: 12 doubles per placement in device memory, complete; n = the scene's placements.  Everything is built into
-// `out` and sc stays as it is — a failure, or the failure of the other side of a mixed scene, changes nothing; commit()
-// then puts it into the scene (no allocation, nothing that fails short of a lost device).  The prototypes' trees are
-// copied, never rebuilt; the scene keeps its node format; who built it does not matter (the new top-level tree is an
-// LBVH).  Returns TAKE_OK or an error with its message: TAKE_E_INVALID naming the first singular or non-finite
-// transform, or starting with "unsupported" when the new top-level tree has fewer than two leaves or is too deep for
-// the traversal stack.
+// d_xforms: 12 doubles per placement in device memory, complete; n = the scene's placements; built into `out`
+// (stage_then_commit).  Both stages' commit() return a TAKE_* code and allocate nothing: MeshUpdateStage's only moves,
+// this one also copies the staged head records over the scene's, which fails only with a lost device.  The prototypes'
+// trees are copied, never rebuilt; the scene keeps its node format; who built it does not matter (the new top-level
+// tree is an LBVH).  Errors: TAKE_E_INVALID naming the first singular or non-finite transform, or starting with
+// "unsupported" when the new top-level tree has fewer than two leaves or is too deep for the traversal stack.
 template <class R> struct ReposeStage {
     DevBuf<Node4<R>> nodes;      // the format the scene traverses: the new top-level tree's nodes, then the prototypes'
     DevBuf<QNode4> qnodes;
@@ -280,9 +296,7 @@ struct MeshUpdateInputs {
     DevBuf<const double *> d_pos, d_nrm;   // the same tables in device memory
     int upload(const std::vector<int64_t> &mesh_vertices, const TakeMeshUpdate *updates, int32_t n_updates);
 };
-// Everything is built into `out` and sc stays as it is — a failure, or the failure of the other side of a mixed scene,
-// changes nothing; commit() then moves it into the scene.
-// Returns TAKE_OK or an error with its message: TAKE_E_INVALID naming mesh and vertex of the first coordinate that is
+// Built into `out` (stage_then_commit).  Errors: TAKE_E_INVALID naming mesh and vertex of the first coordinate that is
 // not finite, or starting with "unsupported" when the new tree has fewer than two leaves or is too deep for the
 // traversal stack.  compressed_ok / _forced: as build_side_on_device.
 template <class R> struct MeshUpdateStage {
@@ -292,7 +306,7 @@ template <class R> struct MeshUpdateStage {
     SceneT<R> built;
     // built.normals: with new normals, the scene's whole array copied and the named meshes' parts rewritten
     bool new_lights = false, new_normals = false, new_trace_state = false;
-    void commit(SceneT<R> &sc);  // moves only: it cannot fail, so a mixed scene gets both sides or neither
+    int commit(SceneT<R> &sc);  // moves only: always TAKE_OK
 };
 template <class R>
 int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
