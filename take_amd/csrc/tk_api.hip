@@ -22,7 +22,7 @@ namespace {
 int check_repose(const TakeScene *ts, int64_t n) {
     if (ts->n_placements <= 0) return fail(TAKE_E_INVALID, "the scene has no placements (none were given, or TAKE_INSTANCES_FLATTEN expanded them)");
     if (n != ts->n_placements) return fail(TAKE_E_INVALID, "n = " + std::to_string(n) + ", but the scene has " + std::to_string(ts->n_placements) + " placements");
-    const bool plain = on_primary(ts, [&](const auto &sc) {
+    const bool plain = on_primary(ts, [&](const auto &sc, const auto &) {
         return sc.trace.two_level && sc.trace.nodes != NodeFormat::Q8 && (int64_t)sc.inst_trace.n == n && (int64_t)sc.host.placements.inst_proto.size() == n;
     });
     if (!plain) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_BRAID > 1 or TAKE_HIP_NODES=q8");
@@ -100,7 +100,7 @@ int take_hip_render_accumulate(TakeScene *ts, const TakeRenderOpts *opts, int32_
                                     "rendered with (seed, max_depth, integrator, strips, ray_epsilon, exact_bounces): pass restart = 1");
     const int64_t first = fresh ? 0 : ts->acc_samples;
     if (first + (int64_t)opts->spp >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "too many accumulated samples");
-    // (a workspace grown for a bigger batch keeps the accumulator: ensure_workspace only ever enlarges it, and the
+    // (a workspace grown for a bigger batch keeps the accumulator: RenderWorkspace::ensure only ever enlarges it, and the
     // strip set — hence the pixel count — is fixed for the sequence)
     const int rc = render_scene(ts, *opts, d_rgb_out, (hipStream_t)stream, first, !fresh);
     if (rc) {
@@ -249,16 +249,16 @@ int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *update
             const TakeMeshUpdate &u = updates[i];
             const std::string who = "update " + std::to_string(i) + ": ";
             if ((size_t)u.mesh >= ts->mesh_vertices.size()) return fail(TAKE_E_INVALID, who + "mesh index out of range");
-            const bool has_normals = on_primary(ts, [&](const auto &sc) { return (size_t)u.mesh < sc.host.meshes.size() && sc.host.meshes[u.mesh].nbase >= 0; });
+            const bool has_normals = on_primary(ts, [&](const auto &sc, const auto &) { return (size_t)u.mesh < sc.host.meshes.size() && sc.host.meshes[u.mesh].nbase >= 0; });
             if (u.normals && !has_normals) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
         }
         if (ts->n_placements > 0) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (the prototypes' trees are not rebuilt)");
         if (ts->flattened) return fail(TAKE_E_INVALID, "unsupported: the scene was flattened from instances");
-        const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc) { return sc.trace.nodes == NodeFormat::Q8; });
+        const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.nodes == NodeFormat::Q8; });
         if (q8) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_NODES=q8");
-        if (on_primary(ts, [&](const auto &sc) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
+        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
         if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
-        if (on_primary(ts, [&](const auto &sc) { return sc.prims.n != ts->shape_face.n; }))
+        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.prims.n != ts->shape_face.n; }))
             return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
         TAKE_ON_DEVICE(ts);
         MeshUpdateInputs in;
@@ -297,7 +297,7 @@ int take_hip_set_instrumentation(TakeScene *ts, int32_t flags) {
 int take_hip_scene_stats(const TakeScene *ts, int64_t *n_nodes, int64_t *n_prims, int32_t *depth,
                          int64_t *device_bytes) {
     if (!ts) return fail(TAKE_E_INVALID, "null scene");
-    const WideBvhStats s = on_primary(ts, [](const auto &sc) { return sc.host.stats; });
+    const WideBvhStats s = on_primary(ts, [](const auto &sc, const auto &) { return sc.host.stats; });
     if (n_nodes) *n_nodes = s.n_nodes;
     if (n_prims) *n_prims = s.n_prims;
     if (depth) *depth = s.depth;

@@ -787,10 +787,7 @@ template <class R> int MeshUpdateStage<R>::commit(SceneT<R> &sc) {
     install_tree(sc, built.host.stats.n_nodes, built.host.stats.depth, built.host.root_child, built.host.grid_lo, built.host.grid_step);
     sc.trace = built.trace;
     sc.built_on_device = true;  // whoever built the tree that is gone
-    if (new_trace_state) {
-        sc.qwords = std::move(built.qwords), sc.counters = std::move(built.counters), sc.spill = std::move(built.spill);
-        sc.blocks_per_cu = built.blocks_per_cu, sc.spill_levels = built.spill_levels, sc.trace_grid = built.trace_grid, sc.spill_stride = built.spill_stride;
-    }
+    if (new_trace_state) sc.trace_state = std::move(built.trace_state);
     return TAKE_OK;
 }
 template struct MeshUpdateStage<float>;

@@ -248,7 +248,7 @@ int upload_scene(SceneT<R> &sc, int num_cus, const TakeSceneDesc &desc, const Ta
     HIP_TRY(sc.env_guide_c.upload(h.env_guide_c));
     sc.dev = h.view();  // (the counts, camera and small tables; the pointers are the device arrays')
     sc.bind();
-    HIP_TRY(alloc_trace_state(sc, num_cus));  // queue words, counters, the persistent trace grid
+    HIP_TRY(alloc_trace_state(sc, num_cus));  // the persistent trace grid
     clock.lap("shading tables -> HBM, grid");
     // everything the kernels read is in HBM now; the host keeps the small tables (camera, material tags, tree
     // statistics) and drops the copies of the large arrays (1.1 GB at 10M triangles)
@@ -320,6 +320,7 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         // (a mixed scene's two sides are two independent trees, each from its own records' boxes, over one upload of the caller's arrays)
         DeviceBuildInputs inputs;
         if (!rc) rc = for_each_side(ts.get(), [&](auto &sc) { return upload_scene(sc, ts->num_cus, local, o, threads, device_builder, staged, inputs); });
+        if (!rc) rc = on_primary(ts.get(), [](auto &, auto &work) -> int { HIP_TRY(work.create()); return TAKE_OK; });  // queue words, counters
         // what take_hip_scene_set_mesh_vertices will need: the meshes' vertex counts, and for a scene without placements
         // the shape_face array in device memory — the device builder's upload, or one made here
         if (!rc) {

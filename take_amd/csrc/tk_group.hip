@@ -53,7 +53,7 @@ template <class R> int replicate_t(const SceneT<R> &a, int a_dev, SceneT<R> &b, 
     b.bind();
     // the persistent trace grid of THIS device: blocks per CU are a property of the kernels (the same code object on
     // every device), the CU count is the replica device's own
-    b.built_on_device = a.built_on_device, b.trace = a.trace, b.blocks_per_cu = a.blocks_per_cu;
+    b.built_on_device = a.built_on_device, b.trace = a.trace, b.trace_state.blocks_per_cu = a.trace_state.blocks_per_cu;
     const hipError_t e = alloc_trace_state(b, b_cus);
     if (e == hipErrorOutOfMemory) return fail(TAKE_E_NOMEM, "out of device memory for a scene replica");
     HIP_TRY(e);
@@ -74,6 +74,9 @@ int replicate_scene(const TakeScene *src, int device, TakeScene **out) {
     // every side of src (a) into the same side of the replica (b: for_each_side's `more`), in take_hip_scene_create's order
     const int rc = for_each_side(src, [&](const auto &a, auto &b) { return replicate_t(a, src->device, b, device, ts->num_cus); }, ts.get());
     if (rc) return rc;
+    const hipError_t e = on_primary(ts.get(), [](auto &, auto &work) { return work.create(); });  // the replica's own workspace
+    if (e == hipErrorOutOfMemory) return fail(TAKE_E_NOMEM, "out of device memory for a scene replica");
+    HIP_TRY(e);
     *out = ts.release();
     return TAKE_OK;
 }
@@ -124,11 +127,11 @@ int group_render(TakeSceneGroup *g, const TakeRenderOpts &opts, void *d_out) {
     // assemble on the first device
     DeviceGuard guard(g->scenes[0]->device);
     if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the first device current");
-    on_primary(g->scenes[0], [&](auto &sc0) {
-        using R = std::remove_pointer_t<decltype(sc0.out.p)>;
+    on_primary(g->scenes[0], [&](auto &, auto &work0) {
+        using R = std::remove_pointer_t<decltype(work0.out.p)>;
         for (int k = 0; k < n; k++) {
             if (g->n_rows[k] == 0) continue;
-            const R *src = k == 0 ? sc0.out.p : (const R *)g->staging[k].p;
+            const R *src = k == 0 ? work0.out.p : (const R *)g->staging[k].p;
             const int64_t total = (int64_t)g->n_rows[k] * row_words;
             const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 4096));
             hipLaunchKernelGGL((k_place_rows<R>), grid, dim3(BLOCK), 0, nullptr, src, g->d_rows[k].p, g->n_rows[k], row_words, (R *)d_out);

@@ -1,7 +1,9 @@
-// tk_render.hip — the host side of tracing and rendering: the render workspace, the kernel launchers, the wavefront
-// render loop, the feature pass, the trace hooks.  The only unit that compiles the kernels of tk_kernels.h and tk_features.h (as tk_build.hip is for
-// tk_build_gpu.h); what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared in tk_scene_handle.h.  Host code only orchestrates:
-// every per-sample operation runs in the kernels.
+// tk_render.hip — the host side of tracing and rendering: the render workspace's allocations, the kernel launchers,
+// the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
+// after them) and the three calls that differ in between — the wavefront render loop, the feature pass, the trace hooks.
+// The only unit that compiles the kernels of tk_kernels.h and tk_features.h (as tk_build.hip is for tk_build_gpu.h);
+// what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
+// in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,36 +48,6 @@ template <class R, bool ANY_HIT, bool COUNT, class Io, class Fn> bool with_trace
     return false;
 }
 
-// Path-state / queue / framebuffer workspace of a scene, grown on demand.  A failed allocation leaves the scene
-// WITHOUT a workspace (capacity 0, every buffer released) and returns TAKE_E_NOMEM: the next render allocates afresh
-// instead of trusting a stale capacity over null pointers.
-template <class R> void release_workspace(SceneT<R> &sc) {
-    sc.state_r.release(), sc.queue[0].release(), sc.queue[1].release(), sc.shadow_queue.release();
-    sc.sorted_queue.release(), sc.sort_keys.release();
-    sc.capacity = 0;
-}
-template <class R> int ensure_workspace(SceneT<R> &sc, int64_t slots, int64_t npix) {
-    if (slots > sc.capacity) {
-        release_workspace(sc);
-        const bool ok = sc.state_r.alloc((size_t)PATH_REC * slots) == hipSuccess && sc.queue[0].alloc(slots) == hipSuccess &&
-                        sc.queue[1].alloc(slots) == hipSuccess && sc.shadow_queue.alloc(slots) == hipSuccess &&
-                        sc.sorted_queue.alloc(slots) == hipSuccess && sc.sort_keys.alloc(slots) == hipSuccess;
-        if (!ok) {
-            release_workspace(sc);
-            return fail(TAKE_E_NOMEM, "out of device memory for " + std::to_string(slots) + " path slots (" +
-                                          std::to_string((size_t)slots * (PATH_REC * sizeof(R) + 17) >> 20) + " MiB)");
-        }
-        sc.capacity = slots;
-    }
-    if ((int64_t)sc.accum.n < 3 * npix) {
-        if (sc.accum.alloc(3 * npix) != hipSuccess || sc.out.alloc(3 * npix) != hipSuccess) {
-            sc.accum.release(), sc.out.release();
-            return fail(TAKE_E_NOMEM, "out of device memory for the framebuffer");
-        }
-    }
-    return TAKE_OK;
-}
-
 __global__ void k_prep(int32_t *q, int next) {
     const int t = threadIdx.x;
     if (t == 0) {
@@ -92,7 +64,7 @@ struct Timer {
     TakeScene *ts;
     hipStream_t stream;
     bool on;
-    hipError_t err = hipSuccess;  // first failure of an event call; render_impl reports it instead of bogus times
+    hipError_t err = hipSuccess;  // first failure of an event call; end_frame reports it instead of bogus times
     void begin(int which) {
         if (!on) return;
         hipEvent_t a = ts->events.get(), b = ts->events.get();
@@ -108,16 +80,17 @@ struct Timer {
     }
 };
 
-// launch the trace kernel instance of a scene for (any-hit, counting)
+// launch the trace kernel instance of a scene side for (any-hit, counting), with the side's spill area
 template <class R, class Io>
-hipError_t launch_trace(TraceKind kind, bool any, bool count, dim3 grid, hipStream_t stream, const DeviceScene<R> &dev, const Io &io,
-                        const int32_t *n_ptr, int32_t n_direct, int32_t *head, unsigned long long *counters, int counter_word,
-                        StackSpill spill) {
+hipError_t launch_trace(const SceneT<R> &sc, bool any, bool count, unsigned grid, hipStream_t stream, const Io &io, const int32_t *n_ptr,
+                        int32_t n_direct, int32_t *head, unsigned long long *counters, int counter_word) {
+    const TraceState &t = sc.trace_state;
     auto launch = [&](auto kernel, auto) {
-        hipLaunchKernelGGL(kernel, grid, dim3(TQ_BLOCK), 0, stream, dev, io, n_ptr, n_direct, head, counters, counter_word, spill);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(TQ_BLOCK), 0, stream, sc.dev, io, n_ptr, n_direct, head, counters, counter_word,
+                           StackSpill{t.spill.p, t.spill_stride});
     };
-    const bool found = any ? (count ? with_trace_kernel<R, true, true, Io>(kind, launch) : with_trace_kernel<R, true, false, Io>(kind, launch))
-                           : (count ? with_trace_kernel<R, false, true, Io>(kind, launch) : with_trace_kernel<R, false, false, Io>(kind, launch));
+    const bool found = any ? (count ? with_trace_kernel<R, true, true, Io>(sc.trace, launch) : with_trace_kernel<R, true, false, Io>(sc.trace, launch))
+                           : (count ? with_trace_kernel<R, false, true, Io>(sc.trace, launch) : with_trace_kernel<R, false, false, Io>(sc.trace, launch));
     return found ? hipSuccess : hipErrorInvalidDeviceFunction;
 }
 
@@ -179,21 +152,27 @@ template <class R> void dump_slot(const PathState<R> &st, int64_t slot, const ch
     std::fprintf(stderr, "\n");
 }
 
-// What the rounds of one render share: the queues, queue words, sort scratch and counters — they belong to the scene
-// whose precision owns the workspace (mixed-precision renders: the f64 scene's; the f32 rounds use them too — slot
-// numbers and queue words do not depend on the precision of the records they point to) — and the render's options.
-struct RoundCtx {
-    int32_t *q;  // queue words + tag counts
-    int32_t *queue[2], *shadow_queue, *sorted_queue;
-    uint8_t *sort_keys;
-    int32_t *sort_hist, *sort_base;
-    unsigned long long *counters;
-    int wide_grid;
-    Timer *tm;
-    bool counting, sort_materials;
+// What the launches of one call (a render, a feature pass, a trace hook) share: the primary side and the handle's
+// workspace, the stream, timer and options, and what pick_strips / begin_frame (the calls over pixels) and start_frame
+// set.  (The f32 rounds of a mixed-precision render launch on the f32 side with the same frame.)
+template <class R> struct Frame {
+    TakeScene *ts;
+    SceneT<R> &sc;
+    RenderWorkspace<R> &work;
     hipStream_t stream;
-    int64_t dump;  // TAKE_HIP_DUMP_SLOT (or -1)
-    int64_t slots;
+    Timer tm{ts, stream, (ts->instrumentation & 1) != 0};
+    bool counting = (ts->instrumentation & 2) != 0;
+    bool sort_materials = false;
+    int64_t dump = -1;  // TAKE_HIP_DUMP_SLOT (or -1)
+    int first = 0, stride = 1, n_rows = 0;  // the strips first, first + stride, ... of the image and their rows (pick_strips)
+    int64_t npix = 0;                       // the pixels of those rows
+    int spb = 0;                            // samples per batch
+    int64_t slots = 0;                      // = spb * npix
+    PathState<R> st{};
+    RenderParams<R> rp{};
+    int wide_grid = 0, pix_grid = 0;  // blocks of a launch over the slots / the pixels
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    unsigned long long raw[C_NUM_WORDS];  // the device counters of the call (end_frame), for the caller's own lines
 };
 // Round 0 of the default integrator on the default node format: no generate pass (CameraIo).  The counting instances,
 // the other integrators (their shade rounds read the initial flag word) and the other node formats keep k_generate.
@@ -205,16 +184,15 @@ bool camera_fused(TraceKind kind, int integrator, bool counting) {
 
 // The closest hits of round k of a batch for the extend queue (k = 0: the camera rays, made by the launch that traces
 // them where camera_fused says so).  tail: an f32 round of a mixed-precision render.
-template <class RR>
-hipError_t launch_closest(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound, bool tail) {
-    Timer &tm = *c.tm;
-    int32_t *q = c.q;
+template <class RR, class R>
+hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound, bool tail) {
+    Timer &tm = c.tm;
+    int32_t *q = c.work.qwords.p;
+    unsigned long long *counters = c.work.counters.p;
     const int cur = k & 1, next = cur ^ 1;
     int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0);
-    StackSpill spill{sc.spill.p, sc.spill_stride};
-    const PathIo<RR> io_ext{sc.dev.prims, st, c.queue[cur], rp.ray_eps};
-    // persistent trace grid, cut down when the queue (bounded by n_bound) cannot fill it: one block per 128 rays
-    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));
+    const PathIo<RR> io_ext{sc.dev.prims, st, c.work.queue[cur].p, rp.ray_eps};
+    const unsigned tgrid = sc.trace_state.grid_for(n_bound);
     hipError_t e;
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
     tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
@@ -223,10 +201,10 @@ hipError_t launch_closest(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, c
         CameraIo<RR> io_cam;
         static_cast<PathIo<RR> &>(io_cam) = io_ext;
         io_cam.cam = sc.dev.cam, io_cam.rp = rp;
-        e = launch_trace<RR>(sc.trace, false, false, tgrid, c.stream, sc.dev, io_cam, n_cur, 0, q + Q_HEAD_CLOSEST, c.counters, (int)C_RAYS_CLOSEST, spill);
+        e = launch_trace(sc, false, false, tgrid, c.stream, io_cam, n_cur, 0, q + Q_HEAD_CLOSEST, counters, (int)C_RAYS_CLOSEST);
     } else {
-        e = launch_trace<RR>(sc.trace, false, c.counting, tgrid, c.stream, sc.dev, io_ext, n_cur, 0, q + Q_HEAD_CLOSEST, c.counters,
-                             tail ? (int)C_RAYS_CLOSEST_TAIL : (int)C_RAYS_CLOSEST, spill);
+        e = launch_trace(sc, false, c.counting, tgrid, c.stream, io_ext, n_cur, 0, q + Q_HEAD_CLOSEST, counters,
+                         tail ? (int)C_RAYS_CLOSEST_TAIL : (int)C_RAYS_CLOSEST);
     }
     if (e != hipSuccess) return e;
     tm.end();
@@ -236,41 +214,40 @@ hipError_t launch_closest(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, c
 // One round k of a batch on the records of precision RR: closest hits of the extend queue, material sort, shade,
 // shadow rays.  (Everything is enqueued; nothing waits.)  tail: an f32 round of a mixed-precision render; to_f32: see
 // ShadeArgs.  (Long because it is the round, kernel by kernel in stream order.)
-template <class RR>
-hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound,
-                        bool tail, float *to_f32) {
-    Timer &tm = *c.tm;
-    int32_t *q = c.q;
+template <class RR, class R>
+hipError_t launch_round(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound, bool tail,
+                        float *to_f32) {
+    Timer &tm = c.tm;
+    RenderWorkspace<R> &w = c.work;
+    int32_t *q = w.qwords.p;
     int32_t *tag_count = q + Q_NUM_WORDS;
     const int cur = k & 1, next = cur ^ 1;
     int32_t *n_cur = q + (cur ? Q_N_EXT1 : Q_N_EXT0), *n_next = q + (next ? Q_N_EXT1 : Q_N_EXT0);
     const bool dump = !tail && c.dump >= 0 && c.dump < c.slots;  // (the slot's f64 record)
-    StackSpill spill{sc.spill.p, sc.spill_stride};
-    const PathIo<RR> io_shadow{sc.dev.prims, st, c.shadow_queue, rp.ray_eps};
-    const dim3 tgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(sc.trace_grid, (n_bound + 127) / 128)));  // (as launch_closest)
+    const PathIo<RR> io_shadow{sc.dev.prims, st, w.shadow_queue.p, rp.ray_eps};
     hipError_t e = launch_closest(c, sc, st, rp, k, n_bound, tail);
     if (e != hipSuccess) return e;
     if (dump) dump_slot(st, c.dump, "after trace_closest", k, c.stream);
-    const int32_t *shade_in = c.queue[cur];
+    const int32_t *shade_in = w.queue[cur].p;
     if (c.sort_materials) {
         tm.begin(TK_OTHER);
         // every wave of the sort gets >= 512 entries of the (bounded) queue: the one-block scan walks
         // 13 x waves counters, which must not dominate small rounds (it was 40 % of a 256x256 render)
         const int sort_grid = (int)std::max<int64_t>(1, std::min<int64_t>(c.wide_grid, (n_bound + 2047) / 2048));
         hipLaunchKernelGGL((k_sort_count<RR>), dim3(sort_grid), dim3(BLOCK), 0, c.stream, sc.dev.prims, sc.dev.inst_shade, st,
-                           c.queue[cur], n_cur, c.sort_keys, c.sort_hist);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_SCAN_THREADS), 0, c.stream, c.sort_hist, c.sort_base, tag_count,
+                           w.queue[cur].p, n_cur, w.sort_keys.p, w.sort_hist.p);
+        hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(SORT_SCAN_THREADS), 0, c.stream, w.sort_hist.p, w.sort_base.p, tag_count,
                            sort_grid * (BLOCK / WAVE));
-        hipLaunchKernelGGL(k_sort_scatter, dim3(sort_grid), dim3(BLOCK), 0, c.stream, c.queue[cur], n_cur, c.sort_keys, c.sort_base,
-                           c.sorted_queue);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(sort_grid), dim3(BLOCK), 0, c.stream, w.queue[cur].p, n_cur, w.sort_keys.p, w.sort_base.p,
+                           w.sorted_queue.p);
         tm.end();
-        shade_in = c.sorted_queue;
+        shade_in = w.sorted_queue.p;
     }
     tm.begin(TK_SHADE);
     {
         const int shade_grid = (int)((n_bound + BLOCK - 1) / BLOCK);
-        ShadeArgs<RR> sa{sc.dev, rp, st, shade_in, n_cur, c.sort_materials ? tag_count : nullptr, c.queue[next],
-                         n_next, c.shadow_queue, q + Q_N_SHADOW, k, c.counters, shade_grid, c.stream, to_f32};
+        ShadeArgs<RR> sa{sc.dev, rp, st, shade_in, n_cur, c.sort_materials ? tag_count : nullptr, w.queue[next].p,
+                         n_next, w.shadow_queue.p, q + Q_N_SHADOW, k, w.counters.p, shade_grid, c.stream, to_f32};
         if (c.sort_materials) {
             // one specialised launch per material tag present in the scene + the miss segment
             for (int t = 0; t < TAKE_MAT_COUNT; t++)
@@ -287,15 +264,15 @@ hipError_t launch_round(const RoundCtx &c, SceneT<RR> &sc, PathState<RR> st, con
             // continue on f32 records from here — converted before this round's shadow rays, as k_shade does it
             tm.begin(TK_OTHER);
             hipLaunchKernelGGL(k_convert_state, dim3(c.wide_grid), dim3(BLOCK), 0, c.stream, st, PathState<float>{to_f32, c.slots},
-                               c.queue[next], n_next);
+                               w.queue[next].p, n_next);
             tm.end();
         }
     }
     if (dump) dump_slot(st, c.dump, "after shade", k, c.stream);
     if (k <= rp.max_depth && rp.integrator == 0) {  // integrators 1..3 trace no shadow rays
         tm.begin(TK_SHADOW);
-        e = launch_trace<RR>(sc.trace, true, c.counting, tgrid, c.stream, sc.dev, io_shadow, q + Q_N_SHADOW, 0, q + Q_HEAD_SHADOW, c.counters,
-                             (int)C_RAYS_SHADOW, spill);
+        e = launch_trace(sc, true, c.counting, sc.trace_state.grid_for(n_bound), c.stream, io_shadow, q + Q_N_SHADOW, 0, q + Q_HEAD_SHADOW,
+                         w.counters.p, (int)C_RAYS_SHADOW);
         if (e != hipSuccess) return e;
         tm.end();
         if (dump) dump_slot(st, c.dump, "after trace_shadow", k, c.stream);
@@ -311,8 +288,8 @@ template <class R> TakeCounters fresh_counters(const SceneT<R> &sc) {
     return c;
 }
 // the device counters of the call that has just finished -> tc (and raw, for the caller's own lines)
-template <class R> int read_counters(const SceneT<R> &sc, TakeCounters &tc, unsigned long long (&raw)[C_NUM_WORDS]) {
-    HIP_TRY(hipMemcpy(raw, sc.counters.p, sizeof raw, hipMemcpyDeviceToHost));
+template <class R> int read_counters(const RenderWorkspace<R> &work, TakeCounters &tc, unsigned long long (&raw)[C_NUM_WORDS]) {
+    HIP_TRY(hipMemcpy(raw, work.counters.p, sizeof raw, hipMemcpyDeviceToHost));
     tc.rays_closest = raw[C_RAYS_CLOSEST] + raw[C_RAYS_CLOSEST_TAIL];
     tc.rays_closest_f32 = raw[C_RAYS_CLOSEST_TAIL];
     tc.rays_shadow = raw[C_RAYS_SHADOW];
@@ -328,20 +305,19 @@ template <class R> int read_counters(const SceneT<R> &sc, TakeCounters &tc, unsi
 // Samples per batch of a render of npix pixels (-> spb, slots = spb * npix) with the workspace for them allocated.
 // render = false (the feature pass): path records and queues only — the framebuffer, which holds a progressive
 // sequence's sums, and the f32 records of a mixed scene stay as they are.
-template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, int64_t npix, int &spb, int64_t &slots, bool render = true) {
+template <class R> int size_batches(const TakeScene *ts, RenderWorkspace<R> &work, const TakeRenderOpts &o, int64_t npix, int &spb, int64_t &slots, bool render) {
     // paths in flight per batch: up to 512 Mi (69 GB of f32 path state + 9 GB of queues) — bigger batches keep the
     // persistent trace grid full for more of each bounce (measured on the 1M-triangle scene, spp per batch 8 / 16 / 32 /
     // 64 / 128 / 256 = 53.2 / 57.7 / 60.3 / 61.9 | 64.5 / 64.9 / 65.5 Msamples/s), and a 288 GB device has the room;
     // capped at four fifths of what is free now (round 3: it was half — a mixed-precision render, 418 B per path, then
     // needed two batches for 256 spp at 1920x1080 and lost ~1 % to the second set of thin late rounds)
     int64_t target = (int64_t)512 << 20;
+    const bool mixed_records = render && ts->precision == TAKE_PRECISION_MIXED;  // every slot has an f32 record beside its f64 one
     {
         size_t free_b = 0, total_b = 0;
-        // (mixed precision: every slot has an f32 record beside its f64 one)
-        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (render && ts->precision == TAKE_PRECISION_MIXED ? sizeof(float) : 0)) +
-                                 4 * (int64_t)sizeof(int32_t);
+        const int64_t per_path = (int64_t)PATH_REC * (int64_t)(sizeof(R) + (mixed_records ? sizeof(float) : 0)) + 4 * (int64_t)sizeof(int32_t);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const int64_t have = (int64_t)sc.capacity * per_path;  // already allocated by an earlier render
+            const int64_t have = (int64_t)work.capacity * per_path;  // already allocated by an earlier render
             // (shards of a scene group that share a device size their batches concurrently: each takes its share)
             target = std::min<int64_t>(target, std::max<int64_t>((int64_t)1 << 20, ((int64_t)free_b / std::max(1, ts->mem_share) + have) / 5 * 4 / per_path));
         }
@@ -352,16 +328,9 @@ template <class R> int size_batches(TakeScene *ts, SceneT<R> &sc, const TakeRend
     // The free-memory figure above is a snapshot: another process on the device (or another host thread) may take the
     // memory before the allocation lands.  A batch size the caller did not pin is then halved until it fits — the
     // image does not depend on it (a sample's random stream is a function of seed, pixel and sample index only).
-    const bool mixed_records = render && sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
     for (;;) {
         slots = (int64_t)spb * npix;
-        int rc = ensure_workspace(sc, slots, render ? npix : 0);
-        if (rc == TAKE_OK && mixed_records && (int64_t)ts->f.state_r.n < (int64_t)PATH_REC * slots &&
-            ts->f.state_r.alloc((size_t)PATH_REC * slots) != hipSuccess) {
-            ts->f.state_r.release();
-            release_workspace(sc);
-            rc = fail(TAKE_E_NOMEM, "out of device memory for the f32 path records of a mixed-precision render (" + std::to_string(slots) + " path slots)");
-        }
+        const int rc = work.ensure(slots, render ? npix : 0, mixed_records);
         if (rc != TAKE_E_NOMEM || spb == 1 || o.samples_per_batch > 0) return rc;
         (void)hipGetLastError();
         spb = (spb + 1) / 2;
@@ -438,64 +407,99 @@ void sum_timings(const TakeScene *ts, TakeCounters &tc) {
     tc.ms_other = acc[TK_OTHER];
 }
 
-// The extend queue of a new batch of n paths: the identity where the closest-hit launch of round 0 makes the camera
-// rays itself (camera_fused), else with the paths' initial records (k_generate).
-template <class R>
-void start_batch(SceneT<R> &sc, PathState<R> st, const RenderParams<R> &rp, int64_t n, int wide_grid, bool counting, Timer &tm, hipStream_t stream) {
-    tm.begin(TK_OTHER);
-    if (camera_fused(sc.trace, rp.integrator, counting)) hipLaunchKernelGGL(k_iota, dim3(wide_grid), dim3(BLOCK), 0, stream, sc.queue[0].p, n);
-    else hipLaunchKernelGGL((k_generate<R>), dim3(wide_grid), dim3(BLOCK), 0, stream, sc.dev, rp, st, sc.queue[0].p, n);
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, sc.qwords.p, (int)Q_N_EXT0, (int32_t)n);
-    tm.end();
+// the strips the options name -> fr's first, stride, rows and pixels
+template <class R> int pick_strips(Frame<R> &fr, const TakeRenderOpts &o) {
+    fr.stride = o.strip_stride > 0 ? o.strip_stride : 1;
+    fr.first = o.strip_first;
+    if (fr.first < 0 || fr.first >= fr.stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    fr.n_rows = rows_of(fr.sc.host.cam.height, fr.first, fr.stride, nullptr);
+    fr.npix = (int64_t)fr.n_rows * fr.sc.host.cam.width;
+    return TAKE_OK;
+}
+// The frame of a call over the pixels of those strips (a render; render = false: a feature pass), up to the call's own
+// set-up: fresh counters, the batch size with the workspace for it, the kernels' parameters, the grids.  A strip set
+// without pixels is TAKE_OK with fr.npix == 0: the caller has nothing to do.
+template <class R> int begin_frame(Frame<R> &fr, const TakeRenderOpts &o, bool render) {
+    TakeScene *ts = fr.ts;
+    const int64_t npix = fr.npix;
+    ts->counters = fresh_counters(fr.sc);
+    if (render && ts->precision == TAKE_PRECISION_MIXED) ts->counters.prim_bytes = PRIM_TEST_BYTES;  // (most rounds read the f32 records)
+    if (npix == 0) return TAKE_OK;
+    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
+    if (const int rc = size_batches(ts, fr.work, o, npix, fr.spb, fr.slots, render)) return rc;
+    fr.st = PathState<R>{fr.work.records.p, fr.work.capacity};
+    fr.rp = make_params<R>(o, fr.sc.host.cam.width, fr.sc.host.cam.height, fr.n_rows, fr.first, fr.stride);
+    fr.wide_grid = (int)std::min<int64_t>((fr.slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    fr.pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+    return TAKE_OK;
+}
+// Every call, before its first launch: no timings of an earlier call, the device counters at zero, the begin event.
+template <class R> int start_frame(Frame<R> &fr) {
+    fr.ts->events.reset();
+    fr.ts->timed.clear();
+    HIP_TRY(hipMemsetAsync(fr.work.counters.p, 0, fr.work.counters.bytes(), fr.stream));
+    fr.ev_begin = fr.ts->events.get(), fr.ev_end = fr.ts->events.get();
+    HIP_TRY(hipEventRecord(fr.ev_begin, fr.stream));
+    return TAKE_OK;
+}
+// Every call, after its last launch: the stream drained, then the device counters (-> fr.raw too), the call's samples
+// and times -> ts->counters (fresh_counters' before the call)
+template <class R> int end_frame(Frame<R> &fr, uint64_t samples) {
+    HIP_TRY(hipEventRecord(fr.ev_end, fr.stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(fr.stream));
+    if (fr.tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(fr.tm.err));
+    TakeCounters &tc = fr.ts->counters;
+    if (const int rc = read_counters(fr.work, tc, fr.raw)) return rc;
+    tc.samples = samples;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, fr.ev_begin, fr.ev_end));
+    tc.ms_total = ms;
+    sum_timings(fr.ts, tc);
+    return TAKE_OK;
+}
+
+// The extend queue of a new batch, samples s0 .. s0 + nb - 1 of every pixel (-> its n paths): the identity where the
+// closest-hit launch of round 0 makes the camera rays itself (camera_fused), else with the paths' initial records (k_generate).
+template <class R> int64_t start_batch(Frame<R> &fr, int s0, int nb) {
+    const int64_t n = (int64_t)nb * fr.npix;
+    fr.rp.s0 = s0, fr.rp.spb = nb;
+    fr.tm.begin(TK_OTHER);
+    if (camera_fused(fr.sc.trace, fr.rp.integrator, fr.counting)) hipLaunchKernelGGL(k_iota, dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.work.queue[0].p, n);
+    else hipLaunchKernelGGL((k_generate<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.sc.dev, fr.rp, fr.st, fr.work.queue[0].p, n);
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, fr.stream, fr.work.qwords.p, (int)Q_N_EXT0, (int32_t)n);
+    fr.tm.end();
+    return n;
 }
 
 // first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
 // random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
 // to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
-// (Long because it is the frame in stream order: checks, set-up, the batch / round loop, resolve, read-back.)
-template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
+// (What is a render's own between the frame's steps: its checks, the sort scratch, the f32 side of a mixed-precision
+// render, the batch / round loop, accumulate and resolve.)
+template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
                                    int64_t first_sample, bool keep_accum) {
     if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
-    const int W = sc.host.cam.width, H = sc.host.cam.height;
     if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
     if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
     if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
     if (o.integrator != 0 && sc.host.env.light >= 0)
         return fail(TAKE_E_INVALID, "integrators 1..3 are the reference's own: they do not know the environment-map extension");
-    const int stride = o.strip_stride > 0 ? o.strip_stride : 1;
-    const int first = o.strip_first;
-    if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int n_rows = rows_of(H, first, stride, nullptr);
-    const int64_t npix = (int64_t)n_rows * W;
-    ts->counters = fresh_counters(sc);
-    if (ts->precision == TAKE_PRECISION_MIXED) ts->counters.prim_bytes = PRIM_TEST_BYTES;  // (most rounds read the f32 records)
-    if (npix == 0) return TAKE_OK;
-    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
-    int spb = 0;
-    int64_t slots = 0;
-    int rc = size_batches(ts, sc, o, npix, spb, slots);
-    if (rc) return rc;
+    Frame<R> fr{ts, sc, work, stream};
+    int rc = pick_strips(fr, o);
+    if (!rc) rc = begin_frame(fr, o, true);
+    const int64_t npix = fr.npix;
+    if (rc || npix == 0) return rc;
 
-    PathState<R> st{sc.state_r.p, sc.capacity};
-    RenderParams<R> rp = make_params<R>(o, W, H, n_rows, first, stride);
-    const bool counting = (ts->instrumentation & 2) != 0;
-    const bool sort_materials = sc.host.n_material_tags > 1;
-    const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT");
-    ts->events.reset();
-    ts->timed.clear();
-    Timer tm{ts, stream, (ts->instrumentation & 1) != 0};
-    int32_t *q = sc.qwords.p;
-    const int wide_grid = (int)std::min<int64_t>((slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-    const int pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-    if (sort_materials) {
-        const size_t need = (size_t)N_SORT_KEYS * wide_grid * (BLOCK / WAVE);
-        if (sc.sort_hist.n != need) {
-            HIP_TRY(sc.sort_hist.alloc(need));
-            HIP_TRY(sc.sort_base.alloc(need));
+    fr.sort_materials = sc.host.n_material_tags > 1;
+    if (const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT")) fr.dump = std::atoll(dump_env);
+    if (fr.sort_materials) {
+        const size_t need = (size_t)N_SORT_KEYS * fr.wide_grid * (BLOCK / WAVE);
+        if (work.sort_hist.n != need) {
+            HIP_TRY(work.sort_hist.alloc(need));
+            HIP_TRY(work.sort_base.alloc(need));
         }
     }
-    const RoundCtx ctx{q, {sc.queue[0].p, sc.queue[1].p}, sc.shadow_queue.p, sc.sorted_queue.p, sc.sort_keys.p, sc.sort_hist.p, sc.sort_base.p,
-                       sc.counters.p, wide_grid, &tm, counting, sort_materials, stream, dump_env ? std::atoll(dump_env) : -1, slots};
     // mixed precision (TAKE_PRECISION_MIXED): rounds k < exact_rounds on the f64 records and scene, the rest on f32
     // records of the same slots and the f32 scene
     const bool mixed = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
@@ -505,170 +509,102 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, const TakeRende
     if (mixed) {
         exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
         if (o.integrator != 0) return fail(TAKE_E_INVALID, "mixed precision renders the reference's path_tracing (integrator 0) only");
-        st32 = PathState<float>{ts->f.state_r.p, slots};
-        rp32 = make_params<float>(o, W, H, n_rows, first, stride);
+        st32 = PathState<float>{work.records_f32.p, fr.slots};
+        rp32 = make_params<float>(o, fr.rp.width, fr.rp.height, fr.n_rows, fr.first, fr.stride);
     }
-    if (!keep_accum) HIP_TRY(hipMemsetAsync(sc.accum.p, 0, sizeof(R) * 3 * npix, stream));
-    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
-    hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
-    HIP_TRY(hipEventRecord(ev_begin, stream));
+    if (!keep_accum) HIP_TRY(hipMemsetAsync(work.accum.p, 0, sizeof(R) * 3 * npix, stream));
+    if ((rc = start_frame(fr))) return rc;
     HIP_TRY(ts->poll.create());
     QueuePoll poll{ts->poll, stream};
 
-    for (int s0 = 0; s0 < o.spp; s0 += spb) {
-        const int nb = std::min(spb, o.spp - s0);
-        const int64_t n = (int64_t)nb * npix;
-        rp.s0 = (int32_t)first_sample + s0;
-        rp.spb = nb;
-        rp32.s0 = rp.s0, rp32.spb = nb;
-        start_batch(sc, st, rp, n, wide_grid, counting, tm, stream);
+    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
+        const int nb = std::min(fr.spb, o.spp - s0);
+        const int64_t n = start_batch(fr, (int32_t)first_sample + s0, nb);
+        rp32.s0 = fr.rp.s0, rp32.spb = nb;
         const int rounds = o.max_depth + 2;
         int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
         bool finished = false;
         for (int k = 0; k < rounds && !finished; k++) {
             // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
             // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
-            if (mixed && k >= exact_rounds) HIP_TRY(launch_round<float>(ctx, ts->f, st32, rp32, k, n_bound, true, nullptr));
-            else HIP_TRY(launch_round<R>(ctx, sc, st, rp, k, n_bound, false, (mixed && k == exact_rounds - 1) ? st32.r : nullptr));
-            if (k + 1 < rounds) rc = poll.post(q + (k & 1 ? Q_N_EXT0 : Q_N_EXT1));  // the length of the next round's queue
+            if (mixed && k >= exact_rounds) HIP_TRY(launch_round(fr, ts->f, st32, rp32, k, n_bound, true, nullptr));
+            else HIP_TRY(launch_round(fr, sc, fr.st, fr.rp, k, n_bound, false, (mixed && k == exact_rounds - 1) ? st32.r : nullptr));
+            if (k + 1 < rounds) rc = poll.post(work.qwords.p + (k & 1 ? Q_N_EXT0 : Q_N_EXT1));  // the length of the next round's queue
             if (!rc) rc = poll.drain(n_bound, finished);
             if (rc) return rc;
         }
         poll.end_batch();
-        tm.begin(TK_OTHER);
+        fr.tm.begin(TK_OTHER);
         if constexpr (sizeof(R) == 8)
-            if (mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(pix_grid), dim3(BLOCK), 0, stream, st, st32, sc.accum.p, (int32_t)npix, nb);
-        if (!mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, st, sc.accum.p, (int32_t)npix, nb);
-        tm.end();
+            if (mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, st32, work.accum.p, (int32_t)npix, nb);
+        if (!mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)npix, nb);
+        fr.tm.end();
     }
-    tm.begin(TK_OTHER);
-    hipLaunchKernelGGL((k_resolve<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.accum.p, (R *)d_out, W, n_rows,
+    fr.tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows,
                        (int32_t)first_sample + o.spp);
-    tm.end();
-    HIP_TRY(hipEventRecord(ev_end, stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(tm.err));
-
-    unsigned long long c[C_NUM_WORDS];
-    TakeCounters &tc = ts->counters;
-    rc = read_counters(sc, tc, c);
-    if (rc) return rc;
-    tc.samples = (uint64_t)npix * (uint64_t)o.spp;
+    fr.tm.end();
+    if ((rc = end_frame(fr, (uint64_t)npix * (uint64_t)o.spp))) return rc;
     if (std::getenv("TAKE_HIP_VERBOSE"))
         std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
-                     c[C_WAIT_SLOTS], c[C_IDLE_SLOTS], c[C_NODE_VISITS], c[C_OCC_CACHE_HITS], c[C_RAYS_SHADOW]);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    tc.ms_total = ms;
-    sum_timings(ts, tc);
+                     fr.raw[C_WAIT_SLOTS], fr.raw[C_IDLE_SLOTS], fr.raw[C_NODE_VISITS], fr.raw[C_OCC_CACHE_HITS], fr.raw[C_RAYS_SHADOW]);
     return TAKE_OK;
 }
 
 // The first-hit feature buffers of a scene (take_hip_render_features*; contract: include/take_hip.h): per batch the
 // camera + closest-hit launch of a render's round 0, then k_features over the batch's records; sums of its own
-// (sc.features), so a progressive sequence — its accumulator and sample count — goes on afterwards.  The timer files
+// (work.features), so a progressive sequence — its accumulator and sample count — goes on afterwards.  The timer files
 // k_features under the shade class: after the call ms_shade is its time.
-template <class R> int features_impl(TakeScene *ts, SceneT<R> &sc, const TakeRenderOpts &opts, const TakeFeatureBuffers &b, hipStream_t stream) {
-    const int W = sc.host.cam.width, H = sc.host.cam.height;
+template <class R>
+int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &opts, const TakeFeatureBuffers &b, hipStream_t stream) {
     if (opts.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
-    const int stride = opts.strip_stride > 0 ? opts.strip_stride : 1;
-    const int first = opts.strip_first;
-    if (first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    Frame<R> fr{ts, sc, work, stream};
+    if (const int rc = pick_strips(fr, opts)) return rc;
     const FeatureOut<R> out{(R *)b.albedo, (R *)b.normal, (R *)b.depth, (R *)b.alpha, b.shape_id, b.material_id};
     const uint32_t want = out.want();
     if (want == 0) return fail(TAKE_E_INVALID, "no feature buffer was asked for: every pointer of TakeFeatureBuffers is NULL");
     TakeRenderOpts o = opts;
     o.max_depth = 0, o.integrator = 0, o.exact_bounces = 0;  // (ignored by this pass: the camera rays do not depend on them)
-    const int n_rows = rows_of(H, first, stride, nullptr);
-    const int64_t npix = (int64_t)n_rows * W;
-    ts->counters = fresh_counters(sc);
-    if (npix == 0) return TAKE_OK;
-    if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
-    int spb = 0;
-    int64_t slots = 0;
-    int rc = size_batches(ts, sc, o, npix, spb, slots, false);
-    if (rc) return rc;
-    if ((int64_t)sc.features.n < FEATURE_WORDS * npix && sc.features.alloc((size_t)FEATURE_WORDS * npix) != hipSuccess) {
-        sc.features.release();
+    int rc = begin_frame(fr, o, false);
+    const int64_t npix = fr.npix;
+    if (rc || npix == 0) return rc;
+    if ((int64_t)work.features.n < FEATURE_WORDS * npix && work.features.alloc((size_t)FEATURE_WORDS * npix) != hipSuccess)
         return fail(TAKE_E_NOMEM, "out of device memory for the feature accumulators");
+    HIP_TRY(hipMemsetAsync(work.features.p, 0, sizeof(R) * FEATURE_WORDS * npix, stream));
+    if ((rc = start_frame(fr))) return rc;
+    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
+        const int nb = std::min(fr.spb, o.spp - s0);
+        const int64_t n = start_batch(fr, s0, nb);
+        HIP_TRY(launch_closest(fr, sc, fr.st, fr.rp, 0, n, false));
+        fr.tm.begin(TK_SHADE);
+        hipLaunchKernelGGL((k_features<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, work.features.p, out, fr.rp.width, fr.n_rows, nb, s0 == 0 ? 1 : 0, want);
+        fr.tm.end();
     }
-
-    PathState<R> st{sc.state_r.p, sc.capacity};
-    RenderParams<R> rp = make_params<R>(o, W, H, n_rows, first, stride);
-    const bool counting = (ts->instrumentation & 2) != 0;
-    ts->events.reset();
-    ts->timed.clear();
-    Timer tm{ts, stream, (ts->instrumentation & 1) != 0};
-    const int wide_grid = (int)std::min<int64_t>((slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-    const int pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-    const RoundCtx ctx{sc.qwords.p, {sc.queue[0].p, sc.queue[1].p}, sc.shadow_queue.p, sc.sorted_queue.p, sc.sort_keys.p, nullptr, nullptr,
-                       sc.counters.p, wide_grid, &tm, counting, false, stream, -1, slots};
-    HIP_TRY(hipMemsetAsync(sc.features.p, 0, sizeof(R) * FEATURE_WORDS * npix, stream));
-    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
-    hipEvent_t ev_begin = ts->events.get(), ev_end = ts->events.get();
-    HIP_TRY(hipEventRecord(ev_begin, stream));
-    for (int s0 = 0; s0 < o.spp; s0 += spb) {
-        const int nb = std::min(spb, o.spp - s0);
-        const int64_t n = (int64_t)nb * npix;
-        rp.s0 = s0, rp.spb = nb;
-        start_batch(sc, st, rp, n, wide_grid, counting, tm, stream);
-        HIP_TRY(launch_closest<R>(ctx, sc, st, rp, 0, n, false));
-        tm.begin(TK_SHADE);
-        hipLaunchKernelGGL((k_features<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.dev, st, sc.features.p, out, W, n_rows, nb, s0 == 0 ? 1 : 0, want);
-        tm.end();
-    }
-    tm.begin(TK_OTHER);
-    hipLaunchKernelGGL((k_features_resolve<R>), dim3(pix_grid), dim3(BLOCK), 0, stream, sc.features.p, out, W, n_rows, o.spp);
-    tm.end();
-    HIP_TRY(hipEventRecord(ev_end, stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (tm.err != hipSuccess) return fail(TAKE_E_DEVICE, std::string("kernel timing events: ") + hipGetErrorString(tm.err));
-
-    unsigned long long c[C_NUM_WORDS];
-    TakeCounters &tc = ts->counters;
-    rc = read_counters(sc, tc, c);
-    if (rc) return rc;
-    tc.samples = (uint64_t)npix * (uint64_t)o.spp;
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    tc.ms_total = ms;
-    sum_timings(ts, tc);
-    return TAKE_OK;
+    fr.tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((k_features_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.features.p, out, fr.rp.width, fr.n_rows, o.spp);
+    fr.tm.end();
+    return end_frame(fr, (uint64_t)npix * (uint64_t)o.spp);
 }
 
 template <class R>
-int trace_impl(TakeScene *ts, SceneT<R> &sc, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any, bool count,
-               hipStream_t stream) {
+int trace_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any,
+               bool count, hipStream_t stream) {
     if (n < 0 || n >= ((int64_t)1 << 31) - (1 << 26)) return fail(TAKE_E_INVALID, "ray count out of range");
-    StackSpill spill{sc.spill.p, sc.spill_stride};
-    int32_t *q = sc.qwords.p;
+    Frame<R> fr{ts, sc, work, stream};
+    int32_t *q = work.qwords.p;
     HIP_TRY(hipMemsetAsync(q + Q_HEAD_CLOSEST, 0, sizeof(int32_t), stream));
-    HIP_TRY(hipMemsetAsync(sc.counters.p, 0, sc.counters.bytes(), stream));
-    ts->events.reset();
-    hipEvent_t a = ts->events.get(), b = ts->events.get();
-    HIP_TRY(hipEventRecord(a, stream));
+    if (const int rc = start_frame(fr)) return rc;
     const HookIo<R> io{sc.dev.prims, (const RayAoS<R> *)d_rays, (HitAoS<R> *)d_hits, d_occ, sc.dev.inst_shade};
-    HIP_TRY(launch_trace<R>(sc.trace, any, count, dim3(sc.trace_grid), stream, sc.dev, io, nullptr, (int32_t)n, q + Q_HEAD_CLOSEST,
-                            sc.counters.p, -1, spill));
-    HIP_TRY(hipEventRecord(b, stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    unsigned long long c[C_NUM_WORDS];
-    ts->counters = fresh_counters(sc);
-    const int rc = read_counters(sc, ts->counters, c);  // (the hooks count no rays on the device: n of the one kind)
-    if (rc) return rc;
-    (any ? ts->counters.rays_shadow : ts->counters.rays_closest) = (uint64_t)n;
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, a, b));
-    (any ? ts->counters.ms_trace_shadow : ts->counters.ms_trace_closest) = ms;
-    (any ? ts->counters.launches_trace_shadow : ts->counters.launches_trace_closest) = 1;
-    ts->counters.ms_total = ms;
+    HIP_TRY(launch_trace(sc, any, count, (unsigned)sc.trace_state.trace_grid, stream, io, nullptr, (int32_t)n, q + Q_HEAD_CLOSEST, work.counters.p, -1));
+    TakeCounters &tc = ts->counters = fresh_counters(sc);
+    if (const int rc = end_frame(fr, 0)) return rc;  // (the hooks count no rays on the device: n of the one kind)
+    (any ? tc.rays_shadow : tc.rays_closest) = (uint64_t)n;
+    (any ? tc.ms_trace_shadow : tc.ms_trace_closest) = tc.ms_total;
+    (any ? tc.launches_trace_shadow : tc.launches_trace_closest) = 1;
     return TAKE_OK;
 }
 
-template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
+template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     if (n == 0) return TAKE_OK;
     // entry distances are ordered through their bit patterns (non-negative floats): a ray must start at tmin >= 0
     for (int64_t i = 0; i < n; i++) {
@@ -682,7 +618,7 @@ template <class R> int trace_host(TakeScene *ts, SceneT<R> &sc, const void *rays
     if (hipMemcpy(d_rays.p, rays, n * sizeof(RayAoS<R>), hipMemcpyHostToDevice) != hipSuccess)
         return fail(TAKE_E_DEVICE, "ray upload failed");
     if (any ? d_occ.alloc(n) != hipSuccess : d_hits.alloc(n) != hipSuccess) return fail(TAKE_E_NOMEM, "hit buffer allocation failed");
-    const int rc = trace_impl(ts, sc, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
+    const int rc = trace_impl(ts, sc, work, d_rays.p, n, d_hits.p, d_occ.p, any, false, nullptr);
     if (rc) return rc;
     hipError_t e = any ? hipMemcpy(occ, d_occ.p, n * sizeof(int32_t), hipMemcpyDeviceToHost)
                        : hipMemcpy(hits, d_hits.p, n * sizeof(HitAoS<R>), hipMemcpyDeviceToHost);
@@ -714,28 +650,67 @@ bool compressed_nodes_supported() { return TQ_GROUP <= 2; }
 // The grid is resident blocks of the instance the render's closest-hit rounds run x CUs.  Blocks per CU: the
 // occupancy of that instance, asked once per scene — a replica arrives with its source's figure.
 template <class R> hipError_t alloc_trace_state(SceneT<R> &sc, int num_cus) {
-    hipError_t e = sc.qwords.alloc(Q_NUM_WORDS + 2 * N_SORT_KEYS);
-    if (e == hipSuccess) e = sc.counters.alloc(C_NUM_WORDS);
+    TraceState &t = sc.trace_state;
+    hipError_t e = hipSuccess;
     int rays_per_block = 0;
     const bool found = with_trace_kernel<R, false, false, PathIo<R>>(sc.trace, [&](auto kernel, auto geom) {
-        rays_per_block = geom.GROUPS, sc.spill_levels = geom.SPILL;
-        if (e != hipSuccess || sc.blocks_per_cu > 0) return;
+        rays_per_block = geom.GROUPS, t.spill_levels = geom.SPILL;
+        if (t.blocks_per_cu > 0) return;
         int per_cu = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TQ_BLOCK, 0);
         per_cu = std::max(1, std::min(per_cu, 8));
         if (const char *env = std::getenv("TAKE_HIP_TRACE_BLOCKS")) per_cu = std::max(1, std::min(per_cu, std::atoi(env)));  // experiment: leave room for a concurrent kernel
-        sc.blocks_per_cu = per_cu;
+        t.blocks_per_cu = per_cu;
     });
     if (e != hipSuccess) return e;
     if (!found) return hipErrorInvalidDeviceFunction;
-    sc.trace_grid = num_cus * sc.blocks_per_cu;
-    sc.spill_stride = (int64_t)sc.trace_grid * rays_per_block;
-    if ((e = sc.spill.alloc((size_t)sc.spill_stride * sc.spill_levels)) != hipSuccess) return e;
-    if ((e = hipMemset(sc.qwords.p, 0, sc.qwords.bytes())) != hipSuccess) return e;
-    return hipMemset(sc.counters.p, 0, sc.counters.bytes());
+    t.trace_grid = num_cus * t.blocks_per_cu;
+    t.spill_stride = (int64_t)t.trace_grid * rays_per_block;
+    return t.spill.alloc((size_t)t.spill_stride * t.spill_levels);
 }
 template hipError_t alloc_trace_state<float>(SceneT<float> &, int);
 template hipError_t alloc_trace_state<double>(SceneT<double> &, int);
+
+template <class R> hipError_t RenderWorkspace<R>::create() {
+    hipError_t e = qwords.alloc(Q_NUM_WORDS + 2 * N_SORT_KEYS);
+    if (e == hipSuccess) e = counters.alloc(C_NUM_WORDS);
+    if (e == hipSuccess) e = hipMemset(qwords.p, 0, qwords.bytes());
+    return e != hipSuccess ? e : hipMemset(counters.p, 0, counters.bytes());
+}
+// (the f32 records of a mixed-precision render stay: they are sized on their own, below)
+template <class R> void RenderWorkspace<R>::release() {
+    records.release(), queue[0].release(), queue[1].release(), shadow_queue.release();
+    sorted_queue.release(), sort_keys.release();
+    capacity = 0;
+}
+// (in this order: the allocation-failure tests count the allocations)
+template <class R> int RenderWorkspace<R>::ensure(int64_t slots, int64_t npix, bool f32_records) {
+    if (slots > capacity) {
+        release();
+        const bool ok = records.alloc((size_t)PATH_REC * slots) == hipSuccess && queue[0].alloc(slots) == hipSuccess &&
+                        queue[1].alloc(slots) == hipSuccess && shadow_queue.alloc(slots) == hipSuccess &&
+                        sorted_queue.alloc(slots) == hipSuccess && sort_keys.alloc(slots) == hipSuccess;
+        if (!ok) {
+            release();
+            return fail(TAKE_E_NOMEM, "out of device memory for " + std::to_string(slots) + " path slots (" +
+                                          std::to_string((size_t)slots * (PATH_REC * sizeof(R) + 17) >> 20) + " MiB)");
+        }
+        capacity = slots;
+    }
+    if ((int64_t)accum.n < 3 * npix) {
+        if (accum.alloc(3 * npix) != hipSuccess || out.alloc(3 * npix) != hipSuccess) {
+            accum.release(), out.release();
+            return fail(TAKE_E_NOMEM, "out of device memory for the framebuffer");
+        }
+    }
+    if (f32_records && (int64_t)records_f32.n < (int64_t)PATH_REC * slots && records_f32.alloc((size_t)PATH_REC * slots) != hipSuccess) {
+        release();  // (a failed alloc has released records_f32 itself)
+        return fail(TAKE_E_NOMEM, "out of device memory for the f32 path records of a mixed-precision render (" + std::to_string(slots) + " path slots)");
+    }
+    return TAKE_OK;
+}
+template struct RenderWorkspace<float>;
+template struct RenderWorkspace<double>;
 
 int rows_of(int height, int first, int stride, int32_t *rows_out) {
     const int n_strips = (height + TILE_ROWS - 1) / TILE_ROWS;
@@ -750,24 +725,24 @@ int rows_of(int height, int first, int stride, int32_t *rows_out) {
 }
 
 int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample, bool keep_accum) {
-    return on_primary(ts, [&](auto &sc) { return render_impl(ts, sc, o, d_out, stream, first_sample, keep_accum); });
+    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, d_out, stream, first_sample, keep_accum); });
 }
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img) {
-    return on_primary(ts, [&](auto &sc) {
-        int rc = ensure_workspace(sc, 0, npix);
-        if (!rc) rc = render_impl(ts, sc, o, sc.out.p, nullptr, 0, false);
-        img = sc.out.p;
+    return on_primary(ts, [&](auto &sc, auto &work) {
+        int rc = work.ensure(0, npix, false);
+        if (!rc) rc = render_impl(ts, sc, work, o, work.out.p, nullptr, 0, false);
+        img = work.out.p;
         return rc;
     });
 }
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream) {
-    return on_primary(ts, [&](auto &sc) { return features_impl(ts, sc, o, d_out, stream); });
+    return on_primary(ts, [&](auto &sc, auto &work) { return features_impl(ts, sc, work, o, d_out, stream); });
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
-    return on_primary(ts, [&](auto &sc) { return trace_host(ts, sc, rays, n, hits, occ, any); });
+    return on_primary(ts, [&](auto &sc, auto &work) { return trace_host(ts, sc, work, rays, n, hits, occ, any); });
 }
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream) {
-    return on_primary(ts, [&](auto &sc) { return trace_impl(ts, sc, d_rays, n, d_hits, nullptr, false, count, stream); });
+    return on_primary(ts, [&](auto &sc, auto &work) { return trace_impl(ts, sc, work, d_rays, n, d_hits, nullptr, false, count, stream); });
 }
 
 }  // namespace tk_host

@@ -1,7 +1,9 @@
-// tk_scene_handle.h — the scene handle (TakeScene: one SceneT per precision side), the walks over its sides
-// (on_primary, for_each_side, on_side, stage_then_commit) and what tk_create.hip (scene creation), tk_group.hip (groups)
-// and tk_api.hip (the other entry points) call of tk_render.hip (the only unit that compiles the kernels of tk_kernels.h)
-// and of tk_build.hip (the device LBVH build: the only one that compiles tk_build_gpu.h's).  Includes no kernel source.
+// tk_scene_handle.h — the scene handle and who owns what in it: TakeScene has one SceneT per precision side (the scene
+// itself), each with the TraceState of its trace kernel instance, and ONE RenderWorkspace, of the primary side's precision.
+// Then the walks over the sides (on_primary, for_each_side, on_side, stage_then_commit) and what tk_create.hip (scene
+// creation), tk_group.hip (groups) and tk_api.hip (the other entry points) call of tk_render.hip (the only unit that
+// compiles the kernels of tk_kernels.h) and of tk_build.hip (the device LBVH build: the only one that compiles
+// tk_build_gpu.h's).  Includes no kernel source.
 #pragma once
 #include <chrono>
 #include <cstdio>
@@ -68,6 +70,18 @@ template <class R> constexpr size_t node_bytes(NodeFormat f) {
     return f == NodeFormat::Q8 ? sizeof(QNode8) : (f == NodeFormat::Q4 ? sizeof(QNode4) : sizeof(Node4<R>));
 }
 
+// The persistent trace grid of one side (alloc_trace_state).  Blocks per CU and spill levels are properties of the kernel
+// instance the side's `trace` selects (a replica takes the former from its source), the grid is blocks per CU times the device's CUs.
+struct TraceState {
+    DevBuf<unsigned long long> spill;  // the stack levels beyond the LDS: [level][ray group of the grid]
+    int blocks_per_cu = 0, spill_levels = 0;
+    int trace_grid = 0;
+    int64_t spill_stride = 0;  // ray groups in the persistent trace grid
+    // blocks of a launch over a queue of at most n_bound rays: the grid, cut down when they cannot fill it (one block per 128 rays)
+    unsigned grid_for(int64_t n_bound) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(trace_grid, (n_bound + 127) / 128)); }
+};
+
+// One precision side of a scene: what a replica copies, bind() points into and a stage replaces.
 template <class R> struct SceneT {
     HostScene<R> host;  // kept: cheap relative to HBM copies, used for stats
     DevBuf<Node4<R>> nodes;
@@ -86,24 +100,9 @@ template <class R> struct SceneT {
     DevBuf<R> env_marginal, env_conditional;
     DevBuf<int32_t> env_guide_m, env_guide_c;
     DeviceScene<R> dev{};
-    // render workspace (grown on demand)
-    DevBuf<R> state_r;
-    DevBuf<int32_t> queue[2], shadow_queue, sorted_queue;
-    DevBuf<uint8_t> sort_keys;            // one key byte per queue entry (material sort)
-    DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
-    DevBuf<R> accum, out;
-    DevBuf<R> features;  // per-pixel sums of the feature pass (take_hip_render_features*): FEATURE_WORDS planes, its own — not accum
-    DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
-    DevBuf<unsigned long long> counters;
-    DevBuf<unsigned long long> spill;
-    int64_t capacity = 0;  // path slots allocated
     bool built_on_device = false;
-    TraceKind trace;           // which trace kernel instance traverses this scene
-    // the persistent trace grid (alloc_trace_state): blocks per CU and spill levels are properties of the instance
-    // (a replica takes them from its source), the grid is that times the CUs of the scene's own device
-    int blocks_per_cu = 0, spill_levels = 0;
-    int trace_grid = 0;
-    int64_t spill_stride = 0;  // ray groups in the persistent trace grid
+    TraceKind trace;         // which trace kernel instance traverses this scene
+    TraceState trace_state;  // that instance's grid on the scene's device
 
     // The scene arrays: f(x.nodes...), f(x.qnodes...), ... for the scenes x, in the order replicate_t allocates them.
     template <class F, class... S> static void for_each_array(F &&f, S &...x) {
@@ -130,6 +129,29 @@ template <class R> struct SceneT {
     }
 };
 
+// The render workspace of a handle, in the precision R of its primary side: every render, feature pass and trace hook
+// of the scene uses this one set (the f32 rounds of a mixed-precision render too: slot numbers and queue words do not
+// depend on the precision of the records they point to).  Per-slot buffers and framebuffers grow on demand (ensure);
+// queue words and counters are made once, with the handle (create).  Defined in tk_render.hip.
+template <class R> struct RenderWorkspace {
+    DevBuf<R> records;           // PATH_REC words per path slot
+    DevBuf<float> records_f32;   // a mixed-precision render: the f32 record beside each f64 one
+    DevBuf<int32_t> queue[2], shadow_queue, sorted_queue;
+    DevBuf<uint8_t> sort_keys;             // one key byte per queue entry (material sort)
+    DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
+    DevBuf<R> accum, out;
+    DevBuf<R> features;  // per-pixel sums of the feature pass (take_hip_render_features*): FEATURE_WORDS planes, its own — not accum
+    DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
+    DevBuf<unsigned long long> counters;
+    int64_t capacity = 0;  // path slots allocated
+    hipError_t create();   // zeroed queue words and counters
+    // Records and queues for `slots` paths, a framebuffer of npix pixels (0: left as it is), with f32_records one f32
+    // record per slot.  A failed allocation leaves the handle WITHOUT per-slot buffers (release) and returns
+    // TAKE_E_NOMEM: the next render allocates afresh instead of trusting a stale capacity over null pointers.
+    int ensure(int64_t slots, int64_t npix, bool f32_records);
+    void release();
+};
+
 }  // namespace tk_host
 
 struct TakeScene {
@@ -152,6 +174,8 @@ struct TakeScene {
     int instrumentation = 0;
     tk_host::SceneT<float> f;
     tk_host::SceneT<double> d;
+    tk_host::RenderWorkspace<float> work_f;  // the one workspace of the handle: of an F32 scene
+    tk_host::RenderWorkspace<double> work_d;  // ... of an F64 or MIXED one
     TakeCounters counters{};
     tk_host::EventPool events;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> timed;
@@ -164,8 +188,8 @@ struct TakeScene {
 
 namespace tk_host {
 
-// f(the scene's SceneT that renders, traces and reports): d for F64 and MIXED scenes, f for F32 ones
-template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d) : f(ts->f); }
+// f(the scene's SceneT that renders, traces and reports, the handle's workspace): d for F64 and MIXED scenes, f for F32 ones
+template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d, ts->work_d) : f(ts->f, ts->work_f); }
 // The sides a scene has: the f64 one (side = TAKE_PRECISION_F64) of F64 and MIXED scenes, the f32 one of F32 and MIXED ones.
 // on_side: f(the named side).  for_each_side: f(every side), f64 first as creation makes them, and of `more` the same
 // side with it; f returns a TAKE_* code, and the first that is not TAKE_OK ends the walk and is returned.
@@ -222,7 +246,7 @@ struct PhaseClock {
 // (f32) and 22 % (f64) ahead of the pair kernel.  The other group sizes stay behind -DTQ_GROUP for
 // comparison builds; the quad kernel does not traverse compressed nodes.
 bool compressed_nodes_supported();
-// Zeroed queue words and counters of a scene side, its persistent trace grid on a device of num_cus CUs, the spill.
+// sc.trace_state: the persistent trace grid of a scene side on a device of num_cus CUs, the spill area.
 template <class R> hipError_t alloc_trace_state(SceneT<R> &sc, int num_cus);
 // image rows of the strips first, first + stride, ... (increasing; rows_out may be null) -> their number
 int rows_of(int height, int first, int stride, int32_t *rows_out);
@@ -302,7 +326,7 @@ struct MeshUpdateInputs {
 template <class R> struct MeshUpdateStage {
     // a side of its own that creation's tail builds into: prims (leaf order), qnodes or nodes, lights and their tables,
     // host.stats / root_child / grid / q_inflation / lights / light_pmf / light_cdf, trace — and, when the node format
-    // changed, the trace state of the new kernel instance (alloc_trace_state)
+    // changed, the trace_state of the new kernel instance (alloc_trace_state).  (A side holds no workspace.)
     SceneT<R> built;
     // built.normals: with new normals, the scene's whole array copied and the named meshes' parts rewritten
     bool new_lights = false, new_normals = false, new_trace_state = false;

@@ -1,8 +1,8 @@
 """GPU robustness of the C ABI: failure paths leave a scene usable, and the regimes the default bench reaches
 (path state beyond 4 GiB, slot indices beyond 2^25) give the same image as small batches.
 
-  * a render whose workspace cannot be allocated (fault injection at the 1st / 3rd / 6th allocation) returns
-    TAKE_E_NOMEM, leaves the scene without a workspace (no stale capacity over null pointers) and the next render on
+  * a render whose workspace cannot be allocated (fault injection at the 1st / 3rd / 6th allocation; mixed precision:
+    the 7th, the f32 records) returns TAKE_E_NOMEM, leaves the scene without a workspace (no stale capacity over null pointers) and the next render on
     the same scene is correct;
   * a 35 M-slot batch (4.5 GB of path state: byte offsets beyond 2^32) is bit-identical to 1-spp batches, on a
     mixed-material scene so that the material sort sees the large queue too;
@@ -18,12 +18,14 @@ from take_amd import cdefs as D
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("nth", [1, 3, 6])
-def test_failed_workspace_allocation_leaves_scene_usable(nth, monkeypatch):
+@pytest.mark.parametrize("precision,nth", [pytest.param(D.TAKE_PRECISION_F32, 1, id="1"), pytest.param(D.TAKE_PRECISION_F32, 3, id="3"),
+                                           pytest.param(D.TAKE_PRECISION_F32, 6, id="6"), pytest.param(D.TAKE_PRECISION_MIXED, 7, id="mixed-7")])
+def test_failed_workspace_allocation_leaves_scene_usable(precision, nth, monkeypatch):
     """the nth allocation of the render workspace fails (fault injection, TAKE_HIP_FAIL_ALLOC: a real out-of-memory
-    cannot be provoked reliably — the driver over-commits): path state = 1st, a queue = 3rd, the sort keys = 6th"""
+    cannot be provoked reliably — the driver over-commits): path state = 1st, a queue = 3rd, the sort keys = 6th; mixed
+    precision, 7th (the framebuffer exists): the f32 records beside the f64 ones, of a batch the caller pinned"""
     sd = golden_scene("cbox")  # 64 x 64
-    sc = capi.Scene(sd, precision=D.TAKE_PRECISION_F32)
+    sc = capi.Scene(sd, precision=precision)
     try:
         want = sc.render(spp=2, max_depth=5, seed=4)
         monkeypatch.setenv("TAKE_HIP_FAIL_ALLOC", str(nth))
