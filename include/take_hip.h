@@ -376,8 +376,8 @@ int take_hip_scene_set_camera(TakeScene *scene, const TakeCamera *camera);
  * The finiteness check is the update's own — take_hip_scene_create has none — and covers what the records are made of:
  * the coordinates of every vertex a face refers to, as the scene's arithmetic takes them (1e300 is not finite for an
  * f32 or mixed scene).  A vertex no face refers to, and the normals, are taken as they are, as scene_create takes them.
- * TAKE_E_INVALID with a message that starts with "unsupported": a two-level scene (n_instances > 0; its prototypes are
- * a follow-up), a scene flattened from instances, a TAKE_HIP_NODES=q8 scene, a new tree of fewer than two leaves or too
+ * TAKE_E_INVALID with a message that starts with "unsupported": a two-level scene (n_instances > 0: this symbol keeps
+ * refusing it; take_hip_scene_update_meshes below takes every scene), a scene flattened from instances, a TAKE_HIP_NODES=q8 scene, a new tree of fewer than two leaves or too
  * deep for the traversal stack. */
 typedef struct TakeMeshUpdate {
     int32_t mesh;             /* index into the TakeSceneDesc.meshes the scene was created from */
@@ -386,6 +386,35 @@ typedef struct TakeMeshUpdate {
     const double *normals;    /* n_vertices x 3, or NULL = keep; only for a mesh that has vertex normals */
 } TakeMeshUpdate;
 int take_hip_scene_set_mesh_vertices(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
+/* The same for EVERY scene, two-level ones included (a new symbol of ABI version 5; TakeMeshUpdate is reused).
+ * A scene without placements: this call IS take_hip_scene_set_mesh_vertices — same path, same bytes, same refusals,
+ * a scene flattened from instances among them.
+ * A two-level scene (n_instances > 0): every record made from a named mesh gets the new geometry, wherever it lives.
+ *  - The mesh is the prototype of at least one placement: its object-space records are made again (shape_id = face,
+ *    no area light), its tree is rebuilt on the device by the LBVH pipeline with the scene's leaf size request and put
+ *    into the scene's node format on its own grid.  Prototypes not named keep their records and trees bit for bit,
+ *    whoever built them.
+ *  - Faces of the mesh are among the shape arrays (a mesh may be both): their records in the head of the record array
+ *    are rewritten, and area lights on them get new records and power tables.
+ *  - New vertex normals are converted in place of the old ones, for either role.
+ *  - The top level is rebuilt under the scene's CURRENT transforms, by the path take_hip_scene_set_instance_transforms
+ *    takes: the shapes' boxes from their records, the placements' from the prototypes' records after the update.
+ *    Placement records keep their transforms, materials, tags and shape bases; placements of a moved prototype get its
+ *    new root and grid, and every placement's root follows its prototype's new position in the node array.
+ * Afterwards the scene traces and renders exactly as a scene newly created with TAKE_BUILDER_DEVICE_LBVH and the same
+ * max_leaf_size from the description with the new arrays and the current transforms: hit tables, occlusion and images
+ * bit for bit.  The top-level tree need not be byte-identical (its placement boxes come from records, not from the
+ * caller's doubles, as after a re-pose); the moved prototypes' records are.  The scene KEEPS its node format — the
+ * float nodes of untouched prototypes no longer exist, so the inflation rule cannot be run again for the whole scene;
+ * results do not depend on it.  take_hip_scene_build_info keeps reporting what it reported (untouched trees may still
+ * be the host's); take_hip_scene_stats reports the new node count and depth.  take_hip_scene_set_instance_transforms
+ * and further updates work on the new layout.
+ * TAKE_E_INVALID: as take_hip_scene_set_mesh_vertices, those that need no scene before the device is looked at; the
+ * finiteness check covers the records made in either role.  TAKE_E_INVALID with a message that starts with
+ * "unsupported": a scene built under TAKE_HIP_BRAID > 1 or TAKE_HIP_NODES=q8, a rebuilt prototype tree of fewer than
+ * two leaves, a depth (new top level + deepest prototype + return marker) beyond the traversal stack, node counts
+ * beyond the 32-bit record offsets. */
+int take_hip_scene_update_meshes(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
 
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order

@@ -28,7 +28,7 @@ EXPORTS = [
     "take_hip_mesh_from_obj", "take_hip_mesh_from_obj_file", "take_hip_mesh_compute_normals", "take_hip_compute_normals",
     "take_hip_scene_build_info",
     "take_hip_scene_set_instance_transforms", "take_hip_scene_set_instance_transforms_device", "take_hip_scene_set_camera",
-    "take_hip_scene_set_mesh_vertices",
+    "take_hip_scene_set_mesh_vertices", "take_hip_scene_update_meshes",
     "take_hip_render_features", "take_hip_render_features_device",
     "take_hip_debug_tree_info", "take_hip_debug_tree",
 ]
@@ -370,7 +370,15 @@ class Scene:
                            D.c_double3(*map(float, lookfrom)), D.c_double3(*map(float, lookat)), D.c_double3(*map(float, up)), float(vfov))
         _check(lib().take_hip_scene_set_camera(self.h, C.byref(cam)))
 
-    def set_mesh_vertices(self, updates):
+    def update_meshes(self, updates):
+        """new vertices for meshes of ANY scene, two-level ones included (take_hip_scene_update_meshes): the arguments of
+        set_mesh_vertices.  In a two-level scene a named mesh moves in every role it has — its faces among the shapes,
+        and as the prototype of placements, whose tree is rebuilt on the device — and the top level is rebuilt under the
+        scene's current transforms; afterwards the scene traces and renders as one newly created from the description
+        with these arrays and those transforms.  A scene without placements: the same as set_mesh_vertices."""
+        self.set_mesh_vertices(updates, _entry="take_hip_scene_update_meshes")
+
+    def set_mesh_vertices(self, updates, _entry="take_hip_scene_set_mesh_vertices"):
         """new vertices for meshes of a scene without placements (take_hip_scene_set_mesh_vertices): `updates` is
         {mesh_id: positions} or {mesh_id: (positions, normals)} (a tuple), every array (n_vertices, 3) float64 and complete, normals
         None = keep.  numpy arrays (or anything numpy converts) are read from host memory; torch device tensors —
@@ -401,7 +409,7 @@ class Scene:
             device = on_device(pos)
             recs[k].mesh, recs[k].flags = int(mesh), D.TAKE_MESH_DEVICE_ARRAYS if device else 0
             recs[k].positions, recs[k].normals = pointer(pos, device), pointer(nrm, device)
-        _check(lib().take_hip_scene_set_mesh_vertices(self.h, recs, len(updates)))
+        _check(getattr(lib(), _entry)(self.h, recs, len(updates)))
         del keep
 
     def trace_closest(self, rays_abi):

@@ -98,6 +98,7 @@ SCENE_UPDATE_PROTOTYPES = {
     "take_hip_scene_set_instance_transforms_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "take_hip_scene_set_camera": [C.c_void_p, C.POINTER(TakeCamera)],
     "take_hip_scene_set_mesh_vertices": [C.c_void_p, C.POINTER(TakeMeshUpdate), C.c_int32],
+    "take_hip_scene_update_meshes": [C.c_void_p, C.POINTER(TakeMeshUpdate), C.c_int32],
 }
 
 

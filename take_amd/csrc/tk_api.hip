@@ -28,10 +28,13 @@ int check_repose(const TakeScene *ts, int64_t n) {
     if (!plain) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_BRAID > 1 or TAKE_HIP_NODES=q8");
     return TAKE_OK;
 }
-// New transforms (device memory, complete) for all placements of ts (check_repose passed)
-int set_instance_transforms(TakeScene *ts, const double *d_xforms, int64_t n) {
+// New transforms (device memory the library owns, complete) for all placements of ts (check_repose passed); a
+// successful call keeps them: they are the scene's current transforms from then on (TakeScene::xforms)
+int set_instance_transforms(TakeScene *ts, DevBuf<double> &xforms, int64_t n) {
     try {
-        return stage_then_commit<ReposeStage>(ts, [&](const auto &sc, auto &stage) { return repose_two_level_device(sc, d_xforms, n, stage); });
+        const int rc = stage_then_commit<ReposeStage>(ts, [&](const auto &sc, auto &stage) { return repose_two_level_device(sc, xforms.p, n, stage); });
+        if (!rc) ts->xforms = std::move(xforms);
+        return rc;
     } catch (const std::bad_alloc &) {
         return fail(TAKE_E_NOMEM, "out of host memory while re-posing the placements");
     }
@@ -211,7 +214,10 @@ int take_hip_scene_set_instance_transforms_device(TakeScene *ts, const double *d
     const int rc = check_repose(ts, n);
     if (rc) return rc;
     if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return set_instance_transforms(ts, d_xforms, n);
+    DevBuf<double> own;  // (a copy the scene can keep: the caller's memory stays the caller's)
+    if (own.alloc(12 * (size_t)n) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the transforms");
+    HIP_TRY(hipMemcpy(own.p, d_xforms, own.bytes(), hipMemcpyDeviceToDevice));
+    return set_instance_transforms(ts, own, n);
 }
 int take_hip_scene_set_instance_transforms(TakeScene *ts, const double *xforms, int64_t n) {
     if (!ts || !xforms) return fail(TAKE_E_INVALID, "null argument");
@@ -223,11 +229,13 @@ int take_hip_scene_set_instance_transforms(TakeScene *ts, const double *xforms, 
     DevBuf<double> d_xforms;
     if (d_xforms.alloc(12 * (size_t)n) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the transforms");
     HIP_TRY(hipMemcpy(d_xforms.p, xforms, d_xforms.bytes(), hipMemcpyHostToDevice));
-    return set_instance_transforms(ts, d_xforms.p, n);
+    return set_instance_transforms(ts, d_xforms, n);
 }
 // New vertices for meshes of a resident scene (include/take_hip.h): the arguments that need no scene, the device, the
 // arguments against the scene, what the path does not support; then every side staged and every side committed.
-int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) {
+// two_level_too: take_hip_scene_update_meshes — a scene with placements takes update_two_level_meshes_device, any other
+// scene the one path both symbols share.
+static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates, bool two_level_too) {
     if (!ts || !updates) return fail(TAKE_E_INVALID, "null argument");
     if (n_updates <= 0) return fail(TAKE_E_INVALID, "n_updates must be positive");
     try {
@@ -252,18 +260,30 @@ int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *update
             const bool has_normals = on_primary(ts, [&](const auto &sc, const auto &) { return (size_t)u.mesh < sc.host.meshes.size() && sc.host.meshes[u.mesh].nbase >= 0; });
             if (u.normals && !has_normals) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
         }
-        if (ts->n_placements > 0) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (the prototypes' trees are not rebuilt)");
+        const bool two_level = ts->n_placements > 0;
+        if (two_level && !two_level_too) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (take_hip_scene_update_meshes moves the vertices of its meshes)");
         if (ts->flattened) return fail(TAKE_E_INVALID, "unsupported: the scene was flattened from instances");
         const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.nodes == NodeFormat::Q8; });
         if (q8) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_NODES=q8");
-        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
-        if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
-        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.prims.n != ts->shape_face.n; }))
-            return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+        if (two_level) {
+            if (const int rc = check_repose(ts, ts->n_placements)) return rc;  // (TAKE_HIP_BRAID > 1: "unsupported")
+            if (!ts->xforms.p || (int64_t)ts->xforms.n != 12 * ts->n_placements) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group");
+            if (on_primary(ts, [&](const auto &sc, const auto &) { return (int64_t)sc.prims.n - sc.host.blas_prims != (int64_t)ts->shape_face.n; }))
+                return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+        } else {
+            if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
+            if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
+            if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.prims.n != ts->shape_face.n; }))
+                return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+        }
         TAKE_ON_DEVICE(ts);
         MeshUpdateInputs in;
         int rc = in.upload(ts->mesh_vertices, updates, n_updates);
         if (rc) return rc;
+        if (two_level)
+            return stage_then_commit<ProtoUpdateStage>(ts, [&](const auto &sc, auto &stage) {
+                return update_two_level_meshes_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->xforms.p, ts->max_leaf, stage);
+            });
         const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
         return stage_then_commit<MeshUpdateStage>(ts, [&](const auto &sc, auto &stage) {
             return update_mesh_vertices_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, stage);
@@ -274,6 +294,8 @@ int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *update
         return fail(TAKE_E_INVALID, std::string("updating the meshes failed: ") + e.what());
     }
 }
+int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) { return update_meshes(ts, updates, n_updates, false); }
+int take_hip_scene_update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) { return update_meshes(ts, updates, n_updates, true); }
 int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
     if (!ts || !camera) return fail(TAKE_E_INVALID, "null argument");
     if (camera->width != ts->width() || camera->height != ts->height())

@@ -3,7 +3,8 @@
 // calls it), and the top-level half of it entered again for a resident scene whose placements get new transforms
 // (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it), and creation's tail entered
 // again for a resident scene whose meshes get new vertices (update_mesh_vertices_device;
-// take_hip_scene_set_mesh_vertices calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
+// take_hip_scene_set_mesh_vertices calls it), and both joined for the meshes of a resident two-level scene
+// (update_two_level_meshes_device; take_hip_scene_update_meshes calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -523,6 +524,9 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     h.blas_depth = proto_depth;
     h.blas_prim_first.assign(prim_base.begin(), prim_base.begin() + n_protos), h.blas_prim_count.resize(n_protos);
     for (int k = 0; k < n_protos; k++) h.blas_prim_count[k] = prim_base[k + 1] - prim_base[k];
+    h.blas_mesh = plan.proto_mesh, h.blas_node_first.assign(node_at.begin() + 1, node_at.begin() + 1 + n_protos);
+    h.blas_node_count.resize(n_protos), h.blas_depths.resize(n_protos);
+    for (int k = 0; k < n_protos; k++) h.blas_node_count[k] = protos[k].n_nodes, h.blas_depths[k] = protos[k].depth;
     bool use_q;
     std::vector<QGrid> grids;  // [1 + k]: prototype k's
     const int ra = assemble_nodes(sc, trees, node_at, compressed_ok, compressed_forced, mem, use_q, grids);
@@ -545,6 +549,65 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     HIP_TRY(hipGetLastError());
     mem.report();
     return TAKE_OK;
+}
+
+
+// The top level of a RESIDENT two-level scene made again: what the re-pose (repose_two_level_device, its steps 2-4) and
+// the update of a scene's meshes (update_two_level_meshes_device) share.  In: `head`, the n_shapes records of the
+// shapes, in any order; `prims`, the record array whose spans h.blas_prim_first / _count hold the prototypes' records;
+// the transforms (12 doubles per placement, device memory); proto_depth: the deepest prototype tree.  Out: `top`, its
+// leaf words final (instance words, single records), and the shapes' records in its leaf order at the head of dst
+// (empty: allocated here, the head alone).  Errors start with "unsupported" where no tree can be made.
+//   2. tight world boxes from the prototypes' records (k_placement_boxes_resident), widened (k_widen_tight) and
+//      padded (k_placement_pad) behind 3. the shapes' boxes from theirs;
+//   4. the top-level tree, one entry per leaf, and its records.  Where the shapes come out of an OLD leaf order, not
+//      the shape order a fresh build sorts, results do not depend on it.  Box tests are conservative, and a tie between
+//      coincident primitives is decided by values — inside the top level by the position of the record, where every
+//      group of coincident records holds its shape ids in ascending order (order_coincident; a stable sort of the shape
+//      order) and keeps them so here: equal geometry is equal boxes is equal Morton codes, and the sort is stable.
+template <class R>
+int top_level_resident(const HostScene<R> &h, const PrimRec<R> *head, const PrimRec<R> *prims, int n_shapes, const double *d_xforms, int n_inst,
+                       int proto_depth, BuildMemory &mem, DeviceTree &top, DevBuf<PrimRec<R>> &dst) {
+    using namespace lbvh;
+    const int n_protos = (int)h.blas_prim_first.size(), n_top = n_shapes + n_inst;
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    DevBuf<Box> pb;
+    DevBuf<int> scene_ord;
+    HIP_TRY(pb.alloc(n_top));
+    HIP_TRY(scene_ord.alloc(6));
+    HIP_TRY(reset_bounds(scene_ord));
+    span_boxes(head, n_shapes, pb.p, scene_ord);
+    {
+        std::vector<int2> span_h((size_t)n_inst);
+        std::vector<int64_t> block0_h((size_t)n_inst + 1, 0);
+        const std::vector<long long> tight_h = empty_tight(n_inst);
+        for (int i = 0; i < n_inst; i++) {
+            const int k = h.placements.inst_proto[i];
+            if (k < 0 || k >= n_protos) return fail(TAKE_E_INVALID, "the scene does not know the prototype of placement " + std::to_string(i));
+            span_h[i] = make_int2((int)h.blas_prim_first[k], (int)h.blas_prim_count[k]);
+            block0_h[i + 1] = block0_h[i] + (h.blas_prim_count[k] + REPOSE_CHUNK - 1) / REPOSE_CHUNK;
+        }
+        if (block0_h[n_inst] >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "unsupported: too many prototype records times placements for one launch");
+        DevBuf<int2> span;
+        DevBuf<int64_t> block0;
+        DevBuf<long long> tight, maxabs;
+        HIP_TRY(span.upload(span_h));
+        HIP_TRY(block0.upload(block0_h));
+        HIP_TRY(tight.upload(tight_h));
+        HIP_TRY(maxabs.alloc(n_inst));
+        HIP_TRY(hipMemsetAsync(maxabs.p, 0, maxabs.bytes(), stream));
+        hipLaunchKernelGGL(k_placement_boxes_resident<R>, dim3((unsigned)block0_h[n_inst]), blk, 0, stream, prims, span.p, block0.p, n_inst, d_xforms,
+                           tight.p, maxabs.p);
+        hipLaunchKernelGGL(k_widen_tight<R>, blocks_for(n_inst), blk, 0, stream, tight.p, maxabs.p, d_xforms, n_inst);
+        hipLaunchKernelGGL(k_placement_pad<R>, blocks_for(n_inst), blk, 0, stream, tight.p, n_inst, n_shapes, pb.p, scene_ord.p);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+    }
+    BuildVerdict why = BuildVerdict::Built;
+    int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top, why);
+    if (!rt && why == BuildVerdict::Built) rt = finish_top_level(top, proto_depth, n_shapes, n_top, head, dst, why);
+    return rt || why != BuildVerdict::Built ? unsupported(rt, why, "top-level tree") : TAKE_OK;
 }
 
 }  // namespace
@@ -571,8 +634,8 @@ template int build_side_on_device<double>(SceneT<double> &, const TakeSceneDesc 
 template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n64, ReposeStage<R> &out) {
     using namespace lbvh;
     const HostScene<R> &h = sc.host;
-    const int n_inst = (int)n64, n_protos = (int)h.blas_prim_first.size();
-    const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims), n_top = n_shapes + n_inst;
+    const int n_inst = (int)n64;
+    const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims);
     const bool use_q = sc.trace.nodes == NodeFormat::Q4;
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
@@ -591,51 +654,11 @@ template <class R> int repose_two_level_device(const SceneT<R> &sc, const double
         if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
     }
 
-    // 2. tight world boxes from the prototypes' resident records, 3. the shapes' boxes from theirs: the head of the
-    // record array, in the leaf order of the tree that is being replaced
-    DevBuf<Box> pb;
-    DevBuf<int> scene_ord;
-    HIP_TRY(pb.alloc(n_top));
-    HIP_TRY(scene_ord.alloc(6));
-    HIP_TRY(reset_bounds(scene_ord));
-    span_boxes(sc.prims.p, n_shapes, pb.p, scene_ord);
-    {
-        std::vector<int2> span_h((size_t)n_inst);
-        std::vector<int64_t> block0_h((size_t)n_inst + 1, 0);
-        const std::vector<long long> tight_h = empty_tight(n_inst);
-        for (int i = 0; i < n_inst; i++) {
-            const int k = h.placements.inst_proto[i];
-            if (k < 0 || k >= n_protos) return fail(TAKE_E_INVALID, "the scene does not know the prototype of placement " + std::to_string(i));
-            span_h[i] = make_int2((int)h.blas_prim_first[k], (int)h.blas_prim_count[k]);
-            block0_h[i + 1] = block0_h[i] + (h.blas_prim_count[k] + REPOSE_CHUNK - 1) / REPOSE_CHUNK;
-        }
-        if (block0_h[n_inst] >= ((int64_t)1 << 31)) return fail(TAKE_E_INVALID, "unsupported: too many prototype records times placements for one launch");
-        DevBuf<int2> span;
-        DevBuf<int64_t> block0;
-        DevBuf<long long> tight, maxabs;
-        HIP_TRY(span.upload(span_h));
-        HIP_TRY(block0.upload(block0_h));
-        HIP_TRY(tight.upload(tight_h));
-        HIP_TRY(maxabs.alloc(n_inst));
-        HIP_TRY(hipMemsetAsync(maxabs.p, 0, maxabs.bytes(), stream));
-        hipLaunchKernelGGL(k_placement_boxes_resident<R>, dim3((unsigned)block0_h[n_inst]), blk, 0, stream, sc.prims.p, span.p, block0.p, n_inst, d_xforms,
-                           tight.p, maxabs.p);
-        hipLaunchKernelGGL(k_widen_tight<R>, blocks_for(n_inst), blk, 0, stream, tight.p, maxabs.p, d_xforms, n_inst);
-        hipLaunchKernelGGL(k_placement_pad<R>, blocks_for(n_inst), blk, 0, stream, tight.p, n_inst, n_shapes, pb.p, scene_ord.p);
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-    }
-
-    // 4. the top-level tree, one entry per leaf, and its records.  The shapes come out of the OLD leaf order, not the
-    // shape order a fresh build sorts: results do not depend on it.  Box tests are conservative, and a tie between
-    // coincident primitives is decided by values — inside the top level by the position of the record, where every
-    // group of coincident records holds its shape ids in ascending order (order_coincident; a stable sort of the shape
-    // order) and keeps them so here: equal geometry is equal boxes is equal Morton codes, and the sort is stable.
+    // 2.-4. the top-level tree over the shapes' records — the head of the record array, in the leaf order of the tree
+    // that is being replaced — and the placements' boxes, from the prototypes' resident records
     DeviceTree top;
-    BuildVerdict why = BuildVerdict::Built;
-    int rt = build_tree_device(pb, scene_ord, n_top, 1, mem, top, why);
-    if (!rt && why == BuildVerdict::Built) rt = finish_top_level(top, h.blas_depth, n_shapes, n_top, sc.prims.p, out.head, why);
-    if (rt || why != BuildVerdict::Built) return unsupported(rt, why, "top-level tree");
+    const int rt = top_level_resident(sc.host, sc.prims.p, sc.prims.p, n_shapes, d_xforms, n_inst, h.blas_depth, mem, top, out.head);
+    if (rt) return rt;
     out.depth = top.depth + h.blas_depth;
 
     // 5. assembly in the scene's node format: the new top-level tree on its own grid, the prototypes' nodes copied behind
@@ -675,6 +698,8 @@ template <class R> int ReposeStage<R>::commit(SceneT<R> &sc) {
     if (qnodes.p) sc.qnodes = std::move(qnodes);
     else sc.nodes = std::move(nodes);
     sc.inst_trace = std::move(inst_trace), sc.inst_shade = std::move(inst_shade);
+    const int64_t delta = n_nodes - sc.host.stats.n_nodes;  // (the prototypes' nodes moved with the top-level tree's size)
+    for (int64_t &first : sc.host.blas_node_first) first += delta;
     install_tree(sc, n_nodes, depth, 0, grid_lo, grid_step);  // (the new tree has at least two leaves: its root is node 0)
     return TAKE_OK;
 }
@@ -710,11 +735,49 @@ int MeshUpdateInputs::upload(const std::vector<int64_t> &mesh_vertices, const Ta
     return TAKE_OK;
 }
 
+// What an update of meshes changes beside records and trees, staged in b so that a commit only moves (new_normals /
+// new_lights: which of it was made).  recs: the n_shapes records of the shapes in SHAPE order, new geometry in them.
+//   new vertex normals as the scene keeps them: a copy of the scene's whole array with the named meshes' parts rewritten;
+//   the light records of emissive faces, and the power tables from them: light_power_tables is a sequential sum in R
+//   in light order — the records come back and the host sums, as it does for a new scene.
+template <class R>
+static int stage_normals_and_lights(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
+                                    const PrimRec<R> *recs, int n_shapes, SceneT<R> &b, bool &new_normals, bool &new_lights) {
+    using namespace lbvh;
+    const int n_lights = (int)sc.lights.n;
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    for (size_t m = 0; m < in.nrm.size(); m++) {
+        if (!in.nrm[m] || mesh_vertices[m] <= 0) continue;
+        if (!new_normals) {
+            HIP_TRY(b.normals.alloc(sc.normals.n));
+            HIP_TRY(hipMemcpyAsync(b.normals.p, sc.normals.p, sc.normals.bytes(), hipMemcpyDeviceToDevice, stream));
+            new_normals = true;
+        }
+        const int64_t words = 3 * mesh_vertices[m];
+        hipLaunchKernelGGL(k_convert_normals<R>, blocks_for(words), blk, 0, stream, in.nrm[m], words, b.normals.p + 3 * (size_t)sc.host.meshes[m].nbase);
+    }
+    if (n_lights > 0) {
+        HIP_TRY(b.lights.alloc((size_t)n_lights));
+        HIP_TRY(hipMemcpyAsync(b.lights.p, sc.lights.p, sc.lights.bytes(), hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(k_update_lights<R>, blocks_for(n_lights), blk, 0, stream, b.lights.p, n_lights, recs, n_shapes, in.d_pos.p, in.d_nrm.p, sc.meshes.p,
+                           d_shape_face, sc.face_idx.p);
+        b.host.lights.resize((size_t)n_lights);
+        HIP_TRY(hipMemcpy(b.host.lights.data(), b.lights.p, b.lights.bytes(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        light_power_tables(b.host);
+        HIP_TRY(b.light_pmf.upload(b.host.light_pmf));
+        HIP_TRY(b.light_cdf.upload(b.host.light_cdf));
+        new_lights = true;
+    }
+    return TAKE_OK;
+}
+
 template <class R>
 int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
                                 int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out) {
     using namespace lbvh;
-    const int n = (int)sc.prims.n, n_lights = (int)sc.lights.n;
+    const int n = (int)sc.prims.n;
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     SceneT<R> &b = out.built;
@@ -731,34 +794,9 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
             return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
     }
 
-    // 2. new vertex normals as the scene keeps them: a copy of the scene's whole array with the named meshes' parts
-    // rewritten, so that commit() only moves
-    for (size_t m = 0; m < in.nrm.size(); m++) {
-        if (!in.nrm[m] || mesh_vertices[m] <= 0) continue;
-        if (!out.new_normals) {
-            HIP_TRY(b.normals.alloc(sc.normals.n));
-            HIP_TRY(hipMemcpyAsync(b.normals.p, sc.normals.p, sc.normals.bytes(), hipMemcpyDeviceToDevice, stream));
-            out.new_normals = true;
-        }
-        const int64_t words = 3 * mesh_vertices[m];
-        hipLaunchKernelGGL(k_convert_normals<R>, blocks_for(words), blk, 0, stream, in.nrm[m], words, b.normals.p + 3 * (size_t)sc.host.meshes[m].nbase);
-    }
-
-    // 3. the light records of emissive faces, and the power tables from them: light_power_tables is a sequential sum
-    // in R in light order — the records come back and the host sums, as it does for a new scene
-    if (n_lights > 0) {
-        HIP_TRY(b.lights.alloc((size_t)n_lights));
-        HIP_TRY(hipMemcpyAsync(b.lights.p, sc.lights.p, sc.lights.bytes(), hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL(k_update_lights<R>, blocks_for(n_lights), blk, 0, stream, b.lights.p, n_lights, b.prims.p, n, in.d_pos.p, in.d_nrm.p, sc.meshes.p,
-                           d_shape_face, sc.face_idx.p);
-        b.host.lights.resize((size_t)n_lights);
-        HIP_TRY(hipMemcpy(b.host.lights.data(), b.lights.p, b.lights.bytes(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipGetLastError());
-        light_power_tables(b.host);
-        HIP_TRY(b.light_pmf.upload(b.host.light_pmf));
-        HIP_TRY(b.light_cdf.upload(b.host.light_cdf));
-        out.new_lights = true;
-    }
+    // 2. new vertex normals, 3. the light records of emissive faces and the power tables
+    const int rl = stage_normals_and_lights(sc, in, mesh_vertices, d_shape_face, b.prims.p, n, b, out.new_normals, out.new_lights);
+    if (rl) return rl;
 
     // 4. creation's tail: boxes, tree, nodes in the format the inflation rule chooses, records into leaf order
     BuildVerdict why = BuildVerdict::Built;
@@ -796,5 +834,205 @@ template int update_mesh_vertices_device<float>(const SceneT<float> &, const Mes
                                                 int, MeshUpdateStage<float> &);
 template int update_mesh_vertices_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, int, bool, bool,
                                                  int, MeshUpdateStage<double> &);
+
+// ---- take_hip_scene_update_meshes on a two-level scene
+template <class R>
+int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
+                                   const double *d_xforms, int max_leaf, ProtoUpdateStage<R> &out) {
+    using namespace lbvh;
+    const HostScene<R> &h = sc.host;
+    const int n_inst = (int)sc.inst_trace.n, n_protos = (int)h.blas_prim_first.size();
+    const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims);
+    const int leaf_size = device_leaf_size(max_leaf);
+    const bool use_q = sc.trace.nodes == NodeFormat::Q4;
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    BuildMemory mem(sizeof(R) == 4 ? "f32 (meshes updated)" : "f64 (meshes updated)");
+    SceneT<R> &b = out.built;
+    if ((int)h.blas_mesh.size() != n_protos || (int)h.blas_node_first.size() != n_protos || (int)h.blas_node_count.size() != n_protos ||
+        (int)h.blas_depths.size() != n_protos || (int)h.placements.inst_proto.size() != n_inst || n_shapes < 0)
+        return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
+    std::vector<char> moved(n_protos, 0);
+    for (int k = 0; k < n_protos; k++) {
+        const int32_t mesh = h.blas_mesh[k];
+        if (mesh < 0 || (size_t)mesh >= in.pos.size() || (size_t)mesh >= h.meshes.size()) return fail(TAKE_E_INVALID, "unsupported: the scene does not know the mesh of prototype " + std::to_string(k));
+        moved[k] = in.pos[mesh] != nullptr;
+        if (moved[k] && (h.blas_prim_count[k] + leaf_size - 1) / leaf_size < 2) return unsupported(TAKE_OK, BuildVerdict::TooFewLeaves, "prototype tree");
+    }
+
+    // 1. the records: the shapes' back in shape order with new geometry where their mesh moved (k_update_prims: the
+    // order a fresh build starts from, and the one k_update_lights reads), the moved prototypes' in face order.  A
+    // coordinate that is not finite, in either role, is reported before anything else is made.
+    DevBuf<PrimRec<R>> shapes;              // shape order
+    std::vector<DevBuf<PrimRec<R>>> faces(n_protos);  // face order, moved prototypes only
+    {
+        FirstOffender<unsigned long long> bad{~0ull};
+        HIP_TRY(shapes.alloc((size_t)n_shapes));
+        HIP_TRY(bad.arm());
+        if (n_shapes > 0)
+            hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n_shapes), blk, 0, stream, sc.prims.p, n_shapes, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p,
+                               shapes.p, bad.cell.p);
+        for (int k = 0; k < n_protos; k++) {
+            if (!moved[k]) continue;
+            const int32_t mesh = h.blas_mesh[k];
+            const MeshInfo &mi = h.meshes[mesh];
+            const int nf = (int)h.blas_prim_count[k];
+            const MeshSrc src{0, mi.fbase, mi.material, h.materials[mi.material].tag, (mi.nbase >= 0 || mi.uvbase >= 0) ? 1 : 0};
+            HIP_TRY(faces[k].alloc((size_t)nf));
+            hipLaunchKernelGGL(k_update_proto_prims<R>, blocks_for(nf), blk, 0, stream, src, mesh, in.pos[mesh], sc.face_idx.p, nf, faces[k].p, bad.cell.p);
+        }
+        HIP_TRY(bad.read());
+        HIP_TRY(hipGetLastError());
+        if (bad.first != bad.none)
+            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
+    }
+
+    // 2. new vertex normals, 3. light records and power tables
+    const int rl = stage_normals_and_lights(sc, in, mesh_vertices, d_shape_face, shapes.p, n_shapes, b, out.new_normals, out.new_lights);
+    if (rl) return rl;
+
+    // 4. the prototypes: a moved one gets the pass of build_two_level_device's step 1 — boxes, tree, records into leaf
+    // order at its place in the new record array, its float nodes cut to size for step 6; an untouched one's records are copied
+    HIP_TRY(b.prims.alloc(sc.prims.n));
+    DevBuf<int> scene_ord;
+    HIP_TRY(scene_ord.alloc(6));
+    std::vector<DeviceTree> trees(n_protos);
+    out.depths = h.blas_depths, out.node_count = h.blas_node_count, out.node_first.assign(n_protos, 0);
+    for (int k = 0; k < n_protos; k++) {
+        const int nf = (int)h.blas_prim_count[k];
+        PrimRec<R> *at = b.prims.p + h.blas_prim_first[k];
+        if (!moved[k]) {
+            HIP_TRY(hipMemcpyAsync(at, sc.prims.p + h.blas_prim_first[k], (size_t)nf * sizeof(PrimRec<R>), hipMemcpyDeviceToDevice, stream));
+            continue;
+        }
+        DevBuf<Box> pb;
+        HIP_TRY(pb.alloc(nf));
+        HIP_TRY(reset_bounds(scene_ord));
+        span_boxes(faces[k].p, nf, pb.p, scene_ord);
+        DeviceTree &t = trees[k];
+        BuildVerdict why = BuildVerdict::Built;
+        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t, why);
+        if (rt || why != BuildVerdict::Built) return unsupported(rt, why, "prototype tree");
+        hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), blk, 0, stream, faces[k].p, t.order.p, nf, at);
+        DevBuf<Node4<float>> cut;
+        HIP_TRY(cut.alloc((size_t)t.n_nodes));
+        HIP_TRY(hipMemcpy(cut.p, t.nodes.p, cut.bytes(), hipMemcpyDeviceToDevice));
+        t.nodes = std::move(cut);
+        t.order.release(), faces[k].release();
+        out.depths[k] = t.depth, out.node_count[k] = t.n_nodes;
+    }
+    out.blas_depth = 0;
+    for (int k = 0; k < n_protos; k++) out.blas_depth = std::max(out.blas_depth, out.depths[k]);
+    mem.sample("prototypes");
+
+    // 5. the top level under the scene's current transforms: the shapes' boxes from their new records, the placements'
+    // from the prototypes' records as they are now; the shapes' records into leaf order at the head of the new array
+    DeviceTree top;
+    const int rt = top_level_resident(h, shapes.p, b.prims.p, n_shapes, d_xforms, n_inst, out.blas_depth, mem, top, b.prims);
+    if (rt) return rt;
+    shapes.release();
+    out.depth = top.depth + out.blas_depth;
+
+    // 6. assembly in the scene's node format: [new top level][prototype 0][prototype 1]...  A moved prototype's tree is
+    // quantised on its own grid (or widened) into place and rebased; untouched ones are copied and rebased by their own
+    // node shift, primitive shift 0 — a run of untouched neighbours shares its shift: one copy, one launch
+    out.n_nodes = top.n_nodes;
+    for (int k = 0; k < n_protos; k++) out.node_first[k] = out.n_nodes, out.n_nodes += out.node_count[k];
+    out.blas_nodes = out.n_nodes - top.n_nodes;
+    if (out.n_nodes >= ((int64_t)1 << 31) || (uint64_t)out.n_nodes * node_bytes<R>(sc.trace.nodes) >= (1ull << 32))
+        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
+    std::vector<ProtoTarget> target(n_protos, ProtoTarget{});
+    DevBuf<double> acc;
+    if (use_q) {
+        QGrid g;
+        double inflation = 1.0;
+        HIP_TRY(b.qnodes.alloc((size_t)out.n_nodes));
+        HIP_TRY(acc.alloc(2));
+        const int rq = quantise_tree_device(top, b.qnodes.p, acc, g, inflation);
+        if (rq) return rq;
+        for (int a = 0; a < 3; a++) out.grid_lo[a] = g.lo[a], out.grid_step[a] = g.step[a];
+    } else {
+        for (int a = 0; a < 3; a++) out.grid_lo[a] = h.grid_lo[a], out.grid_step[a] = h.grid_step[a];  // (not read by the traversal)
+        HIP_TRY(b.nodes.alloc((size_t)out.n_nodes));
+        const int rw = wide_nodes_device(top, b.nodes.p);
+        if (rw) return rw;
+    }
+    for (int k = 0; k < n_protos;) {
+        const int32_t first = (int32_t)out.node_first[k];
+        if (moved[k]) {
+            const int nk = (int)trees[k].n_nodes;
+            target[k].moved = 1, target[k].root = first, target[k].has_grid = use_q;
+            if (use_q) {
+                QGrid g;
+                double inflation = 1.0;  // (not consulted: the scene keeps its format, and the box tests stay conservative)
+                const int rq = quantise_tree_device(trees[k], b.qnodes.p + first, acc, g, inflation);
+                if (rq) return rq;
+                for (int a = 0; a < 3; a++) target[k].grid_lo[a] = g.lo[a], target[k].grid_step[a] = g.step[a];
+                hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(nk), blk, 0, stream, b.qnodes.p + first, nk, first, (int32_t)h.blas_prim_first[k]);
+            } else {
+                const int rw = wide_nodes_device(trees[k], b.nodes.p + first);
+                if (rw) return rw;
+                hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(nk), blk, 0, stream, b.nodes.p + first, nk, first, (int32_t)h.blas_prim_first[k]);
+            }
+            trees[k].nodes.release();
+            k++;
+            continue;
+        }
+        int e = k;
+        int64_t run = 0;
+        while (e < n_protos && !moved[e]) run += h.blas_node_count[e], e++;
+        const int64_t old_first = h.blas_node_first[k], shift = (int64_t)first - old_first;
+        for (int j = k; j < e; j++) target[j].shift = (int32_t)shift;
+        if (run > 0) {
+            if (old_first < 0 || old_first + run > h.stats.n_nodes) return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
+            if (use_q) {
+                HIP_TRY(hipMemcpyAsync(b.qnodes.p + first, sc.qnodes.p + old_first, (size_t)run * sizeof(QNode4), hipMemcpyDeviceToDevice, stream));
+                if (shift) hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(run), blk, 0, stream, b.qnodes.p + first, (int)run, (int32_t)shift, 0);
+            } else {
+                HIP_TRY(hipMemcpyAsync(b.nodes.p + first, sc.nodes.p + old_first, (size_t)run * sizeof(Node4<R>), hipMemcpyDeviceToDevice, stream));
+                if (shift) hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(run), blk, 0, stream, b.nodes.p + first, (int)run, (int32_t)shift, 0);
+            }
+        }
+        k = e;
+    }
+
+    // 7. the placements: records as they are — transforms, materials, tags, shape bases — with the roots, and the
+    // moved prototypes' grids, of the new node array
+    {
+        DevBuf<int32_t> inst_proto;
+        DevBuf<ProtoTarget> d_target;
+        HIP_TRY(b.inst_trace.alloc((size_t)n_inst));
+        HIP_TRY(hipMemcpyAsync(b.inst_trace.p, sc.inst_trace.p, sc.inst_trace.bytes(), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(inst_proto.upload(h.placements.inst_proto));
+        HIP_TRY(d_target.upload(target));
+        hipLaunchKernelGGL(k_retarget_placements<R>, blocks_for(n_inst), blk, 0, stream, b.inst_trace.p, n_inst, inst_proto.p, d_target.p);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+    }
+    mem.report();
+    return TAKE_OK;
+}
+template <class R> int ProtoUpdateStage<R>::commit(SceneT<R> &sc) {
+    HostScene<R> &h = sc.host;
+    if (new_normals) sc.normals = std::move(built.normals);
+    sc.prims = std::move(built.prims);
+    if (built.qnodes.p) sc.qnodes = std::move(built.qnodes);
+    else sc.nodes = std::move(built.nodes);
+    sc.inst_trace = std::move(built.inst_trace);
+    if (new_lights) {
+        sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
+        h.lights = std::move(built.host.lights), h.light_pmf = std::move(built.host.light_pmf), h.light_cdf = std::move(built.host.light_cdf);
+    }
+    h.blas_node_first = std::move(node_first), h.blas_node_count = std::move(node_count), h.blas_depths = std::move(depths);
+    h.blas_nodes = blas_nodes, h.blas_depth = blas_depth;
+    install_tree(sc, n_nodes, depth, 0, grid_lo, grid_step);  // (the new top-level tree has at least two leaves: its root is node 0)
+    return TAKE_OK;
+}
+template struct ProtoUpdateStage<float>;
+template struct ProtoUpdateStage<double>;
+template int update_two_level_meshes_device<float>(const SceneT<float> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, const double *, int,
+                                                   ProtoUpdateStage<float> &);
+template int update_two_level_meshes_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, const double *, int,
+                                                    ProtoUpdateStage<double> &);
 
 }  // namespace tk_host

@@ -30,6 +30,9 @@
 // Moving the vertices of meshes of a resident scene (take_hip_scene_set_mesh_vertices) adds
 //   k_update_prims     the resident records back into shape order, updated meshes' triangles with new geometry words
 //   k_convert_normals / k_update_lights   new vertex normals as R; the records of area lights on updated faces
+// Moving the vertices of prototype meshes of a resident two-level scene (take_hip_scene_update_meshes) adds
+//   k_update_proto_prims     a moved prototype's object-space records from its new positions, with the finiteness check
+//   k_retarget_placements    the placements' roots (every prototype's nodes may move) and the moved prototypes' grids
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
@@ -752,6 +755,59 @@ k_update_lights(LightRec<R> *lights, int n_lights, const PrimRec<R> *__restrict_
             l.v[3 * k + a] = (R)pos[3 * (int64_t)idx[k] + a];
             if (nrm) l.n[3 * k + a] = (R)nrm[3 * (int64_t)idx[k] + a];
         }
+}
+
+
+// ---- moving the vertices of meshes of a RESIDENT two-level scene (tk_build.hip: update_two_level_meshes_device): the
+// shapes' records are k_update_prims', the normals and lights as above; a prototype whose mesh moved gets new records
+// and a new tree, and every prototype's nodes a new place behind the new top-level tree.
+
+// k_make_proto_prims for a prototype whose vertices moved: one face per lane, the positions read from the update's own
+// array (positions: the mesh's vertex 0 first, m.pos_off = 0), the indices from the resident face_idx.  A coordinate
+// that is not finite as R leaves the smallest mesh << 32 | vertex in *bad (all ones before) and the lane writes nothing.
+// Per record: 12 bytes of indices, up to 72 of gathered double vertices, 64 (f32) / 96 (f64) written.
+template <class R>
+__global__ void __launch_bounds__(BLK)
+k_update_proto_prims(MeshSrc m, int32_t mesh_id, const double *__restrict__ positions, const int32_t *__restrict__ face_idx, int n_faces, PrimRec<R> *out,
+                     unsigned long long *bad) {
+    const int f = blockIdx.x * BLK + threadIdx.x;
+    if (f >= n_faces) return;
+    const int32_t *idx = face_idx + 3 * ((int64_t)m.fbase + f);
+    bool finite = true;
+    for (int k = 0; k < 3; k++)
+        for (int a = 0; a < 3; a++)
+            if (!__builtin_isfinite((R)positions[3 * (int64_t)idx[k] + a])) {
+                finite = false;
+                atomicMin(bad, ((unsigned long long)(uint32_t)mesh_id << 32) | (uint32_t)idx[k]);
+            }
+    if (!finite) return;
+    PrimRec<R> p{};
+    p.shape_id = f;
+    p.area_light = -1;
+    p.nidx = -1;
+    triangle_into(p, m, mesh_id, f, positions, face_idx);
+    out[f] = p;
+}
+// Where the placements of prototype k enter after an update: the root of a moved prototype (node 0 of its new tree) and,
+// in a scene of compressed nodes, its new grid; an untouched prototype's nodes moved by `shift` nodes, and its root with
+// them — unless the root is a leaf word (a one-leaf prototype of a host-built scene), which names records: they stay.
+struct ProtoTarget {
+    int32_t shift, moved, root, has_grid;
+    float grid_lo[3], grid_step[3];
+};
+template <class R>
+__global__ void __launch_bounds__(BLK)
+k_retarget_placements(InstTrace<R> *trace, int n, const int32_t *__restrict__ inst_proto, const ProtoTarget *__restrict__ protos) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    const ProtoTarget t = protos[inst_proto[i]];
+    if (t.moved) {
+        trace[i].root_child = t.root;
+        if (t.has_grid)
+            for (int a = 0; a < 3; a++) trace[i].grid_lo[a] = t.grid_lo[a], trace[i].grid_step[a] = t.grid_step[a];
+    } else if (trace[i].root_child >= 0) {
+        trace[i].root_child += t.shift;
+    }
 }
 
 }  // namespace lbvh

@@ -321,19 +321,25 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
         DeviceBuildInputs inputs;
         if (!rc) rc = for_each_side(ts.get(), [&](auto &sc) { return upload_scene(sc, ts->num_cus, local, o, threads, device_builder, staged, inputs); });
         if (!rc) rc = on_primary(ts.get(), [](auto &, auto &work) -> int { HIP_TRY(work.create()); return TAKE_OK; });  // queue words, counters
-        // what take_hip_scene_set_mesh_vertices will need: the meshes' vertex counts, and for a scene without placements
-        // the shape_face array in device memory — the device builder's upload, or one made here
+        // what take_hip_scene_set_mesh_vertices / _update_meshes will need: the meshes' vertex counts, the shape_face
+        // array in device memory — the device builder's upload, or one made here — and, of a two-level scene, the
+        // placements' transforms in double
         if (!rc) {
             ts->mesh_vertices.resize((size_t)desc->n_meshes);
             for (int i = 0; i < desc->n_meshes; i++) ts->mesh_vertices[i] = desc->meshes[i].n_vertices;
             ts->max_leaf = requested_max_leaf(o), ts->flattened = flat.meshes.size() > 0, ts->node_knob = tree_knobs().nodes;
-            if (local.n_instances == 0 && !ts->flattened && local.n_shapes > 0) {
+            if (!ts->flattened && local.n_shapes > 0) {
                 if (inputs.face.p) {
                     ts->shape_face = std::move(inputs.face);
                 } else if (ts->shape_face.alloc((size_t)local.n_shapes) != hipSuccess ||
                            hipMemcpy(ts->shape_face.p, local.shape_face, ts->shape_face.bytes(), hipMemcpyHostToDevice) != hipSuccess) {
                     rc = fail(TAKE_E_NOMEM, "out of device memory for the shape_face array");
                 }
+            }
+            if (!rc && local.n_instances > 0) {
+                std::vector<double> xf(12 * (size_t)local.n_instances);
+                for (int64_t i = 0; i < local.n_instances; i++) std::memcpy(&xf[12 * (size_t)i], local.instances[i].xform, 12 * sizeof(double));
+                if (ts->xforms.upload(xf) != hipSuccess) rc = fail(TAKE_E_NOMEM, "out of device memory for the placements' transforms");
             }
         }
     } catch (const std::bad_alloc &) {

@@ -53,6 +53,12 @@ template <class R> struct HostScene {
     // repose_two_level_device): per prototype its records in the scene's array, and the depth of the deepest tree
     std::vector<int64_t> blas_prim_first, blas_prim_count;
     int blas_depth = 0;
+    // ... and what moving a prototype's vertices needs on top (update_two_level_meshes_device): per prototype its mesh,
+    // its nodes in the scene's node array (none: a host-built tree of one leaf, entered through a leaf word) and its
+    // depth.  Filled by both builders; every commit that moves nodes keeps them current.
+    std::vector<int32_t> blas_mesh;
+    std::vector<int64_t> blas_node_first, blas_node_count;
+    std::vector<int> blas_depths;
     PlacementPlan placements;  // PREP_DEVICE_BUILD of a two-level scene: what the device builder is to build; inst_proto is kept by both builders
     EnvMap<R> env{-1, 0, 0, 1, 1, 0, 0, {R(0), R(0), R(0)}, nullptr, nullptr, nullptr, nullptr};  // pointers: view() / the uploader
     std::vector<R> env_marginal, env_conditional;
@@ -264,6 +270,7 @@ template <class R, int W> struct Prototype {
     std::vector<PrimRec<R>> prims;
     Bounds box;  // object space
     int depth = 0;
+    int mesh = -1;  // the mesh it was built from
     size_t node_base = 0, prim_base = 0;  // where nodes / prims start in the scene's arrays (append_prototypes)
     // "re-braiding" (Benthin et al. 2017): the entries a placement contributes to the top-level build — subtrees
     // of the prototype's tree (child word local to this tree + object-space box), the root opened largest box
@@ -278,6 +285,7 @@ template <class R, int W> struct Prototype {
     // records in leaf order, the tree, the object box, the entries
     void build(const TakeSceneDesc &d, const HostScene<R> &hs, int mesh_id, int leaf_size, int threads, int braid) {
         const int64_t nf = d.meshes[mesh_id].n_faces;
+        mesh = mesh_id;
         std::vector<PrimRec<R>> recs(nf);
         std::vector<BuildPrim> bp(nf);
         for (int64_t f = 0; f < nf; f++) {
@@ -450,6 +458,11 @@ std::string append_prototypes(std::vector<Prototype<R, W>> &protos, const std::v
     hs.blas_depth = max_depth;
     hs.blas_prim_first.clear(), hs.blas_prim_count.clear();
     for (const Prototype<R, W> &b : protos) hs.blas_prim_first.push_back((int64_t)b.prim_base), hs.blas_prim_count.push_back((int64_t)b.prims.size());
+    hs.blas_mesh.clear(), hs.blas_node_first.clear(), hs.blas_node_count.clear(), hs.blas_depths.clear();
+    for (const Prototype<R, W> &b : protos) {
+        hs.blas_mesh.push_back(b.mesh), hs.blas_depths.push_back(b.depth);
+        hs.blas_node_first.push_back((int64_t)b.node_base), hs.blas_node_count.push_back((int64_t)b.nodes.size());
+    }
     hs.placements.inst_proto.assign(inst_proto.begin(), inst_proto.end());  // (per top-level entry: per placement unless braided)
     hs.stats.n_nodes = (int64_t)nodes.size();
     hs.stats.depth += max_depth;  // the traversal stack holds both levels (+ one return marker)

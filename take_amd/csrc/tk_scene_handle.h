@@ -166,7 +166,11 @@ struct TakeScene {
     // what take_hip_scene_set_mesh_vertices needs to know of the description the scene was created from (a replica of
     // a scene group knows none of it: groups take no updates)
     std::vector<int64_t> mesh_vertices;   // per mesh: its vertex count
-    tk_host::DevBuf<int32_t> shape_face;  // TakeSceneDesc.shape_face in device memory (scenes without placements), shared by both sides
+    tk_host::DevBuf<int32_t> shape_face;  // TakeSceneDesc.shape_face in device memory (not of a flattened scene), shared by both sides
+    // the placements' CURRENT transforms, 12 doubles each, in device memory (two-level scenes; one copy, shared by the
+    // sides): written at creation and by every successful take_hip_scene_set_instance_transforms[_device].  Nothing
+    // else holds them in double — take_hip_scene_update_meshes rebuilds the top level under them.
+    tk_host::DevBuf<double> xforms;
     int max_leaf = 0;                     // the leaf size request the trees were built with (TakeBuildOpts / TAKE_HIP_MAX_LEAF)
     bool flattened = false;               // TAKE_INSTANCES_FLATTEN expanded placements: the meshes are no longer the caller's
     std::string node_knob;                // TAKE_HIP_NODES when the scene was built
@@ -199,7 +203,7 @@ template <class TS, class F, class... S> int for_each_side(TS *ts, F &&f, S *...
     const int rc = has_side(ts, TAKE_PRECISION_F64) ? f(ts->d, more->d...) : TAKE_OK;
     return rc || !has_side(ts, TAKE_PRECISION_F32) ? rc : f(ts->f, more->f...);
 }
-// A change of a resident scene (Stage = ReposeStage, MeshUpdateStage): stage_side(sc, its stage) builds every side aside and leaves
+// A change of a resident scene (Stage = ReposeStage, MeshUpdateStage, ProtoUpdateStage): stage_side(sc, its stage) builds every side aside and leaves
 // sc as it is; only when all succeeded commit() puts them in — a mixed scene gets both sides or neither — and a progressive sequence restarts.
 template <template <class> class Stage, class F> int stage_then_commit(TakeScene *ts, F &&stage_side) {
     struct { Stage<double> d; Stage<float> f; } stages;  // (sides named as the scene's: for_each_side pairs them)
@@ -272,7 +276,7 @@ struct DeviceBuildInputs {
     const int32_t *face_idx = nullptr;    // the validated face indices on the device: the array of the side that uploaded them
     bool ready = false;
     int upload(const TakeSceneDesc &d, const double *const *device_positions);  // (a no-op for the second side)
-    // (`face` stays: a scene without placements keeps it resident for take_hip_scene_set_mesh_vertices, 4 bytes per shape)
+    // (`face` stays: a scene keeps it resident for take_hip_scene_set_mesh_vertices / _update_meshes, 4 bytes per shape)
     void release() { pos.release(), kind.release(), ref.release(), area_light.release(); }
 };
 // Records and trees of one side of a new scene, made on the device (the LBVH builder, tk_build_gpu.h).  In: sc.host as
@@ -335,5 +339,27 @@ template <class R> struct MeshUpdateStage {
 template <class R>
 int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
                                 int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out);
+
+// New vertex positions (and vertex normals) for meshes of a resident TWO-LEVEL scene (take_hip_scene_update_meshes):
+// the shapes' records rewritten (k_update_prims), the records and tree of every prototype whose mesh is named made again
+// (k_update_proto_prims, build_tree_device with the scene's leaf size request, the scene's node format on the tree's
+// own grid), the other prototypes' records and nodes copied, the top level rebuilt under d_xforms — the scene's current
+// transforms — by the resident path the re-pose takes, and the placements retargeted (k_retarget_placements).  The
+// scene keeps its node format.  Built into `out` (stage_then_commit); commit() only moves.  Errors: as
+// update_mesh_vertices_device, the trees being the moved prototypes' and the top-level one, the depth both levels'.
+template <class R> struct ProtoUpdateStage {
+    // built.prims (all records), qnodes or nodes, inst_trace, normals / lights and their tables when they change
+    SceneT<R> built;
+    bool new_lights = false, new_normals = false;
+    float grid_lo[3] = {0, 0, 0}, grid_step[3] = {1, 1, 1};  // the new top-level tree's grid (compressed nodes)
+    int64_t n_nodes = 0, blas_nodes = 0;
+    int depth = 0, blas_depth = 0;
+    std::vector<int64_t> node_first, node_count;  // per prototype, as HostScene::blas_node_first / _count
+    std::vector<int> depths;
+    int commit(SceneT<R> &sc);  // moves only: always TAKE_OK
+};
+template <class R>
+int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
+                                   const double *d_xforms, int max_leaf, ProtoUpdateStage<R> &out);
 
 }  // namespace tk_host
