@@ -486,6 +486,56 @@ int take_hip_render_features_device(TakeScene *scene, const TakeRenderOpts *opts
 /* host_out: pointers to host memory */
 int take_hip_render_features(TakeScene *scene, const TakeRenderOpts *opts, const TakeFeatureBuffers *host_out);
 
+/* ---- image-space denoiser (new symbols of ABI version 5; no struct changed): the edge-avoiding A-trous wavelet filter
+ * of Dammertz et al. 2010 on the device, guided by the first-hit feature buffers.  EXTENSION without an upstream
+ * counterpart — parity unpinned with respect to the reference; specified against its own f64 restatement
+ * (tests/denoise_ref.py; DESIGN.md par. 4f has the arithmetic operation by operation).
+ * Planes as take_hip_render_device and take_hip_render_features_device leave them: rgb height * width * 3 Real, row 0 =
+ * top; guides (each optional): albedo and normal height * width * 3, depth height * width; Real = float or double by
+ * `precision`; out height * width * 3 Real, and may be rgb itself (no other aliasing).
+ * With an albedo (and without TAKE_DENOISE_KEEP_ALBEDO) the image is demodulated first — divided per channel by
+ * max(albedo, albedo_floor) — and multiplied back at the end, so that texture detail is not filtered, only illumination.
+ * Then `iterations` levels i = 0.., each a 5 x 5 B3-spline kernel (3/8, 1/4, 1/16) with holes of 2^i pixels, taps
+ * outside the image skipped, every tap weighted by exp(-(|dc|^2 * 4^i / sigma_color^2 + |dn|^2 / sigma_normal^2 +
+ * (dD / max(|D(p)|, |D(q)|))^2 / sigma_depth^2)): the colour sigma halves every level, the depth distance is relative
+ * and symmetric (two misses, both at depth 0, are at distance 0).  exp is the library's exp / expf.  Deterministic:
+ * the same planes give the same bits.  Non-finite inputs are taken as they are: a NaN or an infinity spreads through
+ * every pixel whose footprint holds it.
+ * The defaults are starting values: they have not been tuned on any image beyond the one condition the tests hold them
+ * to (a 4-spp Cornell box gets closer to its 1024-spp render). */
+#define TAKE_DENOISE_KEEP_ALBEDO 1 /* do not demodulate: filter rgb as it is even when an albedo is given */
+typedef struct TakeDenoiseOpts {
+    int32_t iterations;            /* 1..8; <= 0: 5 */
+    int32_t flags;                 /* 0 or TAKE_DENOISE_KEEP_ALBEDO */
+    double sigma_color;            /* <= 0: 1.0  */
+    double sigma_normal;           /* <= 0: 0.3  */
+    double sigma_depth;            /* <= 0: 0.05 */
+    double albedo_floor;           /* <= 0: 1e-3 */
+} TakeDenoiseOpts;
+/* Needs no scene (as take_hip_pack_exr_scanlines does not): also for the output of take_hip_render_accumulate or of a
+ * scene group.  d_rgb, d_out and the guides' pointers are device memory of the current device; d_guides: NULL = no
+ * guides, otherwise its albedo / normal / depth are read (each may be NULL) and the rest ignored; opts: NULL =
+ * defaults.  The two working images are allocated per call.  Enqueued on `stream`, returns after it has completed.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL d_rgb / d_out ("null argument"), width or height <= 0,
+ * an unknown precision (MIXED is a scene's, not a plane's: its planes are F64), iterations > 8, an unknown flag bit, a
+ * sigma or floor that is not finite. */
+int take_hip_denoise_device(const void *d_rgb, const TakeFeatureBuffers *d_guides, int32_t precision, int32_t width,
+                            int32_t height, const TakeDenoiseOpts *opts, void *d_out, void *stream);
+/* the same with host pointers (upload, the same kernels, download) */
+int take_hip_denoise(const void *rgb, const TakeFeatureBuffers *guides, int32_t precision, int32_t width, int32_t height,
+                     const TakeDenoiseOpts *opts, void *out);
+/* Render the whole image (strip_first / strip_stride are ignored, as in take_hip_render_exr_scanlines), make albedo,
+ * normal and depth with the same options, filter — all on the device, the planes and working images kept in the
+ * handle.  Specified as, and bit for bit equal to, take_hip_render_device + take_hip_render_features_device +
+ * take_hip_denoise_device made by hand: a progressive sequence ends as take_hip_render_device ends it, the counters are
+ * the feature pass's.  f32 scenes write float, f64 and MIXED scenes double.  Not for scene groups.
+ * TAKE_E_INVALID: a NULL scene, render options or output ("null argument"), and what take_hip_denoise_device refuses
+ * of the denoise options, before a device is looked for; then what the render refuses. */
+int take_hip_render_denoised_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeDenoiseOpts *denoise,
+                                    void *d_out, void *stream);
+int take_hip_render_denoised(TakeScene *scene, const TakeRenderOpts *opts, const TakeDenoiseOpts *denoise,
+                             void *rgb_out_host);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

@@ -31,6 +31,7 @@ EXPORTS = [
     "take_hip_scene_set_mesh_vertices", "take_hip_scene_update_meshes",
     "take_hip_render_features", "take_hip_render_features_device",
     "take_hip_debug_tree_info", "take_hip_debug_tree",
+    "take_hip_denoise", "take_hip_denoise_device", "take_hip_render_denoised", "take_hip_render_denoised_device",
 ]
 
 
@@ -78,7 +79,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -130,6 +131,57 @@ def compute_normals(positions, indices):
     out = np.zeros_like(pos)
     _check(lib().take_hip_compute_normals(pos.ctypes.data, pos.shape[0], idx.ctypes.data, idx.shape[0], out.ctypes.data))
     return out
+
+
+def _pointer(a):
+    """device pointer of a torch tensor, or the integer itself; None stays None"""
+    return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else int(a))
+
+
+def _denoise_opts(opts, kw):
+    """a TakeDenoiseOpts, keywords of cdefs.denoise_opts, or neither (None: the library's defaults, a NULL pointer)"""
+    if kw and opts is not None:
+        raise ValueError("give opts or keywords, not both")
+    return D.denoise_opts(**kw) if kw else opts
+
+
+def denoise(rgb, albedo=None, normal=None, depth=None, opts=None, **kw):
+    """the image-space denoiser on host arrays (take_hip_denoise: the edge-avoiding A-trous filter, include/take_hip.h):
+    rgb (H, W, 3) float32 or float64 — the dtype picks the precision —, the optional guides albedo and normal (H, W, 3)
+    and depth (H, W) in the same dtype -> the filtered (H, W, 3) image.  Options: keywords of cdefs.denoise_opts
+    (iterations, keep_albedo, sigma_color, sigma_normal, sigma_depth, albedo_floor), or opts = a TakeDenoiseOpts;
+    neither = the library's defaults (a NULL pointer)."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype not in (np.float32, np.float64) or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be a (H, W, 3) float32 or float64 array")
+    h, w = rgb.shape[:2]
+    rgb = np.ascontiguousarray(rgb)
+    bufs, keep = D.TakeFeatureBuffers(), []
+    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a)
+        if a.dtype != rgb.dtype or a.shape != shape:
+            raise ValueError(f"{name} must be a {shape} array of rgb's dtype")
+        keep.append(a)
+        setattr(bufs, name, a.ctypes.data)
+    opts = _denoise_opts(opts, kw)
+    out = np.zeros_like(rgb)
+    precision = D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64
+    _check(lib().take_hip_denoise(rgb.ctypes.data, C.byref(bufs) if keep else None, precision, w, h,
+                                  None if opts is None else C.byref(opts), out.ctypes.data))
+    return out
+
+
+def denoise_device(rgb, width, height, precision, out=None, albedo=None, normal=None, depth=None, opts=None, stream=None, **kw):
+    """the same on planes in device memory (take_hip_denoise_device): rgb, out and the guides are torch device tensors or
+    integer device pointers of `precision`'s Real (TAKE_PRECISION_F32 / _F64); out = None filters in place; blocks until
+    done.  Needs no scene: also for what render_accumulate or a scene group left on the device."""
+    bufs = D.TakeFeatureBuffers(_pointer(albedo), _pointer(normal), _pointer(depth), None, None, None)
+    opts = _denoise_opts(opts, kw)
+    _check(lib().take_hip_denoise_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), int(precision), int(width), int(height),
+                                         None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
+                                         C.c_void_p(stream or 0)))
 
 
 class DeviceMesh:
@@ -342,6 +394,27 @@ class Scene:
                 raise ValueError(f"unknown feature plane {name!r}: one of {tuple(D.FEATURE_PLANES)}")
             setattr(bufs, name, p.data_ptr() if hasattr(p, "data_ptr") else int(p))
         _check(lib().take_hip_render_features_device(self.h, C.byref(o), C.byref(bufs), C.c_void_p(stream or 0)))
+
+    def render_denoised(self, spp=None, max_depth=None, seed=0, ray_epsilon=0.0, samples_per_batch=0, integrator=0, opts=None, **kw):
+        """render the whole image, make albedo, normal and depth with the same options and filter, all on the device
+        (take_hip_render_denoised) -> (H, W, 3) host array.  Equal bit for bit to render + render_features + denoise made
+        by hand.  Denoise options: keywords of cdefs.denoise_opts, or opts = a TakeDenoiseOpts; neither = the defaults."""
+        spp = self.sd.spp if spp is None else spp
+        max_depth = self.sd.max_depth if max_depth is None else max_depth
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        opts = _denoise_opts(opts, kw)
+        out = np.zeros((self.sd.height, self.sd.width, 3), self.dtype)
+        _check(lib().take_hip_render_denoised(self.h, C.byref(o), None if opts is None else C.byref(opts), out.ctypes.data))
+        return out
+
+    def render_denoised_device(self, d_ptr, spp, max_depth, seed=0, ray_epsilon=0.0, samples_per_batch=0, stream=None, integrator=0,
+                               opts=None, **kw):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; H * W * 3 of the
+        scene's Real); blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        opts = _denoise_opts(opts, kw)
+        _check(lib().take_hip_render_denoised_device(self.h, C.byref(o), None if opts is None else C.byref(opts),
+                                                     C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
 
     def set_instance_transforms(self, xforms, stream=None):
         """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the

@@ -124,6 +124,33 @@ FEATURE_PROTOTYPES = {
 }
 
 
+class TakeDenoiseOpts(C.Structure):
+    """take_hip_denoise*: a field <= 0 takes its default (iterations 5, sigma_color 1.0, sigma_normal 0.3, sigma_depth
+    0.05, albedo_floor 1e-3)"""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double), ("albedo_floor", C.c_double)]
+
+
+TAKE_DENOISE_KEEP_ALBEDO = 1  # filter rgb as it is even when an albedo is given
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 1.0, "sigma_normal": 0.3, "sigma_depth": 0.05, "albedo_floor": 1e-3}
+
+# the image-space denoiser (include/take_hip.h): name -> argument types
+DENOISE_PROTOTYPES = {
+    "take_hip_denoise_device": [C.c_void_p, C.POINTER(TakeFeatureBuffers), C.c_int32, C.c_int32, C.c_int32,
+                                C.POINTER(TakeDenoiseOpts), C.c_void_p, C.c_void_p],
+    "take_hip_denoise": [C.c_void_p, C.POINTER(TakeFeatureBuffers), C.c_int32, C.c_int32, C.c_int32,
+                         C.POINTER(TakeDenoiseOpts), C.c_void_p],
+    "take_hip_render_denoised_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeDenoiseOpts), C.c_void_p, C.c_void_p],
+    "take_hip_render_denoised": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeDenoiseOpts), C.c_void_p],
+}
+
+
+def denoise_opts(iterations=0, keep_albedo=False, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, albedo_floor=0.0):
+    """-> TakeDenoiseOpts; what is left out takes the library's default"""
+    return TakeDenoiseOpts(int(iterations), TAKE_DENOISE_KEEP_ALBEDO if keep_albedo else 0, float(sigma_color), float(sigma_normal),
+                           float(sigma_depth), float(albedo_floor))
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

@@ -2,7 +2,8 @@
 // buffers, accumulation, statistics, the changes of a resident scene (new transforms, vertices, camera) and the test
 // hook that reads a resident tree back.  Launches no kernel: tracing and rendering is tk_render.hip, the device LBVH
 // build tk_build.hip, both reached through tk_scene_handle.h.  Scene creation is tk_create.hip, scene groups
-// tk_group.hip, the mesh entry points (PLY, serialized, OBJ, compute_normals) tk_mesh.hip; the shared plumbing is
+// tk_group.hip, the mesh entry points (PLY, serialized, OBJ, compute_normals) tk_mesh.hip, the image-space denoiser
+// tk_denoise.hip; the shared plumbing is
 // tk_host.h.  There is no CPU rendering path in this library: without a HIP device every entry point returns TAKE_E_NO_GPU.
 #include <hip/hip_runtime.h>
 

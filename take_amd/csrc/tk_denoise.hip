@@ -1,0 +1,162 @@
+// tk_denoise.hip — the C entry points of the image-space denoiser (include/take_hip.h: take_hip_denoise*,
+// take_hip_render_denoised*) and the only unit that compiles the kernels of tk_denoise.h.  The scene-free calls need no
+// scene (as take_hip_pack_exr_scanlines does not) and allocate their working images per call; the scene-bound ones
+// render, make the feature planes and filter on the device, with planes and working images in the handle's
+// RenderWorkspace — they are the three public calls made by hand, through the same functions.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <type_traits>
+
+#include "take_hip.h"
+#include "tk_scene_handle.h"
+#include "tk_denoise.h"
+
+using namespace tk;
+using namespace tk_host;
+
+namespace {
+// TakeDenoiseOpts with the defaults filled in
+struct DenoiseOpts {
+    int iterations = 5;
+    bool keep_albedo = false;
+    double sigma_color = 1.0, sigma_normal = 0.3, sigma_depth = 0.05, albedo_floor = 1e-3;
+};
+// what needs no device: TAKE_E_INVALID with a message, or TAKE_OK and the resolved options
+int resolve(const TakeDenoiseOpts *o, DenoiseOpts &r) {
+    r = DenoiseOpts{};
+    if (!o) return TAKE_OK;
+    if (o->iterations > dn::MAX_ITERATIONS) return fail(TAKE_E_INVALID, "iterations must be at most " + std::to_string(dn::MAX_ITERATIONS));
+    if (o->flags & ~TAKE_DENOISE_KEEP_ALBEDO) return fail(TAKE_E_INVALID, "unknown flag bits");
+    if (!std::isfinite(o->sigma_color) || !std::isfinite(o->sigma_normal) || !std::isfinite(o->sigma_depth) || !std::isfinite(o->albedo_floor))
+        return fail(TAKE_E_INVALID, "sigma_color, sigma_normal, sigma_depth and albedo_floor must be finite");
+    if (o->iterations > 0) r.iterations = o->iterations;
+    r.keep_albedo = (o->flags & TAKE_DENOISE_KEEP_ALBEDO) != 0;
+    if (o->sigma_color > 0) r.sigma_color = o->sigma_color;
+    if (o->sigma_normal > 0) r.sigma_normal = o->sigma_normal;
+    if (o->sigma_depth > 0) r.sigma_depth = o->sigma_depth;
+    if (o->albedo_floor > 0) r.albedo_floor = o->albedo_floor;
+    return TAKE_OK;
+}
+int check_image(int32_t precision, int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return fail(TAKE_E_INVALID, "width and height must be positive");
+    if (precision != TAKE_PRECISION_F32 && precision != TAKE_PRECISION_F64) return fail(TAKE_E_INVALID, "unknown precision");
+    return TAKE_OK;
+}
+
+// Reals of working images per pixel: colour, colour, guide records
+constexpr int WORK_REALS = 12;
+
+// Prologue, the levels, the epilogue fused into the last: enqueued on `stream`, no synchronisation.  work: WORK_REALS *
+// width * height Reals, aligned for Rec4<R>.  out may be rgb (the prologue has read rgb before the last level writes).
+template <class R>
+int denoise_enqueue(const R *rgb, const R *albedo, const R *normal, const R *depth, int32_t width, int32_t height, const DenoiseOpts &o, R *work, R *out,
+                    hipStream_t stream) {
+    const int64_t npix = (int64_t)width * height;
+    dn::Params<R> P{};
+    P.width = width, P.height = height;
+    P.guides = (normal ? dn::HAS_NORMAL : 0) | (depth ? dn::HAS_DEPTH : 0) | (albedo && !o.keep_albedo ? dn::DEMODULATE : 0);
+    P.inv_n = (R)(1.0 / (o.sigma_normal * o.sigma_normal)), P.inv_d = (R)(1.0 / (o.sigma_depth * o.sigma_depth));
+    P.albedo_floor = (R)o.albedo_floor;
+    dn::Rec4<R> *colour[2] = {(dn::Rec4<R> *)work, (dn::Rec4<R> *)work + npix}, *guide = (dn::Rec4<R> *)work + 2 * npix;
+    const dim3 pack_grid((unsigned)std::min<int64_t>((npix + 255) / 256, 2048));
+    hipLaunchKernelGGL((dn::k_denoise_pack<R>), pack_grid, dim3(256), 0, stream, P, rgb, albedo, normal, depth, colour[0], guide);
+    const dim3 grid((unsigned)((width + dn::DN_BX - 1) / dn::DN_BX), (unsigned)std::min((height + dn::DN_BY - 1) / dn::DN_BY, 65535)), block(dn::DN_BX, dn::DN_BY);
+    for (int i = 0; i < o.iterations; i++) {
+        const R inv_c = (R)(std::ldexp(1.0, 2 * i) / (o.sigma_color * o.sigma_color));  // the colour sigma halves every level
+        if (i == o.iterations - 1)
+            hipLaunchKernelGGL((dn::k_denoise_level<R, true>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, inv_c, (dn::Rec4<R> *)nullptr, albedo, out);
+        else
+            hipLaunchKernelGGL((dn::k_denoise_level<R, false>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, inv_c, colour[(i + 1) & 1], albedo, (R *)nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return TAKE_OK;
+}
+int denoise_enqueue_any(int32_t precision, const void *rgb, const TakeFeatureBuffers *g, int32_t width, int32_t height, const DenoiseOpts &o, void *work,
+                        void *out, hipStream_t stream) {
+    const void *albedo = g ? g->albedo : nullptr, *normal = g ? g->normal : nullptr, *depth = g ? g->depth : nullptr;
+    if (precision == TAKE_PRECISION_F64)
+        return denoise_enqueue((const double *)rgb, (const double *)albedo, (const double *)normal, (const double *)depth, width, height, o, (double *)work, (double *)out, stream);
+    return denoise_enqueue((const float *)rgb, (const float *)albedo, (const float *)normal, (const float *)depth, width, height, o, (float *)work, (float *)out, stream);
+}
+}  // namespace
+
+extern "C" {
+
+int take_hip_denoise_device(const void *d_rgb, const TakeFeatureBuffers *d_guides, int32_t precision, int32_t width, int32_t height,
+                            const TakeDenoiseOpts *opts, void *d_out, void *stream) {
+    if (!d_rgb || !d_out) return fail(TAKE_E_INVALID, "null argument");
+    DenoiseOpts o;
+    if (int rc = check_image(precision, width, height)) return rc;
+    if (int rc = resolve(opts, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4;
+    DevBuf<char> work;
+    if (work.alloc((size_t)width * height * WORK_REALS * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's working images");
+    if (int rc = denoise_enqueue_any(precision, d_rgb, d_guides, width, height, o, work.p, d_out, (hipStream_t)stream)) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return TAKE_OK;
+}
+
+int take_hip_denoise(const void *rgb, const TakeFeatureBuffers *guides, int32_t precision, int32_t width, int32_t height, const TakeDenoiseOpts *opts,
+                     void *out) {
+    if (!rgb || !out) return fail(TAKE_E_INVALID, "null argument");
+    DenoiseOpts o;
+    if (int rc = check_image(precision, width, height)) return rc;
+    if (int rc = resolve(opts, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
+    // rgb (filtered in place), then the guides that were given: (host pointer, Reals per pixel)
+    const std::pair<const void *, size_t> planes[4] = {{rgb, 3}, {guides ? guides->albedo : nullptr, 3}, {guides ? guides->normal : nullptr, 3}, {guides ? guides->depth : nullptr, 1}};
+    DevBuf<char> d_plane[4];
+    for (int k = 0; k < 4; k++) {
+        if (!planes[k].first) continue;
+        if (d_plane[k].alloc(npix * planes[k].second * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
+        HIP_TRY(hipMemcpy(d_plane[k].p, planes[k].first, d_plane[k].bytes(), hipMemcpyHostToDevice));
+    }
+    const TakeFeatureBuffers d_guides{d_plane[1].p, d_plane[2].p, d_plane[3].p, nullptr, nullptr, nullptr};
+    if (int rc = take_hip_denoise_device(d_plane[0].p, &d_guides, precision, width, height, opts, d_plane[0].p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_plane[0].p, d_plane[0].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+int take_hip_render_denoised_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeDenoiseOpts *dopts, void *d_out, void *stream) {
+    if (!ts || !ropts || !d_out) return fail(TAKE_E_INVALID, "null argument");
+    DenoiseOpts o;
+    if (int rc = resolve(dopts, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    TakeRenderOpts ro = *ropts;
+    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_exr_scanlines
+    const int W = ts->width(), H = ts->height();
+    const int64_t npix = (int64_t)W * H;
+    return on_primary(ts, [&](auto &sc, auto &work) {
+        using R = std::remove_reference_t<decltype(*work.accum.p)>;
+        // the working images, then albedo, normal and depth
+        if (int rc = work.ensure_denoise((WORK_REALS + 7) * npix)) return rc;
+        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
+        if (int rc = render_scene(ts, ro, d_out, (hipStream_t)stream)) return rc;
+        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
+        if (int rc = render_features_scene(ts, ro, planes, (hipStream_t)stream)) return rc;
+        if (int rc = denoise_enqueue((const R *)d_out, (const R *)albedo, (const R *)normal, (const R *)depth, W, H, o, work.denoise.p, (R *)d_out, (hipStream_t)stream)) return rc;
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return (int)TAKE_OK;
+    });
+}
+
+int take_hip_render_denoised(TakeScene *ts, const TakeRenderOpts *ropts, const TakeDenoiseOpts *dopts, void *rgb_out_host) {
+    if (!ts || !ropts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
+    DenoiseOpts o;
+    if (int rc = resolve(dopts, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    DevBuf<char> d_out;
+    if (d_out.alloc((size_t)ts->width() * ts->height() * 3 * (ts->f64() ? 8 : 4)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoised image");
+    if (int rc = take_hip_render_denoised_device(ts, ropts, dopts, d_out.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+}  // extern "C"

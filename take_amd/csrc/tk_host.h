@@ -1,7 +1,7 @@
 // tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_create.hip and tk_group.hip (the C entry
-// points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks) and
-// tk_mesh.hip (mesh ingest): the error string, fault injection, pinned uploads, the owning device buffer.  (The scene
-// handle all but the last share is tk_scene_handle.h.)
+// points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
+// tk_mesh.hip (mesh ingest) and tk_denoise.hip (the image-space denoiser): the error string, fault injection, pinned
+// uploads, the owning device buffer.  (The scene handle all but tk_mesh.hip share is tk_scene_handle.h.)
 // Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
 // take_hip_last_error returns) and ONE TAKE_HIP_FAIL_ALLOC counter.
 #pragma once

@@ -141,6 +141,13 @@ template <class R> struct RenderWorkspace {
     DevBuf<int32_t> sort_hist, sort_base;  // [key][wave] counts and their exclusive scan
     DevBuf<R> accum, out;
     DevBuf<R> features;  // per-pixel sums of the feature pass (take_hip_render_features*): FEATURE_WORDS planes, its own — not accum
+    // take_hip_render_denoised*: the filter's working images and the three guide planes (tk_denoise.hip); grows on
+    // demand, is no per-slot buffer (release() leaves it, as it leaves accum, out and features) and goes with the handle
+    DevBuf<R> denoise;
+    int ensure_denoise(int64_t reals) {
+        if ((int64_t)denoise.n >= reals || denoise.alloc((size_t)reals) == hipSuccess) return TAKE_OK;
+        return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's workspace");
+    }
     DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
     DevBuf<unsigned long long> counters;
     int64_t capacity = 0;  // path slots allocated

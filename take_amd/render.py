@@ -64,18 +64,19 @@ def imwrite_pfm(path, img):
 
 
 def main(argv=None):
-    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features]` — the reference's main.cpp:9-27: render, then
-    imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo and shading
-    normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser reads
-    beside the image."""
+    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise]` — the reference's main.cpp:9-27:
+    render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
+    and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
+    reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
+    the default options (Scene.render_denoised); image.exr is the same bytes with or without it."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
     if "-t" in params:  # main.cpp:13-15: thread count of the CPU pool; meaningless here, accepted and dropped
         i = params.index("-t")
         del params[i:i + 2]
-    features = "-features" in params
-    params = [p for p in params if p != "-features"]
+    features, denoise = "-features" in params, "-denoise" in params
+    params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
         return 0  # an empty image is not written (src/image.cpp:136-138)
     # render + float -> half + scanline packing on the device (take_hip_render_exr_scanlines); what the host adds is
@@ -91,6 +92,8 @@ def main(argv=None):
             planes = scene.render_features(spp=sd.spp, seed=0, want=("albedo", "normal"))
             imwrite("albedo.exr", planes["albedo"])
             imwrite("normal.exr", planes["normal"])
+        if denoise:
+            imwrite("denoised.exr", scene.render_denoised(spp=sd.spp, max_depth=max_depth, seed=0))
     finally:
         scene.close()
     return 0
