@@ -536,6 +536,47 @@ int take_hip_render_denoised_device(TakeScene *scene, const TakeRenderOpts *opts
 int take_hip_render_denoised(TakeScene *scene, const TakeRenderOpts *opts, const TakeDenoiseOpts *denoise,
                              void *rgb_out_host);
 
+/* ---- adaptive sampling (new symbols of ABI version 5; no struct changed): a pixel stops receiving samples once the
+ * relative standard error of its mean is at or below a threshold.  EXTENSION without an upstream counterpart — parity
+ * unpinned with respect to the reference: the sample values are the pinned render's, only the stopping rule is this
+ * library's own (restated in tests/adaptive_ref.py; DESIGN.md par. 4g).
+ * opts->spp is the MAXIMUM per pixel.  Pass 0 gives every pixel the samples 0 .. min_spp - 1; pass i >= 1 gives every
+ * pixel still active the next min(step_spp, spp - n) samples; the active set only shrinks, so all active pixels have
+ * the same number n of samples.  Per pixel, in sample order and in double whatever the scene's precision:
+ *   L_s = ((double)r + (double)g) + (double)b of sample s — the values the image sums take (on MIXED scenes the
+ *   per-channel doubles f64 record + converted f32 record) —, m1 += L_s, m2 += L_s * L_s.
+ * After a pass, for a pixel with n samples (each + - * / sqrt one IEEE operation in this order):
+ *   mean = m1 / n;  v = m2 / n - mean * mean;  v = v > 0 ? v : 0;  err = sqrt(v / (n - 1)) / (fabs(mean) + floor)
+ * and the pixel stops iff (n >= 2 && err <= threshold) or n == spp.  A NaN err never satisfies <=: such a pixel runs
+ * to spp.  A stopped pixel never restarts.  rgb = the render's own sums * (1 / count), flipped as take_hip_render_device.
+ * Consequences: a pixel with count c equals take_hip_render(spp = c) there BIT FOR BIT; image, counts and moments do
+ * not depend on samples_per_batch, on the strip set (pixel lists are local to the rank's rows) or on the run.  Like
+ * every threshold rule the image is a biased estimate (pixels whose first samples happen to agree stop early): min_spp
+ * is the guard.
+ * MIXED, two-level and device-built scenes work; only the default integrator (0); not for scene groups.  Afterwards as
+ * after take_hip_render_device: a progressive sequence has ended (take_hip_accumulated_samples() == 0), and
+ * TakeCounters.samples is the sum of the counts.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL scene, opts or rgb ("null argument"), a threshold or
+ * floor that is not finite, an unknown flag bit; then integrators 1..3 and whatever a render refuses. */
+typedef struct TakeAdaptiveOpts {
+    int32_t min_spp;    /* samples every pixel gets before the first test; <= 0: 16; clamped to opts->spp */
+    int32_t step_spp;   /* samples added per later pass to every pixel still active; <= 0: 8 */
+    double threshold;   /* relative standard error of the mean at which a pixel stops; < 0: 0.05;
+                           0 is a value (only pixels with zero sample variance stop) */
+    double floor;       /* added to |mean| in the denominator; <= 0: 1e-3 */
+    int32_t flags, reserved; /* 0 */
+} TakeAdaptiveOpts;
+typedef struct TakeAdaptiveStats { /* every pointer may be NULL; n_rows * width planes, row 0 = top, as rgb */
+    int32_t *count;     /* samples the pixel received */
+    double *m1, *m2;    /* sum of L_s and of L_s * L_s over those samples, always double */
+} TakeAdaptiveStats;
+/* d_rgb_out and the planes of d_stats: device memory; enqueued on `stream`, returns after it has completed */
+int take_hip_render_adaptive_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive /* NULL = defaults */,
+                                    void *d_rgb_out, const TakeAdaptiveStats *d_stats /* NULL ok */, void *stream);
+/* the same with host pointers */
+int take_hip_render_adaptive(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive, void *rgb_out_host,
+                             const TakeAdaptiveStats *host_stats);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

@@ -32,6 +32,7 @@ EXPORTS = [
     "take_hip_render_features", "take_hip_render_features_device",
     "take_hip_debug_tree_info", "take_hip_debug_tree",
     "take_hip_denoise", "take_hip_denoise_device", "take_hip_render_denoised", "take_hip_render_denoised_device",
+    "take_hip_render_adaptive", "take_hip_render_adaptive_device",
 ]
 
 
@@ -79,7 +80,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -415,6 +416,44 @@ class Scene:
         opts = _denoise_opts(opts, kw)
         _check(lib().take_hip_render_denoised_device(self.h, C.byref(o), None if opts is None else C.byref(opts),
                                                      C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
+
+    def render_adaptive(self, spp=None, max_depth=None, seed=0, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, stats=False, opts="keywords",
+                        ray_epsilon=0.0, strip_first=0, strip_stride=1, samples_per_batch=0, integrator=0):
+        """adaptive sampling (take_hip_render_adaptive): at most `spp` samples per pixel, a pixel stops once the relative
+        standard error of its mean is <= threshold -> (rows, W, 3) host image of this strip set, top row first; a pixel
+        that received c samples equals render(spp=c) there bit for bit.  stats=True: -> (image, {"count": int32 (rows, W),
+        "m1", "m2": float64 (rows, W)}), the samples each pixel received and the sums of its sample values (r + g + b)
+        and of their squares.  What is left out of min_spp / step_spp / threshold / floor takes the library's default
+        (16, 8, 0.05, 1e-3; threshold 0 is a value); opts: a TakeAdaptiveOpts instead of the keywords, or None = a NULL
+        pointer (all defaults)."""
+        spp = self.sd.spp if spp is None else spp
+        max_depth = self.sd.max_depth if max_depth is None else max_depth
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(opts, str) else opts
+        n = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
+        out = np.zeros((n, self.sd.width, 3), self.dtype)
+        planes = {"count": np.zeros((n, self.sd.width), np.int32), "m1": np.zeros((n, self.sd.width), np.float64),
+                  "m2": np.zeros((n, self.sd.width), np.float64)} if stats else None
+        st = D.TakeAdaptiveStats(*[planes[k].ctypes.data for k in ("count", "m1", "m2")]) if stats else None
+        _check(lib().take_hip_render_adaptive(self.h, C.byref(o), None if a is None else C.byref(a), out.ctypes.data,
+                                              None if st is None else C.byref(st)))
+        return (out, planes) if stats else out
+
+    def render_adaptive_device(self, d_ptr, spp, max_depth, seed=0, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, stats=None, opts="keywords",
+                               ray_epsilon=0.0, strip_first=0, strip_stride=1, samples_per_batch=0, stream=None, integrator=0):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; rows * W * 3 of the
+        scene's Real); stats: {"count" / "m1" / "m2": device tensor or pointer} for the planes wanted (int32, float64,
+        float64; rows * W each); blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(opts, str) else opts
+        st = None
+        if stats:
+            unknown = set(stats) - {"count", "m1", "m2"}
+            if unknown:
+                raise ValueError(f"unknown statistics plane {sorted(unknown)[0]!r}: one of ('count', 'm1', 'm2')")
+            st = D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in ("count", "m1", "m2")])
+        _check(lib().take_hip_render_adaptive_device(self.h, C.byref(o), None if a is None else C.byref(a), C.c_void_p(_pointer(d_ptr)),
+                                                     None if st is None else C.byref(st), C.c_void_p(stream or 0)))
 
     def set_instance_transforms(self, xforms, stream=None):
         """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the

@@ -151,6 +151,33 @@ def denoise_opts(iterations=0, keep_albedo=False, sigma_color=0.0, sigma_normal=
                            float(sigma_depth), float(albedo_floor))
 
 
+class TakeAdaptiveOpts(C.Structure):
+    """take_hip_render_adaptive*: a field that is not positive takes its default (min_spp 16, step_spp 8, floor 1e-3);
+    threshold < 0 takes 0.05 and 0 is a value"""
+    _fields_ = [("min_spp", C.c_int32), ("step_spp", C.c_int32), ("threshold", C.c_double), ("floor", C.c_double),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TakeAdaptiveStats(C.Structure):
+    """take_hip_render_adaptive*: one pointer per plane (host or device memory), None = not wanted"""
+    _fields_ = [("count", C.c_void_p), ("m1", C.c_void_p), ("m2", C.c_void_p)]
+
+
+ADAPTIVE_DEFAULTS = {"min_spp": 16, "step_spp": 8, "threshold": 0.05, "floor": 1e-3}
+
+# adaptive sampling (include/take_hip.h): name -> argument types
+ADAPTIVE_PROTOTYPES = {
+    "take_hip_render_adaptive_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.c_void_p,
+                                        C.POINTER(TakeAdaptiveStats), C.c_void_p],
+    "take_hip_render_adaptive": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.c_void_p, C.POINTER(TakeAdaptiveStats)],
+}
+
+
+def adaptive_opts(min_spp=0, step_spp=0, threshold=-1.0, floor=0.0):
+    """-> TakeAdaptiveOpts; what is left out takes the library's default"""
+    return TakeAdaptiveOpts(int(min_spp), int(step_spp), float(threshold), float(floor), 0, 0)
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

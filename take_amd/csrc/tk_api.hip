@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <string>
 #include <vector>
@@ -54,6 +55,13 @@ template <class R> TakeDebugTreeInfo debug_tree_info(const SceneT<R> &sc) {
     o.n_nodes = sc.dev.n_nodes, o.n_prims = (int64_t)sc.prims.n, o.n_instances = (int64_t)sc.inst_trace.n;
     for (int a = 0; a < 3; a++) o.grid_lo[a] = sc.dev.grid_lo[a], o.grid_step[a] = sc.dev.grid_step[a];
     return o;
+}
+// what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device
+int check_adaptive_opts(const TakeAdaptiveOpts *a) {
+    if (!a) return TAKE_OK;
+    if (!std::isfinite(a->threshold) || !std::isfinite(a->floor)) return fail(TAKE_E_INVALID, "threshold and floor must be finite");
+    if (a->flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
+    return TAKE_OK;
 }
 template <class R> int debug_tree_copy(const SceneT<R> &sc, void *nodes, void *prims, void *inst_trace) {
     const TakeDebugTreeInfo o = debug_tree_info(sc);
@@ -184,6 +192,42 @@ int take_hip_render_features(TakeScene *ts, const TakeRenderOpts *opts, const Ta
     if (rc) return rc;
     for (int k = 0; k < 6; k++)
         if (d_ptr[k]) HIP_TRY(hipMemcpy(planes[k].first, d_ptr[k], d_plane[k].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+// Adaptive sampling (stop pixels whose error estimate is below a threshold): tk_render.hip, adaptive_impl.
+int take_hip_render_adaptive_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive, void *d_rgb_out,
+                                    const TakeAdaptiveStats *d_stats, void *stream) {
+    if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_adaptive_opts(adaptive)) return rc;
+    TAKE_ON_DEVICE(ts);
+    return render_adaptive_scene(ts, *opts, adaptive, d_rgb_out, d_stats ? *d_stats : TakeAdaptiveStats{nullptr, nullptr, nullptr}, (hipStream_t)stream);
+}
+int take_hip_render_adaptive(TakeScene *ts, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive, void *rgb_out_host,
+                             const TakeAdaptiveStats *host_stats) {
+    if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_adaptive_opts(adaptive)) return rc;
+    TAKE_ON_DEVICE(ts);
+    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
+    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
+    if (rows < 0) return rows;
+    const size_t npix = (size_t)rows * ts->width();
+    // the image and the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
+    const std::pair<void *, size_t> planes[4] = {{rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4)},
+                                                 {host_stats ? host_stats->count : nullptr, 4},
+                                                 {host_stats ? host_stats->m1 : nullptr, 8},
+                                                 {host_stats ? host_stats->m2 : nullptr, 8}};
+    DevBuf<char> d_plane[4];
+    for (int k = 0; k < 4; k++)
+        if (planes[k].first && npix > 0 && d_plane[k].alloc(npix * planes[k].second) != hipSuccess)
+            return fail(TAKE_E_NOMEM, "out of device memory for the adaptive render's planes");
+    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[1].p, (double *)d_plane[2].p, (double *)d_plane[3].p};
+    // (an empty strip set: the checks run, nothing is written)
+    const int rc = render_adaptive_scene(ts, *opts, adaptive, npix ? (void *)d_plane[0].p : rgb_out_host, d_stats, nullptr);
+    if (rc) return rc;
+    for (int k = 0; k < 4; k++)
+        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
 

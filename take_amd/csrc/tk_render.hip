@@ -1,7 +1,8 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace's allocations, the kernel launchers,
 // the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
-// after them) and the three calls that differ in between — the wavefront render loop, the feature pass, the trace hooks.
-// The only unit that compiles the kernels of tk_kernels.h and tk_features.h (as tk_build.hip is for tk_build_gpu.h);
+// after them) and the calls that differ in between — the wavefront render loop, its adaptive twin (passes over the
+// pixels still active), the feature pass, the trace hooks.
+// The only unit that compiles the kernels of tk_kernels.h, tk_features.h and tk_adaptive.h (as tk_build.hip is for tk_build_gpu.h);
 // what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "tk_scene_handle.h"
 #include "tk_kernels.h"
 #include "tk_features.h"
+#include "tk_adaptive.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -164,6 +166,7 @@ template <class R> struct Frame {
     bool counting = (ts->instrumentation & 2) != 0;
     bool sort_materials = false;
     int64_t dump = -1;  // TAKE_HIP_DUMP_SLOT (or -1)
+    bool listed_pass = false;  // an adaptive pass over listed pixels: k_generate_list made the camera rays (launch_closest)
     int first = 0, stride = 1, n_rows = 0;  // the strips first, first + stride, ... of the image and their rows (pick_strips)
     int64_t npix = 0;                       // the pixels of those rows
     int spb = 0;                            // samples per batch
@@ -196,7 +199,7 @@ hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const R
     hipError_t e;
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
     tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
-    if (k == 0 && camera_fused(sc.trace, rp.integrator, c.counting)) {
+    if (k == 0 && !c.listed_pass && camera_fused(sc.trace, rp.integrator, c.counting)) {
         // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
         CameraIo<RR> io_cam;
         static_cast<PathIo<RR> &>(io_cam) = io_ext;
@@ -472,46 +475,81 @@ template <class R> int64_t start_batch(Frame<R> &fr, int s0, int nb) {
     return n;
 }
 
-// first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
-// random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
-// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
-// (What is a render's own between the frame's steps: its checks, the sort scratch, the f32 side of a mixed-precision
-// render, the batch / round loop, accumulate and resolve.)
-template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
-                                   int64_t first_sample, bool keep_accum) {
-    if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
+// What a render refuses of its options before it looks at the strips
+template <class R> int check_render_opts(const SceneT<R> &sc, const TakeRenderOpts &o) {
     if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
     if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
     if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
     if (o.integrator != 0 && sc.host.env.light >= 0)
         return fail(TAKE_E_INVALID, "integrators 1..3 are the reference's own: they do not know the environment-map extension");
+    return TAKE_OK;
+}
+// What the batches of a render share beyond the frame (a render's own set-up after begin_frame: the material sort with
+// its scratch, the dump slot, the f32 side of a mixed-precision render)
+struct RenderLoop {
+    // mixed precision (TAKE_PRECISION_MIXED): rounds k < exact_rounds on the f64 records and scene, the rest on f32
+    // records of the same slots and the f32 scene
+    bool mixed = false;
+    int exact_rounds = 0;
+    PathState<float> st32{nullptr, 0};
+    RenderParams<float> rp32{};
+};
+template <class R> int prepare_loop(Frame<R> &fr, const TakeRenderOpts &o, RenderLoop &loop) {
+    fr.sort_materials = fr.sc.host.n_material_tags > 1;
+    if (const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT")) fr.dump = std::atoll(dump_env);
+    if (fr.sort_materials) {
+        const size_t need = (size_t)N_SORT_KEYS * fr.wide_grid * (BLOCK / WAVE);
+        if (fr.work.sort_hist.n != need) {
+            HIP_TRY(fr.work.sort_hist.alloc(need));
+            HIP_TRY(fr.work.sort_base.alloc(need));
+        }
+    }
+    loop.mixed = sizeof(R) == 8 && fr.ts->precision == TAKE_PRECISION_MIXED;
+    if (loop.mixed) {
+        loop.exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
+        if (o.integrator != 0) return fail(TAKE_E_INVALID, "mixed precision renders the reference's path_tracing (integrator 0) only");
+        loop.st32 = PathState<float>{fr.work.records_f32.p, fr.slots};
+        loop.rp32 = make_params<float>(o, fr.rp.width, fr.rp.height, fr.n_rows, fr.first, fr.stride);
+    }
+    return TAKE_OK;
+}
+// The rounds of one batch whose extend queue holds n paths (fr.rp.s0 / spb: the batch's): launched until the queue is
+// known to be empty, never waiting for the GPU (QueuePoll)
+template <class R> int run_rounds(Frame<R> &fr, RenderLoop &loop, int max_depth, int64_t n, QueuePoll &poll) {
+    TakeScene *ts = fr.ts;
+    loop.rp32.s0 = fr.rp.s0, loop.rp32.spb = fr.rp.spb;
+    const int rounds = max_depth + 2;
+    int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
+    bool finished = false;
+    for (int k = 0; k < rounds && !finished; k++) {
+        // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
+        // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
+        if (loop.mixed && k >= loop.exact_rounds) HIP_TRY(launch_round(fr, ts->f, loop.st32, loop.rp32, k, n_bound, true, nullptr));
+        else HIP_TRY(launch_round(fr, fr.sc, fr.st, fr.rp, k, n_bound, false, (loop.mixed && k == loop.exact_rounds - 1) ? loop.st32.r : nullptr));
+        int rc = TAKE_OK;
+        if (k + 1 < rounds) rc = poll.post(fr.work.qwords.p + (k & 1 ? Q_N_EXT0 : Q_N_EXT1));  // the length of the next round's queue
+        if (!rc) rc = poll.drain(n_bound, finished);
+        if (rc) return rc;
+    }
+    poll.end_batch();
+    return TAKE_OK;
+}
+
+// first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
+// random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
+// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
+// (What is a render's own between the frame's steps: its checks, the batch loop, accumulate and resolve.)
+template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
+                                   int64_t first_sample, bool keep_accum) {
+    if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
+    if (const int rc = check_render_opts(sc, o)) return rc;
     Frame<R> fr{ts, sc, work, stream};
     int rc = pick_strips(fr, o);
     if (!rc) rc = begin_frame(fr, o, true);
     const int64_t npix = fr.npix;
     if (rc || npix == 0) return rc;
-
-    fr.sort_materials = sc.host.n_material_tags > 1;
-    if (const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT")) fr.dump = std::atoll(dump_env);
-    if (fr.sort_materials) {
-        const size_t need = (size_t)N_SORT_KEYS * fr.wide_grid * (BLOCK / WAVE);
-        if (work.sort_hist.n != need) {
-            HIP_TRY(work.sort_hist.alloc(need));
-            HIP_TRY(work.sort_base.alloc(need));
-        }
-    }
-    // mixed precision (TAKE_PRECISION_MIXED): rounds k < exact_rounds on the f64 records and scene, the rest on f32
-    // records of the same slots and the f32 scene
-    const bool mixed = sizeof(R) == 8 && ts->precision == TAKE_PRECISION_MIXED;
-    int exact_rounds = 0;
-    PathState<float> st32{nullptr, 0};
-    RenderParams<float> rp32{};
-    if (mixed) {
-        exact_rounds = o.exact_bounces > 0 ? o.exact_bounces : TAKE_DEFAULT_EXACT_BOUNCES;
-        if (o.integrator != 0) return fail(TAKE_E_INVALID, "mixed precision renders the reference's path_tracing (integrator 0) only");
-        st32 = PathState<float>{work.records_f32.p, fr.slots};
-        rp32 = make_params<float>(o, fr.rp.width, fr.rp.height, fr.n_rows, fr.first, fr.stride);
-    }
+    RenderLoop loop;
+    if ((rc = prepare_loop(fr, o, loop))) return rc;
     if (!keep_accum) HIP_TRY(hipMemsetAsync(work.accum.p, 0, sizeof(R) * 3 * npix, stream));
     if ((rc = start_frame(fr))) return rc;
     HIP_TRY(ts->poll.create());
@@ -520,24 +558,11 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace
     for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
         const int nb = std::min(fr.spb, o.spp - s0);
         const int64_t n = start_batch(fr, (int32_t)first_sample + s0, nb);
-        rp32.s0 = fr.rp.s0, rp32.spb = nb;
-        const int rounds = o.max_depth + 2;
-        int64_t n_bound = n;  // upper bound of the extend-queue length (queues only shrink)
-        bool finished = false;
-        for (int k = 0; k < rounds && !finished; k++) {
-            // mixed precision: the paths still alive after the last exact shade round continue on f32 records (and
-            // the f32 scene) — converted by that round (k_shade, to_f32; k_convert_state without TK_SHADE_RECORD)
-            if (mixed && k >= exact_rounds) HIP_TRY(launch_round(fr, ts->f, st32, rp32, k, n_bound, true, nullptr));
-            else HIP_TRY(launch_round(fr, sc, fr.st, fr.rp, k, n_bound, false, (mixed && k == exact_rounds - 1) ? st32.r : nullptr));
-            if (k + 1 < rounds) rc = poll.post(work.qwords.p + (k & 1 ? Q_N_EXT0 : Q_N_EXT1));  // the length of the next round's queue
-            if (!rc) rc = poll.drain(n_bound, finished);
-            if (rc) return rc;
-        }
-        poll.end_batch();
+        if ((rc = run_rounds(fr, loop, o.max_depth, n, poll))) return rc;
         fr.tm.begin(TK_OTHER);
         if constexpr (sizeof(R) == 8)
-            if (mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, st32, work.accum.p, (int32_t)npix, nb);
-        if (!mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)npix, nb);
+            if (loop.mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, (int32_t)npix, nb);
+        if (!loop.mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)npix, nb);
         fr.tm.end();
     }
     fr.tm.begin(TK_OTHER);
@@ -549,6 +574,107 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace
         std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
                      fr.raw[C_WAIT_SLOTS], fr.raw[C_IDLE_SLOTS], fr.raw[C_NODE_VISITS], fr.raw[C_OCC_CACHE_HITS], fr.raw[C_RAYS_SHADOW]);
     return TAKE_OK;
+}
+
+// TakeAdaptiveOpts (null: all defaults) with the defaults filled in, for a render of o.spp > 0 samples at most
+ad::Rule make_rule(const TakeRenderOpts &o, const TakeAdaptiveOpts *a) {
+    ad::Rule r{o.spp, 16, 8, 0.05, 1e-3};
+    if (a && a->min_spp > 0) r.min_spp = a->min_spp;
+    if (a && a->step_spp > 0) r.step_spp = a->step_spp;
+    if (a && a->threshold >= 0) r.threshold = a->threshold;
+    if (a && a->floor > 0) r.floor = a->floor;
+    r.min_spp = std::min(r.min_spp, o.spp);
+    return r;
+}
+
+// Adaptive sampling (take_hip_render_adaptive*; contract: include/take_hip.h, kernels: tk_adaptive.h).  Pass 0 is a
+// render's batch loop over min_spp samples of every pixel; every later pass puts the next samples of the pixels still
+// active into the round-0 extend queue (k_generate_list) and runs the render's own rounds on it.  Path records stay
+// addressed by sample * npix + pixel, so the workspace is sized for max(min_spp, step_spp) samples of all pixels and
+// a pass that does not fit is split into batches — which is what keeps slot_pixel / path_rng, and with them every shade
+// instance, untouched.  After each pass: accumulate + moments, the test, the ordered compaction, and the length of the
+// next list read back (one 4-byte copy and one synchronisation: the next pass's grid and reciprocal need it).
+template <class R>
+int adaptive_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, const TakeAdaptiveOpts *ao, void *d_out,
+                  const TakeAdaptiveStats &stats, hipStream_t stream) {
+    ts->acc_samples = 0;  // (the accumulator is overwritten: a progressive sequence ends)
+    if (const int rc = check_render_opts(sc, o)) return rc;
+    const ad::Rule rule = make_rule(o, ao);
+    if (o.integrator != 0) return fail(TAKE_E_INVALID, "adaptive sampling renders the reference's path_tracing (integrator 0) only");
+    Frame<R> fr{ts, sc, work, stream};
+    int rc = pick_strips(fr, o);
+    TakeRenderOpts sized = o;  // the batches hold the samples of one pass, not of the whole render
+    sized.spp = std::min(o.spp, std::max(rule.min_spp, rule.step_spp));
+    if (!rc) rc = begin_frame(fr, sized, true);
+    const int64_t npix = fr.npix;
+    if (rc || npix == 0) return rc;
+    RenderLoop loop;
+    if ((rc = prepare_loop(fr, o, loop))) return rc;
+    if ((rc = work.ensure_adaptive(npix))) return rc;
+    AdaptiveState &a = work.adaptive;
+    HIP_TRY(hipMemsetAsync(work.accum.p, 0, sizeof(R) * 3 * npix, stream));
+    HIP_TRY(hipMemsetAsync(a.count.p, 0, sizeof(int32_t) * npix, stream));
+    HIP_TRY(hipMemsetAsync(a.m1.p, 0, sizeof(double) * npix, stream));
+    HIP_TRY(hipMemsetAsync(a.m2.p, 0, sizeof(double) * npix, stream));
+    if ((rc = start_frame(fr))) return rc;
+    HIP_TRY(ts->poll.create());
+    QueuePoll poll{ts->poll, stream};
+
+    uint64_t samples = 0;
+    const int32_t *list = nullptr;  // (pass 0: every pixel)
+    int32_t n_active = (int32_t)npix;
+    for (int pass = 0, n = 0; n_active > 0 && n < o.spp; pass++) {
+        const int add = pass == 0 ? rule.min_spp : std::min(rule.step_spp, o.spp - n);
+        const int list_grid = (int)std::min<int64_t>(((int64_t)n_active + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+        fr.listed_pass = pass > 0;
+        for (int done = 0; done < add; done += fr.spb) {
+            const int nb = std::min(fr.spb, add - done);
+            int64_t n_paths;
+            if (pass == 0) {
+                n_paths = start_batch(fr, n + done, nb);
+            } else {
+                n_paths = (int64_t)nb * n_active;
+                fr.rp.s0 = n + done, fr.rp.spb = nb;
+                fr.tm.begin(TK_OTHER);
+                const int gen_grid = (int)std::min<int64_t>((n_paths + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
+                hipLaunchKernelGGL((ad::k_generate_list<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
+                                   work.queue[0].p, n_paths);
+                hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, work.qwords.p, (int)Q_N_EXT0, (int32_t)n_paths);
+                fr.tm.end();
+            }
+            if ((rc = run_rounds(fr, loop, o.max_depth, n_paths, poll))) return rc;
+            fr.tm.begin(TK_OTHER);
+            if constexpr (sizeof(R) == 8)
+                if (loop.mixed)
+                    hipLaunchKernelGGL(ad::k_accumulate_stats_mixed, dim3(list_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, a.count.p, a.m1.p, a.m2.p, list,
+                                       n_active, (int32_t)npix, nb);
+            if (!loop.mixed)
+                hipLaunchKernelGGL((ad::k_accumulate_stats<R>), dim3(list_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, a.count.p, a.m1.p, a.m2.p, list, n_active,
+                                   (int32_t)npix, nb);
+            fr.tm.end();
+        }
+        n += add;
+        samples += (uint64_t)n_active * (uint64_t)add;
+        if (n >= o.spp) break;  // (every pixel still active has spp samples: it stops)
+        // the test, and the pixels it keeps in ascending order -> the other list
+        int32_t *next = a.list[pass & 1].p;
+        fr.tm.begin(TK_OTHER);
+        hipLaunchKernelGGL(ad::k_adaptive_select, dim3((unsigned)(((int64_t)n_active + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, rule, a.count.p, a.m1.p, a.m2.p, list,
+                           n_active, a.mask.p);
+        hipLaunchKernelGGL(ad::k_compact_scan, dim3(1), dim3(ad::SCAN_THREADS), 0, stream, a.mask.p, ad::groups_of(n_active), a.base.p, a.n_next.p);
+        hipLaunchKernelGGL(ad::k_compact_scatter, dim3(list_grid), dim3(BLOCK), 0, stream, list, a.mask.p, a.base.p, n_active, next);
+        fr.tm.end();
+        int32_t kept = 0;
+        HIP_TRY(hipMemcpyAsync(&kept, a.n_next.p, sizeof kept, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (kept < 0 || kept > n_active) return fail(TAKE_E_DEVICE, "adaptive sampling: the compacted list is longer than the list it came from");
+        n_active = kept, list = next;
+    }
+    fr.tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((ad::k_resolve_adaptive<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, a.count.p, a.m1.p, a.m2.p, (R *)d_out, stats.count, stats.m1,
+                       stats.m2, fr.rp.width, fr.n_rows);
+    fr.tm.end();
+    return end_frame(fr, samples);
 }
 
 // The first-hit feature buffers of a scene (take_hip_render_features*; contract: include/take_hip.h): per batch the
@@ -709,6 +835,16 @@ template <class R> int RenderWorkspace<R>::ensure(int64_t slots, int64_t npix, b
     }
     return TAKE_OK;
 }
+template <class R> int RenderWorkspace<R>::ensure_adaptive(int64_t npix) {
+    AdaptiveState &a = adaptive;
+    if ((int64_t)a.count.n >= npix) return TAKE_OK;
+    const size_t n = (size_t)npix, groups = (size_t)ad::groups_of(npix);
+    const bool ok = a.count.alloc(n) == hipSuccess && a.m1.alloc(n) == hipSuccess && a.m2.alloc(n) == hipSuccess && a.list[0].alloc(n) == hipSuccess &&
+                    a.list[1].alloc(n) == hipSuccess && a.mask.alloc(groups) == hipSuccess && a.base.alloc(groups) == hipSuccess && a.n_next.alloc(1) == hipSuccess;
+    if (ok) return TAKE_OK;
+    a = AdaptiveState{};
+    return fail(TAKE_E_NOMEM, "out of device memory for the adaptive sampler's per-pixel state");
+}
 template struct RenderWorkspace<float>;
 template struct RenderWorkspace<double>;
 
@@ -734,6 +870,9 @@ int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, co
         img = work.out.p;
         return rc;
     });
+}
+int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdaptiveOpts *a, void *d_out, const TakeAdaptiveStats &d_stats, hipStream_t stream) {
+    return on_primary(ts, [&](auto &sc, auto &work) { return adaptive_impl(ts, sc, work, o, a, d_out, d_stats, stream); });
 }
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return features_impl(ts, sc, work, o, d_out, stream); });

@@ -129,6 +129,18 @@ template <class R> struct SceneT {
     }
 };
 
+// take_hip_render_adaptive*: the per-pixel state of the adaptive sampler (tk_adaptive.h), for the pixels of the call's
+// strip set: samples received and the moments of the sample values (double whatever the scene's precision), the two
+// lists of pixels still active (one read, one written by the compaction), and the compaction's scratch — one keep mask
+// per 64 list entries, its scanned bit counts, the length of the next list.
+struct AdaptiveState {
+    DevBuf<int32_t> count;
+    DevBuf<double> m1, m2;
+    DevBuf<int32_t> list[2];
+    DevBuf<uint64_t> mask;
+    DevBuf<int32_t> base, n_next;
+};
+
 // The render workspace of a handle, in the precision R of its primary side: every render, feature pass and trace hook
 // of the scene uses this one set (the f32 rounds of a mixed-precision render too: slot numbers and queue words do not
 // depend on the precision of the records they point to).  Per-slot buffers and framebuffers grow on demand (ensure);
@@ -148,6 +160,9 @@ template <class R> struct RenderWorkspace {
         if ((int64_t)denoise.n >= reals || denoise.alloc((size_t)reals) == hipSuccess) return TAKE_OK;
         return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's workspace");
     }
+    // grows on demand as the denoiser's planes do, is no per-slot buffer and goes with the handle (defined in tk_render.hip)
+    AdaptiveState adaptive;
+    int ensure_adaptive(int64_t npix);
     DevBuf<int32_t> qwords;  // Q_NUM_WORDS + 2 * N_SORT_KEYS
     DevBuf<unsigned long long> counters;
     int64_t capacity = 0;  // path slots allocated
@@ -267,6 +282,8 @@ int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img);
 // the first-hit feature buffers (include/take_hip.h: take_hip_render_features_device) into device memory
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream);
+// adaptive sampling (include/take_hip.h: take_hip_render_adaptive_device) into device memory; a: checked by the caller, or null
+int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdaptiveOpts *a, void *d_out, const TakeAdaptiveStats &d_stats, hipStream_t stream);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
 

@@ -64,17 +64,30 @@ def imwrite_pfm(path, img):
 
 
 def main(argv=None):
-    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise]` — the reference's main.cpp:9-27:
+    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]` — the
+    reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
-    the default options (Scene.render_denoised); image.exr is the same bytes with or without it."""
+    the default options (Scene.render_denoised); image.exr is the same bytes with or without it.  -adaptive (an
+    extension): also adaptive.exr, the scene's spp as the maximum per pixel and pixels stopped once the relative standard
+    error of their mean is at or below `threshold` (default: the library's; Scene.render_adaptive), and one line with
+    the samples taken against width * height * spp; image.exr is the same bytes with or without it."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
     if "-t" in params:  # main.cpp:13-15: thread count of the CPU pool; meaningless here, accepted and dropped
         i = params.index("-t")
         del params[i:i + 2]
+    adaptive, threshold = "-adaptive" in params, -1.0
+    if adaptive:  # the threshold is optional: the next parameter, if it reads as a number
+        i = params.index("-adaptive")
+        try:
+            threshold = float(params[i + 1])
+            del params[i + 1]
+        except (IndexError, ValueError):
+            pass
+        del params[i]
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
@@ -94,6 +107,11 @@ def main(argv=None):
             imwrite("normal.exr", planes["normal"])
         if denoise:
             imwrite("denoised.exr", scene.render_denoised(spp=sd.spp, max_depth=max_depth, seed=0))
+        if adaptive:
+            img, stats = scene.render_adaptive(spp=sd.spp, max_depth=max_depth, seed=0, threshold=threshold, stats=True)
+            imwrite("adaptive.exr", img)
+            taken, full = int(stats["count"].sum(dtype=np.int64)), sd.width * sd.height * sd.spp
+            print(f"adaptive: {taken} of {full} samples ({100.0 * taken / full:.1f} %)")
     finally:
         scene.close()
     return 0
