@@ -577,6 +577,67 @@ int take_hip_render_adaptive_device(TakeScene *scene, const TakeRenderOpts *opts
 int take_hip_render_adaptive(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive, void *rgb_out_host,
                              const TakeAdaptiveStats *host_stats);
 
+/* ---- variance-guided denoiser (new symbols of ABI version 5; no struct changed): the spatial half of SVGF (Schied et
+ * al. 2017) — the A-trous filter above, but the colour term of a tap is scaled by the pixel's own estimated standard
+ * deviation, taken from the moment planes the adaptive sampler leaves (TakeAdaptiveStats), and that variance is
+ * filtered along with the colour, so that later levels stop blurring once the estimate is clean.  No temporal part, no
+ * trained weights; deterministic.  EXTENSION without an upstream counterpart — parity unpinned with respect to the
+ * reference; specified against its own f64 restatement (tests/denoise_var_ref.py; DESIGN.md par. 4h has the arithmetic
+ * operation by operation).
+ * Planes as take_hip_denoise_device takes them, and the three of TakeAdaptiveStats as take_hip_render_adaptive_device
+ * leaves them: count int32, m1 and m2 double (always), height * width, row 0 = top; the moments are of L_s = (r + g) + b
+ * of the raw radiance.  Real = float or double by `precision`; every + - * / is one operation of Real in the order
+ * written, constants are computed in double and rounded once, exp is the library's, TINY the smallest normal Real.
+ * Options: TakeDenoiseOpts, but sigma_color <= 0 means 4.0 in these calls — it is a multiple of the pixel's standard
+ * deviation, not a radiance; the other defaults as above.
+ *   Initial variance of the pixel mean, in double with the operations of the adaptive rule:
+ *     n = (double)count;  mean = m1 / n;  v = m2 / n - mean * mean;  v = v > 0 ? v : 0;
+ *     s2 = count >= 2 ? v / (n - 1) : mean * mean   (one sample: 100 % relative error; count <= 0: 0 / 0 = NaN, taken
+ *     as it is);  V0 = (Real)s2.
+ *   Demodulate (with an albedo and without TAKE_DENOISE_KEEP_ALBEDO): A = max(albedo, floor) per channel, C0 = rgb / A,
+ *     Am = ((A.r + A.g) + A.b) * (Real)(1.0 / 3.0), V0 = V0 / (Am * Am); otherwise C0 = rgb.
+ *   Level i = 0 .. iterations - 1, s = 2^i, at every pixel p:
+ *     gv = sum of k3 * V_i(q) / sum of k3 over the 3 x 3 taps at unit spacing (dy outer, dx inner, taps outside the
+ *       image skipped), k3 = g[|dx|] * g[|dy|], g = {1/2, 1/4};
+ *     inv_c = 1 / (sigma_color^2 * gv + TINY)   (no 4^i: the variance falls by itself as the filter averages);
+ *     the 5 x 5 taps q = p + s * (dx, dy) as above, k = h[|dx|] * h[|dy|], l(X) = (X.r + X.g) + X.b:
+ *       dl = l(C_i(p)) - l(C_i(q));  x = (dl * dl) * inv_c (+inf gives weight 0), plus the normal and depth terms as
+ *       above;  w = k * exp(-x);  num += w * C_i(q);  nv += (w * w) * V_i(q);  den += w;
+ *     C_{i+1}(p) = num / den;  V_{i+1}(p) = nv / (den * den).
+ *   Remodulate: out = C_n * A (or C_n); variance_out (optional, height * width Real) = V_n * (Am * Am) (or V_n): the
+ *     filter's own estimate of the variance of l(out).
+ * out may be rgb itself; no other aliasing.  The defaults are starting values, held to one condition by the tests (an
+ * 8-spp Cornell box gets closer to its 1024-spp render).
+ * Needs no scene; the working images are allocated per call; enqueued on `stream`, returns after it has completed.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL d_rgb / d_out / d_stats or any of d_stats' three
+ * pointers NULL ("null argument"), and everything take_hip_denoise_device refuses. */
+int take_hip_denoise_variance_device(const void *d_rgb, const TakeFeatureBuffers *d_guides, const TakeAdaptiveStats *d_stats,
+                                     int32_t precision, int32_t width, int32_t height, const TakeDenoiseOpts *opts,
+                                     void *d_out, void *d_variance_out /* NULL ok */, void *stream);
+/* the same with host pointers (upload, the same kernels, download) */
+int take_hip_denoise_variance(const void *rgb, const TakeFeatureBuffers *guides, const TakeAdaptiveStats *stats,
+                              int32_t precision, int32_t width, int32_t height, const TakeDenoiseOpts *opts, void *out,
+                              void *variance_out /* NULL ok */);
+/* Render the whole image adaptively (strip_first / strip_stride are ignored, as in take_hip_render_denoised_device),
+ * make albedo, normal and depth, filter with the sampler's own moments — all on the device, the planes and working
+ * images kept in the handle.  Specified as, and bit for bit equal to, three calls made by hand:
+ * take_hip_render_adaptive_device; take_hip_render_features_device with the same options but spp = the effective
+ * min_spp (after the defaults and the clamp to opts->spp: the samples every pixel has, so the guide pass does not grow
+ * with the maximum); take_hip_denoise_variance_device in place.  d_stats: optional OUTPUTS (every pointer may be NULL,
+ * as in take_hip_render_adaptive_device), d_variance_out optional.  Afterwards a progressive sequence has ended; the
+ * counters are the feature pass's.  f32 scenes use float planes, f64 and MIXED scenes double.  Not for scene groups.
+ * TAKE_E_INVALID: a NULL scene, render options or output ("null argument"), what take_hip_render_adaptive_device
+ * refuses of the adaptive options, what take_hip_denoise_device refuses of the denoise options, in that order and
+ * before a device is looked for; then what the adaptive render refuses. */
+int take_hip_render_adaptive_denoised_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
+                                             const TakeDenoiseOpts *denoise, void *d_out,
+                                             const TakeAdaptiveStats *d_stats /* NULL ok: optional outputs */,
+                                             void *d_variance_out /* NULL ok */, void *stream);
+/* the same with host pointers */
+int take_hip_render_adaptive_denoised(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
+                                      const TakeDenoiseOpts *denoise, void *rgb_out_host,
+                                      const TakeAdaptiveStats *host_stats /* NULL ok */, void *variance_out_host /* NULL ok */);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

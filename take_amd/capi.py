@@ -33,6 +33,7 @@ EXPORTS = [
     "take_hip_debug_tree_info", "take_hip_debug_tree",
     "take_hip_denoise", "take_hip_denoise_device", "take_hip_render_denoised", "take_hip_render_denoised_device",
     "take_hip_render_adaptive", "take_hip_render_adaptive_device",
+    "take_hip_denoise_variance", "take_hip_denoise_variance_device", "take_hip_render_adaptive_denoised", "take_hip_render_adaptive_denoised_device",
 ]
 
 
@@ -80,7 +81,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -183,6 +184,55 @@ def denoise_device(rgb, width, height, precision, out=None, albedo=None, normal=
     _check(lib().take_hip_denoise_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), int(precision), int(width), int(height),
                                          None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
                                          C.c_void_p(stream or 0)))
+
+
+def denoise_variance(rgb, count, m1, m2, albedo=None, normal=None, depth=None, variance=False, opts=None, **kw):
+    """the variance-guided denoiser on host arrays (take_hip_denoise_variance: the A-trous filter with the pixel's own
+    standard deviation as its colour sigma, include/take_hip.h): rgb and the guides as denoise() takes them, and the three
+    planes an adaptive render leaves (Scene.render_adaptive(stats=True)): count (H, W) int32, m1 and m2 (H, W) float64
+    -> the filtered (H, W, 3) image; variance=True: -> (image, the filter's (H, W) estimate of the variance of the
+    result's r + g + b, in rgb's dtype).  Options as denoise(), but sigma_color (default 4.0) counts standard deviations."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype not in (np.float32, np.float64) or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb must be a (H, W, 3) float32 or float64 array")
+    h, w = rgb.shape[:2]
+    rgb = np.ascontiguousarray(rgb)
+    bufs, keep = D.TakeFeatureBuffers(), []
+    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a)
+        if a.dtype != rgb.dtype or a.shape != shape:
+            raise ValueError(f"{name} must be a {shape} array of rgb's dtype")
+        keep.append(a)
+        setattr(bufs, name, a.ctypes.data)
+    stats, moments = D.TakeAdaptiveStats(), []
+    for name, a, dtype in (("count", count, np.int32), ("m1", m1, np.float64), ("m2", m2, np.float64)):
+        a = None if a is None else np.ascontiguousarray(a)
+        if a is None or a.dtype != dtype or a.shape != (h, w):
+            raise ValueError(f"{name} must be a {(h, w)} {np.dtype(dtype).name} array")
+        moments.append(a)
+        setattr(stats, name, a.ctypes.data)
+    opts = _denoise_opts(opts, kw)
+    out = np.zeros_like(rgb)
+    var = np.zeros((h, w), rgb.dtype) if variance else None
+    precision = D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64
+    _check(lib().take_hip_denoise_variance(rgb.ctypes.data, C.byref(bufs) if keep else None, C.byref(stats), precision, w, h,
+                                           None if opts is None else C.byref(opts), out.ctypes.data, None if var is None else var.ctypes.data))
+    return (out, var) if variance else out
+
+
+def denoise_variance_device(rgb, count, m1, m2, width, height, precision, out=None, albedo=None, normal=None, depth=None, variance=None, opts=None,
+                            stream=None, **kw):
+    """the same on planes in device memory (take_hip_denoise_variance_device): rgb, out, the guides and variance (the
+    optional output plane) are torch device tensors or integer device pointers of `precision`'s Real, count int32, m1 and
+    m2 float64; out = None filters in place; blocks until done.  Needs no scene."""
+    bufs = D.TakeFeatureBuffers(_pointer(albedo), _pointer(normal), _pointer(depth), None, None, None)
+    stats = D.TakeAdaptiveStats(_pointer(count), _pointer(m1), _pointer(m2))
+    opts = _denoise_opts(opts, kw)
+    _check(lib().take_hip_denoise_variance_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), C.byref(stats), int(precision), int(width), int(height),
+                                                  None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
+                                                  C.c_void_p(_pointer(variance)), C.c_void_p(stream or 0)))
 
 
 class DeviceMesh:
@@ -454,6 +504,48 @@ class Scene:
             st = D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in ("count", "m1", "m2")])
         _check(lib().take_hip_render_adaptive_device(self.h, C.byref(o), None if a is None else C.byref(a), C.c_void_p(_pointer(d_ptr)),
                                                      None if st is None else C.byref(st), C.c_void_p(stream or 0)))
+
+    def render_adaptive_denoised(self, spp=None, max_depth=None, seed=0, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, stats=False, variance=False,
+                                 adaptive="keywords", ray_epsilon=0.0, samples_per_batch=0, integrator=0, opts=None, **kw):
+        """render the whole image adaptively, make albedo, normal and depth from min_spp samples and filter with the
+        sampler's own moments, all on the device (take_hip_render_adaptive_denoised) -> (H, W, 3) host array.  Equal bit
+        for bit to render_adaptive(stats=True) + render_features(the effective min_spp) + denoise_variance made by hand.
+        stats=True and / or variance=True: -> (image, the planes of render_adaptive) / (image, variance plane) / (image,
+        planes, variance plane).  Sampler options as render_adaptive takes them (adaptive: a TakeAdaptiveOpts instead of
+        the keywords, or None = all defaults); denoise options: keywords of cdefs.denoise_opts, or opts = a
+        TakeDenoiseOpts; neither = the defaults (sigma_color 4.0 standard deviations)."""
+        spp = self.sd.spp if spp is None else spp
+        max_depth = self.sd.max_depth if max_depth is None else max_depth
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
+        opts = _denoise_opts(opts, kw)
+        h, w = self.sd.height, self.sd.width
+        out = np.zeros((h, w, 3), self.dtype)
+        planes = {"count": np.zeros((h, w), np.int32), "m1": np.zeros((h, w), np.float64), "m2": np.zeros((h, w), np.float64)} if stats else None
+        st = D.TakeAdaptiveStats(*[planes[k].ctypes.data for k in ("count", "m1", "m2")]) if stats else None
+        var = np.zeros((h, w), self.dtype) if variance else None
+        _check(lib().take_hip_render_adaptive_denoised(self.h, C.byref(o), None if a is None else C.byref(a), None if opts is None else C.byref(opts),
+                                                       out.ctypes.data, None if st is None else C.byref(st), None if var is None else var.ctypes.data))
+        extra = ([planes] if stats else []) + ([var] if variance else [])
+        return (out, *extra) if extra else out
+
+    def render_adaptive_denoised_device(self, d_ptr, spp, max_depth, seed=0, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, stats=None, variance=None,
+                                        adaptive="keywords", ray_epsilon=0.0, samples_per_batch=0, stream=None, integrator=0, opts=None, **kw):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; H * W * 3 of the
+        scene's Real); stats: {"count" / "m1" / "m2": device tensor or pointer} for the planes wanted; variance: the
+        optional (H * W of the scene's Real) output plane; blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
+        opts = _denoise_opts(opts, kw)
+        st = None
+        if stats:
+            unknown = set(stats) - {"count", "m1", "m2"}
+            if unknown:
+                raise ValueError(f"unknown statistics plane {sorted(unknown)[0]!r}: one of ('count', 'm1', 'm2')")
+            st = D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in ("count", "m1", "m2")])
+        _check(lib().take_hip_render_adaptive_denoised_device(self.h, C.byref(o), None if a is None else C.byref(a), None if opts is None else C.byref(opts),
+                                                              C.c_void_p(_pointer(d_ptr)), None if st is None else C.byref(st), C.c_void_p(_pointer(variance)),
+                                                              C.c_void_p(stream or 0)))
 
     def set_instance_transforms(self, xforms, stream=None):
         """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the

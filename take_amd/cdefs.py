@@ -178,6 +178,22 @@ def adaptive_opts(min_spp=0, step_spp=0, threshold=-1.0, floor=0.0):
     return TakeAdaptiveOpts(int(min_spp), int(step_spp), float(threshold), float(floor), 0, 0)
 
 
+# the variance-guided denoiser (include/take_hip.h): TakeDenoiseOpts, but sigma_color counts the pixel's standard deviations
+DENOISE_VARIANCE_DEFAULTS = dict(DENOISE_DEFAULTS, sigma_color=4.0)
+
+# name -> argument types
+DENOISE_VARIANCE_PROTOTYPES = {
+    "take_hip_denoise_variance_device": [C.c_void_p, C.POINTER(TakeFeatureBuffers), C.POINTER(TakeAdaptiveStats), C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(TakeDenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_denoise_variance": [C.c_void_p, C.POINTER(TakeFeatureBuffers), C.POINTER(TakeAdaptiveStats), C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(TakeDenoiseOpts), C.c_void_p, C.c_void_p],
+    "take_hip_render_adaptive_denoised_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.POINTER(TakeDenoiseOpts), C.c_void_p,
+                                                 C.POINTER(TakeAdaptiveStats), C.c_void_p, C.c_void_p],
+    "take_hip_render_adaptive_denoised": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.POINTER(TakeDenoiseOpts), C.c_void_p,
+                                          C.POINTER(TakeAdaptiveStats), C.c_void_p],
+}
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

@@ -56,13 +56,6 @@ template <class R> TakeDebugTreeInfo debug_tree_info(const SceneT<R> &sc) {
     for (int a = 0; a < 3; a++) o.grid_lo[a] = sc.dev.grid_lo[a], o.grid_step[a] = sc.dev.grid_step[a];
     return o;
 }
-// what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device
-int check_adaptive_opts(const TakeAdaptiveOpts *a) {
-    if (!a) return TAKE_OK;
-    if (!std::isfinite(a->threshold) || !std::isfinite(a->floor)) return fail(TAKE_E_INVALID, "threshold and floor must be finite");
-    if (a->flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
-    return TAKE_OK;
-}
 template <class R> int debug_tree_copy(const SceneT<R> &sc, void *nodes, void *prims, void *inst_trace) {
     const TakeDebugTreeInfo o = debug_tree_info(sc);
     const void *d_nodes = sc.dev.qnodes8 ? (const void *)sc.dev.qnodes8 : (sc.dev.qnodes ? (const void *)sc.dev.qnodes : (const void *)sc.dev.nodes);
@@ -73,6 +66,15 @@ template <class R> int debug_tree_copy(const SceneT<R> &sc, void *nodes, void *p
     return TAKE_OK;
 }
 }  // namespace
+
+namespace tk_host {
+int check_adaptive_opts(const TakeAdaptiveOpts *a) {
+    if (!a) return TAKE_OK;
+    if (!std::isfinite(a->threshold) || !std::isfinite(a->floor)) return fail(TAKE_E_INVALID, "threshold and floor must be finite");
+    if (a->flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
+    return TAKE_OK;
+}
+}  // namespace tk_host
 
 extern "C" {
 

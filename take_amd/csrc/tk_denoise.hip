@@ -1,8 +1,9 @@
-// tk_denoise.hip — the C entry points of the image-space denoiser (include/take_hip.h: take_hip_denoise*,
-// take_hip_render_denoised*) and the only unit that compiles the kernels of tk_denoise.h.  The scene-free calls need no
-// scene (as take_hip_pack_exr_scanlines does not) and allocate their working images per call; the scene-bound ones
-// render, make the feature planes and filter on the device, with planes and working images in the handle's
-// RenderWorkspace — they are the three public calls made by hand, through the same functions.
+// tk_denoise.hip — the C entry points of the image-space denoisers (include/take_hip.h: take_hip_denoise*,
+// take_hip_render_denoised*; the variance-guided take_hip_denoise_variance*, take_hip_render_adaptive_denoised*) and the
+// only unit that compiles the kernels of tk_denoise.h and tk_denoise_var.h.  The scene-free calls need no scene (as
+// take_hip_pack_exr_scanlines does not) and allocate their working images per call; the scene-bound ones render, make
+// the feature planes and filter on the device, with planes and working images in the handle's RenderWorkspace — they
+// are the three public calls made by hand, through the same functions.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "take_hip.h"
 #include "tk_scene_handle.h"
 #include "tk_denoise.h"
+#include "tk_denoise_var.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -24,9 +26,12 @@ struct DenoiseOpts {
     bool keep_albedo = false;
     double sigma_color = 1.0, sigma_normal = 0.3, sigma_depth = 0.05, albedo_floor = 1e-3;
 };
-// what needs no device: TAKE_E_INVALID with a message, or TAKE_OK and the resolved options
-int resolve(const TakeDenoiseOpts *o, DenoiseOpts &r) {
+// what needs no device: TAKE_E_INVALID with a message, or TAKE_OK and the resolved options.  sigma_color: its default —
+// a radiance for the fixed-sigma filter, a multiple of the pixel's standard deviation for the variance-guided one
+constexpr double SIGMA_COLOR = 1.0, SIGMA_COLOR_VARIANCE = 4.0;
+int resolve(const TakeDenoiseOpts *o, DenoiseOpts &r, double sigma_color = SIGMA_COLOR) {
     r = DenoiseOpts{};
+    r.sigma_color = sigma_color;
     if (!o) return TAKE_OK;
     if (o->iterations > dn::MAX_ITERATIONS) return fail(TAKE_E_INVALID, "iterations must be at most " + std::to_string(dn::MAX_ITERATIONS));
     if (o->flags & ~TAKE_DENOISE_KEEP_ALBEDO) return fail(TAKE_E_INVALID, "unknown flag bits");
@@ -80,6 +85,48 @@ int denoise_enqueue_any(int32_t precision, const void *rgb, const TakeFeatureBuf
     if (precision == TAKE_PRECISION_F64)
         return denoise_enqueue((const double *)rgb, (const double *)albedo, (const double *)normal, (const double *)depth, width, height, o, (double *)work, (double *)out, stream);
     return denoise_enqueue((const float *)rgb, (const float *)albedo, (const float *)normal, (const float *)depth, width, height, o, (float *)work, (float *)out, stream);
+}
+
+// The variance-guided filter (tk_denoise_var.h): the same shape of launches.  count / m1 / m2: the planes of
+// TakeAdaptiveStats; variance_out may be null.  o.sigma_color is a multiple of the pixel's standard deviation.
+template <class R>
+int denoise_var_enqueue(const R *rgb, const R *albedo, const R *normal, const R *depth, const TakeAdaptiveStats &s, int32_t width, int32_t height,
+                        const DenoiseOpts &o, R *work, R *out, R *variance_out, hipStream_t stream) {
+    const int64_t npix = (int64_t)width * height;
+    dn::Params<R> P{};
+    P.width = width, P.height = height;
+    P.guides = (normal ? dn::HAS_NORMAL : 0) | (depth ? dn::HAS_DEPTH : 0) | (albedo && !o.keep_albedo ? dn::DEMODULATE : 0);
+    P.inv_n = (R)(1.0 / (o.sigma_normal * o.sigma_normal)), P.inv_d = (R)(1.0 / (o.sigma_depth * o.sigma_depth));
+    P.albedo_floor = (R)o.albedo_floor;
+    const R sl2 = (R)(o.sigma_color * o.sigma_color);
+    dn::Rec4<R> *colour[2] = {(dn::Rec4<R> *)work, (dn::Rec4<R> *)work + npix}, *guide = (dn::Rec4<R> *)work + 2 * npix;
+    const dim3 pack_grid((unsigned)std::min<int64_t>((npix + 255) / 256, 2048));
+    hipLaunchKernelGGL((dn::k_denoise_var_pack<R>), pack_grid, dim3(256), 0, stream, P, rgb, albedo, normal, depth, (const int32_t *)s.count, (const double *)s.m1,
+                       (const double *)s.m2, colour[0], guide);
+    const dim3 grid((unsigned)((width + dn::DN_BX - 1) / dn::DN_BX), (unsigned)std::min((height + dn::DN_BY - 1) / dn::DN_BY, 65535)), block(dn::DN_BX, dn::DN_BY);
+    for (int i = 0; i < o.iterations; i++) {
+        if (i == o.iterations - 1)
+            hipLaunchKernelGGL((dn::k_denoise_var_level<R, true>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, sl2, (dn::Rec4<R> *)nullptr, albedo, out, variance_out);
+        else
+            hipLaunchKernelGGL((dn::k_denoise_var_level<R, false>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, sl2, colour[(i + 1) & 1], albedo, (R *)nullptr,
+                               (R *)nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return TAKE_OK;
+}
+// what the scene-free variance-guided calls refuse, before a device is looked for
+int check_variance_args(const void *rgb, const TakeAdaptiveStats *stats, const void *out, int32_t precision, int32_t width, int32_t height,
+                        const TakeDenoiseOpts *opts, DenoiseOpts &o) {
+    if (!rgb || !out || !stats || !stats->count || !stats->m1 || !stats->m2) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_image(precision, width, height)) return rc;
+    return resolve(opts, o, SIGMA_COLOR_VARIANCE);
+}
+// what the scene-bound variance-guided calls refuse, before a device is looked for: the adaptive part's, then the denoiser's
+int check_adaptive_denoised_args(const TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeDenoiseOpts *dopts, const void *out,
+                                 DenoiseOpts &o) {
+    if (!ts || !ropts || !out) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_adaptive_opts(aopts)) return rc;
+    return resolve(dopts, o, SIGMA_COLOR_VARIANCE);
 }
 }  // namespace
 
@@ -156,6 +203,108 @@ int take_hip_render_denoised(TakeScene *ts, const TakeRenderOpts *ropts, const T
     if (d_out.alloc((size_t)ts->width() * ts->height() * 3 * (ts->f64() ? 8 : 4)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoised image");
     if (int rc = take_hip_render_denoised_device(ts, ropts, dopts, d_out.p, nullptr)) return rc;
     HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+int take_hip_denoise_variance_device(const void *d_rgb, const TakeFeatureBuffers *d_guides, const TakeAdaptiveStats *d_stats, int32_t precision, int32_t width,
+                                     int32_t height, const TakeDenoiseOpts *opts, void *d_out, void *d_variance_out, void *stream) {
+    DenoiseOpts o;
+    if (int rc = check_variance_args(d_rgb, d_stats, d_out, precision, width, height, opts, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4;
+    DevBuf<char> work;
+    if (work.alloc((size_t)width * height * WORK_REALS * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's working images");
+    const void *albedo = d_guides ? d_guides->albedo : nullptr, *normal = d_guides ? d_guides->normal : nullptr, *depth = d_guides ? d_guides->depth : nullptr;
+    int rc;
+    if (precision == TAKE_PRECISION_F64)
+        rc = denoise_var_enqueue((const double *)d_rgb, (const double *)albedo, (const double *)normal, (const double *)depth, *d_stats, width, height, o, (double *)work.p,
+                                 (double *)d_out, (double *)d_variance_out, (hipStream_t)stream);
+    else
+        rc = denoise_var_enqueue((const float *)d_rgb, (const float *)albedo, (const float *)normal, (const float *)depth, *d_stats, width, height, o, (float *)work.p,
+                                 (float *)d_out, (float *)d_variance_out, (hipStream_t)stream);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return TAKE_OK;
+}
+
+int take_hip_denoise_variance(const void *rgb, const TakeFeatureBuffers *guides, const TakeAdaptiveStats *stats, int32_t precision, int32_t width, int32_t height,
+                              const TakeDenoiseOpts *opts, void *out, void *variance_out) {
+    DenoiseOpts o;
+    if (int rc = check_variance_args(rgb, stats, out, precision, width, height, opts, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
+    // rgb (filtered in place), the guides that were given, the three statistics planes: (host pointer, bytes per pixel);
+    // then the variance plane, if wanted
+    const std::pair<const void *, size_t> planes[7] = {{rgb, 3 * real}, {guides ? guides->albedo : nullptr, 3 * real}, {guides ? guides->normal : nullptr, 3 * real},
+                                                       {guides ? guides->depth : nullptr, real}, {stats->count, 4}, {stats->m1, 8}, {stats->m2, 8}};
+    DevBuf<char> d_plane[7], d_variance;
+    for (int k = 0; k < 7; k++) {
+        if (!planes[k].first) continue;
+        if (d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
+        HIP_TRY(hipMemcpy(d_plane[k].p, planes[k].first, d_plane[k].bytes(), hipMemcpyHostToDevice));
+    }
+    if (variance_out && d_variance.alloc(npix * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
+    const TakeFeatureBuffers d_guides{d_plane[1].p, d_plane[2].p, d_plane[3].p, nullptr, nullptr, nullptr};
+    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[4].p, (double *)d_plane[5].p, (double *)d_plane[6].p};
+    if (int rc = take_hip_denoise_variance_device(d_plane[0].p, &d_guides, &d_stats, precision, width, height, opts, d_plane[0].p, d_variance.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_plane[0].p, d_plane[0].bytes(), hipMemcpyDeviceToHost));
+    if (variance_out) HIP_TRY(hipMemcpy(variance_out, d_variance.p, d_variance.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+int take_hip_render_adaptive_denoised_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeDenoiseOpts *dopts, void *d_out,
+                                             const TakeAdaptiveStats *d_stats, void *d_variance_out, void *stream) {
+    DenoiseOpts o;
+    if (int rc = check_adaptive_denoised_args(ts, ropts, aopts, dopts, d_out, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    TakeRenderOpts ro = *ropts;
+    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_denoised_device
+    const int W = ts->width(), H = ts->height();
+    const int64_t npix = (int64_t)W * H;
+    return on_primary(ts, [&](auto &sc, auto &work) {
+        using R = std::remove_reference_t<decltype(*work.accum.p)>;
+        // the working images, then albedo, normal and depth, then — from the next multiple of 8 bytes on — the statistics
+        // planes the caller did not ask for: m1, m2, count
+        const int64_t real_planes = (WORK_REALS + 7) * npix, stats_at = (real_planes * (int64_t)sizeof(R) + 7) / 8 * 8;
+        if (int rc = work.ensure_denoise((stats_at + 20 * npix + (int64_t)sizeof(R) - 1) / (int64_t)sizeof(R))) return rc;
+        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
+        double *own_m1 = (double *)((char *)work.denoise.p + stats_at), *own_m2 = own_m1 + npix;
+        TakeAdaptiveStats stats{(int32_t *)(own_m2 + npix), own_m1, own_m2};
+        if (d_stats && d_stats->count) stats.count = d_stats->count;
+        if (d_stats && d_stats->m1) stats.m1 = d_stats->m1;
+        if (d_stats && d_stats->m2) stats.m2 = d_stats->m2;
+        if (int rc = render_adaptive_scene(ts, ro, aopts, d_out, stats, (hipStream_t)stream)) return rc;
+        TakeRenderOpts fo = ro;
+        fo.spp = adaptive_min_spp(ro, aopts);  // the samples every pixel has: the guide pass does not grow with the maximum
+        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
+        if (int rc = render_features_scene(ts, fo, planes, (hipStream_t)stream)) return rc;
+        if (int rc = denoise_var_enqueue((const R *)d_out, (const R *)albedo, (const R *)normal, (const R *)depth, stats, W, H, o, work.denoise.p, (R *)d_out,
+                                         (R *)d_variance_out, (hipStream_t)stream))
+            return rc;
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return (int)TAKE_OK;
+    });
+}
+
+int take_hip_render_adaptive_denoised(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeDenoiseOpts *dopts, void *rgb_out_host,
+                                      const TakeAdaptiveStats *host_stats, void *variance_out_host) {
+    DenoiseOpts o;
+    if (int rc = check_adaptive_denoised_args(ts, ropts, aopts, dopts, rgb_out_host, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    const size_t npix = (size_t)ts->width() * ts->height(), real = ts->f64() ? 8 : 4;
+    // the image and the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
+    const std::pair<void *, size_t> planes[5] = {{rgb_out_host, 3 * real}, {host_stats ? host_stats->count : nullptr, 4}, {host_stats ? host_stats->m1 : nullptr, 8},
+                                                 {host_stats ? host_stats->m2 : nullptr, 8}, {variance_out_host, real}};
+    DevBuf<char> d_plane[5];
+    for (int k = 0; k < 5; k++)
+        if (planes[k].first && d_plane[k].alloc(npix * planes[k].second) != hipSuccess)
+            return fail(TAKE_E_NOMEM, "out of device memory for the denoised adaptive render's planes");
+    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[1].p, (double *)d_plane[2].p, (double *)d_plane[3].p};
+    if (int rc = take_hip_render_adaptive_denoised_device(ts, ropts, aopts, dopts, d_plane[0].p, &d_stats, d_plane[4].p, nullptr)) return rc;
+    for (int k = 0; k < 5; k++)
+        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
 

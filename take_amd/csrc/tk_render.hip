@@ -874,6 +874,7 @@ int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, co
 int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdaptiveOpts *a, void *d_out, const TakeAdaptiveStats &d_stats, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return adaptive_impl(ts, sc, work, o, a, d_out, d_stats, stream); });
 }
+int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a) { return make_rule(o, a).min_spp; }
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return features_impl(ts, sc, work, o, d_out, stream); });
 }

@@ -284,8 +284,15 @@ int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, co
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream);
 // adaptive sampling (include/take_hip.h: take_hip_render_adaptive_device) into device memory; a: checked by the caller, or null
 int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdaptiveOpts *a, void *d_out, const TakeAdaptiveStats &d_stats, hipStream_t stream);
+// the samples every pixel of an adaptive render of o.spp > 0 samples at most gets before the first test: a's min_spp
+// (null or <= 0: the default) clamped to o.spp
+int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
+
+// ---- defined in tk_api.hip
+// what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device
+int check_adaptive_opts(const TakeAdaptiveOpts *a);
 
 // ---- defined in tk_build.hip
 // What k_make_prims — and, in a two-level scene, k_make_proto_prims and k_placement_boxes — read of the caller's

@@ -72,7 +72,9 @@ def main(argv=None):
     the default options (Scene.render_denoised); image.exr is the same bytes with or without it.  -adaptive (an
     extension): also adaptive.exr, the scene's spp as the maximum per pixel and pixels stopped once the relative standard
     error of their mean is at or below `threshold` (default: the library's; Scene.render_adaptive), and one line with
-    the samples taken against width * height * spp; image.exr is the same bytes with or without it."""
+    the samples taken against width * height * spp; image.exr is the same bytes with or without it.  Both -adaptive and
+    -denoise: also adaptive_denoised.exr, the adaptive render filtered with the sampler's own variance estimate
+    (Scene.render_adaptive_denoised); every other file is the same bytes as without the other flag."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -112,6 +114,8 @@ def main(argv=None):
             imwrite("adaptive.exr", img)
             taken, full = int(stats["count"].sum(dtype=np.int64)), sd.width * sd.height * sd.spp
             print(f"adaptive: {taken} of {full} samples ({100.0 * taken / full:.1f} %)")
+        if adaptive and denoise:
+            imwrite("adaptive_denoised.exr", scene.render_adaptive_denoised(spp=sd.spp, max_depth=max_depth, seed=0, threshold=threshold))
     finally:
         scene.close()
     return 0
