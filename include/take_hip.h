@@ -580,8 +580,8 @@ int take_hip_render_adaptive(TakeScene *scene, const TakeRenderOpts *opts, const
 /* ---- variance-guided denoiser (new symbols of ABI version 5; no struct changed): the spatial half of SVGF (Schied et
  * al. 2017) — the A-trous filter above, but the colour term of a tap is scaled by the pixel's own estimated standard
  * deviation, taken from the moment planes the adaptive sampler leaves (TakeAdaptiveStats), and that variance is
- * filtered along with the colour, so that later levels stop blurring once the estimate is clean.  No temporal part, no
- * trained weights; deterministic.  EXTENSION without an upstream counterpart — parity unpinned with respect to the
+ * filtered along with the colour, so that later levels stop blurring once the estimate is clean.  (The temporal half:
+ * take_hip_temporal_accumulate* below.)  No trained weights; deterministic.  EXTENSION without an upstream counterpart — parity unpinned with respect to the
  * reference; specified against its own f64 restatement (tests/denoise_var_ref.py; DESIGN.md par. 4h has the arithmetic
  * operation by operation).
  * Planes as take_hip_denoise_device takes them, and the three of TakeAdaptiveStats as take_hip_render_adaptive_device
@@ -637,6 +637,117 @@ int take_hip_render_adaptive_denoised_device(TakeScene *scene, const TakeRenderO
 int take_hip_render_adaptive_denoised(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
                                       const TakeDenoiseOpts *denoise, void *rgb_out_host,
                                       const TakeAdaptiveStats *host_stats /* NULL ok */, void *variance_out_host /* NULL ok */);
+
+/* ---- temporal reprojection and accumulation (new symbols of ABI version 5; no struct changed): the temporal half of
+ * SVGF (Schied et al. 2017) — a frame of an animation starts from the samples of the frames before it, fetched through
+ * per-pixel motion vectors that only the scene can make (it alone knows the previous camera and placements), tested
+ * tap by tap and blended sample count by sample count.  EXTENSION without an upstream counterpart — parity unpinned
+ * with respect to the reference; specified against its own restatement (tests/temporal_ref.py; DESIGN.md par. 4i has the
+ * arithmetic operation by operation).  No trained weights; deterministic.
+ *
+ * take_hip_scene_mark_frame: stores "the previous frame" in the handle — the current camera of every resident side and,
+ * in a two-level scene, a device copy of the placements' current object -> world transforms (12 doubles each, as
+ * take_hip_scene_set_instance_transforms takes them).  A later mark replaces the earlier one;
+ * take_hip_scene_set_camera, _set_instance_transforms, _set_mesh_vertices and _update_meshes leave it alone (the
+ * placement count cannot change under them).  TAKE_E_INVALID: a NULL scene ("null argument", before a device is
+ * looked for).  Not for scene groups. */
+int take_hip_scene_mark_frame(TakeScene *scene);
+
+/* The motion pass: ONE ray per pixel through the pixel's centre (the camera ray of a render with 0.5 in place of the
+ * two jitter draws), made by the closest-hit launch that traces it, then one streaming kernel.  Of the options only
+ * ray_epsilon is read; the pass always covers the whole image (as take_hip_render_denoised_device); a MIXED scene uses
+ * its f64 side (as the feature pass).  Per pixel, in the side's Real, every + - * / sqrt one operation in this order,
+ * dot products (a.x * b.x + a.y * b.y) + a.z * b.z, a 3 x 4 map applied row by row as ((m0 * x + m1 * y) + m2 * z) + m3:
+ *   a hit at t:  P = o + d * t;  in placement i:  P' = M_i(marked) * (inv_i(current) * P) with the marked transform's
+ *     doubles rounded to Real, otherwise P' = P (a vertex that moved since the mark is not followed: the surface counts
+ *     as rigid in its mesh; the validity tests of the accumulation reject what no longer matches);  e = P' - lookfrom';
+ *   a miss:  e = d (a point at infinity), depth = prev_depth = 0, shape_id = -1 — a static camera keeps its background
+ *     history, a rotating one moves it;
+ *   with the MARKED camera (u', v', w', lookfrom', viewport'):  z = -(w' . e);  z <= 0: prev_xy = (-2, -2), prev_depth =
+ *     0;  otherwise sx = ((u' . e) / z / viewport_width' + 0.5) * width,  sy = ((v' . e) / z / viewport_height' + 0.5) *
+ *     height,  prev_xy = (sx, height - sy),  prev_depth = |e| = sqrt(e . e) for a hit.
+ * A render, a progressive sequence and the feature planes afterwards are what they were before; the counters are the
+ * pass's own (samples = pixels).
+ * TAKE_E_INVALID: a NULL scene, opts or buffers ("null argument"), all four pointers NULL — both before a device is
+ * looked for —, no marked frame (the message says so); a failed call leaves the scene as it was.  Not for scene groups. */
+typedef struct TakeMotionBuffers { /* every pointer may be NULL = not wanted; planes height * width, row 0 = top */
+    void *prev_xy;      /* 2 Real: where this pixel's surface point was in the marked frame, in plane coordinates
+                           (column, row), a pixel's centre at +0.5; (-2, -2) = nowhere */
+    void *prev_depth;   /* Real: the distance of that point from the marked camera's lookfrom (0 for a miss) */
+    void *depth;        /* Real: t of this frame's centre ray (0 for a miss) */
+    int32_t *shape_id;  /* the centre ray's hit, numbered as the trace hooks number it; -1 = miss */
+} TakeMotionBuffers;
+/* d_out: pointers to device memory; enqueued on `stream`, returns after it has completed */
+int take_hip_render_motion_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeMotionBuffers *d_out, void *stream);
+/* host_out: pointers to host memory */
+int take_hip_render_motion(TakeScene *scene, const TakeRenderOpts *opts, const TakeMotionBuffers *host_out);
+
+/* Accumulate: needs no scene (as take_hip_denoise_device).  Real = float or double by `precision`; the footprint, the
+ * weights, the depth test and the colour are Real, the moments and the history length double (with (double)w and
+ * (double)W); every + - * / is one operation in the order written; depth_tol is rounded to Real once.
+ * Per pixel p, with (px, py) = prev_xy(p):  fx = px - 0.5, x0 = floor(fx), tx = fx - x0, the same for y;  the taps q =
+ * (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in this order with weights w = (1 - tx) * (1 - ty), tx * (1 - ty),
+ * (1 - tx) * ty, tx * ty.  A tap counts only if its weight is > 0, it is inside the image, count_h(q) > 0, where both
+ * frames have ids shape_id_h(q) == shape_id_cur(p), and where the history has a depth plane and prev_depth is given
+ * |depth_h(q) - prev_depth(p)| <= depth_tol * prev_depth(p).  W = the sum of the weights that count (every sum below
+ * runs over the taps that count, in tap order).  W == 0 (a prev_xy that is not a number among the cases), or no
+ * history: the output is the current frame bit for bit.  Otherwise, with c = count_cur(p) and n_h(q) = count_h(q):
+ *   rgb_h = sum(w * rgb_h(q)) / W;  a_h = sum(w * (m1_h(q) / n_h(q))) / W;  b_h = sum(w * (m2_h(q) / n_h(q))) / W;
+ *   n_r = sum(w * n_h(q)) / W;  n_h = min((int32)floor(n_r + 0.5), max_history);  n = n_h + c;
+ *   rgb = (rgb_h * n_h + rgb_cur * c) / n;  m1 = a_h * n_h + m1_cur;  m2 = b_h * n_h + m2_cur;  count = n;
+ * the output's depth and shape_id (where given, and the current frame has them) are the current frame's.
+ * The output is TakeAdaptiveStats-shaped: it goes into take_hip_denoise_variance* unchanged, where it reads as an
+ * adaptive render with larger counts, and it is the next frame's history; clamping n_h makes the blend exponential
+ * once a pixel carries max_history samples.  d_out must not alias d_hist (the taps gather); it may alias d_cur.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL d_cur / d_out / d_prev_xy or any of the two frames'
+ * rgb / count / m1 / m2 ("null argument"), an unknown precision, width or height <= 0, a flag bit, a depth_tol that is
+ * not finite, a history that is given but lacks one of rgb / count / m1 / m2. */
+typedef struct TakeTemporalFrame {   /* one frame's planes, height * width, row 0 = top */
+    void *rgb;                       /* 3 Real: the mean over `count` samples */
+    int32_t *count; double *m1, *m2; /* as TakeAdaptiveStats */
+    void *depth; int32_t *shape_id;  /* the centre-ray planes of the motion pass; each may be NULL = that test is off */
+} TakeTemporalFrame;
+typedef struct TakeTemporalOpts {
+    int32_t max_history; /* samples of history a pixel may carry; <= 0: 64 */
+    int32_t flags;       /* 0 */
+    double depth_tol;    /* relative; <= 0: 0.05 */
+} TakeTemporalOpts;
+/* the frames' planes, d_prev_xy and d_prev_depth: device memory; opts: NULL = defaults; enqueued on `stream`, returns
+ * after it has completed */
+int take_hip_temporal_accumulate_device(const TakeTemporalFrame *d_cur, const TakeTemporalFrame *d_hist /* NULL = none */,
+                                        const void *d_prev_xy, const void *d_prev_depth /* NULL ok */, int32_t precision, int32_t width,
+                                        int32_t height, const TakeTemporalOpts *opts, const TakeTemporalFrame *d_out, void *stream);
+/* the same with host pointers (upload, the same kernel, download) */
+int take_hip_temporal_accumulate(const TakeTemporalFrame *cur, const TakeTemporalFrame *hist /* NULL = none */, const void *prev_xy,
+                                 const void *prev_depth /* NULL ok */, int32_t precision, int32_t width, int32_t height,
+                                 const TakeTemporalOpts *opts, const TakeTemporalFrame *out);
+
+/* One frame of an animation: render the whole image adaptively, accumulate it onto the handle's history through the
+ * motion pass, filter the accumulated image with the accumulated statistics — all on the device, the history kept in
+ * the handle (two frames that alternate).  Specified as, and bit for bit equal to, the calls made by hand:
+ *   1. take_hip_render_adaptive_device;
+ *   2. restart == 0 and the handle has a history: take_hip_render_motion_device (all four planes), then
+ *      take_hip_temporal_accumulate_device of the frame (with the motion pass's depth and shape_id) against the history;
+ *      otherwise the frame is its own accumulation, its depth and shape_id the motion pass's (which then needs no mark:
+ *      by hand, take_hip_scene_mark_frame first);
+ *   3. the result becomes the handle's history;
+ *   4. take_hip_render_features_device at the effective min_spp (as take_hip_render_adaptive_denoised_device), then
+ *      take_hip_denoise_variance_device of the accumulated image with the accumulated count / m1 / m2 into d_out;
+ *   5. take_hip_scene_mark_frame.
+ * The caller changes opts->seed from frame to frame: a frame with the same seed is the same samples again, and pooling
+ * them adds nothing.  The first frame, and one with restart != 0, equals take_hip_render_adaptive_denoised_device.
+ * A call that fails before step 3 leaves the history and the mark as they were.  f32 scenes write float, f64 and MIXED
+ * scenes double.  Not for scene groups.
+ * TAKE_E_INVALID: a NULL scene, render options or output ("null argument"), what take_hip_render_adaptive_device refuses
+ * of the adaptive options, what take_hip_temporal_accumulate_device refuses of the temporal options, what
+ * take_hip_denoise_device refuses of the denoise options, in that order and before a device is looked for; then what
+ * the adaptive render refuses. */
+int take_hip_render_temporal_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
+                                    const TakeTemporalOpts *temporal, const TakeDenoiseOpts *denoise, int32_t restart, void *d_out,
+                                    void *stream);
+/* the same with host pointers */
+int take_hip_render_temporal(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
+                             const TakeTemporalOpts *temporal, const TakeDenoiseOpts *denoise, int32_t restart, void *rgb_out_host);
 
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,

@@ -34,6 +34,8 @@ EXPORTS = [
     "take_hip_denoise", "take_hip_denoise_device", "take_hip_render_denoised", "take_hip_render_denoised_device",
     "take_hip_render_adaptive", "take_hip_render_adaptive_device",
     "take_hip_denoise_variance", "take_hip_denoise_variance_device", "take_hip_render_adaptive_denoised", "take_hip_render_adaptive_denoised_device",
+    "take_hip_scene_mark_frame", "take_hip_render_motion", "take_hip_render_motion_device",
+    "take_hip_temporal_accumulate", "take_hip_temporal_accumulate_device", "take_hip_render_temporal", "take_hip_render_temporal_device",
 ]
 
 
@@ -81,7 +83,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -233,6 +235,92 @@ def denoise_variance_device(rgb, count, m1, m2, width, height, precision, out=No
     _check(lib().take_hip_denoise_variance_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), C.byref(stats), int(precision), int(width), int(height),
                                                   None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
                                                   C.c_void_p(_pointer(variance)), C.c_void_p(stream or 0)))
+
+
+TEMPORAL_PLANES = ("rgb", "count", "m1", "m2", "depth", "shape_id")
+
+
+def _temporal_opts(opts, kw):
+    """a TakeTemporalOpts, keywords of cdefs.temporal_opts, or neither (None: the library's defaults, a NULL pointer)"""
+    if kw and opts is not None:
+        raise ValueError("give opts or keywords, not both")
+    return D.temporal_opts(**kw) if kw else opts
+
+
+def _temporal_frame(name, f, dtype, shape, keep):
+    """{plane: host array} -> TakeTemporalFrame over contiguous arrays (kept alive in `keep`); rgb fixes dtype and shape"""
+    unknown = set(f) - set(TEMPORAL_PLANES)
+    if unknown:
+        raise ValueError(f"{name}: unknown plane {sorted(unknown)[0]!r}: one of {TEMPORAL_PLANES}")
+    h, w = shape
+    want = {"rgb": (dtype, (h, w, 3)), "count": (np.int32, (h, w)), "m1": (np.float64, (h, w)), "m2": (np.float64, (h, w)),
+            "depth": (dtype, (h, w)), "shape_id": (np.int32, (h, w))}
+    out = D.TakeTemporalFrame()
+    for k in TEMPORAL_PLANES:
+        a = f.get(k)
+        if a is None:
+            if k in ("rgb", "count", "m1", "m2"):
+                raise ValueError(f"{name}: {k} is required")
+            continue
+        a = np.ascontiguousarray(a)
+        if a.dtype != want[k][0] or a.shape != want[k][1]:
+            raise ValueError(f"{name}: {k} must be a {want[k][1]} {np.dtype(want[k][0]).name} array")
+        keep.append(a)
+        setattr(out, k, a.ctypes.data)
+    return out
+
+
+def temporal_accumulate(cur, hist, prev_xy, prev_depth=None, opts=None, **kw):
+    """temporal accumulation on host arrays (take_hip_temporal_accumulate, include/take_hip.h): cur and hist are
+    {"rgb": (H, W, 3) float32 or float64 — cur's dtype picks the precision —, "count": int32 (H, W), "m1", "m2": float64
+    (H, W), and optionally "depth": (H, W) of rgb's dtype, "shape_id": int32 (H, W)}; hist = None: no history.  prev_xy
+    (H, W, 2) and the optional prev_depth (H, W), of rgb's dtype, as Scene.render_motion leaves them -> the accumulated
+    frame, a dict of the same planes (depth and shape_id where cur has them).  Options: keywords of cdefs.temporal_opts
+    (max_history, depth_tol), or opts = a TakeTemporalOpts; neither = the library's defaults (a NULL pointer)."""
+    rgb = np.asarray(cur.get("rgb") if isinstance(cur, dict) else None)
+    if rgb.dtype not in (np.float32, np.float64) or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("cur['rgb'] must be a (H, W, 3) float32 or float64 array")
+    h, w = rgb.shape[:2]
+    keep = []
+    c = _temporal_frame("cur", cur, rgb.dtype, (h, w), keep)
+    hf = None if hist is None else _temporal_frame("hist", hist, rgb.dtype, (h, w), keep)
+    xy = None if prev_xy is None else np.ascontiguousarray(prev_xy)
+    if xy is None or xy.dtype != rgb.dtype or xy.shape != (h, w, 2):
+        raise ValueError(f"prev_xy must be a {(h, w, 2)} array of rgb's dtype")
+    pd = None if prev_depth is None else np.ascontiguousarray(prev_depth)
+    if pd is not None and (pd.dtype != rgb.dtype or pd.shape != (h, w)):
+        raise ValueError(f"prev_depth must be a {(h, w)} array of rgb's dtype")
+    opts = _temporal_opts(opts, kw)
+    out = {"rgb": np.zeros_like(rgb), "count": np.zeros((h, w), np.int32), "m1": np.zeros((h, w)), "m2": np.zeros((h, w))}
+    if cur.get("depth") is not None:
+        out["depth"] = np.zeros((h, w), rgb.dtype)
+    if cur.get("shape_id") is not None:
+        out["shape_id"] = np.zeros((h, w), np.int32)
+    o = D.TakeTemporalFrame(*[out[k].ctypes.data if k in out else None for k in TEMPORAL_PLANES])
+    precision = D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64
+    _check(lib().take_hip_temporal_accumulate(C.byref(c), None if hf is None else C.byref(hf), xy.ctypes.data, None if pd is None else pd.ctypes.data,
+                                              precision, w, h, None if opts is None else C.byref(opts), C.byref(o)))
+    return out
+
+
+def temporal_accumulate_device(cur, hist, prev_xy, prev_depth, width, height, precision, out=None, opts=None, stream=None, **kw):
+    """the same on planes in device memory (take_hip_temporal_accumulate_device): cur, hist (or None) and out are
+    {plane: torch device tensor or integer device pointer}, prev_xy and prev_depth (or None) tensors or pointers, of
+    `precision`'s Real (count and shape_id int32, m1 and m2 float64); out = None accumulates into cur's planes (out must
+    never be hist: the taps gather); blocks until done.  Needs no scene."""
+    def frame(name, f):
+        unknown = set(f) - set(TEMPORAL_PLANES)
+        if unknown:
+            raise ValueError(f"{name}: unknown plane {sorted(unknown)[0]!r}: one of {TEMPORAL_PLANES}")
+        return D.TakeTemporalFrame(*[_pointer(f.get(k)) for k in TEMPORAL_PLANES])
+
+    c = frame("cur", cur)
+    hf = None if hist is None else frame("hist", hist)
+    o = c if out is None else frame("out", out)
+    opts = _temporal_opts(opts, kw)
+    _check(lib().take_hip_temporal_accumulate_device(C.byref(c), None if hf is None else C.byref(hf), C.c_void_p(_pointer(prev_xy)), C.c_void_p(_pointer(prev_depth)),
+                                                     int(precision), int(width), int(height), None if opts is None else C.byref(opts), C.byref(o),
+                                                     C.c_void_p(stream or 0)))
 
 
 class DeviceMesh:
@@ -546,6 +634,65 @@ class Scene:
         _check(lib().take_hip_render_adaptive_denoised_device(self.h, C.byref(o), None if a is None else C.byref(a), None if opts is None else C.byref(opts),
                                                               C.c_void_p(_pointer(d_ptr)), None if st is None else C.byref(st), C.c_void_p(_pointer(variance)),
                                                               C.c_void_p(stream or 0)))
+
+    def mark_frame(self):
+        """store "the previous frame" in the handle (take_hip_scene_mark_frame): the current camera and, in a two-level
+        scene, the placements' current transforms — what render_motion takes surface points back to"""
+        _check(lib().take_hip_scene_mark_frame(self.h))
+
+    def render_motion(self, ray_epsilon=0.0, want=tuple(D.MOTION_PLANES)):
+        """the motion pass against the marked frame (take_hip_render_motion) -> {name: host array} for the names in
+        `want`: prev_xy (H, W, 2), prev_depth and depth (H, W) in the scene's Real, shape_id (H, W) int32; row 0 = top"""
+        o = self._opts(1, 0, 0, ray_epsilon, 0, 1, 0)
+        out, bufs = {}, D.TakeMotionBuffers()
+        for name in want:
+            if name not in D.MOTION_PLANES:
+                raise ValueError(f"unknown motion plane {name!r}: one of {tuple(D.MOTION_PLANES)}")
+            per_pixel, real = D.MOTION_PLANES[name]
+            out[name] = np.zeros((self.sd.height, self.sd.width) + ((per_pixel,) if per_pixel > 1 else ()), self.dtype if real else np.int32)
+            setattr(bufs, name, out[name].ctypes.data)
+        _check(lib().take_hip_render_motion(self.h, C.byref(o), C.byref(bufs)))
+        return out
+
+    def render_motion_device(self, ptrs, ray_epsilon=0.0, stream=None):
+        """the same into device memory (take_hip_render_motion_device); ptrs: {name: torch device tensor or integer device
+        pointer} for the planes wanted — contiguous, of the scene's Real (int32 for shape_id); blocks until done"""
+        o = self._opts(1, 0, 0, ray_epsilon, 0, 1, 0)
+        bufs = D.TakeMotionBuffers()
+        for name, p in ptrs.items():
+            if name not in D.MOTION_PLANES:
+                raise ValueError(f"unknown motion plane {name!r}: one of {tuple(D.MOTION_PLANES)}")
+            setattr(bufs, name, _pointer(p))
+        _check(lib().take_hip_render_motion_device(self.h, C.byref(o), C.byref(bufs), C.c_void_p(stream or 0)))
+
+    def render_temporal(self, spp=None, max_depth=None, seed=0, restart=False, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, adaptive="keywords",
+                        temporal=None, ray_epsilon=0.0, samples_per_batch=0, integrator=0, opts=None, **kw):
+        """one frame of an animation (take_hip_render_temporal): render adaptively, accumulate onto the handle's history
+        through the motion pass, filter with the accumulated statistics, mark the frame -> (H, W, 3) host array.  Equal
+        bit for bit to render_adaptive + render_motion + temporal_accumulate + render_features + denoise_variance +
+        mark_frame made by hand.  Change `seed` from frame to frame.  restart=True: drop the history.  Sampler options as
+        render_adaptive takes them; temporal: a TakeTemporalOpts or None = the defaults; denoise options as
+        render_adaptive_denoised takes them."""
+        spp = self.sd.spp if spp is None else spp
+        max_depth = self.sd.max_depth if max_depth is None else max_depth
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
+        opts = _denoise_opts(opts, kw)
+        out = np.zeros((self.sd.height, self.sd.width, 3), self.dtype)
+        _check(lib().take_hip_render_temporal(self.h, C.byref(o), None if a is None else C.byref(a), None if temporal is None else C.byref(temporal),
+                                              None if opts is None else C.byref(opts), 1 if restart else 0, out.ctypes.data))
+        return out
+
+    def render_temporal_device(self, d_ptr, spp, max_depth, seed=0, restart=False, min_spp=0, step_spp=0, threshold=-1.0, floor=0.0, adaptive="keywords",
+                               temporal=None, ray_epsilon=0.0, samples_per_batch=0, stream=None, integrator=0, opts=None, **kw):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; H * W * 3 of the
+        scene's Real); blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
+        opts = _denoise_opts(opts, kw)
+        _check(lib().take_hip_render_temporal_device(self.h, C.byref(o), None if a is None else C.byref(a), None if temporal is None else C.byref(temporal),
+                                                     None if opts is None else C.byref(opts), 1 if restart else 0, C.c_void_p(_pointer(d_ptr)),
+                                                     C.c_void_p(stream or 0)))
 
     def set_instance_transforms(self, xforms, stream=None):
         """new object -> world transforms for ALL placements of a two-level scene, (n, 3, 4) float64 in the order of the

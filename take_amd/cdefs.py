@@ -194,6 +194,49 @@ DENOISE_VARIANCE_PROTOTYPES = {
 }
 
 
+class TakeMotionBuffers(C.Structure):
+    """take_hip_render_motion*: one pointer per plane (host or device memory), None = not wanted"""
+    _fields_ = [("prev_xy", C.c_void_p), ("prev_depth", C.c_void_p), ("depth", C.c_void_p), ("shape_id", C.c_void_p)]
+
+
+# name -> (values per pixel, True = the scene's Real / False = int32)
+MOTION_PLANES = {"prev_xy": (2, True), "prev_depth": (1, True), "depth": (1, True), "shape_id": (1, False)}
+
+
+class TakeTemporalFrame(C.Structure):
+    """take_hip_temporal_accumulate*: one frame's planes (host or device memory); depth and shape_id may be None"""
+    _fields_ = [("rgb", C.c_void_p), ("count", C.c_void_p), ("m1", C.c_void_p), ("m2", C.c_void_p), ("depth", C.c_void_p), ("shape_id", C.c_void_p)]
+
+
+class TakeTemporalOpts(C.Structure):
+    """a field that is not positive takes its default (max_history 64, depth_tol 0.05); flags: 0"""
+    _fields_ = [("max_history", C.c_int32), ("flags", C.c_int32), ("depth_tol", C.c_double)]
+
+
+TEMPORAL_DEFAULTS = {"max_history": 64, "depth_tol": 0.05}
+
+
+def temporal_opts(max_history=0, depth_tol=0.0):
+    """-> TakeTemporalOpts; what is left out takes the library's default"""
+    return TakeTemporalOpts(int(max_history), 0, float(depth_tol))
+
+
+# temporal reprojection and accumulation (include/take_hip.h): name -> argument types
+TEMPORAL_PROTOTYPES = {
+    "take_hip_scene_mark_frame": [C.c_void_p],
+    "take_hip_render_motion_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeMotionBuffers), C.c_void_p],
+    "take_hip_render_motion": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeMotionBuffers)],
+    "take_hip_temporal_accumulate_device": [C.POINTER(TakeTemporalFrame), C.POINTER(TakeTemporalFrame), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(TakeTemporalOpts), C.POINTER(TakeTemporalFrame), C.c_void_p],
+    "take_hip_temporal_accumulate": [C.POINTER(TakeTemporalFrame), C.POINTER(TakeTemporalFrame), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(TakeTemporalOpts), C.POINTER(TakeTemporalFrame)],
+    "take_hip_render_temporal_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.POINTER(TakeTemporalOpts), C.POINTER(TakeDenoiseOpts),
+                                        C.c_int32, C.c_void_p, C.c_void_p],
+    "take_hip_render_temporal": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeAdaptiveOpts), C.POINTER(TakeTemporalOpts), C.POINTER(TakeDenoiseOpts),
+                                 C.c_int32, C.c_void_p],
+}
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

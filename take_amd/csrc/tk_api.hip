@@ -353,6 +353,51 @@ int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
     return TAKE_OK;
 }
 
+// "The previous frame" of the temporal accumulation (include/take_hip.h): every side's camera and a copy of the
+// placements' current transforms.  The copy is made first: a failed call leaves the earlier mark whole.
+int take_hip_scene_mark_frame(TakeScene *ts) {
+    if (!ts) return fail(TAKE_E_INVALID, "null argument");
+    TAKE_ON_DEVICE(ts);
+    DevBuf<double> copy;
+    if (ts->n_placements > 0) {
+        if (!ts->xforms.p || (int64_t)ts->xforms.n != 12 * ts->n_placements) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group");
+        if (copy.alloc(ts->xforms.n) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the marked frame's transforms");
+        HIP_TRY(hipMemcpy(copy.p, ts->xforms.p, copy.bytes(), hipMemcpyDeviceToDevice));
+    }
+    ts->mark.xforms = std::move(copy);
+    ts->mark.cam_f = ts->f.dev.cam, ts->mark.cam_d = ts->d.dev.cam;  // (a side the scene does not have: never read)
+    ts->mark.set = true;
+    return TAKE_OK;
+}
+
+// The motion pass (where every pixel's surface point was in the marked frame): tk_render.hip, motion_impl.
+static int check_motion_args(const TakeScene *ts, const TakeRenderOpts *opts, const TakeMotionBuffers *b) {
+    if (!ts || !opts || !b) return fail(TAKE_E_INVALID, "null argument");
+    if (!b->prev_xy && !b->prev_depth && !b->depth && !b->shape_id)
+        return fail(TAKE_E_INVALID, "no motion buffer was asked for: every pointer of TakeMotionBuffers is NULL");
+    return TAKE_OK;
+}
+int take_hip_render_motion_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeMotionBuffers *d_out, void *stream) {
+    if (int rc = check_motion_args(ts, opts, d_out)) return rc;
+    TAKE_ON_DEVICE(ts);
+    return render_motion_scene(ts, *opts, *d_out, true, (hipStream_t)stream);
+}
+int take_hip_render_motion(TakeScene *ts, const TakeRenderOpts *opts, const TakeMotionBuffers *host_out) {
+    if (int rc = check_motion_args(ts, opts, host_out)) return rc;
+    TAKE_ON_DEVICE(ts);
+    const size_t npix = (size_t)ts->width() * ts->height(), real = ts->f64() ? 8 : 4;
+    // the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
+    const std::pair<void *, size_t> planes[4] = {{host_out->prev_xy, 2 * real}, {host_out->prev_depth, real}, {host_out->depth, real}, {host_out->shape_id, 4}};
+    DevBuf<char> d_plane[4];
+    for (int k = 0; k < 4; k++)
+        if (planes[k].first && d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the motion buffers");
+    const TakeMotionBuffers d_out{d_plane[0].p, d_plane[1].p, d_plane[2].p, (int32_t *)d_plane[3].p};
+    if (int rc = render_motion_scene(ts, *opts, d_out, true, nullptr)) return rc;
+    for (int k = 0; k < 4; k++)
+        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
 int take_hip_get_counters(const TakeScene *ts, TakeCounters *out) {
     if (!ts || !out) return fail(TAKE_E_INVALID, "null argument");
     *out = ts->counters;

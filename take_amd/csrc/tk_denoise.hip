@@ -3,7 +3,8 @@
 // only unit that compiles the kernels of tk_denoise.h and tk_denoise_var.h.  The scene-free calls need no scene (as
 // take_hip_pack_exr_scanlines does not) and allocate their working images per call; the scene-bound ones render, make
 // the feature planes and filter on the device, with planes and working images in the handle's RenderWorkspace — they
-// are the three public calls made by hand, through the same functions.
+// are the three public calls made by hand, through the same functions.  Also the temporal accumulation
+// (take_hip_temporal_accumulate*, take_hip_render_temporal*: the kernel of tk_temporal.h), which feeds the same filter.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "tk_scene_handle.h"
 #include "tk_denoise.h"
 #include "tk_denoise_var.h"
+#include "tk_temporal.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -126,6 +128,63 @@ int check_adaptive_denoised_args(const TakeScene *ts, const TakeRenderOpts *ropt
                                  DenoiseOpts &o) {
     if (!ts || !ropts || !out) return fail(TAKE_E_INVALID, "null argument");
     if (int rc = check_adaptive_opts(aopts)) return rc;
+    return resolve(dopts, o, SIGMA_COLOR_VARIANCE);
+}
+
+// ---- temporal accumulation (tk_temporal.h)
+// TakeTemporalOpts with the defaults filled in
+struct TemporalOpts {
+    int max_history = 64;
+    double depth_tol = 0.05;
+};
+int resolve_temporal(const TakeTemporalOpts *o, TemporalOpts &r) {
+    r = TemporalOpts{};
+    if (!o) return TAKE_OK;
+    if (o->flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
+    if (!std::isfinite(o->depth_tol)) return fail(TAKE_E_INVALID, "depth_tol must be finite");
+    if (o->max_history > 0) r.max_history = o->max_history;
+    if (o->depth_tol > 0) r.depth_tol = o->depth_tol;
+    return TAKE_OK;
+}
+// what the scene-free calls refuse, before a device is looked for
+int check_temporal_args(const TakeTemporalFrame *cur, const TakeTemporalFrame *hist, const void *prev_xy, int32_t precision, int32_t width, int32_t height,
+                        const TakeTemporalOpts *opts, const TakeTemporalFrame *out, TemporalOpts &o) {
+    if (!cur || !out || !prev_xy || !cur->rgb || !cur->count || !cur->m1 || !cur->m2 || !out->rgb || !out->count || !out->m1 || !out->m2)
+        return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_image(precision, width, height)) return rc;
+    if (int rc = resolve_temporal(opts, o)) return rc;
+    if (hist && (!hist->rgb || !hist->count || !hist->m1 || !hist->m2)) return fail(TAKE_E_INVALID, "incomplete history: rgb, count, m1 and m2 are all required");
+    return TAKE_OK;
+}
+template <class R> tp::Frame<R> typed(const TakeTemporalFrame &f) { return {(R *)f.rgb, f.count, f.m1, f.m2, (R *)f.depth, f.shape_id}; }
+// One launch, enqueued on `stream`, no synchronisation.  hist: null = none (the output is the current frame).
+template <class R>
+int temporal_enqueue(const tp::Frame<R> &cur, const tp::Frame<R> *hist, const R *prev_xy, const R *prev_depth, int32_t width, int32_t height, const TemporalOpts &o,
+                     const tp::Frame<R> &out, hipStream_t stream) {
+    tp::Params<R> P{};
+    P.width = width, P.height = height, P.max_history = o.max_history, P.has_history = hist ? 1 : 0, P.depth_tol = (R)o.depth_tol;
+    const dim3 grid((unsigned)((width + tp::TP_BX - 1) / tp::TP_BX), (unsigned)std::min((height + tp::TP_BY - 1) / tp::TP_BY, 65535)), block(tp::TP_BX, tp::TP_BY);
+    hipLaunchKernelGGL((tp::k_temporal_accumulate<R>), grid, block, 0, stream, P, cur, hist ? *hist : tp::Frame<R>{}, prev_xy, prev_depth, out);
+    HIP_TRY(hipGetLastError());
+    return TAKE_OK;
+}
+
+// take_hip_render_temporal*: a frame in one of the handle's buffers — m1, m2, then rgb and depth, then count and
+// shape_id (every plane aligned for its type whatever the pixel count); the current frame's buffer goes on with prev_xy
+// and prev_depth
+template <class R> constexpr int64_t temporal_frame_bytes() { return 16 + 4 * (int64_t)sizeof(R) + 8; }
+template <class R> tp::Frame<R> frame_at(double *base, int64_t npix) {
+    double *m1 = base, *m2 = m1 + npix;
+    R *rgb = (R *)(m2 + npix), *depth = rgb + 3 * npix;
+    int32_t *count = (int32_t *)(depth + npix), *shape_id = count + npix;
+    return {rgb, count, m1, m2, depth, shape_id};
+}
+// what the scene-bound temporal calls refuse, before a device is looked for: the adaptive part's, the temporal part's, the denoiser's
+int check_render_temporal_args(const TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeTemporalOpts *topts,
+                               const TakeDenoiseOpts *dopts, const void *out, TemporalOpts &t, DenoiseOpts &o) {
+    if (!ts || !ropts || !out) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_adaptive_opts(aopts)) return rc;
+    if (int rc = resolve_temporal(topts, t)) return rc;
     return resolve(dopts, o, SIGMA_COLOR_VARIANCE);
 }
 }  // namespace
@@ -305,6 +364,132 @@ int take_hip_render_adaptive_denoised(TakeScene *ts, const TakeRenderOpts *ropts
     if (int rc = take_hip_render_adaptive_denoised_device(ts, ropts, aopts, dopts, d_plane[0].p, &d_stats, d_plane[4].p, nullptr)) return rc;
     for (int k = 0; k < 5; k++)
         if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+int take_hip_temporal_accumulate_device(const TakeTemporalFrame *d_cur, const TakeTemporalFrame *d_hist, const void *d_prev_xy, const void *d_prev_depth,
+                                        int32_t precision, int32_t width, int32_t height, const TakeTemporalOpts *opts, const TakeTemporalFrame *d_out, void *stream) {
+    TemporalOpts o;
+    if (int rc = check_temporal_args(d_cur, d_hist, d_prev_xy, precision, width, height, opts, d_out, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    int rc;
+    if (precision == TAKE_PRECISION_F64) {
+        const tp::Frame<double> hist = d_hist ? typed<double>(*d_hist) : tp::Frame<double>{};
+        rc = temporal_enqueue(typed<double>(*d_cur), d_hist ? &hist : nullptr, (const double *)d_prev_xy, (const double *)d_prev_depth, width, height, o,
+                              typed<double>(*d_out), (hipStream_t)stream);
+    } else {
+        const tp::Frame<float> hist = d_hist ? typed<float>(*d_hist) : tp::Frame<float>{};
+        rc = temporal_enqueue(typed<float>(*d_cur), d_hist ? &hist : nullptr, (const float *)d_prev_xy, (const float *)d_prev_depth, width, height, o,
+                              typed<float>(*d_out), (hipStream_t)stream);
+    }
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return TAKE_OK;
+}
+
+int take_hip_temporal_accumulate(const TakeTemporalFrame *cur, const TakeTemporalFrame *hist, const void *prev_xy, const void *prev_depth, int32_t precision,
+                                 int32_t width, int32_t height, const TakeTemporalOpts *opts, const TakeTemporalFrame *out) {
+    TemporalOpts o;
+    if (int rc = check_temporal_args(cur, hist, prev_xy, precision, width, height, opts, out, o)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
+    // the planes of a frame: bytes per pixel, in the order of TakeTemporalFrame's members
+    const size_t per_pixel[6] = {3 * real, 4, 8, 8, real, 4};
+    auto members = [](const TakeTemporalFrame &f, void *m[6]) { m[0] = f.rgb, m[1] = f.count, m[2] = f.m1, m[3] = f.m2, m[4] = f.depth, m[5] = f.shape_id; };
+    // the current frame (accumulated in place) and the history, uploaded; then the motion planes
+    DevBuf<char> d_cur[6], d_hist[6], d_xy, d_pd;
+    void *h_cur[6], *h_hist[6] = {}, *h_out[6];
+    members(*cur, h_cur), members(*out, h_out);
+    if (hist) members(*hist, h_hist);
+    for (int k = 0; k < 6; k++)
+        for (int which = 0; which < 2; which++) {
+            const void *src = which ? h_hist[k] : h_cur[k];
+            DevBuf<char> &dst = which ? d_hist[k] : d_cur[k];
+            if (!src) continue;
+            if (dst.alloc(npix * per_pixel[k]) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the temporal accumulation's planes");
+            HIP_TRY(hipMemcpy(dst.p, src, dst.bytes(), hipMemcpyHostToDevice));
+        }
+    if (d_xy.alloc(npix * 2 * real) != hipSuccess || (prev_depth && d_pd.alloc(npix * real) != hipSuccess))
+        return fail(TAKE_E_NOMEM, "out of device memory for the temporal accumulation's planes");
+    HIP_TRY(hipMemcpy(d_xy.p, prev_xy, d_xy.bytes(), hipMemcpyHostToDevice));
+    if (prev_depth) HIP_TRY(hipMemcpy(d_pd.p, prev_depth, d_pd.bytes(), hipMemcpyHostToDevice));
+    const TakeTemporalFrame dc{d_cur[0].p, (int32_t *)d_cur[1].p, (double *)d_cur[2].p, (double *)d_cur[3].p, d_cur[4].p, (int32_t *)d_cur[5].p};
+    const TakeTemporalFrame dh{d_hist[0].p, (int32_t *)d_hist[1].p, (double *)d_hist[2].p, (double *)d_hist[3].p, d_hist[4].p, (int32_t *)d_hist[5].p};
+    if (int rc = take_hip_temporal_accumulate_device(&dc, hist ? &dh : nullptr, d_xy.p, d_pd.p, precision, width, height, opts, &dc, nullptr)) return rc;
+    for (int k = 0; k < 6; k++)
+        if (h_out[k] && d_cur[k].p) HIP_TRY(hipMemcpy(h_out[k], d_cur[k].p, d_cur[k].bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+
+int take_hip_render_temporal_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeTemporalOpts *topts,
+                                    const TakeDenoiseOpts *dopts, int32_t restart, void *d_out, void *stream) {
+    TemporalOpts t;
+    DenoiseOpts o;
+    if (int rc = check_render_temporal_args(ts, ropts, aopts, topts, dopts, d_out, t, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    TakeRenderOpts ro = *ropts;
+    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_denoised_device
+    const int W = ts->width(), H = ts->height();
+    const int64_t npix = (int64_t)W * H;
+    const int rc = on_primary(ts, [&](auto &sc, auto &work) {
+        using R = std::remove_reference_t<decltype(*work.accum.p)>;
+        hipStream_t s = (hipStream_t)stream;
+        // the two accumulated frames and the current one with its motion planes (allocated once: the pixel count is the
+        // scene's), the filter's working images with albedo, normal and depth behind them
+        const size_t frame_doubles = (size_t)(temporal_frame_bytes<R>() * npix + 7) / 8, cur_doubles = (size_t)((temporal_frame_bytes<R>() + 3 * (int64_t)sizeof(R)) * npix + 7) / 8;
+        for (auto *b : {&work.temporal[0], &work.temporal[1]})
+            if (b->n < frame_doubles) {
+                ts->temporal_history = -1;  // (never taken: the buffers are sized by the first call)
+                if (b->alloc(frame_doubles) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the accumulated frames");
+            }
+        if (work.temporal_cur.n < cur_doubles && work.temporal_cur.alloc(cur_doubles) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the accumulated frames");
+        if (int rc = work.ensure_denoise((WORK_REALS + 7) * npix)) return rc;
+        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
+        const tp::Frame<R> cur = frame_at<R>(work.temporal_cur.p, npix);
+        R *prev_xy = (R *)(cur.shape_id + npix), *prev_depth = prev_xy + 2 * npix;
+        // 1. the frame
+        if (int rc = render_adaptive_scene(ts, ro, aopts, cur.rgb, TakeAdaptiveStats{cur.count, cur.m1, cur.m2}, s)) return rc;
+        // 2. onto the history, through the motion pass (without one: depth and ids only, against the frame itself)
+        const bool have = restart == 0 && ts->temporal_history >= 0 && ts->mark.set;
+        const int into = have ? 1 - ts->temporal_history : 0;
+        const tp::Frame<R> acc = frame_at<R>(work.temporal[into].p, npix);
+        const TakeMotionBuffers motion{have ? prev_xy : nullptr, have ? prev_depth : nullptr, cur.depth, cur.shape_id};
+        if (int rc = render_motion_scene(ts, ro, motion, have, s)) return rc;
+        if (have) {
+            const tp::Frame<R> hist = frame_at<R>(work.temporal[ts->temporal_history].p, npix);
+            if (int rc = temporal_enqueue(cur, &hist, (const R *)prev_xy, (const R *)prev_depth, W, H, t, acc, s)) return rc;
+        } else {
+            HIP_TRY(hipMemcpyAsync(work.temporal[into].p, work.temporal_cur.p, (size_t)(temporal_frame_bytes<R>() * npix), hipMemcpyDeviceToDevice, s));
+        }
+        // 3. the result is the history from here on
+        ts->temporal_history = into;
+        // 4. the guides, and the filter on the accumulated image with the accumulated statistics
+        TakeRenderOpts fo = ro;
+        fo.spp = adaptive_min_spp(ro, aopts);
+        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
+        if (int rc = render_features_scene(ts, fo, planes, s)) return rc;
+        if (int rc = denoise_var_enqueue((const R *)acc.rgb, (const R *)albedo, (const R *)normal, (const R *)depth, TakeAdaptiveStats{acc.count, acc.m1, acc.m2}, W, H, o,
+                                         work.denoise.p, (R *)d_out, (R *)nullptr, s))
+            return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        return (int)TAKE_OK;
+    });
+    // 5. this frame is the next one's previous frame
+    return rc ? rc : take_hip_scene_mark_frame(ts);
+}
+
+int take_hip_render_temporal(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeTemporalOpts *topts, const TakeDenoiseOpts *dopts,
+                             int32_t restart, void *rgb_out_host) {
+    TemporalOpts t;
+    DenoiseOpts o;
+    if (int rc = check_render_temporal_args(ts, ropts, aopts, topts, dopts, rgb_out_host, t, o)) return rc;
+    TAKE_ON_DEVICE(ts);
+    DevBuf<char> d_out;
+    if (d_out.alloc((size_t)ts->width() * ts->height() * 3 * (ts->f64() ? 8 : 4)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the filtered frame");
+    if (int rc = take_hip_render_temporal_device(ts, ropts, aopts, topts, dopts, restart, d_out.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
 

@@ -1,8 +1,8 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace's allocations, the kernel launchers,
 // the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
 // after them) and the calls that differ in between — the wavefront render loop, its adaptive twin (passes over the
-// pixels still active), the feature pass, the trace hooks.
-// The only unit that compiles the kernels of tk_kernels.h, tk_features.h and tk_adaptive.h (as tk_build.hip is for tk_build_gpu.h);
+// pixels still active), the feature pass, the motion pass, the trace hooks.
+// The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h and tk_adaptive.h (as tk_build.hip is for tk_build_gpu.h);
 // what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "tk_scene_handle.h"
 #include "tk_kernels.h"
 #include "tk_features.h"
+#include "tk_motion.h"
 #include "tk_adaptive.h"
 
 using namespace tk;
@@ -30,9 +31,12 @@ enum TimedKernel { TK_CLOSEST, TK_SHADOW, TK_SHADE, TK_OTHER, TK_CLOSEST_TAIL /*
 // The trace kernel instance for (scene's traversal, any-hit, counting, Io): fn(kernel, its block geometry).  The one
 // place that names an instance; the occupancy query, the launches and the spill size all come through here, so they
 // cannot disagree.  Instantiated: every node format (the 8-wide one with one ray per lane only) for PathIo and HookIo;
-// CameraIo for closest hits on compressed 4-wide nodes, not counting, only.  A combination outside that runs nothing: false.
+// CameraIo for closest hits on compressed 4-wide nodes, not counting, only; CentreCameraIo (the motion pass, which has
+// no generate pass to fall back on) for closest hits, not counting, on every node format.  A combination outside that
+// runs nothing: false.
 template <class R, bool ANY_HIT, bool COUNT, class Io, class Fn> bool with_trace_kernel(TraceKind kind, Fn &&fn) {
-    constexpr bool camera = std::is_same<Io, CameraIo<R>>::value;
+    constexpr bool centre = std::is_same<Io, CentreCameraIo<R>>::value;
+    constexpr bool camera = std::is_same<Io, CameraIo<R>>::value || (centre && (ANY_HIT || COUNT));
     auto pick = [&](auto qn, auto width) {
         constexpr bool QN = decltype(qn)::value;
         constexpr int W = decltype(width)::value;
@@ -712,6 +716,41 @@ int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
     return end_frame(fr, (uint64_t)npix * (uint64_t)o.spp);
 }
 
+// The motion pass of a scene (take_hip_render_motion*; contract: include/take_hip.h): one closest-hit launch over the
+// whole image that makes the centre rays itself (CentreCameraIo: the work list is the identity, no queue is read),
+// then k_motion over its records.  Path records and queue words only, as the feature pass: a progressive sequence goes
+// on afterwards.  marked / marked_xforms: the camera and the placements' transforms the points are taken back to.
+// The timer files k_motion under the shade class.
+template <class R>
+int motion_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &opts, const TakeMotionBuffers &b, const CameraRec<R> &marked,
+                const double *marked_xforms, hipStream_t stream) {
+    const MotionOut<R> out{(R *)b.prev_xy, (R *)b.prev_depth, (R *)b.depth, b.shape_id};
+    if (!out.prev_xy && !out.prev_depth && !out.depth && !out.shape_id)
+        return fail(TAKE_E_INVALID, "no motion buffer was asked for: every pointer of TakeMotionBuffers is NULL");
+    Frame<R> fr{ts, sc, work, stream};
+    TakeRenderOpts o{};  // (of the options only ray_epsilon is read: one sample per pixel, the whole image)
+    o.spp = 1, o.strip_first = 0, o.strip_stride = 1, o.ray_epsilon = opts.ray_epsilon;
+    if (const int rc = pick_strips(fr, o)) return rc;
+    int rc = begin_frame(fr, o, false);
+    const int64_t npix = fr.npix;
+    if (rc || npix == 0) return rc;
+    if ((rc = start_frame(fr))) return rc;
+    fr.rp.s0 = 0, fr.rp.spb = 1;
+    int32_t *q = work.qwords.p;
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, q, (int)Q_N_EXT0, (int32_t)npix);
+    hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, stream, q, 1);
+    fr.tm.begin(TK_CLOSEST);
+    CentreCameraIo<R> io;
+    static_cast<PathIo<R> &>(io) = PathIo<R>{sc.dev.prims, fr.st, work.queue[0].p, fr.rp.ray_eps};
+    io.cam = sc.dev.cam, io.rp = fr.rp;
+    HIP_TRY(launch_trace(sc, false, false, sc.trace_state.grid_for(npix), stream, io, q + Q_N_EXT0, 0, q + Q_HEAD_CLOSEST, work.counters.p, (int)C_RAYS_CLOSEST));
+    fr.tm.end();
+    fr.tm.begin(TK_SHADE);
+    hipLaunchKernelGGL((k_motion<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, marked, sc.dev.inst_trace ? marked_xforms : nullptr, out, fr.rp.width, fr.n_rows);
+    fr.tm.end();
+    return end_frame(fr, (uint64_t)npix);
+}
+
 template <class R>
 int trace_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const void *d_rays, int64_t n, void *d_hits, int32_t *d_occ, bool any,
                bool count, hipStream_t stream) {
@@ -877,6 +916,19 @@ int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdap
 int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a) { return make_rule(o, a).min_spp; }
 int render_features_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeFeatureBuffers &d_out, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return features_impl(ts, sc, work, o, d_out, stream); });
+}
+int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotionBuffers &d_out, bool marked, hipStream_t stream) {
+    if (marked && !ts->mark.set) return fail(TAKE_E_INVALID, "no marked frame: take_hip_scene_mark_frame has not been called on this scene");
+    return on_primary(ts, [&](auto &sc, auto &work) {
+        using R = std::remove_reference_t<decltype(*work.accum.p)>;
+        const CameraRec<R> *cam = &sc.dev.cam;
+        if constexpr (sizeof(R) == 8) { if (marked) cam = &ts->mark.cam_d; }
+        else { if (marked) cam = &ts->mark.cam_f; }
+        // (k_motion indexes the marked transforms with the hit's placement)
+        if (marked && sc.inst_trace.n > 0 && ts->mark.xforms.n != 12 * sc.inst_trace.n)
+            return fail(TAKE_E_INVALID, "unsupported: the marked frame does not have one transform per placement record (a scene built under TAKE_HIP_BRAID > 1)");
+        return motion_impl(ts, sc, work, o, d_out, *cam, marked ? ts->mark.xforms.p : nullptr, stream);
+    });
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     return on_primary(ts, [&](auto &sc, auto &work) { return trace_host(ts, sc, work, rays, n, hits, occ, any); });

@@ -160,6 +160,10 @@ template <class R> struct RenderWorkspace {
         if ((int64_t)denoise.n >= reals || denoise.alloc((size_t)reals) == hipSuccess) return TAKE_OK;
         return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's workspace");
     }
+    // take_hip_render_temporal*: two accumulated frames that alternate (the history, and the one being made from it:
+    // the taps gather, so a frame is never accumulated in place) and the current frame with its motion planes
+    // (tk_denoise.hip has the layout); allocated by the first call, no per-slot buffers, go with the handle
+    DevBuf<double> temporal[2], temporal_cur;
     // grows on demand as the denoiser's planes do, is no per-slot buffer and goes with the handle (defined in tk_render.hip)
     AdaptiveState adaptive;
     int ensure_adaptive(int64_t npix);
@@ -196,6 +200,15 @@ struct TakeScene {
     int max_leaf = 0;                     // the leaf size request the trees were built with (TakeBuildOpts / TAKE_HIP_MAX_LEAF)
     bool flattened = false;               // TAKE_INSTANCES_FLATTEN expanded placements: the meshes are no longer the caller's
     std::string node_knob;                // TAKE_HIP_NODES when the scene was built
+    // take_hip_scene_mark_frame: "the previous frame" — the camera of every resident side and, in a two-level scene, a
+    // copy of the placements' transforms (xforms) as they were then.  The changes of a resident scene leave it alone.
+    struct FrameMark {
+        bool set = false;
+        tk::CameraRec<float> cam_f{};
+        tk::CameraRec<double> cam_d{};
+        tk_host::DevBuf<double> xforms;
+    } mark;
+    int temporal_history = -1;  // take_hip_render_temporal*: which of the workspace's two accumulated frames is the history (-1: none)
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
     int instrumentation = 0;
     tk_host::SceneT<float> f;
@@ -287,6 +300,9 @@ int render_adaptive_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeAdap
 // the samples every pixel of an adaptive render of o.spp > 0 samples at most gets before the first test: a's min_spp
 // (null or <= 0: the default) clamped to o.spp
 int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a);
+// the motion pass (include/take_hip.h: take_hip_render_motion_device) into device memory, against the marked frame;
+// marked = false (take_hip_render_temporal_device's first frame, which wants depth and ids only): against the current one
+int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotionBuffers &d_out, bool marked, hipStream_t stream);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
 
