@@ -142,19 +142,17 @@ def _pointer(a):
     return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else int(a))
 
 
-def _denoise_opts(opts, kw):
-    """a TakeDenoiseOpts, keywords of cdefs.denoise_opts, or neither (None: the library's defaults, a NULL pointer)"""
+def _keyword_opts(make, opts, kw):
+    """an options struct, keywords of `make` (cdefs.denoise_opts, cdefs.temporal_opts), or neither (None: the library's
+    defaults, a NULL pointer)"""
     if kw and opts is not None:
         raise ValueError("give opts or keywords, not both")
-    return D.denoise_opts(**kw) if kw else opts
+    return make(**kw) if kw else opts
 
 
-def denoise(rgb, albedo=None, normal=None, depth=None, opts=None, **kw):
-    """the image-space denoiser on host arrays (take_hip_denoise: the edge-avoiding A-trous filter, include/take_hip.h):
-    rgb (H, W, 3) float32 or float64 — the dtype picks the precision —, the optional guides albedo and normal (H, W, 3)
-    and depth (H, W) in the same dtype -> the filtered (H, W, 3) image.  Options: keywords of cdefs.denoise_opts
-    (iterations, keep_albedo, sigma_color, sigma_normal, sigma_depth, albedo_floor), or opts = a TakeDenoiseOpts;
-    neither = the library's defaults (a NULL pointer)."""
+def _rgb_and_guides(rgb, albedo, normal, depth):
+    """host arrays as denoise() takes them -> (contiguous rgb, its TAKE_PRECISION_*, a TakeFeatureBuffers over the guides that
+    were given, the arrays it points into: empty = no guides)"""
     rgb = np.asarray(rgb)
     if rgb.dtype not in (np.float32, np.float64) or rgb.ndim != 3 or rgb.shape[2] != 3:
         raise ValueError("rgb must be a (H, W, 3) float32 or float64 array")
@@ -169,9 +167,19 @@ def denoise(rgb, albedo=None, normal=None, depth=None, opts=None, **kw):
             raise ValueError(f"{name} must be a {shape} array of rgb's dtype")
         keep.append(a)
         setattr(bufs, name, a.ctypes.data)
-    opts = _denoise_opts(opts, kw)
+    return rgb, D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64, bufs, keep
+
+
+def denoise(rgb, albedo=None, normal=None, depth=None, opts=None, **kw):
+    """the image-space denoiser on host arrays (take_hip_denoise: the edge-avoiding A-trous filter, include/take_hip.h):
+    rgb (H, W, 3) float32 or float64 — the dtype picks the precision —, the optional guides albedo and normal (H, W, 3)
+    and depth (H, W) in the same dtype -> the filtered (H, W, 3) image.  Options: keywords of cdefs.denoise_opts
+    (iterations, keep_albedo, sigma_color, sigma_normal, sigma_depth, albedo_floor), or opts = a TakeDenoiseOpts;
+    neither = the library's defaults (a NULL pointer)."""
+    rgb, precision, bufs, keep = _rgb_and_guides(rgb, albedo, normal, depth)
+    h, w = rgb.shape[:2]
+    opts = _keyword_opts(D.denoise_opts, opts, kw)
     out = np.zeros_like(rgb)
-    precision = D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64
     _check(lib().take_hip_denoise(rgb.ctypes.data, C.byref(bufs) if keep else None, precision, w, h,
                                   None if opts is None else C.byref(opts), out.ctypes.data))
     return out
@@ -182,7 +190,7 @@ def denoise_device(rgb, width, height, precision, out=None, albedo=None, normal=
     integer device pointers of `precision`'s Real (TAKE_PRECISION_F32 / _F64); out = None filters in place; blocks until
     done.  Needs no scene: also for what render_accumulate or a scene group left on the device."""
     bufs = D.TakeFeatureBuffers(_pointer(albedo), _pointer(normal), _pointer(depth), None, None, None)
-    opts = _denoise_opts(opts, kw)
+    opts = _keyword_opts(D.denoise_opts, opts, kw)
     _check(lib().take_hip_denoise_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), int(precision), int(width), int(height),
                                          None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
                                          C.c_void_p(stream or 0)))
@@ -194,20 +202,8 @@ def denoise_variance(rgb, count, m1, m2, albedo=None, normal=None, depth=None, v
     planes an adaptive render leaves (Scene.render_adaptive(stats=True)): count (H, W) int32, m1 and m2 (H, W) float64
     -> the filtered (H, W, 3) image; variance=True: -> (image, the filter's (H, W) estimate of the variance of the
     result's r + g + b, in rgb's dtype).  Options as denoise(), but sigma_color (default 4.0) counts standard deviations."""
-    rgb = np.asarray(rgb)
-    if rgb.dtype not in (np.float32, np.float64) or rgb.ndim != 3 or rgb.shape[2] != 3:
-        raise ValueError("rgb must be a (H, W, 3) float32 or float64 array")
+    rgb, precision, bufs, keep = _rgb_and_guides(rgb, albedo, normal, depth)
     h, w = rgb.shape[:2]
-    rgb = np.ascontiguousarray(rgb)
-    bufs, keep = D.TakeFeatureBuffers(), []
-    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a)
-        if a.dtype != rgb.dtype or a.shape != shape:
-            raise ValueError(f"{name} must be a {shape} array of rgb's dtype")
-        keep.append(a)
-        setattr(bufs, name, a.ctypes.data)
     stats, moments = D.TakeAdaptiveStats(), []
     for name, a, dtype in (("count", count, np.int32), ("m1", m1, np.float64), ("m2", m2, np.float64)):
         a = None if a is None else np.ascontiguousarray(a)
@@ -215,10 +211,9 @@ def denoise_variance(rgb, count, m1, m2, albedo=None, normal=None, depth=None, v
             raise ValueError(f"{name} must be a {(h, w)} {np.dtype(dtype).name} array")
         moments.append(a)
         setattr(stats, name, a.ctypes.data)
-    opts = _denoise_opts(opts, kw)
+    opts = _keyword_opts(D.denoise_opts, opts, kw)
     out = np.zeros_like(rgb)
     var = np.zeros((h, w), rgb.dtype) if variance else None
-    precision = D.TAKE_PRECISION_F32 if rgb.dtype == np.float32 else D.TAKE_PRECISION_F64
     _check(lib().take_hip_denoise_variance(rgb.ctypes.data, C.byref(bufs) if keep else None, C.byref(stats), precision, w, h,
                                            None if opts is None else C.byref(opts), out.ctypes.data, None if var is None else var.ctypes.data))
     return (out, var) if variance else out
@@ -231,27 +226,48 @@ def denoise_variance_device(rgb, count, m1, m2, width, height, precision, out=No
     m2 float64; out = None filters in place; blocks until done.  Needs no scene."""
     bufs = D.TakeFeatureBuffers(_pointer(albedo), _pointer(normal), _pointer(depth), None, None, None)
     stats = D.TakeAdaptiveStats(_pointer(count), _pointer(m1), _pointer(m2))
-    opts = _denoise_opts(opts, kw)
+    opts = _keyword_opts(D.denoise_opts, opts, kw)
     _check(lib().take_hip_denoise_variance_device(C.c_void_p(_pointer(rgb)), C.byref(bufs), C.byref(stats), int(precision), int(width), int(height),
                                                   None if opts is None else C.byref(opts), C.c_void_p(_pointer(rgb if out is None else out)),
                                                   C.c_void_p(_pointer(variance)), C.c_void_p(stream or 0)))
 
 
+STATS_PLANES = ("count", "m1", "m2")
+
+
+def _host_stats(shape):
+    """zeroed count / m1 / m2 host planes of `shape` -> ({name: array}, the TakeAdaptiveStats over them)"""
+    planes = {"count": np.zeros(shape, np.int32), "m1": np.zeros(shape, np.float64), "m2": np.zeros(shape, np.float64)}
+    return planes, D.TakeAdaptiveStats(*[planes[k].ctypes.data for k in STATS_PLANES])
+
+
+def _device_stats(stats):
+    """{"count" / "m1" / "m2": device tensor or pointer} for the planes wanted -> TakeAdaptiveStats; None or empty -> None"""
+    if not stats:
+        return None
+    unknown = set(stats) - set(STATS_PLANES)
+    if unknown:
+        raise ValueError(f"unknown statistics plane {sorted(unknown)[0]!r}: one of ('count', 'm1', 'm2')")
+    return D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in STATS_PLANES])
+
+
+def _adaptive_opts(opts, min_spp, step_spp, threshold, floor):
+    """opts = "keywords": the sampler's keywords as a TakeAdaptiveOpts; else opts itself (a TakeAdaptiveOpts, or None)"""
+    return D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(opts, str) else opts
+
+
 TEMPORAL_PLANES = ("rgb", "count", "m1", "m2", "depth", "shape_id")
 
 
-def _temporal_opts(opts, kw):
-    """a TakeTemporalOpts, keywords of cdefs.temporal_opts, or neither (None: the library's defaults, a NULL pointer)"""
-    if kw and opts is not None:
-        raise ValueError("give opts or keywords, not both")
-    return D.temporal_opts(**kw) if kw else opts
+def _known_temporal_planes(name, f):
+    unknown = set(f) - set(TEMPORAL_PLANES)
+    if unknown:
+        raise ValueError(f"{name}: unknown plane {sorted(unknown)[0]!r}: one of {TEMPORAL_PLANES}")
 
 
 def _temporal_frame(name, f, dtype, shape, keep):
     """{plane: host array} -> TakeTemporalFrame over contiguous arrays (kept alive in `keep`); rgb fixes dtype and shape"""
-    unknown = set(f) - set(TEMPORAL_PLANES)
-    if unknown:
-        raise ValueError(f"{name}: unknown plane {sorted(unknown)[0]!r}: one of {TEMPORAL_PLANES}")
+    _known_temporal_planes(name, f)
     h, w = shape
     want = {"rgb": (dtype, (h, w, 3)), "count": (np.int32, (h, w)), "m1": (np.float64, (h, w)), "m2": (np.float64, (h, w)),
             "depth": (dtype, (h, w)), "shape_id": (np.int32, (h, w))}
@@ -290,7 +306,7 @@ def temporal_accumulate(cur, hist, prev_xy, prev_depth=None, opts=None, **kw):
     pd = None if prev_depth is None else np.ascontiguousarray(prev_depth)
     if pd is not None and (pd.dtype != rgb.dtype or pd.shape != (h, w)):
         raise ValueError(f"prev_depth must be a {(h, w)} array of rgb's dtype")
-    opts = _temporal_opts(opts, kw)
+    opts = _keyword_opts(D.temporal_opts, opts, kw)
     out = {"rgb": np.zeros_like(rgb), "count": np.zeros((h, w), np.int32), "m1": np.zeros((h, w)), "m2": np.zeros((h, w))}
     if cur.get("depth") is not None:
         out["depth"] = np.zeros((h, w), rgb.dtype)
@@ -309,15 +325,13 @@ def temporal_accumulate_device(cur, hist, prev_xy, prev_depth, width, height, pr
     `precision`'s Real (count and shape_id int32, m1 and m2 float64); out = None accumulates into cur's planes (out must
     never be hist: the taps gather); blocks until done.  Needs no scene."""
     def frame(name, f):
-        unknown = set(f) - set(TEMPORAL_PLANES)
-        if unknown:
-            raise ValueError(f"{name}: unknown plane {sorted(unknown)[0]!r}: one of {TEMPORAL_PLANES}")
+        _known_temporal_planes(name, f)
         return D.TakeTemporalFrame(*[_pointer(f.get(k)) for k in TEMPORAL_PLANES])
 
     c = frame("cur", cur)
     hf = None if hist is None else frame("hist", hist)
     o = c if out is None else frame("out", out)
-    opts = _temporal_opts(opts, kw)
+    opts = _keyword_opts(D.temporal_opts, opts, kw)
     _check(lib().take_hip_temporal_accumulate_device(C.byref(c), None if hf is None else C.byref(hf), C.c_void_p(_pointer(prev_xy)), C.c_void_p(_pointer(prev_depth)),
                                                      int(precision), int(width), int(height), None if opts is None else C.byref(opts), C.byref(o),
                                                      C.c_void_p(stream or 0)))
@@ -459,6 +473,8 @@ class Scene:
             pass
 
     def _opts(self, spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator=0):
+        spp = self.sd.spp if spp is None else spp  # (None: the scene description's)
+        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = D.TakeRenderOpts()
         o.exact_bounces = int(getattr(self, "exact_bounces", 0))  # TAKE_PRECISION_MIXED scenes (0 = the library's default)
         o.spp, o.max_depth, o.seed, o.ray_epsilon = int(spp), int(max_depth), int(seed), float(ray_epsilon)
@@ -475,8 +491,6 @@ class Scene:
     def render(self, spp=None, max_depth=None, seed=0, ray_epsilon=0.0, strip_first=0, strip_stride=1,
                samples_per_batch=0, integrator=0):
         """-> (rows, W, 3) image rows owned by this strip set, top row first (host array)."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
         n = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
         out = np.zeros((n, self.sd.width, 3), self.dtype)
@@ -492,8 +506,6 @@ class Scene:
     def render_exr_scanlines(self, spp=None, max_depth=None, seed=0, samples_per_batch=0, integrator=0):
         """Render and convert on the device: -> uint16 (H, 3, W), per scanline the B, G, R halves of the reference's
         image.exr (take_amd.exr.write_exr_scanlines frames them into the file)."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, 0.0, 0, 1, samples_per_batch, integrator)
         out = np.zeros((self.sd.height, 3, self.sd.width), np.uint16)
         _check(lib().take_hip_render_exr_scanlines(self.h, C.byref(o), out.ctypes.data))
@@ -531,17 +543,15 @@ class Scene:
         for name, p in ptrs.items():
             if name not in D.FEATURE_PLANES:
                 raise ValueError(f"unknown feature plane {name!r}: one of {tuple(D.FEATURE_PLANES)}")
-            setattr(bufs, name, p.data_ptr() if hasattr(p, "data_ptr") else int(p))
+            setattr(bufs, name, _pointer(p))
         _check(lib().take_hip_render_features_device(self.h, C.byref(o), C.byref(bufs), C.c_void_p(stream or 0)))
 
     def render_denoised(self, spp=None, max_depth=None, seed=0, ray_epsilon=0.0, samples_per_batch=0, integrator=0, opts=None, **kw):
         """render the whole image, make albedo, normal and depth with the same options and filter, all on the device
         (take_hip_render_denoised) -> (H, W, 3) host array.  Equal bit for bit to render + render_features + denoise made
         by hand.  Denoise options: keywords of cdefs.denoise_opts, or opts = a TakeDenoiseOpts; neither = the defaults."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        opts = _denoise_opts(opts, kw)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
         out = np.zeros((self.sd.height, self.sd.width, 3), self.dtype)
         _check(lib().take_hip_render_denoised(self.h, C.byref(o), None if opts is None else C.byref(opts), out.ctypes.data))
         return out
@@ -551,7 +561,7 @@ class Scene:
         """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; H * W * 3 of the
         scene's Real); blocks until done"""
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        opts = _denoise_opts(opts, kw)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
         _check(lib().take_hip_render_denoised_device(self.h, C.byref(o), None if opts is None else C.byref(opts),
                                                      C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
 
@@ -564,15 +574,11 @@ class Scene:
         and of their squares.  What is left out of min_spp / step_spp / threshold / floor takes the library's default
         (16, 8, 0.05, 1e-3; threshold 0 is a value); opts: a TakeAdaptiveOpts instead of the keywords, or None = a NULL
         pointer (all defaults)."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(opts, str) else opts
+        a = _adaptive_opts(opts, min_spp, step_spp, threshold, floor)
         n = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
         out = np.zeros((n, self.sd.width, 3), self.dtype)
-        planes = {"count": np.zeros((n, self.sd.width), np.int32), "m1": np.zeros((n, self.sd.width), np.float64),
-                  "m2": np.zeros((n, self.sd.width), np.float64)} if stats else None
-        st = D.TakeAdaptiveStats(*[planes[k].ctypes.data for k in ("count", "m1", "m2")]) if stats else None
+        planes, st = _host_stats((n, self.sd.width)) if stats else (None, None)
         _check(lib().take_hip_render_adaptive(self.h, C.byref(o), None if a is None else C.byref(a), out.ctypes.data,
                                               None if st is None else C.byref(st)))
         return (out, planes) if stats else out
@@ -583,13 +589,8 @@ class Scene:
         scene's Real); stats: {"count" / "m1" / "m2": device tensor or pointer} for the planes wanted (int32, float64,
         float64; rows * W each); blocks until done"""
         o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(opts, str) else opts
-        st = None
-        if stats:
-            unknown = set(stats) - {"count", "m1", "m2"}
-            if unknown:
-                raise ValueError(f"unknown statistics plane {sorted(unknown)[0]!r}: one of ('count', 'm1', 'm2')")
-            st = D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in ("count", "m1", "m2")])
+        a = _adaptive_opts(opts, min_spp, step_spp, threshold, floor)
+        st = _device_stats(stats)
         _check(lib().take_hip_render_adaptive_device(self.h, C.byref(o), None if a is None else C.byref(a), C.c_void_p(_pointer(d_ptr)),
                                                      None if st is None else C.byref(st), C.c_void_p(stream or 0)))
 
@@ -602,15 +603,12 @@ class Scene:
         planes, variance plane).  Sampler options as render_adaptive takes them (adaptive: a TakeAdaptiveOpts instead of
         the keywords, or None = all defaults); denoise options: keywords of cdefs.denoise_opts, or opts = a
         TakeDenoiseOpts; neither = the defaults (sigma_color 4.0 standard deviations)."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
-        opts = _denoise_opts(opts, kw)
+        a = _adaptive_opts(adaptive, min_spp, step_spp, threshold, floor)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
         h, w = self.sd.height, self.sd.width
         out = np.zeros((h, w, 3), self.dtype)
-        planes = {"count": np.zeros((h, w), np.int32), "m1": np.zeros((h, w), np.float64), "m2": np.zeros((h, w), np.float64)} if stats else None
-        st = D.TakeAdaptiveStats(*[planes[k].ctypes.data for k in ("count", "m1", "m2")]) if stats else None
+        planes, st = _host_stats((h, w)) if stats else (None, None)
         var = np.zeros((h, w), self.dtype) if variance else None
         _check(lib().take_hip_render_adaptive_denoised(self.h, C.byref(o), None if a is None else C.byref(a), None if opts is None else C.byref(opts),
                                                        out.ctypes.data, None if st is None else C.byref(st), None if var is None else var.ctypes.data))
@@ -623,14 +621,9 @@ class Scene:
         scene's Real); stats: {"count" / "m1" / "m2": device tensor or pointer} for the planes wanted; variance: the
         optional (H * W of the scene's Real) output plane; blocks until done"""
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
-        opts = _denoise_opts(opts, kw)
-        st = None
-        if stats:
-            unknown = set(stats) - {"count", "m1", "m2"}
-            if unknown:
-                raise ValueError(f"unknown statistics plane {sorted(unknown)[0]!r}: one of ('count', 'm1', 'm2')")
-            st = D.TakeAdaptiveStats(*[_pointer(stats.get(k)) for k in ("count", "m1", "m2")])
+        a = _adaptive_opts(adaptive, min_spp, step_spp, threshold, floor)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
+        st = _device_stats(stats)
         _check(lib().take_hip_render_adaptive_denoised_device(self.h, C.byref(o), None if a is None else C.byref(a), None if opts is None else C.byref(opts),
                                                               C.c_void_p(_pointer(d_ptr)), None if st is None else C.byref(st), C.c_void_p(_pointer(variance)),
                                                               C.c_void_p(stream or 0)))
@@ -673,11 +666,9 @@ class Scene:
         mark_frame made by hand.  Change `seed` from frame to frame.  restart=True: drop the history.  Sampler options as
         render_adaptive takes them; temporal: a TakeTemporalOpts or None = the defaults; denoise options as
         render_adaptive_denoised takes them."""
-        spp = self.sd.spp if spp is None else spp
-        max_depth = self.sd.max_depth if max_depth is None else max_depth
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
-        opts = _denoise_opts(opts, kw)
+        a = _adaptive_opts(adaptive, min_spp, step_spp, threshold, floor)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
         out = np.zeros((self.sd.height, self.sd.width, 3), self.dtype)
         _check(lib().take_hip_render_temporal(self.h, C.byref(o), None if a is None else C.byref(a), None if temporal is None else C.byref(temporal),
                                               None if opts is None else C.byref(opts), 1 if restart else 0, out.ctypes.data))
@@ -688,8 +679,8 @@ class Scene:
         """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer; H * W * 3 of the
         scene's Real); blocks until done"""
         o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
-        a = D.adaptive_opts(min_spp, step_spp, threshold, floor) if isinstance(adaptive, str) else adaptive
-        opts = _denoise_opts(opts, kw)
+        a = _adaptive_opts(adaptive, min_spp, step_spp, threshold, floor)
+        opts = _keyword_opts(D.denoise_opts, opts, kw)
         _check(lib().take_hip_render_temporal_device(self.h, C.byref(o), None if a is None else C.byref(a), None if temporal is None else C.byref(temporal),
                                                      None if opts is None else C.byref(opts), 1 if restart else 0, C.c_void_p(_pointer(d_ptr)),
                                                      C.c_void_p(stream or 0)))

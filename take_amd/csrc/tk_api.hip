@@ -178,23 +178,14 @@ int take_hip_render_features(TakeScene *ts, const TakeRenderOpts *opts, const Ta
     const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
     if (rows < 0) return rows;
     const size_t npix = (size_t)rows * ts->width(), real = ts->f64() ? 8 : 4;
-    // the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
-    const std::pair<void *, size_t> planes[6] = {{host_out->albedo, 3 * real}, {host_out->normal, 3 * real}, {host_out->depth, real},
-                                                 {host_out->alpha, real},      {host_out->shape_id, 4},      {host_out->material_id, 4}};
-    DevBuf<char> d_plane[6];
-    void *d_ptr[6] = {};
-    for (int k = 0; k < 6; k++) {
-        if (!planes[k].first || npix == 0) continue;
-        if (d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the feature buffers");
-        d_ptr[k] = d_plane[k].p;
-    }
-    const TakeFeatureBuffers d_out{d_ptr[0], d_ptr[1], d_ptr[2], d_ptr[3], (int32_t *)d_ptr[4], (int32_t *)d_ptr[5]};
+    // the wanted planes in device memory, then copied out
+    StagedPlanes<6> st{{plane_out(host_out->albedo, 3 * real), plane_out(host_out->normal, 3 * real), plane_out(host_out->depth, real),
+                        plane_out(host_out->alpha, real), plane_out(host_out->shape_id, 4), plane_out(host_out->material_id, 4)}};
+    if (int rc = st.alloc(npix, "out of device memory for the feature buffers")) return rc;
+    const TakeFeatureBuffers d_out{st[0], st[1], st[2], st[3], (int32_t *)st[4], (int32_t *)st[5]};
     TakeFeatureBuffers asked = npix == 0 ? *host_out : d_out;  // (an empty strip set: the checks run on what was asked for)
-    const int rc = render_features_scene(ts, *opts, asked, nullptr);
-    if (rc) return rc;
-    for (int k = 0; k < 6; k++)
-        if (d_ptr[k]) HIP_TRY(hipMemcpy(planes[k].first, d_ptr[k], d_plane[k].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    if (int rc = render_features_scene(ts, *opts, asked, nullptr)) return rc;
+    return st.download();
 }
 
 // Adaptive sampling (stop pixels whose error estimate is below a threshold): tk_render.hip, adaptive_impl.
@@ -215,22 +206,14 @@ int take_hip_render_adaptive(TakeScene *ts, const TakeRenderOpts *opts, const Ta
     const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
     if (rows < 0) return rows;
     const size_t npix = (size_t)rows * ts->width();
-    // the image and the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
-    const std::pair<void *, size_t> planes[4] = {{rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4)},
-                                                 {host_stats ? host_stats->count : nullptr, 4},
-                                                 {host_stats ? host_stats->m1 : nullptr, 8},
-                                                 {host_stats ? host_stats->m2 : nullptr, 8}};
-    DevBuf<char> d_plane[4];
-    for (int k = 0; k < 4; k++)
-        if (planes[k].first && npix > 0 && d_plane[k].alloc(npix * planes[k].second) != hipSuccess)
-            return fail(TAKE_E_NOMEM, "out of device memory for the adaptive render's planes");
-    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[1].p, (double *)d_plane[2].p, (double *)d_plane[3].p};
+    // the image and the wanted planes in device memory, then copied out
+    StagedPlanes<4> st{{plane_out(rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4)), plane_out(host_stats ? host_stats->count : nullptr, 4),
+                        plane_out(host_stats ? host_stats->m1 : nullptr, 8), plane_out(host_stats ? host_stats->m2 : nullptr, 8)}};
+    if (int rc = st.alloc(npix, "out of device memory for the adaptive render's planes")) return rc;
+    const TakeAdaptiveStats d_stats{(int32_t *)st[1], (double *)st[2], (double *)st[3]};
     // (an empty strip set: the checks run, nothing is written)
-    const int rc = render_adaptive_scene(ts, *opts, adaptive, npix ? (void *)d_plane[0].p : rgb_out_host, d_stats, nullptr);
-    if (rc) return rc;
-    for (int k = 0; k < 4; k++)
-        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    if (int rc = render_adaptive_scene(ts, *opts, adaptive, npix ? st[0] : rgb_out_host, d_stats, nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_trace_closest(TakeScene *ts, const void *rays, int64_t n, void *hits) {
@@ -386,16 +369,12 @@ int take_hip_render_motion(TakeScene *ts, const TakeRenderOpts *opts, const Take
     if (int rc = check_motion_args(ts, opts, host_out)) return rc;
     TAKE_ON_DEVICE(ts);
     const size_t npix = (size_t)ts->width() * ts->height(), real = ts->f64() ? 8 : 4;
-    // the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
-    const std::pair<void *, size_t> planes[4] = {{host_out->prev_xy, 2 * real}, {host_out->prev_depth, real}, {host_out->depth, real}, {host_out->shape_id, 4}};
-    DevBuf<char> d_plane[4];
-    for (int k = 0; k < 4; k++)
-        if (planes[k].first && d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the motion buffers");
-    const TakeMotionBuffers d_out{d_plane[0].p, d_plane[1].p, d_plane[2].p, (int32_t *)d_plane[3].p};
+    // the wanted planes in device memory, then copied out
+    StagedPlanes<4> st{{plane_out(host_out->prev_xy, 2 * real), plane_out(host_out->prev_depth, real), plane_out(host_out->depth, real), plane_out(host_out->shape_id, 4)}};
+    if (int rc = st.alloc(npix, "out of device memory for the motion buffers")) return rc;
+    const TakeMotionBuffers d_out{st[0], st[1], st[2], (int32_t *)st[3]};
     if (int rc = render_motion_scene(ts, *opts, d_out, true, nullptr)) return rc;
-    for (int k = 0; k < 4; k++)
-        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    return st.download();
 }
 
 int take_hip_get_counters(const TakeScene *ts, TakeCounters *out) {

@@ -56,64 +56,78 @@ int check_image(int32_t precision, int32_t width, int32_t height) {
 // Reals of working images per pixel: colour, colour, guide records
 constexpr int WORK_REALS = 12;
 
-// Prologue, the levels, the epilogue fused into the last: enqueued on `stream`, no synchronisation.  work: WORK_REALS *
-// width * height Reals, aligned for Rec4<R>.  out may be rgb (the prologue has read rgb before the last level writes).
-template <class R>
-int denoise_enqueue(const R *rgb, const R *albedo, const R *normal, const R *depth, int32_t width, int32_t height, const DenoiseOpts &o, R *work, R *out,
-                    hipStream_t stream) {
+// the guide planes of a TakeFeatureBuffers (null: none were given) for Reals of precision R; each may be null
+template <class R> struct Guides {
+    R *albedo, *normal, *depth;
+};
+template <class R> Guides<R> typed(const TakeFeatureBuffers *g) { return g ? Guides<R>{(R *)g->albedo, (R *)g->normal, (R *)g->depth} : Guides<R>{}; }
+
+// The launches both filters share — prologue, the levels, the epilogue fused into the last: enqueued on `stream`, no
+// synchronisation.  work: WORK_REALS * width * height Reals, aligned for Rec4<R>.  pack(grid, block, P, colour, guide)
+// launches the prologue, level(last, grid, block, P, i, src, guide, dst) level i from src to dst; last: std::true_type
+// for the level that is the epilogue (dst is null: it writes the caller's planes), std::false_type before.
+template <class R, class Pack, class Level>
+int filter_enqueue(const Guides<R> &g, int32_t width, int32_t height, const DenoiseOpts &o, R *work, Pack &&pack, Level &&level) {
     const int64_t npix = (int64_t)width * height;
     dn::Params<R> P{};
     P.width = width, P.height = height;
-    P.guides = (normal ? dn::HAS_NORMAL : 0) | (depth ? dn::HAS_DEPTH : 0) | (albedo && !o.keep_albedo ? dn::DEMODULATE : 0);
+    P.guides = (g.normal ? dn::HAS_NORMAL : 0) | (g.depth ? dn::HAS_DEPTH : 0) | (g.albedo && !o.keep_albedo ? dn::DEMODULATE : 0);
     P.inv_n = (R)(1.0 / (o.sigma_normal * o.sigma_normal)), P.inv_d = (R)(1.0 / (o.sigma_depth * o.sigma_depth));
     P.albedo_floor = (R)o.albedo_floor;
     dn::Rec4<R> *colour[2] = {(dn::Rec4<R> *)work, (dn::Rec4<R> *)work + npix}, *guide = (dn::Rec4<R> *)work + 2 * npix;
-    const dim3 pack_grid((unsigned)std::min<int64_t>((npix + 255) / 256, 2048));
-    hipLaunchKernelGGL((dn::k_denoise_pack<R>), pack_grid, dim3(256), 0, stream, P, rgb, albedo, normal, depth, colour[0], guide);
+    pack(dim3((unsigned)std::min<int64_t>((npix + 255) / 256, 2048)), dim3(256), P, colour[0], guide);
     const dim3 grid((unsigned)((width + dn::DN_BX - 1) / dn::DN_BX), (unsigned)std::min((height + dn::DN_BY - 1) / dn::DN_BY, 65535)), block(dn::DN_BX, dn::DN_BY);
     for (int i = 0; i < o.iterations; i++) {
-        const R inv_c = (R)(std::ldexp(1.0, 2 * i) / (o.sigma_color * o.sigma_color));  // the colour sigma halves every level
         if (i == o.iterations - 1)
-            hipLaunchKernelGGL((dn::k_denoise_level<R, true>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, inv_c, (dn::Rec4<R> *)nullptr, albedo, out);
+            level(std::true_type{}, grid, block, P, i, colour[i & 1], guide, (dn::Rec4<R> *)nullptr);
         else
-            hipLaunchKernelGGL((dn::k_denoise_level<R, false>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, inv_c, colour[(i + 1) & 1], albedo, (R *)nullptr);
+            level(std::false_type{}, grid, block, P, i, colour[i & 1], guide, colour[(i + 1) & 1]);
     }
     HIP_TRY(hipGetLastError());
     return TAKE_OK;
 }
-int denoise_enqueue_any(int32_t precision, const void *rgb, const TakeFeatureBuffers *g, int32_t width, int32_t height, const DenoiseOpts &o, void *work,
-                        void *out, hipStream_t stream) {
-    const void *albedo = g ? g->albedo : nullptr, *normal = g ? g->normal : nullptr, *depth = g ? g->depth : nullptr;
-    if (precision == TAKE_PRECISION_F64)
-        return denoise_enqueue((const double *)rgb, (const double *)albedo, (const double *)normal, (const double *)depth, width, height, o, (double *)work, (double *)out, stream);
-    return denoise_enqueue((const float *)rgb, (const float *)albedo, (const float *)normal, (const float *)depth, width, height, o, (float *)work, (float *)out, stream);
+
+// The fixed-sigma filter (tk_denoise.h).  out may be rgb (the prologue has read rgb before the last level writes).
+template <class R>
+int denoise_enqueue(const R *rgb, const Guides<R> &g, int32_t width, int32_t height, const DenoiseOpts &o, R *work, R *out, hipStream_t stream) {
+    return filter_enqueue(
+        g, width, height, o, work,
+        [&](dim3 grid, dim3 block, const dn::Params<R> &P, dn::Rec4<R> *colour, dn::Rec4<R> *guide) {
+            hipLaunchKernelGGL((dn::k_denoise_pack<R>), grid, block, 0, stream, P, rgb, g.albedo, g.normal, g.depth, colour, guide);
+        },
+        [&](auto last, dim3 grid, dim3 block, const dn::Params<R> &P, int i, dn::Rec4<R> *src, dn::Rec4<R> *guide, dn::Rec4<R> *dst) {
+            const R inv_c = (R)(std::ldexp(1.0, 2 * i) / (o.sigma_color * o.sigma_color));  // the colour sigma halves every level
+            hipLaunchKernelGGL((dn::k_denoise_level<R, decltype(last)::value>), grid, block, 0, stream, P, src, guide, 1 << i, inv_c, dst, g.albedo, last ? out : (R *)nullptr);
+        });
 }
 
-// The variance-guided filter (tk_denoise_var.h): the same shape of launches.  count / m1 / m2: the planes of
-// TakeAdaptiveStats; variance_out may be null.  o.sigma_color is a multiple of the pixel's standard deviation.
+// The variance-guided filter (tk_denoise_var.h).  s: the planes of TakeAdaptiveStats; variance_out may be null.
+// o.sigma_color is a multiple of the pixel's standard deviation.
 template <class R>
-int denoise_var_enqueue(const R *rgb, const R *albedo, const R *normal, const R *depth, const TakeAdaptiveStats &s, int32_t width, int32_t height,
-                        const DenoiseOpts &o, R *work, R *out, R *variance_out, hipStream_t stream) {
-    const int64_t npix = (int64_t)width * height;
-    dn::Params<R> P{};
-    P.width = width, P.height = height;
-    P.guides = (normal ? dn::HAS_NORMAL : 0) | (depth ? dn::HAS_DEPTH : 0) | (albedo && !o.keep_albedo ? dn::DEMODULATE : 0);
-    P.inv_n = (R)(1.0 / (o.sigma_normal * o.sigma_normal)), P.inv_d = (R)(1.0 / (o.sigma_depth * o.sigma_depth));
-    P.albedo_floor = (R)o.albedo_floor;
+int denoise_var_enqueue(const R *rgb, const Guides<R> &g, const TakeAdaptiveStats &s, int32_t width, int32_t height, const DenoiseOpts &o, R *work, R *out,
+                        R *variance_out, hipStream_t stream) {
     const R sl2 = (R)(o.sigma_color * o.sigma_color);
-    dn::Rec4<R> *colour[2] = {(dn::Rec4<R> *)work, (dn::Rec4<R> *)work + npix}, *guide = (dn::Rec4<R> *)work + 2 * npix;
-    const dim3 pack_grid((unsigned)std::min<int64_t>((npix + 255) / 256, 2048));
-    hipLaunchKernelGGL((dn::k_denoise_var_pack<R>), pack_grid, dim3(256), 0, stream, P, rgb, albedo, normal, depth, (const int32_t *)s.count, (const double *)s.m1,
-                       (const double *)s.m2, colour[0], guide);
-    const dim3 grid((unsigned)((width + dn::DN_BX - 1) / dn::DN_BX), (unsigned)std::min((height + dn::DN_BY - 1) / dn::DN_BY, 65535)), block(dn::DN_BX, dn::DN_BY);
-    for (int i = 0; i < o.iterations; i++) {
-        if (i == o.iterations - 1)
-            hipLaunchKernelGGL((dn::k_denoise_var_level<R, true>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, sl2, (dn::Rec4<R> *)nullptr, albedo, out, variance_out);
-        else
-            hipLaunchKernelGGL((dn::k_denoise_var_level<R, false>), grid, block, 0, stream, P, colour[i & 1], guide, 1 << i, sl2, colour[(i + 1) & 1], albedo, (R *)nullptr,
-                               (R *)nullptr);
-    }
-    HIP_TRY(hipGetLastError());
+    return filter_enqueue(
+        g, width, height, o, work,
+        [&](dim3 grid, dim3 block, const dn::Params<R> &P, dn::Rec4<R> *colour, dn::Rec4<R> *guide) {
+            hipLaunchKernelGGL((dn::k_denoise_var_pack<R>), grid, block, 0, stream, P, rgb, g.albedo, g.normal, g.depth, s.count, s.m1, s.m2, colour, guide);
+        },
+        [&](auto last, dim3 grid, dim3 block, const dn::Params<R> &P, int i, dn::Rec4<R> *src, dn::Rec4<R> *guide, dn::Rec4<R> *dst) {
+            hipLaunchKernelGGL((dn::k_denoise_var_level<R, decltype(last)::value>), grid, block, 0, stream, P, src, guide, 1 << i, sl2, dst, g.albedo, last ? out : (R *)nullptr,
+                               last ? variance_out : (R *)nullptr);
+        });
+}
+
+// A scene-free filter call, its arguments checked: the device, working images of the call's own, enqueue(them, as R *),
+// the stream drained
+template <class F> int filter_on_own_work(int32_t precision, int32_t width, int32_t height, hipStream_t stream, F &&enqueue) {
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    DevBuf<char> work;
+    if (work.alloc((size_t)width * height * WORK_REALS * (precision == TAKE_PRECISION_F64 ? 8 : 4)) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's working images");
+    if (int rc = with_real(precision, [&](auto tag) { return enqueue((decltype(tag) *)work.p); })) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
     return TAKE_OK;
 }
 // what the scene-free variance-guided calls refuse, before a device is looked for
@@ -129,6 +143,47 @@ int check_adaptive_denoised_args(const TakeScene *ts, const TakeRenderOpts *ropt
     if (!ts || !ropts || !out) return fail(TAKE_E_INVALID, "null argument");
     if (int rc = check_adaptive_opts(aopts)) return rc;
     return resolve(dopts, o, SIGMA_COLOR_VARIANCE);
+}
+
+// ---- what the scene-bound calls share
+// the whole image, as take_hip_render_exr_scanlines
+TakeRenderOpts whole_image(const TakeRenderOpts &o) {
+    TakeRenderOpts ro = o;
+    ro.strip_first = 0, ro.strip_stride = 1;
+    return ro;
+}
+// RenderWorkspace::denoise of a scene of npix pixels, `reals` Reals: the filter's working images, then albedo, normal
+// and depth; then, if wanted — from the next multiple of 8 bytes on — statistics planes of its own: m1, m2, count
+template <class R> struct DenoiseArena {
+    int64_t reals;
+    R *work;
+    Guides<R> guides;
+    TakeAdaptiveStats stats;  // (null without own_stats)
+    TakeFeatureBuffers planes() const { return {guides.albedo, guides.normal, guides.depth, nullptr, nullptr, nullptr}; }
+};
+template <class R> int denoise_arena(RenderWorkspace<R> &w, int64_t npix, bool own_stats, DenoiseArena<R> &a) {
+    const int64_t real_planes = (WORK_REALS + 7) * npix, stats_at = (real_planes * (int64_t)sizeof(R) + 7) / 8 * 8;
+    a.reals = own_stats ? (stats_at + 20 * npix + (int64_t)sizeof(R) - 1) / (int64_t)sizeof(R) : real_planes;
+    if (int rc = w.ensure_denoise(a.reals)) return rc;
+    a.work = w.denoise.p;
+    a.guides.albedo = a.work + WORK_REALS * npix, a.guides.normal = a.guides.albedo + 3 * npix, a.guides.depth = a.guides.normal + 3 * npix;
+    a.stats = TakeAdaptiveStats{nullptr, nullptr, nullptr};
+    if (own_stats) {
+        double *m1 = (double *)((char *)a.work + stats_at), *m2 = m1 + npix;
+        a.stats = TakeAdaptiveStats{(int32_t *)(m2 + npix), m1, m2};
+    }
+    return TAKE_OK;
+}
+// The tail of the adaptive pipelines: the guides from the samples every pixel has (the guide pass does not grow with the
+// maximum), then the variance filter of (rgb, stats) into (out, variance_out); ro: the whole image.  Enqueued on
+// `stream`, no synchronisation.
+template <class R>
+int guides_then_variance_filter(TakeScene *ts, const TakeRenderOpts &ro, const TakeAdaptiveOpts *aopts, const DenoiseArena<R> &a, const R *rgb,
+                                const TakeAdaptiveStats &stats, const DenoiseOpts &o, R *out, R *variance_out, hipStream_t stream) {
+    TakeRenderOpts fo = ro;
+    fo.spp = adaptive_min_spp(ro, aopts);
+    if (int rc = render_features_scene(ts, fo, a.planes(), stream)) return rc;
+    return denoise_var_enqueue(rgb, a.guides, stats, ts->width(), ts->height(), o, a.work, out, variance_out, stream);
 }
 
 // ---- temporal accumulation (tk_temporal.h)
@@ -197,14 +252,10 @@ int take_hip_denoise_device(const void *d_rgb, const TakeFeatureBuffers *d_guide
     DenoiseOpts o;
     if (int rc = check_image(precision, width, height)) return rc;
     if (int rc = resolve(opts, o)) return rc;
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4;
-    DevBuf<char> work;
-    if (work.alloc((size_t)width * height * WORK_REALS * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's working images");
-    if (int rc = denoise_enqueue_any(precision, d_rgb, d_guides, width, height, o, work.p, d_out, (hipStream_t)stream)) return rc;
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return TAKE_OK;
+    return filter_on_own_work(precision, width, height, (hipStream_t)stream, [&](auto *work) {
+        using R = std::remove_pointer_t<decltype(work)>;
+        return denoise_enqueue((const R *)d_rgb, typed<R>(d_guides), width, height, o, work, (R *)d_out, (hipStream_t)stream);
+    });
 }
 
 int take_hip_denoise(const void *rgb, const TakeFeatureBuffers *guides, int32_t precision, int32_t width, int32_t height, const TakeDenoiseOpts *opts,
@@ -216,18 +267,14 @@ int take_hip_denoise(const void *rgb, const TakeFeatureBuffers *guides, int32_t 
     const int nd = check_device();
     if (nd < 0) return nd;
     const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
-    // rgb (filtered in place), then the guides that were given: (host pointer, Reals per pixel)
-    const std::pair<const void *, size_t> planes[4] = {{rgb, 3}, {guides ? guides->albedo : nullptr, 3}, {guides ? guides->normal : nullptr, 3}, {guides ? guides->depth : nullptr, 1}};
-    DevBuf<char> d_plane[4];
-    for (int k = 0; k < 4; k++) {
-        if (!planes[k].first) continue;
-        if (d_plane[k].alloc(npix * planes[k].second * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
-        HIP_TRY(hipMemcpy(d_plane[k].p, planes[k].first, d_plane[k].bytes(), hipMemcpyHostToDevice));
-    }
-    const TakeFeatureBuffers d_guides{d_plane[1].p, d_plane[2].p, d_plane[3].p, nullptr, nullptr, nullptr};
-    if (int rc = take_hip_denoise_device(d_plane[0].p, &d_guides, precision, width, height, opts, d_plane[0].p, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(out, d_plane[0].p, d_plane[0].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    // rgb (filtered in place), then the guides that were given
+    StagedPlanes<4> st{{plane_inout(rgb, out, 3 * real), plane_in(guides ? guides->albedo : nullptr, 3 * real), plane_in(guides ? guides->normal : nullptr, 3 * real),
+                        plane_in(guides ? guides->depth : nullptr, real)}};
+    if (int rc = st.alloc(npix, "out of device memory for the denoiser's planes")) return rc;
+    if (int rc = st.upload()) return rc;
+    const TakeFeatureBuffers d_guides{st[1], st[2], st[3], nullptr, nullptr, nullptr};
+    if (int rc = take_hip_denoise_device(st[0], &d_guides, precision, width, height, opts, st[0], nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_render_denoised_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeDenoiseOpts *dopts, void *d_out, void *stream) {
@@ -235,19 +282,15 @@ int take_hip_render_denoised_device(TakeScene *ts, const TakeRenderOpts *ropts, 
     DenoiseOpts o;
     if (int rc = resolve(dopts, o)) return rc;
     TAKE_ON_DEVICE(ts);
-    TakeRenderOpts ro = *ropts;
-    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_exr_scanlines
+    const TakeRenderOpts ro = whole_image(*ropts);
     const int W = ts->width(), H = ts->height();
-    const int64_t npix = (int64_t)W * H;
     return on_primary(ts, [&](auto &sc, auto &work) {
         using R = std::remove_reference_t<decltype(*work.accum.p)>;
-        // the working images, then albedo, normal and depth
-        if (int rc = work.ensure_denoise((WORK_REALS + 7) * npix)) return rc;
-        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
+        DenoiseArena<R> a;
+        if (int rc = denoise_arena(work, (int64_t)W * H, false, a)) return rc;
         if (int rc = render_scene(ts, ro, d_out, (hipStream_t)stream)) return rc;
-        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
-        if (int rc = render_features_scene(ts, ro, planes, (hipStream_t)stream)) return rc;
-        if (int rc = denoise_enqueue((const R *)d_out, (const R *)albedo, (const R *)normal, (const R *)depth, W, H, o, work.denoise.p, (R *)d_out, (hipStream_t)stream)) return rc;
+        if (int rc = render_features_scene(ts, ro, a.planes(), (hipStream_t)stream)) return rc;
+        if (int rc = denoise_enqueue((const R *)d_out, a.guides, W, H, o, a.work, (R *)d_out, (hipStream_t)stream)) return rc;
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
         return (int)TAKE_OK;
     });
@@ -258,33 +301,20 @@ int take_hip_render_denoised(TakeScene *ts, const TakeRenderOpts *ropts, const T
     DenoiseOpts o;
     if (int rc = resolve(dopts, o)) return rc;
     TAKE_ON_DEVICE(ts);
-    DevBuf<char> d_out;
-    if (d_out.alloc((size_t)ts->width() * ts->height() * 3 * (ts->f64() ? 8 : 4)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoised image");
-    if (int rc = take_hip_render_denoised_device(ts, ropts, dopts, d_out.p, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    StagedPlanes<1> st{{plane_out(rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4))}};
+    if (int rc = st.alloc((size_t)ts->width() * ts->height(), "out of device memory for the denoised image")) return rc;
+    if (int rc = take_hip_render_denoised_device(ts, ropts, dopts, st[0], nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_denoise_variance_device(const void *d_rgb, const TakeFeatureBuffers *d_guides, const TakeAdaptiveStats *d_stats, int32_t precision, int32_t width,
                                      int32_t height, const TakeDenoiseOpts *opts, void *d_out, void *d_variance_out, void *stream) {
     DenoiseOpts o;
     if (int rc = check_variance_args(d_rgb, d_stats, d_out, precision, width, height, opts, o)) return rc;
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4;
-    DevBuf<char> work;
-    if (work.alloc((size_t)width * height * WORK_REALS * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's working images");
-    const void *albedo = d_guides ? d_guides->albedo : nullptr, *normal = d_guides ? d_guides->normal : nullptr, *depth = d_guides ? d_guides->depth : nullptr;
-    int rc;
-    if (precision == TAKE_PRECISION_F64)
-        rc = denoise_var_enqueue((const double *)d_rgb, (const double *)albedo, (const double *)normal, (const double *)depth, *d_stats, width, height, o, (double *)work.p,
-                                 (double *)d_out, (double *)d_variance_out, (hipStream_t)stream);
-    else
-        rc = denoise_var_enqueue((const float *)d_rgb, (const float *)albedo, (const float *)normal, (const float *)depth, *d_stats, width, height, o, (float *)work.p,
-                                 (float *)d_out, (float *)d_variance_out, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return TAKE_OK;
+    return filter_on_own_work(precision, width, height, (hipStream_t)stream, [&](auto *work) {
+        using R = std::remove_pointer_t<decltype(work)>;
+        return denoise_var_enqueue((const R *)d_rgb, typed<R>(d_guides), *d_stats, width, height, o, work, (R *)d_out, (R *)d_variance_out, (hipStream_t)stream);
+    });
 }
 
 int take_hip_denoise_variance(const void *rgb, const TakeFeatureBuffers *guides, const TakeAdaptiveStats *stats, int32_t precision, int32_t width, int32_t height,
@@ -294,23 +324,16 @@ int take_hip_denoise_variance(const void *rgb, const TakeFeatureBuffers *guides,
     const int nd = check_device();
     if (nd < 0) return nd;
     const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
-    // rgb (filtered in place), the guides that were given, the three statistics planes: (host pointer, bytes per pixel);
-    // then the variance plane, if wanted
-    const std::pair<const void *, size_t> planes[7] = {{rgb, 3 * real}, {guides ? guides->albedo : nullptr, 3 * real}, {guides ? guides->normal : nullptr, 3 * real},
-                                                       {guides ? guides->depth : nullptr, real}, {stats->count, 4}, {stats->m1, 8}, {stats->m2, 8}};
-    DevBuf<char> d_plane[7], d_variance;
-    for (int k = 0; k < 7; k++) {
-        if (!planes[k].first) continue;
-        if (d_plane[k].alloc(npix * planes[k].second) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
-        HIP_TRY(hipMemcpy(d_plane[k].p, planes[k].first, d_plane[k].bytes(), hipMemcpyHostToDevice));
-    }
-    if (variance_out && d_variance.alloc(npix * real) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the denoiser's planes");
-    const TakeFeatureBuffers d_guides{d_plane[1].p, d_plane[2].p, d_plane[3].p, nullptr, nullptr, nullptr};
-    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[4].p, (double *)d_plane[5].p, (double *)d_plane[6].p};
-    if (int rc = take_hip_denoise_variance_device(d_plane[0].p, &d_guides, &d_stats, precision, width, height, opts, d_plane[0].p, d_variance.p, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(out, d_plane[0].p, d_plane[0].bytes(), hipMemcpyDeviceToHost));
-    if (variance_out) HIP_TRY(hipMemcpy(variance_out, d_variance.p, d_variance.bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    // rgb (filtered in place), the guides that were given, the three statistics planes; then the variance plane, if wanted
+    StagedPlanes<8> st{{plane_inout(rgb, out, 3 * real), plane_in(guides ? guides->albedo : nullptr, 3 * real), plane_in(guides ? guides->normal : nullptr, 3 * real),
+                        plane_in(guides ? guides->depth : nullptr, real), plane_in(stats->count, 4), plane_in(stats->m1, 8), plane_in(stats->m2, 8),
+                        plane_out(variance_out, real)}};
+    if (int rc = st.alloc(npix, "out of device memory for the denoiser's planes")) return rc;
+    if (int rc = st.upload()) return rc;
+    const TakeFeatureBuffers d_guides{st[1], st[2], st[3], nullptr, nullptr, nullptr};
+    const TakeAdaptiveStats d_stats{(int32_t *)st[4], (double *)st[5], (double *)st[6]};
+    if (int rc = take_hip_denoise_variance_device(st[0], &d_guides, &d_stats, precision, width, height, opts, st[0], st[7], nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_render_adaptive_denoised_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeDenoiseOpts *dopts, void *d_out,
@@ -318,30 +341,18 @@ int take_hip_render_adaptive_denoised_device(TakeScene *ts, const TakeRenderOpts
     DenoiseOpts o;
     if (int rc = check_adaptive_denoised_args(ts, ropts, aopts, dopts, d_out, o)) return rc;
     TAKE_ON_DEVICE(ts);
-    TakeRenderOpts ro = *ropts;
-    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_denoised_device
-    const int W = ts->width(), H = ts->height();
-    const int64_t npix = (int64_t)W * H;
+    const TakeRenderOpts ro = whole_image(*ropts);
     return on_primary(ts, [&](auto &sc, auto &work) {
         using R = std::remove_reference_t<decltype(*work.accum.p)>;
-        // the working images, then albedo, normal and depth, then — from the next multiple of 8 bytes on — the statistics
-        // planes the caller did not ask for: m1, m2, count
-        const int64_t real_planes = (WORK_REALS + 7) * npix, stats_at = (real_planes * (int64_t)sizeof(R) + 7) / 8 * 8;
-        if (int rc = work.ensure_denoise((stats_at + 20 * npix + (int64_t)sizeof(R) - 1) / (int64_t)sizeof(R))) return rc;
-        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
-        double *own_m1 = (double *)((char *)work.denoise.p + stats_at), *own_m2 = own_m1 + npix;
-        TakeAdaptiveStats stats{(int32_t *)(own_m2 + npix), own_m1, own_m2};
+        DenoiseArena<R> a;
+        if (int rc = denoise_arena(work, (int64_t)ts->width() * ts->height(), true, a)) return rc;
+        // the arena's statistics planes stand in for the ones the caller did not ask for
+        TakeAdaptiveStats stats = a.stats;
         if (d_stats && d_stats->count) stats.count = d_stats->count;
         if (d_stats && d_stats->m1) stats.m1 = d_stats->m1;
         if (d_stats && d_stats->m2) stats.m2 = d_stats->m2;
         if (int rc = render_adaptive_scene(ts, ro, aopts, d_out, stats, (hipStream_t)stream)) return rc;
-        TakeRenderOpts fo = ro;
-        fo.spp = adaptive_min_spp(ro, aopts);  // the samples every pixel has: the guide pass does not grow with the maximum
-        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
-        if (int rc = render_features_scene(ts, fo, planes, (hipStream_t)stream)) return rc;
-        if (int rc = denoise_var_enqueue((const R *)d_out, (const R *)albedo, (const R *)normal, (const R *)depth, stats, W, H, o, work.denoise.p, (R *)d_out,
-                                         (R *)d_variance_out, (hipStream_t)stream))
-            return rc;
+        if (int rc = guides_then_variance_filter(ts, ro, aopts, a, (const R *)d_out, stats, o, (R *)d_out, (R *)d_variance_out, (hipStream_t)stream)) return rc;
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
         return (int)TAKE_OK;
     });
@@ -353,18 +364,13 @@ int take_hip_render_adaptive_denoised(TakeScene *ts, const TakeRenderOpts *ropts
     if (int rc = check_adaptive_denoised_args(ts, ropts, aopts, dopts, rgb_out_host, o)) return rc;
     TAKE_ON_DEVICE(ts);
     const size_t npix = (size_t)ts->width() * ts->height(), real = ts->f64() ? 8 : 4;
-    // the image and the wanted planes in device memory, then copied out: (host pointer, bytes per pixel)
-    const std::pair<void *, size_t> planes[5] = {{rgb_out_host, 3 * real}, {host_stats ? host_stats->count : nullptr, 4}, {host_stats ? host_stats->m1 : nullptr, 8},
-                                                 {host_stats ? host_stats->m2 : nullptr, 8}, {variance_out_host, real}};
-    DevBuf<char> d_plane[5];
-    for (int k = 0; k < 5; k++)
-        if (planes[k].first && d_plane[k].alloc(npix * planes[k].second) != hipSuccess)
-            return fail(TAKE_E_NOMEM, "out of device memory for the denoised adaptive render's planes");
-    const TakeAdaptiveStats d_stats{(int32_t *)d_plane[1].p, (double *)d_plane[2].p, (double *)d_plane[3].p};
-    if (int rc = take_hip_render_adaptive_denoised_device(ts, ropts, aopts, dopts, d_plane[0].p, &d_stats, d_plane[4].p, nullptr)) return rc;
-    for (int k = 0; k < 5; k++)
-        if (d_plane[k].p) HIP_TRY(hipMemcpy(planes[k].first, d_plane[k].p, d_plane[k].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    // the image and the wanted planes in device memory, then copied out
+    StagedPlanes<5> st{{plane_out(rgb_out_host, 3 * real), plane_out(host_stats ? host_stats->count : nullptr, 4), plane_out(host_stats ? host_stats->m1 : nullptr, 8),
+                        plane_out(host_stats ? host_stats->m2 : nullptr, 8), plane_out(variance_out_host, real)}};
+    if (int rc = st.alloc(npix, "out of device memory for the denoised adaptive render's planes")) return rc;
+    const TakeAdaptiveStats d_stats{(int32_t *)st[1], (double *)st[2], (double *)st[3]};
+    if (int rc = take_hip_render_adaptive_denoised_device(ts, ropts, aopts, dopts, st[0], &d_stats, st[4], nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_temporal_accumulate_device(const TakeTemporalFrame *d_cur, const TakeTemporalFrame *d_hist, const void *d_prev_xy, const void *d_prev_depth,
@@ -373,16 +379,12 @@ int take_hip_temporal_accumulate_device(const TakeTemporalFrame *d_cur, const Ta
     if (int rc = check_temporal_args(d_cur, d_hist, d_prev_xy, precision, width, height, opts, d_out, o)) return rc;
     const int nd = check_device();
     if (nd < 0) return nd;
-    int rc;
-    if (precision == TAKE_PRECISION_F64) {
-        const tp::Frame<double> hist = d_hist ? typed<double>(*d_hist) : tp::Frame<double>{};
-        rc = temporal_enqueue(typed<double>(*d_cur), d_hist ? &hist : nullptr, (const double *)d_prev_xy, (const double *)d_prev_depth, width, height, o,
-                              typed<double>(*d_out), (hipStream_t)stream);
-    } else {
-        const tp::Frame<float> hist = d_hist ? typed<float>(*d_hist) : tp::Frame<float>{};
-        rc = temporal_enqueue(typed<float>(*d_cur), d_hist ? &hist : nullptr, (const float *)d_prev_xy, (const float *)d_prev_depth, width, height, o,
-                              typed<float>(*d_out), (hipStream_t)stream);
-    }
+    const int rc = with_real(precision, [&](auto tag) {
+        using R = decltype(tag);
+        const tp::Frame<R> hist = d_hist ? typed<R>(*d_hist) : tp::Frame<R>{};
+        return temporal_enqueue(typed<R>(*d_cur), d_hist ? &hist : nullptr, (const R *)d_prev_xy, (const R *)d_prev_depth, width, height, o, typed<R>(*d_out),
+                                (hipStream_t)stream);
+    });
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return TAKE_OK;
@@ -395,32 +397,19 @@ int take_hip_temporal_accumulate(const TakeTemporalFrame *cur, const TakeTempora
     const int nd = check_device();
     if (nd < 0) return nd;
     const size_t real = precision == TAKE_PRECISION_F64 ? 8 : 4, npix = (size_t)width * height;
-    // the planes of a frame: bytes per pixel, in the order of TakeTemporalFrame's members
-    const size_t per_pixel[6] = {3 * real, 4, 8, 8, real, 4};
-    auto members = [](const TakeTemporalFrame &f, void *m[6]) { m[0] = f.rgb, m[1] = f.count, m[2] = f.m1, m[3] = f.m2, m[4] = f.depth, m[5] = f.shape_id; };
-    // the current frame (accumulated in place) and the history, uploaded; then the motion planes
-    DevBuf<char> d_cur[6], d_hist[6], d_xy, d_pd;
-    void *h_cur[6], *h_hist[6] = {}, *h_out[6];
-    members(*cur, h_cur), members(*out, h_out);
-    if (hist) members(*hist, h_hist);
-    for (int k = 0; k < 6; k++)
-        for (int which = 0; which < 2; which++) {
-            const void *src = which ? h_hist[k] : h_cur[k];
-            DevBuf<char> &dst = which ? d_hist[k] : d_cur[k];
-            if (!src) continue;
-            if (dst.alloc(npix * per_pixel[k]) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the temporal accumulation's planes");
-            HIP_TRY(hipMemcpy(dst.p, src, dst.bytes(), hipMemcpyHostToDevice));
-        }
-    if (d_xy.alloc(npix * 2 * real) != hipSuccess || (prev_depth && d_pd.alloc(npix * real) != hipSuccess))
-        return fail(TAKE_E_NOMEM, "out of device memory for the temporal accumulation's planes");
-    HIP_TRY(hipMemcpy(d_xy.p, prev_xy, d_xy.bytes(), hipMemcpyHostToDevice));
-    if (prev_depth) HIP_TRY(hipMemcpy(d_pd.p, prev_depth, d_pd.bytes(), hipMemcpyHostToDevice));
-    const TakeTemporalFrame dc{d_cur[0].p, (int32_t *)d_cur[1].p, (double *)d_cur[2].p, (double *)d_cur[3].p, d_cur[4].p, (int32_t *)d_cur[5].p};
-    const TakeTemporalFrame dh{d_hist[0].p, (int32_t *)d_hist[1].p, (double *)d_hist[2].p, (double *)d_hist[3].p, d_hist[4].p, (int32_t *)d_hist[5].p};
-    if (int rc = take_hip_temporal_accumulate_device(&dc, hist ? &dh : nullptr, d_xy.p, d_pd.p, precision, width, height, opts, &dc, nullptr)) return rc;
-    for (int k = 0; k < 6; k++)
-        if (h_out[k] && d_cur[k].p) HIP_TRY(hipMemcpy(h_out[k], d_cur[k].p, d_cur[k].bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    // member by member of TakeTemporalFrame, the current frame's plane (accumulated in place, copied out where `out`
+    // has the member) and the history's; then the motion planes
+    const TakeTemporalFrame none{}, &h = hist ? *hist : none;
+    StagedPlanes<14> st{{plane_inout(cur->rgb, out->rgb, 3 * real), plane_in(h.rgb, 3 * real), plane_inout(cur->count, out->count, 4), plane_in(h.count, 4),
+                         plane_inout(cur->m1, out->m1, 8), plane_in(h.m1, 8), plane_inout(cur->m2, out->m2, 8), plane_in(h.m2, 8),
+                         plane_inout(cur->depth, out->depth, real), plane_in(h.depth, real), plane_inout(cur->shape_id, out->shape_id, 4), plane_in(h.shape_id, 4),
+                         plane_in(prev_xy, 2 * real), plane_in(prev_depth, real)}};
+    if (int rc = st.alloc(npix, "out of device memory for the temporal accumulation's planes")) return rc;
+    if (int rc = st.upload()) return rc;
+    const TakeTemporalFrame dc{st[0], (int32_t *)st[2], (double *)st[4], (double *)st[6], st[8], (int32_t *)st[10]};
+    const TakeTemporalFrame dh{st[1], (int32_t *)st[3], (double *)st[5], (double *)st[7], st[9], (int32_t *)st[11]};
+    if (int rc = take_hip_temporal_accumulate_device(&dc, hist ? &dh : nullptr, st[12], st[13], precision, width, height, opts, &dc, nullptr)) return rc;
+    return st.download();
 }
 
 int take_hip_render_temporal_device(TakeScene *ts, const TakeRenderOpts *ropts, const TakeAdaptiveOpts *aopts, const TakeTemporalOpts *topts,
@@ -429,8 +418,7 @@ int take_hip_render_temporal_device(TakeScene *ts, const TakeRenderOpts *ropts, 
     DenoiseOpts o;
     if (int rc = check_render_temporal_args(ts, ropts, aopts, topts, dopts, d_out, t, o)) return rc;
     TAKE_ON_DEVICE(ts);
-    TakeRenderOpts ro = *ropts;
-    ro.strip_first = 0, ro.strip_stride = 1;  // the whole image, as take_hip_render_denoised_device
+    const TakeRenderOpts ro = whole_image(*ropts);
     const int W = ts->width(), H = ts->height();
     const int64_t npix = (int64_t)W * H;
     const int rc = on_primary(ts, [&](auto &sc, auto &work) {
@@ -445,8 +433,8 @@ int take_hip_render_temporal_device(TakeScene *ts, const TakeRenderOpts *ropts, 
                 if (b->alloc(frame_doubles) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the accumulated frames");
             }
         if (work.temporal_cur.n < cur_doubles && work.temporal_cur.alloc(cur_doubles) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the accumulated frames");
-        if (int rc = work.ensure_denoise((WORK_REALS + 7) * npix)) return rc;
-        R *albedo = work.denoise.p + WORK_REALS * npix, *normal = albedo + 3 * npix, *depth = normal + 3 * npix;
+        DenoiseArena<R> a;
+        if (int rc = denoise_arena(work, npix, false, a)) return rc;
         const tp::Frame<R> cur = frame_at<R>(work.temporal_cur.p, npix);
         R *prev_xy = (R *)(cur.shape_id + npix), *prev_depth = prev_xy + 2 * npix;
         // 1. the frame
@@ -466,13 +454,7 @@ int take_hip_render_temporal_device(TakeScene *ts, const TakeRenderOpts *ropts, 
         // 3. the result is the history from here on
         ts->temporal_history = into;
         // 4. the guides, and the filter on the accumulated image with the accumulated statistics
-        TakeRenderOpts fo = ro;
-        fo.spp = adaptive_min_spp(ro, aopts);
-        const TakeFeatureBuffers planes{albedo, normal, depth, nullptr, nullptr, nullptr};
-        if (int rc = render_features_scene(ts, fo, planes, s)) return rc;
-        if (int rc = denoise_var_enqueue((const R *)acc.rgb, (const R *)albedo, (const R *)normal, (const R *)depth, TakeAdaptiveStats{acc.count, acc.m1, acc.m2}, W, H, o,
-                                         work.denoise.p, (R *)d_out, (R *)nullptr, s))
-            return rc;
+        if (int rc = guides_then_variance_filter(ts, ro, aopts, a, (const R *)acc.rgb, TakeAdaptiveStats{acc.count, acc.m1, acc.m2}, o, (R *)d_out, (R *)nullptr, s)) return rc;
         HIP_TRY(hipStreamSynchronize(s));
         return (int)TAKE_OK;
     });
@@ -486,11 +468,10 @@ int take_hip_render_temporal(TakeScene *ts, const TakeRenderOpts *ropts, const T
     DenoiseOpts o;
     if (int rc = check_render_temporal_args(ts, ropts, aopts, topts, dopts, rgb_out_host, t, o)) return rc;
     TAKE_ON_DEVICE(ts);
-    DevBuf<char> d_out;
-    if (d_out.alloc((size_t)ts->width() * ts->height() * 3 * (ts->f64() ? 8 : 4)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the filtered frame");
-    if (int rc = take_hip_render_temporal_device(ts, ropts, aopts, topts, dopts, restart, d_out.p, nullptr)) return rc;
-    HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
-    return TAKE_OK;
+    StagedPlanes<1> st{{plane_out(rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4))}};
+    if (int rc = st.alloc((size_t)ts->width() * ts->height(), "out of device memory for the filtered frame")) return rc;
+    if (int rc = take_hip_render_temporal_device(ts, ropts, aopts, topts, dopts, restart, st[0], nullptr)) return rc;
+    return st.download();
 }
 
 }  // extern "C"

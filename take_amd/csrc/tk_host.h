@@ -1,7 +1,8 @@
 // tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_create.hip and tk_group.hip (the C entry
 // points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
 // tk_mesh.hip (mesh ingest) and tk_denoise.hip (the image-space denoiser): the error string, fault injection, pinned
-// uploads, the owning device buffer.  (The scene handle all but tk_mesh.hip share is tk_scene_handle.h.)
+// uploads, the owning device buffer, the staged planes of the host twins, the dispatch on a precision.  (The scene
+// handle all but tk_mesh.hip share is tk_scene_handle.h.)
 // Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
 // take_hip_last_error returns) and ONE TAKE_HIP_FAIL_ALLOC counter.
 #pragma once
@@ -127,6 +128,43 @@ template <class T> struct DevBuf {
     }
     size_t bytes() const { return n * sizeof(T); }
 };
+
+// The per-pixel planes of a host twin (take_hip_denoise, take_hip_render_features, ...), staged in device memory for
+// the call's _device twin.  A plane: where it is uploaded from and where it is downloaded to, either null = not that
+// way; both null = absent (an optional plane the caller left out): never allocated, its device pointer is null.
+struct HostPlane {
+    const void *from;
+    void *to;
+    size_t bytes_per_pixel;
+};
+inline HostPlane plane_in(const void *from, size_t bytes_per_pixel) { return {from, nullptr, bytes_per_pixel}; }
+inline HostPlane plane_out(void *to, size_t bytes_per_pixel) { return {nullptr, to, bytes_per_pixel}; }
+// an input the device call changes in place, then copied out: without the input there is no plane, whatever `to` is
+inline HostPlane plane_inout(const void *from, void *to, size_t bytes_per_pixel) { return {from, from ? to : nullptr, bytes_per_pixel}; }
+template <int N> struct StagedPlanes {
+    HostPlane plane[N];
+    DevBuf<char> dev[N];
+    // the present planes for npix pixels, in the order of `plane` (npix = 0: none); nomem: the TAKE_E_NOMEM message
+    int alloc(size_t npix, const char *nomem) {
+        for (int k = 0; k < N; k++)
+            if ((plane[k].from || plane[k].to) && dev[k].alloc(npix * plane[k].bytes_per_pixel) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+        return TAKE_OK;
+    }
+    int upload() {
+        for (int k = 0; k < N; k++)
+            if (plane[k].from && dev[k].p) HIP_TRY(hipMemcpy(dev[k].p, plane[k].from, dev[k].bytes(), hipMemcpyHostToDevice));
+        return TAKE_OK;
+    }
+    int download() {
+        for (int k = 0; k < N; k++)
+            if (plane[k].to && dev[k].p) HIP_TRY(hipMemcpy(plane[k].to, dev[k].p, dev[k].bytes(), hipMemcpyDeviceToHost));
+        return TAKE_OK;
+    }
+    void *operator[](int k) const { return dev[k].p; }
+};
+
+// f(R{}) with R = float or double: the Real of a TAKE_PRECISION_F32 / _F64 value (checked by the caller)
+template <class F> auto with_real(int32_t precision, F &&f) { return precision == TAKE_PRECISION_F64 ? f(double{}) : f(float{}); }
 
 inline int check_device() {
     int n = 0;

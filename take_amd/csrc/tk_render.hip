@@ -948,10 +948,10 @@ int take_hip_pack_exr_scanlines(const void *d_rgb, int32_t precision, int32_t wi
     if (nd < 0) return nd;
     const int64_t total = (int64_t)width * height * 3;
     const dim3 grid((unsigned)std::min<int64_t>((total + BLOCK - 1) / BLOCK, 8192));
-    if (precision == TAKE_PRECISION_F64)
-        hipLaunchKernelGGL((k_pack_exr<double>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const double *)d_rgb, width, height, d_out);
-    else
-        hipLaunchKernelGGL((k_pack_exr<float>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const float *)d_rgb, width, height, d_out);
+    with_real(precision, [&](auto tag) {
+        using R = decltype(tag);
+        hipLaunchKernelGGL((k_pack_exr<R>), grid, dim3(BLOCK), 0, (hipStream_t)stream, (const R *)d_rgb, width, height, d_out);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return TAKE_OK;
