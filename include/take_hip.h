@@ -649,9 +649,29 @@ int take_hip_render_adaptive_denoised(TakeScene *scene, const TakeRenderOpts *op
  * in a two-level scene, a device copy of the placements' current object -> world transforms (12 doubles each, as
  * take_hip_scene_set_instance_transforms takes them).  A later mark replaces the earlier one;
  * take_hip_scene_set_camera, _set_instance_transforms, _set_mesh_vertices and _update_meshes leave it alone (the
- * placement count cannot change under them).  TAKE_E_INVALID: a NULL scene ("null argument", before a device is
- * looked for).  Not for scene groups. */
+ * placement count cannot change under them).  The vertices of the marked frame are not stored, and a vertex that moves
+ * after the mark is not followed, unless tracking is on (take_hip_scene_track_vertices, below).  TAKE_E_INVALID: a NULL
+ * scene ("null argument", before a device is looked for).  Not for scene groups. */
 int take_hip_scene_mark_frame(TakeScene *scene);
+
+/* take_hip_scene_track_vertices: lets the motion pass follow vertices that moved since the mark (a deforming mesh).
+ * flags: 0 = off, the default — every call is what it is without these two symbols, bit for bit, and no update call
+ * costs a byte or a launch more — or TAKE_TRACK_VERTICES.  With tracking on and a mark set, the FIRST successful
+ * take_hip_scene_set_mesh_vertices / _update_meshes after that mark keeps the geometry words of every triangle record
+ * as they were (copy on write: a mark with no update after it costs nothing; 9 Real per record of the side the motion
+ * pass runs on, held as 12 — 48 bytes per record in f32, 96 in f64 — keyed by shape id, and by prototype and face for a
+ * prototype's records, which survive the rebuild's new leaf order).  Further updates before the next mark leave the
+ * copy alone: the marked frame stays the frame at the mark.  take_hip_scene_mark_frame drops it, and so does turning
+ * tracking off; tracking turned on after an update holds nothing until the next mark.  The copy is staged with the
+ * update: a failed update leaves it as it was, and an update that cannot allocate it fails as a whole with TAKE_E_NOMEM
+ * ("out of device memory for the marked frame's geometry").  Spheres do not move; topology does not change.
+ * TAKE_E_INVALID: a NULL scene ("null argument"), any other bit ("unknown flag bits") — both before a device is looked
+ * for.  Not for scene groups.
+ * take_hip_scene_tracking_info: the flags, and the device bytes of marked geometry the handle holds (0: none — the
+ * motion pass is then the one that follows no vertices).  Either out may be NULL. */
+#define TAKE_TRACK_VERTICES 1
+int take_hip_scene_track_vertices(TakeScene *scene, int32_t flags);
+int take_hip_scene_tracking_info(const TakeScene *scene, int32_t *flags, int64_t *marked_bytes);
 
 /* The motion pass: ONE ray per pixel through the pixel's centre (the camera ray of a render with 0.5 in place of the
  * two jitter draws), made by the closest-hit launch that traces it, then one streaming kernel.  Of the options only
@@ -660,7 +680,10 @@ int take_hip_scene_mark_frame(TakeScene *scene);
  * dot products (a.x * b.x + a.y * b.y) + a.z * b.z, a 3 x 4 map applied row by row as ((m0 * x + m1 * y) + m2 * z) + m3:
  *   a hit at t:  P = o + d * t;  in placement i:  P' = M_i(marked) * (inv_i(current) * P) with the marked transform's
  *     doubles rounded to Real, otherwise P' = P (a vertex that moved since the mark is not followed: the surface counts
- *     as rigid in its mesh; the validity tests of the accumulation reject what no longer matches);  e = P' - lookfrom';
+ *     as rigid in its mesh; the validity tests of the accumulation reject what no longer matches — unless tracking is
+ *     on and the handle holds marked geometry: then a TRIANGLE hit with barycentrics u, v and the marked words v0', e1',
+ *     e2' of its record has Q' = (v0' + e1' * u) + e2' * v per component, P' = M_i(marked) * Q' in placement i — no
+ *     inverse — and P' = Q' otherwise; sphere hits and misses are as without tracking);  e = P' - lookfrom';
  *   a miss:  e = d (a point at infinity), depth = prev_depth = 0, shape_id = -1 — a static camera keeps its background
  *     history, a rotating one moves it;
  *   with the MARKED camera (u', v', w', lookfrom', viewport'):  z = -(w' . e);  z <= 0: prev_xy = (-2, -2), prev_depth =

@@ -36,6 +36,7 @@ EXPORTS = [
     "take_hip_denoise_variance", "take_hip_denoise_variance_device", "take_hip_render_adaptive_denoised", "take_hip_render_adaptive_denoised_device",
     "take_hip_scene_mark_frame", "take_hip_render_motion", "take_hip_render_motion_device",
     "take_hip_temporal_accumulate", "take_hip_temporal_accumulate_device", "take_hip_render_temporal", "take_hip_render_temporal_device",
+    "take_hip_scene_track_vertices", "take_hip_scene_tracking_info",
 ]
 
 
@@ -83,7 +84,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -632,6 +633,19 @@ class Scene:
         """store "the previous frame" in the handle (take_hip_scene_mark_frame): the current camera and, in a two-level
         scene, the placements' current transforms — what render_motion takes surface points back to"""
         _check(lib().take_hip_scene_mark_frame(self.h))
+
+    def track_vertices(self, on=True):
+        """let the motion pass follow vertices that move after a mark (take_hip_scene_track_vertices): with tracking on,
+        the first set_mesh_vertices / update_meshes after a mark keeps the marked frame's geometry; off (the default)
+        drops it"""
+        _check(lib().take_hip_scene_track_vertices(self.h, D.TAKE_TRACK_VERTICES if on else 0))
+
+    def tracking_info(self):
+        """-> {"flags", "marked_bytes"}: whether tracking is on, and the device bytes of marked geometry the handle holds
+        (take_hip_scene_tracking_info)"""
+        flags, held = C.c_int32(-1), C.c_int64(-1)
+        _check(lib().take_hip_scene_tracking_info(self.h, C.byref(flags), C.byref(held)))
+        return {"flags": flags.value, "marked_bytes": held.value}
 
     def render_motion(self, ray_epsilon=0.0, want=tuple(D.MOTION_PLANES)):
         """the motion pass against the marked frame (take_hip_render_motion) -> {name: host array} for the names in

@@ -236,6 +236,13 @@ TEMPORAL_PROTOTYPES = {
                                  C.c_int32, C.c_void_p],
 }
 
+# following moved vertices in the motion pass (include/take_hip.h): name -> argument types
+TAKE_TRACK_VERTICES = 1
+TRACKING_PROTOTYPES = {
+    "take_hip_scene_track_vertices": [C.c_void_p, C.c_int32],
+    "take_hip_scene_tracking_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+}
+
 
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3

@@ -310,14 +310,28 @@ static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n
         MeshUpdateInputs in;
         int rc = in.upload(ts->mesh_vertices, updates, n_updates);
         if (rc) return rc;
-        if (two_level)
-            return stage_then_commit<ProtoUpdateStage>(ts, [&](const auto &sc, auto &stage) {
+        // take_hip_scene_track_vertices: the first update after a mark keeps the geometry words of the primary side's
+        // records as they are now — staged with the update, and the handle's only when every side committed
+        TakeScene::FrameMark kept;
+        const bool keep = ts->track_flags && ts->mark.set && !ts->mark.updated && !ts->mark.has_geometry();
+        if (keep) {
+            rc = ts->f64() ? copy_marked_geometry(ts->d, kept.geom_d, kept.inst_first) : copy_marked_geometry(ts->f, kept.geom_f, kept.inst_first);
+            if (rc) return rc;
+        }
+        if (two_level) {
+            rc = stage_then_commit<ProtoUpdateStage>(ts, [&](const auto &sc, auto &stage) {
                 return update_two_level_meshes_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->xforms.p, ts->max_leaf, stage);
             });
-        const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
-        return stage_then_commit<MeshUpdateStage>(ts, [&](const auto &sc, auto &stage) {
-            return update_mesh_vertices_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, stage);
-        });
+        } else {
+            const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
+            rc = stage_then_commit<MeshUpdateStage>(ts, [&](const auto &sc, auto &stage) {
+                return update_mesh_vertices_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, stage);
+            });
+        }
+        if (rc) return rc;
+        ts->mark.updated = true;
+        if (keep) ts->mark.geom_f = std::move(kept.geom_f), ts->mark.geom_d = std::move(kept.geom_d), ts->mark.inst_first = std::move(kept.inst_first);
+        return TAKE_OK;
     } catch (const std::bad_alloc &) {
         return fail(TAKE_E_NOMEM, "out of host memory while updating the meshes");
     } catch (const std::exception &e) {
@@ -348,8 +362,28 @@ int take_hip_scene_mark_frame(TakeScene *ts) {
         HIP_TRY(hipMemcpy(copy.p, ts->xforms.p, copy.bytes(), hipMemcpyDeviceToDevice));
     }
     ts->mark.xforms = std::move(copy);
+    ts->mark.drop_geometry(), ts->mark.updated = false;  // (the records are the marked ones again)
     ts->mark.cam_f = ts->f.dev.cam, ts->mark.cam_d = ts->d.dev.cam;  // (a side the scene does not have: never read)
     ts->mark.set = true;
+    return TAKE_OK;
+}
+
+// Following moved vertices in the motion pass (include/take_hip.h): a switch in the handle; what it holds is made by
+// update_meshes and dropped by take_hip_scene_mark_frame.
+int take_hip_scene_track_vertices(TakeScene *ts, int32_t flags) {
+    if (!ts) return fail(TAKE_E_INVALID, "null argument");
+    if (flags & ~TAKE_TRACK_VERTICES) return fail(TAKE_E_INVALID, "unknown flag bits");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    if (!flags) ts->mark.drop_geometry();
+    ts->track_flags = flags;
+    return TAKE_OK;
+}
+int take_hip_scene_tracking_info(const TakeScene *ts, int32_t *flags, int64_t *marked_bytes) {
+    if (!ts) return fail(TAKE_E_INVALID, "null argument");
+    if (flags) *flags = ts->track_flags;
+    if (marked_bytes) *marked_bytes = (int64_t)(ts->mark.geom_f.bytes() + ts->mark.geom_d.bytes() + ts->mark.inst_first.bytes());
     return TAKE_OK;
 }
 

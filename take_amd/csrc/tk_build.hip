@@ -1035,4 +1035,39 @@ template int update_two_level_meshes_device<float>(const SceneT<float> &, const 
 template int update_two_level_meshes_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, const double *, int,
                                                     ProtoUpdateStage<double> &);
 
+// ---- take_hip_scene_track_vertices: the marked geometry of a side, before a mesh update replaces its records
+template <class R> int copy_marked_geometry(const SceneT<R> &sc, DevBuf<R> &words, DevBuf<int32_t> &inst_first) {
+    using namespace lbvh;
+    const HostScene<R> &h = sc.host;
+    const int64_t n = (int64_t)sc.prims.n, n_inst = (int64_t)sc.inst_trace.n;
+    const int n_protos = n_inst > 0 ? (int)h.blas_prim_first.size() : 0;
+    const int64_t n_shapes = n - (n_inst > 0 ? h.blas_prims : 0);
+    hipStream_t stream = nullptr;
+    if (n_inst > 0 && ((int)h.blas_prim_count.size() != n_protos || (int64_t)h.placements.inst_proto.size() != n_inst || n_shapes < 0))
+        return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
+    const char *nomem = "out of device memory for the marked frame's geometry";
+    if (words.alloc((size_t)n * MARKED_STRIDE) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+    if (n_shapes > 0) hipLaunchKernelGGL(k_copy_marked<R>, blocks_for(n_shapes), dim3(BLK), 0, stream, sc.prims.p, (int)n_shapes, words.p);
+    std::vector<int32_t> first((size_t)n_inst);
+    for (int k = 0; k < n_protos; k++) {
+        const int64_t at = h.blas_prim_first[k], nf = h.blas_prim_count[k];
+        if (at < n_shapes || nf < 0 || at + nf > n) return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
+        if (nf > 0) hipLaunchKernelGGL(k_copy_marked<R>, blocks_for(nf), dim3(BLK), 0, stream, sc.prims.p + at, (int)nf, words.p + MARKED_STRIDE * at);
+    }
+    for (int64_t i = 0; i < n_inst; i++) {
+        const int32_t k = h.placements.inst_proto[(size_t)i];
+        if (k < 0 || k >= n_protos) return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
+        first[(size_t)i] = (int32_t)h.blas_prim_first[k];
+    }
+    if (n_inst > 0) {
+        if (inst_first.alloc((size_t)n_inst) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+        HIP_TRY(hipMemcpy(inst_first.p, first.data(), inst_first.bytes(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    return TAKE_OK;
+}
+template int copy_marked_geometry<float>(const SceneT<float> &, DevBuf<float> &, DevBuf<int32_t> &);
+template int copy_marked_geometry<double>(const SceneT<double> &, DevBuf<double> &, DevBuf<int32_t> &);
+
 }  // namespace tk_host

@@ -33,6 +33,8 @@
 // Moving the vertices of prototype meshes of a resident two-level scene (take_hip_scene_update_meshes) adds
 //   k_update_proto_prims     a moved prototype's object-space records from its new positions, with the finiteness check
 //   k_retarget_placements    the placements' roots (every prototype's nodes may move) and the moved prototypes' grids
+// Following moved vertices in the motion pass (take_hip_scene_track_vertices) adds
+//   k_copy_marked      the geometry words of the records an update is about to replace, by record identity
 //
 // The tree is an LBVH: built in milliseconds, but without the SAH its boxes overlap more, so traversal visits more
 // nodes than with the host build (numbers in DESIGN.md).  Results do not depend on the tree (conservative box
@@ -51,6 +53,7 @@
 #include <limits>
 
 #include "tk_bvh.h"
+#include "tk_motion_pixel.h"
 #include "tk_round.h"
 #include "tk_scene.h"
 
@@ -808,6 +811,28 @@ k_retarget_placements(InstTrace<R> *trace, int n, const int32_t *__restrict__ in
     } else if (trace[i].root_child >= 0) {
         trace[i].root_child += t.shift;
     }
+}
+
+
+// ---- the marked geometry (take_hip_scene_track_vertices; layout and look-up: tk_motion_pixel.h).  One lane per record
+// of a run whose shape ids are a permutation of 0 .. n-1 — the shapes' records, or one prototype's, whose shape id is
+// the face — in the leaf order of the tree an update is about to replace; the 9 geometry words go to entry[its shape
+// id] as whole 16-byte words (3 in f32, 6 in f64: an entry is MARKED_STRIDE Reals, the last three zero), bit for bit.
+// Per record: 64 (f32) / 96 (f64) bytes read, 48 / 96 written.
+template <class R> __global__ void __launch_bounds__(BLK) k_copy_marked(const PrimRec<R> *__restrict__ recs, int n, R *__restrict__ entries) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    const int32_t id = recs[i].shape_id;
+    if ((uint32_t)id >= (uint32_t)n) return;  // (never: the host checked that the scene has one record per shape)
+    constexpr int QUADS = (int)(MARKED_STRIDE * sizeof(R) / sizeof(uint4));
+    static_assert(MARKED_STRIDE >= 9 && MARKED_STRIDE * sizeof(R) % sizeof(uint4) == 0, "an entry is whole 16-byte words");
+    union {
+        R r[MARKED_STRIDE];
+        uint4 q[QUADS];
+    } e;
+    for (int k = 0; k < MARKED_STRIDE; k++) e.r[k] = k < 9 ? recs[i].a[k] : R(0);
+    uint4 *dst = reinterpret_cast<uint4 *>(entries + MARKED_STRIDE * (int64_t)id);
+    for (int k = 0; k < QUADS; k++) dst[k] = e.q[k];
 }
 
 }  // namespace lbvh

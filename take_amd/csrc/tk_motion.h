@@ -6,12 +6,15 @@
 //   CentreCameraIo   the camera ray through the pixel centre, made by the closest-hit launch that traces it (CameraIo
 //                    with 0.5 in place of the two draws: no generate pass, no random stream)
 //   k_motion         per pixel: the hit the launch left in the path record -> P -> through the placement's current
-//                    inverse and its marked transform -> projected with the marked camera -> the caller's planes
+//                    inverse and its marked transform -> projected with the marked camera -> the caller's planes;
+//                    TRACKED (the handle holds marked geometry: take_hip_scene_track_vertices): a triangle hit goes
+//                    back through the words its record had at the mark instead (tk_motion_pixel.h: tracked_pixel)
 //
 // The pass is one closest-hit launch followed by k_motion.  Nothing here is reached by a render.
 #pragma once
 
 #include "tk_features.h"
+#include "tk_motion_pixel.h"
 
 namespace tk {
 
@@ -42,28 +45,14 @@ template <class R> struct MotionOut {  // TakeMotionBuffers for records of preci
     int32_t *shape_id;
 };
 
-// a 3 x 4 row-major affine map applied to a point, each row ((m0 * x + m1 * y) + m2 * z) + m3
-template <class R> TK_HD Vec3<R> affine_point(const R *m, Vec3<R> p) {
-    return {((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3], ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7], ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11]};
-}
-template <class R> TK_HD R dot3(const R *a, Vec3<R> e) { return (a[0] * e.x + a[1] * e.y) + a[2] * e.z; }
-
-// e (P' - lookfrom', or a direction for a point at infinity) projected with the marked camera -> plane coordinates
-// (column, row), a pixel's centre at +0.5; false: behind the camera (z <= 0, or not a number)
-template <class R> TK_HD bool project_marked(const CameraRec<R> &m, Vec3<R> e, R &px, R &py) {
-    const R z = -dot3(m.w, e);
-    if (!(z > R(0))) return false;
-    const R sx = (dot3(m.u, e) / z / m.viewport_width + R(0.5)) * R(m.width);
-    const R sy = (dot3(m.v, e) / z / m.viewport_height + R(0.5)) * R(m.height);
-    px = sx, py = R(m.height) - sy;
-    return true;
-}
-
 // marked: the camera of the marked frame; marked_xforms: the placements' object -> world transforms of the marked
-// frame, 12 doubles each (null in a scene without placements), each rounded to R once where it is used
-template <class R>
+// frame, 12 doubles each (null in a scene without placements), each rounded to R once where it is used.
+// TRACKED: geom is the marked geometry (its words never null); per pixel one more gather, of the 9 words of the hit
+// record's entry (36 bytes in f32, 72 in f64), and no read of the placement's inverse for a triangle.
+template <class R, bool TRACKED>
 __global__ void __launch_bounds__(BLOCK)
-k_motion(DeviceScene<R> sc, PathState<R> st, CameraRec<R> marked, const double *__restrict__ marked_xforms, MotionOut<R> out, int32_t width, int32_t n_local_rows) {
+k_motion(DeviceScene<R> sc, PathState<R> st, CameraRec<R> marked, const double *__restrict__ marked_xforms, MarkedGeometry<R> geom, MotionOut<R> out, int32_t width,
+         int32_t n_local_rows) {
     const int32_t npix = width * n_local_rows;
     for (int32_t p = blockIdx.x * BLOCK + threadIdx.x; p < npix; p += gridDim.x * BLOCK) {
         const int64_t slot = p;
@@ -71,6 +60,31 @@ k_motion(DeviceScene<R> sc, PathState<R> st, CameraRec<R> marked, const double *
         const Vec3<R> rd{st.R_(S_DX, slot), st.R_(S_DY, slot), st.R_(S_DZ, slot)};
         R depth = R(0), prev_depth = R(0), px = R(-2), py = R(-2);
         int32_t shape = -1;
+        if constexpr (TRACKED) {
+            MotionHit<R> h{MOTION_MISS, Vec3<R>{R(0), R(0), R(0)}, rd, R(0), R(0), R(0), nullptr, nullptr, nullptr};
+            if (prim >= 0) {
+                const int32_t inst = sc.inst_shade ? st.I_(S_INST, slot) : -1;
+                const int32_t id = sc.prims[prim].shape_id;  // the shape id, or the face of a prototype's record
+                const bool in_placement = inst >= 0 && marked_xforms;
+                h.ro = {st.R_(S_OX, slot), st.R_(S_OY, slot), st.R_(S_OZ, slot)};
+                h.t = depth = st.R_(S_HT, slot);
+                shape = inst >= 0 ? id + sc.inst_shade[inst].shape_base : id;
+                if (in_placement) h.inv = sc.inst_trace[inst].inv, h.fwd = marked_xforms + 12 * (int64_t)inst;
+                if ((sc.prims[prim].meta & 0xff) == PRIM_TRIANGLE) {
+                    h.kind = MOTION_TRIANGLE, h.u = st.R_(S_HU, slot), h.v = st.R_(S_HV, slot);
+                    h.words = geom.words + MARKED_STRIDE * ((int64_t)id + (inst >= 0 ? geom.inst_first[inst] : 0));
+                } else {
+                    h.kind = MOTION_POINT;
+                }
+            }
+            tracked_pixel(marked, h, px, py, prev_depth);
+            const int64_t o = feature_out_index(p, width, n_local_rows);
+            if (out.prev_xy) out.prev_xy[2 * o] = px, out.prev_xy[2 * o + 1] = py;
+            if (out.prev_depth) out.prev_depth[o] = prev_depth;
+            if (out.depth) out.depth[o] = depth;
+            if (out.shape_id) out.shape_id[o] = shape;
+            continue;
+        }
         Vec3<R> e = rd;  // a miss: a point at infinity
         if (prim >= 0) {
             const R t = st.R_(S_HT, slot);

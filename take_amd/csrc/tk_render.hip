@@ -720,10 +720,11 @@ int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
 // whole image that makes the centre rays itself (CentreCameraIo: the work list is the identity, no queue is read),
 // then k_motion over its records.  Path records and queue words only, as the feature pass: a progressive sequence goes
 // on afterwards.  marked / marked_xforms: the camera and the placements' transforms the points are taken back to.
+// geom: the marked geometry the handle holds (words null: none — the instance that follows no vertices).
 // The timer files k_motion under the shade class.
 template <class R>
 int motion_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &opts, const TakeMotionBuffers &b, const CameraRec<R> &marked,
-                const double *marked_xforms, hipStream_t stream) {
+                const double *marked_xforms, const MarkedGeometry<R> &geom, hipStream_t stream) {
     const MotionOut<R> out{(R *)b.prev_xy, (R *)b.prev_depth, (R *)b.depth, b.shape_id};
     if (!out.prev_xy && !out.prev_depth && !out.depth && !out.shape_id)
         return fail(TAKE_E_INVALID, "no motion buffer was asked for: every pointer of TakeMotionBuffers is NULL");
@@ -746,7 +747,9 @@ int motion_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const Ta
     HIP_TRY(launch_trace(sc, false, false, sc.trace_state.grid_for(npix), stream, io, q + Q_N_EXT0, 0, q + Q_HEAD_CLOSEST, work.counters.p, (int)C_RAYS_CLOSEST));
     fr.tm.end();
     fr.tm.begin(TK_SHADE);
-    hipLaunchKernelGGL((k_motion<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, marked, sc.dev.inst_trace ? marked_xforms : nullptr, out, fr.rp.width, fr.n_rows);
+    const double *xf = sc.dev.inst_trace ? marked_xforms : nullptr;
+    if (geom.words) hipLaunchKernelGGL((k_motion<R, true>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, marked, xf, geom, out, fr.rp.width, fr.n_rows);
+    else hipLaunchKernelGGL((k_motion<R, false>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, marked, xf, geom, out, fr.rp.width, fr.n_rows);
     fr.tm.end();
     return end_frame(fr, (uint64_t)npix);
 }
@@ -927,7 +930,18 @@ int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotion
         // (k_motion indexes the marked transforms with the hit's placement)
         if (marked && sc.inst_trace.n > 0 && ts->mark.xforms.n != 12 * sc.inst_trace.n)
             return fail(TAKE_E_INVALID, "unsupported: the marked frame does not have one transform per placement record (a scene built under TAKE_HIP_BRAID > 1)");
-        return motion_impl(ts, sc, work, o, d_out, *cam, marked ? ts->mark.xforms.p : nullptr, stream);
+        // the marked geometry, when the handle holds it (take_hip_scene_track_vertices): one entry per record, and per
+        // placement record the first entry of its prototype
+        MarkedGeometry<R> geom{nullptr, nullptr};
+        if (marked && ts->mark.has_geometry()) {
+            if constexpr (sizeof(R) == 8) geom.words = ts->mark.geom_d.p;
+            else geom.words = ts->mark.geom_f.p;
+            const size_t held = sizeof(R) == 8 ? ts->mark.geom_d.n : ts->mark.geom_f.n;
+            geom.inst_first = ts->mark.inst_first.p;
+            if (!geom.words || held != (size_t)MARKED_STRIDE * sc.prims.n || ts->mark.inst_first.n != sc.inst_trace.n)
+                return fail(TAKE_E_INVALID, "unsupported: the marked geometry does not have one entry per primitive record");
+        }
+        return motion_impl(ts, sc, work, o, d_out, *cam, marked ? ts->mark.xforms.p : nullptr, geom, stream);
     });
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {

@@ -207,7 +207,17 @@ struct TakeScene {
         tk::CameraRec<float> cam_f{};
         tk::CameraRec<double> cam_d{};
         tk_host::DevBuf<double> xforms;
+        // take_hip_scene_track_vertices: the marked geometry (tk_motion_pixel.h: MarkedGeometry) of the primary side, in
+        // its Real — made by the first mesh update after the mark (copy on write: until then the scene's records are the
+        // marked ones), dropped by the next mark and by turning tracking off.  inst_first: per placement.
+        tk_host::DevBuf<float> geom_f;
+        tk_host::DevBuf<double> geom_d;
+        tk_host::DevBuf<int32_t> inst_first;
+        bool updated = false;  // a mesh update succeeded since the mark: the scene's records are no longer the marked ones
+        bool has_geometry() const { return geom_f.p || geom_d.p; }
+        void drop_geometry() { geom_f.release(), geom_d.release(), inst_first.release(); }
     } mark;
+    int track_flags = 0;  // take_hip_scene_track_vertices
     int temporal_history = -1;  // take_hip_render_temporal*: which of the workspace's two accumulated frames is the history (-1: none)
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
     int instrumentation = 0;
@@ -311,6 +321,11 @@ int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits
 int check_adaptive_opts(const TakeAdaptiveOpts *a);
 
 // ---- defined in tk_build.hip
+// The marked geometry of a side whose records are still the marked frame's (take_hip_scene_track_vertices; layout:
+// tk_motion_pixel.h), made aside before a mesh update is staged: words = one entry per record of sc, inst_first = per
+// placement record the first entry of its prototype (empty without placements).  TAKE_E_NOMEM with its own message.
+template <class R> int copy_marked_geometry(const SceneT<R> &sc, DevBuf<R> &words, DevBuf<int32_t> &inst_first);
+
 // What k_make_prims — and, in a two-level scene, k_make_proto_prims and k_placement_boxes — read of the caller's
 // arrays, in device memory: the mesh positions as they are (double, one copy per mesh, no host staging) and the four
 // shape arrays.  Uploaded once per scene: both sides of a mixed-precision scene make their records from these.
