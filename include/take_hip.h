@@ -772,6 +772,94 @@ int take_hip_render_temporal_device(TakeScene *scene, const TakeRenderOpts *opts
 int take_hip_render_temporal(TakeScene *scene, const TakeRenderOpts *opts, const TakeAdaptiveOpts *adaptive,
                              const TakeTemporalOpts *temporal, const TakeDenoiseOpts *denoise, int32_t restart, void *rgb_out_host);
 
+/* ---- display transform (new symbols of ABI version 5; no struct changed): the last stage of the image-space chain —
+ * a luminance histogram made on the device, an auto-exposure derived from it (with temporal adaptation, so that the
+ * frames of a sequence share an exposure that follows the scene smoothly), and one fused pass exposure -> tone operator
+ * -> sRGB transfer -> 8-bit RGBA.  EXTENSION without an upstream counterpart — parity unpinned with respect to the
+ * reference; specified against its own restatement (tests/display_ref.py; DESIGN.md par. 4j has the arithmetic
+ * operation by operation).  Scene-free and deterministic: the same planes give the same bits.
+ * Planes as take_hip_render_device leaves them: rgb height * width * 3 Real, row 0 = top; Real = float or double by
+ * `precision`.
+ *
+ * The histogram.  Per pixel Y = ((0.2126 r) + (0.7152 g)) + (0.0722 b) in Real (Rec.709), rounded to float (nearest
+ * even).  NaN or an infinity — a double beyond float's range included — counts in slot [385]; Y <= 0 in slot [384];
+ * every other pixel in bin clamp((float_bits(Y) >> 20) - 8 * (127 - 24), 0, 383): the 8 exponent bits and the top 3
+ * mantissa bits, 8 bins per octave over [2^-24, 2^24), what lies outside in the end bins.  No logarithm is taken: the
+ * counts are exact, and the 386 slots sum to width * height. */
+#define TAKE_LUMINANCE_BINS 384
+#define TAKE_LUMINANCE_SLOTS 386 /* the bins, then [384] non-positive, [385] non-finite */
+/* d_rgb: device memory of the current device; hist_out_host: TAKE_LUMINANCE_SLOTS counts in HOST memory (both calls).
+ * The block histograms and their sum are allocated per call.  Enqueued on `stream`, returns after it has completed.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL pointer ("null argument"), width or height <= 0, an
+ * unknown precision (MIXED is a scene's, not a plane's: its planes are F64). */
+int take_hip_luminance_histogram_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, int64_t *hist_out_host,
+                                        void *stream);
+/* the same with a host pointer (upload, the same kernels) */
+int take_hip_luminance_histogram(const void *rgb, int32_t precision, int32_t width, int32_t height, int64_t *hist_out);
+
+/* The auto-exposure of a histogram: the factor that takes the log-average luminance of the pixels between two
+ * percentiles to `key`.  Host only, in double, needs no device.  In this order:
+ *   1. N = the sum of the 384 bins (the two extra slots are left out); N == 0: target = 1, on to step 7;
+ *   2. a = low_fraction * N, z = high_fraction * N; the bins in ascending order, c0 the count before bin b, c1 after it;
+ *   3. the bin's weight w_b = max(0, min(c1, z) - max(c0, a)): the part of it between the percentiles;
+ *   4. its representative log2 luminance l_b = e + log2(1 + (m + 0.5) / 8), e = b / 8 - 24, m = b % 8;
+ *   5. mean = sum(w_b l_b) / sum(w_b); if sum(w_b) <= 0, with w_b = the bin's count instead;
+ *   6. target = key / exp2(mean);
+ *   7. with prev_exposure > 0: E = exp2(log2(prev) + rate * (log2(target) - log2(prev))) — a step of `rate` in log2,
+ *      rate 1 jumps to the target; without: E = target;
+ *   8. E clamped to [min_exposure, max_exposure].
+ * TAKE_E_INVALID: a NULL hist or exposure_out ("null argument"), a negative count in any of the 386 slots, an option
+ * that is not finite, low_fraction >= high_fraction, high_fraction > 1, rate > 1, min_exposure > max_exposure (each
+ * after the defaults are filled in).  opts: NULL = defaults. */
+typedef struct TakeExposureOpts { /* every field: <= 0 (low_fraction: < 0) = its default */
+    double key;                   /* <= 0: 0.18 */
+    double low_fraction;          /* < 0: 0.05 */
+    double high_fraction;         /* <= 0: 0.95 */
+    double min_exposure;          /* <= 0: 2^-16 */
+    double max_exposure;          /* <= 0: 2^16 */
+    double prev_exposure;         /* <= 0: none (no adaptation) */
+    double rate;                  /* <= 0: 1.0 (jump to the target); in (0, 1]: the step in log2 */
+} TakeExposureOpts;
+int take_hip_auto_exposure(const int64_t *hist, const TakeExposureOpts *opts, double *exposure_out);
+
+/* The fused pass.  Per channel c, in Real, every operation in the order written:
+ *   1. x = c * E;   2. if (!(x > 0)) x = 0 (NaN and negatives become 0);   3. x = min(x, 65504);
+ *   4. the operator: LINEAR y = x; REINHARD y = x * (1 + x / white^2) / (1 + x); ACES (Narkowicz's rational fit)
+ *      y = (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14);
+ *   5. y = min(y, 1);
+ *   6. the transfer: SRGB y <= 0.0031308 ? 12.92 y : 1.055 pow(y, 1 / 2.4) - 0.055 (the library's pow / powf); LINEAR none;
+ *   7. RGBA: code = (int)(y * 255 + 0.5), the bytes R, G, B, 255 per pixel; REAL: the three y.
+ * E (and 1 / white^2) are computed in double and rounded to Real once. */
+#define TAKE_TONEMAP_LINEAR 0
+#define TAKE_TONEMAP_REINHARD 1
+#define TAKE_TONEMAP_ACES 2
+#define TAKE_TRANSFER_SRGB 0
+#define TAKE_TRANSFER_LINEAR 1
+#define TAKE_DISPLAY_RGBA 0 /* uint8 x 4 per pixel */
+#define TAKE_DISPLAY_REAL 1 /* 3 Reals per pixel; out may be rgb */
+typedef struct TakeTonemapOpts {
+    double exposure;            /* > 0: used as given; <= 0: auto (the histogram + take_hip_auto_exposure with `auto_opts`) */
+    double white;               /* REINHARD; <= 0: 4.0 */
+    int32_t op;                 /* TAKE_TONEMAP_* */
+    int32_t transfer;           /* TAKE_TRANSFER_* */
+    int32_t format;             /* TAKE_DISPLAY_* */
+    int32_t reserved;           /* 0 */
+    TakeExposureOpts auto_opts; /* read (and checked) whether or not the exposure is automatic */
+} TakeTonemapOpts;
+/* d_rgb, d_out: device memory of the current device; d_out: height * width * 4 bytes (RGBA, 4-byte aligned) or height *
+ * width * 3 Real (REAL; may be d_rgb itself, no other aliasing).  opts: NULL = ACES, sRGB, RGBA, automatic exposure with
+ * the default options.  exposure_used (may be NULL; HOST memory in both calls): the E that was applied.  With an
+ * automatic exposure the call is take_hip_luminance_histogram_device + take_hip_auto_exposure + the pass with that E,
+ * made by hand.  Enqueued on `stream`, returns after it has completed.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL d_rgb / d_out ("null argument"), width or height <= 0,
+ * an unknown precision, an unknown op / transfer / format, reserved != 0, an exposure or white that is not finite, what
+ * take_hip_auto_exposure refuses of auto_opts, RGBA output that overlaps the input or is not 4-byte aligned. */
+int take_hip_tonemap_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts,
+                            void *d_out, double *exposure_used, void *stream);
+/* the same with host pointers (upload, the same kernels, download) */
+int take_hip_tonemap(const void *rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts, void *out,
+                     double *exposure_used);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

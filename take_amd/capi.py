@@ -37,6 +37,7 @@ EXPORTS = [
     "take_hip_scene_mark_frame", "take_hip_render_motion", "take_hip_render_motion_device",
     "take_hip_temporal_accumulate", "take_hip_temporal_accumulate_device", "take_hip_render_temporal", "take_hip_render_temporal_device",
     "take_hip_scene_track_vertices", "take_hip_scene_tracking_info",
+    "take_hip_luminance_histogram", "take_hip_luminance_histogram_device", "take_hip_auto_exposure", "take_hip_tonemap", "take_hip_tonemap_device",
 ]
 
 
@@ -84,7 +85,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -336,6 +337,84 @@ def temporal_accumulate_device(cur, hist, prev_xy, prev_depth, width, height, pr
     _check(lib().take_hip_temporal_accumulate_device(C.byref(c), None if hf is None else C.byref(hf), C.c_void_p(_pointer(prev_xy)), C.c_void_p(_pointer(prev_depth)),
                                                      int(precision), int(width), int(height), None if opts is None else C.byref(opts), C.byref(o),
                                                      C.c_void_p(stream or 0)))
+
+
+def _image(img):
+    """a host image as the display calls take it -> (contiguous (H, W, 3) array, its TAKE_PRECISION_*)"""
+    img = np.asarray(img)
+    if img.dtype not in (np.float32, np.float64) or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("the image must be a (H, W, 3) float32 or float64 array")
+    return np.ascontiguousarray(img), D.TAKE_PRECISION_F32 if img.dtype == np.float32 else D.TAKE_PRECISION_F64
+
+
+def luminance_histogram(img):
+    """the luminance histogram of a host image (take_hip_luminance_histogram, include/take_hip.h), made on the device:
+    img (H, W, 3) float32 or float64 -> int64 (386,): 384 bins, 8 per octave over [2^-24, 2^24), then the counts of
+    the non-positive and of the non-finite luminances"""
+    img, precision = _image(img)
+    hist = np.zeros(D.TAKE_LUMINANCE_SLOTS, np.int64)
+    _check(lib().take_hip_luminance_histogram(img.ctypes.data, precision, img.shape[1], img.shape[0], hist.ctypes.data_as(C.POINTER(C.c_int64))))
+    return hist
+
+
+def luminance_histogram_device(ptr, width, height, precision, stream=None):
+    """the same of an image in device memory (take_hip_luminance_histogram_device): ptr is a torch device tensor or an
+    integer device pointer of `precision`'s Real -> the host histogram; blocks until done"""
+    hist = np.zeros(D.TAKE_LUMINANCE_SLOTS, np.int64)
+    _check(lib().take_hip_luminance_histogram_device(C.c_void_p(_pointer(ptr)), int(precision), int(width), int(height),
+                                                     hist.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(stream or 0)))
+    return hist
+
+
+def auto_exposure(hist, opts=None, **kw):
+    """the exposure that takes the log-average luminance between two percentiles of `hist` (a luminance_histogram) to
+    the key (take_hip_auto_exposure: host arithmetic, needs no GPU).  Options: keywords of cdefs.exposure_opts (key,
+    low_fraction, high_fraction, min_exposure, max_exposure, prev_exposure, rate), or opts = a TakeExposureOpts; neither
+    = the library's defaults (a NULL pointer).  With prev_exposure the result moves from it towards the target by `rate`
+    in log2: feed each frame's result to the next."""
+    h = np.ascontiguousarray(hist)
+    if h.dtype != np.int64 or h.shape != (D.TAKE_LUMINANCE_SLOTS,):
+        raise ValueError(f"hist must be an int64 array of {D.TAKE_LUMINANCE_SLOTS} counts")
+    opts = _keyword_opts(D.exposure_opts, opts, kw)
+    out = C.c_double(0.0)
+    _check(lib().take_hip_auto_exposure(h.ctypes.data_as(C.POINTER(C.c_int64)), None if opts is None else C.byref(opts), C.byref(out)))
+    return out.value
+
+
+def _tonemap_opts(opts, exposure, op, transfer, format, kw):
+    if opts is not None:
+        if kw or exposure is not None:
+            raise ValueError("give opts or keywords, not both")
+        return opts
+    return D.tonemap_opts(exposure, op, transfer, format, **kw)
+
+
+def tonemap(img, exposure=None, op="aces", transfer="srgb", format="rgba", opts=None, **kw):
+    """the display transform of a host image (take_hip_tonemap, include/take_hip.h): exposure, tone operator ("linear",
+    "reinhard", "aces"), transfer ("srgb", "linear"), on the device -> (array, exposure_used): uint8 (H, W, 4) for
+    format "rgba", (H, W, 3) of img's dtype for "real".  exposure None = automatic: the auto_exposure of the image's
+    luminance_histogram, with the further keywords (white for "reinhard", and those of cdefs.exposure_opts); or opts = a
+    TakeTonemapOpts instead of all keywords."""
+    img, precision = _image(img)
+    o = _tonemap_opts(opts, exposure, op, transfer, format, kw)
+    h, w = img.shape[:2]
+    out = np.zeros((h, w, 4), np.uint8) if o.format == D.TAKE_DISPLAY_RGBA else np.zeros_like(img)
+    used = C.c_double(0.0)
+    _check(lib().take_hip_tonemap(img.ctypes.data, precision, w, h, C.byref(o), out.ctypes.data, C.byref(used)))
+    return out, used.value
+
+
+def tonemap_device(rgb, width, height, precision, out=None, exposure=None, op="aces", transfer="srgb", format="rgba", opts=None, stream=None, **kw):
+    """the same on planes in device memory (take_hip_tonemap_device): rgb is a torch device tensor or an integer device
+    pointer of `precision`'s Real, out one of height * width * 4 bytes ("rgba") or height * width * 3 Reals ("real":
+    out = None transforms in place) -> exposure_used; blocks until done.  Needs no scene."""
+    o = _tonemap_opts(opts, exposure, op, transfer, format, kw)
+    if out is None and o.format == D.TAKE_DISPLAY_RGBA:
+        raise ValueError("format 'rgba' needs an output plane")
+    used = C.c_double(0.0)
+    _check(lib().take_hip_tonemap_device(C.c_void_p(_pointer(rgb)), int(precision), int(width), int(height), C.byref(o),
+                                         C.c_void_p(_pointer(rgb if out is None else out)), C.byref(used), C.c_void_p(stream or 0)))
+    return used.value
 
 
 class DeviceMesh:

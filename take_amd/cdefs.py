@@ -244,6 +244,62 @@ TRACKING_PROTOTYPES = {
 }
 
 
+# the display transform (include/take_hip.h)
+TAKE_LUMINANCE_BINS, TAKE_LUMINANCE_SLOTS = 384, 386  # the bins, then [384] non-positive, [385] non-finite
+TAKE_TONEMAP_LINEAR, TAKE_TONEMAP_REINHARD, TAKE_TONEMAP_ACES = 0, 1, 2
+TAKE_TRANSFER_SRGB, TAKE_TRANSFER_LINEAR = 0, 1
+TAKE_DISPLAY_RGBA, TAKE_DISPLAY_REAL = 0, 1
+TONEMAP_OPS = {"linear": TAKE_TONEMAP_LINEAR, "reinhard": TAKE_TONEMAP_REINHARD, "aces": TAKE_TONEMAP_ACES}
+TRANSFERS = {"srgb": TAKE_TRANSFER_SRGB, "linear": TAKE_TRANSFER_LINEAR}
+DISPLAY_FORMATS = {"rgba": TAKE_DISPLAY_RGBA, "real": TAKE_DISPLAY_REAL}
+
+
+class TakeExposureOpts(C.Structure):
+    """take_hip_auto_exposure: a field <= 0 (low_fraction: < 0) takes its default (DISPLAY_DEFAULTS)"""
+    _fields_ = [("key", C.c_double), ("low_fraction", C.c_double), ("high_fraction", C.c_double), ("min_exposure", C.c_double),
+                ("max_exposure", C.c_double), ("prev_exposure", C.c_double), ("rate", C.c_double)]
+
+
+class TakeTonemapOpts(C.Structure):
+    """take_hip_tonemap*: exposure <= 0 = automatic (with auto_opts), white <= 0 = 4.0"""
+    _fields_ = [("exposure", C.c_double), ("white", C.c_double), ("op", C.c_int32), ("transfer", C.c_int32), ("format", C.c_int32),
+                ("reserved", C.c_int32), ("auto_opts", TakeExposureOpts)]
+
+
+DISPLAY_DEFAULTS = {"key": 0.18, "low_fraction": 0.05, "high_fraction": 0.95, "min_exposure": 2.0 ** -16, "max_exposure": 2.0 ** 16, "rate": 1.0,
+                    "white": 4.0}
+
+
+def exposure_opts(key=0.0, low_fraction=-1.0, high_fraction=0.0, min_exposure=0.0, max_exposure=0.0, prev_exposure=0.0, rate=0.0):
+    """-> TakeExposureOpts; what is left out takes the library's default (prev_exposure: none, no adaptation)"""
+    return TakeExposureOpts(float(key), float(low_fraction), float(high_fraction), float(min_exposure), float(max_exposure),
+                            float(prev_exposure or 0.0), float(rate))
+
+
+def tonemap_opts(exposure=None, op="aces", transfer="srgb", format="rgba", white=0.0, **auto):
+    """-> TakeTonemapOpts; exposure None (or <= 0) = automatic, with the keywords of exposure_opts in `auto`; op,
+    transfer and format by name (TONEMAP_OPS, TRANSFERS, DISPLAY_FORMATS) or by their TAKE_* value"""
+    def pick(table, what, v):
+        if isinstance(v, str):
+            if v not in table:
+                raise ValueError(f"unknown {what} {v!r}: one of {tuple(table)}")
+            return table[v]
+        return int(v)
+
+    return TakeTonemapOpts(float(exposure or 0.0), float(white), pick(TONEMAP_OPS, "tone operator", op), pick(TRANSFERS, "transfer", transfer),
+                           pick(DISPLAY_FORMATS, "format", format), 0, exposure_opts(**auto))
+
+
+# name -> argument types
+DISPLAY_PROTOTYPES = {
+    "take_hip_luminance_histogram_device": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p],
+    "take_hip_luminance_histogram": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "take_hip_auto_exposure": [C.POINTER(C.c_int64), C.POINTER(TakeExposureOpts), C.POINTER(C.c_double)],
+    "take_hip_tonemap_device": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TakeTonemapOpts), C.c_void_p, C.POINTER(C.c_double), C.c_void_p],
+    "take_hip_tonemap": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TakeTonemapOpts), C.c_void_p, C.POINTER(C.c_double)],
+}
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

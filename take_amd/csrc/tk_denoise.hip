@@ -47,12 +47,6 @@ int resolve(const TakeDenoiseOpts *o, DenoiseOpts &r, double sigma_color = SIGMA
     if (o->albedo_floor > 0) r.albedo_floor = o->albedo_floor;
     return TAKE_OK;
 }
-int check_image(int32_t precision, int32_t width, int32_t height) {
-    if (width <= 0 || height <= 0) return fail(TAKE_E_INVALID, "width and height must be positive");
-    if (precision != TAKE_PRECISION_F32 && precision != TAKE_PRECISION_F64) return fail(TAKE_E_INVALID, "unknown precision");
-    return TAKE_OK;
-}
-
 // Reals of working images per pixel: colour, colour, guide records
 constexpr int WORK_REALS = 12;
 

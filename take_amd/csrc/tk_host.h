@@ -1,8 +1,9 @@
 // tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_create.hip and tk_group.hip (the C entry
 // points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
-// tk_mesh.hip (mesh ingest) and tk_denoise.hip (the image-space denoiser): the error string, fault injection, pinned
-// uploads, the owning device buffer, the staged planes of the host twins, the dispatch on a precision.  (The scene
-// handle all but tk_mesh.hip share is tk_scene_handle.h.)
+// tk_mesh.hip (mesh ingest), tk_denoise.hip (the image-space denoiser) and tk_display.hip (the display transform): the
+// error string, fault injection, pinned uploads, the owning device buffer, the staged planes of the host twins, the
+// dispatch on a precision, the check of a plane's size and precision.  (The scene handle all but tk_mesh.hip and
+// tk_display.hip share is tk_scene_handle.h.)
 // Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
 // take_hip_last_error returns) and ONE TAKE_HIP_FAIL_ALLOC counter.
 #pragma once
@@ -165,6 +166,13 @@ template <int N> struct StagedPlanes {
 
 // f(R{}) with R = float or double: the Real of a TAKE_PRECISION_F32 / _F64 value (checked by the caller)
 template <class F> auto with_real(int32_t precision, F &&f) { return precision == TAKE_PRECISION_F64 ? f(double{}) : f(float{}); }
+
+// what every scene-free image-space call (tk_denoise.hip, tk_display.hip) refuses of its planes' size and precision
+inline int check_image(int32_t precision, int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return fail(TAKE_E_INVALID, "width and height must be positive");
+    if (precision != TAKE_PRECISION_F32 && precision != TAKE_PRECISION_F64) return fail(TAKE_E_INVALID, "unknown precision");
+    return TAKE_OK;
+}
 
 inline int check_device() {
     int n = 0;

@@ -9,7 +9,7 @@ All rendering happens in libtake_hip.so on the current HIP device; without it th
 import numpy as np
 
 from . import cdefs as D
-from .capi import Scene
+from .capi import Scene, tonemap
 from .scene import SceneData, load_tkscene
 
 
@@ -64,8 +64,8 @@ def imwrite_pfm(path, img):
 
 
 def main(argv=None):
-    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]` — the
-    reference's main.cpp:9-27:
+    """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
+    [-png [linear|reinhard|aces]]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
@@ -74,7 +74,11 @@ def main(argv=None):
     error of their mean is at or below `threshold` (default: the library's; Scene.render_adaptive), and one line with
     the samples taken against width * height * spp; image.exr is the same bytes with or without it.  Both -adaptive and
     -denoise: also adaptive_denoised.exr, the adaptive render filtered with the sampler's own variance estimate
-    (Scene.render_adaptive_denoised); every other file is the same bytes as without the other flag."""
+    (Scene.render_adaptive_denoised); every other file is the same bytes as without the other flag.  -png (an extension):
+    beside every .exr a .png of the same stem — exposure, the tone operator (default aces), the sRGB transfer and 8-bit
+    RGBA on the device (capi.tonemap), from the float image that was rendered, not from the halves in the .exr.  All of
+    them use ONE exposure, the auto-exposure of image.exr's render, so that image.png, denoised.png and
+    adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -90,10 +94,24 @@ def main(argv=None):
         except (IndexError, ValueError):
             pass
         del params[i]
+    png_op = None
+    if "-png" in params:  # the operator is optional: the next parameter, if it is one of the three words
+        i = params.index("-png")
+        png_op = "aces"
+        if i + 1 < len(params) and params[i + 1] in D.TONEMAP_OPS:
+            png_op = params[i + 1]
+            del params[i + 1]
+        del params[i]
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
         return 0  # an empty image is not written (src/image.cpp:136-138)
+    floats = []  # (stem, float image) of every .exr written from one: what -png transforms
+
+    def imwrite_exr(stem, img):
+        imwrite(stem + ".exr", img)
+        floats.append((stem, img))
+
     # render + float -> half + scanline packing on the device (take_hip_render_exr_scanlines); what the host adds is
     # the byte-serial rest of imwrite: ZIP pre-filter, deflate, header (take_amd/exr.py)
     from .exr import write_exr_scanlines
@@ -105,17 +123,27 @@ def main(argv=None):
         write_exr_scanlines("image.exr", scene.render_exr_scanlines(spp=sd.spp, max_depth=max_depth, seed=0))
         if features:
             planes = scene.render_features(spp=sd.spp, seed=0, want=("albedo", "normal"))
-            imwrite("albedo.exr", planes["albedo"])
-            imwrite("normal.exr", planes["normal"])
+            imwrite_exr("albedo", planes["albedo"])
+            imwrite_exr("normal", planes["normal"])
         if denoise:
-            imwrite("denoised.exr", scene.render_denoised(spp=sd.spp, max_depth=max_depth, seed=0))
+            imwrite_exr("denoised", scene.render_denoised(spp=sd.spp, max_depth=max_depth, seed=0))
         if adaptive:
             img, stats = scene.render_adaptive(spp=sd.spp, max_depth=max_depth, seed=0, threshold=threshold, stats=True)
-            imwrite("adaptive.exr", img)
+            imwrite_exr("adaptive", img)
             taken, full = int(stats["count"].sum(dtype=np.int64)), sd.width * sd.height * sd.spp
             print(f"adaptive: {taken} of {full} samples ({100.0 * taken / full:.1f} %)")
         if adaptive and denoise:
-            imwrite("adaptive_denoised.exr", scene.render_adaptive_denoised(spp=sd.spp, max_depth=max_depth, seed=0, threshold=threshold))
+            imwrite_exr("adaptive_denoised", scene.render_adaptive_denoised(spp=sd.spp, max_depth=max_depth, seed=0, threshold=threshold))
+        if png_op:
+            # after every .exr is written: image.exr's render as floats (the halves in the file are not read back), its
+            # auto-exposure, and that one exposure for every image
+            from .png import write_png
+
+            rgba, exposure = tonemap(scene.render(spp=sd.spp, max_depth=max_depth, seed=0), op=png_op)
+            write_png("image.png", rgba)
+            for stem, img in floats:
+                write_png(stem + ".png", tonemap(img, exposure=exposure, op=png_op)[0])
+            print(f"png: exposure {exposure!r} ({png_op})")
     finally:
         scene.close()
     return 0
