@@ -416,6 +416,41 @@ int take_hip_scene_set_mesh_vertices(TakeScene *scene, const TakeMeshUpdate *upd
  * beyond the 32-bit record offsets. */
 int take_hip_scene_update_meshes(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
 
+/* ---- thin-lens camera (EXTENSION; new symbols of ABI version 5; no struct changed): depth of field.  A scene is
+ * created with a pinhole camera; take_hip_scene_set_lens gives it a circular aperture of radius aperture_radius (world
+ * units) around lookfrom, in the plane spanned by the camera's u and v, focused on the plane perpendicular to the view
+ * axis at focus_distance along it.  Every camera ray of a sample then starts at a point of the lens — a concentric
+ * (Shirley-Chiu) map of two draws taken from the sample's own key at the counters 0xFFFFFFFE and 0xFFFFFFFF, which no
+ * path reaches — and passes through the point of the plane of focus that the sample's pinhole ray passes through: the
+ * two jitter draws, the stream counter after them and everything the shade rounds draw are the pinhole render's.
+ * What follows the camera ray — take_hip_render*, _render_accumulate, _render_adaptive*, _render_features* (its
+ * "exactly the render's camera rays" now are lens rays: depth is the t along the LENS ray, the first-hit guides are
+ * means over the blur circle), the denoisers — takes the lens ray from the path record.  The motion pass, the marked
+ * frame and the temporal calls are unchanged: their centre rays start at lookfrom, so with a lens the motion vectors,
+ * depth and ids are those of the lens CENTRE.  The trace hooks trace the caller's rays as before.
+ * set_lens follows the contract of "a resident scene changes" above (a failed call leaves the scene as it was; a
+ * successful one ends a progressive sequence; F32, F64 and MIXED scenes, on both sides — the camera rays of a mixed
+ * scene are made on its f64 side; not for scene groups).  aperture_radius == 0 returns the scene to the pinhole camera:
+ * the kernels it launches and the bits it produces are those of a scene that never had a lens.  focus_distance <= 0
+ * asks for |lookat - lookfrom| of the scene's current camera; the effective distance is computed in double and rounded
+ * to the side's Real once.  take_hip_scene_set_camera keeps the lens, and an automatic focus follows the new lookat.
+ * TAKE_E_INVALID, before a device is looked for: a NULL argument ("null argument"), a radius that is negative or not
+ * finite, a focus distance that is not finite, non-zero flags or reserved; then, with a radius > 0, an effective focus
+ * distance that is not > 0.
+ * get_lens: the request as it was given (zeros before any), with focus_distance replaced by the effective distance.
+ * focus_distance_at: what to focus on the surface seen in pixel (column, row; row 0 = the top): the pixel's centre ray
+ * from lookfrom — the pinhole ray — is traced through the closest-hit hook (on the f64 side of a MIXED scene) and
+ * *distance_out = t * -(w . d), the hit's distance along the view axis, which goes straight into
+ * TakeLens::focus_distance; a miss gives 0 and TAKE_OK.  TAKE_E_INVALID: a NULL argument, a pixel outside the image. */
+typedef struct TakeLens {
+    double aperture_radius;  /* world units; 0 = pinhole */
+    double focus_distance;   /* along the view axis; <= 0: |lookat - lookfrom| of the scene's current camera */
+    int32_t flags, reserved; /* 0 */
+} TakeLens;
+int take_hip_scene_set_lens(TakeScene *scene, const TakeLens *lens);
+int take_hip_scene_get_lens(const TakeScene *scene, TakeLens *out);
+int take_hip_scene_focus_distance_at(TakeScene *scene, int32_t column, int32_t row /* 0 = top */, double *distance_out);
+
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order
  * (n_rows(strip_first, strip_stride) * width * 3 Real), already flipped as

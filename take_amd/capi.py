@@ -38,6 +38,7 @@ EXPORTS = [
     "take_hip_temporal_accumulate", "take_hip_temporal_accumulate_device", "take_hip_render_temporal", "take_hip_render_temporal_device",
     "take_hip_scene_track_vertices", "take_hip_scene_tracking_info",
     "take_hip_luminance_histogram", "take_hip_luminance_histogram_device", "take_hip_auto_exposure", "take_hip_tonemap", "take_hip_tonemap_device",
+    "take_hip_scene_set_lens", "take_hip_scene_get_lens", "take_hip_scene_focus_distance_at",
 ]
 
 
@@ -85,7 +86,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -804,6 +805,25 @@ class Scene:
         cam = D.TakeCamera(self.sd.width if width is None else int(width), self.sd.height if height is None else int(height),
                            D.c_double3(*map(float, lookfrom)), D.c_double3(*map(float, lookat)), D.c_double3(*map(float, up)), float(vfov))
         _check(lib().take_hip_scene_set_camera(self.h, C.byref(cam)))
+
+    def set_lens(self, aperture_radius, focus_distance=0.0):
+        """a thin lens for the resident scene (take_hip_scene_set_lens): aperture radius in world units, 0 = back to the
+        pinhole camera; focus_distance along the view axis, <= 0 = |lookat - lookfrom| of the current camera"""
+        lens = D.TakeLens(float(aperture_radius), float(focus_distance), 0, 0)
+        _check(lib().take_hip_scene_set_lens(self.h, C.byref(lens)))
+
+    def get_lens(self):
+        """-> {"aperture_radius", "focus_distance"}: the radius as given and the focus distance in effect (take_hip_scene_get_lens)"""
+        lens = D.TakeLens()
+        _check(lib().take_hip_scene_get_lens(self.h, C.byref(lens)))
+        return {"aperture_radius": lens.aperture_radius, "focus_distance": lens.focus_distance}
+
+    def focus_distance_at(self, column, row):
+        """the distance along the view axis of the surface the centre ray of pixel (column, row; row 0 = top) sees, 0 for
+        a miss (take_hip_scene_focus_distance_at): what set_lens takes as focus_distance to focus on it"""
+        out = C.c_double(-1.0)
+        _check(lib().take_hip_scene_focus_distance_at(self.h, int(column), int(row), C.byref(out)))
+        return out.value
 
     def update_meshes(self, updates):
         """new vertices for meshes of ANY scene, two-level ones included (take_hip_scene_update_meshes): the arguments of

@@ -244,6 +244,19 @@ TRACKING_PROTOTYPES = {
 }
 
 
+# the thin-lens camera (include/take_hip.h)
+class TakeLens(C.Structure):
+    """take_hip_scene_set_lens: aperture_radius 0 = pinhole; focus_distance <= 0 = |lookat - lookfrom| of the current camera"""
+    _fields_ = [("aperture_radius", C.c_double), ("focus_distance", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+LENS_PROTOTYPES = {
+    "take_hip_scene_set_lens": [C.c_void_p, C.POINTER(TakeLens)],
+    "take_hip_scene_get_lens": [C.c_void_p, C.POINTER(TakeLens)],
+    "take_hip_scene_focus_distance_at": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)],
+}
+
+
 # the display transform (include/take_hip.h)
 TAKE_LUMINANCE_BINS, TAKE_LUMINANCE_SLOTS = 384, 386  # the bins, then [384] non-positive, [385] non-finite
 TAKE_TONEMAP_LINEAR, TAKE_TONEMAP_REINHARD, TAKE_TONEMAP_ACES = 0, 1, 2

@@ -122,7 +122,20 @@ k_generate_list(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, const in
         uint32_t sample, idx;
         list_entry((uint32_t)j, (uint32_t)n_active, inv_n_active, sample, idx);
         const int64_t slot = slot_of(sample, list[idx], rp.npix);
-        generate_path(sc, rp, st, slot);
+        generate_path_as<R, false>(sc, rp, st, slot);
+        queue[j] = (int32_t)slot;
+    }
+}
+// the same for a scene with a lens (CameraRec::lens_radius > 0): the host picks (adaptive_impl)
+template <class R>
+__global__ void __launch_bounds__(BLOCK)
+k_generate_list_lens(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, const int32_t *__restrict__ list, int32_t n_active, double inv_n_active,
+                     int32_t *queue, int64_t n) {
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < n; j += (int64_t)gridDim.x * BLOCK) {
+        uint32_t sample, idx;
+        list_entry((uint32_t)j, (uint32_t)n_active, inv_n_active, sample, idx);
+        const int64_t slot = slot_of(sample, list[idx], rp.npix);
+        generate_path_as<R, true>(sc, rp, st, slot);
         queue[j] = (int32_t)slot;
     }
 }

@@ -340,14 +340,68 @@ static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n
 }
 int take_hip_scene_set_mesh_vertices(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) { return update_meshes(ts, updates, n_updates, false); }
 int take_hip_scene_update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates) { return update_meshes(ts, updates, n_updates, true); }
+// the lens of the handle (ts->lens, ts->lens_focus) -> every side's camera record, each value rounded to Real once;
+// radius 0 is the pinhole camera, whose record holds zeros there
+static void apply_lens(TakeScene *ts) {
+    const bool on = ts->lens.aperture_radius > 0;
+    for_each_side(ts, [&](auto &sc) {
+        using R = std::remove_reference_t<decltype(sc.host.cam.focus)>;
+        sc.host.cam.lens_radius = on ? R(ts->lens.aperture_radius) : R(0), sc.host.cam.focus = on ? R(ts->lens_focus) : R(0);
+        sc.dev.cam = sc.host.cam;
+        return TAKE_OK;
+    });
+}
+// > 0, and still finite where the scene has an f32 side
+static bool lens_focus_usable(const TakeScene *ts, double focus) {
+    return focus > 0 && std::isfinite(focus) && (ts->precision == TAKE_PRECISION_F64 || ((float)focus > 0 && std::isfinite((float)focus)));
+}
 int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
     if (!ts || !camera) return fail(TAKE_E_INVALID, "null argument");
     if (camera->width != ts->width() || camera->height != ts->height())
         return fail(TAKE_E_INVALID, "the new camera is " + std::to_string(camera->width) + " x " + std::to_string(camera->height) + ", the scene " +
                                         std::to_string(ts->width()) + " x " + std::to_string(ts->height()) + ": the render buffers are sized at creation");
+    // (the lens stays: make_camera leaves its two members alone; an automatic focus follows the new lookat)
+    const double look = look_distance(*camera);
+    const bool refocus = ts->lens.aperture_radius > 0 && !(ts->lens.focus_distance > 0);
+    if (refocus && !lens_focus_usable(ts, look)) return fail(TAKE_E_INVALID, "the scene's lens focuses on lookat, and the new camera's lookat is not in front of its lookfrom");
     for_each_side(ts, [&](auto &sc) { return make_camera(*camera, sc.host.cam), sc.dev.cam = sc.host.cam, TAKE_OK; });
+    ts->look_distance = look;
+    if (!(ts->lens.focus_distance > 0)) ts->lens_focus = look;
+    apply_lens(ts);
     ts->acc_samples = 0, ts->acc_restart_needed = true;
     return TAKE_OK;
+}
+
+// The thin lens (include/take_hip.h; tk_lens.h): two members of every side's camera record, which the launches pass by
+// value — no device memory changes, so no device is looked for.
+int take_hip_scene_set_lens(TakeScene *ts, const TakeLens *lens) {
+    if (!ts || !lens) return fail(TAKE_E_INVALID, "null argument");
+    if (!(lens->aperture_radius >= 0) || !std::isfinite(lens->aperture_radius)) return fail(TAKE_E_INVALID, "the aperture radius must be finite and >= 0");
+    if (!std::isfinite(lens->focus_distance)) return fail(TAKE_E_INVALID, "the focus distance must be finite");
+    if (lens->flags != 0 || lens->reserved != 0) return fail(TAKE_E_INVALID, "flags and reserved must be 0");
+    const double focus = lens->focus_distance > 0 ? lens->focus_distance : ts->look_distance;
+    if (lens->aperture_radius > 0 && !lens_focus_usable(ts, focus))
+        return fail(TAKE_E_INVALID, "the effective focus distance must be > 0 (and finite in the scene's precision): focus_distance <= 0 asks for |lookat - lookfrom|");
+    ts->lens = *lens, ts->lens_focus = focus;
+    apply_lens(ts);
+    ts->acc_samples = 0, ts->acc_restart_needed = true;
+    return TAKE_OK;
+}
+int take_hip_scene_get_lens(const TakeScene *ts, TakeLens *out) {
+    if (!ts || !out) return fail(TAKE_E_INVALID, "null argument");
+    *out = ts->lens;
+    out->focus_distance = ts->lens_focus;
+    return TAKE_OK;
+}
+int take_hip_scene_focus_distance_at(TakeScene *ts, int32_t column, int32_t row, double *distance_out) {
+    if (!ts || !distance_out) return fail(TAKE_E_INVALID, "null argument");
+    if (column < 0 || column >= ts->width() || row < 0 || row >= ts->height())
+        return fail(TAKE_E_INVALID, "pixel (" + std::to_string(column) + ", " + std::to_string(row) + ") is outside the " + std::to_string(ts->width()) + " x " +
+                                        std::to_string(ts->height()) + " image");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    return focus_distance_scene(ts, column, row, distance_out);
 }
 
 // "The previous frame" of the temporal accumulation (include/take_hip.h): every side's camera and a copy of the

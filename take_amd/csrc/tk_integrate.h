@@ -11,6 +11,7 @@
 // draws and every `break` of the reference loop are kept; what changes is who executes them and when.
 #pragma once
 
+#include "tk_lens.h"
 #include "tk_shade.h"
 
 namespace tk {
@@ -85,18 +86,33 @@ template <class R> TK_HD Vec3<R> camera_dir(const CameraRec<R> &c, const RenderP
     return normalize(ld3(c.u) * ((R(x) + rx) / R(c.width) - R(0.5)) * c.viewport_width +
                      ld3(c.v) * ((R(y) + ry) / R(c.height) - R(0.5)) * c.viewport_height - ld3(c.w));
 }
+// The camera ray of a scene with a lens (c.lens_radius > 0; tk_lens.h): the plane coordinates are camera_dir's — the
+// same two draws, y first — and the lens point comes from the same key at the top of the counter space.
+template <class R> TK_HD void lens_camera_ray(const CameraRec<R> &c, const RenderParams<R> &rp, int64_t slot, Vec3<R> &o, Vec3<R> &d) {
+    int sl, lr, x;
+    slot_pixel(rp, slot, sl, lr, x);
+    const int y = local_row_to_y(rp, lr);
+    Rng rng = path_rng(rp, slot, 0);
+    const R ry = random_real<R>(rng);
+    const R rx = random_real<R>(rng);
+    lens_ray(c, (R(x) + rx) / R(c.width) - R(0.5), (R(y) + ry) / R(c.height) - R(0.5), rng.key, o, d);
+}
 // The whole initial record of a path.  (The render loop of the default integrator does not run this: its first
 // closest-hit launch makes the camera rays itself — CameraIo, tk_kernels.h — and round 0 of shade_path starts from
 // throughput 1, radiance 0 and counter CAMERA_DRAWS whatever the record holds; this function states what that equals.)
-template <class R>
-TK_HD void generate_path(const DeviceScene<R> &sc, const RenderParams<R> &rp, const PathState<R> &st, int64_t slot) {
+// LENS: which of the two cameras, at compile time — the kernels that run this (k_generate, k_generate_list and their
+// _lens twins) are instances of their own per camera, so that the pinhole camera's are the ones they were; generate_path below is the same with the choice made at run time.
+template <class R, bool LENS>
+TK_HD void generate_path_as(const DeviceScene<R> &sc, const RenderParams<R> &rp, const PathState<R> &st, int64_t slot) {
     const CameraRec<R> &c = sc.cam;
-    const Vec3<R> d = camera_dir(c, rp, slot);
+    Vec3<R> o{c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]}, d;
+    if constexpr (LENS) lens_camera_ray(c, rp, slot, o, d);
+    else d = camera_dir(c, rp, slot);
     Rng rng = path_rng(rp, slot, 0);
     rng.ctr = CAMERA_DRAWS;
-    st.R_(S_OX, slot) = c.lookfrom[0];
-    st.R_(S_OY, slot) = c.lookfrom[1];
-    st.R_(S_OZ, slot) = c.lookfrom[2];
+    st.R_(S_OX, slot) = o.x;
+    st.R_(S_OY, slot) = o.y;
+    st.R_(S_OZ, slot) = o.z;
     st.R_(S_DX, slot) = d.x;
     st.R_(S_DY, slot) = d.y;
     st.R_(S_DZ, slot) = d.z;
@@ -110,6 +126,11 @@ TK_HD void generate_path(const DeviceScene<R> &sc, const RenderParams<R> &rp, co
     st.I_(S_FLAGS, slot) = 0;
     st.I_(S_OCC, slot) = -1;
     st.I_(S_CONV, slot) = 0;
+}
+template <class R>
+TK_HD void generate_path(const DeviceScene<R> &sc, const RenderParams<R> &rp, const PathState<R> &st, int64_t slot) {
+    if (sc.cam.lens_radius > R(0)) generate_path_as<R, true>(sc, rp, st, slot);
+    else generate_path_as<R, false>(sc, rp, st, slot);
 }
 
 constexpr uint32_t REQ_EXTEND = 1, REQ_SHADOW = 2;

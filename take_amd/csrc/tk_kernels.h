@@ -44,7 +44,16 @@ template <class R>
 __global__ void __launch_bounds__(BLOCK)
 k_generate(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, int32_t *queue, int64_t n) {
     for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < n; s += (int64_t)gridDim.x * BLOCK) {
-        generate_path(sc, rp, st, s);
+        generate_path_as<R, false>(sc, rp, st, s);
+        queue[s] = (int32_t)s;
+    }
+}
+// the same for a scene with a lens (CameraRec::lens_radius > 0): the host picks (start_batch)
+template <class R>
+__global__ void __launch_bounds__(BLOCK)
+k_generate_lens(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, int32_t *queue, int64_t n) {
+    for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < n; s += (int64_t)gridDim.x * BLOCK) {
+        generate_path_as<R, true>(sc, rp, st, s);
         queue[s] = (int32_t)s;
     }
 }
@@ -68,6 +77,8 @@ template <class R> struct CameraIo : PathIo<R> {
         ray = make_ray(cam.lookfrom[0], cam.lookfrom[1], cam.lookfrom[2], d.x, d.y, d.z, this->eps, Const<R>::inf());
     }
 };
+// (A scene with a lens — CameraRec::lens_radius > 0, tk_lens.h — does not take this launch: its camera rays are made by
+// the generate pass, k_generate_lens, and traced by the PathIo instances; camera_fused, tk_render.hip.)
 __global__ void __launch_bounds__(BLOCK) k_iota(int32_t *queue, int64_t n) {
     for (int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x; s < n; s += (int64_t)gridDim.x * BLOCK) queue[s] = (int32_t)s;
 }

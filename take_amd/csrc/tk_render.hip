@@ -183,10 +183,11 @@ template <class R> struct Frame {
 };
 // Round 0 of the default integrator on the default node format: no generate pass (CameraIo).  The counting instances,
 // the other integrators (their shade rounds read the initial flag word) and the other node formats keep k_generate.
-// TAKE_HIP_CAMERA_FUSED=0 turns it off (A/B runs).
-bool camera_fused(TraceKind kind, int integrator, bool counting) {
+// So does a scene with a lens (lens: CameraRec::lens_radius > 0), whose rays k_generate_lens makes: CameraIo is the
+// pinhole camera's.  TAKE_HIP_CAMERA_FUSED=0 turns it off (A/B runs).
+bool camera_fused(TraceKind kind, int integrator, bool counting, bool lens) {
     static const bool enabled = !(std::getenv("TAKE_HIP_CAMERA_FUSED") && std::atoi(std::getenv("TAKE_HIP_CAMERA_FUSED")) == 0);
-    return enabled && TQ_GROUP == 1 && !counting && integrator == 0 && kind.nodes == NodeFormat::Q4;
+    return enabled && TQ_GROUP == 1 && !counting && integrator == 0 && kind.nodes == NodeFormat::Q4 && !lens;
 }
 
 // The closest hits of round k of a batch for the extend queue (k = 0: the camera rays, made by the launch that traces
@@ -203,7 +204,7 @@ hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const R
     hipError_t e;
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
     tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
-    if (k == 0 && !c.listed_pass && camera_fused(sc.trace, rp.integrator, c.counting)) {
+    if (k == 0 && !c.listed_pass && camera_fused(sc.trace, rp.integrator, c.counting, sc.dev.cam.lens_radius > RR(0))) {
         // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
         CameraIo<RR> io_cam;
         static_cast<PathIo<RR> &>(io_cam) = io_ext;
@@ -472,7 +473,8 @@ template <class R> int64_t start_batch(Frame<R> &fr, int s0, int nb) {
     const int64_t n = (int64_t)nb * fr.npix;
     fr.rp.s0 = s0, fr.rp.spb = nb;
     fr.tm.begin(TK_OTHER);
-    if (camera_fused(fr.sc.trace, fr.rp.integrator, fr.counting)) hipLaunchKernelGGL(k_iota, dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.work.queue[0].p, n);
+    if (camera_fused(fr.sc.trace, fr.rp.integrator, fr.counting, fr.sc.dev.cam.lens_radius > R(0))) hipLaunchKernelGGL(k_iota, dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.work.queue[0].p, n);
+    else if (fr.sc.dev.cam.lens_radius > R(0)) hipLaunchKernelGGL((k_generate_lens<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.sc.dev, fr.rp, fr.st, fr.work.queue[0].p, n);
     else hipLaunchKernelGGL((k_generate<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.sc.dev, fr.rp, fr.st, fr.work.queue[0].p, n);
     hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, fr.stream, fr.work.qwords.p, (int)Q_N_EXT0, (int32_t)n);
     fr.tm.end();
@@ -641,8 +643,12 @@ int adaptive_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
                 fr.rp.s0 = n + done, fr.rp.spb = nb;
                 fr.tm.begin(TK_OTHER);
                 const int gen_grid = (int)std::min<int64_t>((n_paths + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-                hipLaunchKernelGGL((ad::k_generate_list<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
-                                   work.queue[0].p, n_paths);
+                if (sc.dev.cam.lens_radius > R(0))
+                    hipLaunchKernelGGL((ad::k_generate_list_lens<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
+                                       work.queue[0].p, n_paths);
+                else
+                    hipLaunchKernelGGL((ad::k_generate_list<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
+                                       work.queue[0].p, n_paths);
                 hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, work.qwords.p, (int)Q_N_EXT0, (int32_t)n_paths);
                 fr.tm.end();
             }
@@ -946,6 +952,21 @@ int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotion
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     return on_primary(ts, [&](auto &sc, auto &work) { return trace_host(ts, sc, work, rays, n, hits, occ, any); });
+}
+// take_hip_scene_focus_distance_at: the centre ray of the pixel from lookfrom — the pinhole ray, camera_dir_centre's
+// operations on the host — through the closest-hit hook; the hit's t times -(w . d), its distance along the view axis
+int focus_distance_scene(TakeScene *ts, int32_t column, int32_t row, double *distance_out) {
+    return on_primary(ts, [&](auto &sc, auto &work) {
+        using R = std::remove_reference_t<decltype(*work.accum.p)>;
+        const CameraRec<R> &c = sc.dev.cam;
+        const RenderParams<R> rp = make_params<R>(TakeRenderOpts{}, c.width, c.height, c.height, 0, 1);
+        const Vec3<R> d = camera_dir_centre(c, rp, (int64_t)(c.height - 1 - row) * c.width + column);
+        const RayAoS<R> ray{{c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]}, R(0), {d.x, d.y, d.z}, Const<R>::inf()};
+        HitAoS<R> hit{};
+        if (const int rc = trace_host(ts, sc, work, &ray, 1, &hit, nullptr, false)) return rc;
+        *distance_out = hit.shape_id >= 0 ? (double)(hit.t * -dot(Vec3<R>{c.w[0], c.w[1], c.w[2]}, d)) : 0.0;
+        return (int)TAKE_OK;
+    });
 }
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return trace_impl(ts, sc, work, d_rays, n, d_hits, nullptr, false, count, stream); });

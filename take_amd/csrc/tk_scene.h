@@ -196,6 +196,10 @@ template <class R> struct CameraRec {
     R u[3], v[3], w[3], lookfrom[3];
     R viewport_width, viewport_height;
     int32_t width, height;
+    // the thin lens (EXTENSION, tk_lens.h; take_hip_scene_set_lens): aperture radius, 0 = the pinhole camera, and the
+    // distance of the plane of focus along -w.  Trailing, and left alone by make_camera — so zero from the start, also
+    // in a record nobody value-initialises (a HostScene on the stack).
+    R lens_radius = R(0), focus = R(0);
 };
 
 // All device pointers of one scene.  Passed to kernels by value.

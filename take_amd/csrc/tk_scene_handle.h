@@ -6,6 +6,7 @@
 // tk_build_gpu.h's).  Includes no kernel source.
 #pragma once
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <utility>
@@ -217,6 +218,10 @@ struct TakeScene {
         bool has_geometry() const { return geom_f.p || geom_d.p; }
         void drop_geometry() { geom_f.release(), geom_d.release(), inst_first.release(); }
     } mark;
+    // take_hip_scene_set_lens: the request as given, the focus distance in effect (0 until a lens is set) and what an
+    // automatic focus follows — |lookat - lookfrom| of the current camera (creation, take_hip_scene_set_camera), in double
+    TakeLens lens{};
+    double lens_focus = 0.0, look_distance = 0.0;
     int track_flags = 0;  // take_hip_scene_track_vertices
     int temporal_history = -1;  // take_hip_render_temporal*: which of the workspace's two accumulated frames is the history (-1: none)
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
@@ -237,6 +242,11 @@ struct TakeScene {
 
 namespace tk_host {
 
+// |lookat - lookfrom| of a camera, in double: what an automatic focus (TakeLens::focus_distance <= 0) means
+inline double look_distance(const TakeCamera &c) {
+    const double x = c.lookat[0] - c.lookfrom[0], y = c.lookat[1] - c.lookfrom[1], z = c.lookat[2] - c.lookfrom[2];
+    return std::sqrt(x * x + y * y + z * z);
+}
 // f(the scene's SceneT that renders, traces and reports, the handle's workspace): d for F64 and MIXED scenes, f for F32 ones
 template <class TS, class F> decltype(auto) on_primary(TS *ts, F &&f) { return ts->f64() ? f(ts->d, ts->work_d) : f(ts->f, ts->work_f); }
 // The sides a scene has: the f64 one (side = TAKE_PRECISION_F64) of F64 and MIXED scenes, the f32 one of F32 and MIXED ones.
@@ -315,6 +325,8 @@ int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a);
 int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotionBuffers &d_out, bool marked, hipStream_t stream);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
+// the distance along the view axis of what the centre ray of pixel (column, row; both inside the image) hits, 0 for a miss
+int focus_distance_scene(TakeScene *ts, int32_t column, int32_t row, double *distance_out);
 
 // ---- defined in tk_api.hip
 // what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device

@@ -63,9 +63,38 @@ def imwrite_pfm(path, img):
         f.write(a.tobytes())
 
 
+def parse_lens(params):
+    """`-aperture R [-focus D | -focus_pixel X,Y]` taken out of `params` -> (radius, focus distance, (column, row) or None),
+    or None without -aperture; the focus distance is 0 (automatic: the camera's lookat) unless -focus gives one"""
+    def take(flag):
+        if flag not in params:
+            return None
+        i = params.index(flag)
+        if i + 1 >= len(params):
+            raise SystemExit(f"{flag} needs a value")
+        value = params[i + 1]
+        del params[i:i + 2]
+        return value
+
+    aperture, focus, pixel = take("-aperture"), take("-focus"), take("-focus_pixel")
+    if aperture is None:
+        if focus is not None or pixel is not None:
+            raise SystemExit("-focus and -focus_pixel need -aperture")
+        return None
+    if focus is not None and pixel is not None:
+        raise SystemExit("-focus and -focus_pixel exclude each other")
+    try:
+        xy = None if pixel is None else tuple(int(v) for v in pixel.split(","))
+        if xy is not None and len(xy) != 2:
+            raise ValueError(pixel)
+        return float(aperture), 0.0 if focus is None else float(focus), xy
+    except ValueError as e:
+        raise SystemExit(f"-aperture R [-focus D | -focus_pixel X,Y]: {e}")
+
+
 def main(argv=None):
     """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
-    [-png [linear|reinhard|aces]]` — the reference's main.cpp:9-27:
+    [-png [linear|reinhard|aces]] [-aperture R [-focus D | -focus_pixel X,Y]]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
@@ -78,7 +107,10 @@ def main(argv=None):
     beside every .exr a .png of the same stem — exposure, the tone operator (default aces), the sRGB transfer and 8-bit
     RGBA on the device (capi.tonemap), from the float image that was rendered, not from the halves in the .exr.  All of
     them use ONE exposure, the auto-exposure of image.exr's render, so that image.png, denoised.png and
-    adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag."""
+    adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag.  -aperture (an extension): a thin lens of
+    that radius (Scene.set_lens) set before anything is rendered, focused at -focus D along the view axis, on what pixel
+    X,Y (row 0 = top) sees (-focus_pixel; Scene.focus_distance_at), or on the camera's lookat; every file is then of the
+    camera with the lens, and one line prints the focus distance in effect."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -102,6 +134,7 @@ def main(argv=None):
             png_op = params[i + 1]
             del params[i + 1]
         del params[i]
+    lens = parse_lens(params)
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
@@ -120,6 +153,14 @@ def main(argv=None):
     sd = load_tkscene(filename)
     scene = Scene(sd)
     try:
+        if lens is not None:  # before every render: all the files below are of the camera with the lens
+            radius, focus, pixel = lens
+            if pixel is not None:
+                focus = scene.focus_distance_at(*pixel)
+                if not focus > 0:
+                    raise SystemExit(f"-focus_pixel {pixel[0]},{pixel[1]}: the pixel's centre ray hits nothing to focus on")
+            scene.set_lens(radius, focus)
+            print(f"lens: aperture radius {radius!r}, focus distance {scene.get_lens()['focus_distance']!r}")
         write_exr_scanlines("image.exr", scene.render_exr_scanlines(spp=sd.spp, max_depth=max_depth, seed=0))
         if features:
             planes = scene.render_features(spp=sd.spp, seed=0, want=("albedo", "normal"))
