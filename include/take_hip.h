@@ -451,6 +451,57 @@ int take_hip_scene_set_lens(TakeScene *scene, const TakeLens *lens);
 int take_hip_scene_get_lens(const TakeScene *scene, TakeLens *out);
 int take_hip_scene_focus_distance_at(TakeScene *scene, int32_t column, int32_t row /* 0 = top */, double *distance_out);
 
+/* ---- motion blur (EXTENSION, parity unpinned; new symbols of ABI version 5; no struct changed; DESIGN.md par. 4l): a
+ * render whose exposure lasts from `open` to `close` of the interval between the marked frame (scene time 0:
+ * take_hip_scene_mark_frame) and the current one (scene time 1).  Time is sampled per SLICE of samples, not per ray:
+ *  - The plan (take_hip_shutter_plan; needs no scene and no device).  K = slices, capped at spp; slices <= 0 asks for
+ *    min(spp, 16), an interface default, not a tuned value.  Slice k holds the samples [floor(k spp / K),
+ *    floor((k + 1) spp / K)) of every pixel (64-bit integer arithmetic; first_sample gets the K + 1 bounds): contiguous,
+ *    covering [0, spp), none empty.  Its time is t_k = open + (close - open) * ((k + 0.5) / K) in double, each operation
+ *    one rounding in that order.  The shutter is a box: every sample weighs the same.
+ *  - The pose at t (take_hip_shutter_pose).  Every lerp is (1 - t) * a + t * b in double — `1 - t` rounded once, two
+ *    products, one sum, no contraction — so t = 0 gives a and t = 1 gives b (as values: a zero comes out as +0 unless
+ *    both ends are -0); where a == b the result is b itself (the sum's three roundings would not give it back), so what
+ *    did not move between the mark and now stays where it is at every t, bit for bit.  Camera: lookfrom, lookat, up and vfov of the marked and the current TakeCamera, component by
+ *    component; width and height are the scene's; the result goes through the arithmetic take_hip_scene_set_camera puts
+ *    a camera through.  Placements: the 12 doubles of each object -> world transform, entry by entry, marked -> current:
+ *    the matrix motion transform of Embree and OptiX.  A rotation moves along its CHORD, not its arc (a half turn passes
+ *    through a singular matrix at t = 0.5): callers with fast rotations mark more often.  The lens (take_hip_scene_set_lens:
+ *    radius and effective focus distance) is the current frame's at every t.  Vertices that moved since the mark
+ *    (take_hip_scene_set_mesh_vertices / _update_meshes) are NOT interpolated: the meshes are at their current vertices
+ *    throughout, whether or not take_hip_scene_track_vertices is on.
+ *    xforms_out: 12 * n_instances doubles in host memory, or NULL = not wanted (ignored for a scene without placements).
+ *  - The render.  For k = 0 .. K-1 the scene is posed at t_k on the device — the camera records; the placements by the
+ *    path take_hip_scene_set_instance_transforms takes, the top level alone rebuilt — and slice k's samples are rendered
+ *    on top of the accumulator take_hip_render_accumulate keeps; their numbers continue those of a one-shot render.  One
+ *    resolve over spp.  The image is the mean over the samples s = 0 .. spp-1 of "sample s of take_hip_render of the
+ *    scene posed at the time of s's slice": with no motion between mark and now it is take_hip_render's image bit for
+ *    bit, and with one slice it is the image of a scene newly created (TAKE_BUILDER_DEVICE_LBVH) at the pose of t_0.
+ *    Strips, samples_per_batch and the other options as take_hip_render takes them; F32, F64 and MIXED scenes (a mixed
+ *    scene is posed on both sides); one- and two-level scenes — a scene without placements gets camera blur, with no
+ *    rebuild at all.  The call ends a progressive sequence exactly as take_hip_render does.  Not for scene groups.  The
+ *    adaptive, feature, motion and temporal calls are unchanged: they render the current frame.
+ *  - Afterwards, on success or failure, the scene is at its current pose again and traces and renders exactly as before
+ *    the call (hit tables, occlusion, images bit for bit); the mark, the current transforms and the current camera are
+ *    untouched.  As after any re-pose, a host-built top level may have become an LBVH one (take_hip_scene_stats).
+ * TAKE_E_INVALID, before a device is looked for: a NULL argument ("null argument"; `shutter` may be NULL = {0, 1, 0, 0}),
+ * open / close not finite or outside 0 <= open <= close <= 1 (shutter_pose: t outside [0, 1]), non-zero flags, spp <= 0.
+ * Then: no marked frame (the motion pass's message); what take_hip_scene_set_instance_transforms refuses of the scene
+ * ("unsupported": TAKE_HIP_BRAID > 1, TAKE_HIP_NODES=q8); a pose that is singular (|det| <= 1e-300) or not finite, or a
+ * camera whose lookat coincides with its lookfrom, at ANY slice time — found for all K slices before the first sample is
+ * rendered; the message names the first such slice (and placement).  A refusal that can only appear in the loop (a
+ * top-level tree too deep at some slice) restores the current pose before it returns. */
+typedef struct TakeShutter {
+    double open, close;  /* scene time: 0 = the marked frame, 1 = the current frame; 0 <= open <= close <= 1 */
+    int32_t slices;      /* K >= 1; <= 0: the default, min(spp, 16) */
+    int32_t flags;       /* 0 */
+} TakeShutter;
+int take_hip_shutter_plan(int32_t spp, const TakeShutter *shutter /* NULL = {0, 1, 0, 0} */,
+                          int32_t *slices_out, int32_t *first_sample /* K + 1, may be NULL */, double *time /* K, may be NULL */);
+int take_hip_shutter_pose(TakeScene *scene, double t, TakeCamera *camera_out, double *xforms_out /* 12 * n_instances, host; NULL = not wanted */);
+int take_hip_render_shutter_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, void *d_rgb_out, void *stream);
+int take_hip_render_shutter(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, void *rgb_out_host);
+
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order
  * (n_rows(strip_first, strip_stride) * width * 3 Real), already flipped as

@@ -39,6 +39,7 @@ EXPORTS = [
     "take_hip_scene_track_vertices", "take_hip_scene_tracking_info",
     "take_hip_luminance_histogram", "take_hip_luminance_histogram_device", "take_hip_auto_exposure", "take_hip_tonemap", "take_hip_tonemap_device",
     "take_hip_scene_set_lens", "take_hip_scene_get_lens", "take_hip_scene_focus_distance_at",
+    "take_hip_shutter_plan", "take_hip_shutter_pose", "take_hip_render_shutter", "take_hip_render_shutter_device",
 ]
 
 
@@ -86,7 +87,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
@@ -120,6 +121,18 @@ def _check(rc):
 
 def device_count():
     return _check(lib().take_hip_device_count())
+
+
+def shutter_plan(spp, open=0.0, close=1.0, slices=0):
+    """how a render over the shutter [open, close] cuts `spp` samples into slices (take_hip_shutter_plan; no scene, no
+    GPU) -> (first_sample, time): K + 1 int32 bounds — slice k holds the samples first_sample[k] .. first_sample[k + 1] - 1
+    of every pixel — and the K scene times the slices are posed at"""
+    sh, k = D.TakeShutter(float(open), float(close), int(slices), 0), C.c_int32()
+    _check(lib().take_hip_shutter_plan(int(spp), C.byref(sh), C.byref(k), None, None))
+    first, time = np.zeros(k.value + 1, np.int32), np.zeros(k.value, np.float64)
+    _check(lib().take_hip_shutter_plan(int(spp), C.byref(sh), C.byref(k), first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       time.ctypes.data_as(C.POINTER(C.c_double))))
+    return first, time
 
 
 def ply_layout(data):
@@ -824,6 +837,34 @@ class Scene:
         out = C.c_double(-1.0)
         _check(lib().take_hip_scene_focus_distance_at(self.h, int(column), int(row), C.byref(out)))
         return out.value
+
+    def render_shutter(self, spp=None, max_depth=None, seed=0, open=0.0, close=1.0, slices=0, ray_epsilon=0.0, strip_first=0,
+                       strip_stride=1, samples_per_batch=0, integrator=0):
+        """motion blur (take_hip_render_shutter): a render whose exposure lasts from scene time `open` to `close`, 0 being
+        the marked frame (mark_frame) and 1 the current one; the samples are cut into `slices` slices (<= 0: min(spp, 16)),
+        each rendered with camera and placements lerped to its time; the scene is at its current pose again afterwards
+        -> (rows, W, 3) host array, as render's"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        sh = D.TakeShutter(float(open), float(close), int(slices), 0)
+        n = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
+        out = np.zeros((n, self.sd.width, 3), self.dtype)
+        _check(lib().take_hip_render_shutter(self.h, C.byref(o), C.byref(sh), out.ctypes.data))
+        return out
+
+    def render_shutter_device(self, d_ptr, spp, max_depth, seed=0, open=0.0, close=1.0, slices=0, ray_epsilon=0.0, strip_first=0,
+                              strip_stride=1, samples_per_batch=0, stream=None, integrator=0):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer); blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        sh = D.TakeShutter(float(open), float(close), int(slices), 0)
+        _check(lib().take_hip_render_shutter_device(self.h, C.byref(o), C.byref(sh), C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
+
+    def shutter_pose(self, t):
+        """the pose render_shutter gives the scene at scene time t in [0, 1] (take_hip_shutter_pose) -> {"lookfrom", "lookat",
+        "up" (3,), "vfov", "xforms" (n, 3, 4) float64 — n = 0 for a scene without placements}"""
+        cam = D.TakeCamera()
+        x = np.zeros((len(self.sd.instance_mesh), 3, 4), np.float64)
+        _check(lib().take_hip_shutter_pose(self.h, float(t), C.byref(cam), x.ctypes.data if x.size else None))
+        return {"lookfrom": np.array(cam.lookfrom[:]), "lookat": np.array(cam.lookat[:]), "up": np.array(cam.up[:]), "vfov": cam.vfov, "xforms": x}
 
     def update_meshes(self, updates):
         """new vertices for meshes of ANY scene, two-level ones included (take_hip_scene_update_meshes): the arguments of

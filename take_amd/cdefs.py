@@ -257,6 +257,20 @@ LENS_PROTOTYPES = {
 }
 
 
+# motion blur (include/take_hip.h)
+class TakeShutter(C.Structure):
+    """take_hip_render_shutter*: scene time 0 = the marked frame, 1 = the current one; slices <= 0 = min(spp, 16)"""
+    _fields_ = [("open", C.c_double), ("close", C.c_double), ("slices", C.c_int32), ("flags", C.c_int32)]
+
+
+SHUTTER_PROTOTYPES = {
+    "take_hip_shutter_plan": [C.c_int32, C.POINTER(TakeShutter), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    "take_hip_shutter_pose": [C.c_void_p, C.c_double, C.POINTER(TakeCamera), C.c_void_p],
+    "take_hip_render_shutter_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeShutter), C.c_void_p, C.c_void_p],
+    "take_hip_render_shutter": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeShutter), C.c_void_p],
+}
+
+
 # the display transform (include/take_hip.h)
 TAKE_LUMINANCE_BINS, TAKE_LUMINANCE_SLOTS = 384, 386  # the bins, then [384] non-positive, [385] non-finite
 TAKE_TONEMAP_LINEAR, TAKE_TONEMAP_REINHARD, TAKE_TONEMAP_ACES = 0, 1, 2

@@ -365,7 +365,7 @@ int take_hip_scene_set_camera(TakeScene *ts, const TakeCamera *camera) {
     const bool refocus = ts->lens.aperture_radius > 0 && !(ts->lens.focus_distance > 0);
     if (refocus && !lens_focus_usable(ts, look)) return fail(TAKE_E_INVALID, "the scene's lens focuses on lookat, and the new camera's lookat is not in front of its lookfrom");
     for_each_side(ts, [&](auto &sc) { return make_camera(*camera, sc.host.cam), sc.dev.cam = sc.host.cam, TAKE_OK; });
-    ts->look_distance = look;
+    ts->look_distance = look, ts->camera = *camera;
     if (!(ts->lens.focus_distance > 0)) ts->lens_focus = look;
     apply_lens(ts);
     ts->acc_samples = 0, ts->acc_restart_needed = true;
@@ -418,6 +418,7 @@ int take_hip_scene_mark_frame(TakeScene *ts) {
     ts->mark.xforms = std::move(copy);
     ts->mark.drop_geometry(), ts->mark.updated = false;  // (the records are the marked ones again)
     ts->mark.cam_f = ts->f.dev.cam, ts->mark.cam_d = ts->d.dev.cam;  // (a side the scene does not have: never read)
+    ts->mark.camera = ts->camera;
     ts->mark.set = true;
     return TAKE_OK;
 }
@@ -463,6 +464,145 @@ int take_hip_render_motion(TakeScene *ts, const TakeRenderOpts *opts, const Take
     const TakeMotionBuffers d_out{st[0], st[1], st[2], (int32_t *)st[3]};
     if (int rc = render_motion_scene(ts, *opts, d_out, true, nullptr)) return rc;
     return st.download();
+}
+
+// ------------------------------------------------------------------------------------------------ motion blur
+// A render over a shutter between the marked and the current frame (include/take_hip.h): the plan, the
+// pose at a time (tk_shutter.h; launched by tk_render.hip's shutter_pose_device) and the loop over the slices, which
+// re-poses through set_instance_transforms' own path and renders through take_hip_render_accumulate's.
+static int check_shutter(const TakeShutter &s) {
+    if (!std::isfinite(s.open) || !std::isfinite(s.close) || !(0.0 <= s.open && s.open <= s.close && s.close <= 1.0))
+        return fail(TAKE_E_INVALID, "the shutter must have 0 <= open <= close <= 1");
+    if (s.flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
+    return TAKE_OK;
+}
+int take_hip_shutter_plan(int32_t spp, const TakeShutter *shutter, int32_t *slices_out, int32_t *first_sample, double *time) {
+    if (!slices_out) return fail(TAKE_E_INVALID, "null argument");
+    const TakeShutter s = shutter ? *shutter : TakeShutter{0.0, 1.0, 0, 0};
+    if (int rc = check_shutter(s)) return rc;
+    if (spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    const int32_t K = s.slices <= 0 ? std::min<int32_t>(spp, 16) : std::min(s.slices, spp);
+    *slices_out = K;
+    for (int32_t k = 0; first_sample && k <= K; k++) first_sample[k] = (int32_t)((int64_t)k * spp / K);
+    for (int32_t k = 0; time && k < K; k++) time[k] = s.open + (s.close - s.open) * ((k + 0.5) / K);
+    return TAKE_OK;
+}
+// what the shutter needs of the scene: a mark, and — with placements — what the re-pose accepts and both sets of transforms
+static int check_shutter_scene(const TakeScene *ts) {
+    if (!ts->mark.set) return fail(TAKE_E_INVALID, "no marked frame: take_hip_scene_mark_frame has not been called on this scene");
+    if (ts->n_placements <= 0) return TAKE_OK;
+    if (const int rc = check_repose(ts, ts->n_placements)) return rc;
+    if (!ts->xforms.p || (int64_t)ts->xforms.n != 12 * ts->n_placements || (int64_t)ts->mark.xforms.n != 12 * ts->n_placements)
+        return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group");
+    return TAKE_OK;
+}
+static bool camera_usable(const TakeCamera &c) {
+    bool finite = std::isfinite(c.vfov), apart = false;
+    for (int a = 0; a < 3; a++) finite = finite && std::isfinite(c.lookfrom[a]) && std::isfinite(c.lookat[a]) && std::isfinite(c.up[a]), apart = apart || c.lookfrom[a] != c.lookat[a];
+    return finite && apart;
+}
+static int bad_pose(int64_t first_bad, int64_t n) {
+    return fail(TAKE_E_INVALID, "slice " + std::to_string(first_bad / n) + ": instance " + std::to_string(first_bad % n) + ": singular or non-finite transform");
+}
+int take_hip_shutter_pose(TakeScene *ts, double t, TakeCamera *camera_out, double *xforms_out) {
+    if (!ts || !camera_out) return fail(TAKE_E_INVALID, "null argument");
+    if (!(t >= 0.0 && t <= 1.0)) return fail(TAKE_E_INVALID, "t must be in [0, 1]");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    if (const int rc = check_shutter_scene(ts)) return rc;
+    const TakeCamera cam = shutter_camera(ts->mark.camera, ts->camera, t);
+    if (!camera_usable(cam)) return fail(TAKE_E_INVALID, "slice 0: the interpolated camera is not finite, or its lookat coincides with its lookfrom");
+    if (xforms_out && ts->n_placements > 0) {
+        DevBuf<double> posed;
+        int64_t first_bad = -1;
+        std::vector<int> moved;
+        if (const int rc = shutter_pose_device(ts->mark.xforms.p, ts->xforms.p, std::vector<double>{t}, ts->n_placements, posed, first_bad, moved)) return rc;
+        if (first_bad >= 0) return bad_pose(first_bad, ts->n_placements);
+        HIP_TRY(hipMemcpy(xforms_out, posed.p, posed.bytes(), hipMemcpyDeviceToHost));
+    }
+    *camera_out = cam;
+    return TAKE_OK;
+}
+// every side's camera record from `cam`, lens members kept (take_hip_scene_set_camera's arithmetic; nothing else of the handle)
+static void pose_camera(TakeScene *ts, const TakeCamera &cam) {
+    for_each_side(ts, [&](auto &sc) { return make_camera(cam, sc.host.cam), sc.dev.cam = sc.host.cam, TAKE_OK; });
+}
+int take_hip_render_shutter_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *d_rgb_out, void *stream) {
+    if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
+    int32_t K = 0;
+    if (int rc = take_hip_shutter_plan(opts->spp, shutter, &K, nullptr, nullptr)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    if (const int rc = check_shutter_scene(ts)) return rc;
+    try {
+        std::vector<int32_t> first((size_t)K + 1);
+        std::vector<double> time((size_t)K);
+        take_hip_shutter_plan(opts->spp, shutter, &K, first.data(), time.data());
+        // every slice's pose, looked at before the first sample is rendered
+        const int64_t n = ts->n_placements;
+        std::vector<TakeCamera> cams;
+        for (int32_t k = 0; k < K; k++) {
+            cams.push_back(shutter_camera(ts->mark.camera, ts->camera, time[k]));
+            if (!camera_usable(cams.back()))
+                return fail(TAKE_E_INVALID, "slice " + std::to_string(k) + ": the interpolated camera is not finite, or its lookat coincides with its lookfrom");
+        }
+        DevBuf<double> posed;
+        int64_t first_bad = -1;
+        std::vector<int> moved;
+        if (n > 0) {
+            if (const int rc = shutter_pose_device(ts->mark.xforms.p, ts->xforms.p, time, n, posed, first_bad, moved)) return rc;
+            if (first_bad >= 0) return bad_pose(first_bad, n);
+        }
+        // the slices; whatever happens from here on, the scene goes back to its current pose.  `at`: the transforms the
+        // placements are under — a slice whose pose is the current transforms bit for bit is rendered under those, and
+        // placements that did not move since the mark are never re-posed at all
+        const bool restart_needed = ts->acc_restart_needed;  // (a re-pose sets it; a one-shot render leaves it alone, and so does this call)
+        const double *at = ts->xforms.p;
+        auto repose_to = [&](const double *x) {
+            if (x == at) return (int)TAKE_OK;
+            const int rc = stage_then_commit<ReposeStage>(ts, [&](const auto &sc, auto &stage) { return repose_two_level_device(sc, x, n, stage); });
+            if (!rc) at = x;
+            return rc;
+        };
+        int rc = TAKE_OK;
+        for (int32_t k = 0; k < K && !rc; k++) {
+            pose_camera(ts, cams[k]);
+            if (n > 0) rc = repose_to(moved[k] ? posed.p + 12 * n * (int64_t)k : ts->xforms.p);
+            TakeRenderOpts o = *opts;
+            o.spp = first[k + 1] - first[k];
+            if (!rc) rc = render_scene(ts, o, d_rgb_out, (hipStream_t)stream, first[k], k > 0, k + 1 == K);
+        }
+        const std::string why = g_error;
+        pose_camera(ts, ts->camera);
+        const int back = n > 0 ? repose_to(ts->xforms.p) : (int)TAKE_OK;
+        ts->acc_samples = 0, ts->acc_restart_needed = restart_needed || back != TAKE_OK;
+        if (rc) return fail(rc, why);
+        if (back) return fail(back, "the render is complete, but putting the scene back at its current pose failed: " + g_error);
+        return TAKE_OK;
+    } catch (const std::bad_alloc &) {
+        return fail(TAKE_E_NOMEM, "out of host memory while rendering over the shutter");
+    }
+}
+int take_hip_render_shutter(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *rgb_out_host) {
+    if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
+    int32_t K = 0;
+    if (int rc = take_hip_shutter_plan(opts->spp, shutter, &K, nullptr, nullptr)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
+    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
+    if (rows < 0) return rows;
+    const size_t bytes = (size_t)rows * ts->width() * 3 * (ts->f64() ? 8 : 4);
+    if (bytes == 0) return TAKE_OK;
+    DevBuf<char> img;
+    if (img.alloc(bytes) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the image");
+    if (int rc = take_hip_render_shutter_device(ts, opts, shutter, img.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rgb_out_host, img.p, bytes, hipMemcpyDeviceToHost));
+    return TAKE_OK;
 }
 
 int take_hip_get_counters(const TakeScene *ts, TakeCounters *out) {

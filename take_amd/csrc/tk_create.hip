@@ -276,7 +276,7 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
     std::unique_ptr<TakeScene> ts(new (std::nothrow) TakeScene());
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
     ts->precision = o.precision;
-    ts->look_distance = look_distance(desc->camera);
+    ts->look_distance = look_distance(desc->camera), ts->camera = desc->camera;
     hipDeviceProp_t prop;
     if (hipGetDevice(&ts->device) != hipSuccess || hipGetDeviceProperties(&prop, ts->device) != hipSuccess)
         return fail(TAKE_E_DEVICE, "cannot query the HIP device");

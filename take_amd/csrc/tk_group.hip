@@ -67,7 +67,7 @@ int replicate_scene(const TakeScene *src, int device, TakeScene **out) {
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
     ts->precision = src->precision, ts->device = device, ts->num_cus = src->num_cus, ts->instrumentation = 0;
     ts->n_placements = src->n_placements;
-    ts->lens = src->lens, ts->lens_focus = src->lens_focus, ts->look_distance = src->look_distance;  // (the camera records are copied with the sides)
+    ts->lens = src->lens, ts->lens_focus = src->lens_focus, ts->look_distance = src->look_distance, ts->camera = src->camera;  // (the camera records are copied with the sides)
     if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the replica's device current");
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ts->num_cus = cus;

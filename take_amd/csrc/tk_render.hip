@@ -2,7 +2,7 @@
 // the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
 // after them) and the calls that differ in between — the wavefront render loop, its adaptive twin (passes over the
 // pixels still active), the feature pass, the motion pass, the trace hooks.
-// The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h and tk_adaptive.h (as tk_build.hip is for tk_build_gpu.h);
+// The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h, tk_adaptive.h and tk_shutter.h (as tk_build.hip is for tk_build_gpu.h);
 // what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "tk_features.h"
 #include "tk_motion.h"
 #include "tk_adaptive.h"
+#include "tk_shutter.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -543,10 +544,11 @@ template <class R> int run_rounds(Frame<R> &fr, RenderLoop &loop, int max_depth,
 
 // first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
 // random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
-// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples.
+// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples —
+// written unless resolve is false (all but the last slice of take_hip_render_shutter*: the accumulator is the result).
 // (What is a render's own between the frame's steps: its checks, the batch loop, accumulate and resolve.)
 template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
-                                   int64_t first_sample, bool keep_accum) {
+                                   int64_t first_sample, bool keep_accum, bool resolve) {
     if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
     if (const int rc = check_render_opts(sc, o)) return rc;
     Frame<R> fr{ts, sc, work, stream};
@@ -572,8 +574,8 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace
         fr.tm.end();
     }
     fr.tm.begin(TK_OTHER);
-    hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows,
-                       (int32_t)first_sample + o.spp);
+    if (resolve) hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows,
+                                    (int32_t)first_sample + o.spp);
     fr.tm.end();
     if ((rc = end_frame(fr, (uint64_t)npix * (uint64_t)o.spp))) return rc;
     if (std::getenv("TAKE_HIP_VERBOSE"))
@@ -908,13 +910,13 @@ int rows_of(int height, int first, int stride, int32_t *rows_out) {
     return n;
 }
 
-int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample, bool keep_accum) {
-    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, d_out, stream, first_sample, keep_accum); });
+int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample, bool keep_accum, bool resolve) {
+    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, d_out, stream, first_sample, keep_accum, resolve); });
 }
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img) {
     return on_primary(ts, [&](auto &sc, auto &work) {
         int rc = work.ensure(0, npix, false);
-        if (!rc) rc = render_impl(ts, sc, work, o, work.out.p, nullptr, 0, false);
+        if (!rc) rc = render_impl(ts, sc, work, o, work.out.p, nullptr, 0, false, true);
         img = work.out.p;
         return rc;
     });
@@ -970,6 +972,39 @@ int focus_distance_scene(TakeScene *ts, int32_t column, int32_t row, double *dis
 }
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return trace_impl(ts, sc, work, d_rays, n, d_hits, nullptr, false, count, stream); });
+}
+TakeCamera shutter_camera(const TakeCamera &marked, const TakeCamera &current, double t) {
+    TakeCamera c = current;  // (width and height: the scene's)
+    for (int a = 0; a < 3; a++) {
+        c.lookfrom[a] = shutter_lerp(t, marked.lookfrom[a], current.lookfrom[a]);
+        c.lookat[a] = shutter_lerp(t, marked.lookat[a], current.lookat[a]);
+        c.up[a] = shutter_lerp(t, marked.up[a], current.up[a]);
+    }
+    c.vfov = shutter_lerp(t, marked.vfov, current.vfov);
+    return c;
+}
+// On the default stream, as the re-pose that reads `posed` next; returns after the kernel has completed.
+int shutter_pose_device(const double *d_marked, const double *d_current, const std::vector<double> &times, int64_t n, DevBuf<double> &posed, int64_t &first_bad,
+                        std::vector<int> &moved) {
+    first_bad = -1;
+    moved.assign(times.size(), 0);
+    const int64_t lanes = (int64_t)times.size() * n;
+    if (lanes <= 0) return TAKE_OK;
+    if (lanes >= ((int64_t)1 << 31) / 12) return fail(TAKE_E_INVALID, "unsupported: too many slices times placements for one launch");
+    DevBuf<double> d_times;
+    DevBuf<int> words;  // [0] the first offender, [1 ..] the slices' moved flags
+    std::vector<int> words_h(1 + times.size(), 0);
+    const int none = INT32_MAX;
+    words_h[0] = none;
+    if (posed.alloc(12 * (size_t)lanes) != hipSuccess || d_times.upload(times) != hipSuccess || words.upload(words_h) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for the placements' poses over the shutter");
+    hipLaunchKernelGGL(k_shutter_pose, dim3((unsigned)((lanes + SHUTTER_BLOCK - 1) / SHUTTER_BLOCK)), dim3(SHUTTER_BLOCK), 0, nullptr, d_marked, d_current,
+                       d_times.p, (int)times.size(), (int)n, posed.p, words.p, words.p + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(words_h.data(), words.p, words.bytes(), hipMemcpyDeviceToHost));
+    if (words_h[0] != none) first_bad = words_h[0];
+    std::copy(words_h.begin() + 1, words_h.end(), moved.begin());
+    return TAKE_OK;
 }
 
 }  // namespace tk_host

@@ -207,6 +207,7 @@ struct TakeScene {
         bool set = false;
         tk::CameraRec<float> cam_f{};
         tk::CameraRec<double> cam_d{};
+        TakeCamera camera{};  // as it was given (TakeScene::camera then): the shutter lerps the cameras, not their records
         tk_host::DevBuf<double> xforms;
         // take_hip_scene_track_vertices: the marked geometry (tk_motion_pixel.h: MarkedGeometry) of the primary side, in
         // its Real — made by the first mesh update after the mark (copy on write: until then the scene's records are the
@@ -222,6 +223,9 @@ struct TakeScene {
     // automatic focus follows — |lookat - lookfrom| of the current camera (creation, take_hip_scene_set_camera), in double
     TakeLens lens{};
     double lens_focus = 0.0, look_distance = 0.0;
+    // the camera the scene was last given (creation, take_hip_scene_set_camera), as it was given: the sides keep only
+    // the records derived from it, and take_hip_render_shutter* lerps the marked and the current one
+    TakeCamera camera{};
     int track_flags = 0;  // take_hip_scene_track_vertices
     int temporal_history = -1;  // take_hip_render_temporal*: which of the workspace's two accumulated frames is the history (-1: none)
     int mem_share = 1;  // scenes of one group on this device: each sizes its path-state batch for 1/mem_share of the free HBM
@@ -309,8 +313,8 @@ bool compressed_nodes_supported();
 template <class R> hipError_t alloc_trace_state(SceneT<R> &sc, int num_cus);
 // image rows of the strips first, first + stride, ... (increasing; rows_out may be null) -> their number
 int rows_of(int height, int first, int stride, int32_t *rows_out);
-// first_sample / keep_accum: progressive rendering (render_impl)
-int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample = 0, bool keep_accum = false);
+// first_sample / keep_accum: progressive rendering (render_impl); resolve = false: the samples are accumulated, d_out is not written
+int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample = 0, bool keep_accum = false, bool resolve = true);
 // a render of npix pixels into the scene's own output buffer (-> img)
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img);
 // the first-hit feature buffers (include/take_hip.h: take_hip_render_features_device) into device memory
@@ -327,6 +331,14 @@ int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int3
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
 // the distance along the view axis of what the centre ray of pixel (column, row; both inside the image) hits, 0 for a miss
 int focus_distance_scene(TakeScene *ts, int32_t column, int32_t row, double *distance_out);
+// the camera at scene time t between the marked and the current one (tk_shutter.h: shutter_lerp, component by component)
+TakeCamera shutter_camera(const TakeCamera &marked, const TakeCamera &current, double t);
+// take_hip_render_shutter* / take_hip_shutter_pose (tk_shutter.h: k_shutter_pose): the n placements' transforms, d_marked
+// -> d_current (device memory, 12 doubles each), at the times[0 .. n_slices) of the shutter -> posed, n_slices * n * 12
+// doubles, slice-major, allocated here; first_bad = slice * n + placement of the first pose the re-pose would refuse, -1:
+// none; moved[slice] = 0 where the slice's pose is the current transforms bit for bit (no re-pose needed), 1 elsewhere
+int shutter_pose_device(const double *d_marked, const double *d_current, const std::vector<double> &times, int64_t n, DevBuf<double> &posed, int64_t &first_bad,
+                        std::vector<int> &moved);
 
 // ---- defined in tk_api.hip
 // what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device

@@ -92,9 +92,40 @@ def parse_lens(params):
         raise SystemExit(f"-aperture R [-focus D | -focus_pixel X,Y]: {e}")
 
 
+def parse_shutter(params):
+    """`-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az` taken out of `params` -> (open, close, slices,
+    lookfrom, lookat) of the marked frame's camera, or None without -shutter; slices is 0 (the library's default) unless
+    -slices gives one"""
+    def take(flag):
+        if flag not in params:
+            return None
+        i = params.index(flag)
+        if i + 1 >= len(params):
+            raise SystemExit(f"{flag} needs a value")
+        value = params[i + 1]
+        del params[i:i + 2]
+        return value
+
+    shutter, slices, cam = take("-shutter"), take("-slices"), take("-from_camera")
+    if shutter is None:
+        if slices is not None or cam is not None:
+            raise SystemExit("-slices and -from_camera need -shutter")
+        return None
+    if cam is None:
+        raise SystemExit("-shutter needs -from_camera: the marked frame's lookfrom and lookat")
+    try:
+        oc, six = [float(v) for v in shutter.split(",")], [float(v) for v in cam.split(",")]
+        if len(oc) != 2 or len(six) != 6:
+            raise ValueError("two numbers for -shutter, six for -from_camera")
+        return oc[0], oc[1], 0 if slices is None else int(slices), tuple(six[:3]), tuple(six[3:])
+    except ValueError as e:
+        raise SystemExit(f"-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az: {e}")
+
+
 def main(argv=None):
     """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
-    [-png [linear|reinhard|aces]] [-aperture R [-focus D | -focus_pixel X,Y]]` — the reference's main.cpp:9-27:
+    [-png [linear|reinhard|aces]] [-aperture R [-focus D | -focus_pixel X,Y]]
+    [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
@@ -110,7 +141,11 @@ def main(argv=None):
     adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag.  -aperture (an extension): a thin lens of
     that radius (Scene.set_lens) set before anything is rendered, focused at -focus D along the view axis, on what pixel
     X,Y (row 0 = top) sees (-focus_pixel; Scene.focus_distance_at), or on the camera's lookat; every file is then of the
-    camera with the lens, and one line prints the focus distance in effect."""
+    camera with the lens, and one line prints the focus distance in effect.  -shutter (an extension): also shutter.exr,
+    camera motion blur (Scene.render_shutter) — the scene file's camera is the current frame, the six numbers of
+    -from_camera are lookfrom and lookat of the marked one (up and vfov stay), the exposure lasts from OPEN to CLOSE of
+    the interval between them, in K slices (default: the library's); every other file is the same bytes with or without
+    it.  Moving placements need the API."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -135,6 +170,7 @@ def main(argv=None):
             del params[i + 1]
         del params[i]
     lens = parse_lens(params)
+    shutter = parse_shutter(params)
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
@@ -153,6 +189,10 @@ def main(argv=None):
     sd = load_tkscene(filename)
     scene = Scene(sd)
     try:
+        if shutter is not None:  # the marked frame: the other camera, marked; then the scene file's camera again
+            scene.set_camera(shutter[3], shutter[4], sd.up, sd.vfov)
+            scene.mark_frame()
+            scene.set_camera(sd.lookfrom, sd.lookat, sd.up, sd.vfov)
         if lens is not None:  # before every render: all the files below are of the camera with the lens
             radius, focus, pixel = lens
             if pixel is not None:
@@ -162,6 +202,8 @@ def main(argv=None):
             scene.set_lens(radius, focus)
             print(f"lens: aperture radius {radius!r}, focus distance {scene.get_lens()['focus_distance']!r}")
         write_exr_scanlines("image.exr", scene.render_exr_scanlines(spp=sd.spp, max_depth=max_depth, seed=0))
+        if shutter is not None:
+            imwrite_exr("shutter", scene.render_shutter(spp=sd.spp, max_depth=max_depth, seed=0, open=shutter[0], close=shutter[1], slices=shutter[2]))
         if features:
             planes = scene.render_features(spp=sd.spp, seed=0, want=("albedo", "normal"))
             imwrite_exr("albedo", planes["albedo"])
