@@ -946,6 +946,65 @@ int take_hip_tonemap_device(const void *d_rgb, int32_t precision, int32_t width,
 int take_hip_tonemap(const void *rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts, void *out,
                      double *exposure_used);
 
+/* ---- bloom for the display transform, on an image workspace the caller keeps (new symbols of ABI version 5; no struct
+ * changed): glare around what exceeds the display range — a bright pass, a pyramid of 13-tap downsamples, bilinear
+ * upsamples summed back, the layer added between the exposure and the tone operator.  EXTENSION, parity unpinned with
+ * respect to the reference; specified against its own restatement (tests/bloom_ref.py; DESIGN.md par. 4m has the
+ * arithmetic and every order of additions).  Scene-free; every output pixel is written by one thread from fixed inputs,
+ * no atomics: the same planes give the same bits.  Planes as above.  In Real, every operation in the order written:
+ *   1. per channel x = c * E; if (!(x > 0)) x = 0; x = min(x, 65504) — E the exposure the tone-mapping uses, so that
+ *      threshold and knee are in exposed units: 1.0 is what the display clips;
+ *   2. the bright pass (soft knee): Y = the Rec.709 luminance of x; with t = threshold, k = knee: s = Y - (t - k);
+ *      s = min(max(s, 0), 2 k); s = k > 0 ? (s s) / (4 k) : 0; m = max(s, Y - t); w = m > 0 ? m / Y : 0; b = x w;
+ *   3. level 0 has ceil(W / 2) x ceil(H / 2) pixels, every further level the ceil-halving of the one before; Lmax = the
+ *      number of levels until both axes are 1 (at least 1), at most TAKE_BLOOM_MAX_LEVELS; L = levels > 0 ?
+ *      min(levels, Lmax) : Lmax;
+ *   4. downsample (the 13-tap filter of Jimenez, "Next Generation Post Processing in Call of Duty", discrete): a
+ *      destination pixel reads the 6 x 6 source pixels at rows 2 y - 2 .. 2 y + 3 and columns 2 x - 2 .. 2 x + 3,
+ *      clamped to the source; nine 2 x 2 means B on the even grid, four C on the odd grid;
+ *      0.125 sum(C) + 0.125 B[1][1] + 0.0625 (the four edge B) + 0.03125 (the four corner B); D_0 of b, D_k of D_k-1;
+ *   5. upsample: bilinear x 2, weights 9/16, 3/16, 3/16, 1/16 of the near and far source pixels per axis (even x: near
+ *      x / 2, far x / 2 - 1; odd x: near (x - 1) / 2, far near + 1; far clamped); U_L-1 = D_L-1, U_k = D_k + up(U_k+1);
+ *   6. layer = gain * up(U_0) at full resolution, gain = (Real)(intensity / L); x' = x + layer; then steps 3 to 7 of the
+ *      fused pass above on x'. */
+#define TAKE_BLOOM_MAX_LEVELS 8
+typedef struct TakeBloomOpts { /* a field < 0 (levels: <= 0) = its default */
+    double threshold;          /* < 0: 1.0 */
+    double knee;               /* < 0: 0.5; at most the threshold */
+    double intensity;          /* < 0: 0.25; 0 is allowed: no bloom */
+    int32_t levels;            /* <= 0: all (Lmax) */
+    int32_t reserved;          /* 0 */
+} TakeBloomOpts;
+/* The workspace of the scene-free image-space calls: it owns the histogram's block rows and the bloom pyramid (one
+ * device allocation), grows on demand and never shrinks, so that a sequence of frames allocates nothing after its first.
+ * Bound to the device that was current when it was created: a call with it on another device is TAKE_E_INVALID.  NOT
+ * thread-safe: one call at a time per workspace.  destroy(NULL) is a no-op. */
+typedef struct TakeImageWorkspace TakeImageWorkspace;
+int take_hip_image_workspace_create(TakeImageWorkspace **out);
+void take_hip_image_workspace_destroy(TakeImageWorkspace *ws);
+/* The full-resolution layer of step 6, height * width * 3 Real, for an explicit exposure.  d_rgb, d_layer_out: device
+ * memory of the current device; d_layer_out may be d_rgb itself.  opts: NULL = the defaults.  ws: NULL = the pyramid is
+ * allocated per call and freed on return.  Enqueued on `stream`, returns after it has completed.
+ * TAKE_E_INVALID, checked before a device is looked for: a NULL d_rgb / d_layer_out ("null argument"), width or height
+ * <= 0, an unknown precision, an exposure that is not > 0 (NaN included), an option that is not finite, knee >
+ * threshold, reserved != 0, levels > TAKE_BLOOM_MAX_LEVELS (each after the defaults are filled in), a layer output that
+ * partly overlaps the input. */
+int take_hip_bloom_layer_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, double exposure,
+                                const TakeBloomOpts *opts, void *d_layer_out, TakeImageWorkspace *ws, void *stream);
+/* the same with host pointers (upload, the same kernels, download; a temporary workspace) */
+int take_hip_bloom_layer(const void *rgb, int32_t precision, int32_t width, int32_t height, double exposure, const TakeBloomOpts *opts,
+                         void *layer_out);
+/* take_hip_tonemap_device with the composite of step 6: the same options, formats, in-place rule for REAL and overlap
+ * rule for RGBA; the automatic exposure is that of the input image's histogram, exactly as there (made in the
+ * workspace's rows).  bloom: NULL = the defaults.  ws: NULL = allocate per call and free on return.
+ * TAKE_E_INVALID, checked before a device is looked for: everything take_hip_tonemap_device refuses, and of `bloom`
+ * what take_hip_bloom_layer_device refuses. */
+int take_hip_tonemap_bloom_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts,
+                                  const TakeBloomOpts *bloom, void *d_out, double *exposure_used, TakeImageWorkspace *ws, void *stream);
+/* the same with host pointers (upload, the same kernels, download; a temporary workspace) */
+int take_hip_tonemap_bloom(const void *rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts,
+                           const TakeBloomOpts *bloom, void *out, double *exposure_used);
+
 /* rows this rank owns / their image-row indices (rows_out may be NULL) */
 int take_hip_render_rows(const TakeScene *scene, int32_t strip_first, int32_t strip_stride,
                          int32_t *rows_out);

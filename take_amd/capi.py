@@ -40,6 +40,8 @@ EXPORTS = [
     "take_hip_luminance_histogram", "take_hip_luminance_histogram_device", "take_hip_auto_exposure", "take_hip_tonemap", "take_hip_tonemap_device",
     "take_hip_scene_set_lens", "take_hip_scene_get_lens", "take_hip_scene_focus_distance_at",
     "take_hip_shutter_plan", "take_hip_shutter_pose", "take_hip_render_shutter", "take_hip_render_shutter_device",
+    "take_hip_image_workspace_create", "take_hip_image_workspace_destroy", "take_hip_bloom_layer", "take_hip_bloom_layer_device",
+    "take_hip_tonemap_bloom", "take_hip_tonemap_bloom_device",
 ]
 
 
@@ -87,8 +89,9 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
+        L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.take_hip_render_exr_scanlines.argtypes = [C.c_void_p, C.POINTER(D.TakeRenderOpts), C.c_void_p]
         L.take_hip_group_create.argtypes = [C.POINTER(D.TakeSceneDesc), C.POINTER(D.TakeBuildOpts), C.c_int32,
@@ -428,6 +431,106 @@ def tonemap_device(rgb, width, height, precision, out=None, exposure=None, op="a
     used = C.c_double(0.0)
     _check(lib().take_hip_tonemap_device(C.c_void_p(_pointer(rgb)), int(precision), int(width), int(height), C.byref(o),
                                          C.c_void_p(_pointer(rgb if out is None else out)), C.byref(used), C.c_void_p(stream or 0)))
+    return used.value
+
+
+class ImageWorkspace:
+    """the workspace of the scene-free image-space calls (take_hip_image_workspace_create): it owns the histogram's block
+    rows and the bloom pyramid, grows on demand and never shrinks, so that a sequence of frames allocates nothing after
+    its first.  Bound to the device current at its creation; not thread-safe.  A context manager: `with ImageWorkspace()
+    as ws: tonemap_bloom_device(..., workspace=ws)`."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        _check(lib().take_hip_image_workspace_create(C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().take_hip_image_workspace_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (interpreter shutdown: the library may be gone)
+            pass
+
+
+def _workspace(workspace):
+    if workspace is None:
+        return None
+    if not isinstance(workspace, ImageWorkspace) or not workspace._h:
+        raise ValueError("workspace must be an open ImageWorkspace")
+    return workspace._h
+
+
+def _bloom_opts(bloom, kw):
+    """the bloom options of a call: a TakeBloomOpts, or the keywords of cdefs.bloom_opts taken out of `kw`, or neither
+    (None: the library's defaults, a NULL pointer)"""
+    names = [k for k in ("threshold", "knee", "intensity", "levels") if k in kw]
+    if bloom is not None:
+        if names:
+            raise ValueError("give bloom or its keywords, not both")
+        return bloom
+    return D.bloom_opts(**{k: kw.pop(k) for k in names}) if names else None
+
+
+def bloom_layer(img, exposure, bloom=None, **kw):
+    """the bloom layer of a host image at that exposure (take_hip_bloom_layer, include/take_hip.h): what
+    tonemap_bloom adds to the exposed image before the tone operator -> (H, W, 3) of img's dtype.  Options: threshold,
+    knee, intensity, levels (cdefs.bloom_opts), or bloom = a TakeBloomOpts; neither = the library's defaults."""
+    img, precision = _image(img)
+    b = _bloom_opts(bloom, kw)
+    if kw:
+        raise ValueError(f"unknown keywords {sorted(kw)}")
+    out = np.zeros_like(img)
+    _check(lib().take_hip_bloom_layer(img.ctypes.data, precision, img.shape[1], img.shape[0], float(exposure), None if b is None else C.byref(b), out.ctypes.data))
+    return out
+
+
+def bloom_layer_device(rgb, width, height, precision, exposure, out, bloom=None, workspace=None, stream=None, **kw):
+    """the same on planes in device memory (take_hip_bloom_layer_device): rgb and out are torch device tensors or integer
+    device pointers of height * width * 3 of `precision`'s Real (out may be rgb); workspace: an ImageWorkspace, or None =
+    the pyramid is allocated per call; blocks until done.  Needs no scene."""
+    b = _bloom_opts(bloom, kw)
+    if kw:
+        raise ValueError(f"unknown keywords {sorted(kw)}")
+    _check(lib().take_hip_bloom_layer_device(C.c_void_p(_pointer(rgb)), int(precision), int(width), int(height), float(exposure), None if b is None else C.byref(b),
+                                             C.c_void_p(_pointer(out)), _workspace(workspace), C.c_void_p(stream or 0)))
+
+
+def tonemap_bloom(img, exposure=None, op="aces", transfer="srgb", format="rgba", opts=None, bloom=None, **kw):
+    """tonemap with bloom (take_hip_tonemap_bloom, include/take_hip.h): the layer of what exceeds the threshold after
+    exposure, blurred over a pyramid, added before the tone operator -> (array, exposure_used) as tonemap.  The further
+    keywords: threshold, knee, intensity, levels (cdefs.bloom_opts; or bloom = a TakeBloomOpts), and tonemap's."""
+    img, precision = _image(img)
+    b = _bloom_opts(bloom, kw)
+    o = _tonemap_opts(opts, exposure, op, transfer, format, kw)
+    h, w = img.shape[:2]
+    out = np.zeros((h, w, 4), np.uint8) if o.format == D.TAKE_DISPLAY_RGBA else np.zeros_like(img)
+    used = C.c_double(0.0)
+    _check(lib().take_hip_tonemap_bloom(img.ctypes.data, precision, w, h, C.byref(o), None if b is None else C.byref(b), out.ctypes.data, C.byref(used)))
+    return out, used.value
+
+
+def tonemap_bloom_device(rgb, width, height, precision, out=None, exposure=None, op="aces", transfer="srgb", format="rgba", opts=None, bloom=None,
+                         workspace=None, stream=None, **kw):
+    """the same on planes in device memory (take_hip_tonemap_bloom_device), as tonemap_device; workspace: an
+    ImageWorkspace that keeps the histogram's rows and the pyramid between calls, or None = allocated per call
+    -> exposure_used; blocks until done.  Needs no scene."""
+    b = _bloom_opts(bloom, kw)
+    o = _tonemap_opts(opts, exposure, op, transfer, format, kw)
+    if out is None and o.format == D.TAKE_DISPLAY_RGBA:
+        raise ValueError("format 'rgba' needs an output plane")
+    used = C.c_double(0.0)
+    _check(lib().take_hip_tonemap_bloom_device(C.c_void_p(_pointer(rgb)), int(precision), int(width), int(height), C.byref(o), None if b is None else C.byref(b),
+                                               C.c_void_p(_pointer(rgb if out is None else out)), C.byref(used), _workspace(workspace), C.c_void_p(stream or 0)))
     return used.value
 
 

@@ -327,6 +327,36 @@ DISPLAY_PROTOTYPES = {
 }
 
 
+# bloom for the display transform, and the image workspace (include/take_hip.h)
+TAKE_BLOOM_MAX_LEVELS = 8
+
+
+class TakeBloomOpts(C.Structure):
+    """take_hip_bloom_layer*, take_hip_tonemap_bloom*: a field < 0 (levels: <= 0) takes its default (BLOOM_DEFAULTS; levels: all)"""
+    _fields_ = [("threshold", C.c_double), ("knee", C.c_double), ("intensity", C.c_double), ("levels", C.c_int32), ("reserved", C.c_int32)]
+
+
+BLOOM_DEFAULTS = {"threshold": 1.0, "knee": 0.5, "intensity": 0.25}
+
+
+def bloom_opts(threshold=-1.0, knee=-1.0, intensity=-1.0, levels=0):
+    """-> TakeBloomOpts; what is left out takes the library's default"""
+    return TakeBloomOpts(float(threshold), float(knee), float(intensity), int(levels), 0)
+
+
+# name -> argument types
+BLOOM_PROTOTYPES = {
+    "take_hip_image_workspace_create": [C.POINTER(C.c_void_p)],
+    "take_hip_image_workspace_destroy": [C.c_void_p],
+    "take_hip_bloom_layer_device": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(TakeBloomOpts), C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_bloom_layer": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(TakeBloomOpts), C.c_void_p],
+    "take_hip_tonemap_bloom_device": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TakeTonemapOpts), C.POINTER(TakeBloomOpts), C.c_void_p,
+                                      C.POINTER(C.c_double), C.c_void_p, C.c_void_p],
+    "take_hip_tonemap_bloom": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TakeTonemapOpts), C.POINTER(TakeBloomOpts), C.c_void_p,
+                               C.POINTER(C.c_double)],
+}
+
+
 # TakeRenderOpts.integrator: the reference's integrators (src/integrator/path_tracing.h:5, :114, :161, :274)
 INTEGRATOR_PATH_MIS, INTEGRATOR_RAW, INTEGRATOR_ONE_SAMPLE_MIS, INTEGRATOR_ONE_SAMPLE_MIS_POWER = 0, 1, 2, 3
 

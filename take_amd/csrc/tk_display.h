@@ -50,11 +50,16 @@ template <class R> struct Params {
     int32_t op, transfer;  // TAKE_TONEMAP_*, TAKE_TRANSFER_*
 };
 
-// One channel: exposure, clamp to [0, 65504] (NaN and negatives to 0; every operator then stays finite in f32), the
-// operator, clamp to 1, the transfer -> y in [0, 1]
-template <class R> TK_HD R tone_channel(const Params<R> &P, R c) {
-    R x = c * P.exposure;
+// One channel in two halves, so that the bloom composite (tk_bloom.h) can add its layer between them.  The head:
+// exposure, NaN and negatives to 0
+template <class R> TK_HD R expose_channel(R E, R c) {
+    R x = c * E;
     if (!(x > R(0))) x = R(0);
+    return x;
+}
+// The tail, from x >= 0: clamp to 65504 (every operator then stays finite in f32), the operator, clamp to 1, the
+// transfer -> y in [0, 1]
+template <class R> TK_HD R tone_tail(const Params<R> &P, R x) {
     x = tk_fmin(x, R(65504));
     R y = x;
     if (P.op == TAKE_TONEMAP_REINHARD)
@@ -65,6 +70,7 @@ template <class R> TK_HD R tone_channel(const Params<R> &P, R c) {
     if (P.transfer == TAKE_TRANSFER_SRGB) y = y <= R(0.0031308) ? R(12.92) * y : R(1.055) * tk_pow(y, R(1.0 / 2.4)) - R(0.055);
     return y;
 }
+template <class R> TK_HD R tone_channel(const Params<R> &P, R c) { return tone_tail(P, expose_channel(P.exposure, c)); }
 // the 8-bit code of y in [0, 1]
 template <class R> TK_HD uint32_t quantise(R y) { return (uint32_t)(int)(y * R(255) + R(0.5)); }
 
@@ -79,7 +85,9 @@ template <class R> TK_HD uint32_t tone_pixel_rgba(const Params<R> &P, const R *r
     return r | (g << 8) | (b << 16) | (255u << 24);
 }
 
-#if defined(__HIPCC__)
+// The kernels, for the one unit that launches them: tk_display.hip defines TK_DISPLAY_KERNELS before it includes this file;
+// tk_bloom.hip includes it for the per-pixel functions above only.
+#if defined(__HIPCC__) && defined(TK_DISPLAY_KERNELS)
 // Launch geometry of all three kernels over the pixels: 256-thread blocks, at most MAX_BLOCKS of them, grid-stride.
 constexpr int BLOCK = 256, WAVES = BLOCK / 64, MAX_BLOCKS = 2048;
 
@@ -153,7 +161,7 @@ template <class R, bool RGBA> __global__ __launch_bounds__(BLOCK) void k_tonemap
             tone_pixel_real(P, rgb, p, (R *)out);
     }
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && TK_DISPLAY_KERNELS
 
 }  // namespace dp
 }  // namespace tk

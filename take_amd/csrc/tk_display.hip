@@ -1,7 +1,8 @@
 // tk_display.hip — the C entry points of the display transform (include/take_hip.h: take_hip_luminance_histogram*,
 // take_hip_auto_exposure, take_hip_tonemap*) and the only unit that compiles the kernels of tk_display.h.  Scene-free,
 // as the scene-free denoiser calls of tk_denoise.hip: the block histograms are allocated per call, the host twins stage
-// their planes through StagedPlanes.  The auto-exposure is host arithmetic in double and needs no device.
+// their planes through StagedPlanes.  The auto-exposure is host arithmetic in double and needs no device.  What the
+// bloom variant of the transform (tk_bloom.hip) shares is declared in tk_display_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,16 +11,15 @@
 
 #include "take_hip.h"
 #include "tk_host.h"
+#define TK_DISPLAY_KERNELS  // this unit compiles tk_display.h's kernels
 #include "tk_display.h"
+#include "tk_display_host.h"
 
 using namespace tk;
 using namespace tk_host;
+using namespace tk_display;
 
 namespace {
-// TakeExposureOpts with the defaults filled in
-struct ExposureOpts {
-    double key = 0.18, low_fraction = 0.05, high_fraction = 0.95, min_exposure = 1.0 / 65536.0, max_exposure = 65536.0, prev_exposure = 0.0, rate = 1.0;
-};
 int resolve_exposure(const TakeExposureOpts *o, ExposureOpts &r) {
     r = ExposureOpts{};
     if (!o) return TAKE_OK;
@@ -38,9 +38,9 @@ int resolve_exposure(const TakeExposureOpts *o, ExposureOpts &r) {
     if (r.min_exposure > r.max_exposure) return fail(TAKE_E_INVALID, "min_exposure must be at most max_exposure");
     return TAKE_OK;
 }
+}  // namespace
 
-// steps 1 to 8 of take_hip_auto_exposure (include/take_hip.h), in double; hist: no negative count
-double auto_exposure(const int64_t *hist, const ExposureOpts &o) {
+double tk_display::auto_exposure(const int64_t *hist, const ExposureOpts &o) {
     int64_t N = 0;
     for (int b = 0; b < dp::BINS; b++) N += hist[b];
     double target = 1.0;
@@ -68,12 +68,7 @@ double auto_exposure(const int64_t *hist, const ExposureOpts &o) {
     return std::min(std::max(E, o.min_exposure), o.max_exposure);
 }
 
-// TakeTonemapOpts with the defaults filled in
-struct TonemapOpts {
-    double exposure = 0.0, white = 4.0;  // exposure <= 0: automatic
-    int op = TAKE_TONEMAP_ACES, transfer = TAKE_TRANSFER_SRGB, format = TAKE_DISPLAY_RGBA;
-    ExposureOpts auto_opts;
-};
+namespace {
 int resolve_tonemap(const TakeTonemapOpts *o, TonemapOpts &r) {
     r = TonemapOpts{};
     if (!o) return TAKE_OK;
@@ -87,9 +82,9 @@ int resolve_tonemap(const TakeTonemapOpts *o, TonemapOpts &r) {
     if (o->white > 0) r.white = o->white;
     return resolve_exposure(&o->auto_opts, r.auto_opts);
 }
-size_t real_bytes(int32_t precision) { return precision == TAKE_PRECISION_F64 ? 8 : 4; }
-// what both tone-mapping calls refuse, before a device is looked for
-int check_tonemap_args(const void *rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts, const void *out, TonemapOpts &o) {
+}  // namespace
+
+int tk_display::check_tonemap_args(const void *rgb, int32_t precision, int32_t width, int32_t height, const TakeTonemapOpts *opts, const void *out, TonemapOpts &o) {
     if (!rgb || !out) return fail(TAKE_E_INVALID, "null argument");
     if (int rc = check_image(precision, width, height)) return rc;
     if (int rc = resolve_tonemap(opts, o)) return rc;
@@ -102,28 +97,33 @@ int check_tonemap_args(const void *rgb, int32_t precision, int32_t width, int32_
     return TAKE_OK;
 }
 
+namespace {
 dim3 pixel_grid(int64_t npix) { return dim3((unsigned)std::min<int64_t>((npix + dp::BLOCK - 1) / dp::BLOCK, dp::MAX_BLOCKS)); }
+}  // namespace
 
-// The two histogram launches and the copy to the host, on `stream`, drained.  The device is there.
-int histogram_on_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, int64_t *hist_out_host, hipStream_t stream) {
+// the blocks' rows, then (8-byte aligned: SLOTS is even) the sums
+size_t tk_display::histogram_slab_words(int64_t npix) { return ((size_t)pixel_grid(npix).x + 2) * dp::SLOTS; }
+
+int tk_display::histogram_on_device(const void *d_rgb, int32_t precision, int32_t width, int32_t height, int64_t *hist_out_host, hipStream_t stream, uint32_t *slab) {
     const int64_t npix = (int64_t)width * height;
     const dim3 grid = pixel_grid(npix);
-    // the blocks' rows, then (8-byte aligned: SLOTS is even) the sums
-    DevBuf<uint32_t> work;
-    if (work.alloc(((size_t)grid.x + 2) * dp::SLOTS) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the block histograms");
-    int64_t *d_hist = (int64_t *)(work.p + (size_t)grid.x * dp::SLOTS);
+    DevBuf<uint32_t> own;
+    if (!slab) {
+        if (own.alloc(histogram_slab_words(npix)) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the block histograms");
+        slab = own.p;
+    }
+    int64_t *d_hist = (int64_t *)(slab + (size_t)grid.x * dp::SLOTS);
     with_real(precision, [&](auto tag) {
         using R = decltype(tag);
-        hipLaunchKernelGGL((dp::k_luminance_histogram<R>), grid, dim3(dp::BLOCK), 0, stream, (const R *)d_rgb, npix, work.p);
+        hipLaunchKernelGGL((dp::k_luminance_histogram<R>), grid, dim3(dp::BLOCK), 0, stream, (const R *)d_rgb, npix, slab);
         return 0;
     });
-    hipLaunchKernelGGL(dp::k_luminance_sum, dim3((dp::SLOTS + dp::SUM_SLOTS - 1) / dp::SUM_SLOTS), dim3(dp::SUM_SLOTS, dp::SUM_ROWS), 0, stream, (const uint32_t *)work.p, (int)grid.x, d_hist);
+    hipLaunchKernelGGL(dp::k_luminance_sum, dim3((dp::SLOTS + dp::SUM_SLOTS - 1) / dp::SUM_SLOTS), dim3(dp::SUM_SLOTS, dp::SUM_ROWS), 0, stream, (const uint32_t *)slab, (int)grid.x, d_hist);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hist_out_host, d_hist, dp::SLOTS * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return TAKE_OK;
 }
-}  // namespace
 
 extern "C" {
 

@@ -9,7 +9,7 @@ All rendering happens in libtake_hip.so on the current HIP device; without it th
 import numpy as np
 
 from . import cdefs as D
-from .capi import Scene, tonemap
+from .capi import Scene, tonemap, tonemap_bloom
 from .scene import SceneData, load_tkscene
 
 
@@ -124,7 +124,7 @@ def parse_shutter(params):
 
 def main(argv=None):
     """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
-    [-png [linear|reinhard|aces]] [-aperture R [-focus D | -focus_pixel X,Y]]
+    [-png [linear|reinhard|aces] [-bloom [INTENSITY]]] [-aperture R [-focus D | -focus_pixel X,Y]]
     [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
@@ -138,7 +138,10 @@ def main(argv=None):
     beside every .exr a .png of the same stem — exposure, the tone operator (default aces), the sRGB transfer and 8-bit
     RGBA on the device (capi.tonemap), from the float image that was rendered, not from the halves in the .exr.  All of
     them use ONE exposure, the auto-exposure of image.exr's render, so that image.png, denoised.png and
-    adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag.  -aperture (an extension): a thin lens of
+    adaptive_denoised.png can be compared; one line prints it.  Every .exr is the same bytes with or without the flag.
+    -bloom (an extension, needs -png): the .png files get glare around what exceeds the display range after that one
+    exposure (capi.tonemap_bloom with the library's threshold and knee, and INTENSITY if the next parameter reads as a
+    number); one more line says so; without it every file is the same bytes as before.  -aperture (an extension): a thin lens of
     that radius (Scene.set_lens) set before anything is rendered, focused at -focus D along the view axis, on what pixel
     X,Y (row 0 = top) sees (-focus_pixel; Scene.focus_distance_at), or on the camera's lookat; every file is then of the
     camera with the lens, and one line prints the focus distance in effect.  -shutter (an extension): also shutter.exr,
@@ -169,6 +172,18 @@ def main(argv=None):
             png_op = params[i + 1]
             del params[i + 1]
         del params[i]
+    bloom = None
+    if "-bloom" in params:  # the intensity is optional: the next parameter, if it reads as a number
+        i = params.index("-bloom")
+        bloom = {}
+        try:
+            bloom = {"intensity": float(params[i + 1])}
+            del params[i + 1]
+        except (IndexError, ValueError):
+            pass
+        del params[i]
+        if png_op is None:
+            raise SystemExit("-bloom needs -png")
     lens = parse_lens(params)
     shutter = parse_shutter(params)
     features, denoise = "-features" in params, "-denoise" in params
@@ -222,11 +237,18 @@ def main(argv=None):
             # auto-exposure, and that one exposure for every image
             from .png import write_png
 
-            rgba, exposure = tonemap(scene.render(spp=sd.spp, max_depth=max_depth, seed=0), op=png_op)
+            def display(img, exposure=None):
+                if bloom is None:
+                    return tonemap(img, exposure=exposure, op=png_op)
+                return tonemap_bloom(img, exposure=exposure, op=png_op, **bloom)
+
+            rgba, exposure = display(scene.render(spp=sd.spp, max_depth=max_depth, seed=0))
             write_png("image.png", rgba)
             for stem, img in floats:
-                write_png(stem + ".png", tonemap(img, exposure=exposure, op=png_op)[0])
+                write_png(stem + ".png", display(img, exposure)[0])
             print(f"png: exposure {exposure!r} ({png_op})")
+            if bloom is not None:
+                print(f"png: bloom intensity {bloom.get('intensity', D.BLOOM_DEFAULTS['intensity'])!r}")
     finally:
         scene.close()
     return 0
