@@ -67,10 +67,140 @@ struct Fix {
 TK_HD bool is_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
 TK_HD bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
 
-#if defined(__HIPCC__)
-__constant__ double k_pow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                                   1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+// ---- tokens and lines: host-callable, so that tests/obj_host can run this text without a GPU ----------------------
+TK_HD void trim(const uint8_t *b, int64_t &s, int64_t &e) {
+    while (s < e && is_space(b[s])) s++;
+    while (e > s && is_space(b[e - 1])) e--;
+}
 
+// the next whitespace-delimited token of [p, e) (operator>> of a std::string) -> [ts, te)
+TK_HD bool next_token(const uint8_t *b, int64_t &p, int64_t e, int64_t &ts, int64_t &te) {
+    while (p < e && is_space(b[p])) p++;
+    if (p >= e) return false;
+    ts = p;
+    while (p < e && !is_space(b[p])) p++;
+    te = p;
+    return true;
+}
+
+// the type of the line [s, e): the first token of the trimmed line; for `f`, how many corners follow (counting stops at 5)
+TK_HD uint8_t classify_line(const uint8_t *b, int64_t s, int64_t e) {
+    int64_t ts = 0, te = 0;
+    trim(b, s, e);
+    uint8_t t = L_NONE;
+    int64_t p = s;
+    if (s < e && b[s] != '#' && next_token(b, p, e, ts, te)) {
+        const int64_t len = te - ts;
+        if (len == 1 && b[ts] == 'v') t = L_V;
+        else if (len == 2 && b[ts] == 'v' && b[ts + 1] == 't') t = L_VT;
+        else if (len == 2 && b[ts] == 'v' && b[ts + 1] == 'n') t = L_VN;
+        else if (len == 1 && b[ts] == 'f') {
+            int k = 0;
+            while (k < 5 && next_token(b, p, e, ts, te)) k++;
+            t = k == 3 ? L_F3 : k == 4 ? L_F4 : L_FBAD;
+        }
+    }
+    return t;
+}
+
+// 10^k for k in [0, 22]: the powers of ten a double holds exactly
+TK_HD double pow10_exact(int64_t k) {
+    static constexpr double t[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                                     1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+    return t[k];
+}
+
+// `ss >> Real` on one token [p, e): 0 = converted exactly into *out, 1 = in the grammar but the host's strtod converts
+// it, -1 = not a number num_get would read whole (the file is unsupported)
+TK_HD int parse_real(const uint8_t *b, int64_t p, int64_t e, double *out) {
+    bool neg = false;
+    if (p < e && (b[p] == '+' || b[p] == '-')) neg = b[p++] == '-';
+    uint64_t m = 0;
+    int64_t nd = 0, zeros = 0, nint = 0, nfrac = 0;  // significant digits so far, trailing zeros not in m yet
+    auto digit = [&](int d) {
+        if (nd == 0) {
+            if (d) m = (uint64_t)d, nd = 1;
+        } else if (d == 0) {
+            zeros++;
+        } else {
+            nd += zeros + 1;
+            if (nd <= 15) {
+                for (int64_t k = 0; k <= zeros; k++) m *= 10;
+                m += (uint64_t)d;
+            }
+            zeros = 0;
+        }
+    };
+    while (p < e && is_digit(b[p])) digit(b[p++] - '0'), nint++;
+    if (p < e && b[p] == '.') {
+        p++;
+        while (p < e && is_digit(b[p])) digit(b[p++] - '0'), nfrac++;
+    }
+    if (nint == 0 && nfrac == 0) return -1;
+    int64_t ex = 0;
+    if (p < e && (b[p] == 'e' || b[p] == 'E')) {
+        p++;
+        bool eneg = false;
+        if (p < e && (b[p] == '+' || b[p] == '-')) eneg = b[p++] == '-';
+        if (p >= e || !is_digit(b[p])) return -1;
+        while (p < e && is_digit(b[p])) {
+            ex = ex * 10 + (b[p++] - '0');
+            if (ex > 100000000) ex = 100000000;
+        }
+        if (eneg) ex = -ex;
+    }
+    if (p != e) return -1;
+    if (nd == 0) {  // every digit zero: a signed zero, whatever the exponent
+        *out = neg ? -0.0 : 0.0;
+        return 0;
+    }
+    const int64_t E = ex - nfrac + zeros;
+    if (nd > 15 || E < -22 || E > 22) return 1;
+    double v = (double)m;
+    v = E >= 0 ? v * pow10_exact(E) : v / pow10_exact(-E);
+    *out = neg ? -v : v;
+    return 0;
+}
+
+// std::stoi on a non-empty piece [p, e): a leading [+-]?digits (anything behind it ignored), or false where stoi throws
+TK_HD bool stoi_prefix(const uint8_t *b, int64_t p, int64_t e, int32_t &v) {
+    bool neg = false;
+    if (p < e && (b[p] == '+' || b[p] == '-')) neg = b[p++] == '-';
+    if (p >= e || !is_digit(b[p])) return false;
+    int64_t a = 0;
+    while (p < e && is_digit(b[p])) {
+        a = a * 10 + (b[p++] - '0');
+        if (a > ((int64_t)1 << 32)) a = (int64_t)1 << 32;
+    }
+    if (neg) a = -a;
+    if (a < INT32_MIN || a > INT32_MAX) return false;
+    v = (int32_t)a;
+    return true;
+}
+
+// split_face_str: the pieces between '/' (std::sregex_token_iterator, -1: every piece in front of a '/', and the piece
+// behind the last one only if it is not empty), "" -> 0, std::stoi on the others, padded with zeros to three; pieces
+// after the third are converted (and can throw) but not kept
+TK_HD bool parse_corner(const uint8_t *b, int64_t s, int64_t e, int32_t key[3]) {
+    key[0] = key[1] = key[2] = 0;
+    int part = 0;
+    int64_t p = s;
+    while (true) {
+        int64_t q = p;
+        while (q < e && b[q] != '/') q++;
+        const bool last = q >= e;
+        if (last && q == p) break;
+        int32_t v = 0;
+        if (q > p && !stoi_prefix(b, p, q, v)) return false;
+        if (part < 3) key[part] = v;
+        part++;
+        if (last) break;
+        p = q + 1;
+    }
+    return true;
+}
+
+#if defined(__HIPCC__)
 // ---- three-phase scan: f.load(i) -> T, f.store(i, exclusive prefix) ----------------------------------------------
 constexpr int SCAN_BLK = 256, SCAN_IPT = 16;
 constexpr int64_t SCAN_TILE = (int64_t)SCAN_BLK * SCAN_IPT;
@@ -163,136 +293,16 @@ TK_D void line_bounds(const int32_t *nl, int64_t nnl, int64_t n, int64_t i, int6
     e = i < nnl ? (int64_t)nl[i] : n;
 }
 
-TK_D void trim(const uint8_t *b, int64_t &s, int64_t &e) {
-    while (s < e && is_space(b[s])) s++;
-    while (e > s && is_space(b[e - 1])) e--;
-}
-
-// the next whitespace-delimited token of [p, e) (operator>> of a std::string) -> [ts, te)
-TK_D bool next_token(const uint8_t *b, int64_t &p, int64_t e, int64_t &ts, int64_t &te) {
-    while (p < e && is_space(b[p])) p++;
-    if (p >= e) return false;
-    ts = p;
-    while (p < e && !is_space(b[p])) p++;
-    te = p;
-    return true;
-}
-
 TK_D void report(unsigned long long *status, int64_t line, uint32_t code) {
     atomicMin(status, ((unsigned long long)line << 8) | code);
 }
 
-// the first token of the trimmed line; for `f`, how many corners follow (counting stops at 5)
 __global__ void k_obj_classify(const uint8_t *b, int64_t n, const int32_t *nl, int64_t nnl, uint8_t *type) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > nnl) return;
-    int64_t s, e, ts = 0, te = 0;
+    int64_t s, e;
     line_bounds(nl, nnl, n, i, s, e);
-    trim(b, s, e);
-    uint8_t t = L_NONE;
-    int64_t p = s;
-    if (s < e && b[s] != '#' && next_token(b, p, e, ts, te)) {
-        const int64_t len = te - ts;
-        if (len == 1 && b[ts] == 'v') t = L_V;
-        else if (len == 2 && b[ts] == 'v' && b[ts + 1] == 't') t = L_VT;
-        else if (len == 2 && b[ts] == 'v' && b[ts + 1] == 'n') t = L_VN;
-        else if (len == 1 && b[ts] == 'f') {
-            int k = 0;
-            while (k < 5 && next_token(b, p, e, ts, te)) k++;
-            t = k == 3 ? L_F3 : k == 4 ? L_F4 : L_FBAD;
-        }
-    }
-    type[i] = t;
-}
-
-// `ss >> Real` on one token [p, e): 0 = converted exactly into *out, 1 = in the grammar but the host's strtod converts
-// it, -1 = not a number num_get would read whole (the file is unsupported)
-TK_D int parse_real(const uint8_t *b, int64_t p, int64_t e, double *out) {
-    bool neg = false;
-    if (p < e && (b[p] == '+' || b[p] == '-')) neg = b[p++] == '-';
-    uint64_t m = 0;
-    int64_t nd = 0, zeros = 0, nint = 0, nfrac = 0;  // significant digits so far, trailing zeros not in m yet
-    auto digit = [&](int d) {
-        if (nd == 0) {
-            if (d) m = (uint64_t)d, nd = 1;
-        } else if (d == 0) {
-            zeros++;
-        } else {
-            nd += zeros + 1;
-            if (nd <= 15) {
-                for (int64_t k = 0; k <= zeros; k++) m *= 10;
-                m += (uint64_t)d;
-            }
-            zeros = 0;
-        }
-    };
-    while (p < e && is_digit(b[p])) digit(b[p++] - '0'), nint++;
-    if (p < e && b[p] == '.') {
-        p++;
-        while (p < e && is_digit(b[p])) digit(b[p++] - '0'), nfrac++;
-    }
-    if (nint == 0 && nfrac == 0) return -1;
-    int64_t ex = 0;
-    if (p < e && (b[p] == 'e' || b[p] == 'E')) {
-        p++;
-        bool eneg = false;
-        if (p < e && (b[p] == '+' || b[p] == '-')) eneg = b[p++] == '-';
-        if (p >= e || !is_digit(b[p])) return -1;
-        while (p < e && is_digit(b[p])) {
-            ex = ex * 10 + (b[p++] - '0');
-            if (ex > 100000000) ex = 100000000;
-        }
-        if (eneg) ex = -ex;
-    }
-    if (p != e) return -1;
-    if (nd == 0) {  // every digit zero: a signed zero, whatever the exponent
-        *out = neg ? -0.0 : 0.0;
-        return 0;
-    }
-    const int64_t E = ex - nfrac + zeros;
-    if (nd > 15 || E < -22 || E > 22) return 1;
-    double v = (double)m;
-    v = E >= 0 ? v * k_pow10[E] : v / k_pow10[-E];
-    *out = neg ? -v : v;
-    return 0;
-}
-
-// std::stoi on a non-empty piece [p, e): a leading [+-]?digits (anything behind it ignored), or false where stoi throws
-TK_D bool stoi_prefix(const uint8_t *b, int64_t p, int64_t e, int32_t &v) {
-    bool neg = false;
-    if (p < e && (b[p] == '+' || b[p] == '-')) neg = b[p++] == '-';
-    if (p >= e || !is_digit(b[p])) return false;
-    int64_t a = 0;
-    while (p < e && is_digit(b[p])) {
-        a = a * 10 + (b[p++] - '0');
-        if (a > ((int64_t)1 << 32)) a = (int64_t)1 << 32;
-    }
-    if (neg) a = -a;
-    if (a < INT32_MIN || a > INT32_MAX) return false;
-    v = (int32_t)a;
-    return true;
-}
-
-// split_face_str: the pieces between '/' (std::sregex_token_iterator, -1: every piece in front of a '/', and the piece
-// behind the last one only if it is not empty), "" -> 0, std::stoi on the others, padded with zeros to three; pieces
-// after the third are converted (and can throw) but not kept
-TK_D bool parse_corner(const uint8_t *b, int64_t s, int64_t e, int32_t key[3]) {
-    key[0] = key[1] = key[2] = 0;
-    int part = 0;
-    int64_t p = s;
-    while (true) {
-        int64_t q = p;
-        while (q < e && b[q] != '/') q++;
-        const bool last = q >= e;
-        if (last && q == p) break;
-        int32_t v = 0;
-        if (q > p && !stoi_prefix(b, p, q, v)) return false;
-        if (part < 3) key[part] = v;
-        part++;
-        if (last) break;
-        p = q + 1;
-    }
-    return true;
+    type[i] = classify_line(b, s, e);
 }
 
 // per line: the numbers of v / vt / vn lines into the raw pools (v: x y z w, w = 1 unless given; vt: s t; vn: x y z),

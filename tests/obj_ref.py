@@ -67,6 +67,22 @@ def split_face(tok):
     return (out + [0, 0, 0])[:3]
 
 
+def line_kind(ln):
+    """what parse_obj's loop makes of one line (without its '\\n') -> (kind, tokens): "v" / "vt" / "vn", "f3" / "f4" for a
+    face of 3 / 4 corners, "fbad" for any other number of them, or None for a line it skips (blank, a comment, any other
+    keyword)"""
+    ln = ln.strip()
+    if not ln or ln[:1] == b"#":
+        return None, []
+    tok = ln.split()
+    kw = tok[0]
+    if kw in (b"v", b"vt", b"vn"):
+        return kw.decode(), tok
+    if kw == b"f":
+        return {3: "f3", 4: "f4"}.get(len(tok) - 1, "fbad"), tok
+    return None, []
+
+
 def xform_point(m, p):
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     tx = m[0, 0] * x + m[0, 1] * y + m[0, 2] * z + m[0, 3]
@@ -79,7 +95,7 @@ def xform_point(m, p):
 
 def normalize(n):
     x, y, z = n[:, 0], n[:, 1], n[:, 2]
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         l = np.sqrt(x * x + y * y + z * z)
         inv = 1.0 / l
         out = np.stack([x * inv, y * inv, z * inv], 1)
@@ -108,10 +124,9 @@ def parse_obj(data, to_world=None, inv_to_world=None):
             err = (line, code)
 
     for i, ln in enumerate(bytes(data).split(b"\n")):
-        ln = ln.strip()
-        if not ln or ln[:1] == b"#":
+        kind, tok = line_kind(ln)
+        if kind is None:
             continue
-        tok = ln.split()
         kw = tok[0]
         if kw in (b"v", b"vt", b"vn"):
             need = 2 if kw == b"vt" else 3

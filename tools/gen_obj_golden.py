@@ -25,6 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from oracle import obj_tokens  # noqa: E402  (the token lists of the number_grammar case)
 from oracle.gen_golden import HARNESS, run, write_ply  # noqa: E402
 from take_amd.scene import load_tkscene  # noqa: E402
 
@@ -117,6 +118,21 @@ def cases():
         "f 1// 2/ 4",
         "f 4/// +3 2//",
     ]) + "\n", I4, False)
+    # 10. the number grammar at the edges of the window in which the device converts a number itself (15 / 16
+    #     significant digits, effective exponent 22 / 23, zero runs, signed zeros, the ends of the double range): the
+    #     curated tokens and a fixed slice of the generated ones (oracle/obj_tokens.py), every one as a vt's first
+    #     coordinate (the decode leaves it untouched: signed zeros are visible), as a v coordinate and as a vn coordinate;
+    #     a few v lines carry a w.  Identity to_world; the faces use every vertex.
+    toks = [t.decode() for t in obj_tokens.CURATED + obj_tokens.number_tokens(180 - len(obj_tokens.CURATED))]
+    n = len(toks)
+    mild = [t for t in toks if 1e-3 <= abs(float(t)) <= 1e3]
+    v = [f"v {toks[i]} {toks[(i + 1) % n]} {toks[(i + 2) % n]}" for i in range(n)]
+    v += [f"v {mild[i]} {mild[i + 1]} {mild[i + 2]} {mild[i + 3]}" for i in range(12)]
+    m = len(v)
+    vt = [f"vt {toks[i % n]} {toks[(i + 5) % n]}" for i in range(m)]
+    vn = [f"vn {toks[(i + 3) % n]} {toks[(i + 4) % n]} {toks[(i + 7) % n]}" for i in range(m)]
+    faces = ["f " + " ".join(f"{j % m + 1}/{j % m + 1}/{j % m + 1}" for j in (i, i + 1, i + 2)) for i in range(0, m, 3)]
+    out["number_grammar"] = ("\n".join(["# number grammar"] + v + vt + vn + faces) + "\n", I4, True)
     return out
 
 
