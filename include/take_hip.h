@@ -1018,6 +1018,65 @@ int take_hip_trace_any(TakeScene *scene, const void *rays, int64_t n, int32_t *o
 int take_hip_trace_closest_device(TakeScene *scene, const void *d_rays, int64_t n, void *d_hits,
                                   int32_t count_mode, void *stream);
 
+/* ---- path tracing of caller-supplied rays, and the scene's own camera rays (EXTENSION, parity unpinned; new symbols
+ * of ABI version 5; no struct changed; DESIGN.md par. 4n).  The trace hooks above take rays from the caller and stop
+ * at the first hit; take_hip_render_rays* carries radiance along them: light probes and lightmap texels, a panoramic,
+ * orthographic or fisheye camera, a batch of rays in a torch tensor, a reprojected or foveated sample pattern.
+ *  - take_hip_render_rays*: n rays = n output texels.  rgb_out: n * 3 Real in ray order (float for F32 scenes, double
+ *    for F64 and MIXED ones); texel i is the mean over the opts->spp samples of "the integrator's radiance along that
+ *    sample's ray", summed in sample order and then multiplied by 1 / spp, as a render's pixel is.  ray_sets == 1: ray
+ *    i serves all spp samples of texel i; ray_sets == spp: sample s of texel i travels along rays[s * n + i].
+ *    The random stream of sample s of ray i is the stream a render gives sample first_sample + s of pixel index i
+ *    — rng_key(seed, i, first_sample + s) — and the path starts it at counter 2 (CAMERA_DRAWS): counters 0 and 1 are
+ *    left to the caller's own jitter.  The stream does not depend on n, ray_sets or samples_per_batch: a ray traced in
+ *    a call of its own at the same index i gives the same bits, and spp = 1 calls with first_sample = 0, 1, ... are
+ *    the samples of one spp call.
+ *    Of a ray record org and dir are used.  tmin and tmax are IGNORED: the first segment starts at the effective
+ *    ray_epsilon and is unbounded, as a camera ray's is (the render loop keeps one tmin for all rays of a launch).
+ *    Directions must have unit length: the shade rounds take cosines against them.  The host entry refuses a ray with
+ *    a non-finite component of org or dir, and — without TAKE_RAYS_NORMALIZE — one with | |dir|^2 - 1 | > 1e-3 (with
+ *    the flag: one whose direction has zero or overflowing length); the message names the first such ray.  The device
+ *    entry cannot look: it takes the rays as they are, a direction that is not of unit length scales the cosines of
+ *    its first vertex (a biased texel, no fault), and a non-finite one gives a texel that is not finite.  With
+ *    TAKE_RAYS_NORMALIZE every direction goes through the camera ray's own normalize on the device before use.
+ *    All four integrators, max_depth, samples_per_batch and ray_epsilon as take_hip_render takes them, environment
+ *    maps too (and the refusal of one for integrators 1..3); strip_first / strip_stride are ignored, and so is the
+ *    lens: the rays are the caller's.  F32, F64 and MIXED scenes (a mixed scene makes its records on the f64 side and
+ *    hands over as a render does), one- and two-level scenes; not for scene groups.  The call uses the render
+ *    workspace, the accumulator included: it ends a progressive sequence as take_hip_render does.
+ *    take_hip_get_counters afterwards: samples = n * spp, the rest as after a render.  n == 0 is TAKE_OK and writes
+ *    nothing.  The device entry: d_rays and d_rgb_out are device memory, d_rays 16-byte aligned; enqueued on `stream`,
+ *    returns after enqueue + sync.
+ *    TAKE_E_INVALID, before a device is looked for: a NULL argument ("null argument"; rays and the output may be NULL
+ *    when n == 0), spp <= 0, max_depth < -1 or an unknown integrator, n < 0 or n >= 2^30, ray_sets other than 1 or
+ *    spp, first_sample < 0 or first_sample + spp beyond int32, unknown flag bits, a non-zero reserved, a device ray
+ *    pointer that is not 16-byte aligned; the host entry's look at the rays; then what take_hip_render refuses of the
+ *    scene.  A failed call leaves the scene rendering as before.
+ *  - take_hip_camera_rays*: the inverse — opts->spp * W * H ray records in that layout (ray_sets == spp, n = W * H),
+ *    TakeRayF for F32 scenes and TakeRayD for F64 and MIXED ones (the f64 camera).  Ray index i = y * W + x with
+ *    y = 0 the BOTTOM image row: the render loop's pixel index, so that the keys above line up.  Set s holds exactly
+ *    the rays a whole-image take_hip_render with the same seed traces for sample first_sample + s: org = lookfrom for
+ *    the pinhole camera, the lens ray with a lens (take_hip_scene_set_lens); tmin = the effective ray epsilon and
+ *    tmax = +inf, so that the buffer can go straight into the trace hooks — or back into take_hip_render_rays*, whose
+ *    image for (these rays, ray_sets = spp, the same seed and first_sample) is take_hip_render's bit for bit, row y of
+ *    it being image row H - 1 - y.  Of the options only seed, spp and ray_epsilon are read; strips are ignored.  The
+ *    call uses path records only: a progressive sequence goes on after it, as after the feature pass.  Not for scene
+ *    groups.  TAKE_E_INVALID, before a device is looked for: a NULL argument, spp <= 0, first_sample < 0 or
+ *    first_sample + spp beyond int32, a device pointer that is not 16-byte aligned. */
+#define TAKE_RAYS_NORMALIZE 1 /* normalise every direction on the device before use */
+typedef struct TakeRayBatch {
+    const void *rays;     /* TakeRayF (F32 scenes) or TakeRayD (F64, MIXED): ray_sets * n records */
+    int64_t n;            /* rays = output texels */
+    int32_t ray_sets;     /* 1: ray i serves all spp samples; == spp: sample s of ray i is rays[s * n + i] */
+    int32_t first_sample; /* samples are numbered first_sample .. first_sample + spp - 1 (>= 0) */
+    int32_t flags;        /* 0 or TAKE_RAYS_NORMALIZE */
+    int32_t reserved;     /* 0 */
+} TakeRayBatch;
+int take_hip_render_rays_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeRayBatch *batch /* rays: device */, void *d_rgb_out, void *stream);
+int take_hip_render_rays(TakeScene *scene, const TakeRenderOpts *opts, const TakeRayBatch *batch /* rays: host */, void *rgb_out_host);
+int take_hip_camera_rays_device(TakeScene *scene, const TakeRenderOpts *opts, int32_t first_sample, void *d_rays_out, void *stream);
+int take_hip_camera_rays(TakeScene *scene, const TakeRenderOpts *opts, int32_t first_sample, void *rays_out_host);
+
 /* ---- several GPUs from ONE process (the C++ host of the reference is a single process: main.cpp -> render()).
  * Replaces the thread pool of src/parallel.cpp:183-237 for the drop-in: the scene is built once per device
  * (replicated), device k of n renders the 4-row strips s with s % n == k on its own host thread, and the strips are

@@ -42,6 +42,7 @@ EXPORTS = [
     "take_hip_shutter_plan", "take_hip_shutter_pose", "take_hip_render_shutter", "take_hip_render_shutter_device",
     "take_hip_image_workspace_create", "take_hip_image_workspace_destroy", "take_hip_bloom_layer", "take_hip_bloom_layer_device",
     "take_hip_tonemap_bloom", "take_hip_tonemap_bloom_device",
+    "take_hip_render_rays", "take_hip_render_rays_device", "take_hip_camera_rays", "take_hip_camera_rays_device",
 ]
 
 
@@ -89,7 +90,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -1032,6 +1033,51 @@ class Scene:
     def trace_closest_device(self, d_rays, n, d_hits, count_mode=False, stream=None):
         _check(lib().take_hip_trace_closest_device(self.h, C.c_void_p(d_rays), int(n), C.c_void_p(d_hits),
                                                    int(count_mode), C.c_void_p(stream or 0)))
+
+    def _ray_batch(self, ptr, n, ray_sets, first_sample, normalize):
+        return D.TakeRayBatch(ptr, int(n), int(ray_sets), int(first_sample), D.TAKE_RAYS_NORMALIZE if normalize else 0, 0)
+
+    def render_rays(self, rays, spp, max_depth=None, seed=0, ray_epsilon=0.0, samples_per_batch=0, integrator=0, ray_sets=1, first_sample=0,
+                    normalize=False):
+        """path tracing of the caller's rays (take_hip_render_rays): rays is (n, 8) — or (ray_sets, n, 8) — in TakeRayF/D
+        layout (org3 tmin dir3 tmax; tmin and tmax are ignored, directions of unit length unless normalize=True) ->
+        (n, 3) host array in the scene's Real, texel i the mean over spp samples of the radiance along ray i.  ray_sets:
+        1 = ray i serves all samples, spp = sample s of texel i travels along rays[s, i].  The random stream of sample s
+        of ray i is a render's for sample first_sample + s of pixel index i."""
+        rays = np.ascontiguousarray(rays, self.dtype)
+        if rays.shape[-1] != 8 or rays.size % (8 * int(ray_sets)):
+            raise ValueError("rays must have shape (n, 8) or (ray_sets, n, 8)")
+        n = rays.size // (8 * int(ray_sets))
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        b = self._ray_batch(rays.ctypes.data, n, ray_sets, first_sample, normalize)
+        out = np.zeros((n, 3), self.dtype)
+        _check(lib().take_hip_render_rays(self.h, C.byref(o), C.byref(b), out.ctypes.data))
+        return out
+
+    def render_rays_device(self, d_rays, n, d_out, spp, max_depth, seed=0, ray_epsilon=0.0, samples_per_batch=0, stream=None, integrator=0,
+                           ray_sets=1, first_sample=0, normalize=False):
+        """the same on device memory (take_hip_render_rays_device): d_rays and d_out are torch device tensors or integer
+        device pointers (e.g. a tensor's data_ptr()) — ray_sets * n records of 8 Reals, 16-byte aligned, and n * 3 Reals
+        of the scene's Real; the rays are taken as they are (unit directions, or normalize=True); blocks until done"""
+        o = self._opts(spp, max_depth, seed, ray_epsilon, 0, 1, samples_per_batch, integrator)
+        b = self._ray_batch(_pointer(d_rays), n, ray_sets, first_sample, normalize)
+        _check(lib().take_hip_render_rays_device(self.h, C.byref(o), C.byref(b), C.c_void_p(_pointer(d_out)), C.c_void_p(stream or 0)))
+
+    def camera_rays(self, spp, seed=0, first_sample=0, ray_epsilon=0.0):
+        """the scene's own camera rays (take_hip_camera_rays) -> (spp, H * W, 8) host array in TakeRayF/D layout: set s
+        holds the rays a whole-image render with this seed traces for sample first_sample + s, ray i = y * W + x with
+        y = 0 the BOTTOM image row; tmin = the effective ray epsilon, tmax = inf.  Goes into trace_closest as it is, and
+        back into render_rays(ray_sets=spp), whose image — flipped vertically — is render()'s bit for bit."""
+        o = self._opts(spp, 0, seed, ray_epsilon, 0, 1, 0)
+        out = np.zeros((int(spp), self.sd.height * self.sd.width, 8), self.dtype)
+        _check(lib().take_hip_camera_rays(self.h, C.byref(o), int(first_sample), out.ctypes.data))
+        return out
+
+    def camera_rays_device(self, d_rays_out, spp, seed=0, first_sample=0, ray_epsilon=0.0, stream=None):
+        """the same into device memory (take_hip_camera_rays_device): d_rays_out is a torch device tensor or an integer
+        device pointer of spp * H * W * 8 of the scene's Real, 16-byte aligned; blocks until done"""
+        o = self._opts(spp, 0, seed, ray_epsilon, 0, 1, 0)
+        _check(lib().take_hip_camera_rays_device(self.h, C.byref(o), int(first_sample), C.c_void_p(_pointer(d_rays_out)), C.c_void_p(stream or 0)))
 
     def set_instrumentation(self, timing=False, counting=False):
         _check(lib().take_hip_set_instrumentation(self.h, (1 if timing else 0) | (2 if counting else 0)))

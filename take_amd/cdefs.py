@@ -369,6 +369,25 @@ class TakeRayD(C.Structure):
     _fields_ = [("org", c_double3), ("tmin", C.c_double), ("dir", c_double3), ("tmax", C.c_double)]
 
 
+# path tracing of caller-supplied rays, and the scene's own camera rays (include/take_hip.h)
+TAKE_RAYS_NORMALIZE = 1  # normalise every direction on the device before use
+
+
+class TakeRayBatch(C.Structure):
+    """take_hip_render_rays*: ray_sets * n ray records (host or device memory), n = output texels; ray_sets 1 or spp"""
+    _fields_ = [("rays", C.c_void_p), ("n", C.c_int64), ("ray_sets", C.c_int32), ("first_sample", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# name -> argument types
+RAYS_PROTOTYPES = {
+    "take_hip_render_rays_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeRayBatch), C.c_void_p, C.c_void_p],
+    "take_hip_render_rays": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeRayBatch), C.c_void_p],
+    "take_hip_camera_rays_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_int32, C.c_void_p, C.c_void_p],
+    "take_hip_camera_rays": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_int32, C.c_void_p],
+}
+
+
 class TakeHitF(C.Structure):
     _fields_ = [("shape_id", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
 

@@ -65,6 +65,41 @@ template <class R> int debug_tree_copy(const SceneT<R> &sc, void *nodes, void *p
     if (o.n_instances > 0) HIP_TRY(hipMemcpy(inst_trace, sc.dev.inst_trace, (size_t)o.n_instances * o.inst_bytes, hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
+// take_hip_render_rays* / take_hip_camera_rays*: what needs neither scene nor device
+int check_first_sample(int32_t first_sample, int32_t spp) {
+    if (first_sample < 0 || (int64_t)first_sample + (int64_t)spp > (int64_t)INT32_MAX)
+        return fail(TAKE_E_INVALID, "first_sample must be >= 0 and first_sample + spp must fit int32");
+    return TAKE_OK;
+}
+int check_ray_batch(const TakeScene *ts, const TakeRenderOpts *opts, const TakeRayBatch *b, const void *out) {
+    if (!ts || !opts || !b || (b->n > 0 && (!b->rays || !out))) return fail(TAKE_E_INVALID, "null argument");
+    if (int rc = check_render_values(*opts)) return rc;
+    if (b->n < 0 || b->n >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "n must be in [0, 2^30)");
+    if (b->ray_sets != 1 && b->ray_sets != opts->spp) return fail(TAKE_E_INVALID, "ray_sets must be 1 or spp");
+    if (int rc = check_first_sample(b->first_sample, opts->spp)) return rc;
+    if (b->flags & ~TAKE_RAYS_NORMALIZE) return fail(TAKE_E_INVALID, "unknown flag bits");
+    if (b->reserved != 0) return fail(TAKE_E_INVALID, "reserved must be 0");
+    return TAKE_OK;
+}
+// the host entry's look at the rays: the first with a non-finite component, or a direction the call cannot use
+template <class R> int check_host_rays(const void *rays, int64_t count, bool normalise) {
+    const R *r = (const R *)rays;
+    auto refuse = [](int64_t i, const char *why) { return fail(TAKE_E_INVALID, "ray " + std::to_string(i) + ": " + why); };
+    for (int64_t i = 0; i < count; i++, r += 8) {
+        for (int c : {0, 1, 2, 4, 5, 6})
+            if (!std::isfinite(r[c])) return refuse(i, "org and dir must be finite");
+        if (normalise) {
+            const R l2 = r[4] * r[4] + r[5] * r[5] + r[6] * r[6];  // (in Real, as the device's normalize)
+            if (!(l2 > R(0)) || !std::isfinite(l2)) return refuse(i, "the direction's length is zero or overflows: it cannot be normalised");
+        } else {
+            const double x = r[4], y = r[5], z = r[6];
+            if (!(std::fabs(x * x + y * y + z * z - 1.0) <= 1e-3))
+                return refuse(i, "the direction is not of unit length (| |dir|^2 - 1 | > 1e-3): normalise it, or pass TAKE_RAYS_NORMALIZE");
+        }
+    }
+    return TAKE_OK;
+}
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 namespace tk_host {
@@ -232,6 +267,64 @@ int take_hip_trace_closest_device(TakeScene *ts, const void *d_rays, int64_t n, 
     if (n == 0) return TAKE_OK;
     TAKE_ON_DEVICE(ts);
     return trace_rays_device(ts, d_rays, n, d_hits, count_mode != 0, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------ caller-supplied rays
+// Path tracing of caller-supplied rays and the export of the scene's camera rays (include/take_hip.h):
+// tk_render.hip, rays_impl and camera_rays_impl.  What needs no device is looked at before one is looked for.
+int take_hip_render_rays_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeRayBatch *batch, void *d_rgb_out, void *stream) {
+    if (int rc = check_ray_batch(ts, opts, batch, d_rgb_out)) return rc;
+    if (!aligned16(batch->rays)) return fail(TAKE_E_INVALID, "the rays must be 16-byte aligned");
+    if (batch->n == 0) return TAKE_OK;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    return render_rays_scene(ts, *opts, *batch, d_rgb_out, (hipStream_t)stream);
+}
+int take_hip_render_rays(TakeScene *ts, const TakeRenderOpts *opts, const TakeRayBatch *batch, void *rgb_out_host) {
+    if (int rc = check_ray_batch(ts, opts, batch, rgb_out_host)) return rc;
+    const int64_t count = (int64_t)batch->ray_sets * batch->n;
+    const bool normalise = (batch->flags & TAKE_RAYS_NORMALIZE) != 0;
+    if (int rc = ts->f64() ? check_host_rays<double>(batch->rays, count, normalise) : check_host_rays<float>(batch->rays, count, normalise)) return rc;
+    if (batch->n == 0) return TAKE_OK;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    const size_t real = ts->f64() ? 8 : 4;
+    DevBuf<char> d_rays, d_out;
+    if (d_rays.alloc((size_t)count * 8 * real) != hipSuccess || d_out.alloc((size_t)batch->n * 3 * real) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for the rays and their texels");
+    if (hipMemcpy(d_rays.p, batch->rays, d_rays.bytes(), hipMemcpyHostToDevice) != hipSuccess) return fail(TAKE_E_DEVICE, "ray upload failed");
+    TakeRayBatch d_batch = *batch;
+    d_batch.rays = d_rays.p;
+    if (int rc = render_rays_scene(ts, *opts, d_batch, d_out.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rgb_out_host, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+int take_hip_camera_rays_device(TakeScene *ts, const TakeRenderOpts *opts, int32_t first_sample, void *d_rays_out, void *stream) {
+    if (!ts || !opts || !d_rays_out) return fail(TAKE_E_INVALID, "null argument");
+    if (opts->spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    if (int rc = check_first_sample(first_sample, opts->spp)) return rc;
+    if (!aligned16(d_rays_out)) return fail(TAKE_E_INVALID, "the rays must be 16-byte aligned");
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    return camera_rays_scene(ts, *opts, first_sample, d_rays_out, (hipStream_t)stream);
+}
+int take_hip_camera_rays(TakeScene *ts, const TakeRenderOpts *opts, int32_t first_sample, void *rays_out_host) {
+    if (!ts || !opts || !rays_out_host) return fail(TAKE_E_INVALID, "null argument");
+    if (opts->spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    if (int rc = check_first_sample(first_sample, opts->spp)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    TAKE_ON_DEVICE(ts);
+    const size_t bytes = (size_t)opts->spp * (size_t)ts->width() * (size_t)ts->height() * 8 * (ts->f64() ? 8 : 4);
+    if (bytes == 0) return TAKE_OK;
+    DevBuf<char> d_rays;
+    if (d_rays.alloc(bytes) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the camera rays");
+    if (int rc = camera_rays_scene(ts, *opts, first_sample, d_rays.p, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(rays_out_host, d_rays.p, bytes, hipMemcpyDeviceToHost));
+    return TAKE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ a resident scene changes

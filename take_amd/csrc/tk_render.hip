@@ -1,8 +1,9 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace's allocations, the kernel launchers,
 // the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
 // after them) and the calls that differ in between — the wavefront render loop, its adaptive twin (passes over the
-// pixels still active), the feature pass, the motion pass, the trace hooks.
-// The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h, tk_adaptive.h and tk_shutter.h (as tk_build.hip is for tk_build_gpu.h);
+// pixels still active), the feature pass, the motion pass, the trace hooks, the render of caller-supplied rays and the
+// export of the camera's.
+// The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h, tk_adaptive.h, tk_shutter.h and tk_rays.h (as tk_build.hip is for tk_build_gpu.h);
 // what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "tk_motion.h"
 #include "tk_adaptive.h"
 #include "tk_shutter.h"
+#include "tk_rays.h"
 
 using namespace tk;
 using namespace tk_host;
@@ -172,6 +174,8 @@ template <class R> struct Frame {
     bool sort_materials = false;
     int64_t dump = -1;  // TAKE_HIP_DUMP_SLOT (or -1)
     bool listed_pass = false;  // an adaptive pass over listed pixels: k_generate_list made the camera rays (launch_closest)
+    bool caller_rays = false;  // take_hip_render_rays*: k_generate_rays made the first rays from the caller's, never the camera (launch_closest)
+    int width = 0, height = 0;  // of what the call covers: the camera's image (pick_strips), or n texels in one row (pick_texels)
     int first = 0, stride = 1, n_rows = 0;  // the strips first, first + stride, ... of the image and their rows (pick_strips)
     int64_t npix = 0;                       // the pixels of those rows
     int spb = 0;                            // samples per batch
@@ -205,7 +209,7 @@ hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const R
     hipError_t e;
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
     tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
-    if (k == 0 && !c.listed_pass && camera_fused(sc.trace, rp.integrator, c.counting, sc.dev.cam.lens_radius > RR(0))) {
+    if (k == 0 && !c.listed_pass && !c.caller_rays && camera_fused(sc.trace, rp.integrator, c.counting, sc.dev.cam.lens_radius > RR(0))) {
         // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
         CameraIo<RR> io_cam;
         static_cast<PathIo<RR> &>(io_cam) = io_ext;
@@ -421,9 +425,17 @@ template <class R> int pick_strips(Frame<R> &fr, const TakeRenderOpts &o) {
     fr.stride = o.strip_stride > 0 ? o.strip_stride : 1;
     fr.first = o.strip_first;
     if (fr.first < 0 || fr.first >= fr.stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    fr.n_rows = rows_of(fr.sc.host.cam.height, fr.first, fr.stride, nullptr);
-    fr.npix = (int64_t)fr.n_rows * fr.sc.host.cam.width;
+    fr.width = fr.sc.host.cam.width, fr.height = fr.sc.host.cam.height;
+    fr.n_rows = rows_of(fr.height, fr.first, fr.stride, nullptr);
+    fr.npix = (int64_t)fr.n_rows * fr.width;
     return TAKE_OK;
+}
+// the same for a call over n texels that are no pixels of the camera (take_hip_render_rays*): one row of width n, so
+// that slot_pixel / path_rng key texel i as pixel i
+template <class R> void pick_texels(Frame<R> &fr, int64_t n) {
+    fr.first = 0, fr.stride = 1;
+    fr.width = (int)n, fr.height = 1, fr.n_rows = 1;
+    fr.npix = n;
 }
 // The frame of a call over the pixels of those strips (a render; render = false: a feature pass), up to the call's own
 // set-up: fresh counters, the batch size with the workspace for it, the kernels' parameters, the grids.  A strip set
@@ -437,7 +449,7 @@ template <class R> int begin_frame(Frame<R> &fr, const TakeRenderOpts &o, bool r
     if (npix >= ((int64_t)1 << 30)) return fail(TAKE_E_INVALID, "image too large");
     if (const int rc = size_batches(ts, fr.work, o, npix, fr.spb, fr.slots, render)) return rc;
     fr.st = PathState<R>{fr.work.records.p, fr.work.capacity};
-    fr.rp = make_params<R>(o, fr.sc.host.cam.width, fr.sc.host.cam.height, fr.n_rows, fr.first, fr.stride);
+    fr.rp = make_params<R>(o, fr.width, fr.height, fr.n_rows, fr.first, fr.stride);
     fr.wide_grid = (int)std::min<int64_t>((fr.slots + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
     fr.pix_grid = (int)std::min<int64_t>((npix + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
     return TAKE_OK;
@@ -482,11 +494,9 @@ template <class R> int64_t start_batch(Frame<R> &fr, int s0, int nb) {
     return n;
 }
 
-// What a render refuses of its options before it looks at the strips
+// What a render refuses of its options before it looks at the strips (check_render_values: the part that needs no scene)
 template <class R> int check_render_opts(const SceneT<R> &sc, const TakeRenderOpts &o) {
-    if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
-    if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
-    if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
+    if (const int rc = check_render_values(o)) return rc;
     if (o.integrator != 0 && sc.host.env.light >= 0)
         return fail(TAKE_E_INVALID, "integrators 1..3 are the reference's own: they do not know the environment-map extension");
     return TAKE_OK;
@@ -724,6 +734,76 @@ int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
     return end_frame(fr, (uint64_t)npix * (uint64_t)o.spp);
 }
 
+// Path tracing of caller-supplied rays (take_hip_render_rays*; contract: include/take_hip.h, kernels: tk_rays.h).  A
+// render whose frame covers n texels in one row instead of the camera's pixels — so that the unchanged path_rng keys
+// sample s of ray i as rng_key(seed, i, first_sample + s) — and whose batches start from k_generate_rays instead of the
+// camera; the rounds, accumulate and resolve are the render's own (one row: k_resolve does not flip).  b.rays: device
+// memory, checked by the caller (tk_api.hip) as far as it can be.
+template <class R> int rays_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, const TakeRayBatch &b, void *d_out, hipStream_t stream) {
+    ts->acc_samples = 0;  // (the accumulator is overwritten: a progressive sequence ends)
+    if (const int rc = check_render_opts(sc, o)) return rc;
+    Frame<R> fr{ts, sc, work, stream};
+    fr.caller_rays = true;
+    pick_texels(fr, b.n);
+    int rc = begin_frame(fr, o, true);
+    const int64_t n = fr.npix;
+    if (rc || n == 0) return rc;
+    RenderLoop loop;
+    if ((rc = prepare_loop(fr, o, loop))) return rc;
+    HIP_TRY(hipMemsetAsync(work.accum.p, 0, sizeof(R) * 3 * n, stream));
+    if ((rc = start_frame(fr))) return rc;
+    HIP_TRY(ts->poll.create());
+    QueuePoll poll{ts->poll, stream};
+
+    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
+        const int nb = std::min(fr.spb, o.spp - s0);
+        const int64_t n_paths = (int64_t)nb * n;
+        fr.rp.s0 = b.first_sample + s0, fr.rp.spb = nb;
+        fr.tm.begin(TK_OTHER);
+        hipLaunchKernelGGL((k_generate_rays<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, (const RayRec<R> *)b.rays, n, 1.0 / (double)n,
+                           b.ray_sets == 1 ? (int64_t)-1 : (int64_t)s0, (int)(b.flags & TAKE_RAYS_NORMALIZE), fr.st, work.queue[0].p, n_paths);
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, work.qwords.p, (int)Q_N_EXT0, (int32_t)n_paths);
+        fr.tm.end();
+        if ((rc = run_rounds(fr, loop, o.max_depth, n_paths, poll))) return rc;
+        fr.tm.begin(TK_OTHER);
+        if constexpr (sizeof(R) == 8)
+            if (loop.mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, (int32_t)n, nb);
+        if (!loop.mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)n, nb);
+        fr.tm.end();
+    }
+    fr.tm.begin(TK_OTHER);
+    hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows, o.spp);
+    fr.tm.end();
+    return end_frame(fr, (uint64_t)n * (uint64_t)o.spp);
+}
+
+// The scene's own camera rays (take_hip_camera_rays*): per batch the generate pass of a whole-image render — the pinhole
+// camera's or the lens's, as start_batch picks it where the camera is not fused into the trace launch — then
+// k_export_rays over the batch's records.  Path records and queues only, as the feature pass: a progressive sequence
+// goes on afterwards.  d_out: opts.spp sets of W * H records, sample-major.
+template <class R> int camera_rays_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &opts, int32_t first_sample, void *d_out, hipStream_t stream) {
+    if (opts.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    Frame<R> fr{ts, sc, work, stream};
+    TakeRenderOpts o{};  // (of the options only seed, spp and ray_epsilon are read: the whole image)
+    o.spp = opts.spp, o.seed = opts.seed, o.ray_epsilon = opts.ray_epsilon, o.strip_first = 0, o.strip_stride = 1;
+    if (const int rc = pick_strips(fr, o)) return rc;
+    int rc = begin_frame(fr, o, false);
+    const int64_t npix = fr.npix;
+    if (rc || npix == 0) return rc;
+    if ((rc = start_frame(fr))) return rc;
+    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
+        const int nb = std::min(fr.spb, o.spp - s0);
+        const int64_t n = (int64_t)nb * npix;
+        fr.rp.s0 = first_sample + s0, fr.rp.spb = nb;
+        fr.tm.begin(TK_OTHER);
+        if (sc.dev.cam.lens_radius > R(0)) hipLaunchKernelGGL((k_generate_lens<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, work.queue[0].p, n);
+        else hipLaunchKernelGGL((k_generate<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, work.queue[0].p, n);
+        hipLaunchKernelGGL((k_export_rays<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, fr.st, (RayRec<R> *)d_out + (int64_t)s0 * npix, n, fr.rp.ray_eps);
+        fr.tm.end();
+    }
+    return end_frame(fr, (uint64_t)npix * (uint64_t)o.spp);
+}
+
 // The motion pass of a scene (take_hip_render_motion*; contract: include/take_hip.h): one closest-hit launch over the
 // whole image that makes the centre rays itself (CentreCameraIo: the work list is the identity, no queue is read),
 // then k_motion over its records.  Path records and queue words only, as the feature pass: a progressive sequence goes
@@ -951,6 +1031,18 @@ int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotion
         }
         return motion_impl(ts, sc, work, o, d_out, *cam, marked ? ts->mark.xforms.p : nullptr, geom, stream);
     });
+}
+int check_render_values(const TakeRenderOpts &o) {
+    if (o.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
+    if (o.max_depth < -1) return fail(TAKE_E_INVALID, "max_depth must be >= -1");
+    if (o.integrator < 0 || o.integrator > 3) return fail(TAKE_E_INVALID, "unknown integrator");
+    return TAKE_OK;
+}
+int render_rays_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeRayBatch &d_batch, void *d_out, hipStream_t stream) {
+    return on_primary(ts, [&](auto &sc, auto &work) { return rays_impl(ts, sc, work, o, d_batch, d_out, stream); });
+}
+int camera_rays_scene(TakeScene *ts, const TakeRenderOpts &o, int32_t first_sample, void *d_rays_out, hipStream_t stream) {
+    return on_primary(ts, [&](auto &sc, auto &work) { return camera_rays_impl(ts, sc, work, o, first_sample, d_rays_out, stream); });
 }
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any) {
     return on_primary(ts, [&](auto &sc, auto &work) { return trace_host(ts, sc, work, rays, n, hits, occ, any); });

@@ -327,6 +327,13 @@ int adaptive_min_spp(const TakeRenderOpts &o, const TakeAdaptiveOpts *a);
 // the motion pass (include/take_hip.h: take_hip_render_motion_device) into device memory, against the marked frame;
 // marked = false (take_hip_render_temporal_device's first frame, which wants depth and ids only): against the current one
 int render_motion_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeMotionBuffers &d_out, bool marked, hipStream_t stream);
+// what a render refuses of its options without looking at a scene: spp, max_depth, the integrator's range
+int check_render_values(const TakeRenderOpts &o);
+// path tracing of caller-supplied rays (include/take_hip.h: take_hip_render_rays_device) into device memory; d_batch:
+// checked by the caller, its rays in device memory
+int render_rays_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeRayBatch &d_batch, void *d_out, hipStream_t stream);
+// the scene's camera rays (include/take_hip.h: take_hip_camera_rays_device) into device memory; first_sample: checked by the caller
+int camera_rays_scene(TakeScene *ts, const TakeRenderOpts &o, int32_t first_sample, void *d_rays_out, hipStream_t stream);
 int trace_rays_host(TakeScene *ts, const void *rays, int64_t n, void *hits, int32_t *occ, bool any);
 int trace_rays_device(TakeScene *ts, const void *d_rays, int64_t n, void *d_hits, bool count, hipStream_t stream);
 // the distance along the view axis of what the centre ray of pixel (column, row; both inside the image) hits, 0 for a miss
