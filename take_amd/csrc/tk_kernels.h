@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tk_integrate.h"
+#include "tk_record_io.h"
 #include "tk_trace_quad.h"
 
 namespace tk {
@@ -90,6 +91,9 @@ __global__ void __launch_bounds__(BLOCK) k_iota(int32_t *queue, int64_t n) {
 // (single-tag scenes) the one instance of the scene's tag walks the whole queue.
 // ALT: the reference's other integrators (shade_path_alt, tk_integrate.h; rp.integrator 1..3) — separate instances, so
 // that the default integrator's register allocation is untouched.
+// COOP: the wave moves the records of its 64 paths as whole lines (tk_record_io.h) instead of every lane its own record
+// with 16-byte accesses at a record's stride; the same registers either way, so shade_path sees no difference and the
+// results are bit-identical.  COOP = false is the row-per-lane form (TAKE_HIP_SHADE_COOP=0, A/B runs and tests).
 #ifndef TK_SHADE_RECORD
 #define TK_SHADE_RECORD 1  // the shade kernels work on a register copy of the path record (0: in memory)
 #endif
@@ -104,20 +108,22 @@ template <class R> struct RecordView {
     __device__ __forceinline__ int32_t &I_(int c, int64_t) const { return *reinterpret_cast<int32_t *>(&w[c]); }
 };
 #ifndef TK_SHADE_WAVES_F32
-#define TK_SHADE_WAVES_F32 5  // register cap of the shade kernels in waves per SIMD (0: none).  The f32 Diffuse instance sits at 96 VGPRs = the last count that gives five waves; 97 is four, and the fifth wave is worth 4 % of its time: the cap keeps an innocent edit from costing it
+#define TK_SHADE_WAVES_F32 5  // register cap of the shade kernels in waves per SIMD (0: none).  The f32 Diffuse instance sits at 96 VGPRs = the last count that gives five waves; 97 is four, and the fifth wave is worth 4 % of its time: the cap keeps an innocent edit from costing it (the row-per-lane form; the cooperative one sits at 88)
 #endif
 #ifndef TK_SHADE_WAVES_F64
 #define TK_SHADE_WAVES_F64 0
 #endif
 // (the f32 cap applies to the Diffuse instance of the default integrator — the one the headline workload runs — and to
 // the Disney stubs that clone it: 97 VGPRs without it, 96 and no scratch with it; the other tags would pay with scratch)
-template <class R, int TAG, bool ALT> constexpr int shade_waves() {
+// (the cooperative f64 miss instance: 98 VGPRs without a cap, 96 and no scratch with it — the five waves the
+// row-per-lane form has at 93)
+template <class R, int TAG, bool ALT, bool COOP> constexpr int shade_waves() {
     const bool lambert = TAG == 0 || TAG == 7 || TAG == 8 || TAG == 10 || TAG == 11;  // Diffuse and the Disney stubs that clone it
-    const int w = sizeof(R) == 4 ? ((lambert && !ALT) ? TK_SHADE_WAVES_F32 : 0) : TK_SHADE_WAVES_F64;
+    const int w = sizeof(R) == 4 ? ((lambert && !ALT) ? TK_SHADE_WAVES_F32 : 0) : ((COOP && TAG == TAG_MISS) ? 5 : TK_SHADE_WAVES_F64);
     return w > 0 ? w : 1;
 }
-template <class R, int TAG, bool ALT = false>
-__global__ void __launch_bounds__(BLOCK, (shade_waves<R, TAG, ALT>()))
+template <class R, int TAG, bool ALT = false, bool COOP = true>
+__global__ void __launch_bounds__(BLOCK, (shade_waves<R, TAG, ALT, COOP>()))
 k_shade(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, const int32_t *__restrict__ queue,
         const int32_t *__restrict__ n_ptr, const int32_t *__restrict__ tag_count, int32_t *next_queue,
         int32_t *n_next, int32_t *shadow_queue, int32_t *n_shadow, int k, unsigned long long *counters, float *to_f32) {
@@ -133,6 +139,46 @@ k_shade(DeviceScene<R> sc, RenderParams<R> rp, PathState<R> st, const int32_t *_
     if (blockIdx.x * BLOCK >= n) return;  // whole block beyond the queue (uniform)
     uint32_t req = 0;
     int32_t slot = 0;
+#if TK_SHADE_RECORD
+    if constexpr (COOP) {
+        // Lanes past the end of the queue own no record (and read no queue entry: those are stale) but still move
+        // their neighbours' pieces, so the moves sit outside the `i < n` test; `owned` keeps every access inside the
+        // records of the wave's own paths.
+        __shared__ rec_piece s_stage[BLOCK / WAVE][REC_STAGE_BYTES / 16];
+        rec_piece *stage = wave_stage(&s_stage[0][0]);
+        const bool own = i < n;
+        if (own) slot = queue[begin + i];
+        const uint64_t owned = __ballot(own);
+        RecordView<R> rv;
+        // (the f64 miss instance is so light that the load itself is its register peak: with one fill in flight and
+        // the cap of shade_waves it keeps its five waves — 96 registers, 114 with two fills in flight)
+        record_load_coop<PATH_REC * sizeof(R), !(sizeof(R) == 8 && TAG == TAG_MISS)>((const char *)st.r, slot, owned, stage, rv.q);
+        if (own)
+            req = ALT ? shade_path_alt<R, TAG, RecordView<R>>(sc, rp, rv, (int64_t)slot, k)
+                      : shade_path<R, TAG, RecordView<R>>(sc, rp, rv, (int64_t)slot, k);
+        if constexpr (sizeof(R) == 8) {
+            if (to_f32 != nullptr) {  // the handover round (see the row-per-lane form below); uniform
+                RecordView<float> fv;
+                const bool go = own && (req & REQ_EXTEND) != 0;
+                if (go) {
+#pragma unroll
+                    for (int c = 0; c < PATH_REC / 4; c++) fv.q[c] = make_uint4(0, 0, 0, 0);
+                    constexpr int WORDS[] = {S_OX, S_OY, S_OZ, S_DX, S_DY, S_DZ, S_PDF, S_TX, S_TY, S_TZ, S_LX, S_LY, S_LZ, S_FX, S_FY, S_FZ};
+#pragma unroll
+                    for (int w = 0; w < 16; w++) fv.w[WORDS[w]] = (float)rv.w[WORDS[w]];
+                    fv.I_(S_CTR, 0) = rv.I_(S_CTR, 0);
+                    fv.I_(S_FLAGS, 0) = rv.I_(S_FLAGS, 0);
+                    fv.I_(S_OCC, 0) = -1;
+                    rv.w[S_LX] = 0.0, rv.w[S_LY] = 0.0, rv.w[S_LZ] = 0.0;
+                    rv.I_(S_CONV, 0) = 1;
+                }
+                // only the f32 records of the paths that go on are written: the others' stay as they are
+                record_store_coop<PATH_REC * sizeof(float)>((char *)to_f32, slot, __ballot(go), stage, fv.q);
+            }
+        }
+        record_store_coop<PATH_REC * sizeof(R)>((char *)st.r, slot, owned, stage, rv.q);
+    } else
+#endif
     if (i < n) {
         slot = queue[begin + i];
 #if TK_SHADE_RECORD

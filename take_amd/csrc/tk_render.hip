@@ -116,14 +116,15 @@ template <class R> struct ShadeArgs {
     int grid;
     hipStream_t stream;
     float *to_f32;  // mixed precision, last exact round: the f32 records the continuing paths are converted into (else null)
+    bool coop;      // the wave moves its paths' records as whole lines (tk_record_io.h); false: every lane its own record
 };
+template <class R, int TAG, bool ALT, bool COOP> void launch_shade_instance(const ShadeArgs<R> &a) {
+    hipLaunchKernelGGL((k_shade<R, TAG, ALT, COOP>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur, a.tag_count,
+                       a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
+}
 template <class R, int TAG> void launch_shade_tag(const ShadeArgs<R> &a) {
-    if (a.rp.integrator != 0)
-        hipLaunchKernelGGL((k_shade<R, TAG, true>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
-                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
-    else
-        hipLaunchKernelGGL((k_shade<R, TAG, false>), dim3(a.grid), dim3(BLOCK), 0, a.stream, a.dev, a.rp, a.st, a.queue, a.n_cur,
-                           a.tag_count, a.next_queue, a.n_next, a.shadow_queue, a.n_shadow, a.k, a.counters, a.to_f32);
+    if (a.rp.integrator != 0) a.coop ? launch_shade_instance<R, TAG, true, true>(a) : launch_shade_instance<R, TAG, true, false>(a);
+    else a.coop ? launch_shade_instance<R, TAG, false, true>(a) : launch_shade_instance<R, TAG, false, false>(a);
 }
 template <class R> void launch_shade(int tag, const ShadeArgs<R> &a) {
     switch (tag) {
@@ -173,6 +174,7 @@ template <class R> struct Frame {
     bool counting = (ts->instrumentation & 2) != 0;
     bool sort_materials = false;
     int64_t dump = -1;  // TAKE_HIP_DUMP_SLOT (or -1)
+    bool shade_coop = true;  // the shade kernels' record moves (k_shade, COOP); TAKE_HIP_SHADE_COOP=0 turns it off (A/B runs)
     bool listed_pass = false;  // an adaptive pass over listed pixels: k_generate_list made the camera rays (launch_closest)
     bool caller_rays = false;  // take_hip_render_rays*: k_generate_rays made the first rays from the caller's, never the camera (launch_closest)
     int width = 0, height = 0;  // of what the call covers: the camera's image (pick_strips), or n texels in one row (pick_texels)
@@ -260,7 +262,7 @@ hipError_t launch_round(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const Ren
     {
         const int shade_grid = (int)((n_bound + BLOCK - 1) / BLOCK);
         ShadeArgs<RR> sa{sc.dev, rp, st, shade_in, n_cur, c.sort_materials ? tag_count : nullptr, w.queue[next].p,
-                         n_next, w.shadow_queue.p, q + Q_N_SHADOW, k, w.counters.p, shade_grid, c.stream, to_f32};
+                         n_next, w.shadow_queue.p, q + Q_N_SHADOW, k, w.counters.p, shade_grid, c.stream, to_f32, c.shade_coop};
         if (c.sort_materials) {
             // one specialised launch per material tag present in the scene + the miss segment
             for (int t = 0; t < TAKE_MAT_COUNT; t++)
@@ -514,6 +516,7 @@ struct RenderLoop {
 template <class R> int prepare_loop(Frame<R> &fr, const TakeRenderOpts &o, RenderLoop &loop) {
     fr.sort_materials = fr.sc.host.n_material_tags > 1;
     if (const char *dump_env = std::getenv("TAKE_HIP_DUMP_SLOT")) fr.dump = std::atoll(dump_env);
+    if (const char *coop_env = std::getenv("TAKE_HIP_SHADE_COOP")) fr.shade_coop = std::atoi(coop_env) != 0;  // read per call: a test flips it
     if (fr.sort_materials) {
         const size_t need = (size_t)N_SORT_KEYS * fr.wide_grid * (BLOCK / WAVE);
         if (fr.work.sort_hist.n != need) {
