@@ -415,6 +415,38 @@ int take_hip_scene_set_mesh_vertices(TakeScene *scene, const TakeMeshUpdate *upd
  * two leaves, a depth (new top level + deepest prototype + return marker) beyond the traversal stack, node counts
  * beyond the 32-bit record offsets. */
 int take_hip_scene_update_meshes(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
+/* A new environment map (EXTENSION; new symbols of ABI version 5; no struct changed; specification: DESIGN.md §4o).
+ * The call replaces the image images[k] of the description the scene was created from, k being the shape_id of its
+ * environment-map light (TakeLight kind 2), and — with scale3 — that light's intensity; scale3 == NULL keeps it.
+ * Afterwards the scene is, byte for byte, the scene take_hip_scene_create makes from that description with the image
+ * (and the intensity) replaced, on every resident side:
+ *  - the image's texels in the texel array — a material that uses image k as a texture sees the new image too;
+ *  - the image table: later images keep their order and get shifted offsets.  With unchanged dimensions the texels are
+ *    overwritten in place and nothing moves; otherwise the texel array is laid out again as [images before | new image |
+ *    images after] by device-to-device copies;
+ *  - the EnvMap record, the marginal and the conditional CDFs, both guide tables with their sizes (creation's rule,
+ *    TAKE_HIP_ENV_GUIDE included) and the light record's intensity.
+ * Renders, take_hip_debug_env outputs and trace results are those of the fresh scene, bit for bit.  A float image is
+ * taken as its values widened to double: the fresh scene in question holds those doubles.  The tables are made on the
+ * device (take_amd/csrc/tk_envmap.h), once in double, and rounded per side; each side's guide tables are searched on
+ * that side's own rounded CDF.  The contract of "a resident scene changes" above holds: a failed call leaves the scene
+ * exactly as it was (everything is built aside and swapped in at the end), a successful one ends a progressive sequence;
+ * F32, F64 and MIXED scenes, a mixed scene on both sides or on neither; not for scene groups.
+ * TAKE_E_INVALID, before a device is looked for: a NULL scene, image or data ("null argument"), width or height <= 0,
+ * an unknown `real`, unknown flag bits, a scale that is not finite.  After a device was found: a scene without an
+ * environment-map light ("no environment map": adding a light is out of scope), a map whose total weight is not > 0
+ * ("environment map: no positive luminance", creation's own message; found on the device).  TAKE_E_NOMEM leaves the
+ * scene untouched. */
+typedef struct TakeEnvImage {
+    int32_t width, height;
+    const void *data;      /* height * width * 3, row 0 = zenith, as TakeImage3 */
+    int32_t real;          /* TAKE_PRECISION_F32: float texels, TAKE_PRECISION_F64: double texels */
+    int32_t flags;         /* 0, or TAKE_MESH_DEVICE_ARRAYS: data is device memory */
+} TakeEnvImage;
+int take_hip_scene_set_envmap(TakeScene *scene, const TakeEnvImage *image, const double *scale3 /* NULL = keep */);
+/* the same after waiting for `stream` (hipStream_t, NULL = default stream), whose work may still be writing the texels
+ * (e.g. a torch tensor): builds on the default stream, returns after it has completed */
+int take_hip_scene_set_envmap_device(TakeScene *scene, const TakeEnvImage *image, const double *scale3, void *stream);
 
 /* ---- thin-lens camera (EXTENSION; new symbols of ABI version 5; no struct changed): depth of field.  A scene is
  * created with a pinhole camera; take_hip_scene_set_lens gives it a circular aperture of radius aperture_radius (world
@@ -1141,6 +1173,28 @@ typedef struct TakeDebugTreeInfo {
 } TakeDebugTreeInfo;
 int take_hip_debug_tree_info(const TakeScene *scene, int32_t side, TakeDebugTreeInfo *info);
 int take_hip_debug_tree(const TakeScene *scene, int32_t side, void *nodes, void *prims, void *inst_trace);
+
+/* Test hook (new symbols of ABI version 5; no struct changed): the environment map of one resident side of a scene as
+ * the shade kernels read it — the EnvMap record (take_amd/csrc/tk_scene.h), its tables, its texels and the scene's
+ * whole image table, copied from device memory — after creation and after every take_hip_scene_set_envmap.
+ * take_hip_debug_env_tables_info says what there is; take_hip_debug_env_tables copies height + 1 Reals of marginal,
+ * height * (width + 1) of conditional, n_guide_m + 1 int32 of guide_m, height * (n_guide_c + 1) of guide_c,
+ * 3 * width * height Reals of texels and n_images records of {int32 width, height; int64 offset} into host buffers the
+ * caller sized from the info.
+ * TAKE_E_INVALID: NULL arguments ("null argument", before a device is looked for), a side the scene does not have, a
+ * scene without an environment map ("no environment map"). */
+typedef struct TakeDebugEnvTablesInfo {
+    int32_t width, height;
+    int32_t n_guide_m, n_guide_c;
+    int32_t real_bytes;  /* 4 or 8: the side's Real */
+    int32_t n_images;
+    int64_t texel0;      /* first texel of the map in the side's texel array */
+    double scale[3];     /* EnvMap::scale and the light record's intensity, widened */
+    double intensity[3];
+} TakeDebugEnvTablesInfo;
+int take_hip_debug_env_tables_info(const TakeScene *scene, int32_t side, TakeDebugEnvTablesInfo *info);
+int take_hip_debug_env_tables(const TakeScene *scene, int32_t side, void *marginal, void *conditional, int32_t *guide_m, int32_t *guide_c, void *texels,
+                              void *images);
 
 /* ---- PLY -> device mesh arrays ------------------------------------------------------------
  * Replaces src/parse/parse_ply.cpp:9-123 (`TriangleMesh parse_ply(filename, to_world)`) for binary_little_endian

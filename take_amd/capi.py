@@ -43,6 +43,7 @@ EXPORTS = [
     "take_hip_image_workspace_create", "take_hip_image_workspace_destroy", "take_hip_bloom_layer", "take_hip_bloom_layer_device",
     "take_hip_tonemap_bloom", "take_hip_tonemap_bloom_device",
     "take_hip_render_rays", "take_hip_render_rays_device", "take_hip_camera_rays", "take_hip_camera_rays_device",
+    "take_hip_scene_set_envmap", "take_hip_scene_set_envmap_device", "take_hip_debug_env_tables_info", "take_hip_debug_env_tables",
 ]
 
 
@@ -90,7 +91,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -917,6 +918,33 @@ class Scene:
             return
         _check(lib().take_hip_scene_set_instance_transforms_device(self.h, C.c_void_p(ptr), n, C.c_void_p(stream or 0)))
 
+    def set_envmap(self, image, scale=None, stream=None):
+        """a new environment map for the resident scene (take_hip_scene_set_envmap): `image` is (h, w, 3), row 0 = zenith —
+        a numpy float32 or float64 array (anything else numpy converts is taken as float64) read from host memory, or a
+        contiguous float32 / float64 torch tensor on the device, read through its device pointer after `stream` (default:
+        torch's current stream).  scale: the light's new (r, g, b) intensity, None = keep.  The tables are built on the
+        device; afterwards the scene equals one newly created from its description with this image and scale."""
+        sc = None if scale is None else D.c_double3(*map(float, scale))
+        if hasattr(image, "data_ptr") and getattr(image, "is_cuda", False):
+            reals = {"torch.float32": D.TAKE_PRECISION_F32, "torch.float64": D.TAKE_PRECISION_F64}
+            if str(image.dtype) not in reals or not image.is_contiguous() or image.dim() != 3 or image.shape[2] != 3:
+                raise ValueError("an environment map on the device must be a contiguous float32 or float64 tensor of shape (h, w, 3)")
+            if stream is None:
+                import torch
+
+                stream = torch.cuda.current_stream(image.device).cuda_stream
+            im = D.TakeEnvImage(int(image.shape[1]), int(image.shape[0]), image.data_ptr(), reals[str(image.dtype)], D.TAKE_MESH_DEVICE_ARRAYS)
+            _check(lib().take_hip_scene_set_envmap_device(self.h, C.byref(im), sc, C.c_void_p(stream or 0)))
+            return
+        if hasattr(image, "data_ptr"):  # a torch tensor in host memory
+            image = image.numpy()
+        a = np.asarray(image)
+        a = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("an environment map must have shape (h, w, 3)")
+        im = D.TakeEnvImage(a.shape[1], a.shape[0], a.ctypes.data, D.TAKE_PRECISION_F32 if a.dtype == np.float32 else D.TAKE_PRECISION_F64, 0)
+        _check(lib().take_hip_scene_set_envmap(self.h, C.byref(im), sc))
+
     def set_camera(self, lookfrom, lookat, up, vfov, width=None, height=None):
         """a new camera for the resident scene (take_hip_scene_set_camera); width and height stay the scene's"""
         cam = D.TakeCamera(self.sd.width if width is None else int(width), self.sd.height if height is None else int(height),
@@ -1101,6 +1129,25 @@ class Scene:
         inp = np.ascontiguousarray(inp, np.float64).reshape(-1, 3 if kind else 2)
         out = np.zeros((inp.shape[0], 5 if kind else 8), np.float64)
         _check(lib().take_hip_debug_env(self.h, int(side), int(kind), inp.ctypes.data, inp.shape[0], out.ctypes.data))
+        return out
+
+    def debug_env_tables(self, side=None):
+        """the environment map of one resident side, read back from device memory as the shade kernels read it
+        (take_hip_debug_env_tables, a test hook) -> {"width", "height", "n_guide_m", "n_guide_c", "texel0", "scale",
+        "intensity", "marginal" (h + 1,), "conditional" (h, w + 1), "guide_m" (n_guide_m + 1,), "guide_c" (h, n_guide_c + 1),
+        "texels" (h, w, 3), "images" (n_images,) of cdefs.IMAGE_INFO_DTYPE}.  side: as debug_env's"""
+        if side is None:
+            side = D.TAKE_PRECISION_F32 if self.precision == D.TAKE_PRECISION_F32 else D.TAKE_PRECISION_F64
+        info = D.TakeDebugEnvTablesInfo()
+        _check(lib().take_hip_debug_env_tables_info(self.h, int(side), C.byref(info)))
+        w, h, real = info.width, info.height, np.float32 if info.real_bytes == 4 else np.float64
+        out = {"marginal": np.zeros(h + 1, real), "conditional": np.zeros((h, w + 1), real), "guide_m": np.zeros(info.n_guide_m + 1, np.int32),
+               "guide_c": np.zeros((h, info.n_guide_c + 1), np.int32), "texels": np.zeros((h, w, 3), real),
+               "images": np.zeros(max(info.n_images, 1), D.IMAGE_INFO_DTYPE)}
+        _check(lib().take_hip_debug_env_tables(self.h, int(side), *(out[k].ctypes.data for k in ("marginal", "conditional", "guide_m", "guide_c", "texels", "images"))))
+        out["images"] = out["images"][:info.n_images]
+        out.update(width=w, height=h, n_guide_m=info.n_guide_m, n_guide_c=info.n_guide_c, texel0=info.texel0, scale=np.array(info.scale[:]),
+                   intensity=np.array(info.intensity[:]))
         return out
 
     def debug_tree(self, side=None):

@@ -426,6 +426,28 @@ DEBUG_TREE_PROTOTYPES = {
 NODE_FORMAT_WIDE, NODE_FORMAT_Q4, NODE_FORMAT_Q8 = 0, 1, 2
 
 
+# a new environment map for a resident scene, and the test hook that reads a side's map back (include/take_hip.h)
+class TakeEnvImage(C.Structure):
+    """take_hip_scene_set_envmap*: height * width * 3 texels, row 0 = zenith; real: TAKE_PRECISION_F32 float texels,
+    TAKE_PRECISION_F64 double texels; flags: 0, or TAKE_MESH_DEVICE_ARRAYS = data is device memory"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("data", C.c_void_p), ("real", C.c_int32), ("flags", C.c_int32)]
+
+
+class TakeDebugEnvTablesInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_guide_m", C.c_int32), ("n_guide_c", C.c_int32),
+                ("real_bytes", C.c_int32), ("n_images", C.c_int32), ("texel0", C.c_int64), ("scale", c_double3), ("intensity", c_double3)]
+
+
+IMAGE_INFO_DTYPE = [("width", "<i4"), ("height", "<i4"), ("offset", "<i8")]  # ImageInfo, take_amd/csrc/tk_scene.h
+# name -> argument types
+ENVMAP_PROTOTYPES = {
+    "take_hip_scene_set_envmap": [C.c_void_p, C.POINTER(TakeEnvImage), C.POINTER(C.c_double)],
+    "take_hip_scene_set_envmap_device": [C.c_void_p, C.POINTER(TakeEnvImage), C.POINTER(C.c_double), C.c_void_p],
+    "take_hip_debug_env_tables_info": [C.c_void_p, C.c_int32, C.POINTER(TakeDebugEnvTablesInfo)],
+    "take_hip_debug_env_tables": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
 def debug_tree_dtypes(info):
     """numpy dtypes of the arrays take_hip_debug_tree fills, from its info (the layouts of take_amd/csrc/tk_scene.h:
     NodeW<Real, 4> / QNodeW<W>, PrimRec<Real>, InstTrace<Real>) -> (node, prim, inst)"""

@@ -18,6 +18,7 @@
 
 #include "take_hip.h"
 #include "tk_bvh.h"
+#include "tk_envmap.h"
 #include "tk_scene.h"
 
 namespace tk {
@@ -760,42 +761,34 @@ inline bool env_tables(const double *rgb, int w, int h, std::vector<double> &mar
         double run = 0;
         for (int x = 0; x < w; x++) {
             const double *t = rgb + 3 * ((size_t)y * w + x);
-            const double lum = 0.2126 * t[0] + 0.7152 * t[1] + 0.0722 * t[2];
             c[x] = run;
-            run += (lum > 0 ? lum : 0.0) * wy;
+            run += em::texel_weight(t[0], t[1], t[2], wy);
         }
         row_sum[y] = run;
-        for (int x = 0; x < w; x++) c[x] = run > 0 ? c[x] / run : (double)x / w;
-        c[w] = 1.0;
+        for (int x = 0; x <= w; x++) c[x] = em::cond_entry(c[x], run, x, w);
     }
-    double total = 0;
-    for (int y = 0; y < h; y++) {
-        marg[y] = total;
-        total += row_sum[y];
-    }
-    if (!(total > 0)) return false;
-    for (int y = 0; y < h; y++) marg[y] /= total;
-    marg[h] = 1.0;
-    return true;
+    return em::marginal_cdf(row_sum.data(), h, marg.data());
 }
 
 // guide table over an R-typed CDF of n intervals (what the device searches): out[k] = interval of k / g, k = 0..g
+// (the bisection: tk_envmap.h, which runs it per lane for take_hip_scene_set_envmap)
 template <class R> inline void guide_table(const R *cdf, int n, int g, int32_t *out) {
-    for (int k = 0; k <= g; k++) {
-        const R xi = R(k) / R(g);
-        int lo = 0, hi = n;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (cdf[mid] <= xi) lo = mid;
-            else hi = mid;
-        }
-        out[k] = lo;
-    }
+    for (int k = 0; k <= g; k++) out[k] = em::guide_entry(cdf, n, g, k);
 }
 inline int pow2_at_least(int v, int cap) {
     int p = 1;
     while (p < v && p < cap) p <<= 1;
     return p;
+}
+// entries of the guide tables of a width x height map: one per ~quarter row / per column — the bisection that remains
+// is 0-1 steps (round 3: with 256 / 64 entries it was 2-3 and ~5 dependent loads; shade kernel -4 % on the bench
+// workload, same samples); TAKE_HIP_ENV_GUIDE="<m>,<c>", powers of two, overrides them
+inline void env_guide_sizes(int width, int height, int &gm, int &gc) {
+    gm = pow2_at_least(4 * height, ENV_GUIDE_M_MAX), gc = pow2_at_least(width, ENV_GUIDE_C_MAX);
+    if (const char *e = std::getenv("TAKE_HIP_ENV_GUIDE")) {
+        int a = 0, b = 0;
+        if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0 && !(a & (a - 1)) && !(b & (b - 1)) && a <= (1 << 16) && b <= (1 << 16)) gm = a, gc = b;
+    }
 }
 
 // Light i is an environment map (extension: shape_id = image index, intensity = scale): hs.env and its tables
@@ -811,13 +804,8 @@ template <class R> std::string env_light(const TakeSceneDesc &d, int i, HostScen
     for (int a = 0; a < 3; a++) hs.env.scale[a] = R(l.intensity[a]);
     hs.env_marginal.assign(marg.begin(), marg.end());
     hs.env_conditional.assign(cond.begin(), cond.end());
-    // one guide entry per ~quarter row / per column: the bisection that remains is 0-1 steps (round 3: with
-    // 256 / 64 entries it was 2-3 and ~5 dependent loads; shade kernel -4 % on the bench workload, same samples)
-    int gm = pow2_at_least(4 * im.height, ENV_GUIDE_M_MAX), gc = pow2_at_least(im.width, ENV_GUIDE_C_MAX);
-    if (const char *e = std::getenv("TAKE_HIP_ENV_GUIDE")) {  // "<m>,<c>", powers of two
-        int a = 0, b = 0;
-        if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b > 0 && !(a & (a - 1)) && !(b & (b - 1)) && a <= (1 << 16) && b <= (1 << 16)) gm = a, gc = b;
-    }
+    int gm, gc;
+    env_guide_sizes(im.width, im.height, gm, gc);
     hs.env.n_guide_m = gm, hs.env.n_guide_c = gc;
     hs.env_guide_m.resize(gm + 1);
     guide_table(hs.env_marginal.data(), im.height, gm, hs.env_guide_m.data());

@@ -122,10 +122,50 @@ def parse_shutter(params):
         raise SystemExit(f"-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az: {e}")
 
 
+def parse_envmap(params):
+    """`-envmap FILE [-envscale R,G,B]` taken out of `params` -> ((h, w, 3) image, scale or None), or None without -envmap;
+    FILE is an .exr (take_amd/exr.read_exr) or a .npy holding a float32 or float64 (h, w, 3) array"""
+    def take(flag):
+        if flag not in params:
+            return None
+        i = params.index(flag)
+        if i + 1 >= len(params):
+            raise SystemExit(f"{flag} needs a value")
+        value = params[i + 1]
+        del params[i:i + 2]
+        return value
+
+    path, scale = take("-envmap"), take("-envscale")
+    if path is None:
+        if scale is not None:
+            raise SystemExit("-envscale needs -envmap")
+        return None
+    try:
+        rgb = None if scale is None else tuple(float(v) for v in scale.split(","))
+        if rgb is not None and len(rgb) != 3:
+            raise ValueError("three numbers for -envscale")
+        if path.endswith(".npy"):
+            img = np.load(path)
+        elif path.endswith(".exr"):
+            from .exr import read_exr
+
+            channels, _ = read_exr(path)
+            if not all(c in channels for c in "RGB"):
+                raise ValueError(f"{path}: the file has no R, G and B channels")
+            img = np.stack([channels[c].astype(np.float32) for c in "RGB"], -1)
+        else:
+            raise ValueError(f"unsupported image format: {path}")
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"{path}: the image must have shape (h, w, 3)")
+        return img, rgb
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"-envmap FILE [-envscale R,G,B]: {e}")
+
+
 def main(argv=None):
     """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
     [-png [linear|reinhard|aces] [-bloom [INTENSITY]]] [-aperture R [-focus D | -focus_pixel X,Y]]
-    [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az]` — the reference's main.cpp:9-27:
+    [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az] [-envmap FILE [-envscale R,G,B]]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
@@ -148,7 +188,10 @@ def main(argv=None):
     camera motion blur (Scene.render_shutter) — the scene file's camera is the current frame, the six numbers of
     -from_camera are lookfrom and lookat of the marked one (up and vfov stay), the exposure lasts from OPEN to CLOSE of
     the interval between them, in K slices (default: the library's); every other file is the same bytes with or without
-    it.  Moving placements need the API."""
+    it.  Moving placements need the API.  -envmap (an extension): the scene's environment map is replaced by FILE (.exr or
+    .npy, (h, w, 3), row 0 = zenith) right after the scene is created (Scene.set_envmap: its tables are built on the device),
+    and the light's intensity by -envscale if given; the scene must have an environment-map light; every file is then
+    of the scene under the new map."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -186,6 +229,7 @@ def main(argv=None):
             raise SystemExit("-bloom needs -png")
     lens = parse_lens(params)
     shutter = parse_shutter(params)
+    envmap = parse_envmap(params)
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
@@ -204,6 +248,8 @@ def main(argv=None):
     sd = load_tkscene(filename)
     scene = Scene(sd)
     try:
+        if envmap is not None:  # before everything else: all the files below are of the scene under the new map
+            scene.set_envmap(envmap[0], scale=envmap[1])
         if shutter is not None:  # the marked frame: the other camera, marked; then the scene file's camera again
             scene.set_camera(shutter[3], shutter[4], sd.up, sd.vfov)
             scene.mark_frame()
