@@ -109,6 +109,13 @@ int check_adaptive_opts(const TakeAdaptiveOpts *a) {
     if (a->flags != 0) return fail(TAKE_E_INVALID, "unknown flag bits");
     return TAKE_OK;
 }
+int strip_set(const TakeScene *ts, int first, int stride, StripSet &s, int32_t *rows_out) {
+    if (stride <= 0 || first < 0 || first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
+    s.first = first, s.stride = stride;
+    s.rows = rows_of(ts->height(), first, stride, rows_out);
+    s.npix = (int64_t)s.rows * ts->width();
+    return TAKE_OK;
+}
 }  // namespace tk_host
 
 extern "C" {
@@ -119,9 +126,9 @@ int take_hip_device_count(void) { return check_device(); }
 
 int take_hip_render_rows(const TakeScene *ts, int32_t strip_first, int32_t strip_stride, int32_t *rows_out) {
     if (!ts) return fail(TAKE_E_INVALID, "null scene");
-    if (strip_stride <= 0 || strip_first < 0 || strip_first >= strip_stride)
-        return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    return rows_of(ts->height(), strip_first, strip_stride, rows_out);
+    StripSet s;
+    if (int rc = strip_set(ts, strip_first, strip_stride, s, rows_out)) return rc;
+    return s.rows;
 }
 
 int take_hip_render_device(TakeScene *ts, const TakeRenderOpts *opts, void *d_rgb_out, void *stream) {
@@ -166,17 +173,13 @@ int64_t take_hip_accumulated_samples(const TakeScene *ts) { return ts ? ts->acc_
 int take_hip_render(TakeScene *ts, const TakeRenderOpts *opts, void *rgb_out_host) {
     if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    const int W = ts->width();
-    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
-    if (opts->strip_first < 0 || opts->strip_first >= stride)
-        return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
-    if (rows < 0) return rows;
-    const size_t bytes = (size_t)rows * W * 3 * (ts->f64() ? 8 : 4);
+    StripSet s;
+    if (int rc = strip_set(ts, *opts, s)) return rc;
+    const size_t bytes = (size_t)s.npix * 3 * (ts->f64() ? 8 : 4);
     if (bytes == 0) return TAKE_OK;
     // render into the scene's own output buffer, then copy out
     const void *img = nullptr;
-    const int rc = render_scene_to_out(ts, *opts, (int64_t)rows * W, img);
+    const int rc = render_scene_to_out(ts, *opts, s.npix, img);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(rgb_out_host, img, bytes, hipMemcpyDeviceToHost));
     return TAKE_OK;
@@ -208,11 +211,9 @@ int take_hip_render_features_device(TakeScene *ts, const TakeRenderOpts *opts, c
 int take_hip_render_features(TakeScene *ts, const TakeRenderOpts *opts, const TakeFeatureBuffers *host_out) {
     if (!ts || !opts || !host_out) return fail(TAKE_E_INVALID, "null argument");
     TAKE_ON_DEVICE(ts);
-    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
-    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
-    if (rows < 0) return rows;
-    const size_t npix = (size_t)rows * ts->width(), real = ts->f64() ? 8 : 4;
+    StripSet s;
+    if (int rc = strip_set(ts, *opts, s)) return rc;
+    const size_t npix = (size_t)s.npix, real = ts->f64() ? 8 : 4;
     // the wanted planes in device memory, then copied out
     StagedPlanes<6> st{{plane_out(host_out->albedo, 3 * real), plane_out(host_out->normal, 3 * real), plane_out(host_out->depth, real),
                         plane_out(host_out->alpha, real), plane_out(host_out->shape_id, 4), plane_out(host_out->material_id, 4)}};
@@ -236,11 +237,9 @@ int take_hip_render_adaptive(TakeScene *ts, const TakeRenderOpts *opts, const Ta
     if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
     if (int rc = check_adaptive_opts(adaptive)) return rc;
     TAKE_ON_DEVICE(ts);
-    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
-    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
-    if (rows < 0) return rows;
-    const size_t npix = (size_t)rows * ts->width();
+    StripSet s;
+    if (int rc = strip_set(ts, *opts, s)) return rc;
+    const size_t npix = (size_t)s.npix;
     // the image and the wanted planes in device memory, then copied out
     StagedPlanes<4> st{{plane_out(rgb_out_host, (size_t)3 * (ts->f64() ? 8 : 4)), plane_out(host_stats ? host_stats->count : nullptr, 4),
                         plane_out(host_stats ? host_stats->m1 : nullptr, 8), plane_out(host_stats ? host_stats->m2 : nullptr, 8)}};
@@ -271,7 +270,7 @@ int take_hip_trace_closest_device(TakeScene *ts, const void *d_rays, int64_t n, 
 
 // ------------------------------------------------------------------------------------------------ caller-supplied rays
 // Path tracing of caller-supplied rays and the export of the scene's camera rays (include/take_hip.h):
-// tk_render.hip, rays_impl and camera_rays_impl.  What needs no device is looked at before one is looked for.
+// tk_render.hip, render_impl (FirstRays::CALLER) and camera_rays_impl.  What needs no device is looked at before one is looked for.
 int take_hip_render_rays_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeRayBatch *batch, void *d_rgb_out, void *stream) {
     if (int rc = check_ray_batch(ts, opts, batch, d_rgb_out)) return rc;
     if (!aligned16(batch->rays)) return fail(TAKE_E_INVALID, "the rays must be 16-byte aligned");
@@ -685,11 +684,9 @@ int take_hip_render_shutter(TakeScene *ts, const TakeRenderOpts *opts, const Tak
     const int nd = check_device();
     if (nd < 0) return nd;
     TAKE_ON_DEVICE(ts);
-    const int stride = opts->strip_stride > 0 ? opts->strip_stride : 1;
-    if (opts->strip_first < 0 || opts->strip_first >= stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    const int rows = take_hip_render_rows(ts, opts->strip_first, stride, nullptr);
-    if (rows < 0) return rows;
-    const size_t bytes = (size_t)rows * ts->width() * 3 * (ts->f64() ? 8 : 4);
+    StripSet s;
+    if (int rc = strip_set(ts, *opts, s)) return rc;
+    const size_t bytes = (size_t)s.npix * 3 * (ts->f64() ? 8 : 4);
     if (bytes == 0) return TAKE_OK;
     DevBuf<char> img;
     if (img.alloc(bytes) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the image");

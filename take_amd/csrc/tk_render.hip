@@ -1,8 +1,10 @@
 // tk_render.hip — the host side of tracing and rendering: the render workspace's allocations, the kernel launchers,
 // the frame (Frame: what the launches of one call share; begin_frame / start / finish: what every call does before and
-// after them) and the calls that differ in between — the wavefront render loop, its adaptive twin (passes over the
-// pixels still active), the feature pass, the motion pass, the trace hooks, the render of caller-supplied rays and the
-// export of the camera's.
+// after them), the batch step every path-traced call runs (run_batch: start_batch — the one place that decides who makes
+// a batch's first rays, from the call's FirstRays — then run_rounds and accumulate_batch) and the calls that differ
+// around it — the render of the camera's pixels or of caller-supplied rays (render_impl), the adaptive passes over the
+// pixels still active, the feature pass and the export of the camera's rays (start_batch only), the motion pass, the
+// trace hooks.
 // The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h, tk_adaptive.h, tk_shutter.h and tk_rays.h (as tk_build.hip is for tk_build_gpu.h);
 // what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
@@ -126,27 +128,11 @@ template <class R, int TAG> void launch_shade_tag(const ShadeArgs<R> &a) {
     if (a.rp.integrator != 0) a.coop ? launch_shade_instance<R, TAG, true, true>(a) : launch_shade_instance<R, TAG, true, false>(a);
     else a.coop ? launch_shade_instance<R, TAG, false, true>(a) : launch_shade_instance<R, TAG, false, false>(a);
 }
-template <class R> void launch_shade(int tag, const ShadeArgs<R> &a) {
-    switch (tag) {
-        case 0: launch_shade_tag<R, 0>(a); break;
-        case 1: launch_shade_tag<R, 1>(a); break;
-        case 2: launch_shade_tag<R, 2>(a); break;
-        case 3: launch_shade_tag<R, 3>(a); break;
-        case 4: launch_shade_tag<R, 4>(a); break;
-        case 5: launch_shade_tag<R, 5>(a); break;
-        case 6: launch_shade_tag<R, 6>(a); break;
-        case 7: launch_shade_tag<R, 7>(a); break;
-        case 8: launch_shade_tag<R, 8>(a); break;
-        case 9: launch_shade_tag<R, 9>(a); break;
-        case 10: launch_shade_tag<R, 10>(a); break;
-        case 11: launch_shade_tag<R, 11>(a); break;
-        case 12: launch_shade_tag<R, 12>(a); break;
-        case 13: launch_shade_tag<R, 13>(a); break;
-        case 14: launch_shade_tag<R, 14>(a); break;
-        case 15: launch_shade_tag<R, 15>(a); break;
-        case 16: launch_shade_tag<R, 16>(a); break;
-        default: launch_shade_tag<R, TAG_MISS>(a); break;
-    }
+// the instance of a material tag 0 .. TAKE_MAT_COUNT - 1; any other tag: the miss segment's (TAG_MISS)
+template <class R, int TAG = 0> void launch_shade(int tag, const ShadeArgs<R> &a) {
+    if constexpr (TAG == TAKE_MAT_COUNT) launch_shade_tag<R, TAG_MISS>(a);
+    else if (tag == TAG) launch_shade_tag<R, TAG>(a);
+    else launch_shade<R, TAG + 1>(tag, a);
 }
 
 // Debug aid (TAKE_HIP_DUMP_SLOT=<slot>): print one path's state after every kernel of a round.
@@ -175,8 +161,7 @@ template <class R> struct Frame {
     bool sort_materials = false;
     int64_t dump = -1;  // TAKE_HIP_DUMP_SLOT (or -1)
     bool shade_coop = true;  // the shade kernels' record moves (k_shade, COOP); TAKE_HIP_SHADE_COOP=0 turns it off (A/B runs)
-    bool listed_pass = false;  // an adaptive pass over listed pixels: k_generate_list made the camera rays (launch_closest)
-    bool caller_rays = false;  // take_hip_render_rays*: k_generate_rays made the first rays from the caller's, never the camera (launch_closest)
+    bool camera_in_trace = false;  // of the batch under way: round 0's trace launch makes the camera rays itself (start_batch decides, launch_closest obeys)
     int width = 0, height = 0;  // of what the call covers: the camera's image (pick_strips), or n texels in one row (pick_texels)
     int first = 0, stride = 1, n_rows = 0;  // the strips first, first + stride, ... of the image and their rows (pick_strips)
     int64_t npix = 0;                       // the pixels of those rows
@@ -197,8 +182,8 @@ bool camera_fused(TraceKind kind, int integrator, bool counting, bool lens) {
     return enabled && TQ_GROUP == 1 && !counting && integrator == 0 && kind.nodes == NodeFormat::Q4 && !lens;
 }
 
-// The closest hits of round k of a batch for the extend queue (k = 0: the camera rays, made by the launch that traces
-// them where camera_fused says so).  tail: an f32 round of a mixed-precision render.
+// The closest hits of round k of a batch for the extend queue (k = 0: the batch's first rays — made by the launch that
+// traces them where start_batch left it so, Frame::camera_in_trace).  tail: an f32 round of a mixed-precision render.
 template <class RR, class R>
 hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const RenderParams<RR> &rp, int k, int64_t n_bound, bool tail) {
     Timer &tm = c.tm;
@@ -211,7 +196,7 @@ hipError_t launch_closest(Frame<R> &c, SceneT<RR> &sc, PathState<RR> st, const R
     hipError_t e;
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(64), 0, c.stream, q, next);
     tm.begin(tail ? TK_CLOSEST_TAIL : TK_CLOSEST);
-    if (k == 0 && !c.listed_pass && !c.caller_rays && camera_fused(sc.trace, rp.integrator, c.counting, sc.dev.cam.lens_radius > RR(0))) {
+    if (k == 0 && c.camera_in_trace) {
         // (the camera rays are made by the launch that traces them: CameraIo, tk_kernels.h)
         CameraIo<RR> io_cam;
         static_cast<PathIo<RR> &>(io_cam) = io_ext;
@@ -424,12 +409,10 @@ void sum_timings(const TakeScene *ts, TakeCounters &tc) {
 
 // the strips the options name -> fr's first, stride, rows and pixels
 template <class R> int pick_strips(Frame<R> &fr, const TakeRenderOpts &o) {
-    fr.stride = o.strip_stride > 0 ? o.strip_stride : 1;
-    fr.first = o.strip_first;
-    if (fr.first < 0 || fr.first >= fr.stride) return fail(TAKE_E_INVALID, "strip_first must be in [0, strip_stride)");
-    fr.width = fr.sc.host.cam.width, fr.height = fr.sc.host.cam.height;
-    fr.n_rows = rows_of(fr.height, fr.first, fr.stride, nullptr);
-    fr.npix = (int64_t)fr.n_rows * fr.width;
+    StripSet s;
+    if (const int rc = strip_set(fr.ts, o, s)) return rc;
+    fr.first = s.first, fr.stride = s.stride, fr.n_rows = s.rows, fr.npix = s.npix;
+    fr.width = fr.ts->width(), fr.height = fr.ts->height();
     return TAKE_OK;
 }
 // the same for a call over n texels that are no pixels of the camera (take_hip_render_rays*): one row of width n, so
@@ -482,16 +465,49 @@ template <class R> int end_frame(Frame<R> &fr, uint64_t samples) {
     return TAKE_OK;
 }
 
-// The extend queue of a new batch, samples s0 .. s0 + nb - 1 of every pixel (-> its n paths): the identity where the
-// closest-hit launch of round 0 makes the camera rays itself (camera_fused), else with the paths' initial records (k_generate).
-template <class R> int64_t start_batch(Frame<R> &fr, int s0, int nb) {
-    const int64_t n = (int64_t)nb * fr.npix;
-    fr.rp.s0 = s0, fr.rp.spb = nb;
+// Where the first rays of a call's batches come from, and how its samples are numbered: sample s of the call is sample
+// first_sample + s of the random streams.
+struct FirstRays {
+    enum Kind {
+        CAMERA,         // the camera's, of every pixel
+        CAMERA_LISTED,  // the camera's, of the n_listed pixels in `list` (an adaptive pass after the first)
+        CAMERA_EXPORT,  // the camera's, of every pixel, as records to be read: never left to the trace launch (the export)
+        CALLER          // the caller's (take_hip_render_rays*): texel i of a one-row frame travels along ray i
+    } kind = CAMERA;
+    int32_t first_sample = 0;
+    const int32_t *list = nullptr;  // device memory
+    int32_t n_listed = 0;
+    const TakeRayBatch *batch = nullptr;  // its rays in device memory
+};
+// The extend queue of a new batch, samples s .. s + nb - 1 of the call (-> its n paths), and its length in Q_N_EXT0:
+// the identity where the closest-hit launch of round 0 makes the camera rays itself (camera_fused: the one place that
+// asks, and fr.camera_in_trace is the answer launch_closest follows), else with the paths' initial records from the
+// source's generator — the pinhole camera's or the lens's.  (The export runs no round: nothing reads the length.)
+template <class R> int64_t start_batch(Frame<R> &fr, const FirstRays &src, int s, int nb) {
+    const SceneT<R> &sc = fr.sc;
+    const bool lens = sc.dev.cam.lens_radius > R(0);
+    const int64_t n = (int64_t)nb * (src.kind == FirstRays::CAMERA_LISTED ? (int64_t)src.n_listed : fr.npix);
+    int32_t *queue = fr.work.queue[0].p;
+    const dim3 grid(fr.wide_grid), block(BLOCK);
+    fr.rp.s0 = src.first_sample + s, fr.rp.spb = nb;
+    fr.camera_in_trace = src.kind == FirstRays::CAMERA && camera_fused(sc.trace, fr.rp.integrator, fr.counting, lens);
     fr.tm.begin(TK_OTHER);
-    if (camera_fused(fr.sc.trace, fr.rp.integrator, fr.counting, fr.sc.dev.cam.lens_radius > R(0))) hipLaunchKernelGGL(k_iota, dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.work.queue[0].p, n);
-    else if (fr.sc.dev.cam.lens_radius > R(0)) hipLaunchKernelGGL((k_generate_lens<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.sc.dev, fr.rp, fr.st, fr.work.queue[0].p, n);
-    else hipLaunchKernelGGL((k_generate<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, fr.stream, fr.sc.dev, fr.rp, fr.st, fr.work.queue[0].p, n);
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, fr.stream, fr.work.qwords.p, (int)Q_N_EXT0, (int32_t)n);
+    if (fr.camera_in_trace) {
+        hipLaunchKernelGGL(k_iota, grid, block, 0, fr.stream, queue, n);
+    } else if (src.kind == FirstRays::CALLER) {
+        const TakeRayBatch &b = *src.batch;
+        hipLaunchKernelGGL((k_generate_rays<R>), grid, block, 0, fr.stream, (const RayRec<R> *)b.rays, fr.npix, 1.0 / (double)fr.npix,
+                           b.ray_sets == 1 ? (int64_t)-1 : (int64_t)s, (int)(b.flags & TAKE_RAYS_NORMALIZE), fr.st, queue, n);
+    } else if (src.kind == FirstRays::CAMERA_LISTED) {
+        const dim3 list_grid((unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, (int64_t)fr.ts->num_cus * 8));
+        const double inv_listed = 1.0 / (double)src.n_listed;
+        if (lens) hipLaunchKernelGGL((ad::k_generate_list_lens<R>), list_grid, block, 0, fr.stream, sc.dev, fr.rp, fr.st, src.list, src.n_listed, inv_listed, queue, n);
+        else hipLaunchKernelGGL((ad::k_generate_list<R>), list_grid, block, 0, fr.stream, sc.dev, fr.rp, fr.st, src.list, src.n_listed, inv_listed, queue, n);
+    } else {
+        if (lens) hipLaunchKernelGGL((k_generate_lens<R>), grid, block, 0, fr.stream, sc.dev, fr.rp, fr.st, queue, n);
+        else hipLaunchKernelGGL((k_generate<R>), grid, block, 0, fr.stream, sc.dev, fr.rp, fr.st, queue, n);
+    }
+    if (src.kind != FirstRays::CAMERA_EXPORT) hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, fr.stream, fr.work.qwords.p, (int)Q_N_EXT0, (int32_t)n);
     fr.tm.end();
     return n;
 }
@@ -555,17 +571,54 @@ template <class R> int run_rounds(Frame<R> &fr, RenderLoop &loop, int max_depth,
     return TAKE_OK;
 }
 
-// first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
+// The nb samples a batch has finished, from its path records (the f64 and f32 ones of a mixed-precision render) into
+// the accumulator.  stats (the adaptive sampler's): also the counts and moments, of the source's listed pixels only
+// (no list: of every pixel).
+template <class R> void accumulate_batch(Frame<R> &fr, const RenderLoop &loop, const FirstRays &src, int nb, AdaptiveState *stats) {
+    R *accum = fr.work.accum.p;
+    const int32_t npix = (int32_t)fr.npix, n_listed = src.list ? src.n_listed : npix;
+    const dim3 grid(stats ? (unsigned)std::min<int64_t>(((int64_t)n_listed + BLOCK - 1) / BLOCK, (int64_t)fr.ts->num_cus * 8) : (unsigned)fr.pix_grid), block(BLOCK);
+    fr.tm.begin(TK_OTHER);
+    // (loop.mixed is false for f32 records; the mixed kernels are compiled for f64 ones only)
+    if (stats) {
+        if constexpr (sizeof(R) == 8)
+            if (loop.mixed) hipLaunchKernelGGL(ad::k_accumulate_stats_mixed, grid, block, 0, fr.stream, fr.st, loop.st32, accum, stats->count.p, stats->m1.p, stats->m2.p, src.list, n_listed, npix, nb);
+        if (!loop.mixed) hipLaunchKernelGGL((ad::k_accumulate_stats<R>), grid, block, 0, fr.stream, fr.st, accum, stats->count.p, stats->m1.p, stats->m2.p, src.list, n_listed, npix, nb);
+    } else {
+        if constexpr (sizeof(R) == 8)
+            if (loop.mixed) hipLaunchKernelGGL(k_accumulate_mixed, grid, block, 0, fr.stream, fr.st, loop.st32, accum, npix, nb);
+        if (!loop.mixed) hipLaunchKernelGGL((k_accumulate<R>), grid, block, 0, fr.stream, fr.st, accum, npix, nb);
+    }
+    fr.tm.end();
+}
+// One batch of a path-traced call, samples s .. s + nb - 1 of it: the first rays, the rounds, the accumulate
+template <class R>
+int run_batch(Frame<R> &fr, RenderLoop &loop, const FirstRays &src, int s, int nb, int max_depth, QueuePoll &poll, AdaptiveState *stats = nullptr) {
+    const int64_t n = start_batch(fr, src, s, nb);
+    if (const int rc = run_rounds(fr, loop, max_depth, n, poll)) return rc;
+    accumulate_batch(fr, loop, src, nb, stats);
+    return TAKE_OK;
+}
+
+// A render of the camera's pixels (take_hip_render*, src.kind = CAMERA) or of the caller's rays (take_hip_render_rays*,
+// CALLER; contract: include/take_hip.h, kernels: tk_rays.h) — then a frame of n texels in one row instead of the strips'
+// pixels, so that the unchanged path_rng keys sample s of ray i as rng_key(seed, i, first_sample + s), and one row,
+// which k_resolve does not flip.
+// src.first_sample / keep_accum: progressive rendering — the samples of this call are numbered from first_sample (their
 // random streams are those of a one-shot render's samples first_sample .. first_sample + spp - 1), keep_accum adds them
-// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples —
-// written unless resolve is false (all but the last slice of take_hip_render_shutter*: the accumulator is the result).
-// (What is a render's own between the frame's steps: its checks, the batch loop, accumulate and resolve.)
-template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, void *d_out, hipStream_t stream,
-                                   int64_t first_sample, bool keep_accum, bool resolve) {
+// to what `accum` holds instead of starting from zero, and the image is the mean over first_sample + spp samples (the
+// camera's; the caller's rays only number their samples from first_sample: the mean is over spp) — written unless
+// resolve is false (all but the last slice of take_hip_render_shutter*: the accumulator is the result).
+// (What is a render's own between the frame's steps: its checks, the batch loop and resolve.)
+template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, const FirstRays &src, void *d_out,
+                                   hipStream_t stream, bool keep_accum, bool resolve) {
+    const bool camera = src.kind == FirstRays::CAMERA;
     if (!keep_accum) ts->acc_samples = 0;  // (a one-shot render overwrites the accumulator: a progressive sequence ends)
     if (const int rc = check_render_opts(sc, o)) return rc;
     Frame<R> fr{ts, sc, work, stream};
-    int rc = pick_strips(fr, o);
+    int rc = TAKE_OK;
+    if (camera) rc = pick_strips(fr, o);
+    else pick_texels(fr, src.batch->n);
     if (!rc) rc = begin_frame(fr, o, true);
     const int64_t npix = fr.npix;
     if (rc || npix == 0) return rc;
@@ -576,22 +629,14 @@ template <class R> int render_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace
     HIP_TRY(ts->poll.create());
     QueuePoll poll{ts->poll, stream};
 
-    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
-        const int nb = std::min(fr.spb, o.spp - s0);
-        const int64_t n = start_batch(fr, (int32_t)first_sample + s0, nb);
-        if ((rc = run_rounds(fr, loop, o.max_depth, n, poll))) return rc;
-        fr.tm.begin(TK_OTHER);
-        if constexpr (sizeof(R) == 8)
-            if (loop.mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, (int32_t)npix, nb);
-        if (!loop.mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)npix, nb);
-        fr.tm.end();
-    }
+    for (int s = 0; s < o.spp; s += fr.spb)
+        if ((rc = run_batch(fr, loop, src, s, std::min(fr.spb, o.spp - s), o.max_depth, poll))) return rc;
     fr.tm.begin(TK_OTHER);
     if (resolve) hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows,
-                                    (int32_t)first_sample + o.spp);
+                                    (camera ? src.first_sample : 0) + o.spp);
     fr.tm.end();
     if ((rc = end_frame(fr, (uint64_t)npix * (uint64_t)o.spp))) return rc;
-    if (std::getenv("TAKE_HIP_VERBOSE"))
+    if (camera && std::getenv("TAKE_HIP_VERBOSE"))
         std::fprintf(stderr, "[take_hip] node-step ray slots: waiting-at-leaf %llu idle %llu running %llu; shadow rays the slot's previous occluder stops again: %llu of %llu\n",
                      fr.raw[C_WAIT_SLOTS], fr.raw[C_IDLE_SLOTS], fr.raw[C_NODE_VISITS], fr.raw[C_OCC_CACHE_HITS], fr.raw[C_RAYS_SHADOW]);
     return TAKE_OK;
@@ -609,8 +654,8 @@ ad::Rule make_rule(const TakeRenderOpts &o, const TakeAdaptiveOpts *a) {
 }
 
 // Adaptive sampling (take_hip_render_adaptive*; contract: include/take_hip.h, kernels: tk_adaptive.h).  Pass 0 is a
-// render's batch loop over min_spp samples of every pixel; every later pass puts the next samples of the pixels still
-// active into the round-0 extend queue (k_generate_list) and runs the render's own rounds on it.  Path records stay
+// render's batches over min_spp samples of every pixel; every later pass is the same batches with the pixels still
+// active as the source of their first rays (FirstRays::CAMERA_LISTED: k_generate_list).  Path records stay
 // addressed by sample * npix + pixel, so the workspace is sized for max(min_spp, step_spp) samples of all pixels and
 // a pass that does not fit is split into batches — which is what keeps slot_pixel / path_rng, and with them every shade
 // instance, untouched.  After each pass: accumulate + moments, the test, the ordered compaction, and the length of the
@@ -647,37 +692,10 @@ int adaptive_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
     for (int pass = 0, n = 0; n_active > 0 && n < o.spp; pass++) {
         const int add = pass == 0 ? rule.min_spp : std::min(rule.step_spp, o.spp - n);
         const int list_grid = (int)std::min<int64_t>(((int64_t)n_active + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-        fr.listed_pass = pass > 0;
-        for (int done = 0; done < add; done += fr.spb) {
-            const int nb = std::min(fr.spb, add - done);
-            int64_t n_paths;
-            if (pass == 0) {
-                n_paths = start_batch(fr, n + done, nb);
-            } else {
-                n_paths = (int64_t)nb * n_active;
-                fr.rp.s0 = n + done, fr.rp.spb = nb;
-                fr.tm.begin(TK_OTHER);
-                const int gen_grid = (int)std::min<int64_t>((n_paths + BLOCK - 1) / BLOCK, (int64_t)ts->num_cus * 8);
-                if (sc.dev.cam.lens_radius > R(0))
-                    hipLaunchKernelGGL((ad::k_generate_list_lens<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
-                                       work.queue[0].p, n_paths);
-                else
-                    hipLaunchKernelGGL((ad::k_generate_list<R>), dim3(gen_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, list, n_active, 1.0 / (double)n_active,
-                                       work.queue[0].p, n_paths);
-                hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, work.qwords.p, (int)Q_N_EXT0, (int32_t)n_paths);
-                fr.tm.end();
-            }
-            if ((rc = run_rounds(fr, loop, o.max_depth, n_paths, poll))) return rc;
-            fr.tm.begin(TK_OTHER);
-            if constexpr (sizeof(R) == 8)
-                if (loop.mixed)
-                    hipLaunchKernelGGL(ad::k_accumulate_stats_mixed, dim3(list_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, a.count.p, a.m1.p, a.m2.p, list,
-                                       n_active, (int32_t)npix, nb);
-            if (!loop.mixed)
-                hipLaunchKernelGGL((ad::k_accumulate_stats<R>), dim3(list_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, a.count.p, a.m1.p, a.m2.p, list, n_active,
-                                   (int32_t)npix, nb);
-            fr.tm.end();
-        }
+        FirstRays src;
+        if (pass > 0) src.kind = FirstRays::CAMERA_LISTED, src.list = list, src.n_listed = n_active;
+        for (int done = 0; done < add; done += fr.spb)
+            if ((rc = run_batch(fr, loop, src, n + done, std::min(fr.spb, add - done), o.max_depth, poll, &a))) return rc;
         n += add;
         samples += (uint64_t)n_active * (uint64_t)add;
         if (n >= o.spp) break;  // (every pixel still active has spp samples: it stops)
@@ -725,7 +743,7 @@ int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
     if ((rc = start_frame(fr))) return rc;
     for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
         const int nb = std::min(fr.spb, o.spp - s0);
-        const int64_t n = start_batch(fr, s0, nb);
+        const int64_t n = start_batch(fr, FirstRays{}, s0, nb);
         HIP_TRY(launch_closest(fr, sc, fr.st, fr.rp, 0, n, false));
         fr.tm.begin(TK_SHADE);
         hipLaunchKernelGGL((k_features<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, sc.dev, fr.st, work.features.p, out, fr.rp.width, fr.n_rows, nb, s0 == 0 ? 1 : 0, want);
@@ -737,53 +755,10 @@ int features_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const 
     return end_frame(fr, (uint64_t)npix * (uint64_t)o.spp);
 }
 
-// Path tracing of caller-supplied rays (take_hip_render_rays*; contract: include/take_hip.h, kernels: tk_rays.h).  A
-// render whose frame covers n texels in one row instead of the camera's pixels — so that the unchanged path_rng keys
-// sample s of ray i as rng_key(seed, i, first_sample + s) — and whose batches start from k_generate_rays instead of the
-// camera; the rounds, accumulate and resolve are the render's own (one row: k_resolve does not flip).  b.rays: device
-// memory, checked by the caller (tk_api.hip) as far as it can be.
-template <class R> int rays_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &o, const TakeRayBatch &b, void *d_out, hipStream_t stream) {
-    ts->acc_samples = 0;  // (the accumulator is overwritten: a progressive sequence ends)
-    if (const int rc = check_render_opts(sc, o)) return rc;
-    Frame<R> fr{ts, sc, work, stream};
-    fr.caller_rays = true;
-    pick_texels(fr, b.n);
-    int rc = begin_frame(fr, o, true);
-    const int64_t n = fr.npix;
-    if (rc || n == 0) return rc;
-    RenderLoop loop;
-    if ((rc = prepare_loop(fr, o, loop))) return rc;
-    HIP_TRY(hipMemsetAsync(work.accum.p, 0, sizeof(R) * 3 * n, stream));
-    if ((rc = start_frame(fr))) return rc;
-    HIP_TRY(ts->poll.create());
-    QueuePoll poll{ts->poll, stream};
-
-    for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
-        const int nb = std::min(fr.spb, o.spp - s0);
-        const int64_t n_paths = (int64_t)nb * n;
-        fr.rp.s0 = b.first_sample + s0, fr.rp.spb = nb;
-        fr.tm.begin(TK_OTHER);
-        hipLaunchKernelGGL((k_generate_rays<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, (const RayRec<R> *)b.rays, n, 1.0 / (double)n,
-                           b.ray_sets == 1 ? (int64_t)-1 : (int64_t)s0, (int)(b.flags & TAKE_RAYS_NORMALIZE), fr.st, work.queue[0].p, n_paths);
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, stream, work.qwords.p, (int)Q_N_EXT0, (int32_t)n_paths);
-        fr.tm.end();
-        if ((rc = run_rounds(fr, loop, o.max_depth, n_paths, poll))) return rc;
-        fr.tm.begin(TK_OTHER);
-        if constexpr (sizeof(R) == 8)
-            if (loop.mixed) hipLaunchKernelGGL(k_accumulate_mixed, dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, loop.st32, work.accum.p, (int32_t)n, nb);
-        if (!loop.mixed) hipLaunchKernelGGL((k_accumulate<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, fr.st, work.accum.p, (int32_t)n, nb);
-        fr.tm.end();
-    }
-    fr.tm.begin(TK_OTHER);
-    hipLaunchKernelGGL((k_resolve<R>), dim3(fr.pix_grid), dim3(BLOCK), 0, stream, work.accum.p, (R *)d_out, fr.rp.width, fr.n_rows, o.spp);
-    fr.tm.end();
-    return end_frame(fr, (uint64_t)n * (uint64_t)o.spp);
-}
-
-// The scene's own camera rays (take_hip_camera_rays*): per batch the generate pass of a whole-image render — the pinhole
-// camera's or the lens's, as start_batch picks it where the camera is not fused into the trace launch — then
-// k_export_rays over the batch's records.  Path records and queues only, as the feature pass: a progressive sequence
-// goes on afterwards.  d_out: opts.spp sets of W * H records, sample-major.
+// The scene's own camera rays (take_hip_camera_rays*): per batch the first rays of a whole-image render as records
+// (FirstRays::CAMERA_EXPORT: the pinhole camera's or the lens's generate pass), then k_export_rays over them.  Path
+// records and queues only, as the feature pass: a progressive sequence goes on afterwards.  d_out: opts.spp sets of
+// W * H records, sample-major.
 template <class R> int camera_rays_impl(TakeScene *ts, SceneT<R> &sc, RenderWorkspace<R> &work, const TakeRenderOpts &opts, int32_t first_sample, void *d_out, hipStream_t stream) {
     if (opts.spp <= 0) return fail(TAKE_E_INVALID, "spp must be positive");
     Frame<R> fr{ts, sc, work, stream};
@@ -794,13 +769,11 @@ template <class R> int camera_rays_impl(TakeScene *ts, SceneT<R> &sc, RenderWork
     const int64_t npix = fr.npix;
     if (rc || npix == 0) return rc;
     if ((rc = start_frame(fr))) return rc;
+    FirstRays src;
+    src.kind = FirstRays::CAMERA_EXPORT, src.first_sample = first_sample;
     for (int s0 = 0; s0 < o.spp; s0 += fr.spb) {
-        const int nb = std::min(fr.spb, o.spp - s0);
-        const int64_t n = (int64_t)nb * npix;
-        fr.rp.s0 = first_sample + s0, fr.rp.spb = nb;
-        fr.tm.begin(TK_OTHER);
-        if (sc.dev.cam.lens_radius > R(0)) hipLaunchKernelGGL((k_generate_lens<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, work.queue[0].p, n);
-        else hipLaunchKernelGGL((k_generate<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, sc.dev, fr.rp, fr.st, work.queue[0].p, n);
+        const int64_t n = start_batch(fr, src, s0, std::min(fr.spb, o.spp - s0));
+        fr.tm.begin(TK_OTHER);  // (a second interval of the class beside start_batch's: with timing on, one more event pair per batch)
         hipLaunchKernelGGL((k_export_rays<R>), dim3(fr.wide_grid), dim3(BLOCK), 0, stream, fr.st, (RayRec<R> *)d_out + (int64_t)s0 * npix, n, fr.rp.ray_eps);
         fr.tm.end();
     }
@@ -994,12 +967,14 @@ int rows_of(int height, int first, int stride, int32_t *rows_out) {
 }
 
 int render_scene(TakeScene *ts, const TakeRenderOpts &o, void *d_out, hipStream_t stream, int64_t first_sample, bool keep_accum, bool resolve) {
-    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, d_out, stream, first_sample, keep_accum, resolve); });
+    FirstRays camera;
+    camera.first_sample = (int32_t)first_sample;
+    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, camera, d_out, stream, keep_accum, resolve); });
 }
 int render_scene_to_out(TakeScene *ts, const TakeRenderOpts &o, int64_t npix, const void *&img) {
     return on_primary(ts, [&](auto &sc, auto &work) {
         int rc = work.ensure(0, npix, false);
-        if (!rc) rc = render_impl(ts, sc, work, o, work.out.p, nullptr, 0, false, true);
+        if (!rc) rc = render_impl(ts, sc, work, o, FirstRays{}, work.out.p, nullptr, false, true);
         img = work.out.p;
         return rc;
     });
@@ -1042,7 +1017,9 @@ int check_render_values(const TakeRenderOpts &o) {
     return TAKE_OK;
 }
 int render_rays_scene(TakeScene *ts, const TakeRenderOpts &o, const TakeRayBatch &d_batch, void *d_out, hipStream_t stream) {
-    return on_primary(ts, [&](auto &sc, auto &work) { return rays_impl(ts, sc, work, o, d_batch, d_out, stream); });
+    FirstRays rays;
+    rays.kind = FirstRays::CALLER, rays.first_sample = d_batch.first_sample, rays.batch = &d_batch;
+    return on_primary(ts, [&](auto &sc, auto &work) { return render_impl(ts, sc, work, o, rays, d_out, stream, false, true); });
 }
 int camera_rays_scene(TakeScene *ts, const TakeRenderOpts &o, int32_t first_sample, void *d_rays_out, hipStream_t stream) {
     return on_primary(ts, [&](auto &sc, auto &work) { return camera_rays_impl(ts, sc, work, o, first_sample, d_rays_out, stream); });

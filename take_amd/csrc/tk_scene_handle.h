@@ -350,6 +350,15 @@ int shutter_pose_device(const double *d_marked, const double *d_current, const s
 // ---- defined in tk_api.hip
 // what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device
 int check_adaptive_opts(const TakeAdaptiveOpts *a);
+// The strips first, first + stride, ... of the scene's image a call covers, their rows and pixels: the one place that
+// refuses a strip set (stride <= 0, first outside [0, stride)).  rows_out: as rows_of's.  From render options: a stride
+// <= 0 means 1.
+struct StripSet {
+    int first = 0, stride = 1, rows = 0;
+    int64_t npix = 0;
+};
+int strip_set(const TakeScene *ts, int first, int stride, StripSet &s, int32_t *rows_out = nullptr);
+inline int strip_set(const TakeScene *ts, const TakeRenderOpts &o, StripSet &s) { return strip_set(ts, o.strip_first, o.strip_stride > 0 ? o.strip_stride : 1, s); }
 
 // ---- defined in tk_build.hip
 // The marked geometry of a side whose records are still the marked frame's (take_hip_scene_track_vertices; layout:
