@@ -447,6 +447,40 @@ int take_hip_scene_set_envmap(TakeScene *scene, const TakeEnvImage *image, const
 /* the same after waiting for `stream` (hipStream_t, NULL = default stream), whose work may still be writing the texels
  * (e.g. a torch tensor): builds on the default stream, returns after it has completed */
 int take_hip_scene_set_envmap_device(TakeScene *scene, const TakeEnvImage *image, const double *scale3, void *stream);
+/* New materials and new light intensities (EXTENSION; new symbols of ABI version 5; no struct changed; specification:
+ * DESIGN.md §4p).
+ * take_hip_scene_set_materials replaces materials [first, first + count) of the table the scene was created with.
+ * Afterwards every resident side holds, byte for byte, what take_hip_scene_create makes from the original description
+ * with those materials replaced, under the same TakeBuildOpts (burley_lobes remaps a new material as it remapped the
+ * old ones): the material table, the tag byte of every primitive record's meta, the tag of every placement record of a
+ * two-level scene, and the host's record of which tags are in use — whether a render sorts by material and which shade
+ * instances it launches; unused materials count, as at creation.  The table keeps its size, and which shape, mesh or
+ * placement uses which material does not change.  Each new material passes creation's checks with creation's messages,
+ * the material numbered by its place in the table.  The tag bytes are rewritten in place by a kernel (one lane per
+ * record) only when some material of the range changes its effective tag; a change of colours, textures and
+ * parameters writes the table alone.  Later updates (take_hip_scene_set_mesh_vertices, take_hip_scene_update_meshes,
+ * take_hip_scene_set_instance_transforms) build on the new tags.
+ * take_hip_scene_set_light_intensities replaces the intensity of lights [first, first + count) by rgb[3 k ..],
+ * k = 0 .. count - 1 (host memory); kinds and geometry do not change.  Afterwards every resident side holds creation's
+ * bytes for the light records, the power table and its running sum (a point light's power stays 0; a total power of 0
+ * leaves creation's NaN tables) and, when the range holds the environment-map light, for the map's scale, as
+ * take_hip_scene_set_envmap's scale3 sets it.  Only the 3 * count doubles are uploaded: the records are rewritten and
+ * the range's powers computed on the device, the serial sum over all lights runs on the host.
+ * The _device variant reads d_rgb from device memory after waiting for `stream` (hipStream_t, NULL = default stream),
+ * whose work may still be writing the values; it runs on the default stream and returns after it has completed.  It
+ * cannot look at the values before they are used: an intensity that is not finite is NOT refused there.
+ * The contract of "a resident scene changes" above holds: everything that can fail happens aside, for every side of a
+ * MIXED scene, before anything resident changes — a failed call leaves the scene exactly as it was; a successful one
+ * ends a progressive sequence.  The marked frame and vertex tracking are left alone (no geometry moved); whether a
+ * temporal history made under the old materials or lights is still worth keeping is the caller's decision.  F32, F64
+ * and MIXED scenes; flattened, two-level, q8 and host- or device-built scenes alike; not for scene groups.
+ * TAKE_E_INVALID before a device is looked for: a NULL scene or array ("null argument"), count <= 0, first < 0 or
+ * first + count beyond INT32_MAX, and — host variant — an intensity that is not finite.  After a device was found: a
+ * range that ends beyond the scene's table (the handle is not read earlier), an unknown tag, a bad texture image id
+ * against the scene's image count, a Burley parameter outside its range.  TAKE_E_NOMEM leaves the scene untouched. */
+int take_hip_scene_set_materials(TakeScene *scene, const TakeMaterial *materials, int32_t first, int32_t count);
+int take_hip_scene_set_light_intensities(TakeScene *scene, const double *rgb /* 3 * count, host */, int32_t first, int32_t count);
+int take_hip_scene_set_light_intensities_device(TakeScene *scene, const double *d_rgb, int32_t first, int32_t count, void *stream);
 
 /* ---- thin-lens camera (EXTENSION; new symbols of ABI version 5; no struct changed): depth of field.  A scene is
  * created with a pinhole camera; take_hip_scene_set_lens gives it a circular aperture of radius aperture_radius (world
@@ -1195,6 +1229,25 @@ typedef struct TakeDebugEnvTablesInfo {
 int take_hip_debug_env_tables_info(const TakeScene *scene, int32_t side, TakeDebugEnvTablesInfo *info);
 int take_hip_debug_env_tables(const TakeScene *scene, int32_t side, void *marginal, void *conditional, int32_t *guide_m, int32_t *guide_c, void *texels,
                               void *images);
+
+/* Test hook (new symbols of ABI version 5; no struct changed): the shading tables of one resident side of a scene as
+ * the kernels read them, copied from device memory — after creation and after every take_hip_scene_set_materials /
+ * _set_light_intensities: n_materials MaterialRec, n_lights LightRec, n_pmf Reals of light_pmf, n_cdf of light_cdf and
+ * n_instances InstShade (two-level scenes; take_amd/csrc/tk_scene.h has the layouts), into host buffers the caller
+ * sized from the info — every pointer non-NULL, also where the count is 0.  The info also says what the HOST holds of
+ * the material tags: tag_mask, n_material_tags, single_tag.  (Primitive records: take_hip_debug_tree.)
+ * TAKE_E_INVALID: NULL arguments ("null argument", before a device is looked for), a side the scene does not have. */
+typedef struct TakeDebugShadingTablesInfo {
+    int32_t n_materials, n_lights;
+    int64_t n_instances;
+    int32_t real_bytes;  /* 4 or 8: the side's Real */
+    int32_t material_bytes, light_bytes, inst_shade_bytes; /* element sizes */
+    int32_t n_pmf, n_cdf;
+    uint32_t tag_mask;
+    int32_t n_material_tags, single_tag, reserved;
+} TakeDebugShadingTablesInfo;
+int take_hip_debug_shading_tables_info(const TakeScene *scene, int32_t side, TakeDebugShadingTablesInfo *info);
+int take_hip_debug_shading_tables(const TakeScene *scene, int32_t side, void *materials, void *lights, void *light_pmf, void *light_cdf, void *inst_shade);
 
 /* ---- PLY -> device mesh arrays ------------------------------------------------------------
  * Replaces src/parse/parse_ply.cpp:9-123 (`TriangleMesh parse_ply(filename, to_world)`) for binary_little_endian

@@ -44,6 +44,8 @@ EXPORTS = [
     "take_hip_tonemap_bloom", "take_hip_tonemap_bloom_device",
     "take_hip_render_rays", "take_hip_render_rays_device", "take_hip_camera_rays", "take_hip_camera_rays_device",
     "take_hip_scene_set_envmap", "take_hip_scene_set_envmap_device", "take_hip_debug_env_tables_info", "take_hip_debug_env_tables",
+    "take_hip_scene_set_materials", "take_hip_scene_set_light_intensities", "take_hip_scene_set_light_intensities_device",
+    "take_hip_debug_shading_tables_info", "take_hip_debug_shading_tables",
 ]
 
 
@@ -91,7 +93,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -945,6 +947,38 @@ class Scene:
         im = D.TakeEnvImage(a.shape[1], a.shape[0], a.ctypes.data, D.TAKE_PRECISION_F32 if a.dtype == np.float32 else D.TAKE_PRECISION_F64, 0)
         _check(lib().take_hip_scene_set_envmap(self.h, C.byref(im), sc))
 
+    def set_materials(self, materials, first=0):
+        """new materials for the resident scene (take_hip_scene_set_materials): `materials` is a list of
+        take_amd.scene.Material that replaces the scene's materials first, first + 1, ...; the table keeps its size and
+        every shape, mesh and placement keeps its material id.  Afterwards the scene equals one newly created from its
+        description with these materials."""
+        materials = list(materials)
+        mats = (D.TakeMaterial * max(len(materials), 1))()
+        for c, m in zip(mats, materials):
+            D.fill_material(c, m)
+        _check(lib().take_hip_scene_set_materials(self.h, mats, int(first), len(materials)))
+
+    def set_light_intensities(self, rgb, first=0, stream=None):
+        """new (r, g, b) intensities for the lights first, first + 1, ... of the resident scene
+        (take_hip_scene_set_light_intensities): a (count, 3) numpy array (or anything numpy converts) read from host
+        memory, or a contiguous float64 torch tensor of that shape on the device, read through its device pointer after
+        `stream` (default: torch's current stream).  Kinds and geometry stay; the power tables are made again."""
+        if hasattr(rgb, "data_ptr") and getattr(rgb, "is_cuda", False):
+            if str(rgb.dtype) != "torch.float64" or not rgb.is_contiguous() or rgb.dim() != 2 or rgb.shape[1] != 3:
+                raise ValueError("intensities on the device must be a contiguous float64 tensor of shape (count, 3)")
+            if stream is None:
+                import torch
+
+                stream = torch.cuda.current_stream(rgb.device).cuda_stream
+            _check(lib().take_hip_scene_set_light_intensities_device(self.h, C.c_void_p(rgb.data_ptr()), int(first), int(rgb.shape[0]), C.c_void_p(stream or 0)))
+            return
+        if hasattr(rgb, "data_ptr"):  # a torch tensor in host memory
+            rgb = rgb.numpy()
+        a = np.ascontiguousarray(rgb, np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("intensities must have shape (count, 3)")
+        _check(lib().take_hip_scene_set_light_intensities(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), int(first), a.shape[0]))
+
     def set_camera(self, lookfrom, lookat, up, vfov, width=None, height=None):
         """a new camera for the resident scene (take_hip_scene_set_camera); width and height stay the scene's"""
         cam = D.TakeCamera(self.sd.width if width is None else int(width), self.sd.height if height is None else int(height),
@@ -1148,6 +1182,26 @@ class Scene:
         out["images"] = out["images"][:info.n_images]
         out.update(width=w, height=h, n_guide_m=info.n_guide_m, n_guide_c=info.n_guide_c, texel0=info.texel0, scale=np.array(info.scale[:]),
                    intensity=np.array(info.intensity[:]))
+        return out
+
+    def debug_shading_tables(self, side=None):
+        """the shading tables of one resident side, read back from device memory as the kernels read them
+        (take_hip_debug_shading_tables, a test hook) -> {"materials", "lights", "inst_shade": numpy structured arrays
+        (cdefs.shading_table_dtypes), "light_pmf", "light_cdf": arrays of the side's Real, "tag_mask", "n_material_tags",
+        "single_tag": what the host holds of the tags in use, "real_bytes"}.  side: as debug_env's"""
+        if side is None:
+            side = D.TAKE_PRECISION_F32 if self.precision == D.TAKE_PRECISION_F32 else D.TAKE_PRECISION_F64
+        info = D.TakeDebugShadingTablesInfo()
+        _check(lib().take_hip_debug_shading_tables_info(self.h, int(side), C.byref(info)))
+        material, light, inst = D.shading_table_dtypes(info.real_bytes)
+        assert (material.itemsize, light.itemsize, inst.itemsize) == (info.material_bytes, info.light_bytes, info.inst_shade_bytes), "layout of the shading hook changed"
+        real = np.float32 if info.real_bytes == 4 else np.float64
+        counts = {"materials": (info.n_materials, material), "lights": (info.n_lights, light), "light_pmf": (info.n_pmf, real), "light_cdf": (info.n_cdf, real),
+                  "inst_shade": (info.n_instances, inst)}
+        out = {k: np.zeros(max(n, 1), t) for k, (n, t) in counts.items()}
+        _check(lib().take_hip_debug_shading_tables(self.h, int(side), *(out[k].ctypes.data for k in ("materials", "lights", "light_pmf", "light_cdf", "inst_shade"))))
+        out = {k: out[k][:n] for k, (n, _) in counts.items()}
+        out.update(tag_mask=int(info.tag_mask), n_material_tags=int(info.n_material_tags), single_tag=int(info.single_tag), real_bytes=int(info.real_bytes))
         return out
 
     def debug_tree(self, side=None):

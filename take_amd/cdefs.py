@@ -448,6 +448,48 @@ ENVMAP_PROTOTYPES = {
 }
 
 
+# new materials and light intensities for a resident scene, and the test hook that reads a side's shading tables back
+# (include/take_hip.h)
+class TakeDebugShadingTablesInfo(C.Structure):
+    _fields_ = [("n_materials", C.c_int32), ("n_lights", C.c_int32), ("n_instances", C.c_int64), ("real_bytes", C.c_int32),
+                ("material_bytes", C.c_int32), ("light_bytes", C.c_int32), ("inst_shade_bytes", C.c_int32), ("n_pmf", C.c_int32), ("n_cdf", C.c_int32),
+                ("tag_mask", C.c_uint32), ("n_material_tags", C.c_int32), ("single_tag", C.c_int32), ("reserved", C.c_int32)]
+
+
+SHADING_UPDATE_PROTOTYPES = {
+    "take_hip_scene_set_materials": [C.c_void_p, C.POINTER(TakeMaterial), C.c_int32, C.c_int32],
+    "take_hip_scene_set_light_intensities": [C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_int32],
+    "take_hip_scene_set_light_intensities_device": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "take_hip_debug_shading_tables_info": [C.c_void_p, C.c_int32, C.POINTER(TakeDebugShadingTablesInfo)],
+    "take_hip_debug_shading_tables": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+def fill_material(c, m):
+    """the TakeMaterial `c` from a take_amd.scene.Material: what SceneData.to_desc and Scene.set_materials both use"""
+    c.tag = m.tag
+    c.reflectance.kind, c.reflectance.image_id = m.tex_kind, m.tex_image
+    c.reflectance.value = c_double3(*m.color)
+    c.reflectance.uscale, c.reflectance.vscale, c.reflectance.uoffset, c.reflectance.voffset = m.uvxf
+    c.param = (C.c_double * 12)(*(tuple(m.param) + (0.0,) * (12 - len(m.param))))
+
+
+def shading_table_dtypes(real_bytes):
+    """numpy dtypes of the arrays take_hip_debug_shading_tables fills (the layouts of take_amd/csrc/tk_scene.h:
+    MaterialRec<Real>, LightRec<Real>, InstShade<Real>) -> (material, light, inst_shade)"""
+    import numpy as np
+
+    real, rb = ("<f4", 4) if real_bytes == 4 else ("<f8", 8)
+    material = np.dtype({"names": ["tag", "tex_kind", "tex_image", "pad", "color", "uvxf", "p0", "p1", "p"],
+                         "formats": ["<i4"] * 4 + [(real, 3), (real, 4), real, real, (real, MATERIAL_PARAMS)],
+                         "offsets": [0, 4, 8, 12, 16, 16 + 3 * rb, 16 + 7 * rb, 16 + 8 * rb, 16 + 9 * rb], "itemsize": 16 + (9 + MATERIAL_PARAMS) * rb})
+    light = np.dtype({"names": ["kind", "shape_id", "is_sphere", "pad", "intensity", "v", "n"], "formats": ["<i4"] * 4 + [(real, 3), (real, 9), (real, 9)],
+                      "offsets": [0, 4, 8, 12, 16, 16 + 3 * rb, 16 + 12 * rb], "itemsize": 16 + 21 * rb})
+    inst = np.dtype({"names": ["fwd", "material", "tag", "shape_base", "pad"], "formats": [(real, 9)] + ["<i4"] * 4,
+                     "offsets": [0, 9 * rb, 9 * rb + 4, 9 * rb + 8, 9 * rb + 12], "itemsize": 64 if rb == 4 else 96})
+    return material, light, inst
+
+
 def debug_tree_dtypes(info):
     """numpy dtypes of the arrays take_hip_debug_tree fills, from its info (the layouts of take_amd/csrc/tk_scene.h:
     NodeW<Real, 4> / QNodeW<W>, PrimRec<Real>, InstTrace<Real>) -> (node, prim, inst)"""

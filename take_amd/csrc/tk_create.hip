@@ -275,7 +275,7 @@ int take_hip_scene_create(const TakeSceneDesc *desc, const TakeBuildOpts *opts, 
     // (a scene that fails is freed on return, with its device current: nothing here changes the current device)
     std::unique_ptr<TakeScene> ts(new (std::nothrow) TakeScene());
     if (!ts) return fail(TAKE_E_NOMEM, "out of host memory");
-    ts->precision = o.precision;
+    ts->precision = o.precision, ts->burley_lobes = o.burley_lobes != 0;
     ts->look_distance = look_distance(desc->camera), ts->camera = desc->camera;
     hipDeviceProp_t prop;
     if (hipGetDevice(&ts->device) != hipSuccess || hipGetDeviceProperties(&prop, ts->device) != hipSuccess)

@@ -20,6 +20,7 @@
 #include "tk_bvh.h"
 #include "tk_envmap.h"
 #include "tk_scene.h"
+#include "tk_shading_update.h"
 
 namespace tk {
 
@@ -660,31 +661,41 @@ inline bool burley_params_in_range(int tag, const double *param) {
 }
 
 // materials, and which material tags are in use
+// (material i of a scene with n_images images -> its record, or the error: creation's table and
+// take_hip_scene_set_materials check and convert a material with this one text)
+template <class R> std::string material_record(const TakeMaterial &m, int i, int n_images, bool burley_lobes, MaterialRec<R> &o) {
+    if (m.tag < 0 || m.tag >= TAKE_MAT_COUNT) return "material " + std::to_string(i) + ": unknown tag";
+    const TakeTexture &t = m.reflectance;
+    if (t.kind == 1 && (t.image_id < 0 || t.image_id >= n_images))
+        return "material " + std::to_string(i) + ": bad texture image id";
+    o.tag = m.tag;
+    // TakeBuildOpts.burley_lobes: the reference's Disney alternatives (Lambert clones upstream) get the real lobes
+    if (burley_lobes && m.tag >= TAKE_MAT_DISNEY_METAL && m.tag <= TAKE_MAT_DISNEY_BSDF) o.tag = m.tag + 5;
+    o.tex_kind = t.kind, o.tex_image = t.image_id, o.pad = 0;
+    for (int a = 0; a < 3; a++) o.color[a] = R(t.value[a]);
+    o.uscale = R(t.uscale), o.vscale = R(t.vscale), o.uoffset = R(t.uoffset), o.voffset = R(t.voffset);
+    o.p0 = R(m.param[0]), o.p1 = R(m.param[1]);
+    for (int k = 0; k < TAKE_MATERIAL_PARAMS; k++) o.p[k] = R(m.param[k]);
+    if (o.tag >= TAKE_MAT_BURLEY_METAL && o.tag <= TAKE_MAT_BURLEY_BSDF && !burley_params_in_range(o.tag, m.param))
+        return "material " + std::to_string(i) + ": Burley parameter outside [0, 1] (or eta <= 0)";
+    return "";
+}
+// which tags a material table uses, unused materials included: what decides whether a render sorts by material and
+// which shade instances it launches
+template <class R> void material_tags_in_use(const std::vector<MaterialRec<R>> &materials, int &n_material_tags, uint32_t &tag_mask, int &single_tag) {
+    bool tag_used[TAKE_MAT_COUNT] = {false};
+    for (const MaterialRec<R> &o : materials) tag_used[o.tag] = true;
+    n_material_tags = 0, tag_mask = 0;
+    for (int t = 0; t < TAKE_MAT_COUNT; t++)
+        if (tag_used[t]) n_material_tags++, tag_mask |= 1u << t, single_tag = t;
+}
 template <class R> std::string material_table(const TakeSceneDesc &d, bool burley_lobes, HostScene<R> &hs) {
     hs.materials.resize(d.n_materials);
-    bool tag_used[TAKE_MAT_COUNT] = {false};
     for (int i = 0; i < d.n_materials; i++) {
-        const TakeMaterial &m = d.materials[i];
-        if (m.tag < 0 || m.tag >= TAKE_MAT_COUNT) return "material " + std::to_string(i) + ": unknown tag";
-        const TakeTexture &t = m.reflectance;
-        if (t.kind == 1 && (t.image_id < 0 || t.image_id >= d.n_images))
-            return "material " + std::to_string(i) + ": bad texture image id";
-        MaterialRec<R> &o = hs.materials[i];
-        o.tag = m.tag;
-        // TakeBuildOpts.burley_lobes: the reference's Disney alternatives (Lambert clones upstream) get the real lobes
-        if (burley_lobes && m.tag >= TAKE_MAT_DISNEY_METAL && m.tag <= TAKE_MAT_DISNEY_BSDF) o.tag = m.tag + 5;
-        o.tex_kind = t.kind, o.tex_image = t.image_id, o.pad = 0;
-        for (int a = 0; a < 3; a++) o.color[a] = R(t.value[a]);
-        o.uscale = R(t.uscale), o.vscale = R(t.vscale), o.uoffset = R(t.uoffset), o.voffset = R(t.voffset);
-        o.p0 = R(m.param[0]), o.p1 = R(m.param[1]);
-        for (int k = 0; k < TAKE_MATERIAL_PARAMS; k++) o.p[k] = R(m.param[k]);
-        if (o.tag >= TAKE_MAT_BURLEY_METAL && o.tag <= TAKE_MAT_BURLEY_BSDF && !burley_params_in_range(o.tag, m.param))
-            return "material " + std::to_string(i) + ": Burley parameter outside [0, 1] (or eta <= 0)";
-        tag_used[o.tag] = true;
+        const std::string err = material_record(d.materials[i], i, d.n_images, burley_lobes, hs.materials[i]);
+        if (!err.empty()) return err;
     }
-    hs.n_material_tags = 0, hs.tag_mask = 0;
-    for (int t = 0; t < TAKE_MAT_COUNT; t++)
-        if (tag_used[t]) hs.n_material_tags++, hs.tag_mask |= 1u << t, hs.single_tag = t;
+    material_tags_in_use(hs.materials, hs.n_material_tags, hs.tag_mask, hs.single_tag);
     return "";
 }
 
@@ -861,29 +872,12 @@ template <class R> std::string light_records(const TakeSceneDesc &d, HostScene<R
 // fills them; filled here from its light_power(): luminance(intensity) * area * pi for an area light, 0 otherwise;
 // pmf = power / total, cdf = running sum from 0 (n + 1 entries) — in R arithmetic, in light order (the recipe
 // the golden `ptpow` tables were made with: the test harness applies it to the reference's own Scene).
+// (the per-light expression and the serial pass: tk_shading_update.h, which runs the former per lane for
+// take_hip_scene_set_light_intensities)
 template <class R> void light_power_tables(HostScene<R> &hs) {
     hs.light_pmf.clear();  // (the powers first)
-    R total = R(0);
-    for (const LightRec<R> &l : hs.lights) {
-        R p = R(0);
-        if (l.kind == 1) {
-            R area;
-            if (l.is_sphere) {
-                area = R(4) * Const<R>::PI * l.v[3] * l.v[3];
-            } else {
-                const Vec3<R> v0 = {l.v[0], l.v[1], l.v[2]}, v1 = {l.v[3], l.v[4], l.v[5]}, v2 = {l.v[6], l.v[7], l.v[8]};
-                area = length(cross(v1 - v0, v2 - v0)) / R(2);
-            }
-            p = (l.intensity[0] * R(0.212671) + l.intensity[1] * R(0.715160) + l.intensity[2] * R(0.072169)) * area * Const<R>::PI;
-        }
-        hs.light_pmf.push_back(p);
-        total += p;
-    }
-    hs.light_cdf.assign(1, R(0));
-    for (R &p : hs.light_pmf) {
-        p = p / total;
-        hs.light_cdf.push_back(hs.light_cdf.back() + p);
-    }
+    for (const LightRec<R> &l : hs.lights) hs.light_pmf.push_back(su::light_power(l));
+    su::light_tables_from_powers<R>(hs.light_pmf, hs.light_cdf);
 }
 
 // Who makes the primitive records and the tree.  PREP_HOST_BUILD: prepare_scene (records, host SAH tree).

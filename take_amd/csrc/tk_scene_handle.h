@@ -200,6 +200,7 @@ struct TakeScene {
     tk_host::DevBuf<double> xforms;
     int max_leaf = 0;                     // the leaf size request the trees were built with (TakeBuildOpts / TAKE_HIP_MAX_LEAF)
     bool flattened = false;               // TAKE_INSTANCES_FLATTEN expanded placements: the meshes are no longer the caller's
+    bool burley_lobes = false;            // TakeBuildOpts.burley_lobes at creation: take_hip_scene_set_materials remaps new materials the same way
     std::string node_knob;                // TAKE_HIP_NODES when the scene was built
     // take_hip_scene_mark_frame: "the previous frame" — the camera of every resident side and, in a two-level scene, a
     // copy of the placements' transforms (xforms) as they were then.  The changes of a resident scene leave it alone.

@@ -237,13 +237,7 @@ class SceneData:
             lights[i].position = D.c_double3(*l.position)
         mats = (D.TakeMaterial * max(len(self.materials), 1))()
         for i, m in enumerate(self.materials):
-            mats[i].tag = m.tag
-            mats[i].reflectance.kind = m.tex_kind
-            mats[i].reflectance.image_id = m.tex_image
-            mats[i].reflectance.value = D.c_double3(*m.color)
-            (mats[i].reflectance.uscale, mats[i].reflectance.vscale, mats[i].reflectance.uoffset,
-             mats[i].reflectance.voffset) = m.uvxf
-            mats[i].param = (C.c_double * 12)(*(tuple(m.param) + (0.0,) * (12 - len(m.param))))
+            D.fill_material(mats[i], m)
         images = (D.TakeImage3 * max(len(self.images), 1))()
         for i, im in enumerate(self.images):
             a = np.ascontiguousarray(im, np.float64)
