@@ -102,13 +102,24 @@ template <class R> inline V3<R> to_world(V3<R> n, V3<R> v) {
     return x * v.x + y * v.y + n * v.z;
 }
 
+// take.h:60-68 with one departure: where r + b rounds to b (a in (-b * eps/4, 0)) the result is the largest value below
+// b, so result < b always.  The reference returns b there and its texture lookup (the only caller) then reads outside
+// the image: it defines no value for such an a, so nothing pinned to it changes.
 inline double modulo(double a, double b) {  // take.h:65-68
     double r = std::fmod(a, b);
-    return (r < 0.0) ? r + b : r;
+    if (r < 0.0) {
+        r = r + b;
+        if (!(r < b)) r = std::nextafter(b, 0.0);
+    }
+    return r;
 }
 inline float modulo(float a, float b) {  // take.h:60-63
     float r = std::fmod(a, b);
-    return (r < 0.0f) ? r + b : r;
+    if (r < 0.0f) {
+        r = r + b;
+        if (!(r < b)) r = std::nextafter(b, 0.0f);
+    }
+    return r;
 }
 template <class R> inline R clampR(R v, R lo, R hi) { return std::clamp(v, lo, hi); }
 
@@ -594,6 +605,7 @@ template <class R> bool scene_occluded(const Scene<R> &sc, const Ray<R> &r, Trav
 }
 
 // ------------------------------------------------------------------ src/texture.cpp:3-25
+// (modulo() above stays below 1, so 0 <= x1 < width and 0 <= y1 < height for every finite uv)
 template <class R> V3<R> eval_texture(const Texture<R> &t, V2<R> uv, const Scene<R> &sc) {
     if (t.kind == 0) return t.value;
     const Image3<R> &img = sc.images[t.image_id];

@@ -32,6 +32,7 @@ template <> struct Const<float> {
     static constexpr float INVTWOPI = 1.0f / TWOPI;
     static constexpr float BOX_GROW = 1.0000004f;  // 1 + 3 ulp: far-plane widening of the slab test
     static constexpr float BOX_SHRINK = 0.9999996f;
+    static constexpr float BELOW_ONE = 0x1.fffffep-1f;  // the largest float below 1
     static TK_HD float inf() { return __builtin_huge_valf(); }
 };
 template <> struct Const<double> {
@@ -42,6 +43,7 @@ template <> struct Const<double> {
     static constexpr double INVTWOPI = 1.0 / TWOPI;
     static constexpr double BOX_GROW = 1.0000000000000007;
     static constexpr double BOX_SHRINK = 0.9999999999999993;
+    static constexpr double BELOW_ONE = 0x1.fffffffffffffp-1;  // the largest double below 1
     static TK_HD double inf() { return __builtin_huge_val(); }
 };
 

@@ -91,9 +91,19 @@ TK_HD void make_isect(const DeviceScene<R> &sc, Vec3<R> ro, Vec3<R> rd, int32_t 
 }
 
 // ---- textures (src/texture.cpp:3-25; the wrap-seam arithmetic of :13-24 is kept as is)
+// modulo(a, 1) of src/take.h:60-68 with ONE departure: for a in (-eps/4, 0) (eps/4 = 2^-25 in f32, 2^-54 in f64) the
+// reference's r + 1 rounds to exactly 1, its x1 becomes `width` and its lookup reads outside the image.  Here the result
+// is then the largest value below 1, so it lies in [0, 1) for every finite a, 0 <= x1 < width and 0 <= y1 < height
+// follow (width * (1 - eps/2) rounds below width for every width), and the cell is the seam cell width-1 -> 0 that
+// exact arithmetic picks.  Every a whose result was below 1 keeps its bits; where the reference read out of bounds it
+// defined no value, so no pinned value moves.
 template <class R> TK_HD R modulo1(R a) {
     R r = tk_fmod(a, R(1));
-    return (r < R(0)) ? r + R(1) : r;
+    if (r < R(0)) {
+        r = r + R(1);
+        r = (r < R(1)) ? r : Const<R>::BELOW_ONE;
+    }
+    return r;
 }
 template <class R> TK_HD Vec3<R> eval_texture(const DeviceScene<R> &sc, const MaterialRec<R> &m, Vec2<R> uv) {
     if (m.tex_kind == 0) return ld3(m.color);

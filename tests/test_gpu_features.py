@@ -66,7 +66,7 @@ def texture_lookup(sd, m, uv):
 
     def mod1(a):
         r = np.fmod(a, 1.0)
-        return np.where(r < 0, r + 1.0, r)
+        return np.where(r < 0, np.minimum(r + 1.0, np.nextafter(1.0, 0.0)), r)  # below 1 where r + 1 rounds to 1
 
     x, y = iw * mod1(us * uv[:, 0] + uo), ih * mod1(vs * uv[:, 1] + vo)
     x1, y1 = np.floor(x).astype(int), np.floor(y).astype(int)
