@@ -415,6 +415,79 @@ int take_hip_scene_set_mesh_vertices(TakeScene *scene, const TakeMeshUpdate *upd
  * two leaves, a depth (new top level + deepest prototype + return marker) beyond the traversal stack, node counts
  * beyond the 32-bit record offsets. */
 int take_hip_scene_update_meshes(TakeScene *scene, const TakeMeshUpdate *updates, int32_t n_updates);
+/* Skinning and morph targets on the device (EXTENSION; new symbols of ABI version 5; no struct changed; specification:
+ * DESIGN.md §4q).  A rig is the producer in front of take_hip_scene_update_meshes: it keeps a mesh's rest pose, joint
+ * influences and morph targets in device memory, and a pose — one 3x4 matrix per joint, one weight per target — makes
+ * the posed positions and normals there.  The handle is scene-free, bound to the device current at its creation, and
+ * not thread-safe (it owns the buffers a pose is written into).
+ * Arithmetic, in double, every operation in the order written:
+ *   palette   J_j = X_j · B_j (3x4 affine; X = joint_xforms, B = inverse_bind; B NULL: J_j = X_j)
+ *   morph     p = rest + sum_t w_t dp_t, t in order; n likewise with target_normals
+ *   blend     M = sum_k weight_k J_{joint_k}, k in order, no influence skipped; weights are taken AS THEY ARE: they are
+ *             neither checked for summing to 1 nor renormalised, and padding is a zero weight on any joint in range
+ *   position  p' = M (p, 1)
+ *   normal    n' = cof(M3x3) n, negated when det(M3x3) < 0 — the inverse transpose up to a positive factor, right under
+ *             non-uniform scale and mirroring —, then divided by its length when that is positive and finite
+ *   a rig without joints (n_joints == 0) only morphs: p' = p, n' = n / |n|. */
+typedef struct TakeRig TakeRig;
+#define TAKE_RIG_DEVICE_ARRAYS 1
+#define TAKE_RIG_POSE_DEVICE_ARRAYS 1
+typedef struct TakeRigDesc {
+    int64_t n_vertices;             /* > 0 */
+    const double *positions;        /* n_vertices x 3, rest pose; required */
+    const double *normals;          /* n_vertices x 3, or NULL: the rig poses no normals */
+    int32_t n_joints;               /* >= 0; 0 = a morph-only rig */
+    int32_t n_influences;           /* K: 1..8 when n_joints > 0, else 0 */
+    const int32_t *joints;          /* n_vertices x K, each in [0, n_joints) */
+    const double *weights;          /* n_vertices x K; taken as they are, never renormalised */
+    const double *inverse_bind;     /* n_joints x 12 (3x4 row-major, as set_instance_transforms takes them), NULL = identity */
+    int32_t n_targets;              /* T >= 0 */
+    const double *target_positions; /* T x n_vertices x 3 deltas, target-major; required when T > 0 */
+    const double *target_normals;   /* T x n_vertices x 3 deltas, or NULL; only for a rig with normals */
+    int32_t flags;                  /* 0, or TAKE_RIG_DEVICE_ARRAYS: every array above is device memory */
+} TakeRigDesc;
+typedef struct TakeRigPose {
+    const double *joint_xforms;     /* n_joints x 12: joint -> world; required when n_joints > 0 */
+    const double *target_weights;   /* T doubles; required when T > 0 */
+    int32_t flags;                  /* 0, or TAKE_RIG_POSE_DEVICE_ARRAYS: both arrays are device memory */
+} TakeRigPose;
+typedef struct TakeRigBinding {
+    int32_t mesh;                   /* index into the TakeSceneDesc.meshes the scene was created from */
+    int32_t reserved;
+    TakeRig *rig;
+    TakeRigPose pose;
+} TakeRigBinding;
+/* The rig copies its arrays to the device and allocates everything a pose needs (posed positions, posed normals, the
+ * palette, the staged pose): no later call allocates for the pose.
+ * TAKE_E_INVALID before a device is looked for: a NULL argument, n_vertices <= 0, negative counts, K outside 1..8 with
+ * joints or not 0 without, a missing required array, target_normals without normals, unknown flag bits.  With the
+ * device: host arrays with a joint index out of range or a value that is not finite (the message names array and index);
+ * device arrays with a joint index out of range (a kernel finds the smallest such vertex; values are not looked at).
+ * TAKE_E_NOMEM: the device has no room for the rig. */
+int take_hip_rig_create(const TakeRigDesc *desc, TakeRig **out);
+int take_hip_rig_destroy(TakeRig *rig);
+/* what the rig holds; device_bytes: everything it has allocated, which no pose changes.  Any output may be NULL. */
+int take_hip_rig_info(const TakeRig *rig, int64_t *n_vertices, int32_t *n_joints, int32_t *n_influences, int32_t *n_targets, int32_t *has_normals,
+                      int64_t *device_bytes);
+/* The rig under `pose` into device memory: n_vertices x 3 doubles each; d_normals_out NULL = not wanted (given for a
+ * rig without normals: TAKE_E_INVALID).  Runs on `stream` (hipStream_t, NULL = the default stream), after whatever that
+ * stream still has to write into device pose arrays, and returns after it has completed. */
+int take_hip_rig_pose_device(TakeRig *rig, const TakeRigPose *pose, double *d_positions_out, double *d_normals_out, void *stream);
+/* the same into host arrays (the rig's own buffers, then a download); normals_out NULL = not wanted */
+int take_hip_rig_pose(TakeRig *rig, const TakeRigPose *pose, double *positions_out, double *normals_out);
+/* Pose and update in one step: every binding's rig is posed into the rig's own buffers, then the scene takes exactly the
+ * path of take_hip_scene_update_meshes with TAKE_MESH_DEVICE_ARRAYS over them.  Afterwards the scene is, byte for byte,
+ * the scene after take_hip_rig_pose to the host followed by take_hip_scene_update_meshes with those host arrays — with
+ * everything that call carries: both kinds of scene, every precision, the finiteness refusal (which is what catches a
+ * joint matrix that is not finite), frame marks and vertex tracking, the end of a progressive sequence, and a failed
+ * call leaving the scene as it was (the pose kernels write rig-owned memory only, before anything is staged).
+ * Normals are passed on only when both the rig and the mesh have them: a mesh with normals keeps them under a rig
+ * without, and a rig with normals computes none for a mesh without.
+ * TAKE_E_INVALID before a device is looked for: a NULL argument (a binding's rig, a required pose array), n <= 0, a
+ * negative mesh index, unknown pose flag bits, a mesh named twice, a rig bound twice.  Right after it, against the
+ * scene: a mesh index out of range, a rig on another device, a rig whose n_vertices is not the mesh's (the message
+ * names the binding, the mesh and both counts).  Then every refusal of take_hip_scene_update_meshes, in its words. */
+int take_hip_scene_pose_meshes(TakeScene *scene, const TakeRigBinding *bindings, int32_t n);
 /* A new environment map (EXTENSION; new symbols of ABI version 5; no struct changed; specification: DESIGN.md §4o).
  * The call replaces the image images[k] of the description the scene was created from, k being the shape_id of its
  * environment-map light (TakeLight kind 2), and — with scale3 — that light's intensity; scale3 == NULL keeps it.

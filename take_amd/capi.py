@@ -46,6 +46,7 @@ EXPORTS = [
     "take_hip_scene_set_envmap", "take_hip_scene_set_envmap_device", "take_hip_debug_env_tables_info", "take_hip_debug_env_tables",
     "take_hip_scene_set_materials", "take_hip_scene_set_light_intensities", "take_hip_scene_set_light_intensities_device",
     "take_hip_debug_shading_tables_info", "take_hip_debug_shading_tables",
+    "take_hip_rig_create", "take_hip_rig_destroy", "take_hip_rig_info", "take_hip_rig_pose_device", "take_hip_rig_pose", "take_hip_scene_pose_meshes",
 ]
 
 
@@ -93,7 +94,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()) + list(D.RIG_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -625,6 +626,134 @@ class DeviceMesh:
             pass
 
 
+def _on_device(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def _rig_array(a, dtype, shape, name, device, keep):
+    """one array of a rig or of a pose -> its pointer (None stays None): a contiguous torch tensor on the device when
+    `device`, else host memory through numpy; `shape` with -1 for a free extent"""
+    if a is None:
+        return None
+    if device:
+        if not _on_device(a) or str(a.dtype) != "torch." + np.dtype(dtype).name or not a.is_contiguous():
+            raise ValueError(f"{name}: arrays on the device must be contiguous {np.dtype(dtype).name} tensors, and all arrays of a call on the device")
+        got = tuple(a.shape)
+    else:
+        if hasattr(a, "data_ptr"):  # a torch tensor in host memory
+            a = a.numpy()
+        a = np.ascontiguousarray(a, dtype)
+        got = a.shape
+    if len(got) != len(shape) or any(w >= 0 and g != w for g, w in zip(got, shape)):
+        raise ValueError(f"{name} must have shape {tuple('n' if w < 0 else w for w in shape)}, not {tuple(got)}")
+    keep.append(a)
+    return a.data_ptr() if device else a.ctypes.data
+
+
+class Rig:
+    """A mesh's rest pose, joint influences and morph targets in device memory (take_hip_rig_create): what pose(),
+    pose_device() and Scene.pose_meshes() skin and morph on the device — linear-blend skinning over a joint palette,
+    normals by the cofactor matrix (include/take_hip.h has the arithmetic).  positions (n, 3) and the optional normals
+    (n, 3) are the rest pose; joints (n, K) int32 and weights (n, K), K = 1..8, name each vertex's influences (weights are
+    taken as they are, padding is a zero weight on any valid joint); inverse_bind (n_joints, 3, 4), None = identity —
+    it fixes the joint count, which without it is max(joints) + 1 or `n_joints`; target_positions / target_normals
+    (T, n, 3) are morph deltas.  Either numpy arrays (or anything numpy converts), or contiguous float64 / int32 torch
+    tensors on the device — all of them then.  Bound to the device current at its creation; not thread-safe."""
+
+    def __init__(self, positions, normals=None, joints=None, weights=None, inverse_bind=None, target_positions=None, target_normals=None, n_joints=None):
+        self._h = C.c_void_p()
+        device = _on_device(positions)
+        keep = []
+        d = D.TakeRigDesc()
+        d.positions = _rig_array(positions, np.float64, (-1, 3), "positions", device, keep)
+        nv = int(keep[0].shape[0])
+        d.n_vertices, d.flags = nv, D.TAKE_RIG_DEVICE_ARRAYS if device else 0
+        d.normals = _rig_array(normals, np.float64, (nv, 3), "normals", device, keep)
+        if (joints is None) != (weights is None):
+            raise ValueError("joints and weights go together")
+        if joints is not None:
+            d.joints = _rig_array(joints, np.int32, (nv, -1), "joints", device, keep)
+            ja = keep[-1]
+            k = int(ja.shape[1])
+            d.weights = _rig_array(weights, np.float64, (nv, k), "weights", device, keep)
+            d.inverse_bind = _rig_array(inverse_bind, np.float64, (-1, 3, 4), "inverse_bind", device, keep)
+            if inverse_bind is not None:
+                nj = int(keep[-1].shape[0])
+            elif n_joints is not None:
+                nj = int(n_joints)
+            else:
+                nj = int(ja.max()) + 1 if nv * k else 0
+            d.n_joints, d.n_influences = nj, k
+        if target_positions is not None:
+            d.target_positions = _rig_array(target_positions, np.float64, (-1, nv, 3), "target_positions", device, keep)
+            d.n_targets = int(keep[-1].shape[0])
+            d.target_normals = _rig_array(target_normals, np.float64, (d.n_targets, nv, 3), "target_normals", device, keep)
+        elif target_normals is not None:
+            raise ValueError("target_normals without target_positions")
+        _check(lib().take_hip_rig_create(C.byref(d), C.byref(self._h)))
+        self.n_vertices, self.n_joints, self.n_influences, self.n_targets, self.has_normals = nv, int(d.n_joints), int(d.n_influences), int(d.n_targets), normals is not None
+
+    def info(self):
+        """-> {"n_vertices", "n_joints", "n_influences", "n_targets", "has_normals", "device_bytes"} (take_hip_rig_info)"""
+        nv, bytes_ = C.c_int64(), C.c_int64()
+        nj, k, t, hn = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().take_hip_rig_info(self._h, C.byref(nv), C.byref(nj), C.byref(k), C.byref(t), C.byref(hn), C.byref(bytes_)))
+        return {"n_vertices": nv.value, "n_joints": nj.value, "n_influences": k.value, "n_targets": t.value, "has_normals": bool(hn.value),
+                "device_bytes": bytes_.value}
+
+    def _pose(self, joint_xforms, target_weights, keep):
+        """a TakeRigPose over host arrays, or over device tensors (both then)"""
+        device = _on_device(joint_xforms) or _on_device(target_weights)
+        p = D.TakeRigPose()
+        p.joint_xforms = _rig_array(joint_xforms, np.float64, (self.n_joints, 3, 4), "joint_xforms", device, keep)
+        p.target_weights = _rig_array(target_weights, np.float64, (self.n_targets,), "target_weights", device, keep)
+        p.flags = D.TAKE_RIG_POSE_DEVICE_ARRAYS if device else 0
+        return p, device
+
+    def pose(self, joint_xforms=None, target_weights=None):
+        """the rig under a pose (take_hip_rig_pose): joint_xforms (n_joints, 3, 4) joint -> world, target_weights (T,)
+        -> the posed positions (n, 3), or (positions, normals) when the rig has normals; numpy arrays"""
+        keep = []
+        p, device = self._pose(joint_xforms, target_weights, keep)
+        if device:
+            import torch
+
+            torch.cuda.current_stream(keep[0].device).synchronize()
+        pos = np.zeros((self.n_vertices, 3), np.float64)
+        nrm = np.zeros((self.n_vertices, 3), np.float64) if self.has_normals else None
+        _check(lib().take_hip_rig_pose(self._h, C.byref(p), pos.ctypes.data, None if nrm is None else nrm.ctypes.data))
+        return pos if nrm is None else (pos, nrm)
+
+    def pose_device(self, out_positions, out_normals=None, joint_xforms=None, target_weights=None, stream=None):
+        """the same into device memory (take_hip_rig_pose_device): out_positions, out_normals are (n, 3) float64 torch
+        device tensors or integer device pointers; runs on `stream` (default: torch's current stream when a pose array
+        is a device tensor, else the default stream) and blocks until done"""
+        keep = []
+        p, device = self._pose(joint_xforms, target_weights, keep)
+        if stream is None and device:
+            import torch
+
+            stream = torch.cuda.current_stream(keep[0].device).cuda_stream
+        _check(lib().take_hip_rig_pose_device(self._h, C.byref(p), C.c_void_p(_pointer(out_positions)), C.c_void_p(_pointer(out_normals)), C.c_void_p(stream or 0)))
+
+    def close(self):
+        if self._h:
+            lib().take_hip_rig_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (interpreter shutdown: the library may be gone)
+            pass
+
+
 DEBUG_TABLES = {"material": (0, 27, 14), "light": (1, 30, 9), "texture": (2, 6, 3), "to_world": (3, 6, 3),
                 "hemicos": (4, 1, 4), "burley": (5, 30, 14)}
 
@@ -1039,6 +1168,30 @@ class Scene:
         scene's current transforms; afterwards the scene traces and renders as one newly created from the description
         with these arrays and those transforms.  A scene without placements: the same as set_mesh_vertices."""
         self.set_mesh_vertices(updates, _entry="take_hip_scene_update_meshes")
+
+    def pose_meshes(self, bindings, stream=None):
+        """skin / morph meshes of the resident scene and update it in one step (take_hip_scene_pose_meshes): `bindings` is
+        [(mesh_id, rig, joint_xforms, target_weights), ...] — a Rig of the mesh's vertex count and a pose as Rig.pose
+        takes it (None for what the rig has none of).  Every rig is posed into its own device buffers and the scene takes
+        update_meshes' path over them: afterwards it equals the scene after update_meshes({mesh_id: rig.pose(...)}).
+        Pose arrays may be device tensors written on `stream` (default: torch's current stream), which the call waits
+        for first."""
+        bindings = list(bindings)
+        recs = (D.TakeRigBinding * max(len(bindings), 1))()
+        keep, wait = [], None
+        for k, (mesh, rig, joint_xforms, target_weights) in enumerate(bindings):
+            if not isinstance(rig, Rig) or not rig._h:
+                raise ValueError("a binding's rig must be an open Rig")
+            pose, device = rig._pose(joint_xforms, target_weights, keep)
+            if device and wait is None:
+                wait = keep[-1].device
+            recs[k].mesh, recs[k].rig, recs[k].pose = int(mesh), rig._h, pose
+        if wait is not None:
+            import torch
+
+            (torch.cuda.current_stream(wait) if stream is None else torch.cuda.ExternalStream(int(stream), device=wait)).synchronize()
+        _check(lib().take_hip_scene_pose_meshes(self.h, recs, len(bindings)))
+        del keep
 
     def set_mesh_vertices(self, updates, _entry="take_hip_scene_set_mesh_vertices"):
         """new vertices for meshes of a scene without placements (take_hip_scene_set_mesh_vertices): `updates` is

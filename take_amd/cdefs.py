@@ -102,6 +102,41 @@ SCENE_UPDATE_PROTOTYPES = {
 }
 
 
+# rigs: skinning and morph targets on the device (include/take_hip.h: take_hip_rig_*, take_hip_scene_pose_meshes)
+TAKE_RIG_DEVICE_ARRAYS = 1
+TAKE_RIG_POSE_DEVICE_ARRAYS = 1
+
+
+class TakeRigDesc(C.Structure):
+    """take_hip_rig_create: rest pose, influences and morph targets of one mesh (host memory, or device memory under
+    TAKE_RIG_DEVICE_ARRAYS)"""
+    _fields_ = [("n_vertices", C.c_int64), ("positions", C.c_void_p), ("normals", C.c_void_p), ("n_joints", C.c_int32),
+                ("n_influences", C.c_int32), ("joints", C.c_void_p), ("weights", C.c_void_p), ("inverse_bind", C.c_void_p),
+                ("n_targets", C.c_int32), ("target_positions", C.c_void_p), ("target_normals", C.c_void_p), ("flags", C.c_int32)]
+
+
+class TakeRigPose(C.Structure):
+    """one pose of a rig: n_joints x 12 joint -> world matrices and T target weights (host memory, or device memory under
+    TAKE_RIG_POSE_DEVICE_ARRAYS)"""
+    _fields_ = [("joint_xforms", C.c_void_p), ("target_weights", C.c_void_p), ("flags", C.c_int32)]
+
+
+class TakeRigBinding(C.Structure):
+    """take_hip_scene_pose_meshes: one mesh of the scene, the rig that poses it, the pose"""
+    _fields_ = [("mesh", C.c_int32), ("reserved", C.c_int32), ("rig", C.c_void_p), ("pose", TakeRigPose)]
+
+
+RIG_PROTOTYPES = {
+    "take_hip_rig_create": [C.POINTER(TakeRigDesc), C.POINTER(C.c_void_p)],
+    "take_hip_rig_destroy": [C.c_void_p],
+    "take_hip_rig_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                          C.POINTER(C.c_int64)],
+    "take_hip_rig_pose_device": [C.c_void_p, C.POINTER(TakeRigPose), C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_rig_pose": [C.c_void_p, C.POINTER(TakeRigPose), C.c_void_p, C.c_void_p],
+    "take_hip_scene_pose_meshes": [C.c_void_p, C.POINTER(TakeRigBinding), C.c_int32],
+}
+
+
 class TakeRenderOpts(C.Structure):
     _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64), ("ray_epsilon", C.c_double),
                 ("strip_first", C.c_int32), ("strip_stride", C.c_int32), ("samples_per_batch", C.c_int32),

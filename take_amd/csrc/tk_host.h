@@ -1,8 +1,8 @@
 // tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_create.hip and tk_group.hip (the C entry
 // points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
 // tk_mesh.hip (mesh ingest), tk_denoise.hip (the image-space denoiser), tk_display.hip (the display transform),
-// tk_bloom.hip (its bloom and the image workspace), tk_envmap.hip (a new environment map for a resident scene) and
-// tk_shading_update.hip (its new materials and light intensities): the error string, fault injection, pinned uploads, the owning device buffer, the staged planes of the host twins, the
+// tk_bloom.hip (its bloom and the image workspace), tk_envmap.hip (a new environment map for a resident scene),
+// tk_shading_update.hip (its new materials and light intensities) and tk_skin.hip (rigs: skinning and morph targets): the error string, fault injection, pinned uploads, the owning device buffer, the staged planes of the host twins, the
 // dispatch on a precision, the check of a plane's size and precision.  (The scene handle all but tk_mesh.hip and
 // tk_display.hip share is tk_scene_handle.h.)
 // Everything here has external linkage (inline, in a named namespace): the units share ONE error string (what
