@@ -607,8 +607,9 @@ int take_hip_scene_focus_distance_at(TakeScene *scene, int32_t column, int32_t r
  *    the matrix motion transform of Embree and OptiX.  A rotation moves along its CHORD, not its arc (a half turn passes
  *    through a singular matrix at t = 0.5): callers with fast rotations mark more often.  The lens (take_hip_scene_set_lens:
  *    radius and effective focus distance) is the current frame's at every t.  Vertices that moved since the mark
- *    (take_hip_scene_set_mesh_vertices / _update_meshes) are NOT interpolated: the meshes are at their current vertices
- *    throughout, whether or not take_hip_scene_track_vertices is on.
+ *    (take_hip_scene_set_mesh_vertices / _update_meshes) are at their current positions throughout THESE calls, whether
+ *    or not take_hip_scene_track_vertices is on: the scene keeps no second set of vertices.  A caller that has both sets
+ *    passes them to take_hip_render_shutter_meshes* below, which lerps them per slice.
  *    xforms_out: 12 * n_instances doubles in host memory, or NULL = not wanted (ignored for a scene without placements).
  *  - The render.  For k = 0 .. K-1 the scene is posed at t_k on the device — the camera records; the placements by the
  *    path take_hip_scene_set_instance_transforms takes, the top level alone rebuilt — and slice k's samples are rendered
@@ -640,6 +641,58 @@ int take_hip_shutter_plan(int32_t spp, const TakeShutter *shutter /* NULL = {0, 
 int take_hip_shutter_pose(TakeScene *scene, double t, TakeCamera *camera_out, double *xforms_out /* 12 * n_instances, host; NULL = not wanted */);
 int take_hip_render_shutter_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, void *d_rgb_out, void *stream);
 int take_hip_render_shutter(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, void *rgb_out_host);
+/* Motion blur for deforming meshes (EXTENSION, parity unpinned; new symbols of ABI version 5; no struct changed;
+ * DESIGN.md par. 4r): take_hip_render_shutter* with one addition — for every slice k, before its samples are rendered,
+ * the named meshes are at the lerp of their two vertex arrays at t_k.
+ *  - The arithmetic.  Every coordinate of a position, and every component of a vertex normal, is the shutter's lerp
+ *    above ((1 - t) * a + t * b in double, `1 - t` rounded once, no contraction; b itself where a == b), so t = 0 gives
+ *    the marked array, t = 1 the current one, and a vertex that did not move stays where it is bit for bit at every t.
+ *    A vertex moves along its CHORD.  Normals are lerped component by component and NOT renormalised: the shading
+ *    normal is normalised at every hit after the barycentric blend, into which the shorter lerped normals enter with a
+ *    slightly smaller weight.  Values that are not finite pass through; refusing them is the update's business.
+ *  - take_hip_shutter_vertices* needs no scene: the lerp of n doubles (3 * n_vertices) at one t, on the device — what
+ *    take_hip_shutter_pose is for placements.  *moved (NULL = not wanted) becomes 1 where any out[e] differs bit for bit
+ *    from b[e], else 0.  The _device variant reads and writes device memory on `stream` (hipStream_t, NULL = the default
+ *    stream) and returns after it has completed; d_out may be d_a or d_b.
+ *  - The render.  PRECONDITION: the scene's meshes are at positions1 / normals1 — the caller has updated them
+ *    (take_hip_scene_update_meshes, take_hip_scene_pose_meshes); the call cannot check this and relies on it only where
+ *    it skips work.  Per named mesh one buffer for positions (and one for normals) is allocated, and host arrays are
+ *    uploaded, once, before the first slice.  Per slice the vertices are made in those buffers and the scene takes
+ *    take_hip_scene_update_meshes' staged path over them — in a two-level scene under THAT SLICE's posed transforms, the
+ *    placements' records and the one top-level rebuild serving both — so area lights on moved faces get their records
+ *    and power tables as in an update.  A slice whose vertices are the current ones bit for bit, in a scene that is at
+ *    them, runs no update: with n = 0, or positions0 == positions1 in value, the call IS take_hip_render_shutter — same
+ *    launches, same image.  These updates are internal: the mark, vertex tracking (take_hip_scene_tracking_info, the
+ *    marked geometry) and `updated since the mark` are left as they were.
+ *  - Afterwards, on success or failure: if any slice updated the meshes they are updated once more with positions1 /
+ *    normals1 under the current transforms, camera and placements are restored as by take_hip_render_shutter, and the
+ *    scene traces and renders exactly as after take_hip_scene_update_meshes with the ...1 arrays — for a scene that was
+ *    at them already, hit tables, occlusion and images are bit for bit those before the call.  As after any update,
+ *    take_hip_scene_build_info and take_hip_scene_stats may report the device builder's tree.  A progressive sequence
+ *    ends as take_hip_render_shutter ends it.  F32, F64 and MIXED scenes (both sides), one- and two-level; strips,
+ *    samples_per_batch and a lens as take_hip_render_shutter.  Not for scene groups.
+ * Still open: interpolating the POSE of a rig instead of its vertices (arcs for joints), a time per ray, scene groups.
+ * TAKE_E_INVALID, before a device is looked for: everything take_hip_render_shutter* refuses there; n < 0; motions
+ * NULL with n > 0; positions0 or positions1 NULL; one of normals0 / normals1 without the other; unknown flag bits; a
+ * negative mesh index; a mesh named twice.  shutter_vertices: a NULL a, b or out, n <= 0, t outside [0, 1].  Against
+ * the scene: a mesh index out of range; normals for a mesh without vertex normals; no marked frame; every
+ * "unsupported" case of take_hip_scene_update_meshes, in its words.  In the loop: the update's own refusals (a vertex
+ * that is not finite, a tree too deep), prefixed with "slice k: "; the scene is restored before the call returns.
+ * TAKE_E_NOMEM: no room for the buffers, before anything changed. */
+typedef struct TakeMeshMotion {
+    int32_t mesh;              /* index into the TakeSceneDesc.meshes the scene was created from */
+    int32_t flags;             /* 0, or TAKE_MESH_DEVICE_ARRAYS: all four pointers are device memory */
+    const double *positions0;  /* n_vertices x 3 at the marked frame (scene time 0); required */
+    const double *positions1;  /* n_vertices x 3 at the current frame (scene time 1); required */
+    const double *normals0;    /* both or neither; only for a mesh that has vertex normals */
+    const double *normals1;
+} TakeMeshMotion;
+int take_hip_shutter_vertices(const double *a, const double *b, int64_t n, double t, double *out, int32_t *moved /* NULL ok */);
+int take_hip_shutter_vertices_device(const double *d_a, const double *d_b, int64_t n, double t, double *d_out, int32_t *moved_host, void *stream);
+int take_hip_render_shutter_meshes(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n,
+                                   void *rgb_out_host);
+int take_hip_render_shutter_meshes_device(TakeScene *scene, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n,
+                                          void *d_rgb_out, void *stream);
 
 /* Replaces the parallel_for tile loop of render() (src/render.cpp:59-82) and all it
  * calls.  rgb_out: this rank's rows only, compacted in increasing image-row order

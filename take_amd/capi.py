@@ -40,6 +40,7 @@ EXPORTS = [
     "take_hip_luminance_histogram", "take_hip_luminance_histogram_device", "take_hip_auto_exposure", "take_hip_tonemap", "take_hip_tonemap_device",
     "take_hip_scene_set_lens", "take_hip_scene_get_lens", "take_hip_scene_focus_distance_at",
     "take_hip_shutter_plan", "take_hip_shutter_pose", "take_hip_render_shutter", "take_hip_render_shutter_device",
+    "take_hip_shutter_vertices", "take_hip_shutter_vertices_device", "take_hip_render_shutter_meshes", "take_hip_render_shutter_meshes_device",
     "take_hip_image_workspace_create", "take_hip_image_workspace_destroy", "take_hip_bloom_layer", "take_hip_bloom_layer_device",
     "take_hip_tonemap_bloom", "take_hip_tonemap_bloom_device",
     "take_hip_render_rays", "take_hip_render_rays_device", "take_hip_camera_rays", "take_hip_camera_rays_device",
@@ -94,7 +95,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()) + list(D.RIG_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.SHUTTER_MESHES_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()) + list(D.RIG_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -141,6 +142,37 @@ def shutter_plan(spp, open=0.0, close=1.0, slices=0):
     _check(lib().take_hip_shutter_plan(int(spp), C.byref(sh), C.byref(k), first.ctypes.data_as(C.POINTER(C.c_int32)),
                                        time.ctypes.data_as(C.POINTER(C.c_double))))
     return first, time
+
+
+def _on_device(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def shutter_vertices(a, b, t, stream=None):
+    """the vertices of a deforming mesh at scene time t in [0, 1] (take_hip_shutter_vertices): `a` the array at the marked
+    frame, `b` at the current one — positions or normals, any shape, float64 — lerped entry by entry on the device as
+    render_shutter_meshes lerps them -> (out, moved): the array at t, and 1 where any entry of it is not b's bit for bit.
+    numpy arrays give a numpy array; contiguous float64 torch device tensors are read through their device pointers after
+    `stream` (default: torch's current stream) and give a new device tensor."""
+    moved = C.c_int32(-1)
+    if _on_device(a) or _on_device(b):
+        import torch
+
+        if not (_on_device(a) and _on_device(b)) or a.shape != b.shape or a.device != b.device or not all(str(x.dtype) == "torch.float64" and x.is_contiguous() for x in (a, b)):
+            raise ValueError("arrays on the device must be contiguous float64 tensors of one shape, both on one device")
+        out = torch.empty_like(a)
+        if stream is None:
+            stream = torch.cuda.current_stream(a.device).cuda_stream
+        with torch.cuda.device(a.device):
+            _check(lib().take_hip_shutter_vertices_device(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.numel(), float(t), C.c_void_p(out.data_ptr()),
+                                                          C.byref(moved), C.c_void_p(stream or 0)))
+        return out, moved.value
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    if a.shape != b.shape:
+        raise ValueError("a and b must have one shape")
+    out = np.zeros_like(a)
+    _check(lib().take_hip_shutter_vertices(a.ctypes.data, b.ctypes.data, a.size, float(t), out.ctypes.data, C.byref(moved)))
+    return out, moved.value
 
 
 def ply_layout(data):
@@ -1152,6 +1184,72 @@ class Scene:
         o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
         sh = D.TakeShutter(float(open), float(close), int(slices), 0)
         _check(lib().take_hip_render_shutter_device(self.h, C.byref(o), C.byref(sh), C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
+
+    def _motions(self, motions, stream):
+        """[(mesh_id, positions0, positions1[, normals0, normals1]), ...] -> (TakeMeshMotion array, n, what keeps the
+        arrays alive); device tensors are waited for on `stream` (default: torch's current stream)"""
+        motions = list(motions)
+        recs = (D.TakeMeshMotion * max(len(motions), 1))()
+        keep, wait = [], None
+        for k, m in enumerate(motions):
+            if len(m) not in (3, 5):
+                raise ValueError("a motion is (mesh_id, positions0, positions1) or (mesh_id, positions0, positions1, normals0, normals1)")
+            arrays = list(m[1:]) + [None] * (5 - len(m))
+            device = _on_device(arrays[0])
+            ptrs = []
+            for a in arrays:
+                if a is None:
+                    ptrs.append(None)
+                elif device:
+                    if not _on_device(a) or str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                        raise ValueError("arrays on the device must be contiguous float64 tensors, and all arrays of a mesh on the device")
+                    keep.append(a)
+                    ptrs.append(a.data_ptr())
+                    wait = a.device if wait is None else wait
+                else:
+                    a = np.ascontiguousarray(a.numpy() if hasattr(a, "data_ptr") else a, np.float64)
+                    keep.append(a)
+                    ptrs.append(a.ctypes.data)
+            recs[k].mesh, recs[k].flags = int(m[0]), D.TAKE_MESH_DEVICE_ARRAYS if device else 0
+            recs[k].positions0, recs[k].positions1, recs[k].normals0, recs[k].normals1 = ptrs
+        if wait is not None:
+            import torch
+
+            (torch.cuda.current_stream(wait) if stream is None else torch.cuda.ExternalStream(int(stream), device=wait)).synchronize()
+        return recs, len(motions), keep
+
+    def render_shutter_meshes(self, motions, spp=None, max_depth=None, seed=0, open=0.0, close=1.0, slices=0, ray_epsilon=0.0, strip_first=0,
+                              strip_stride=1, samples_per_batch=0, integrator=0, stream=None):
+        """motion blur for deforming meshes (take_hip_render_shutter_meshes): render_shutter, with the vertices of the
+        named meshes lerped to every slice's time.  `motions` is [(mesh_id, positions0, positions1), ...] or, for a mesh
+        with vertex normals, [(mesh_id, positions0, positions1, normals0, normals1), ...]: (n_vertices, 3) float64 arrays
+        at the marked frame (0) and at the current one (1) — numpy arrays, or contiguous torch device tensors (all arrays
+        of a mesh on the device), which are waited for on `stream` (default: torch's current stream) first.  The scene
+        must BE at the ...1 arrays; it is again afterwards -> (rows, W, 3) host array, as render's.
+
+        With a rig: pose it twice into two tensors, bring the scene to the current pose, pass both —
+            p0, n0, p1, n1 = (torch.empty((rig.n_vertices, 3), dtype=torch.float64, device="cuda") for _ in range(4))
+            rig.pose_device(p0, n0, joints_then)          # the pose at the marked frame
+            rig.pose_device(p1, n1, joints_now)           # the current pose
+            scene.update_meshes({mesh_id: (p1, n1)})      # or scene.pose_meshes([(mesh_id, rig, joints_now, None)])
+            image = scene.render_shutter_meshes([(mesh_id, p0, p1, n0, n1)], spp=64)"""
+        recs, n, keep = self._motions(motions, stream)
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        sh = D.TakeShutter(float(open), float(close), int(slices), 0)
+        rows = _check(lib().take_hip_render_rows(self.h, strip_first, strip_stride, None))
+        out = np.zeros((rows, self.sd.width, 3), self.dtype)
+        _check(lib().take_hip_render_shutter_meshes(self.h, C.byref(o), C.byref(sh), recs, n, out.ctypes.data))
+        del keep
+        return out
+
+    def render_shutter_meshes_device(self, d_ptr, motions, spp, max_depth, seed=0, open=0.0, close=1.0, slices=0, ray_epsilon=0.0, strip_first=0,
+                                     strip_stride=1, samples_per_batch=0, stream=None, integrator=0):
+        """the same into device memory at `d_ptr` (a torch device tensor or an integer device pointer); blocks until done"""
+        recs, n, keep = self._motions(motions, stream)
+        o = self._opts(spp, max_depth, seed, ray_epsilon, strip_first, strip_stride, samples_per_batch, integrator)
+        sh = D.TakeShutter(float(open), float(close), int(slices), 0)
+        _check(lib().take_hip_render_shutter_meshes_device(self.h, C.byref(o), C.byref(sh), recs, n, C.c_void_p(_pointer(d_ptr)), C.c_void_p(stream or 0)))
+        del keep
 
     def shutter_pose(self, t):
         """the pose render_shutter gives the scene at scene time t in [0, 1] (take_hip_shutter_pose) -> {"lookfrom", "lookat",

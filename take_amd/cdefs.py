@@ -306,6 +306,22 @@ SHUTTER_PROTOTYPES = {
 }
 
 
+class TakeMeshMotion(C.Structure):
+    """take_hip_render_shutter_meshes*: the vertex arrays of one mesh at the marked (0) and at the current frame (1), in
+    host memory, or all in device memory under TAKE_MESH_DEVICE_ARRAYS; normals: both or neither"""
+    _fields_ = [("mesh", C.c_int32), ("flags", C.c_int32), ("positions0", C.c_void_p), ("positions1", C.c_void_p),
+                ("normals0", C.c_void_p), ("normals1", C.c_void_p)]
+
+
+SHUTTER_MESHES_PROTOTYPES = {
+    "take_hip_shutter_vertices": [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.POINTER(C.c_int32)],
+    "take_hip_shutter_vertices_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
+    "take_hip_render_shutter_meshes": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeShutter), C.POINTER(TakeMeshMotion), C.c_int32, C.c_void_p],
+    "take_hip_render_shutter_meshes_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.POINTER(TakeShutter), C.POINTER(TakeMeshMotion), C.c_int32, C.c_void_p,
+                                              C.c_void_p],
+}
+
+
 # the display transform (include/take_hip.h)
 TAKE_LUMINANCE_BINS, TAKE_LUMINANCE_SLOTS = 384, 386  # the bins, then [384] non-positive, [385] non-finite
 TAKE_TONEMAP_LINEAR, TAKE_TONEMAP_REINHARD, TAKE_TONEMAP_ACES = 0, 1, 2

@@ -353,10 +353,48 @@ int take_hip_scene_set_instance_transforms(TakeScene *ts, const double *xforms, 
     HIP_TRY(hipMemcpy(d_xforms.p, xforms, d_xforms.bytes(), hipMemcpyHostToDevice));
     return set_instance_transforms(ts, d_xforms, n);
 }
-// New vertices for meshes of a resident scene (include/take_hip.h): the arguments that need no scene, the device, the
-// arguments against the scene, what the path does not support; then every side staged and every side committed.
-// two_level_too: take_hip_scene_update_meshes — a scene with placements takes update_two_level_meshes_device, any other
-// scene the one path both symbols share.
+// New vertices for meshes of a resident scene (include/take_hip.h), in two parts: what the path does not support of a
+// scene (check_update_scene), and the core that stages every side and commits every side (commit_mesh_update).
+// update_meshes, below them, is the public symbols: the arguments that need no scene, the device, the arguments against
+// the scene, then both parts and the mark's bookkeeping.  two_level_too: take_hip_scene_update_meshes — a scene with
+// placements takes update_two_level_meshes_device, any other scene the one path both symbols share.
+// What the update does not support, in its words (take_hip_render_shutter_meshes* refuses the same):
+static int check_update_scene(const TakeScene *ts, bool two_level_too) {
+    const bool two_level = ts->n_placements > 0;
+    if (two_level && !two_level_too) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (take_hip_scene_update_meshes moves the vertices of its meshes)");
+    if (ts->flattened) return fail(TAKE_E_INVALID, "unsupported: the scene was flattened from instances");
+    const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.nodes == NodeFormat::Q8; });
+    if (q8) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_NODES=q8");
+    if (two_level) {
+        if (const int rc = check_repose(ts, ts->n_placements)) return rc;  // (TAKE_HIP_BRAID > 1: "unsupported")
+        if (!ts->xforms.p || (int64_t)ts->xforms.n != 12 * ts->n_placements) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group");
+        if (on_primary(ts, [&](const auto &sc, const auto &) { return (int64_t)sc.prims.n - sc.host.blas_prims != (int64_t)ts->shape_face.n; }))
+            return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+    } else {
+        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
+        if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
+        if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.prims.n != ts->shape_face.n; }))
+            return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
+    }
+    return TAKE_OK;
+}
+static bool mesh_has_normals(const TakeScene *ts, int32_t mesh) {
+    return on_primary(ts, [&](const auto &sc, const auto &) { return (size_t)mesh < sc.host.meshes.size() && sc.host.meshes[mesh].nbase >= 0; });
+}
+// The core of an update (check_update_scene passed): every side staged from `in`, then every side committed.  A scene
+// with placements gets its top level under d_xforms; new_records: they are not the transforms its placement records
+// were made from (a slice of take_hip_render_shutter_meshes*), which are made again with it.  The mark, vertex tracking
+// and the current transforms are the caller's business.
+static int commit_mesh_update(TakeScene *ts, const MeshUpdateInputs &in, const double *d_xforms, bool new_records) {
+    if (ts->n_placements > 0)
+        return stage_then_commit<ProtoUpdateStage>(ts, [&](const auto &sc, auto &stage) {
+            return update_two_level_meshes_device(sc, in, ts->mesh_vertices, ts->shape_face.p, d_xforms, ts->max_leaf, new_records, stage);
+        });
+    const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
+    return stage_then_commit<MeshUpdateStage>(ts, [&](const auto &sc, auto &stage) {
+        return update_mesh_vertices_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, stage);
+    });
+}
 static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n_updates, bool two_level_too) {
     if (!ts || !updates) return fail(TAKE_E_INVALID, "null argument");
     if (n_updates <= 0) return fail(TAKE_E_INVALID, "n_updates must be positive");
@@ -379,25 +417,9 @@ static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n
             const TakeMeshUpdate &u = updates[i];
             const std::string who = "update " + std::to_string(i) + ": ";
             if ((size_t)u.mesh >= ts->mesh_vertices.size()) return fail(TAKE_E_INVALID, who + "mesh index out of range");
-            const bool has_normals = on_primary(ts, [&](const auto &sc, const auto &) { return (size_t)u.mesh < sc.host.meshes.size() && sc.host.meshes[u.mesh].nbase >= 0; });
-            if (u.normals && !has_normals) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
+            if (u.normals && !mesh_has_normals(ts, u.mesh)) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
         }
-        const bool two_level = ts->n_placements > 0;
-        if (two_level && !two_level_too) return fail(TAKE_E_INVALID, "unsupported: a two-level scene (take_hip_scene_update_meshes moves the vertices of its meshes)");
-        if (ts->flattened) return fail(TAKE_E_INVALID, "unsupported: the scene was flattened from instances");
-        const bool q8 = ts->node_knob == "q8" || on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.nodes == NodeFormat::Q8; });
-        if (q8) return fail(TAKE_E_INVALID, "unsupported: the scene was built under TAKE_HIP_NODES=q8");
-        if (two_level) {
-            if (const int rc = check_repose(ts, ts->n_placements)) return rc;  // (TAKE_HIP_BRAID > 1: "unsupported")
-            if (!ts->xforms.p || (int64_t)ts->xforms.n != 12 * ts->n_placements) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group");
-            if (on_primary(ts, [&](const auto &sc, const auto &) { return (int64_t)sc.prims.n - sc.host.blas_prims != (int64_t)ts->shape_face.n; }))
-                return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
-        } else {
-            if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.trace.two_level; })) return fail(TAKE_E_INVALID, "unsupported: a two-level scene");
-            if (!ts->shape_face.p) return fail(TAKE_E_INVALID, "unsupported: the scene is a replica of a scene group, or has no shapes");
-            if (on_primary(ts, [&](const auto &sc, const auto &) { return sc.prims.n != ts->shape_face.n; }))
-                return fail(TAKE_E_INVALID, "unsupported: the scene does not have one primitive record per shape");
-        }
+        if (const int rc = check_update_scene(ts, two_level_too)) return rc;
         TAKE_ON_DEVICE(ts);
         MeshUpdateInputs in;
         int rc = in.upload(ts->mesh_vertices, updates, n_updates);
@@ -410,16 +432,7 @@ static int update_meshes(TakeScene *ts, const TakeMeshUpdate *updates, int32_t n
             rc = ts->f64() ? copy_marked_geometry(ts->d, kept.geom_d, kept.inst_first) : copy_marked_geometry(ts->f, kept.geom_f, kept.inst_first);
             if (rc) return rc;
         }
-        if (two_level) {
-            rc = stage_then_commit<ProtoUpdateStage>(ts, [&](const auto &sc, auto &stage) {
-                return update_two_level_meshes_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->xforms.p, ts->max_leaf, stage);
-            });
-        } else {
-            const bool compressed_ok = compressed_nodes_supported() && ts->node_knob != "wide", compressed_forced = ts->node_knob == "q16";
-            rc = stage_then_commit<MeshUpdateStage>(ts, [&](const auto &sc, auto &stage) {
-                return update_mesh_vertices_device(sc, in, ts->mesh_vertices, ts->shape_face.p, ts->max_leaf, compressed_ok, compressed_forced, ts->num_cus, stage);
-            });
-        }
+        rc = commit_mesh_update(ts, in, ts->xforms.p, false);
         if (rc) return rc;
         ts->mark.updated = true;
         if (keep) ts->mark.geom_f = std::move(kept.geom_f), ts->mark.geom_d = std::move(kept.geom_d), ts->mark.inst_first = std::move(kept.inst_first);
@@ -561,7 +574,9 @@ int take_hip_render_motion(TakeScene *ts, const TakeRenderOpts *opts, const Take
 // ------------------------------------------------------------------------------------------------ motion blur
 // A render over a shutter between the marked and the current frame (include/take_hip.h): the plan, the
 // pose at a time (tk_shutter.h; launched by tk_render.hip's shutter_pose_device) and the loop over the slices, which
-// re-poses through set_instance_transforms' own path and renders through take_hip_render_accumulate's.
+// re-poses through set_instance_transforms' own path and renders through take_hip_render_accumulate's.  With deforming
+// meshes (take_hip_render_shutter_meshes*) the same loop also lerps their vertices per slice
+// (tk_shutter.h: k_shutter_vertices; tk_render.hip: shutter_vertices_launch) and takes them in through commit_mesh_update.
 static int check_shutter(const TakeShutter &s) {
     if (!std::isfinite(s.open) || !std::isfinite(s.close) || !(0.0 <= s.open && s.open <= s.close && s.close <= 1.0))
         return fail(TAKE_E_INVALID, "the shutter must have 0 <= open <= close <= 1");
@@ -620,15 +635,102 @@ int take_hip_shutter_pose(TakeScene *ts, double t, TakeCamera *camera_out, doubl
 static void pose_camera(TakeScene *ts, const TakeCamera &cam) {
     for_each_side(ts, [&](auto &sc) { return make_camera(cam, sc.host.cam), sc.dev.cam = sc.host.cam, TAKE_OK; });
 }
-int take_hip_render_shutter_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *d_rgb_out, void *stream) {
+// take_hip_render_shutter_meshes* (DESIGN.md §4r): what it refuses of its motions without a scene
+static int check_motions(const TakeMeshMotion *motions, int32_t n) {
+    if (n < 0) return fail(TAKE_E_INVALID, "n must not be negative");
+    if (n > 0 && !motions) return fail(TAKE_E_INVALID, "null argument");
+    std::vector<int32_t> ids((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const TakeMeshMotion &m = motions[i];
+        const std::string who = "motion " + std::to_string(i) + ": ";
+        if (m.mesh < 0) return fail(TAKE_E_INVALID, who + "mesh index out of range");
+        if (m.flags & ~TAKE_MESH_DEVICE_ARRAYS) return fail(TAKE_E_INVALID, who + "unknown flag bits");
+        if (!m.positions0 || !m.positions1) return fail(TAKE_E_INVALID, who + "positions0 or positions1 is null");
+        if (!m.normals0 != !m.normals1) return fail(TAKE_E_INVALID, who + "normals0 and normals1 must be given together");
+        ids[i] = m.mesh;
+    }
+    std::sort(ids.begin(), ids.end());
+    for (int32_t i = 1; i < n; i++)
+        if (ids[i] == ids[i - 1]) return fail(TAKE_E_INVALID, "mesh " + std::to_string(ids[i]) + " appears more than once");
+    return TAKE_OK;
+}
+// The deforming meshes of a render over the shutter, in device memory: per array of a motion its two ends (host arrays
+// uploaded once, device arrays borrowed) and the buffer the slices' vertices are made in; the update's inputs over
+// those buffers — the same for every slice — and over the current ends, which put the scene back.
+struct SliceMeshes {
+    struct Array {
+        const double *a, *b;
+        double *out;
+        int64_t n;
+    };
+    std::vector<DevBuf<double>> owned;
+    std::vector<Array> arrays;
+    MeshUpdateInputs slice, current;
+    DevBuf<int> moved;
+    int make(const TakeScene *ts, const TakeMeshMotion *motions, int32_t n) {
+        const char *nomem = "out of device memory for the meshes' vertices over the shutter";
+        std::vector<TakeMeshUpdate> to_slice((size_t)n), to_current((size_t)n);
+        auto resident = [&](const double *src, bool device, size_t words, const double *&dst) {
+            if (device) return dst = src, (int)TAKE_OK;
+            owned.emplace_back();
+            if (owned.back().alloc(std::max<size_t>(words, 1)) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+            if (words) HIP_TRY(hipMemcpy(owned.back().p, src, words * sizeof(double), hipMemcpyHostToDevice));
+            return dst = owned.back().p, (int)TAKE_OK;
+        };
+        for (int32_t i = 0; i < n; i++) {
+            const TakeMeshMotion &m = motions[i];
+            const size_t words = 3 * (size_t)ts->mesh_vertices[m.mesh];
+            const bool device = (m.flags & TAKE_MESH_DEVICE_ARRAYS) != 0;
+            const double *ends[2][2] = {{m.positions0, m.positions1}, {m.normals0, m.normals1}};
+            const double *out[2] = {nullptr, nullptr}, *now[2] = {nullptr, nullptr};
+            for (int k = 0; k < 2; k++) {
+                if (!ends[k][0]) continue;
+                Array arr{nullptr, nullptr, nullptr, (int64_t)words};
+                if (const int rc = resident(ends[k][0], device, words, arr.a)) return rc;
+                if (const int rc = resident(ends[k][1], device, words, arr.b)) return rc;
+                owned.emplace_back();
+                if (owned.back().alloc(std::max<size_t>(words, 1)) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+                arr.out = owned.back().p, out[k] = arr.out, now[k] = arr.b;
+                arrays.push_back(arr);
+            }
+            to_slice[i] = TakeMeshUpdate{m.mesh, TAKE_MESH_DEVICE_ARRAYS, out[0], out[1]};
+            to_current[i] = TakeMeshUpdate{m.mesh, TAKE_MESH_DEVICE_ARRAYS, now[0], now[1]};
+        }
+        if (moved.alloc(1) != hipSuccess) return fail(TAKE_E_NOMEM, nomem);
+        if (const int rc = slice.upload(ts->mesh_vertices, to_slice.data(), n)) return rc;
+        return current.upload(ts->mesh_vertices, to_current.data(), n);
+    }
+    // every array at time t -> its buffer (the default stream, as the update that reads them next); any: some vertex is
+    // not the current one bit for bit
+    int lerp(double t, int num_cus, bool &any) {
+        HIP_TRY(hipMemsetAsync(moved.p, 0, sizeof(int), nullptr));
+        for (const Array &x : arrays) shutter_vertices_launch(x.a, x.b, x.n, t, x.out, moved.p, num_cus, nullptr);
+        HIP_TRY(hipGetLastError());
+        int flag = 0;
+        HIP_TRY(hipMemcpy(&flag, moved.p, sizeof(int), hipMemcpyDeviceToHost));
+        any = flag != 0;
+        return TAKE_OK;
+    }
+};
+// The one loop over the slices: take_hip_render_shutter_device (n_motions = 0) and take_hip_render_shutter_meshes_device.
+static int render_over_shutter(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n_motions,
+                               void *d_rgb_out, void *stream) {
     if (!ts || !opts || !d_rgb_out) return fail(TAKE_E_INVALID, "null argument");
     int32_t K = 0;
     if (int rc = take_hip_shutter_plan(opts->spp, shutter, &K, nullptr, nullptr)) return rc;
-    const int nd = check_device();
-    if (nd < 0) return nd;
-    TAKE_ON_DEVICE(ts);
-    if (const int rc = check_shutter_scene(ts)) return rc;
     try {
+        if (int rc = check_motions(motions, n_motions)) return rc;
+        const int nd = check_device();
+        if (nd < 0) return nd;
+        TAKE_ON_DEVICE(ts);
+        for (int32_t i = 0; i < n_motions; i++) {
+            const std::string who = "motion " + std::to_string(i) + ": ";
+            if ((size_t)motions[i].mesh >= ts->mesh_vertices.size()) return fail(TAKE_E_INVALID, who + "mesh index out of range");
+            if (motions[i].normals0 && !mesh_has_normals(ts, motions[i].mesh)) return fail(TAKE_E_INVALID, who + "normals given for a mesh without vertex normals");
+        }
+        if (const int rc = check_shutter_scene(ts)) return rc;
+        if (n_motions > 0)
+            if (const int rc = check_update_scene(ts, true)) return rc;
         std::vector<int32_t> first((size_t)K + 1);
         std::vector<double> time((size_t)K);
         take_hip_shutter_plan(opts->spp, shutter, &K, first.data(), time.data());
@@ -647,28 +749,51 @@ int take_hip_render_shutter_device(TakeScene *ts, const TakeRenderOpts *opts, co
             if (const int rc = shutter_pose_device(ts->mark.xforms.p, ts->xforms.p, time, n, posed, first_bad, moved)) return rc;
             if (first_bad >= 0) return bad_pose(first_bad, n);
         }
+        // the deforming meshes: both ends and the slices' buffers in device memory before the first slice (the default
+        // stream reads them: first whatever `stream` still has to write into device arrays)
+        SliceMeshes meshes;
+        if (n_motions > 0) {
+            if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+            if (const int rc = meshes.make(ts, motions, n_motions)) return rc;
+        }
         // the slices; whatever happens from here on, the scene goes back to its current pose.  `at`: the transforms the
         // placements are under — a slice whose pose is the current transforms bit for bit is rendered under those, and
-        // placements that did not move since the mark are never re-posed at all
+        // placements that did not move since the mark are never re-posed at all.  `deformed`: the meshes are not at
+        // their current vertices — a slice whose vertices are the current ones bit for bit, in a scene that is at them,
+        // runs no update, and one that runs it makes the placements' records and the top level for its pose with it
         const bool restart_needed = ts->acc_restart_needed;  // (a re-pose sets it; a one-shot render leaves it alone, and so does this call)
         const double *at = ts->xforms.p;
+        bool deformed = false, updated = false;
         auto repose_to = [&](const double *x) {
             if (x == at) return (int)TAKE_OK;
             const int rc = stage_then_commit<ReposeStage>(ts, [&](const auto &sc, auto &stage) { return repose_two_level_device(sc, x, n, stage); });
             if (!rc) at = x;
             return rc;
         };
+        auto update_to = [&](const MeshUpdateInputs &in, const double *x, bool now_deformed) {
+            const int rc = commit_mesh_update(ts, in, x, x != at);
+            if (!rc) at = x, deformed = now_deformed, updated = true;
+            return rc;
+        };
         int rc = TAKE_OK;
         for (int32_t k = 0; k < K && !rc; k++) {
             pose_camera(ts, cams[k]);
-            if (n > 0) rc = repose_to(moved[k] ? posed.p + 12 * n * (int64_t)k : ts->xforms.p);
+            const double *x = n > 0 && moved[k] ? posed.p + 12 * n * (int64_t)k : ts->xforms.p;
+            bool any = false;
+            if (n_motions > 0) rc = meshes.lerp(time[k], ts->num_cus, any);
+            if (!rc && (any || deformed)) {
+                rc = update_to(meshes.slice, x, any);
+                if (rc) rc = fail(rc, "slice " + std::to_string(k) + ": " + g_error);
+            } else if (!rc && n > 0) {
+                rc = repose_to(x);
+            }
             TakeRenderOpts o = *opts;
             o.spp = first[k + 1] - first[k];
             if (!rc) rc = render_scene(ts, o, d_rgb_out, (hipStream_t)stream, first[k], k > 0, k + 1 == K);
         }
         const std::string why = g_error;
         pose_camera(ts, ts->camera);
-        const int back = n > 0 ? repose_to(ts->xforms.p) : (int)TAKE_OK;
+        const int back = updated ? update_to(meshes.current, ts->xforms.p, false) : (n > 0 ? repose_to(ts->xforms.p) : (int)TAKE_OK);
         ts->acc_samples = 0, ts->acc_restart_needed = restart_needed || back != TAKE_OK;
         if (rc) return fail(rc, why);
         if (back) return fail(back, "the render is complete, but putting the scene back at its current pose failed: " + g_error);
@@ -677,7 +802,9 @@ int take_hip_render_shutter_device(TakeScene *ts, const TakeRenderOpts *opts, co
         return fail(TAKE_E_NOMEM, "out of host memory while rendering over the shutter");
     }
 }
-int take_hip_render_shutter(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *rgb_out_host) {
+// the host entries: the image in device memory, then copied out
+static int render_shutter_to_host(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n_motions,
+                                  void *rgb_out_host) {
     if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
     int32_t K = 0;
     if (int rc = take_hip_shutter_plan(opts->spp, shutter, &K, nullptr, nullptr)) return rc;
@@ -690,8 +817,68 @@ int take_hip_render_shutter(TakeScene *ts, const TakeRenderOpts *opts, const Tak
     if (bytes == 0) return TAKE_OK;
     DevBuf<char> img;
     if (img.alloc(bytes) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the image");
-    if (int rc = take_hip_render_shutter_device(ts, opts, shutter, img.p, nullptr)) return rc;
+    if (int rc = render_over_shutter(ts, opts, shutter, motions, n_motions, img.p, nullptr)) return rc;
     HIP_TRY(hipMemcpy(rgb_out_host, img.p, bytes, hipMemcpyDeviceToHost));
+    return TAKE_OK;
+}
+int take_hip_render_shutter_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *d_rgb_out, void *stream) {
+    return render_over_shutter(ts, opts, shutter, nullptr, 0, d_rgb_out, stream);
+}
+int take_hip_render_shutter(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, void *rgb_out_host) {
+    return render_shutter_to_host(ts, opts, shutter, nullptr, 0, rgb_out_host);
+}
+int take_hip_render_shutter_meshes_device(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n,
+                                          void *d_rgb_out, void *stream) {
+    return render_over_shutter(ts, opts, shutter, motions, n, d_rgb_out, stream);
+}
+int take_hip_render_shutter_meshes(TakeScene *ts, const TakeRenderOpts *opts, const TakeShutter *shutter, const TakeMeshMotion *motions, int32_t n,
+                                   void *rgb_out_host) {
+    if (!ts || !opts || !rgb_out_host) return fail(TAKE_E_INVALID, "null argument");
+    int32_t K = 0;
+    if (int rc = take_hip_shutter_plan(opts->spp, shutter, &K, nullptr, nullptr)) return rc;
+    try {
+        if (int rc = check_motions(motions, n)) return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(TAKE_E_NOMEM, "out of host memory while rendering over the shutter");
+    }
+    return render_shutter_to_host(ts, opts, shutter, motions, n, rgb_out_host);
+}
+// The vertices of a mesh at a time of the shutter, without a scene (include/take_hip.h; tk_shutter.h: k_shutter_vertices)
+static int check_shutter_vertices(const void *a, const void *b, int64_t n, double t, const void *out) {
+    if (!a || !b || !out) return fail(TAKE_E_INVALID, "null argument");
+    if (n <= 0) return fail(TAKE_E_INVALID, "n must be positive");
+    if (!(t >= 0.0 && t <= 1.0)) return fail(TAKE_E_INVALID, "t must be in [0, 1]");
+    return TAKE_OK;
+}
+int take_hip_shutter_vertices_device(const double *d_a, const double *d_b, int64_t n, double t, double *d_out, int32_t *moved_host, void *stream) {
+    if (int rc = check_shutter_vertices(d_a, d_b, n, t, d_out)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    int device = 0, num_cus = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || num_cus <= 0) num_cus = 256;
+    DevBuf<int> moved;
+    if (moved.alloc(1) != hipSuccess) return fail(TAKE_E_NOMEM, "out of device memory for the vertices at a time of the shutter");
+    HIP_TRY(hipMemsetAsync(moved.p, 0, sizeof(int), (hipStream_t)stream));
+    shutter_vertices_launch(d_a, d_b, n, t, d_out, moved.p, num_cus, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, moved.p, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (moved_host) *moved_host = flag;
+    return TAKE_OK;
+}
+int take_hip_shutter_vertices(const double *a, const double *b, int64_t n, double t, double *out, int32_t *moved) {
+    if (int rc = check_shutter_vertices(a, b, n, t, out)) return rc;
+    const int nd = check_device();
+    if (nd < 0) return nd;
+    DevBuf<double> d_a, d_b, d_out;
+    if (d_a.alloc((size_t)n) != hipSuccess || d_b.alloc((size_t)n) != hipSuccess || d_out.alloc((size_t)n) != hipSuccess)
+        return fail(TAKE_E_NOMEM, "out of device memory for the vertices at a time of the shutter");
+    HIP_TRY(hipMemcpy(d_a.p, a, d_a.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_b.p, b, d_b.bytes(), hipMemcpyHostToDevice));
+    if (int rc = take_hip_shutter_vertices_device(d_a.p, d_b.p, n, t, d_out.p, moved, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(out, d_out.p, d_out.bytes(), hipMemcpyDeviceToHost));
     return TAKE_OK;
 }
 

@@ -838,7 +838,7 @@ template int update_mesh_vertices_device<double>(const SceneT<double> &, const M
 // ---- take_hip_scene_update_meshes on a two-level scene
 template <class R>
 int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
-                                   const double *d_xforms, int max_leaf, ProtoUpdateStage<R> &out) {
+                                   const double *d_xforms, int max_leaf, bool new_records, ProtoUpdateStage<R> &out) {
     using namespace lbvh;
     const HostScene<R> &h = sc.host;
     const int n_inst = (int)sc.inst_trace.n, n_protos = (int)h.blas_prim_first.size();
@@ -997,12 +997,24 @@ int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &
     }
 
     // 7. the placements: records as they are — transforms, materials, tags, shape bases — with the roots, and the
-    // moved prototypes' grids, of the new node array
+    // moved prototypes' grids, of the new node array.  new_records (a slice of take_hip_render_shutter_meshes*, whose
+    // d_xforms are not the transforms the records were made from): the re-pose's records under d_xforms instead
     {
         DevBuf<int32_t> inst_proto;
         DevBuf<ProtoTarget> d_target;
         HIP_TRY(b.inst_trace.alloc((size_t)n_inst));
-        HIP_TRY(hipMemcpyAsync(b.inst_trace.p, sc.inst_trace.p, sc.inst_trace.bytes(), hipMemcpyDeviceToDevice, stream));
+        if (new_records) {
+            FirstOffender<int> bad{INT32_MAX};
+            HIP_TRY(b.inst_shade.alloc((size_t)n_inst));
+            HIP_TRY(bad.arm());
+            hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), blk, 0, stream, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p, b.inst_trace.p,
+                               b.inst_shade.p, bad.cell.p);
+            HIP_TRY(bad.read());
+            HIP_TRY(hipGetLastError());
+            if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
+        } else {
+            HIP_TRY(hipMemcpyAsync(b.inst_trace.p, sc.inst_trace.p, sc.inst_trace.bytes(), hipMemcpyDeviceToDevice, stream));
+        }
         HIP_TRY(inst_proto.upload(h.placements.inst_proto));
         HIP_TRY(d_target.upload(target));
         hipLaunchKernelGGL(k_retarget_placements<R>, blocks_for(n_inst), blk, 0, stream, b.inst_trace.p, n_inst, inst_proto.p, d_target.p);
@@ -1019,6 +1031,7 @@ template <class R> int ProtoUpdateStage<R>::commit(SceneT<R> &sc) {
     if (built.qnodes.p) sc.qnodes = std::move(built.qnodes);
     else sc.nodes = std::move(built.nodes);
     sc.inst_trace = std::move(built.inst_trace);
+    if (built.inst_shade.p) sc.inst_shade = std::move(built.inst_shade);  // (new_records)
     if (new_lights) {
         sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
         h.lights = std::move(built.host.lights), h.light_pmf = std::move(built.host.light_pmf), h.light_cdf = std::move(built.host.light_cdf);
@@ -1031,9 +1044,9 @@ template <class R> int ProtoUpdateStage<R>::commit(SceneT<R> &sc) {
 template struct ProtoUpdateStage<float>;
 template struct ProtoUpdateStage<double>;
 template int update_two_level_meshes_device<float>(const SceneT<float> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, const double *, int,
-                                                   ProtoUpdateStage<float> &);
+                                                   bool, ProtoUpdateStage<float> &);
 template int update_two_level_meshes_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, const double *, int,
-                                                    ProtoUpdateStage<double> &);
+                                                    bool, ProtoUpdateStage<double> &);
 
 // ---- take_hip_scene_track_vertices: the marked geometry of a side, before a mesh update replaces its records
 template <class R> int copy_marked_geometry(const SceneT<R> &sc, DevBuf<R> &words, DevBuf<int32_t> &inst_first) {

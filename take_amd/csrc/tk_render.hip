@@ -1078,6 +1078,18 @@ int shutter_pose_device(const double *d_marked, const double *d_current, const s
     std::copy(words_h.begin() + 1, words_h.end(), moved.begin());
     return TAKE_OK;
 }
+// The launch alone: the 16-byte path where the three addresses agree mod 16 (one element in front of it where they are
+// 8 mod 16), the scalar loop for everything otherwise; a grid for the device, never for n.
+void shutter_vertices_launch(const double *d_a, const double *d_b, int64_t n, double t, double *d_out, int *d_moved, int num_cus, hipStream_t stream) {
+    if (n <= 0) return;
+    const uintptr_t pa = (uintptr_t)d_a & 15, pb = (uintptr_t)d_b & 15, po = (uintptr_t)d_out & 15;
+    const bool vec = pa == pb && pb == po && (pa == 0 || pa == 8);
+    const int head = vec && pa == 8 ? 1 : 0;
+    const int64_t pairs = vec ? (n - head) / 2 : 0;
+    const int64_t lanes = std::max<int64_t>(pairs, n - 2 * pairs);
+    const int64_t blocks = std::min<int64_t>((lanes + SHUTTER_BLOCK - 1) / SHUTTER_BLOCK, (int64_t)std::max(num_cus, 1) * SHUTTER_BLOCKS_PER_CU);
+    hipLaunchKernelGGL(k_shutter_vertices, dim3((unsigned)blocks), dim3(SHUTTER_BLOCK), 0, stream, d_a, d_b, n, head, pairs, t, d_out, d_moved);
+}
 
 }  // namespace tk_host
 

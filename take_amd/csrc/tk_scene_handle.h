@@ -347,6 +347,10 @@ TakeCamera shutter_camera(const TakeCamera &marked, const TakeCamera &current, d
 // none; moved[slice] = 0 where the slice's pose is the current transforms bit for bit (no re-pose needed), 1 elsewhere
 int shutter_pose_device(const double *d_marked, const double *d_current, const std::vector<double> &times, int64_t n, DevBuf<double> &posed, int64_t &first_bad,
                         std::vector<int> &moved);
+// take_hip_shutter_vertices* / take_hip_render_shutter_meshes* (tk_shutter.h: k_shutter_vertices): n doubles of device
+// memory, d_a (scene time 0) -> d_b (scene time 1), at time t -> d_out; *d_moved — a word of device memory, 0 before —
+// becomes 1 where any of them is not d_b's bit for bit.  Launches on `stream` and returns; n <= 0 launches nothing.
+void shutter_vertices_launch(const double *d_a, const double *d_b, int64_t n, double t, double *d_out, int *d_moved, int num_cus, hipStream_t stream);
 
 // ---- defined in tk_api.hip
 // what take_hip_render_adaptive* refuse of their options (null: the defaults), needing neither scene nor device
@@ -450,6 +454,9 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
 // transforms — by the resident path the re-pose takes, and the placements retargeted (k_retarget_placements).  The
 // scene keeps its node format.  Built into `out` (stage_then_commit); commit() only moves.  Errors: as
 // update_mesh_vertices_device, the trees being the moved prototypes' and the top-level one, the depth both levels'.
+// new_records (a slice of take_hip_render_shutter_meshes*): d_xforms are NOT the transforms the placements' records were
+// made from — the records are made again under them (k_placement_records, the re-pose's step 1 and its refusal), so
+// that the one top-level rebuild serves both the new vertices and the new pose.
 template <class R> struct ProtoUpdateStage {
     // built.prims (all records), qnodes or nodes, inst_trace, normals / lights and their tables when they change
     SceneT<R> built;
@@ -463,6 +470,6 @@ template <class R> struct ProtoUpdateStage {
 };
 template <class R>
 int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
-                                   const double *d_xforms, int max_leaf, ProtoUpdateStage<R> &out);
+                                   const double *d_xforms, int max_leaf, bool new_records, ProtoUpdateStage<R> &out);
 
 }  // namespace tk_host

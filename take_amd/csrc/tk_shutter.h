@@ -3,7 +3,8 @@
 // the entry-by-entry lerp of the two — the matrix motion transform of Embree and OptiX: a rotation moves along its
 // chord, not its arc.  TK_HD and written once, as tk_lens.h: k_shutter_pose runs it on the device, tk_render.hip's
 // shutter_camera calls the same text for the camera, tests/shutter_host runs it on the host, tests/shutter_ref.py restates it in numpy.  Every
-// + - * is one operation of double in the order written (-ffp-contract=off).
+// + - * is one operation of double in the order written (-ffp-contract=off).  k_shutter_vertices runs the same lerp over
+// the vertex arrays of a deforming mesh (tests/shutter_deform_host, tests/shutter_deform_ref.py).
 #pragma once
 #include <cstdint>
 
@@ -53,6 +54,39 @@ __global__ void __launch_bounds__(SHUTTER_BLOCK) k_shutter_pose(const double *__
     for (int e = 0; e < 12; e++) posed[12 * lane + e] = m[e], same = same && __double_as_longlong(m[e]) == __double_as_longlong(b[e]);
     if (!ok) atomicMin(bad, (int)lane);
     if (!same) atomicOr(&moved[k], 1);
+}
+
+// The vertices of a deforming mesh at scene time t (take_hip_render_shutter_meshes*): n doubles — the
+// 3 n_vertices coordinates of its positions, or of its vertex normals —, a (the marked frame) -> b (the current one),
+// out[e] = shutter_lerp(t, a[e], b[e]).  Nothing is looked at: a value that is not finite passes through, a lerped normal
+// is not renormalised.  A streaming kernel: per lane and step 16 bytes in from each side and 16 out, over a grid sized
+// to the device (SHUTTER_BLOCKS_PER_CU blocks per CU) that strides over the array.  `head` (0 or 1) elements come before
+// the `pairs` 16-byte-aligned pairs — the launch finds both from the three addresses, pairs = 0 where they do not agree
+// mod 16 — and n - head - 2 pairs after them; those take the scalar loop.  out may be a or b: every lane reads its
+// elements before it writes them.  *moved (0 before) becomes 1 where any out[e] is not b[e] bit for bit: the flags are
+// reduced inside the wave, and a wave adds at most one atomic.
+constexpr int SHUTTER_BLOCKS_PER_CU = 8;
+__global__ void __launch_bounds__(SHUTTER_BLOCK) k_shutter_vertices(const double *a, const double *b, int64_t n, int head, int64_t pairs, double t, double *out,
+                                                                    int *moved) {
+    const int64_t lane = (int64_t)blockIdx.x * SHUTTER_BLOCK + threadIdx.x, step = (int64_t)gridDim.x * SHUTTER_BLOCK;
+    const double2 *a2 = (const double2 *)(a + head), *b2 = (const double2 *)(b + head);
+    double2 *out2 = (double2 *)(out + head);
+    bool differs = false;
+    for (int64_t i = lane; i < pairs; i += step) {
+        const double2 x = a2[i], y = b2[i];
+        double2 r;
+        r.x = shutter_lerp(t, x.x, y.x), r.y = shutter_lerp(t, x.y, y.y);
+        out2[i] = r;
+        differs = differs || __double_as_longlong(r.x) != __double_as_longlong(y.x) || __double_as_longlong(r.y) != __double_as_longlong(y.y);
+    }
+    const int64_t tail = head + 2 * pairs, rest = head + (n - tail);
+    for (int64_t i = lane; i < rest; i += step) {
+        const int64_t e = i < head ? i : tail + (i - head);
+        const double y = b[e], r = shutter_lerp(t, a[e], y);
+        out[e] = r;
+        differs = differs || __double_as_longlong(r) != __double_as_longlong(y);
+    }
+    if (__any(differs) && (threadIdx.x & 63) == 0) atomicOr(moved, 1);
 }
 #endif
 
