@@ -1,10 +1,11 @@
 // tk_build.hip — the host driver of the device LBVH builder: the records and trees of one side of a new scene made on
 // the device from the caller's arrays (build_side_on_device, declared in tk_scene_handle.h; tk_create.hip's upload_scene
-// calls it), and the top-level half of it entered again for a resident scene whose placements get new transforms
-// (repose_two_level_device; tk_api.hip's take_hip_scene_set_instance_transforms calls it), and creation's tail entered
-// again for a resident scene whose meshes get new vertices (update_mesh_vertices_device;
-// take_hip_scene_set_mesh_vertices calls it), and both joined for the meshes of a resident two-level scene
-// (update_two_level_meshes_device; take_hip_scene_update_meshes calls it).  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
+// calls it), and the three drivers that tk_scene_update.hip stages a change of a resident scene with: the top-level half
+// of the build entered again for new transforms of the placements (repose_two_level_device), creation's tail entered
+// again for new vertices (update_mesh_vertices_device), and both joined for the meshes of a two-level scene
+// (update_two_level_meshes_device).  What they share with each other and with the fresh build is one step each, in the
+// anonymous namespace: prototype_pass, top_level_resident, assemble_resident_nodes, placement_records,
+// update_shape_records, commit_normals_and_lights.  The only unit that compiles the kernels of tk_build_gpu.h, and rocPRIM with them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "take_hip.h"
@@ -394,6 +396,27 @@ template <class R> int finish_top_level(DeviceTree &top, int proto_depth, int n_
     top.order.release();
     return TAKE_OK;
 }
+// The prototype pass, of a fresh build and of an update alike.  In: recs, a prototype's nf records in FACE order (the
+// caller's to free).  Out: t — boxes, tree, the float nodes cut to size (the collapse allocates a node per leaf and uses
+// about a third; they wait for the assembly), `order` released — and the records in its leaf order at dst, their place
+// in the scene's record array.  scene_ord: six ints of scratch.  Any verdict but Built: nothing else was made.
+template <class R>
+int prototype_pass(const PrimRec<R> *recs, int nf, int leaf_size, PrimRec<R> *dst, DevBuf<int> &scene_ord, BuildMemory &mem, DeviceTree &t, BuildVerdict &why) {
+    using namespace lbvh;
+    DevBuf<Box> pb;
+    HIP_TRY(pb.alloc(nf));
+    HIP_TRY(reset_bounds(scene_ord));
+    span_boxes(recs, nf, pb.p, scene_ord);
+    const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t, why);
+    if (rt || why != BuildVerdict::Built) return rt;
+    hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), dim3(BLK), 0, nullptr, recs, t.order.p, nf, dst);
+    DevBuf<Node4<float>> cut;
+    HIP_TRY(cut.alloc((size_t)t.n_nodes));
+    HIP_TRY(hipMemcpy(cut.p, t.nodes.p, cut.bytes(), hipMemcpyDeviceToDevice));
+    t.nodes = std::move(cut);
+    t.order.release();
+    return TAKE_OK;
+}
 
 // BVH build on the device of a two-level scene (TakeInstance placements, TAKE_INSTANCES_TWO_LEVEL): the scene
 // build_host_trees makes, with LBVH trees.  In: sc.prims = the shapes' records in shape order (possibly none),
@@ -402,8 +425,8 @@ template <class R> int finish_top_level(DeviceTree &top, int proto_depth, int n_
 // sc.qnodes or sc.nodes = the top-level tree's nodes, then each prototype's, child words global; the placements'
 // root_child and grid; stats.  Any verdict but Built is for the whole scene: a tree of fewer than two leaves (a
 // one-face prototype) or too deep a stack over both levels.
-//   1. per distinct prototype, one pass: k_make_proto_prims -> k_prim_boxes -> build_tree_device; its records go
-//      straight to their place behind the shapes' records, its float nodes wait (cut to size) for step 4;
+//   1. per distinct prototype k_make_proto_prims, then prototype_pass: its records go straight to their place behind
+//      the shapes' records, its float nodes wait for step 4;
 //   2. k_placement_boxes / k_placement_pad: the placements' boxes behind the shapes' boxes (host formula beyond 4e8
 //      vertex transforms, placement_box);
 //   3. the top-level tree over both, ONE entry per leaf whatever max_leaf is (a placement is a leaf of its own, and
@@ -441,22 +464,11 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
     for (int k = 0; k < n_protos; k++) {
         const int mesh = plan.proto_mesh[k], nf = (int)d.meshes[mesh].n_faces;
         DevBuf<PrimRec<R>> recs;
-        DevBuf<Box> pb;
         HIP_TRY(recs.alloc(nf));
-        HIP_TRY(pb.alloc(nf));
-        HIP_TRY(reset_bounds(scene_ord));
         hipLaunchKernelGGL(k_make_proto_prims<R>, blocks_for(nf), blk, 0, stream, mesh_src(h, in, mesh), mesh, in.pos.p, sc.face_idx.p, nf, recs.p);
-        span_boxes(recs.p, nf, pb.p, scene_ord);
-        DeviceTree &t = protos[k];
-        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t, why);
+        const int rt = prototype_pass(recs.p, nf, leaf_size, prims.p + prim_base[k], scene_ord, mem, protos[k], why);
         if (rt || why != BuildVerdict::Built) return rt;
-        hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), blk, 0, stream, recs.p, t.order.p, nf, prims.p + prim_base[k]);
-        DevBuf<Node4<float>> cut;  // (the collapse allocates a node per leaf and uses about a third)
-        HIP_TRY(cut.alloc((size_t)t.n_nodes));
-        HIP_TRY(hipMemcpy(cut.p, t.nodes.p, cut.bytes(), hipMemcpyDeviceToDevice));
-        t.nodes = std::move(cut);
-        t.order.release();
-        proto_depth = std::max(proto_depth, t.depth);
+        proto_depth = std::max(proto_depth, protos[k].depth);
     }
     mem.sample("prototypes");
 
@@ -552,8 +564,7 @@ int build_two_level_device(SceneT<R> &sc, const TakeSceneDesc &d, const DeviceBu
 }
 
 
-// The top level of a RESIDENT two-level scene made again: what the re-pose (repose_two_level_device, its steps 2-4) and
-// the update of a scene's meshes (update_two_level_meshes_device) share.  In: `head`, the n_shapes records of the
+// The top level of a RESIDENT two-level scene made again, for the re-pose and for the update of a scene's meshes.  In: `head`, the n_shapes records of the
 // shapes, in any order; `prims`, the record array whose spans h.blas_prim_first / _count hold the prototypes' records;
 // the transforms (12 doubles per placement, device memory); proto_depth: the deepest prototype tree.  Out: `top`, its
 // leaf words final (instance words, single records), and the shapes' records in its leaf order at the head of dst
@@ -610,6 +621,126 @@ int top_level_resident(const HostScene<R> &h, const PrimRec<R> *head, const Prim
     return rt || why != BuildVerdict::Built ? unsupported(rt, why, "top-level tree") : TAKE_OK;
 }
 
+// "This tree's nodes at dst, its grid out", once per node format of a resident scene: compressed on the tree's own grid
+// (acc: quantise_tree_device's scratch, allocated by the first call; the inflation is not consulted — the scene keeps
+// its format, and the box tests stay conservative), or full-width, which has no grid and leaves the caller's as it is.
+int put_nodes(const DeviceTree &t, QNode4 *dst, DevBuf<double> &acc, float *grid_lo, float *grid_step) {
+    QGrid g;
+    double inflation = 1.0;
+    if (!acc.p) HIP_TRY(acc.alloc(2));
+    if (const int rq = quantise_tree_device(t, dst, acc, g, inflation)) return rq;
+    for (int a = 0; a < 3; a++) grid_lo[a] = g.lo[a], grid_step[a] = g.step[a];
+    return TAKE_OK;
+}
+template <class R> int put_nodes(const DeviceTree &t, Node4<R> *dst, DevBuf<double> &, float *, float *) { return wide_nodes_device(t, dst); }
+
+// Node assembly for a RESIDENT two-level scene in the node format it keeps (NodeT; old, nodes: its array and the new
+// one, out's): [new top level][prototype 0][prototype 1]...  Per prototype either its new tree (fresh[k]: put into
+// place, rebased to its nodes and records, its float nodes freed) or null = untouched: the scene's nodes copied and
+// rebased by their own node shift, primitive shift 0 — a run of untouched neighbours shares its shift: one copy, one
+// launch.  Out: everything of `out` but the depth (full-width nodes: the grid stays the scene's, which the traversal
+// does not read), and per prototype what its placements have to be told (target: k_retarget_placements).
+template <class R, class NodeT>
+int assemble_resident_nodes(const HostScene<R> &h, const DevBuf<NodeT> &old, const DeviceTree &top, const std::vector<DeviceTree *> &fresh, DevBuf<NodeT> &nodes,
+                            ResidentNodes<R> &out, std::vector<lbvh::ProtoTarget> &target) {
+    using namespace lbvh;
+    const int n_protos = (int)fresh.size();
+    const char *lost = "unsupported: the scene does not know where its prototypes are";
+    if ((int)h.blas_node_first.size() != n_protos || (int)h.blas_node_count.size() != n_protos || (int)h.blas_prim_first.size() != n_protos) return fail(TAKE_E_INVALID, lost);
+    hipStream_t stream = nullptr;
+    const dim3 blk(BLK);
+    out.node_first.assign(n_protos, 0), out.node_count = h.blas_node_count;
+    out.n_nodes = top.n_nodes;
+    for (int k = 0; k < n_protos; k++) {
+        if (fresh[k]) out.node_count[k] = fresh[k]->n_nodes;
+        out.node_first[k] = out.n_nodes, out.n_nodes += out.node_count[k];
+    }
+    out.blas_nodes = out.n_nodes - top.n_nodes;
+    if (out.n_nodes >= ((int64_t)1 << 31) || (uint64_t)out.n_nodes * sizeof(NodeT) >= (1ull << 32))
+        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
+    target.assign(n_protos, ProtoTarget{});
+    DevBuf<double> acc;
+    for (int a = 0; a < 3; a++) out.grid_lo[a] = h.grid_lo[a], out.grid_step[a] = h.grid_step[a];
+    HIP_TRY(nodes.alloc((size_t)out.n_nodes));
+    if (const int rc = put_nodes(top, nodes.p, acc, out.grid_lo, out.grid_step)) return rc;
+    for (int k = 0; k < n_protos;) {
+        const int32_t first = (int32_t)out.node_first[k];
+        if (fresh[k]) {
+            const int nk = (int)fresh[k]->n_nodes;
+            target[k].moved = 1, target[k].root = first, target[k].has_grid = std::is_same<NodeT, QNode4>::value;
+            if (const int rc = put_nodes(*fresh[k], nodes.p + first, acc, target[k].grid_lo, target[k].grid_step)) return rc;
+            hipLaunchKernelGGL(k_rebase<NodeT>, blocks_for(nk), blk, 0, stream, nodes.p + first, nk, first, (int32_t)h.blas_prim_first[k]);
+            fresh[k]->nodes.release();
+            k++;
+            continue;
+        }
+        int e = k;
+        int64_t run = 0;
+        while (e < n_protos && !fresh[e]) run += h.blas_node_count[e], e++;
+        const int64_t old_first = h.blas_node_first[k], shift = (int64_t)first - old_first;
+        for (int j = k; j < e; j++) target[j].shift = (int32_t)shift;
+        if (run > 0) {
+            if (old_first < 0 || old_first + run > h.stats.n_nodes) return fail(TAKE_E_INVALID, lost);
+            HIP_TRY(hipMemcpyAsync(nodes.p + first, old.p + old_first, (size_t)run * sizeof(NodeT), hipMemcpyDeviceToDevice, stream));
+            if (shift) hipLaunchKernelGGL(k_rebase<NodeT>, blocks_for(run), blk, 0, stream, nodes.p + first, (int)run, (int32_t)shift, 0);
+        }
+        k = e;
+    }
+    return TAKE_OK;
+}
+// ... the node type chosen, once, by the format the scene traverses (Q8 scenes are refused before any of this)
+template <class R> int assemble_resident_nodes(const SceneT<R> &sc, const DeviceTree &top, const std::vector<DeviceTree *> &fresh, ResidentNodes<R> &out, std::vector<lbvh::ProtoTarget> &target) {
+    return sc.trace.nodes == NodeFormat::Q4 ? assemble_resident_nodes(sc.host, sc.qnodes, top, fresh, out.qnodes, out, target)
+                                            : assemble_resident_nodes(sc.host, sc.nodes, top, fresh, out.nodes, out, target);
+}
+// What a stage's commit() does with them, last — it binds the scene's arrays: the scene takes the nodes and where the
+// prototypes' are (the new top-level tree has at least two leaves: its root is node 0)
+template <class R> void install_resident_nodes(SceneT<R> &sc, ResidentNodes<R> &t) {
+    if (t.qnodes.p) sc.qnodes = std::move(t.qnodes);
+    else sc.nodes = std::move(t.nodes);
+    sc.host.blas_node_first = std::move(t.node_first), sc.host.blas_node_count = std::move(t.node_count), sc.host.blas_nodes = t.blas_nodes;
+    install_tree(sc, t.n_nodes, t.depth, 0, t.grid_lo, t.grid_step);
+}
+
+// The placements' records under transforms they were not made from (d_xforms: 12 doubles each, device memory): trace
+// and shade, allocated here, from the scene's and the transforms.  A transform that cannot be inverted is refused.
+template <class R> int placement_records(const SceneT<R> &sc, const double *d_xforms, int n_inst, DevBuf<InstTrace<R>> &trace, DevBuf<InstShade<R>> &shade) {
+    using namespace lbvh;
+    FirstOffender<int> bad{INT32_MAX};
+    HIP_TRY(trace.alloc((size_t)n_inst));
+    HIP_TRY(shade.alloc((size_t)n_inst));
+    HIP_TRY(bad.arm());
+    hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), dim3(BLK), 0, nullptr, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p, trace.p, shade.p, bad.cell.p);
+    HIP_TRY(bad.read());
+    HIP_TRY(hipGetLastError());
+    if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
+    return TAKE_OK;
+}
+
+// The shapes' records — the first n_shapes of the scene's, in the leaf order of the tree that is being replaced — back in
+// SHAPE order at dst, with new geometry where their mesh has new positions (k_update_prims: the order a fresh build
+// starts from, and the one k_update_lights reads).  bad: armed by the caller, who may go on feeding it
+// (k_update_proto_prims) before new_position_refusal reads it: mesh << 32 | vertex of the first coordinate that is not finite.
+template <class R>
+void update_shape_records(const SceneT<R> &sc, int n_shapes, const MeshUpdateInputs &in, const int32_t *d_shape_face, PrimRec<R> *dst, FirstOffender<unsigned long long> &bad) {
+    using namespace lbvh;
+    if (n_shapes > 0)
+        hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n_shapes), dim3(BLK), 0, nullptr, sc.prims.p, n_shapes, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p, dst, bad.cell.p);
+}
+int new_position_refusal(FirstOffender<unsigned long long> &bad) {
+    HIP_TRY(bad.read());
+    HIP_TRY(hipGetLastError());
+    if (bad.first == bad.none) return TAKE_OK;
+    return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
+}
+// What stage_normals_and_lights staged in `built`, moved into the scene (new_normals / new_lights: which of it was made)
+template <class R> void commit_normals_and_lights(SceneT<R> &sc, SceneT<R> &built, bool new_normals, bool new_lights) {
+    if (new_normals) sc.normals = std::move(built.normals);
+    if (!new_lights) return;
+    sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
+    sc.host.lights = std::move(built.host.lights), sc.host.light_pmf = std::move(built.host.light_pmf), sc.host.light_cdf = std::move(built.host.light_cdf);
+}
+
 }  // namespace
 
 namespace tk_host {
@@ -631,76 +762,35 @@ int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInput
 template int build_side_on_device<float>(SceneT<float> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
 template int build_side_on_device<double>(SceneT<double> &, const TakeSceneDesc &, DeviceBuildInputs &, const double *const *, int, bool, bool, bool, PhaseClock &);
 
+// The re-pose, by its steps: placement_records — a transform that cannot be inverted is reported before anything else
+// is made; top_level_resident over the shapes' records (the head of the record array, in the leaf order of the tree
+// that is being replaced) and the prototypes' resident records; assemble_resident_nodes with every prototype untouched —
+// one run, moved by the difference of the two top-level trees' sizes — and k_shift_roots for the placements' roots.
 template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n64, ReposeStage<R> &out) {
     using namespace lbvh;
     const HostScene<R> &h = sc.host;
     const int n_inst = (int)n64;
     const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims);
-    const bool use_q = sc.trace.nodes == NodeFormat::Q4;
-    hipStream_t stream = nullptr;
-    const dim3 blk(BLK);
     BuildMemory mem(sizeof(R) == 4 ? "f32 (placements re-posed)" : "f64 (placements re-posed)");
-
-    // 1. the placements' records; a transform that cannot be inverted is reported before anything else is made
-    {
-        FirstOffender<int> bad{INT32_MAX};
-        HIP_TRY(out.inst_trace.alloc(n_inst));
-        HIP_TRY(out.inst_shade.alloc(n_inst));
-        HIP_TRY(bad.arm());
-        hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), blk, 0, stream, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p,
-                           out.inst_trace.p, out.inst_shade.p, bad.cell.p);
-        HIP_TRY(bad.read());
-        HIP_TRY(hipGetLastError());
-        if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
-    }
-
-    // 2.-4. the top-level tree over the shapes' records — the head of the record array, in the leaf order of the tree
-    // that is being replaced — and the placements' boxes, from the prototypes' resident records
+    if (const int rc = placement_records(sc, d_xforms, n_inst, out.inst_trace, out.inst_shade)) return rc;
     DeviceTree top;
     const int rt = top_level_resident(sc.host, sc.prims.p, sc.prims.p, n_shapes, d_xforms, n_inst, h.blas_depth, mem, top, out.head);
     if (rt) return rt;
-    out.depth = top.depth + h.blas_depth;
-
-    // 5. assembly in the scene's node format: the new top-level tree on its own grid, the prototypes' nodes copied behind
-    // it — moved by the difference of the two top-level trees' sizes, and their child words and the placements' roots with them
-    const int64_t old_top = h.stats.n_nodes - h.blas_nodes, delta = top.n_nodes - old_top;
-    out.n_nodes = top.n_nodes + h.blas_nodes;
-    if (out.n_nodes >= ((int64_t)1 << 31) || (uint64_t)out.n_nodes * node_bytes<R>(sc.trace.nodes) >= (1ull << 32))
-        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
-    const int nb = (int)h.blas_nodes;
-    if (use_q) {
-        DevBuf<double> acc;
-        QGrid g;
-        double inflation = 1.0;
-        HIP_TRY(out.qnodes.alloc((size_t)out.n_nodes));
-        HIP_TRY(acc.alloc(2));
-        const int rq = quantise_tree_device(top, out.qnodes.p, acc, g, inflation);
-        if (rq) return rq;
-        for (int a = 0; a < 3; a++) out.grid_lo[a] = g.lo[a], out.grid_step[a] = g.step[a];
-        if (nb > 0) HIP_TRY(hipMemcpyAsync(out.qnodes.p + top.n_nodes, sc.qnodes.p + old_top, (size_t)nb * sizeof(QNode4), hipMemcpyDeviceToDevice, stream));
-        if (nb > 0 && delta) hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(nb), blk, 0, stream, out.qnodes.p + top.n_nodes, nb, (int32_t)delta, 0);
-    } else {
-        for (int a = 0; a < 3; a++) out.grid_lo[a] = h.grid_lo[a], out.grid_step[a] = h.grid_step[a];  // (not read by the traversal)
-        HIP_TRY(out.nodes.alloc((size_t)out.n_nodes));
-        const int rw = wide_nodes_device(top, out.nodes.p);
-        if (rw) return rw;
-        if (nb > 0) HIP_TRY(hipMemcpyAsync(out.nodes.p + top.n_nodes, sc.nodes.p + old_top, (size_t)nb * sizeof(Node4<R>), hipMemcpyDeviceToDevice, stream));
-        if (nb > 0 && delta) hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(nb), blk, 0, stream, out.nodes.p + top.n_nodes, nb, (int32_t)delta, 0);
-    }
-    if (delta) hipLaunchKernelGGL(k_shift_roots<R>, blocks_for(n_inst), blk, 0, stream, out.inst_trace.p, n_inst, (int32_t)delta);
-    HIP_TRY(hipStreamSynchronize(stream));
+    out.tree.depth = top.depth + h.blas_depth;
+    std::vector<ProtoTarget> target;  // (not uploaded: every shift is delta)
+    const int ra = assemble_resident_nodes(sc, top, std::vector<DeviceTree *>(h.blas_prim_first.size(), nullptr), out.tree, target);
+    if (ra) return ra;
+    const int64_t delta = out.tree.n_nodes - h.stats.n_nodes;
+    if (delta) hipLaunchKernelGGL(k_shift_roots<R>, blocks_for(n_inst), dim3(BLK), 0, nullptr, out.inst_trace.p, n_inst, (int32_t)delta);
+    HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(hipGetLastError());
     mem.report();
     return TAKE_OK;
 }
 template <class R> int ReposeStage<R>::commit(SceneT<R> &sc) {
     if (head.n) HIP_TRY(hipMemcpy(sc.prims.p, head.p, head.bytes(), hipMemcpyDeviceToDevice));
-    if (qnodes.p) sc.qnodes = std::move(qnodes);
-    else sc.nodes = std::move(nodes);
     sc.inst_trace = std::move(inst_trace), sc.inst_shade = std::move(inst_shade);
-    const int64_t delta = n_nodes - sc.host.stats.n_nodes;  // (the prototypes' nodes moved with the top-level tree's size)
-    for (int64_t &first : sc.host.blas_node_first) first += delta;
-    install_tree(sc, n_nodes, depth, 0, grid_lo, grid_step);  // (the new tree has at least two leaves: its root is node 0)
+    install_resident_nodes(sc, tree);  // (the prototypes' nodes moved with the top-level tree's size)
     return TAKE_OK;
 }
 template struct ReposeStage<float>;
@@ -773,32 +863,23 @@ static int stage_normals_and_lights(const SceneT<R> &sc, const MeshUpdateInputs 
     return TAKE_OK;
 }
 
+// The update of a scene without placements, by its steps: update_shape_records — a coordinate that is not finite is
+// reported before anything else is made; stage_normals_and_lights; creation's tail (build_bvh_device: boxes, tree, nodes
+// in the format the inflation rule chooses, records into leaf order), and a trace state where the format changed.
 template <class R>
 int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
                                 int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out) {
-    using namespace lbvh;
     const int n = (int)sc.prims.n;
-    hipStream_t stream = nullptr;
-    const dim3 blk(BLK);
     SceneT<R> &b = out.built;
-
-    // 1. the records, back in shape order; a coordinate that is not finite is reported before anything else is made
     {
         FirstOffender<unsigned long long> bad{~0ull};
         HIP_TRY(b.prims.alloc((size_t)n));
         HIP_TRY(bad.arm());
-        hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n), blk, 0, stream, sc.prims.p, n, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p, b.prims.p, bad.cell.p);
-        HIP_TRY(bad.read());
-        HIP_TRY(hipGetLastError());
-        if (bad.first != bad.none)
-            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
+        update_shape_records(sc, n, in, d_shape_face, b.prims.p, bad);
+        if (const int rc = new_position_refusal(bad)) return rc;
     }
-
-    // 2. new vertex normals, 3. the light records of emissive faces and the power tables
     const int rl = stage_normals_and_lights(sc, in, mesh_vertices, d_shape_face, b.prims.p, n, b, out.new_normals, out.new_lights);
     if (rl) return rl;
-
-    // 4. creation's tail: boxes, tree, nodes in the format the inflation rule chooses, records into leaf order
     BuildVerdict why = BuildVerdict::Built;
     const int rb = build_bvh_device(b, max_leaf, compressed_ok, compressed_forced, why);
     if (rb || why != BuildVerdict::Built) return unsupported(rb, why, "tree");
@@ -814,13 +895,9 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
     return TAKE_OK;
 }
 template <class R> int MeshUpdateStage<R>::commit(SceneT<R> &sc) {
-    if (new_normals) sc.normals = std::move(built.normals);
+    commit_normals_and_lights(sc, built, new_normals, new_lights);
     sc.prims = std::move(built.prims);
     sc.qnodes = std::move(built.qnodes), sc.nodes = std::move(built.nodes);  // (the one the new format does not use is empty: the scene's is freed)
-    if (new_lights) {
-        sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
-        sc.host.lights = std::move(built.host.lights), sc.host.light_pmf = std::move(built.host.light_pmf), sc.host.light_cdf = std::move(built.host.light_cdf);
-    }
     sc.host.stats = built.host.stats, sc.host.q_inflation = built.host.q_inflation, sc.host.node_width = 4;  // (stats: n_prims and sah too)
     install_tree(sc, built.host.stats.n_nodes, built.host.stats.depth, built.host.root_child, built.host.grid_lo, built.host.grid_step);
     sc.trace = built.trace;
@@ -835,7 +912,17 @@ template int update_mesh_vertices_device<float>(const SceneT<float> &, const Mes
 template int update_mesh_vertices_device<double>(const SceneT<double> &, const MeshUpdateInputs &, const std::vector<int64_t> &, const int32_t *, int, bool, bool,
                                                  int, MeshUpdateStage<double> &);
 
-// ---- take_hip_scene_update_meshes on a two-level scene
+// ---- take_hip_scene_update_meshes on a two-level scene, by its steps:
+//   1. the records: update_shape_records, and k_update_proto_prims for the moved prototypes', in face order, feeding the
+//      same offender cell — a coordinate that is not finite, in either role, is reported before anything else is made;
+//   2. stage_normals_and_lights;
+//   3. per prototype prototype_pass, or its records copied to their place in the new record array;
+//   4. top_level_resident under d_xforms: the shapes' boxes from their new records, the placements' from the
+//      prototypes' records as they are now; the shapes' records into leaf order at the head of the new array;
+//   5. assemble_resident_nodes;
+//   6. the placements: their records as they are — transforms, materials, tags, shape bases — or, new_records,
+//      placement_records under d_xforms; then k_retarget_placements to the roots, and the moved prototypes' grids, of
+//      the new node array.
 template <class R>
 int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &in, const std::vector<int64_t> &mesh_vertices, const int32_t *d_shape_face,
                                    const double *d_xforms, int max_leaf, bool new_records, ProtoUpdateStage<R> &out) {
@@ -844,7 +931,6 @@ int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &
     const int n_inst = (int)sc.inst_trace.n, n_protos = (int)h.blas_prim_first.size();
     const int n_shapes = (int)((int64_t)sc.prims.n - h.blas_prims);
     const int leaf_size = device_leaf_size(max_leaf);
-    const bool use_q = sc.trace.nodes == NodeFormat::Q4;
     hipStream_t stream = nullptr;
     const dim3 blk(BLK);
     BuildMemory mem(sizeof(R) == 4 ? "f32 (meshes updated)" : "f64 (meshes updated)");
@@ -852,28 +938,25 @@ int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &
     if ((int)h.blas_mesh.size() != n_protos || (int)h.blas_node_first.size() != n_protos || (int)h.blas_node_count.size() != n_protos ||
         (int)h.blas_depths.size() != n_protos || (int)h.placements.inst_proto.size() != n_inst || n_shapes < 0)
         return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
-    std::vector<char> moved(n_protos, 0);
+    std::vector<DeviceTree> trees(n_protos);
+    std::vector<DeviceTree *> fresh(n_protos, nullptr);  // the moved prototypes' trees (step 3 builds them), null: untouched
     for (int k = 0; k < n_protos; k++) {
         const int32_t mesh = h.blas_mesh[k];
         if (mesh < 0 || (size_t)mesh >= in.pos.size() || (size_t)mesh >= h.meshes.size()) return fail(TAKE_E_INVALID, "unsupported: the scene does not know the mesh of prototype " + std::to_string(k));
-        moved[k] = in.pos[mesh] != nullptr;
-        if (moved[k] && (h.blas_prim_count[k] + leaf_size - 1) / leaf_size < 2) return unsupported(TAKE_OK, BuildVerdict::TooFewLeaves, "prototype tree");
+        if (in.pos[mesh]) fresh[k] = &trees[k];
+        if (fresh[k] && (h.blas_prim_count[k] + leaf_size - 1) / leaf_size < 2) return unsupported(TAKE_OK, BuildVerdict::TooFewLeaves, "prototype tree");
     }
 
-    // 1. the records: the shapes' back in shape order with new geometry where their mesh moved (k_update_prims: the
-    // order a fresh build starts from, and the one k_update_lights reads), the moved prototypes' in face order.  A
-    // coordinate that is not finite, in either role, is reported before anything else is made.
+    // 1.
     DevBuf<PrimRec<R>> shapes;              // shape order
     std::vector<DevBuf<PrimRec<R>>> faces(n_protos);  // face order, moved prototypes only
     {
         FirstOffender<unsigned long long> bad{~0ull};
         HIP_TRY(shapes.alloc((size_t)n_shapes));
         HIP_TRY(bad.arm());
-        if (n_shapes > 0)
-            hipLaunchKernelGGL(k_update_prims<R>, blocks_for(n_shapes), blk, 0, stream, sc.prims.p, n_shapes, in.d_pos.p, sc.meshes.p, d_shape_face, sc.face_idx.p,
-                               shapes.p, bad.cell.p);
+        update_shape_records(sc, n_shapes, in, d_shape_face, shapes.p, bad);
         for (int k = 0; k < n_protos; k++) {
-            if (!moved[k]) continue;
+            if (!fresh[k]) continue;
             const int32_t mesh = h.blas_mesh[k];
             const MeshInfo &mi = h.meshes[mesh];
             const int nf = (int)h.blas_prim_count[k];
@@ -881,138 +964,55 @@ int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &
             HIP_TRY(faces[k].alloc((size_t)nf));
             hipLaunchKernelGGL(k_update_proto_prims<R>, blocks_for(nf), blk, 0, stream, src, mesh, in.pos[mesh], sc.face_idx.p, nf, faces[k].p, bad.cell.p);
         }
-        HIP_TRY(bad.read());
-        HIP_TRY(hipGetLastError());
-        if (bad.first != bad.none)
-            return fail(TAKE_E_INVALID, "mesh " + std::to_string(bad.first >> 32) + ": vertex " + std::to_string(bad.first & 0xffffffffull) + ": a new position is not finite");
+        if (const int rc = new_position_refusal(bad)) return rc;
     }
 
-    // 2. new vertex normals, 3. light records and power tables
+    // 2.
     const int rl = stage_normals_and_lights(sc, in, mesh_vertices, d_shape_face, shapes.p, n_shapes, b, out.new_normals, out.new_lights);
     if (rl) return rl;
 
-    // 4. the prototypes: a moved one gets the pass of build_two_level_device's step 1 — boxes, tree, records into leaf
-    // order at its place in the new record array, its float nodes cut to size for step 6; an untouched one's records are copied
+    // 3.
     HIP_TRY(b.prims.alloc(sc.prims.n));
     DevBuf<int> scene_ord;
     HIP_TRY(scene_ord.alloc(6));
-    std::vector<DeviceTree> trees(n_protos);
-    out.depths = h.blas_depths, out.node_count = h.blas_node_count, out.node_first.assign(n_protos, 0);
+    out.depths = h.blas_depths;
     for (int k = 0; k < n_protos; k++) {
         const int nf = (int)h.blas_prim_count[k];
         PrimRec<R> *at = b.prims.p + h.blas_prim_first[k];
-        if (!moved[k]) {
+        if (!fresh[k]) {
             HIP_TRY(hipMemcpyAsync(at, sc.prims.p + h.blas_prim_first[k], (size_t)nf * sizeof(PrimRec<R>), hipMemcpyDeviceToDevice, stream));
             continue;
         }
-        DevBuf<Box> pb;
-        HIP_TRY(pb.alloc(nf));
-        HIP_TRY(reset_bounds(scene_ord));
-        span_boxes(faces[k].p, nf, pb.p, scene_ord);
-        DeviceTree &t = trees[k];
         BuildVerdict why = BuildVerdict::Built;
-        const int rt = build_tree_device(pb, scene_ord, nf, leaf_size, mem, t, why);
+        const int rt = prototype_pass(faces[k].p, nf, leaf_size, at, scene_ord, mem, trees[k], why);
         if (rt || why != BuildVerdict::Built) return unsupported(rt, why, "prototype tree");
-        hipLaunchKernelGGL((k_permute<PrimRec<R>>), blocks_for(nf), blk, 0, stream, faces[k].p, t.order.p, nf, at);
-        DevBuf<Node4<float>> cut;
-        HIP_TRY(cut.alloc((size_t)t.n_nodes));
-        HIP_TRY(hipMemcpy(cut.p, t.nodes.p, cut.bytes(), hipMemcpyDeviceToDevice));
-        t.nodes = std::move(cut);
-        t.order.release(), faces[k].release();
-        out.depths[k] = t.depth, out.node_count[k] = t.n_nodes;
+        faces[k].release();
+        out.depths[k] = trees[k].depth;
     }
     out.blas_depth = 0;
     for (int k = 0; k < n_protos; k++) out.blas_depth = std::max(out.blas_depth, out.depths[k]);
     mem.sample("prototypes");
 
-    // 5. the top level under the scene's current transforms: the shapes' boxes from their new records, the placements'
-    // from the prototypes' records as they are now; the shapes' records into leaf order at the head of the new array
+    // 4.
     DeviceTree top;
     const int rt = top_level_resident(h, shapes.p, b.prims.p, n_shapes, d_xforms, n_inst, out.blas_depth, mem, top, b.prims);
     if (rt) return rt;
     shapes.release();
-    out.depth = top.depth + out.blas_depth;
+    out.tree.depth = top.depth + out.blas_depth;
 
-    // 6. assembly in the scene's node format: [new top level][prototype 0][prototype 1]...  A moved prototype's tree is
-    // quantised on its own grid (or widened) into place and rebased; untouched ones are copied and rebased by their own
-    // node shift, primitive shift 0 — a run of untouched neighbours shares its shift: one copy, one launch
-    out.n_nodes = top.n_nodes;
-    for (int k = 0; k < n_protos; k++) out.node_first[k] = out.n_nodes, out.n_nodes += out.node_count[k];
-    out.blas_nodes = out.n_nodes - top.n_nodes;
-    if (out.n_nodes >= ((int64_t)1 << 31) || (uint64_t)out.n_nodes * node_bytes<R>(sc.trace.nodes) >= (1ull << 32))
-        return fail(TAKE_E_INVALID, "unsupported: too many nodes for the 32-bit record offsets of the trace kernels");
-    std::vector<ProtoTarget> target(n_protos, ProtoTarget{});
-    DevBuf<double> acc;
-    if (use_q) {
-        QGrid g;
-        double inflation = 1.0;
-        HIP_TRY(b.qnodes.alloc((size_t)out.n_nodes));
-        HIP_TRY(acc.alloc(2));
-        const int rq = quantise_tree_device(top, b.qnodes.p, acc, g, inflation);
-        if (rq) return rq;
-        for (int a = 0; a < 3; a++) out.grid_lo[a] = g.lo[a], out.grid_step[a] = g.step[a];
-    } else {
-        for (int a = 0; a < 3; a++) out.grid_lo[a] = h.grid_lo[a], out.grid_step[a] = h.grid_step[a];  // (not read by the traversal)
-        HIP_TRY(b.nodes.alloc((size_t)out.n_nodes));
-        const int rw = wide_nodes_device(top, b.nodes.p);
-        if (rw) return rw;
-    }
-    for (int k = 0; k < n_protos;) {
-        const int32_t first = (int32_t)out.node_first[k];
-        if (moved[k]) {
-            const int nk = (int)trees[k].n_nodes;
-            target[k].moved = 1, target[k].root = first, target[k].has_grid = use_q;
-            if (use_q) {
-                QGrid g;
-                double inflation = 1.0;  // (not consulted: the scene keeps its format, and the box tests stay conservative)
-                const int rq = quantise_tree_device(trees[k], b.qnodes.p + first, acc, g, inflation);
-                if (rq) return rq;
-                for (int a = 0; a < 3; a++) target[k].grid_lo[a] = g.lo[a], target[k].grid_step[a] = g.step[a];
-                hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(nk), blk, 0, stream, b.qnodes.p + first, nk, first, (int32_t)h.blas_prim_first[k]);
-            } else {
-                const int rw = wide_nodes_device(trees[k], b.nodes.p + first);
-                if (rw) return rw;
-                hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(nk), blk, 0, stream, b.nodes.p + first, nk, first, (int32_t)h.blas_prim_first[k]);
-            }
-            trees[k].nodes.release();
-            k++;
-            continue;
-        }
-        int e = k;
-        int64_t run = 0;
-        while (e < n_protos && !moved[e]) run += h.blas_node_count[e], e++;
-        const int64_t old_first = h.blas_node_first[k], shift = (int64_t)first - old_first;
-        for (int j = k; j < e; j++) target[j].shift = (int32_t)shift;
-        if (run > 0) {
-            if (old_first < 0 || old_first + run > h.stats.n_nodes) return fail(TAKE_E_INVALID, "unsupported: the scene does not know where its prototypes are");
-            if (use_q) {
-                HIP_TRY(hipMemcpyAsync(b.qnodes.p + first, sc.qnodes.p + old_first, (size_t)run * sizeof(QNode4), hipMemcpyDeviceToDevice, stream));
-                if (shift) hipLaunchKernelGGL(k_rebase<QNode4>, blocks_for(run), blk, 0, stream, b.qnodes.p + first, (int)run, (int32_t)shift, 0);
-            } else {
-                HIP_TRY(hipMemcpyAsync(b.nodes.p + first, sc.nodes.p + old_first, (size_t)run * sizeof(Node4<R>), hipMemcpyDeviceToDevice, stream));
-                if (shift) hipLaunchKernelGGL(k_rebase<Node4<R>>, blocks_for(run), blk, 0, stream, b.nodes.p + first, (int)run, (int32_t)shift, 0);
-            }
-        }
-        k = e;
-    }
+    // 5.
+    std::vector<ProtoTarget> target;
+    const int ra = assemble_resident_nodes(sc, top, fresh, out.tree, target);
+    if (ra) return ra;
 
-    // 7. the placements: records as they are — transforms, materials, tags, shape bases — with the roots, and the
-    // moved prototypes' grids, of the new node array.  new_records (a slice of take_hip_render_shutter_meshes*, whose
-    // d_xforms are not the transforms the records were made from): the re-pose's records under d_xforms instead
+    // 6.
     {
         DevBuf<int32_t> inst_proto;
         DevBuf<ProtoTarget> d_target;
-        HIP_TRY(b.inst_trace.alloc((size_t)n_inst));
         if (new_records) {
-            FirstOffender<int> bad{INT32_MAX};
-            HIP_TRY(b.inst_shade.alloc((size_t)n_inst));
-            HIP_TRY(bad.arm());
-            hipLaunchKernelGGL(k_placement_records<R>, blocks_for(n_inst), blk, 0, stream, d_xforms, n_inst, sc.inst_trace.p, sc.inst_shade.p, b.inst_trace.p,
-                               b.inst_shade.p, bad.cell.p);
-            HIP_TRY(bad.read());
-            HIP_TRY(hipGetLastError());
-            if (bad.first != bad.none) return fail(TAKE_E_INVALID, "instance " + std::to_string(bad.first) + ": singular or non-finite transform");
+            if (const int rc = placement_records(sc, d_xforms, n_inst, b.inst_trace, b.inst_shade)) return rc;
         } else {
+            HIP_TRY(b.inst_trace.alloc((size_t)n_inst));
             HIP_TRY(hipMemcpyAsync(b.inst_trace.p, sc.inst_trace.p, sc.inst_trace.bytes(), hipMemcpyDeviceToDevice, stream));
         }
         HIP_TRY(inst_proto.upload(h.placements.inst_proto));
@@ -1026,19 +1026,12 @@ int update_two_level_meshes_device(const SceneT<R> &sc, const MeshUpdateInputs &
 }
 template <class R> int ProtoUpdateStage<R>::commit(SceneT<R> &sc) {
     HostScene<R> &h = sc.host;
-    if (new_normals) sc.normals = std::move(built.normals);
+    commit_normals_and_lights(sc, built, new_normals, new_lights);
     sc.prims = std::move(built.prims);
-    if (built.qnodes.p) sc.qnodes = std::move(built.qnodes);
-    else sc.nodes = std::move(built.nodes);
     sc.inst_trace = std::move(built.inst_trace);
     if (built.inst_shade.p) sc.inst_shade = std::move(built.inst_shade);  // (new_records)
-    if (new_lights) {
-        sc.lights = std::move(built.lights), sc.light_pmf = std::move(built.light_pmf), sc.light_cdf = std::move(built.light_cdf);
-        h.lights = std::move(built.host.lights), h.light_pmf = std::move(built.host.light_pmf), h.light_cdf = std::move(built.host.light_cdf);
-    }
-    h.blas_node_first = std::move(node_first), h.blas_node_count = std::move(node_count), h.blas_depths = std::move(depths);
-    h.blas_nodes = blas_nodes, h.blas_depth = blas_depth;
-    install_tree(sc, n_nodes, depth, 0, grid_lo, grid_step);  // (the new top-level tree has at least two leaves: its root is node 0)
+    h.blas_depths = std::move(depths), h.blas_depth = blas_depth;
+    install_resident_nodes(sc, tree);
     return TAKE_OK;
 }
 template struct ProtoUpdateStage<float>;

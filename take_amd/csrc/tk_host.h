@@ -1,5 +1,5 @@
-// tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_create.hip and tk_group.hip (the C entry
-// points, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
+// tk_host.h — host plumbing shared by the library's units, tk_api.hip, tk_scene_update.hip, tk_create.hip and
+// tk_group.hip (the C entry points that render and that change a scene, scene creation, groups), tk_build.hip (the device LBVH build), tk_render.hip (rendering, trace hooks),
 // tk_mesh.hip (mesh ingest), tk_denoise.hip (the image-space denoiser), tk_display.hip (the display transform),
 // tk_bloom.hip (its bloom and the image workspace), tk_envmap.hip (a new environment map for a resident scene),
 // tk_shading_update.hip (its new materials and light intensities) and tk_skin.hip (rigs: skinning and morph targets): the error string, fault injection, pinned uploads, the owning device buffer, the staged planes of the host twins, the

@@ -1,6 +1,6 @@
 // tk_mesh.hip — mesh ingest of the C ABI of include/take_hip.h: PLY, Mitsuba serialized and Wavefront OBJ files decoded
 // into device-array meshes (tk_ply.h, tk_obj.h), and compute_normals on device or host arrays (tk_normals.h).  The
-// plumbing it shares with the other units (tk_api.hip, tk_create.hip, tk_group.hip, tk_build.hip, tk_render.hip) is tk_host.h.
+// plumbing it shares with the other units (tk_api.hip, tk_scene_update.hip, tk_create.hip, tk_group.hip, tk_build.hip, tk_render.hip) is tk_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

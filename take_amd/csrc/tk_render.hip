@@ -6,7 +6,7 @@
 // pixels still active, the feature pass and the export of the camera's rays (start_batch only), the motion pass, the
 // trace hooks.
 // The only unit that compiles the kernels of tk_kernels.h, tk_features.h, tk_motion.h, tk_adaptive.h, tk_shutter.h and tk_rays.h (as tk_build.hip is for tk_build_gpu.h);
-// what tk_api.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
+// what tk_api.hip, tk_scene_update.hip, tk_create.hip and tk_group.hip (the C entry points, scene creation, groups) call here is declared
 // in tk_scene_handle.h.  Host code only orchestrates: every per-sample operation runs in the kernels.
 #include <hip/hip_runtime.h>
 

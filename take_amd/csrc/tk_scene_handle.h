@@ -1,9 +1,9 @@
 // tk_scene_handle.h — the scene handle and who owns what in it: TakeScene has one SceneT per precision side (the scene
 // itself), each with the TraceState of its trace kernel instance, and ONE RenderWorkspace, of the primary side's precision.
 // Then the walks over the sides (on_primary, for_each_side, on_side, stage_then_commit) and what tk_create.hip (scene
-// creation), tk_group.hip (groups) and tk_api.hip (the other entry points) call of tk_render.hip (the only unit that
-// compiles the kernels of tk_kernels.h) and of tk_build.hip (the device LBVH build: the only one that compiles
-// tk_build_gpu.h's).  Includes no kernel source.
+// creation), tk_group.hip (groups), tk_api.hip (the entry points that render and trace) and tk_scene_update.hip (those
+// that change a resident scene) call of tk_render.hip (the only unit that compiles the kernels of tk_kernels.h) and of
+// tk_build.hip (the device LBVH build: the only one that compiles tk_build_gpu.h's).  Includes no kernel source.
 #pragma once
 #include <chrono>
 #include <cmath>
@@ -397,24 +397,31 @@ template <class R>
 int build_side_on_device(SceneT<R> &sc, const TakeSceneDesc &d, DeviceBuildInputs &in, const double *const *device_positions, int max_leaf,
                          bool compressed_ok, bool compressed_forced, bool last_side, PhaseClock &clock);
 
-// The placements of a resident two-level scene under new transforms (take_hip_scene_set_instance_transforms): the
-// top-level half of the device build entered a second time, reading only what the scene keeps — the old placement
-// records, the prototypes' records (tight boxes: k_placement_boxes_resident), the shapes' records now in leaf order.
-// d_xforms: 12 doubles per placement in device memory, complete; n = the scene's placements; built into `out`
-// (stage_then_commit).  Both stages' commit() return a TAKE_* code and allocate nothing: MeshUpdateStage's only moves,
-// this one also copies the staged head records over the scene's, which fails only with a lost device.  The prototypes'
-// trees are copied, never rebuilt; the scene keeps its node format; who built it does not matter (the new top-level
-// tree is an LBVH).  Errors: TAKE_E_INVALID naming the first singular or non-finite transform, or starting with
-// "unsupported" when the new top-level tree has fewer than two leaves or is too deep for the traversal stack.
-template <class R> struct ReposeStage {
-    DevBuf<Node4<R>> nodes;      // the format the scene traverses: the new top-level tree's nodes, then the prototypes'
+// The three changes of a resident scene that rebuild trees, each built into a stage of its own (stage_then_commit) by a
+// driver of tk_build.hip, where the steps they share are described.  A commit() returns a TAKE_* code and allocates nothing.
+
+// What the node assembly of a resident two-level scene makes, in the node format the scene keeps: the new top-level
+// tree's nodes, then the prototypes'; the top-level tree's grid (compressed nodes); the depth over both levels.
+template <class R> struct ResidentNodes {
+    DevBuf<Node4<R>> nodes;
     DevBuf<QNode4> qnodes;
+    float grid_lo[3] = {0, 0, 0}, grid_step[3] = {1, 1, 1};
+    int64_t n_nodes = 0, blas_nodes = 0;
+    int depth = 0;
+    std::vector<int64_t> node_first, node_count;  // per prototype, as HostScene::blas_node_first / _count
+};
+// The placements of a resident two-level scene under new transforms (take_hip_scene_set_instance_transforms): the
+// top-level half of the device build entered a second time, reading only what the scene keeps.  d_xforms: 12 doubles
+// per placement in device memory, complete; n = the scene's placements.  The prototypes' trees are copied, never
+// rebuilt; who built the scene does not matter (the new top-level tree is an LBVH).  commit() copies the staged head
+// records over the scene's — not every prototype's records — which fails only with a lost device.  Errors:
+// TAKE_E_INVALID naming the first singular or non-finite transform, or starting with "unsupported" when the new
+// top-level tree has fewer than two leaves or is too deep for the traversal stack.
+template <class R> struct ReposeStage {
+    ResidentNodes<R> tree;
     DevBuf<PrimRec<R>> head;     // the shapes' records in the new leaf order (the head of sc.prims)
     DevBuf<InstTrace<R>> inst_trace;
     DevBuf<InstShade<R>> inst_shade;
-    float grid_lo[3] = {0, 0, 0}, grid_step[3] = {1, 1, 1};  // the new top-level tree's grid (compressed nodes)
-    int64_t n_nodes = 0;
-    int depth = 0;
     int commit(SceneT<R> &sc);
 };
 template <class R> int repose_two_level_device(const SceneT<R> &sc, const double *d_xforms, int64_t n, ReposeStage<R> &out);
@@ -448,24 +455,20 @@ int update_mesh_vertices_device(const SceneT<R> &sc, const MeshUpdateInputs &in,
                                 int max_leaf, bool compressed_ok, bool compressed_forced, int num_cus, MeshUpdateStage<R> &out);
 
 // New vertex positions (and vertex normals) for meshes of a resident TWO-LEVEL scene (take_hip_scene_update_meshes):
-// the shapes' records rewritten (k_update_prims), the records and tree of every prototype whose mesh is named made again
-// (k_update_proto_prims, build_tree_device with the scene's leaf size request, the scene's node format on the tree's
-// own grid), the other prototypes' records and nodes copied, the top level rebuilt under d_xforms — the scene's current
-// transforms — by the resident path the re-pose takes, and the placements retargeted (k_retarget_placements).  The
-// scene keeps its node format.  Built into `out` (stage_then_commit); commit() only moves.  Errors: as
-// update_mesh_vertices_device, the trees being the moved prototypes' and the top-level one, the depth both levels'.
+// the records and tree of every prototype whose mesh is named are made again with the scene's leaf size request, the
+// others' copied, and the top level is rebuilt under d_xforms — the scene's current transforms — by the resident path
+// the re-pose takes.  The scene keeps its node format.  commit() only moves.  Errors: as update_mesh_vertices_device,
+// the trees being the moved prototypes' and the top-level one, the depth both levels'.
 // new_records (a slice of take_hip_render_shutter_meshes*): d_xforms are NOT the transforms the placements' records were
-// made from — the records are made again under them (k_placement_records, the re-pose's step 1 and its refusal), so
-// that the one top-level rebuild serves both the new vertices and the new pose.
+// made from — the records are made again under them, with the re-pose's refusal, so that the one top-level rebuild
+// serves both the new vertices and the new pose.
 template <class R> struct ProtoUpdateStage {
-    // built.prims (all records), qnodes or nodes, inst_trace, normals / lights and their tables when they change
+    // built.prims (all records), inst_trace (inst_shade: new_records), normals / lights and their tables when they change
     SceneT<R> built;
+    ResidentNodes<R> tree;
     bool new_lights = false, new_normals = false;
-    float grid_lo[3] = {0, 0, 0}, grid_step[3] = {1, 1, 1};  // the new top-level tree's grid (compressed nodes)
-    int64_t n_nodes = 0, blas_nodes = 0;
-    int depth = 0, blas_depth = 0;
-    std::vector<int64_t> node_first, node_count;  // per prototype, as HostScene::blas_node_first / _count
-    std::vector<int> depths;
+    int blas_depth = 0;
+    std::vector<int> depths;  // per prototype, as HostScene::blas_depths
     int commit(SceneT<R> &sc);  // moves only: always TAKE_OK
 };
 template <class R>

@@ -1,6 +1,6 @@
 """The bytes every path-traced call returns, as one SHA-256 per call: what a change of the host side of rendering
-(take_amd/csrc/tk_render.hip, tk_api.hip) must leave as it is.  Two runs — two builds (TAKE_HIP_LIB), or the two settings
-of TAKE_HIP_CAMERA_FUSED — are compared line by line; tests/test_gpu_camera_routes.py does the latter.
+(take_amd/csrc/tk_render.hip, tk_api.hip, tk_scene_update.hip) must leave as it is.  Two runs — two builds (TAKE_HIP_LIB),
+or the two settings of TAKE_HIP_CAMERA_FUSED — are compared line by line; tests/test_gpu_camera_routes.py does the latter.
 
 Scenes, each built once per precision: the golden cbox at 9 x 7 and at 65 x 3 (at 1 spp 63 and 195 paths: a queue that
 ends inside a wave, one that crosses a block), the golden mats at its own size (sorted material tags) and
@@ -13,6 +13,14 @@ either setting of TAKE_HIP_CAMERA_FUSED, so these lines say nothing about the tw
 equal too.
 
     python tools/render_digests.py > digests.txt
+
+With --resident the tool prints another list instead: the bytes a resident scene holds in device memory after each change
+of it (take_amd/csrc/tk_scene_update.hip, and the drivers of tk_build.hip behind it), which a change of those must leave as
+they are.  One line per item, "resident/<scene>/<precision>/<step>/<array> <sha256>": per side of the scene the arrays
+Scene.debug_tree returns (<side>.nodes, .prims, .inst_trace) and its scalars (<side>.info), and one 9 x 7, 2 spp render,
+which covers the placements' shading records, lights, tables and normals.  Scenes and steps: see resident_steps.
+
+    python tools/render_digests.py --resident > resident.txt
 """
 import hashlib
 import os
@@ -153,8 +161,78 @@ def counted_calls(sc, name, precision):
     return [(label, f) for label, f in image_calls(sc, name, precision) if label in keep]
 
 
+def resident_steps():
+    """[(scene name, SceneData, [(step, f(sc))])]: what each step does to the resident scene `sc`.  The scenes and the
+    deformations are those of tests/test_gpu_proto_update.py and tests/test_gpu_mesh_update.py, at 9 x 7 pixels."""
+    import test_gpu_mesh_update as M
+    import test_gpu_proto_update as P
+
+    def small(sd):
+        sd.width, sd.height = 9, 7
+        return sd
+
+    two = small(P.scene())
+    first, second, _, last = P.proto_meshes(two)
+    pos = {m: two.meshes[m].positions for m in (first, second, last)}
+    at_rest = np.array(two.instance_xform, np.float64)
+
+    def current_frame(sc):
+        # the mark under the moved transforms, the current frame under the description's
+        sc.mark_frame()
+        sc.set_instance_transforms(at_rest)
+
+    def shutter_meshes(sc):
+        # every slice's pose differs from the transforms the placements' records were made from, and the first prototype
+        # deforms: the update makes the records again (new_records).  Afterwards the scene is at the current frame again:
+        # every line of this step equals the step before's
+        sc.render_shutter_meshes([(first, pos[first], M.smooth(pos[first]))], spp=4, max_depth=DEPTH, seed=SEED, slices=2)
+
+    flat, lamp = M.emissive_scene()
+    old = flat.meshes[lamp].positions
+    return [
+        ("protos", two, [
+            ("created", lambda sc: None),
+            ("set_instance_transforms", lambda sc: sc.set_instance_transforms(moved_transforms(two))),
+            # (a run of two untouched prototypes between moved ones)
+            ("update_first_and_last", lambda sc: sc.update_meshes({first: M.smooth(pos[first]), last: M.smooth(pos[last])})),
+            # (untouched runs on both sides, with different shifts: half_shrunk changes the tree's node count)
+            ("update_second", lambda sc: sc.update_meshes({second: P.half_shrunk(pos[second])})),
+            ("mark_and_current_frame", current_frame),
+            ("render_shutter_meshes", shutter_meshes),
+        ]),
+        ("emissive", small(flat), [
+            ("created", lambda sc: None),
+            ("set_mesh_vertices", lambda sc: sc.set_mesh_vertices({lamp: (M.smooth(old) - (0.0, 0.15, 0.0), -M.bent_grid(6)[2][::-1].copy())})),
+        ]),
+    ]
+
+
+def resident():
+    arrays = ("nodes", "prims", "inst_trace")
+    sides = {D.TAKE_PRECISION_F32: "f32", D.TAKE_PRECISION_F64: "f64"}
+    for name, sd, steps in resident_steps():
+        for precision, code in PRECISIONS.items():
+            sc = capi.Scene(sd, precision=code, builder=D.TAKE_BUILDER_DEVICE_LBVH)
+            try:
+                for step, change in steps:
+                    change(sc)
+                    where = f"resident/{name}/{precision}/{step}"
+                    for side, side_name in sides.items():
+                        if precision != "mixed" and side_name != precision:
+                            continue
+                        tree = sc.debug_tree(side)
+                        for a in arrays:
+                            print(f"{where}/{side_name}.{a} {digest(tree[a])}", flush=True)
+                        print(f"{where}/{side_name}.info {digest({k: np.asarray(v) for k, v in tree.items() if k not in arrays})}", flush=True)
+                    print(f"{where}/render {digest(sc.render(spp=2, max_depth=DEPTH, seed=SEED))}", flush=True)
+            finally:
+                sc.close()
+
+
 def main():
     assert capi.device_count() >= 1
+    if "--resident" in sys.argv[1:]:
+        return resident()
     compressed = []  # the scenes on 64-byte 4-wide nodes: the only ones whose round 0 has the fused route
     for name, sd in scene_set().items():
         for precision, code in PRECISIONS.items():
