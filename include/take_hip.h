@@ -488,6 +488,76 @@ int take_hip_rig_pose(TakeRig *rig, const TakeRigPose *pose, double *positions_o
  * scene: a mesh index out of range, a rig on another device, a rig whose n_vertices is not the mesh's (the message
  * names the binding, the mesh and both counts).  Then every refusal of take_hip_scene_update_meshes, in its words. */
 int take_hip_scene_pose_meshes(TakeScene *scene, const TakeRigBinding *bindings, int32_t n);
+/* Loop subdivision surfaces on the device (EXTENSION; new symbols of ABI version 5; no struct changed; specification:
+ * DESIGN.md §4s).  A TakeSubdiv is the stage between "pose" and "update": made once from a cage's TOPOLOGY — its faces,
+ * optional per-vertex uvs, a level count —, it keeps the refined topology and the per-level stencil tables in device
+ * memory; every frame cage POSITIONS go in and refined positions and vertex normals come out there.  The handle is
+ * scene-free, bound to the device current at its creation, and not thread-safe (it owns the buffers a refine writes).
+ * One level, in double, every operation in the order written:
+ *   edges      the distinct unordered corner pairs (lo < hi), numbered in ascending (lo, hi) order
+ *   vertices   even vertex v keeps index v; the odd vertex of edge e is V + e
+ *   faces      (a, b, c) becomes (a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca) at 4 f .. 4 f + 3
+ *   uvs        even: kept; odd: 0.5 * (uv[lo] + uv[hi]) — made once at creation, no refine touches them
+ *   even       interior, neighbours n0 < n1 < ... (n of them): s = p[n0]; s = s + p[n1]; ...;
+ *              (1.0 - n * beta) * p[v] + beta * s with beta = 3/16 for n = 3, else 3.0 / (8.0 * n)   (Warren's weights)
+ *              on the boundary, boundary neighbours b0 < b1: 0.75 * p[v] + 0.125 * (p[b0] + p[b1]);  no face: copied
+ *   odd        interior: 0.375 * (p[lo] + p[hi]) + 0.125 * (p[c] + p[d]), c the opposite corner in the lower-numbered
+ *              face, d in the higher;  boundary: 0.5 * (p[lo] + p[hi])
+ * After the last level: N_f = cross(p1 - p0, p2 - p0); a vertex's normal is the sum of N_f over its faces in ascending
+ * face order, divided by its length when that is positive and finite. */
+typedef struct TakeSubdiv TakeSubdiv;
+#define TAKE_SUBDIV_DEVICE_ARRAYS 1 /* cage_positions is device memory */
+typedef struct TakeSubdivDesc {
+    int64_t n_vertices, n_faces; /* of the cage; > 0 */
+    const int32_t *indices;      /* n_faces x 3; host memory */
+    const double *uvs;           /* n_vertices x 2, or NULL; host memory */
+    int32_t levels;              /* 1..6 */
+    int32_t flags;               /* 0 */
+} TakeSubdivDesc;
+typedef struct TakeSubdivBinding {
+    int32_t mesh;                 /* index into the TakeSceneDesc.meshes the scene was created from */
+    int32_t flags;                /* 0, or TAKE_SUBDIV_DEVICE_ARRAYS */
+    TakeSubdiv *subdiv;
+    const double *cage_positions; /* cage vertices x 3, or NULL when `rig` is given */
+    TakeRig *rig;                 /* NULL, or the cage comes from this rig under `pose` */
+    TakeRigPose pose;
+} TakeSubdivBinding;
+/* These two need no GPU (as take_hip_ply_layout, take_hip_shutter_plan): the refined counts, and the refined faces
+ * (n_faces_out x 3) and uvs (n_vertices_out x 2; NULL = not wanted; wanted from a cage without uvs: TAKE_E_INVALID) —
+ * what a caller builds the TakeSceneDesc mesh from, with positions from one refine.
+ * TAKE_E_INVALID, the message naming the level and the face, edge or vertex: a NULL argument, counts <= 0, levels
+ * outside 1..6, unknown flag bits, an index out of range, a face with a repeated index, an edge with more than two
+ * faces, a boundary vertex with other than two boundary edges (a bow-tie).  TAKE_E_INVALID with a message that starts
+ * with "unsupported": refined counts at which 3 * n_faces or n_vertices passes INT32_MAX.  Inconsistent orientation
+ * across an edge is accepted: no weight reads orientation. */
+int take_hip_subdiv_counts(const TakeSubdivDesc *desc, int64_t *n_vertices_out, int64_t *n_faces_out);
+int take_hip_subdiv_topology(const TakeSubdivDesc *desc, int32_t *indices_out, double *uvs_out);
+/* The same refusals, before a device is looked for; then the tables are built on the host, uploaded, and everything a
+ * refine needs is allocated: the staged cage, the level buffers, the face normals, the handle's own outputs.  No later
+ * call allocates for the refine.  TAKE_E_NOMEM: the device has no room. */
+int take_hip_subdiv_create(const TakeSubdivDesc *desc, TakeSubdiv **out);
+int take_hip_subdiv_destroy(TakeSubdiv *subdiv);
+/* what the handle holds; device_bytes: everything it has allocated, which no refine changes.  Any output may be NULL. */
+int take_hip_subdiv_info(const TakeSubdiv *subdiv, int64_t *cage_vertices, int64_t *n_vertices, int64_t *n_faces, int32_t *levels, int64_t *device_bytes);
+/* The cage refined into device memory: n_vertices x 3 doubles each; d_normals_out NULL = not wanted.  cage_positions is
+ * host memory, or device memory under TAKE_SUBDIV_DEVICE_ARRAYS.  Runs on `stream` (hipStream_t, NULL = the default
+ * stream), after whatever that stream still has to write into a device cage, and returns after it has completed.  A
+ * position that is not finite is refined as it is: the mesh update's own finiteness check catches it. */
+int take_hip_subdiv_refine_device(TakeSubdiv *subdiv, const double *cage_positions, int32_t flags, double *d_positions_out, double *d_normals_out, void *stream);
+/* the same from a host cage into host arrays (the handle's own buffers, then a download); normals_out NULL = not wanted */
+int take_hip_subdiv_refine(TakeSubdiv *subdiv, const double *cage_positions, double *positions_out, double *normals_out);
+/* Refine and update in one step: every binding's cage — host or device positions, or a rig that is posed first (its
+ * n_vertices must equal the cage's) — is refined into the handle's own buffers, then the scene takes exactly the path of
+ * take_hip_scene_update_meshes with TAKE_MESH_DEVICE_ARRAYS over them, with everything that call carries: both kinds of
+ * scene, every precision, the finiteness refusal, frame marks and vertex tracking, the end of a progressive sequence, and
+ * a failed call leaving the scene as it was (the kernels write handle-owned memory only, before anything is staged).
+ * Normals are passed on only when the mesh has vertex normals.
+ * TAKE_E_INVALID before a device is looked for: a NULL argument, n <= 0, a negative mesh index, unknown flag bits,
+ * neither or both of cage_positions and rig, what take_hip_rig_pose refuses of a bound rig's pose, a mesh named twice, a
+ * handle bound twice.  Right after it, against the scene: a mesh index out of range, a handle or rig on another device,
+ * a rig whose n_vertices is not the cage's, a refined vertex count that is not the mesh's (the message names the binding
+ * and both counts).  Then every refusal of take_hip_scene_update_meshes, in its words. */
+int take_hip_scene_subdivide_meshes(TakeScene *scene, const TakeSubdivBinding *bindings, int32_t n);
 /* A new environment map (EXTENSION; new symbols of ABI version 5; no struct changed; specification: DESIGN.md §4o).
  * The call replaces the image images[k] of the description the scene was created from, k being the shape_id of its
  * environment-map light (TakeLight kind 2), and — with scale3 — that light's intensity; scale3 == NULL keeps it.

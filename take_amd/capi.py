@@ -48,6 +48,8 @@ EXPORTS = [
     "take_hip_scene_set_materials", "take_hip_scene_set_light_intensities", "take_hip_scene_set_light_intensities_device",
     "take_hip_debug_shading_tables_info", "take_hip_debug_shading_tables",
     "take_hip_rig_create", "take_hip_rig_destroy", "take_hip_rig_info", "take_hip_rig_pose_device", "take_hip_rig_pose", "take_hip_scene_pose_meshes",
+    "take_hip_subdiv_counts", "take_hip_subdiv_topology", "take_hip_subdiv_create", "take_hip_subdiv_destroy", "take_hip_subdiv_info",
+    "take_hip_subdiv_refine_device", "take_hip_subdiv_refine", "take_hip_scene_subdivide_meshes",
 ]
 
 
@@ -95,7 +97,7 @@ def lib():
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.take_hip_scene_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.take_hip_debug_env.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
-        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.SHUTTER_MESHES_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()) + list(D.RIG_PROTOTYPES.items()):
+        for name, argtypes in list(D.SCENE_UPDATE_PROTOTYPES.items()) + list(D.FEATURE_PROTOTYPES.items()) + list(D.DEBUG_TREE_PROTOTYPES.items()) + list(D.DENOISE_PROTOTYPES.items()) + list(D.ADAPTIVE_PROTOTYPES.items()) + list(D.DENOISE_VARIANCE_PROTOTYPES.items()) + list(D.TEMPORAL_PROTOTYPES.items()) + list(D.TRACKING_PROTOTYPES.items()) + list(D.DISPLAY_PROTOTYPES.items()) + list(D.LENS_PROTOTYPES.items()) + list(D.SHUTTER_PROTOTYPES.items()) + list(D.SHUTTER_MESHES_PROTOTYPES.items()) + list(D.BLOOM_PROTOTYPES.items()) + list(D.RAYS_PROTOTYPES.items()) + list(D.ENVMAP_PROTOTYPES.items()) + list(D.SHADING_UPDATE_PROTOTYPES.items()) + list(D.RIG_PROTOTYPES.items()) + list(D.SUBDIV_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.take_hip_image_workspace_destroy.restype = None
         L.take_hip_pack_exr_scanlines.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -786,6 +788,134 @@ class Rig:
             pass
 
 
+def _subdiv_desc(indices, n_vertices, levels, uvs, keep):
+    d = D.TakeSubdivDesc()
+    idx = np.ascontiguousarray(indices, np.int32)
+    if idx.ndim != 2 or idx.shape[1] != 3:
+        raise ValueError(f"indices must have shape ('n', 3), not {idx.shape}")
+    keep.append(idx)
+    d.n_vertices, d.n_faces, d.indices, d.levels, d.flags = int(n_vertices), idx.shape[0], idx.ctypes.data, int(levels), 0
+    if uvs is not None:
+        uv = np.ascontiguousarray(uvs, np.float64)
+        if uv.shape != (int(n_vertices), 2):
+            raise ValueError(f"uvs must have shape ({int(n_vertices)}, 2), not {uv.shape}")
+        keep.append(uv)
+        d.uvs = uv.ctypes.data
+    return d
+
+
+def subdiv_counts(indices, n_vertices, levels):
+    """(refined vertices, refined faces) of a cage under `levels` levels of Loop subdivision (take_hip_subdiv_counts);
+    needs no GPU"""
+    keep = []
+    d = _subdiv_desc(indices, n_vertices, levels, None, keep)
+    nv, nf = C.c_int64(), C.c_int64()
+    _check(lib().take_hip_subdiv_counts(C.byref(d), C.byref(nv), C.byref(nf)))
+    return nv.value, nf.value
+
+
+def subdiv_topology(indices, n_vertices, levels, uvs=None):
+    """the refined faces (n, 3) int32 and — for a cage with uvs — the refined uvs (n, 2), else None
+    (take_hip_subdiv_topology); needs no GPU"""
+    keep = []
+    d = _subdiv_desc(indices, n_vertices, levels, uvs, keep)
+    nv, nf = C.c_int64(), C.c_int64()
+    _check(lib().take_hip_subdiv_counts(C.byref(d), C.byref(nv), C.byref(nf)))
+    idx = np.zeros((nf.value, 3), np.int32)
+    uv = np.zeros((nv.value, 2), np.float64) if uvs is not None else None
+    _check(lib().take_hip_subdiv_topology(C.byref(d), idx.ctypes.data, None if uv is None else uv.ctypes.data))
+    return idx, uv
+
+
+class Subdiv:
+    """Loop subdivision of one triangle cage on the device (take_hip_subdiv_create; include/take_hip.h has the scheme):
+    made once from the cage's topology — indices (n_faces, 3), the vertex count, optional uvs (n_vertices, 2), 1..6
+    levels —, it keeps the stencil tables in device memory; refine(), refine_device() and Scene.subdivide_meshes() turn
+    cage positions into refined positions and vertex normals there.  Bound to the device current at its creation; not
+    thread-safe."""
+
+    def __init__(self, indices, n_vertices, levels, uvs=None):
+        self._h = C.c_void_p()
+        self._keep = []
+        self._desc = _subdiv_desc(indices, n_vertices, levels, uvs, self._keep)
+        self._has_uvs = uvs is not None
+        _check(lib().take_hip_subdiv_create(C.byref(self._desc), C.byref(self._h)))
+        info = self.info()
+        self.cage_vertices, self.n_vertices, self.n_faces, self.levels = info["cage_vertices"], info["n_vertices"], info["n_faces"], info["levels"]
+
+    def info(self):
+        """-> {"cage_vertices", "n_vertices", "n_faces", "levels", "device_bytes"} (take_hip_subdiv_info)"""
+        cv, nv, nf, bytes_ = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        lv = C.c_int32()
+        _check(lib().take_hip_subdiv_info(self._h, C.byref(cv), C.byref(nv), C.byref(nf), C.byref(lv), C.byref(bytes_)))
+        return {"cage_vertices": cv.value, "n_vertices": nv.value, "n_faces": nf.value, "levels": lv.value, "device_bytes": bytes_.value}
+
+    def topology(self):
+        """-> (refined indices (n_faces, 3) int32, refined uvs (n_vertices, 2) or None).  Every call builds the refined
+        topology again on the host (take_hip_subdiv_topology over the kept description: one sort of the face sides per
+        level, millions of them at 6 levels) — call it once per cage, when the scene's mesh is made"""
+        idx = np.zeros((self.n_faces, 3), np.int32)
+        uv = np.zeros((self.n_vertices, 2), np.float64) if self._has_uvs else None
+        _check(lib().take_hip_subdiv_topology(C.byref(self._desc), idx.ctypes.data, None if uv is None else uv.ctypes.data))
+        return idx, uv
+
+    def _cage(self, cage, keep):
+        """-> (pointer, flags, on the device?) of cage positions: a numpy array, or a torch device tensor"""
+        device = _on_device(cage)
+        ptr = _rig_array(cage, np.float64, (self.cage_vertices, 3), "cage", device, keep)
+        if ptr is None:
+            raise ValueError("cage positions are required")
+        return ptr, (D.TAKE_SUBDIV_DEVICE_ARRAYS if device else 0), device
+
+    def refine_device(self, out_positions, out_normals=None, cage=None, stream=None):
+        """the cage refined into device memory (take_hip_subdiv_refine_device): out_positions, out_normals are
+        (n_vertices, 3) float64 torch device tensors or integer device pointers (out_normals None: no normals); runs on
+        `stream` (default: torch's current stream when the cage is a device tensor, else the default stream) and blocks
+        until done"""
+        keep = []
+        ptr, flags, device = self._cage(cage, keep)
+        if stream is None and device:
+            import torch
+
+            stream = torch.cuda.current_stream(keep[0].device).cuda_stream
+        _check(lib().take_hip_subdiv_refine_device(self._h, C.c_void_p(ptr), flags, C.c_void_p(_pointer(out_positions)), C.c_void_p(_pointer(out_normals)),
+                                                   C.c_void_p(stream or 0)))
+
+    def refine(self, cage, normals=True):
+        """-> (positions, normals), or positions alone with normals=False: (n_vertices, 3) numpy arrays.  A numpy cage
+        takes take_hip_subdiv_refine; a torch device tensor is refined on torch's current stream and downloaded"""
+        if _on_device(cage):
+            import torch
+
+            out_p = torch.empty((self.n_vertices, 3), dtype=torch.float64, device=cage.device)
+            out_n = torch.empty((self.n_vertices, 3), dtype=torch.float64, device=cage.device) if normals else None
+            self.refine_device(out_p, out_n, cage)
+            return (out_p.cpu().numpy(), out_n.cpu().numpy()) if normals else out_p.cpu().numpy()
+        keep = []
+        ptr, _, _ = self._cage(cage, keep)
+        pos = np.zeros((self.n_vertices, 3), np.float64)
+        nrm = np.zeros((self.n_vertices, 3), np.float64) if normals else None
+        _check(lib().take_hip_subdiv_refine(self._h, C.c_void_p(ptr), pos.ctypes.data, None if nrm is None else nrm.ctypes.data))
+        return (pos, nrm) if normals else pos
+
+    def close(self):
+        if self._h:
+            lib().take_hip_subdiv_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (interpreter shutdown: the library may be gone)
+            pass
+
+
 DEBUG_TABLES = {"material": (0, 27, 14), "light": (1, 30, 9), "texture": (2, 6, 3), "to_world": (3, 6, 3),
                 "hemicos": (4, 1, 4), "burley": (5, 30, 14)}
 
@@ -1289,6 +1419,39 @@ class Scene:
 
             (torch.cuda.current_stream(wait) if stream is None else torch.cuda.ExternalStream(int(stream), device=wait)).synchronize()
         _check(lib().take_hip_scene_pose_meshes(self.h, recs, len(bindings)))
+        del keep
+
+    def subdivide_meshes(self, bindings, stream=None):
+        """refine cages by Loop subdivision and update the resident scene in one step (take_hip_scene_subdivide_meshes):
+        `bindings` is [(mesh_id, subdiv, cage), ...] — a Subdiv whose refined vertex count is the mesh's, and cage
+        positions (cage_vertices, 3) as a numpy array or a torch device tensor — or [(mesh_id, subdiv, (rig,
+        joint_xforms, target_weights)), ...]: the cage is then the rig's pose.  Afterwards the scene equals the one
+        after update_meshes({mesh_id: subdiv.refine(cage)}); normals go to meshes that have vertex normals.  Device
+        tensors may have been written on `stream` (default: torch's current stream), which the call waits for first."""
+        bindings = list(bindings)
+        recs = (D.TakeSubdivBinding * max(len(bindings), 1))()
+        keep, wait = [], None
+        for k, (mesh, subdiv, cage) in enumerate(bindings):
+            if not isinstance(subdiv, Subdiv) or not subdiv._h:
+                raise ValueError("a binding's subdiv must be an open Subdiv")
+            recs[k].mesh, recs[k].subdiv = int(mesh), subdiv._h
+            if isinstance(cage, tuple):
+                rig, joint_xforms, target_weights = cage
+                if not isinstance(rig, Rig) or not rig._h:
+                    raise ValueError("a binding's rig must be an open Rig")
+                pose, device = rig._pose(joint_xforms, target_weights, keep)
+                recs[k].rig, recs[k].pose = rig._h, pose
+            elif cage is not None:
+                recs[k].cage_positions, recs[k].flags, device = subdiv._cage(cage, keep)
+            else:
+                device = False
+            if device and wait is None:
+                wait = keep[-1].device
+        if wait is not None:
+            import torch
+
+            (torch.cuda.current_stream(wait) if stream is None else torch.cuda.ExternalStream(int(stream), device=wait)).synchronize()
+        _check(lib().take_hip_scene_subdivide_meshes(self.h, recs, len(bindings)))
         del keep
 
     def set_mesh_vertices(self, updates, _entry="take_hip_scene_set_mesh_vertices"):

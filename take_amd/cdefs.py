@@ -137,6 +137,30 @@ RIG_PROTOTYPES = {
 }
 
 
+class TakeSubdivDesc(C.Structure):
+    """take_hip_subdiv_create / _counts / _topology: a cage's topology (host memory) and the level count"""
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("indices", C.c_void_p), ("uvs", C.c_void_p), ("levels", C.c_int32), ("flags", C.c_int32)]
+
+
+class TakeSubdivBinding(C.Structure):
+    """take_hip_scene_subdivide_meshes: one mesh of the scene, the handle that refines it, the cage — positions, or a
+    rig and its pose"""
+    _fields_ = [("mesh", C.c_int32), ("flags", C.c_int32), ("subdiv", C.c_void_p), ("cage_positions", C.c_void_p), ("rig", C.c_void_p), ("pose", TakeRigPose)]
+
+
+TAKE_SUBDIV_DEVICE_ARRAYS = 1
+SUBDIV_PROTOTYPES = {
+    "take_hip_subdiv_counts": [C.POINTER(TakeSubdivDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "take_hip_subdiv_topology": [C.POINTER(TakeSubdivDesc), C.c_void_p, C.c_void_p],
+    "take_hip_subdiv_create": [C.POINTER(TakeSubdivDesc), C.POINTER(C.c_void_p)],
+    "take_hip_subdiv_destroy": [C.c_void_p],
+    "take_hip_subdiv_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+    "take_hip_subdiv_refine_device": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_subdiv_refine": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_scene_subdivide_meshes": [C.c_void_p, C.POINTER(TakeSubdivBinding), C.c_int32],
+}
+
+
 class TakeRenderOpts(C.Structure):
     _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64), ("ray_epsilon", C.c_double),
                 ("strip_first", C.c_int32), ("strip_stride", C.c_int32), ("samples_per_batch", C.c_int32),

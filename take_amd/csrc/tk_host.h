@@ -175,6 +175,11 @@ inline int check_image(int32_t precision, int32_t width, int32_t height) {
     return TAKE_OK;
 }
 
+// A rig seen from another unit (tk_subdiv.hip poses the rig a cage is bound with; defined in tk_skin.hip): what a pose
+// call refuses without a device, `who` in front of the message; the rig's device and vertex count.
+int rig_check_pose(const TakeRig *rig, const TakeRigPose *pose, const std::string &who);
+void rig_shape(const TakeRig *rig, int *device, int64_t *n_vertices);
+
 inline int check_device() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)

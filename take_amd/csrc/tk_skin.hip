@@ -204,6 +204,12 @@ int pose_meshes(TakeScene *ts, const TakeRigBinding *bindings, int32_t n) {
 
 }  // namespace
 
+// what tk_subdiv.hip needs of a rig it is bound with (declared in tk_host.h)
+namespace tk_host {
+int rig_check_pose(const TakeRig *rig, const TakeRigPose *pose, const std::string &who) { return check_pose_args(rig, pose, who); }
+void rig_shape(const TakeRig *rig, int *device, int64_t *n_vertices) { *device = rig->device, *n_vertices = rig->n_vertices; }
+}  // namespace tk_host
+
 extern "C" {
 
 int take_hip_rig_create(const TakeRigDesc *desc, TakeRig **out) {

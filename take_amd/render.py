@@ -42,6 +42,59 @@ def render(params, seed=0, precision=D.TAKE_PRECISION_F32, ray_epsilon=0.0):
         scene.close()
 
 
+def with_refined_meshes(sd, refined, levels):
+    """the description with some meshes replaced by their Loop subdivision: `refined` is {mesh: (positions, indices,
+    normals or None, uvs or None)} after `levels` levels.  Face f of such a mesh became the faces 4^levels f ..
+    4^levels (f + 1) - 1, so every triangle shape on it becomes that many shapes in its place, and an area light on it
+    one light per new shape in the light's place; everything else keeps its order."""
+    import copy
+    import dataclasses
+
+    out = copy.copy(sd)
+    out.meshes = list(sd.meshes)
+    for m, (pos, idx, nrm, uv) in refined.items():
+        out.meshes[m] = dataclasses.replace(sd.meshes[m], positions=np.ascontiguousarray(pos, np.float64), indices=np.ascontiguousarray(idx, np.int32),
+                                            normals=nrm if sd.meshes[m].normals is not None else None, uvs=uv)
+    k = 4 ** int(levels)
+    split = (sd.shape_kind == 1) & np.isin(sd.shape_ref, list(refined))
+    rep = np.where(split, k, 1)
+    first = np.concatenate([[0], np.cumsum(rep)])[:-1]  # where an old shape's (first) new shape is
+    within = np.arange(int(rep.sum())) - np.repeat(first, rep)
+    out.shape_kind, out.shape_ref = np.repeat(sd.shape_kind, rep).astype(np.int32), np.repeat(sd.shape_ref, rep).astype(np.int32)
+    out.shape_face = (np.repeat(np.where(split, sd.shape_face.astype(np.int64) * k, sd.shape_face), rep) + within).astype(np.int32)
+    out.shape_area_light = np.full(int(rep.sum()), -1, np.int32)
+    out.lights = []
+    for light in sd.lights:
+        if light.kind != 1:  # (a point light, an environment map: no shape)
+            out.lights.append(light)
+            continue
+        for j in range(int(rep[light.shape_id])):
+            out.shape_area_light[first[light.shape_id] + j] = len(out.lights)
+            out.lights.append(dataclasses.replace(light, shape_id=int(first[light.shape_id] + j)))
+    return out
+
+
+def subdivide_scene(sd, levels, log=None):
+    """every triangle mesh of the description refined `levels` levels on the device (capi.Subdiv): positions, indices and
+    uvs, and vertex normals where the mesh had them.  A mesh the scheme refuses is named through `log` and left as it is."""
+    from .capi import Subdiv, TakeError
+
+    refined = {}
+    for m, mesh in enumerate(sd.meshes):
+        try:
+            with Subdiv(mesh.indices, mesh.positions.shape[0], levels, uvs=mesh.uvs) as sub:
+                idx, uv = sub.topology()
+                pos, nrm = sub.refine(mesh.positions)
+        except TakeError as e:
+            if e.code != D.TAKE_E_INVALID:
+                raise
+            if log:
+                log(f"-subdivide: mesh {m} is left as loaded: {e}")
+            continue
+        refined[m] = (pos, idx, nrm, uv)
+    return with_refined_meshes(sd, refined, levels)
+
+
 def imwrite(path, img):
     """the reference's imwrite (src/image.cpp:135-177): `.exr` (half, as tinyexr writes it — take_amd/exr.py) or `.pfm`"""
     if str(path).endswith(".exr"):
@@ -191,7 +244,10 @@ def main(argv=None):
     it.  Moving placements need the API.  -envmap (an extension): the scene's environment map is replaced by FILE (.exr or
     .npy, (h, w, 3), row 0 = zenith) right after the scene is created (Scene.set_envmap: its tables are built on the device),
     and the light's intensity by -envscale if given; the scene must have an environment-map light; every file is then
-    of the scene under the new map."""
+    of the scene under the new map.  -subdivide L (an extension): every triangle mesh of the scene is refined by L levels
+    of Loop subdivision on the device (subdivide_scene) before the scene is created, vertex normals replaced by the
+    refined surface's where the mesh had them; a mesh the scheme refuses (an edge of three faces, a bow-tie, ...) is
+    named on stderr and left as loaded; every file is then of the refined scene."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -230,6 +286,16 @@ def main(argv=None):
     lens = parse_lens(params)
     shutter = parse_shutter(params)
     envmap = parse_envmap(params)
+    subdivide = 0
+    if "-subdivide" in params:
+        i = params.index("-subdivide")
+        try:
+            subdivide = int(params[i + 1])
+        except (IndexError, ValueError):
+            raise SystemExit("-subdivide L: L is the number of levels, 1..6")
+        del params[i:i + 2]
+        if not 1 <= subdivide <= 6:
+            raise SystemExit("-subdivide L: L is the number of levels, 1..6")
     features, denoise = "-features" in params, "-denoise" in params
     params = [p for p in params if p not in ("-features", "-denoise")]
     if not params:
@@ -246,6 +312,8 @@ def main(argv=None):
 
     filename, max_depth = parse_params(params)
     sd = load_tkscene(filename)
+    if subdivide:
+        sd = subdivide_scene(sd, subdivide, log=lambda line: print(line, file=sys.stderr))
     scene = Scene(sd)
     try:
         if envmap is not None:  # before everything else: all the files below are of the scene under the new map
