@@ -45,6 +45,22 @@ class TakePlyLayout(C.Structure):
                 ("position_is_f64", C.c_int32), ("index_bytes", C.c_int32), ("header_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
+# mesh ingest on the device, and the normals of host arrays (include/take_hip.h): name -> argument types
+MESH_PROTOTYPES = {
+    "take_hip_ply_layout": [C.c_void_p, C.c_size_t, C.POINTER(TakePlyLayout)],
+    "take_hip_mesh_from_ply": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_from_ply_file": [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_from_serialized": [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_from_serialized_file": [C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_from_obj": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_from_obj_file": [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TakeMesh)],
+    "take_hip_mesh_download": [C.POINTER(TakeMesh), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_mesh_release": [C.POINTER(TakeMesh)],
+    "take_hip_mesh_compute_normals": [C.POINTER(TakeMesh)],
+    "take_hip_compute_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
+}
+
+
 class TakeSphere(C.Structure):
     _fields_ = [("center", c_double3), ("radius", C.c_double), ("material_id", C.c_int32), ("reserved", C.c_int32)]
 
@@ -486,6 +502,45 @@ class TakeCounters(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+# the library itself, scenes, renders, traces, scene groups and EXR egress (include/take_hip.h): name -> argument types
+SCENE_PROTOTYPES = {
+    "take_hip_last_error": [],
+    "take_hip_abi_version": [],
+    "take_hip_device_count": [],
+    "take_hip_scene_create": [C.POINTER(TakeSceneDesc), C.POINTER(TakeBuildOpts), C.POINTER(C.c_void_p)],
+    "take_hip_scene_destroy": [C.c_void_p],
+    "take_hip_render": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_void_p],
+    "take_hip_render_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_void_p, C.c_void_p],
+    "take_hip_render_accumulate": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_int32, C.c_void_p, C.c_void_p],
+    "take_hip_accumulated_samples": [C.c_void_p],
+    "take_hip_render_rows": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
+    "take_hip_trace_closest": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "take_hip_trace_any": [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)],
+    "take_hip_trace_closest_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
+    "take_hip_get_counters": [C.c_void_p, C.POINTER(TakeCounters)],
+    "take_hip_set_instrumentation": [C.c_void_p, C.c_int32],
+    "take_hip_scene_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+    "take_hip_scene_build_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+}
+GROUP_PROTOTYPES = {
+    "take_hip_group_create": [C.POINTER(TakeSceneDesc), C.POINTER(TakeBuildOpts), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)],
+    "take_hip_group_destroy": [C.c_void_p],
+    "take_hip_group_render": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_void_p],
+    "take_hip_group_render_device": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_void_p],
+    "take_hip_group_size": [C.c_void_p],
+    "take_hip_group_get_counters": [C.c_void_p, C.c_int32, C.POINTER(TakeCounters)],
+}
+EXR_PROTOTYPES = {
+    "take_hip_pack_exr_scanlines": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    "take_hip_render_exr_scanlines": [C.c_void_p, C.POINTER(TakeRenderOpts), C.c_void_p],
+}
+# the test hooks on the shading functions and on a scene's environment map
+DEBUG_PROTOTYPES = {
+    "take_hip_debug_table": [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32],
+    "take_hip_debug_env": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p],
+}
+
+
 class TakeDebugTreeInfo(C.Structure):
     _fields_ = [("node_format", C.c_int32), ("node_width", C.c_int32), ("two_level", C.c_int32), ("root_child", C.c_int32),
                 ("real_bytes", C.c_int32), ("node_bytes", C.c_int32), ("prim_bytes", C.c_int32), ("inst_bytes", C.c_int32),
@@ -593,3 +648,21 @@ def debug_tree_result(info, nodes, prims, inst):
             "root_child": int(info.root_child), "real_bytes": int(info.real_bytes), "n_nodes": int(info.n_nodes),
             "n_prims": int(info.n_prims), "n_instances": int(info.n_instances), "grid_lo": [float(x) for x in info.grid_lo],
             "grid_step": [float(x) for x in info.grid_step], "nodes": nodes, "prims": prims, "inst_trace": inst}
+
+
+def _one_table(tables):
+    """the union of the *_PROTOTYPES dicts; a name in two of them is a mistake"""
+    out = {}
+    for table in tables:
+        twice = sorted(set(out) & set(table))
+        if twice:
+            raise RuntimeError(f"{twice[0]} has a prototype in two tables")
+        out.update(table)
+    return out
+
+
+# every function include/take_hip.h declares: name -> argument types.  A new entry point goes into the *_PROTOTYPES dict
+# beside its structs (or a new dict of that name) and nowhere else; tests/test_capi_cpu.py holds the table against the header
+PROTOTYPES = _one_table([v for k, v in sorted(globals().items()) if k.endswith("_PROTOTYPES")])
+# the functions that do not return int
+RESTYPES = {"take_hip_last_error": C.c_char_p, "take_hip_accumulated_samples": C.c_int64, "take_hip_image_workspace_destroy": None}

@@ -36,6 +36,45 @@ def test_header_symbols_all_exported(lib):
     assert sorted(capi.EXPORTS) == names
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter declarations]) of every take_hip_* function the header declares"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t*]*?)\b(take_hip_[a-z_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def test_prototype_table_matches_the_header():
+    """cdefs.PROTOTYPES / RESTYPES against include/take_hip.h, function by function: the number of parameters, pointer or
+    scalar, a scalar's size and whether it is a double, and the return type"""
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "double": C.c_double}
+    returns = {"const char *": C.c_char_p, "int64_t": C.c_int64, "void": None}
+    declared = declared_prototypes()
+    assert sorted(declared) == declared_symbols() == sorted(D.PROTOTYPES)
+    for name, (ret, params) in declared.items():
+        argtypes = D.PROTOTYPES[name]
+        assert len(argtypes) == len(params), name
+        for k, (param, t) in enumerate(zip(params, argtypes)):
+            is_pointer = t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer)
+            assert is_pointer == ("*" in param), f"{name}: parameter {k} ({param})"
+            if not is_pointer:
+                want = scalars[param.replace("const ", "").split()[0]]
+                assert C.sizeof(t) == C.sizeof(want) and (t is C.c_double) == (want is C.c_double), f"{name}: parameter {k} ({param})"
+        if ret == "int":
+            assert name not in D.RESTYPES, name
+        else:
+            assert name in D.RESTYPES and D.RESTYPES[name] is returns[ret], name
+    assert set(D.RESTYPES) <= set(declared)
+    assert len(D.RESTYPES) == 3
+
+
+def test_a_name_in_two_prototype_tables_is_refused():
+    with pytest.raises(RuntimeError, match="take_hip_render has a prototype in two tables"):
+        D._one_table([D.SCENE_PROTOTYPES, {"take_hip_render": []}])
+
+
 def test_abi_version(lib):
     assert lib.take_hip_abi_version() == 5
 
