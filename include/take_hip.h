@@ -558,6 +558,91 @@ int take_hip_subdiv_refine(TakeSubdiv *subdiv, const double *cage_positions, dou
  * a rig whose n_vertices is not the cage's, a refined vertex count that is not the mesh's (the message names the binding
  * and both counts).  Then every refusal of take_hip_scene_update_meshes, in its words. */
 int take_hip_scene_subdivide_meshes(TakeScene *scene, const TakeSubdivBinding *bindings, int32_t n);
+/* Displacement mapping on the device (EXTENSION; new symbols of ABI version 5; no struct changed; specification:
+ * DESIGN.md §4t).  A TakeDisplace is the stage between "refine" and "update": made once from a mesh's TOPOLOGY — its
+ * faces and per-vertex uvs — and a one-channel height image, it keeps the image, every vertex's lookup coordinates and
+ * every vertex's row of faces in device memory; every frame base POSITIONS (and the unit normals to move along) go in and
+ * displaced positions and their vertex normals come out there.  Displacement is per vertex: a vertex shared by several
+ * faces moves once, so no mesh cracks.  The handle is scene-free, bound to the device current at its creation, and not
+ * thread-safe (it owns the buffers a call writes).
+ * In double, every operation in the order written:
+ *   sources    once, at creation: s = uscale * u + uoffset, t = vscale * v + voffset, a = modulo1(s), b = modulo1(t), with
+ *              the modulo of the texture lookup: in [0, 1) for every finite argument
+ *   height     bilinear with wrap, sample i at a = i / width: x = width * a; x1 = floor(x); fx = x - x1;
+ *              x2 = (x1 + 1 == width) ? 0 : x1 + 1; the same for y from b and height;
+ *              h = (q11 * (1.0 - fx) + q21 * fx) * (1.0 - fy) + (q12 * (1.0 - fx) + q22 * fx) * fy with q11 = texel(y1, x1),
+ *              q21 = texel(y1, x2), q12 = texel(y2, x1), q22 = texel(y2, x2); a float texel is widened, which is exact.
+ *              (NOT the seam arithmetic of the colour textures, which extrapolates in the wrap cell.)
+ *   position   d = scale * h + bias; p' = p + d * n
+ *   direction  n as given, or — left out — the vertex normals of the base positions, by the rule of the last line
+ *   normals    of the displaced positions: N_f = cross(p1 - p0, p2 - p0); a vertex's normal is the sum of N_f over its
+ *              faces in ascending face order, divided by its length when that is positive and finite. */
+typedef struct TakeDisplace TakeDisplace;
+#define TAKE_DISPLACE_DEVICE_ARRAYS 1 /* texels (a description), positions and normals (a call, a binding) are device memory */
+typedef struct TakeDisplaceDesc {
+    int64_t n_vertices, n_faces; /* of the mesh; > 0 */
+    const int32_t *indices;      /* n_faces x 3; host memory */
+    const double *uvs;           /* n_vertices x 2; host memory; required */
+    int32_t width, height;       /* of the height image; > 0, width * height <= INT32_MAX */
+    const void *texels;          /* height * width values, row-major, ONE channel */
+    int32_t real;                /* TAKE_PRECISION_F32: float texels, TAKE_PRECISION_F64: double texels */
+    int32_t flags;               /* 0, or TAKE_DISPLACE_DEVICE_ARRAYS: texels is device memory */
+    double uscale, vscale, uoffset, voffset; /* the lookup, as TakeTexture's */
+} TakeDisplaceDesc;
+typedef struct TakeDisplaceBinding {
+    int32_t mesh;                 /* index into the TakeSceneDesc.meshes the scene was created from */
+    int32_t flags;                /* 0, or TAKE_DISPLACE_DEVICE_ARRAYS: positions and normals, or cage_positions */
+    TakeDisplace *displace;
+    double scale, bias;
+    const double *positions;      /* the base surface as arrays: n_vertices x 3, or NULL when `subdiv` is given */
+    const double *normals;        /* n_vertices x 3 unit normals, or NULL = the handle's own; NULL with `subdiv` */
+    TakeSubdiv *subdiv;           /* NULL, or the base surface is this handle's refined cage, moved along its normals */
+    const double *cage_positions; /* with `subdiv`: cage vertices x 3, or NULL when `rig` is given */
+    TakeRig *rig;                 /* with `subdiv`: NULL, or the cage comes from this rig under `pose` */
+    TakeRigPose pose;
+} TakeDisplaceBinding;
+/* The image is copied to the device in the width it came in, the rows of faces and the lookup coordinates are built on
+ * the host and uploaded, and everything a call needs is allocated: the staged base arrays, the face normals, the
+ * handle's own outputs.  No later call allocates for the displacement.
+ * TAKE_E_INVALID before a device is looked for, the message naming the face or vertex: a NULL argument, uvs == NULL,
+ * counts <= 0, an index out of range, width or height <= 0 or width * height beyond INT32_MAX, `real` neither F32 nor
+ * F64, unknown flag bits, a lookup parameter that is not finite, a vertex whose s or t is not finite.  TAKE_E_INVALID
+ * with a message that starts with "unsupported": counts at which 3 * n_faces or n_vertices passes INT32_MAX.
+ * TAKE_E_NOMEM: the device has no room. */
+int take_hip_displace_create(const TakeDisplaceDesc *desc, TakeDisplace **out);
+int take_hip_displace_destroy(TakeDisplace *displace);
+/* what the handle holds; device_bytes: everything it has allocated, which no call changes.  Any output may be NULL. */
+int take_hip_displace_info(const TakeDisplace *displace, int64_t *n_vertices, int64_t *n_faces, int32_t *width, int32_t *height, int64_t *device_bytes);
+/* The base surface displaced into device memory: n_vertices x 3 doubles each; d_normals_out NULL = not wanted.  positions
+ * and normals are host memory, or device memory under TAKE_DISPLACE_DEVICE_ARRAYS; normals NULL: the direction is the
+ * handle's own vertex normals of `positions`.  Runs on `stream` (hipStream_t, NULL = the default stream), after whatever
+ * that stream still has to write into device arrays, and returns after it has completed.  TAKE_E_INVALID before a device
+ * is looked for: a NULL argument, unknown flag bits, a scale or bias that is not finite, an output that IS an input
+ * (d_positions_out or d_normals_out equal to positions or normals: the kernels read and write through pointers they
+ * take as distinct, so the outputs must not overlap the inputs or each other at all; displace into a second array).  A
+ * base position that is not finite is displaced as it is: the mesh update's own finiteness check catches it. */
+int take_hip_displace_apply_device(TakeDisplace *displace, const double *positions, const double *normals /* NULL = own */, int32_t flags, double scale, double bias,
+                                   double *d_positions_out, double *d_normals_out /* NULL = not wanted */, void *stream);
+/* the same from host arrays into host arrays (the handle's own buffers, then a download); normals_out NULL = not wanted */
+int take_hip_displace_apply(TakeDisplace *displace, const double *positions, const double *normals, double scale, double bias, double *positions_out, double *normals_out);
+/* Displace and update in one step.  Every binding names its base surface in exactly one of two ways: `positions` with
+ * optional `normals` — host arrays, or device arrays under TAKE_DISPLACE_DEVICE_ARRAYS —, or `subdiv` with exactly one of
+ * cage_positions and rig: the cage is then refined into the subdivision handle's own buffers, with normals, exactly as
+ * take_hip_scene_subdivide_meshes refines it.  The surface is displaced into the displacement handle's own buffers, then
+ * the scene takes exactly the path of take_hip_scene_update_meshes with TAKE_MESH_DEVICE_ARRAYS over them, with
+ * everything that call carries: both kinds of scene, every precision, the finiteness refusal, frame marks and vertex
+ * tracking, the end of a progressive sequence, and a failed call leaving the scene as it was (the kernels write
+ * handle-owned memory only, before anything is staged).  Normals are passed on only when the mesh has vertex normals.
+ * TAKE_E_INVALID before a device is looked for: a NULL argument, n <= 0, a negative mesh index, unknown flag bits, a scale
+ * or bias that is not finite, neither or both of positions and subdiv, normals given with subdiv, neither or both of
+ * cage_positions and rig under subdiv (either of them without it), what take_hip_rig_pose refuses of a bound rig's pose, a
+ * mesh named twice, a displacement or subdivision handle bound twice.  Right after it, against the scene: a mesh index
+ * out of range, a handle or rig on another device, a rig whose n_vertices is not the cage's, a refined count, a
+ * displacement count and a mesh count that disagree (the message names the binding and the counts).  Then every refusal
+ * of take_hip_scene_update_meshes, in its words.  The vertex counts are all that is compared: that the handle was made
+ * from the FACES of that mesh is the caller's responsibility (a scene keeps its meshes' vertex counts, not their
+ * topology) — a handle made from other faces over as many vertices gives the normals of that other mesh. */
+int take_hip_scene_displace_meshes(TakeScene *scene, const TakeDisplaceBinding *bindings, int32_t n);
 /* A new environment map (EXTENSION; new symbols of ABI version 5; no struct changed; specification: DESIGN.md §4o).
  * The call replaces the image images[k] of the description the scene was created from, k being the shape_id of its
  * environment-map light (TakeLight kind 2), and — with scale3 — that light's intensity; scale3 == NULL keeps it.

@@ -3,7 +3,7 @@
   capi    ctypes binding of the C ABI (include/take_hip.h, take_amd/libtake_hip.so built from csrc/): Scene, SceneGroup,
           and every name of the modules below, which is where callers import the binding from
   image   the binding's scene-free image-space calls (denoisers, temporal accumulation, display transform, bloom)
-  meshes  the binding's DeviceMesh, Rig, Subdiv and the calls on bare meshes
+  meshes  the binding's DeviceMesh, Rig, Subdiv, Displace and the calls on bare meshes
   _lib    loads the library and gives every entry point its prototype;  _marshal: arrays, streams and handles
   cdefs   ctypes mirror of the header's structs and constants, and PROTOTYPES: every entry point's argument types
   scene   SceneData: a flattened reference `Scene` (+ .tkscene files written by take_amd/host/take_flatten.hpp)

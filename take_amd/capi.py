@@ -1,8 +1,8 @@
 """ctypes binding of libtake_hip.so (include/take_hip.h).
 
 The library is the product; this package only marshals.  This module holds the resident scene and the scene group, and
-hands on everything else the binding has: loading and errors (_lib), the image-space calls (image), meshes, rigs and
-subdivision (meshes).  What the wrappers share — arrays to pointers, streams, handle lifetime — is in _marshal.
+hands on everything else the binding has: loading and errors (_lib), the image-space calls (image), meshes, rigs,
+subdivision and displacement (meshes).  What the wrappers share — arrays to pointers, streams, handle lifetime — is in _marshal.
 """
 import ctypes as C
 
@@ -15,7 +15,7 @@ from .image import (STATS_PLANES, TEMPORAL_PLANES, ImageWorkspace, _adaptive_opt
                     auto_exposure, bloom_layer, bloom_layer_device, denoise, denoise_device, denoise_variance, denoise_variance_device,
                     luminance_histogram, luminance_histogram_device, temporal_accumulate, temporal_accumulate_device, tonemap, tonemap_bloom,
                     tonemap_bloom_device, tonemap_device)
-from .meshes import (DeviceMesh, Rig, Subdiv, _shutter, compute_normals, ply_layout, shutter_plan, shutter_vertices, subdiv_counts,  # noqa: F401
+from .meshes import (DeviceMesh, Displace, Rig, Subdiv, _shutter, compute_normals, ply_layout, shutter_plan, shutter_vertices, subdiv_counts,  # noqa: F401
                      subdiv_topology)
 
 DEBUG_TABLES = {"material": (0, 27, 14), "light": (1, 30, 9), "texture": (2, 6, 3), "to_world": (3, 6, 3),
@@ -79,6 +79,26 @@ def _subdiv_binding(rec, binding, keep):
     if cage is None:
         return False
     rec.cage_positions, rec.flags, device = subdiv._cage(cage, keep)
+    return device
+
+
+def _displace_binding(rec, binding, keep):
+    mesh, displace, base = binding[:3]
+    rec.mesh, rec.displace = int(mesh), M.handle_of(displace, Displace, "a binding's displace")
+    rec.scale, rec.bias = (float(x) for x in (tuple(binding[3:]) + (1.0, 0.0)[len(binding) - 3:]))
+    if isinstance(base, tuple) and len(base) == 2 and isinstance(base[0], Subdiv):
+        subdiv, cage = base
+        rec.subdiv = M.handle_of(subdiv, Subdiv, "a binding's subdiv")
+        if isinstance(cage, tuple):
+            return _rig_pose(rec, *cage, keep)
+        if cage is None:
+            return False
+        rec.cage_positions, rec.flags, device = subdiv._cage(cage, keep)
+        return device
+    if base is None:
+        return False
+    positions, normals = base if isinstance(base, tuple) else (base, None)
+    rec.positions, rec.normals, rec.flags, device = displace._base(positions, normals, keep)
     return device
 
 
@@ -484,7 +504,7 @@ class Scene(M.Handle):
         self.set_mesh_vertices(updates, _entry="take_hip_scene_update_meshes")
 
     def _bind(self, entry, record, fill, bindings, stream):
-        """what pose_meshes and subdivide_meshes share: one `record` per binding, filled by fill(record, binding, keep)
+        """what pose_meshes, subdivide_meshes and displace_meshes share: one `record` per binding, filled by fill(record, binding, keep)
         -> whether the binding reads device tensors; those are waited for on `stream`, then the call is made"""
         bindings = list(bindings)
         recs = (record * max(len(bindings), 1))()
@@ -513,6 +533,17 @@ class Scene(M.Handle):
         after update_meshes({mesh_id: subdiv.refine(cage)}); normals go to meshes that have vertex normals.  Device
         tensors may have been written on `stream` (default: torch's current stream), which the call waits for first."""
         self._bind("take_hip_scene_subdivide_meshes", D.TakeSubdivBinding, _subdiv_binding, bindings, stream)
+
+    def displace_meshes(self, bindings, stream=None):
+        """displace surfaces by height maps and update the resident scene in one step (take_hip_scene_displace_meshes):
+        `bindings` is [(mesh_id, displace, base, scale, bias), ...] (scale 1, bias 0 when left out) — a Displace of the
+        mesh's vertex count, and the base surface: positions (n_vertices, 3), or (positions, normals) — numpy arrays or
+        torch device tensors; normals None: the handle's own —, or (subdiv, cage) with cage as subdivide_meshes takes it
+        (positions, or (rig, joint_xforms, target_weights)): the cage is refined first and moved along the refined
+        normals.  Afterwards the scene equals the one after update_meshes({mesh_id: displace.apply(...)}); normals go to
+        meshes that have vertex normals.  Device tensors may have been written on `stream` (default: torch's current
+        stream), which the call waits for first."""
+        self._bind("take_hip_scene_displace_meshes", D.TakeDisplaceBinding, _displace_binding, bindings, stream)
 
     def set_mesh_vertices(self, updates, _entry="take_hip_scene_set_mesh_vertices"):
         """new vertices for meshes of a scene without placements (take_hip_scene_set_mesh_vertices): `updates` is

@@ -177,6 +177,32 @@ SUBDIV_PROTOTYPES = {
 }
 
 
+class TakeDisplaceDesc(C.Structure):
+    """take_hip_displace_create: a mesh's topology and uvs (host memory), a one-channel height image (host memory, or
+    device memory under TAKE_DISPLACE_DEVICE_ARRAYS) and the lookup"""
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("indices", C.c_void_p), ("uvs", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("texels", C.c_void_p), ("real", C.c_int32), ("flags", C.c_int32), ("uscale", C.c_double), ("vscale", C.c_double), ("uoffset", C.c_double),
+                ("voffset", C.c_double)]
+
+
+class TakeDisplaceBinding(C.Structure):
+    """take_hip_scene_displace_meshes: one mesh of the scene, the handle that displaces it, the amplitude, the base
+    surface — positions and optional normals, or a subdivision handle with its cage (positions, or a rig and its pose)"""
+    _fields_ = [("mesh", C.c_int32), ("flags", C.c_int32), ("displace", C.c_void_p), ("scale", C.c_double), ("bias", C.c_double), ("positions", C.c_void_p),
+                ("normals", C.c_void_p), ("subdiv", C.c_void_p), ("cage_positions", C.c_void_p), ("rig", C.c_void_p), ("pose", TakeRigPose)]
+
+
+TAKE_DISPLACE_DEVICE_ARRAYS = 1
+DISPLACE_PROTOTYPES = {
+    "take_hip_displace_create": [C.POINTER(TakeDisplaceDesc), C.POINTER(C.c_void_p)],
+    "take_hip_displace_destroy": [C.c_void_p],
+    "take_hip_displace_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+    "take_hip_displace_apply_device": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "take_hip_displace_apply": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
+    "take_hip_scene_displace_meshes": [C.c_void_p, C.POINTER(TakeDisplaceBinding), C.c_int32],
+}
+
+
 class TakeRenderOpts(C.Structure):
     _fields_ = [("spp", C.c_int32), ("max_depth", C.c_int32), ("seed", C.c_uint64), ("ray_epsilon", C.c_double),
                 ("strip_first", C.c_int32), ("strip_stride", C.c_int32), ("samples_per_batch", C.c_int32),

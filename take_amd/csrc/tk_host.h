@@ -180,6 +180,19 @@ inline int check_image(int32_t precision, int32_t width, int32_t height) {
 int rig_check_pose(const TakeRig *rig, const TakeRigPose *pose, const std::string &who);
 void rig_shape(const TakeRig *rig, int *device, int64_t *n_vertices);
 
+// A subdivision handle seen from another unit (tk_displace.hip displaces the surface a cage is refined to; defined in
+// tk_subdiv.hip, the only unit that compiles the kernels of tk_subdiv.h): the handle's device and vertex counts;
+// one binding's cage — host or device positions, or a rig that is posed first — refined into the handle's own buffers on
+// the default stream, as take_hip_scene_subdivide_meshes refines it (out_n null: no normals) -> where the results are;
+// and the two normal launches over any mesh in device memory — face normals into face_n (n_faces x 3), then every
+// vertex's normal over its row of faces into out_n — on `stream`, without waiting; `between`, unless null, is recorded
+// between the two.
+void subdiv_shape(const TakeSubdiv *subdiv, int *device, int64_t *cage_vertices, int64_t *n_vertices);
+int subdiv_refine_own(TakeSubdiv *subdiv, const double *cage_positions, bool on_device, TakeRig *rig, const TakeRigPose *pose, bool normals, const double **d_positions,
+                      const double **d_normals);
+void subdiv_launch_normals(const int32_t *indices, const int32_t *face_start, const int32_t *faces, const double *positions, int64_t n_faces, int64_t n_vertices,
+                           double *face_n, double *out_n, hipStream_t stream, hipEvent_t between);
+
 inline int check_device() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)

@@ -130,11 +130,8 @@ int refine_on_stream(TakeSubdiv &s, const double *d_cage, double *out_p, double 
                            (const int32_t *)s.faces.p, (const int32_t *)s.indices.p, (const double *)out_p, s.n_vertices, out_n);
         tick();
     } else if (out_n) {
-        hipLaunchKernelGGL(subdiv::k_subdiv_face_normals, dim3((unsigned)subdiv::blocks_for(s.n_faces)), block, 0, stream, (const int32_t *)s.indices.p, (const double *)out_p,
-                           s.n_faces, s.face_n.p);
-        tick();
-        hipLaunchKernelGGL(subdiv::k_subdiv_vertex_normals, dim3((unsigned)subdiv::blocks_for(s.n_vertices)), block, 0, stream, (const int32_t *)s.face_start.p,
-                           (const int32_t *)s.faces.p, (const double *)s.face_n.p, s.n_vertices, out_n);
+        subdiv_launch_normals(s.indices.p, s.face_start.p, s.faces.p, out_p, s.n_faces, s.n_vertices, s.face_n.p, out_n, stream, clocked ? ev[mark] : nullptr);
+        mark++;
         tick();
     }
     HIP_TRY(hipGetLastError());
@@ -214,17 +211,37 @@ int subdivide_meshes(TakeScene *ts, const TakeSubdivBinding *bindings, int32_t n
     // scene is staged
     for (int32_t i = 0; i < n; i++) {
         const TakeSubdivBinding &b = bindings[i];
-        TakeSubdiv &s = *b.subdiv;
-        if (b.rig)  // (posed into the handle's staged cage: positions alone — the normals are the refined surface's)
-            if (int rc = take_hip_rig_pose_device(b.rig, &b.pose, s.cage.p, nullptr, nullptr)) return rc;
-        TAKE_ON_DEVICE(ts);
-        const bool on_device = b.rig || (b.flags & TAKE_SUBDIV_DEVICE_ARRAYS);
-        if (int rc = refine_from(s, b.rig ? s.cage.p : b.cage_positions, on_device, s.out_p.p, updates[i].normals ? s.out_n.p : nullptr, nullptr)) return rc;
+        const double *p = nullptr, *nrm = nullptr;
+        if (int rc = subdiv_refine_own(b.subdiv, b.cage_positions, (b.flags & TAKE_SUBDIV_DEVICE_ARRAYS) != 0, b.rig, &b.pose, updates[i].normals != nullptr, &p, &nrm)) return rc;
     }
     return take_hip_scene_update_meshes(ts, updates.data(), n);
 }
 
 }  // namespace
+
+// what tk_displace.hip calls of this unit (tk_host.h)
+void tk_host::subdiv_shape(const TakeSubdiv *subdiv, int *device, int64_t *cage_vertices, int64_t *n_vertices) {
+    *device = subdiv->device, *cage_vertices = subdiv->cage_vertices, *n_vertices = subdiv->n_vertices;
+}
+int tk_host::subdiv_refine_own(TakeSubdiv *subdiv, const double *cage_positions, bool on_device, TakeRig *rig, const TakeRigPose *pose, bool normals,
+                               const double **d_positions, const double **d_normals) {
+    TakeSubdiv &s = *subdiv;
+    if (rig)  // (posed into the handle's staged cage: positions alone — the normals are the refined surface's)
+        if (int rc = take_hip_rig_pose_device(rig, pose, s.cage.p, nullptr, nullptr)) return rc;
+    DeviceGuard guard(s.device);
+    if (!guard.ok) return fail(TAKE_E_DEVICE, "cannot make the subdivision handle's device current");
+    if (int rc = refine_from(s, rig ? s.cage.p : cage_positions, rig || on_device, s.out_p.p, normals ? s.out_n.p : nullptr, nullptr)) return rc;
+    *d_positions = s.out_p.p, *d_normals = normals ? s.out_n.p : nullptr;
+    return TAKE_OK;
+}
+void tk_host::subdiv_launch_normals(const int32_t *indices, const int32_t *face_start, const int32_t *faces, const double *positions, int64_t n_faces, int64_t n_vertices,
+                                    double *face_n, double *out_n, hipStream_t stream, hipEvent_t between) {
+    const dim3 block(subdiv::BLOCK);
+    hipLaunchKernelGGL(subdiv::k_subdiv_face_normals, dim3((unsigned)subdiv::blocks_for(n_faces)), block, 0, stream, indices, positions, n_faces, face_n);
+    if (between) (void)hipEventRecord(between, stream);
+    hipLaunchKernelGGL(subdiv::k_subdiv_vertex_normals, dim3((unsigned)subdiv::blocks_for(n_vertices)), block, 0, stream, face_start, faces, (const double *)face_n, n_vertices,
+                       out_n);
+}
 
 extern "C" {
 

@@ -1,5 +1,5 @@
 """Meshes on the device, apart from any scene (include/take_hip.h): decoding mesh files, vertex normals, rigs (skinning
-and morph targets), Loop subdivision, and the vertex lerp of the shutter."""
+and morph targets), Loop subdivision, displacement mapping, and the vertex lerp of the shutter."""
 import ctypes as C
 import os
 
@@ -328,3 +328,83 @@ class Subdiv(Handle):
         nrm = np.zeros((self.n_vertices, 3), np.float64) if normals else None
         _check(lib().take_hip_subdiv_refine(self._h, C.c_void_p(ptr), pos.ctypes.data, None if nrm is None else nrm.ctypes.data))
         return (pos, nrm) if normals else pos
+
+
+class Displace(Handle):
+    """Displacement mapping of one triangle mesh on the device (take_hip_displace_create; include/take_hip.h has the
+    arithmetic): made once from the mesh's topology — indices (n_faces, 3), the vertex count, uvs (n_vertices, 2) — and a
+    height image (height, width), float32 or float64, a numpy array or a torch device tensor, with the lookup uvxf =
+    (uscale, vscale, uoffset, voffset) of a texture; apply(), apply_device() and Scene.displace_meshes() move base
+    positions along unit normals by scale * height + bias and compute the normals of the result.  Bound to the device
+    current at its creation; not thread-safe."""
+    _destroy = "take_hip_displace_destroy"
+
+    def __init__(self, indices, n_vertices, uvs, image, uvxf=(1.0, 1.0, 0.0, 0.0), stream=None):
+        self._new()
+        keep = []
+        d = D.TakeDisplaceDesc()
+        d.indices = array(required(indices, "indices"), np.int32, (-1, 3), "indices", False, keep)
+        d.n_vertices, d.n_faces = int(n_vertices), keep[0].shape[0]
+        d.uvs = array(required(uvs, "uvs"), np.float64, (int(n_vertices), 2), "uvs", False, keep)
+        device = on_device(image)
+        d.texels = array(required(image, "image"), (np.float32, np.float64), (-1, -1), "image", device, keep)
+        texels = keep[-1]
+        d.height, d.width = int(texels.shape[0]), int(texels.shape[1])
+        d.real = D.TAKE_PRECISION_F64 if str(texels.dtype).endswith("float64") else D.TAKE_PRECISION_F32
+        d.flags = D.TAKE_DISPLACE_DEVICE_ARRAYS if device else 0
+        d.uscale, d.vscale, d.uoffset, d.voffset = (float(x) for x in uvxf)
+        wait_for(stream, texels.device if device else None)
+        _check(lib().take_hip_displace_create(C.byref(d), C.byref(self._h)))
+        info = self.info()
+        self.n_vertices, self.n_faces, self.width, self.height = info["n_vertices"], info["n_faces"], info["width"], info["height"]
+
+    @classmethod
+    def of_subdiv(cls, subdiv, image, uvxf=(1.0, 1.0, 0.0, 0.0), stream=None):
+        """the handle for the surface a Subdiv refines its cage to — a cage with uvs: indices and uvs are its topology()"""
+        indices, uvs = subdiv.topology()
+        return cls(indices, subdiv.n_vertices, required(uvs, "the cage's uvs"), image, uvxf, stream)
+
+    def info(self):
+        """-> {"n_vertices", "n_faces", "width", "height", "device_bytes"} (take_hip_displace_info)"""
+        nv, nf, bytes_ = C.c_int64(), C.c_int64(), C.c_int64()
+        w, h = C.c_int32(), C.c_int32()
+        _check(lib().take_hip_displace_info(self._h, C.byref(nv), C.byref(nf), C.byref(w), C.byref(h), C.byref(bytes_)))
+        return {"n_vertices": nv.value, "n_faces": nf.value, "width": w.value, "height": h.value, "device_bytes": bytes_.value}
+
+    def _base(self, positions, normals, keep):
+        """-> (positions pointer, normals pointer or None, flags, on the device?) of a base surface: numpy arrays, or
+        torch device tensors (both then)"""
+        device = on_device(positions) or on_device(normals)
+        p = array(required(positions, "positions"), np.float64, (self.n_vertices, 3), "positions", device, keep)
+        n = array(normals, np.float64, (self.n_vertices, 3), "normals", device, keep)
+        return p, n, (D.TAKE_DISPLACE_DEVICE_ARRAYS if device else 0), device
+
+    def apply_device(self, out_positions, out_normals=None, positions=None, normals=None, scale=1.0, bias=0.0, stream=None):
+        """the base surface displaced into device memory (take_hip_displace_apply_device): out_positions, out_normals are
+        (n_vertices, 3) float64 torch device tensors or integer device pointers (out_normals None: no normals); normals
+        None: the direction is the handle's own vertex normals of `positions`; an output must not be (or overlap) an
+        input: displacing in place is refused; runs on `stream` (default: torch's current
+        stream when the base is a device tensor, else the default stream) and blocks until done"""
+        keep = []
+        p, n, flags, device = self._base(positions, normals, keep)
+        if device:
+            stream = stream_of(stream, keep[0])
+        _check(lib().take_hip_displace_apply_device(self._h, C.c_void_p(p), C.c_void_p(n), flags, float(scale), float(bias), C.c_void_p(pointer(out_positions)),
+                                                    C.c_void_p(pointer(out_normals)), C.c_void_p(stream or 0)))
+
+    def apply(self, positions, normals=None, scale=1.0, bias=0.0, out_normals=True):
+        """-> (positions, normals), or positions alone with out_normals=False: (n_vertices, 3) numpy arrays.  numpy base
+        arrays take take_hip_displace_apply; torch device tensors are displaced on torch's current stream and downloaded"""
+        if on_device(positions):
+            import torch
+
+            out_p = torch.empty((self.n_vertices, 3), dtype=torch.float64, device=positions.device)
+            out_n = torch.empty((self.n_vertices, 3), dtype=torch.float64, device=positions.device) if out_normals else None
+            self.apply_device(out_p, out_n, positions, normals, scale, bias)
+            return (out_p.cpu().numpy(), out_n.cpu().numpy()) if out_normals else out_p.cpu().numpy()
+        keep = []
+        p, n, _, _ = self._base(positions, normals, keep)
+        pos = np.zeros((self.n_vertices, 3), np.float64)
+        nrm = np.zeros((self.n_vertices, 3), np.float64) if out_normals else None
+        _check(lib().take_hip_displace_apply(self._h, C.c_void_p(p), C.c_void_p(n), float(scale), float(bias), pos.ctypes.data, None if nrm is None else nrm.ctypes.data))
+        return (pos, nrm) if out_normals else pos

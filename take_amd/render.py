@@ -95,6 +95,63 @@ def subdivide_scene(sd, levels, log=None):
     return with_refined_meshes(sd, refined, levels)
 
 
+def displace_scene(sd, image, scale, bias=0.0, log=None):
+    """every triangle mesh of the description that has uvs displaced by the height image (h, w) on the device
+    (capi.Displace): positions move along the mesh's own vertex normals where it has them, otherwise along the handle's
+    own, and vertex normals are replaced by the displaced surface's where the mesh had them.  A mesh without uvs is named
+    through `log` and left as it is."""
+    import copy
+    import dataclasses
+
+    from .capi import Displace
+
+    out = copy.copy(sd)
+    out.meshes = list(sd.meshes)
+    for m, mesh in enumerate(sd.meshes):
+        if mesh.uvs is None:
+            if log:
+                log(f"-displace: mesh {m} is left as loaded: it has no uvs")
+            continue
+        with Displace(mesh.indices, mesh.positions.shape[0], mesh.uvs, image) as dis:
+            pos, nrm = dis.apply(mesh.positions, mesh.normals, scale, bias)
+        out.meshes[m] = dataclasses.replace(mesh, positions=pos, normals=nrm if mesh.normals is not None else None)
+    return out
+
+
+def parse_displace(params):
+    """`-displace FILE,SCALE[,BIAS]` taken out of `params` -> ((h, w) height image, scale, bias), or None without
+    -displace; FILE is read as -envmap reads its file (.exr or .npy), of which the first channel is the height"""
+    if "-displace" not in params:
+        return None
+    i = params.index("-displace")
+    if i + 1 >= len(params):
+        raise SystemExit("-displace needs a value")
+    value = params[i + 1]
+    del params[i:i + 2]
+    try:
+        parts = value.split(",")
+        if len(parts) not in (2, 3):
+            raise ValueError("a file, a scale and an optional bias")
+        path, scale, bias = parts[0], float(parts[1]), float(parts[2]) if len(parts) == 3 else 0.0
+        if path.endswith(".npy"):
+            img = np.load(path)
+        elif path.endswith(".exr"):
+            from .exr import read_exr
+
+            channels, _ = read_exr(path)
+            first = next((c for c in ("R", "Y") if c in channels), None) or sorted(channels)[0]
+            img = channels[first].astype(np.float32)
+        else:
+            raise ValueError(f"unsupported image format: {path}")
+        if img.ndim == 3:
+            img = img[:, :, 0]
+        if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{path}: the image must be a float32 or float64 array of shape (h, w) or (h, w, channels)")
+        return np.ascontiguousarray(img), scale, bias
+    except (ValueError, OSError, IndexError) as e:
+        raise SystemExit(f"-displace FILE,SCALE[,BIAS]: {e}")
+
+
 def imwrite(path, img):
     """the reference's imwrite (src/image.cpp:135-177): `.exr` (half, as tinyexr writes it — take_amd/exr.py) or `.pfm`"""
     if str(path).endswith(".exr"):
@@ -218,7 +275,8 @@ def parse_envmap(params):
 def main(argv=None):
     """`python -m take_amd.render scene.tkscene [-max_depth D] [-features] [-denoise] [-adaptive [threshold]]
     [-png [linear|reinhard|aces] [-bloom [INTENSITY]]] [-aperture R [-focus D | -focus_pixel X,Y]]
-    [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az] [-envmap FILE [-envscale R,G,B]]` — the reference's main.cpp:9-27:
+    [-shutter OPEN,CLOSE [-slices K] -from_camera fx,fy,fz,ax,ay,az] [-envmap FILE [-envscale R,G,B]] [-subdivide L]
+    [-displace FILE,SCALE[,BIAS]]` — the reference's main.cpp:9-27:
     render, then imwrite("image.exr") into the current directory.  -features (an extension): also the first-hit albedo
     and shading normal of the same camera rays (Scene.render_features), as albedo.exr and normal.exr — what a denoiser
     reads beside the image.  -denoise (an extension): also denoised.exr, the same render filtered on the device with
@@ -247,7 +305,11 @@ def main(argv=None):
     of the scene under the new map.  -subdivide L (an extension): every triangle mesh of the scene is refined by L levels
     of Loop subdivision on the device (subdivide_scene) before the scene is created, vertex normals replaced by the
     refined surface's where the mesh had them; a mesh the scheme refuses (an edge of three faces, a bow-tie, ...) is
-    named on stderr and left as loaded; every file is then of the refined scene."""
+    named on stderr and left as loaded; every file is then of the refined scene.  -displace FILE,SCALE[,BIAS] (an
+    extension): every triangle mesh with uvs is displaced by SCALE * height + BIAS along its vertex normals on the device
+    (displace_scene), after -subdivide and before the scene is created; FILE is read as -envmap's (.exr or .npy), its
+    first channel the height; vertex normals are replaced where the mesh had them; a mesh without uvs is named on stderr
+    and left as loaded."""
     import sys
 
     params = list(sys.argv[1:] if argv is None else argv)
@@ -286,6 +348,7 @@ def main(argv=None):
     lens = parse_lens(params)
     shutter = parse_shutter(params)
     envmap = parse_envmap(params)
+    displace = parse_displace(params)
     subdivide = 0
     if "-subdivide" in params:
         i = params.index("-subdivide")
@@ -314,6 +377,8 @@ def main(argv=None):
     sd = load_tkscene(filename)
     if subdivide:
         sd = subdivide_scene(sd, subdivide, log=lambda line: print(line, file=sys.stderr))
+    if displace is not None:
+        sd = displace_scene(sd, *displace, log=lambda line: print(line, file=sys.stderr))
     scene = Scene(sd)
     try:
         if envmap is not None:  # before everything else: all the files below are of the scene under the new map
